@@ -22,11 +22,15 @@ THIS build of the library (build tags compared).  `mfma` prices the MLP kernels 
 dense bf16 peak from their live HIP-event times.  The occupancy-grid refresh (H10, `update_extra_state()`) runs INSIDE
 the timed region at the trainer's cadence (every `update_extra_interval` = 16 steps, eager launches between replays)
 and is part of `value`; it writes a shadow copy of the occupancy state so that the analytic scene of the workload
-stays pinned (`refresh` on the line says so and carries the refresh-free rate of the same run).  A run shorter than
-100 steps times 5 regions of --steps steps each and reports the median region (`repeats`).  `trainer` is the product
-entry point -- `Trainer.train()` with the seeded synthetic guidance, captured step, refreshes included -- on the same
-configuration.  `f32` is the same step with the exact-f32 parity configuration.  `cpu_baseline` is the oracle
-(oracle/nerf_oracle.py, pure PyTorch fp32) doing the same step on the host cores: the only use of `oracle/` here.
+stays pinned (`refresh` on the line says so and carries the refresh-free rate of the same run).  The timed region is
+exactly --steps steps (`--repeats R`: R such regions, the median one reported).
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the outputs (--dump-outputs DIR) and
+the line.  `--full` adds the companions, each outside the timed region: `trainer` is the product entry point --
+`Trainer.train()` with the seeded synthetic guidance, captured step, refreshes included -- on the same configuration;
+`views8`, `layout_companion` and `f32` are the same step with 8 views per batch, the other table layout and the
+exact-f32 parity configuration; `cpu_baseline` is the oracle (oracle/nerf_oracle.py, pure PyTorch fp32) doing the
+same step on the host cores: the only use of `oracle/` here.
 """
 import argparse
 import json
@@ -71,9 +75,14 @@ def parse():
     ap.add_argument("--table", default="auto", choices=["auto", "f32", "bf16"],
                     help="dtype of the hash table the gather reads (auto: follows --precision, the SURVEY §8(b) dtype policy; "
                          "bf16 = half-size shadow refreshed by the fused Adam pass)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the untimed companions (trainer, views8, layout_companion, f32) and the "
+                         "cpu_baseline; a plain run does none of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline")
     ap.add_argument("--cpu-frames", type=int, default=5, help="timed CPU frames (~2 s each on 16 cores; + 1 warm-up)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed companions (f32 step, occupancy refresh)")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the untimed companions")
     ap.add_argument("--gather-variant", type=int, default=0)
     ap.add_argument("--gridtype", default="auto", choices=["auto", "hash", "tiled", "blocked"],
                     help="layout of the levels larger than their table: auto (default) = what TrainConfig picks -- `blocked` "
@@ -126,8 +135,8 @@ def parse():
     ap.add_argument("--refresh", type=int, default=1,
                     help="1: the occupancy refresh runs inside the timed region every update_extra_interval steps (shadow "
                          "state: the analytic scene stays pinned); 0: the refresh-free step only")
-    ap.add_argument("--repeats", type=int, default=0, help="timed regions of --steps steps each (0 = auto: 5 below 100 steps, else 1); the median region is reported")
-    ap.add_argument("--trainer-steps", type=int, default=200, help="steps of the `trainer` companion (0 = skip)")
+    ap.add_argument("--repeats", type=int, default=1, help="timed regions of --steps steps each; the median region is reported")
+    ap.add_argument("--trainer-steps", type=int, default=200, help="--full: steps of the `trainer` companion (0 = skip)")
     ap.add_argument("--shard-optimizer", type=int, default=0,
                     help="N > 1, bf16 on the wire, pipelined groups: row-sharded table optimiser -- reduce-scatter of the "
                          "gradient, the owning rank steps its 1/N of the rows, all-gather of the bf16 shadow")
@@ -355,6 +364,34 @@ def cpu_baseline(frames):
     return {"value": 1.0 / med, "unit": "latent-frames/sec", "cores": cores, "kind": "port",
             "sample": "%d timed frames (+1 warm-up) of the same 64x64x4 / 128^3 step, M=%d samples/frame, "
                       "oracle/nerf_oracle.py fp32 PyTorch, %d threads" % (len(times), M, cores)}
+
+
+DUMP_MAX_ELEMS = 1 << 20   # per array; a larger one (the hash table) is written as a fixed sample of its rows
+
+
+def dump_outputs(directory, out, net):
+    """--dump-outputs DIR: what the last timed step handed its caller, as DIR/<name>.npy -- the render outputs `image`,
+    `depth`, `weights_sum`, the `sigmas` of the M marched samples and the device `counter` (int32, written as float64),
+    and every parameter after the step's Adam update as `param.<name>`; float32 otherwise.  An array of more than
+    DUMP_MAX_ELEMS elements keeps the rows torch.randperm(rows, seed 0) picks first, in ascending order: the same rows
+    in every run.  The inputs are seeded (build()), so two builds run with the same arguments compare file for file."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    M = int(out["counter"][0].item())
+    arrays = {"image": out["image"], "depth": out["depth"], "weights_sum": out["weights_sum"],
+              "sigmas": out["sigmas"][:M], "counter": out["counter"]}
+    arrays.update(("param." + n, p) for n, p in net.named_parameters())
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            keep = max(1, DUMP_MAX_ELEMS // max(1, t[0].numel()))
+            rows = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = t[rows.to(t.device)]
+        a = t.cpu().float().numpy() if t.is_floating_point() else t.cpu().double().numpy()
+        np.save(os.path.join(directory, name + ".npy"), a)
+        total += a.nbytes
+    log("outputs of the last timed step: %d arrays, %.1f MB in %s" % (len(arrays), total / 2 ** 20, directory))
 
 
 def load_pmc(build_tag):
@@ -877,7 +914,7 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item()), host_enqueue, out, n_ref
 
-    repeats = args.repeats if args.repeats > 0 else (5 if args.steps < 100 else 1)
+    repeats = max(1, args.repeats)
     regions = [region(args.steps) for _ in range(repeats)]
     order = sorted(range(repeats), key=lambda k: regions[k][0])
     elapsed, host_enqueue, out, n_ref = regions[order[repeats // 2]]     # the median region
@@ -904,6 +941,8 @@ def main():
             raise SystemExit("bench: the replicas diverged (rank checksums differ)")
     if float((emb - emb0).abs().max()) == 0.0 and (args.lr is None or args.lr != 0.0):
         raise SystemExit("bench: the hash table did not change during the timed steps (optimiser not applied?)")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, regions[-1][2], net)   # (the last region ends with the last timed step)
 
     breakdown = None
     if args.breakdown and rank == 0:
@@ -1018,7 +1057,7 @@ def main():
             res["exchange_tuning"] = exchange_tuning
         if tuned:
             res["tuning_overrides"] = tuned
-        if not args.no_extras and not dist_on and args.gridtype in ("hash", "blocked") and kv == 1:
+        if args.full and not args.no_extras and not dist_on and args.gridtype in ("hash", "blocked") and kv == 1:
             if args.trainer_steps > 0:
                 # the product loop twice: on the bench's own view (same GPU work per step as the headline: what the loop
                 # itself costs) and on the training pose distribution (random radius / angles / field of view per step)
@@ -1029,7 +1068,7 @@ def main():
             res["layout_companion"] = companion_layout(dev, rank, args.precision,
                                                        "hash" if args.gridtype == "blocked" else "blocked")
             res["f32"] = companion_f32(dev, rank)
-        if not args.no_cpu_baseline and not dist_on:
+        if args.full and not args.no_cpu_baseline and not dist_on:
             res["cpu_baseline"] = cpu_baseline(args.cpu_frames)
         print(json.dumps(res), flush=True)
     if dist_on:

@@ -120,3 +120,27 @@ def test_bench_two_ranks_row_sharded_optimiser_and_two_views_each(built_lib):
     assert res["n_gpus"] == 2 and res["config"]["views_per_step"] == 4 and res["config"]["views_per_rank"] == 2
     assert "row-sharded table optimiser" in res["config"]["parallelism"]
     assert abs(res["value"] - 4e3 / res["ms_per_step"]) < 1e-6 * res["value"]
+
+
+def test_plain_run_times_exactly_its_steps_and_dumps_the_last_step(built_lib, tmp_path):
+    """`--gpus 1 --steps K --warmup W` alone: ONE timed region of exactly K steps, none of the `--full` companions, and
+    with --dump-outputs the last timed step's outputs as float32 / float64 .npy files (64 MB at most)."""
+    import numpy as np
+    d = tmp_path / "out"
+    rc, out, err = _bench(["--gpus", "1", "--steps", "12", "--warmup", "4", "--dump-outputs", str(d)])
+    assert rc == 0, err[-3000:]
+    lines = [l for l in out.splitlines() if l.strip()]
+    assert len(lines) == 1, out
+    res = json.loads(lines[0])
+    assert res["steps"] == 12 and res["repeats"] == 1 and len(res["region_ms_per_step"]) == 1
+    assert abs(res["value"] - 12 / (res["ms_per_step"] * 1e-3 * 12)) < 1e-6 * res["value"]
+    for k in ("trainer", "trainer_random_views", "views8", "layout_companion", "f32", "cpu_baseline"):
+        assert k not in res, k
+    files = {f.name: np.load(f) for f in d.iterdir()}
+    assert {"image.npy", "depth.npy", "weights_sum.npy", "sigmas.npy", "counter.npy", "param.encoder.embeddings.npy",
+            "param.w1.npy"} <= set(files), sorted(files)
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert files["image.npy"].shape == (1, 64 * 64, 4) and np.isfinite(files["image.npy"]).all()
+    M = int(files["counter.npy"][0])
+    assert M == res["config"]["samples_per_view"] and files["sigmas.npy"].shape == (M,)

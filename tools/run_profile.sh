@@ -9,7 +9,7 @@
 #   pmc        every counter group bench.py reports (tools/run_pmc_all.sh)  -> gpurun_out/<name>.json
 #   ab         per-kernel times for several library builds: extra args = lib1.so lib2.so ...
 #   bench      plain bench line                                             -> gpurun_out/<name>_bench.json
-#   evidence   -m gpu suite + default bench line + stats + timeline (a round's evidence run)
+#   evidence   -m gpu suite + --full bench line + stats + timeline (a round's evidence run)
 #
 # rocprofv3 is only ever given the program itself after `--` (python3 ...), and --pmc is never combined with anything
 # but --kernel-trace (see the pool's rules).  Every GPU step is bounded by `timeout -k 10`.
@@ -38,7 +38,7 @@ timeline() {
 
 trainer() {
   rm -rf $OUT/${NAME}_tr
-  timeout -k 10 400 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT/${NAME}_tr -- python3 $R/bench.py --steps 20 --warmup 5 --repeats 1 --no-cpu-baseline --trainer-steps 96 "$@" > $OUT/${NAME}_tr.log 2>&1
+  timeout -k 10 400 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT/${NAME}_tr -- python3 $R/bench.py --full --steps 20 --warmup 5 --repeats 1 --no-cpu-baseline --trainer-steps 96 "$@" > $OUT/${NAME}_tr.log 2>&1
   rc=$?; echo "rocprof trainer rc=$rc"; [ $rc -ne 0 ] && { tail -5 $OUT/${NAME}_tr.log; return $rc; }
   python3 $R/tools/trainer_timeline.py $OUT/${NAME}_tr/*/*kernel_trace.csv | tee $OUT/${NAME}_trainer_timeline.txt
 }
@@ -56,7 +56,7 @@ case $MODE in
     cd $R
     timeout -k 10 1100 python3 -m pytest tests -x -q -m gpu > $OUT/${NAME}_tests.log 2>&1
     rc=$?; tail -3 $OUT/${NAME}_tests.log; [ $rc -ne 0 ] && exit $rc
-    timeout -k 10 400 python3 bench.py --breakdown > $OUT/${NAME}_bench_default.json 2> $OUT/${NAME}_bench.err
+    timeout -k 10 400 python3 bench.py --full --breakdown > $OUT/${NAME}_bench_default.json 2> $OUT/${NAME}_bench.err
     rc=$?; head -c 400 $OUT/${NAME}_bench_default.json; [ $rc -ne 0 ] && { tail -5 $OUT/${NAME}_bench.err; exit $rc; }
     cd /tmp
     stats && timeline ;;

@@ -474,6 +474,41 @@ int lnerf_grid_encode_backward_adam_tail(const float *xyzs, float bound, const v
                                          int flags, lnerf_stream_t stream);
 int lnerf_cast_f32_to_bf16(const float *src, void *dst, int64_t n, lnerf_stream_t stream);
 
+/* ---- iso-surface extraction (marching cubes): NeRFRenderer.export_mesh's kernel (the upstream renderer runs
+ * `mcubes.marching_cubes` on the host).  Additive to ABI 7.
+ *   vol [nx][ny][nz] f32, contiguous, z fastest (the layout mcubes uses); 2 <= nx, ny, nz <= LNERF_MC_MAX_DIM.
+ *   Lattice point (i, j, k) sits at  x_a(i) = lo_a + (hi_a - lo_a) * i / (n_a - 1)  (f32, evaluated left to right).
+ *   A point is INSIDE iff value > iso; NaN is outside.  LNERF_MC_CLOSE_BOUNDARY: a layer of outside points surrounds
+ *   the lattice, so a surface that reaches the box is capped (the mesh is closed); without it the mesh is open there.
+ * Tables and orientation: csrc/mc_tables.h (tools/gen_mc_tables.py): corner c = x + 2y + 4z, ambiguous faces never
+ * connect their inside corners, triangles (a, b, c) have (b - a) x (c - a) pointing from inside to outside.
+ * Vertices: every point of the working lattice (the lattice, plus the outside layer under CLOSE_BOUNDARY) owns its
+ *   +x, +y, +z edges; a vertex exists on every edge whose ends differ in inside-ness.  Order: (owning point's linear
+ *   index in the working lattice, axis x < y < z) -- shared vertices get one index, no dedup pass.  On the edge from
+ *   p0 (value v0) to p0 + e_a (value v1):  t = (iso - v0) / (v1 - v0);  if 0 <= t <= 1 the vertex's axis-a coordinate
+ *   is  x0 + t * (x1 - x0)  (x0, x1: the ends' coordinates), else (a NaN or outside-the-lattice end) the vertex sits
+ *   exactly on the inside end; the two other coordinates are the owning point's.  f32, no fused multiply-adds.
+ * Normals: world-space gradients at the two ends (central differences of vol over the ends' coordinate differences,
+ *   one-sided at the lattice border), blended with the same t (or taken from the inside end), negated, normalised
+ *   (0 for a zero gradient): they point from inside to outside.  `normals` may be NULL.
+ * Triangles: cells in order of their corner-0 point, table order within a cell; faces [F][3] int32 vertex indices.
+ *   The output is fully deterministic.  V must stay below 2^31 (int32 faces).
+ * counts_dev int64[2] receives {n_verts, n_faces}.  Vertices with index >= max_verts and triangles with index >=
+ * max_faces are not written (the counts are still the true ones).  Scratch: lnerf_marching_cubes_scratch_bytes()
+ * (~4 bytes per working point; 16-byte aligned).  Flags:
+ *   LNERF_MC_COUNT_ONLY  only the counts (and the scratch state for a following REUSE_COUNT call); outputs unused;
+ *   LNERF_MC_REUSE_COUNT only the emit pass, from the scratch of an immediately preceding COUNT_ONLY call with the
+ *                        same volume, lattice, iso and CLOSE_BOUNDARY (the caller sizes its buffers in between). */
+#define LNERF_MC_CLOSE_BOUNDARY 1
+#define LNERF_MC_COUNT_ONLY 2
+#define LNERF_MC_REUSE_COUNT 4
+#define LNERF_MC_MAX_DIM 1024
+size_t lnerf_marching_cubes_scratch_bytes(int nx, int ny, int nz, int flags);
+int lnerf_marching_cubes(const float *vol, int nx, int ny, int nz, float iso, float lo_x, float lo_y, float lo_z,
+                         float hi_x, float hi_y, float hi_z, int flags, void *scratch, size_t scratch_bytes,
+                         float *verts, float *normals, int64_t max_verts, int32_t *faces, int64_t max_faces,
+                         int64_t *counts_dev, lnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

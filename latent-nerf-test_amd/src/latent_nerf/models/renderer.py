@@ -7,6 +7,7 @@ src/stable_diffusion.py:259) and receives the SDS gradient via `pred.backward(gr
 
 Everything below runs on the HIP library; there is no PyTorch/CPU fallback path."""
 import math
+import os
 
 import torch
 import torch.nn as nn
@@ -381,6 +382,59 @@ class NeRFRenderer(nn.Module):
         rm.packbits(self.density_grid, self.density_thresh if thresh is None else float(thresh), self.density_bitfield,
                     None if thresh is not None else self.mean_density_dev)
         return self.density_bitfield
+
+    @torch.no_grad()
+    def density_lattice(self, resolution=None, S=128):
+        """sigma x density_scale on a resolution^3 lattice spanning [-bound, bound]^3 -> [R, R, R] f32 on the device
+        (z fastest; point (i, j, k) at -bound + 2 bound * (i, j, k) / (R - 1), the coordinates lnerf_marching_cubes
+        gives the lattice), queried through field() in S^3-point chunks."""
+        R = int(resolution or self.grid_size)
+        S = int(S)
+        dev = self.density_grid.device
+        lo = torch.tensor(-self.bound, dtype=torch.float32, device=dev)
+        span = torch.tensor(self.bound, dtype=torch.float32, device=dev) - lo
+        den = torch.tensor(float(R - 1), dtype=torch.float32, device=dev)
+        coords = lo + (span * torch.arange(R, dtype=torch.float32, device=dev)) / den
+        vol = torch.empty(R, R, R, device=dev, dtype=torch.float32)
+        for x0 in range(0, R, S):
+            for y0 in range(0, R, S):
+                for z0 in range(0, R, S):
+                    xs, ys, zs = coords[x0:x0 + S], coords[y0:y0 + S], coords[z0:z0 + S]
+                    pts = torch.stack(torch.meshgrid(xs, ys, zs, indexing="ij"), -1).reshape(-1, 3).contiguous()
+                    sigmas, _ = self.field(pts, pts.shape[0])
+                    vol[x0:x0 + S, y0:y0 + S, z0:z0 + S] = (sigmas * self.density_scale).view(len(xs), len(ys), len(zs))
+        return vol
+
+    @torch.no_grad()
+    def export_mesh(self, path, resolution=None, S=128, thresh=None):
+        """Triangle mesh of the density field -> `path`/mesh.obj (the upstream renderer's export_mesh(path, resolution,
+        S)): the density on a `resolution`^3 lattice over [-bound, bound]^3 (density_lattice), marching cubes on the GPU
+        at iso `thresh` (default min(mean density, density_thresh), as upstream) with the box capped, vertex colours
+        from the field at the vertices (latent mode: the linear latent->RGB preview), clamped to [0, 1].
+        Returns dict(verts [V,3], faces [F,3] int32, normals [V,3], colors [V,3], iso, path) with device tensors."""
+        from .mesh_io import write_obj
+        from ..training.guidance import LATENT_TO_RGB
+        vol = self.density_lattice(resolution, S)
+        if thresh is None:
+            iso = float(torch.clamp(self.mean_density_dev.reshape(-1)[0], max=float(self.density_thresh)))
+        else:
+            iso = float(thresh)
+        b = self.bound
+        verts, faces, normals = rm.marching_cubes(vol, iso, (-b, -b, -b), (b, b, b), close_boundary=True)
+        colors = torch.empty(verts.shape[0], 3, device=verts.device)
+        chunk = S ** 3
+        for s in range(0, verts.shape[0], chunk):
+            pts = verts[s:s + chunk].contiguous()
+            _, feats = self.field(pts, pts.shape[0])
+            if self.latent_mode and feats.shape[-1] == 4:
+                m = torch.tensor(LATENT_TO_RGB, device=feats.device, dtype=torch.float32)
+                rgb = (feats.float() @ m) / 2 + 0.5
+            else:
+                rgb = feats[:, :3].float()
+            colors[s:s + chunk] = rgb.clamp(0, 1)
+        out = os.path.join(str(path), "mesh.obj")
+        write_obj(out, verts.cpu().numpy(), faces.cpu().numpy(), normals.cpu().numpy(), colors.cpu().numpy())
+        return {"verts": verts, "faces": faces, "normals": normals, "colors": colors, "iso": iso, "path": out}
 
     def shadow_extra_state(self):
         """Context manager: inside it the occupancy state (density grid, bitfield, mean) is a SHADOW copy, so

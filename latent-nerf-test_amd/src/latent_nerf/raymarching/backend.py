@@ -23,6 +23,7 @@ TAIL_TICK, TAIL_CLEAR_SCATTER = 1, 2
 GRID_BLOCKED = 0x400          # flag on the gather's / scatter's variant: blocked layout of the hashed levels
 GRID_TILED = 0x800            # ... the upstream's `tiled` layout (dense index wrapped instead of hashed)
 SCATTER_CLEARED = 0x100       # flag on the scatter's variant: the caller cleared the cursors (lnerf_grid_scatter_clear_bytes)
+MC_CLOSE_BOUNDARY, MC_COUNT_ONLY, MC_REUSE_COUNT = 1, 2, 4   # LNERF_MC_* flags of lnerf_marching_cubes
 
 
 class LnerfLibraryError(RuntimeError):
@@ -107,6 +108,8 @@ _SIGNATURES = {
     "lnerf_mlp_backward_slabs": [_L, _I],
     "lnerf_grid_encode_backward_adam_tail": [_P, _F, _P, _I, _I, _I, _P, _P, _P, _L, _P, _L, _P, _I, _P, _Z, _P, _P, _P, _P,
                                              _F, _P, _Z, _I, _I, _P, _P, _P, _F, _P, _F, _F, _F, _I, _P, _F, _I, _P],
+    "lnerf_marching_cubes_scratch_bytes": [_I, _I, _I, _I],
+    "lnerf_marching_cubes": [_P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _I, _P, _Z, _P, _P, _L, _P, _L, _P, _P],
     "lnerf_step_tail": [_I, _I, _P, _P, _P, _L, _I, _P, _Z, _P, _P, _P, _P, _P, _F, _P, _Z, _I, _I, _P, _P, _P, _F, _P,
                         _F, _F, _F, _I, _P, _F, _I, _P],
 }
@@ -118,6 +121,7 @@ _RESTYPES = {
     "lnerf_occ_sample_scratch_bytes": _Z,
     "lnerf_march_counter_len": _L,
     "lnerf_grid_encode_backward_workspace_bytes": _Z,
+    "lnerf_marching_cubes_scratch_bytes": _Z,
 }
 
 _lib = None

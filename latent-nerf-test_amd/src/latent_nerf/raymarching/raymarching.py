@@ -299,3 +299,40 @@ def composite_rays_train(sigmas, rgbs, deltas, rays, T_thresh=1e-4, bg_color=Non
     """sigmas [M], rgbs [M,C], deltas [M,2]=(dt,t), rays int32 [N,3]=(id,offset,count)
     -> weights_sum [N], depth [N], image [N,C] (+ (1-weights_sum)*bg_color)."""
     return _CompositeRaysTrain.apply(sigmas, rgbs, deltas, rays, T_thresh, bg_color)
+
+
+# ------------------------------------------------------------------------------ mesh export
+def marching_cubes(volume, iso, lo, hi, close_boundary=True):
+    """Iso-surface of a dense f32 volume [nx, ny, nz] (z fastest) on the GPU (lnerf_marching_cubes, include/lnerf_hip.h).
+    Lattice point (i, j, k) sits at lo + (hi - lo) * (i, j, k) / (n - 1); inside is value > iso.
+    -> verts [V,3] f32, faces [F,3] int32 (normals from inside to outside), normals [V,3] f32, all on the device.
+    One host synchronisation: a count pass sizes the outputs, the emit pass fills them from its scratch."""
+    if not isinstance(volume, torch.Tensor) or volume.dim() != 3:
+        raise ValueError("marching_cubes: volume must be a 3-d tensor [nx, ny, nz]")
+    volume = volume.contiguous()
+    _chk(volume, "volume")
+    nx, ny, nz = (int(s) for s in volume.shape)
+    lo = [float(v) for v in (lo.tolist() if isinstance(lo, torch.Tensor) else lo)]
+    hi = [float(v) for v in (hi.tolist() if isinstance(hi, torch.Tensor) else hi)]
+    if len(lo) != 3 or len(hi) != 3:
+        raise ValueError("marching_cubes: lo and hi take three coordinates each")
+    flags = _b.MC_CLOSE_BOUNDARY if close_boundary else 0
+    dev = volume.device
+    nbytes = _b.get_lib().lnerf_marching_cubes_scratch_bytes(nx, ny, nz, flags)
+    if nbytes == 0:
+        raise ValueError("marching_cubes: lattice %d x %d x %d outside [2, 1024] per axis" % (nx, ny, nz))
+    scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    counts = torch.zeros(2, device=dev, dtype=torch.int64)
+    args = (_p(volume), nx, ny, nz, float(iso), *lo, *hi)
+    _b.call("lnerf_marching_cubes", *args, flags | _b.MC_COUNT_ONLY, _p(scratch), nbytes, None, None, 0, None, 0,
+            _p(counts), _stream())
+    V, F = (int(v) for v in counts.tolist())
+    if V >= 2 ** 31:
+        raise ValueError("marching_cubes: %d vertices do not fit int32 face indices" % V)
+    verts = torch.empty(V, 3, device=dev, dtype=torch.float32)
+    normals = torch.empty(V, 3, device=dev, dtype=torch.float32)
+    faces = torch.empty(F, 3, device=dev, dtype=torch.int32)
+    if V > 0 or F > 0:
+        _b.call("lnerf_marching_cubes", *args, flags | _b.MC_REUSE_COUNT, _p(scratch), nbytes, _p(verts), _p(normals), V,
+                _p(faces), F, _p(counts), _stream())
+    return verts, faces, normals

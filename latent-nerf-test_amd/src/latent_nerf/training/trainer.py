@@ -468,7 +468,13 @@ class Trainer:
         return frames
 
     def full_eval(self):
-        return self.evaluate(self.dataloaders["val_large"], self.final_renders_path, save_as_video=True)
+        frames = self.evaluate(self.dataloaders["val_large"], self.final_renders_path, save_as_video=True)
+        if getattr(self.cfg.log, "save_mesh", False) and self.rank == 0:
+            # the density field as a triangle mesh (NeRFRenderer.export_mesh) -> <exp_dir>/mesh/mesh.obj
+            mesh = self.nerf.export_mesh(self.exp_path / "mesh")
+            self.log("exported %s (%d vertices, %d triangles, iso %.4g)"
+                     % (mesh["path"], mesh["verts"].shape[0], mesh["faces"].shape[0], mesh["iso"]))
+        return frames
 
     def preview_rgb(self, latents):
         """[1,C,H,W] latents -> uint8 [H',W',3].  With `log.decode_eval` the guidance model's decoder turns the latents

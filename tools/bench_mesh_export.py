@@ -1,0 +1,80 @@
+"""Mesh export timing on the bench's field: the density lattice query (NeRFRenderer.density_lattice, S = 128 chunks) and
+marching cubes (raymarching.marching_cubes: count pass, scan, one host read of the counts, emit pass) at 128^3, 256^3
+and 512^3.  Prints ONE JSON line.
+
+    python tools/bench_mesh_export.py [--precision bf16|f32] [--reps 5]
+
+Field: bench.py's (seed 0, Linear-default MLP, table N(0, 0.1), density blob; bf16 runs the blocked bf16 default), iso =
+density_thresh (10).  Times are HIP events around the call (median of --reps after one warm-up call per size).
+mc_bytes is the marching-cubes traffic model: the volume read by the count and the emit pass (2 x 4 B per working point),
+the per-point words (written, rewritten and read: 4 x 4 B), and the outputs (24 B per vertex with its normal, 12 B per
+triangle); mc_GBps = mc_bytes / mc time."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "latent-nerf-test_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def field(dev, precision):
+    from src.latent_nerf.configs.render_config import RenderConfig
+    from src.latent_nerf.models.network_grid import NeRFNetwork
+    torch.manual_seed(0)
+    cfg = RenderConfig(grid_size=128, train_h=64, train_w=64, mlp_precision=precision, table_dtype=precision,
+                       gridtype="blocked" if precision == "bf16" else "hash")
+    net = NeRFNetwork(cfg)
+    net.encoder.embeddings.data.normal_(0, 0.1)
+    return net.to(dev).eval(), cfg
+
+
+def timed(fn, reps):
+    fn()   # warm-up
+    torch.cuda.synchronize()
+    times, out = [], None
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = fn()
+        b.record()
+        torch.cuda.synchronize()
+        times.append(a.elapsed_time(b))
+    return statistics.median(times), out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--precision", default="bf16", choices=["bf16", "f32"])
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--sizes", default="128,256,512")
+    args = ap.parse_args()
+    from src.latent_nerf.raymarching import marching_cubes
+    assert torch.cuda.is_available(), "bench_mesh_export needs the GPU"
+    dev = torch.device("cuda:0")
+    net, cfg = field(dev, args.precision)
+    iso = float(cfg.density_thresh)
+    b = net.bound
+    res = []
+    for R in (int(s) for s in args.sizes.split(",")):
+        t_q, vol = timed(lambda: net.density_lattice(R, S=128), args.reps)
+        t_mc, (v, f, n) = timed(lambda: marching_cubes(vol, iso, (-b,) * 3, (b,) * 3, close_boundary=True), args.reps)
+        N = (R + 2) ** 3
+        V, F = int(v.shape[0]), int(f.shape[0])
+        mc_bytes = 8 * N + 16 * N + 24 * V + 12 * F
+        res.append({"resolution": R, "points": R ** 3, "query_ms": round(t_q, 4), "mc_ms": round(t_mc, 4), "V": V, "F": F,
+                    "mc_bytes": mc_bytes, "mc_GBps": round(mc_bytes / (t_mc * 1e-3) / 1e9, 1),
+                    "query_Mpts_per_s": round(R ** 3 / (t_q * 1e-3) / 1e6, 1)})
+        del vol, v, f, n
+        torch.cuda.empty_cache()
+    print(json.dumps({"tool": "bench_mesh_export", "precision": args.precision, "iso": iso, "reps": args.reps,
+                      "device": torch.cuda.get_device_name(0), "results": res}))
+
+
+if __name__ == "__main__":
+    main()

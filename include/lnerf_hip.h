@@ -68,8 +68,7 @@ const char *lnerf_build_info(void);
  *   "gather_dedup_max_res":    levels with resolution <= value fetch a cell's 8 vertices once per run of
  *                              lanes (consecutive samples of a ray) in that cell (default 512; 0 = off).
  *   "mlp_fwd_blocks":          persistent workgroups of the bf16 MLP forward (default 768).
- *   "mlp_fwd_wps":             wavefronts per SIMD the bf16 forward is compiled for, 3 (default), 2 or 4.
- *   "gather_wgs_per_xcd":      workgroups per XCD of the XCD-owned-level gather variant (variant 2).
+ *   "mlp_fwd_wps":             wavefronts per SIMD the bf16 forward is compiled for, 3 (default) or 2.
  *   "mlp_bwd_blocks":          persistent workgroups of the MLP backward (default and maximum 512 = slab count).
  */
 int lnerf_set_tuning(const char *key, int value);
@@ -166,8 +165,7 @@ int lnerf_compact_rays(const int32_t *alive_in, int64_t n, int32_t *alive_out, i
  * Level metadata is passed from the host (num_levels <= LNERF_MAX_LEVELS):
  *   offsets_host [L+1] row offsets, scales_host [L] per-level scale, res_host [L] resolution.
  * xyzs are world positions; the kernels normalise x01 = (x + bound) / (2*bound).
- * `variant` selects the workgroup->(level,tile) mapping: 0 = level on blockIdx.y,
- * 1 = XCD-aware (levels pinned to XCDs so each XCD's L2 holds two levels). */
+ * `variant` must be 0 (level on blockIdx.y), optionally with the layout flags LNERF_GRID_BLOCKED / LNERF_GRID_TILED. */
 int lnerf_grid_encode_forward(const float *xyzs, float bound, const void *table, int table_dtype, int num_levels,
                               int level_dim, const int32_t *offsets_host, const float *scales_host,
                               const int32_t *res_host, int64_t m_host, const int32_t *m_dev, int64_t level_stride,

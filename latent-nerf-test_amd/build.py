@@ -19,11 +19,6 @@ LIB = os.path.join(LIBDIR, "liblnerf_hip.so")
 SOURCES = ["api.cc", "rays.hip", "grid_gather.hip", "grid_bin.hip", "grid.hip", "mlp.hip", "mlp_bf16.hip", "composite.hip", "optim.hip", "bg.hip", "mesh.hip", "raster.hip", "guidance.hip", "isosurface.hip"]
 DEPS = ["common.h", "mlp_shared.h", "adam_shared.h", "grid_shared.h", "mc_tables.h", os.path.join("..", "..", "include", "lnerf_hip.h")]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
-# LNERF_EXPERIMENTS=1 in the environment: also compile the measured-and-rejected kernel variants (operand-swap MLP backward,
-# four-wave MLP forward, XCD-pinned gather mappings) that DESIGN.md's experiment log refers to; the product build leaves
-# them out (two of them spill)
-if os.environ.get("LNERF_EXPERIMENTS", "0") not in ("", "0"):
-    FLAGS = FLAGS + ["-DLNERF_EXPERIMENTS"]
 
 
 def _digest():

@@ -63,20 +63,11 @@ __device__ __forceinline__ int active_slices(int n, int smax) {
 //
 // The records of bucket b are the segments (first slot, count) = segtab entry of (item, b), one per item of pass 1, inside
 // the items' chunks.  Wave w of the workgroup takes items w, w + 16, ...: it reads 64 of its entries with one load and
-// walks the concatenation of those segments 64 records per round (see the loop).  LNERF_REDUCE_ROUNDS rounds of loads
-// are in flight per lane.  Built and measured on the way (profiles/r03_exp_scatter.jsonl): the segment of a lane found by
+// walks the concatenation of those segments 64 records per round (see the loop).  REDUCE_ROUNDS rounds of loads are
+// in flight per lane.  Built and measured on the way (profiles/r03_exp_scatter.jsonl): the segment of a lane found by
 // a binary search through ds_bpermute (+12 us: the permutes share the LDS pipe with the atomics); one segment per round
 // (half-empty waves: three times the instructions, 2-3x the time).
-#ifndef LNERF_REDUCE_ROUNDS
-#define LNERF_REDUCE_ROUNDS 8
-#endif
-#ifndef LNERF_REDUCE_XCD
-#define LNERF_REDUCE_XCD 1
-#endif
-// how a lane of the record loop finds its record: 0 = scalar walk over the segments a round spans, 1 = start bitmap
-#ifndef LNERF_REDUCE_WALK
-#define LNERF_REDUCE_WALK 1
-#endif
+constexpr int REDUCE_ROUNDS = 8;
 // ---- the step's TAIL: what is left of a single-GPU step besides the scatter.  In a replayed graph a dependent dispatch
 // costs ~4.5 us whatever it computes, and three of them sat behind pass 2 for a few microseconds of work: the finishing
 // pass of the sliced buckets (pass 2 does it itself now), the sum of the MLP's gradient slabs and the Adam step of the
@@ -201,36 +192,16 @@ struct TailJob {
     int rev_lo, rev_hi;    // work units [rev_lo, rev_hi) are taken in DESCENDING order (0, 0: none)
 };
 
-// LNERF_REDUCE_NT (bit mask): non-temporal policy on the once-per-step streams of the reduce pass -- 1: parameter /
-// moment loads, 2: their stores (the bf16 shadow the gather reads keeps the default policy), 4: the record loads
-// (measured: the gather gains 1.5 us more, the reduce pass loses 8 -- off)
-#ifndef LNERF_REDUCE_NT
-#define LNERF_REDUCE_NT 3
-#endif
+// The once-per-step streams of the reduce pass, parameter / moment loads and their stores, are non-temporal (the bf16
+// shadow the gather reads keeps the default policy; measured with the binning pass's streams: grid_shared.h).  The
+// record loads keep the default policy: non-temporal, the gather gained 1.5 us more and the reduce pass lost 8.
 __device__ __forceinline__ float4 ld_f4(const float4 *p) {
-    if (LNERF_REDUCE_NT & 1) {
-        const nt_f4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_f4 *>(p));
-        return make_float4(v.x, v.y, v.z, v.w);
-    }
-    return *p;
+    const nt_f4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_f4 *>(p));
+    return make_float4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ void st_f4(float4 *p, const float4 &x) {
-    if (LNERF_REDUCE_NT & 2) {
-        nt_f4 v = {x.x, x.y, x.z, x.w};
-        __builtin_nontemporal_store(v, reinterpret_cast<nt_f4 *>(p));
-    } else {
-        *p = x;
-    }
-}
-template <typename REC> __device__ __forceinline__ REC ld_rec(const REC *p) { return *p; }
-template <> __device__ __forceinline__ Rec8 ld_rec<Rec8>(const Rec8 *p) {
-    if (LNERF_REDUCE_NT & 4) {
-        const nt_u2 v = __builtin_nontemporal_load(reinterpret_cast<const nt_u2 *>(p));
-        Rec8 r;
-        r.lo = v.x; r.hi = v.y;
-        return r;
-    }
-    return *p;
+    nt_f4 v = {x.x, x.y, x.z, x.w};
+    __builtin_nontemporal_store(v, reinterpret_cast<nt_f4 *>(p));
 }
 
 template <int RT, typename REC, bool FUSE>
@@ -246,10 +217,8 @@ __device__ __forceinline__ void scatter_reduce_one(int wg, const GridMeta &meta,
     // flat atomic -- measured 0.211 -> 0.275 ms for the scatter call)
     __shared__ long long acc[BK_ROWS * 2];  // [feature][row]: a wave's 64 random rows spread over 32 bank pairs
     __shared__ int s_red[RT / 64];
-#if LNERF_REDUCE_WALK
     __shared__ uint32_t s_bmp[RT / 64][128];            // per wave: segment-start bitmap of a sub-batch (4096 records)
     __shared__ uint32_t s_soff[RT / 64][64];            // per wave: (chunk slot - flat start) of its non-empty segments
-#endif
     constexpr int NW = RT / 64;
     if (wg < 0) {
         // a SLAB workgroup of the closing launch (wg = -1 - index): RT / 256 slab blocks, their 1 KiB of LDS each carved
@@ -271,7 +240,7 @@ __device__ __forceinline__ void scatter_reduce_one(int wg, const GridMeta &meta,
     // bucket count is a multiple of 8 the workgroups of one XCD take CONTIGUOUS buckets.  The segments of neighbouring
     // buckets are neighbours inside every chunk and share 128-byte lines at their seams: read by workgroups of one XCD at
     // about the same time, those lines come from that XCD's L2 the second time instead of twice through the fabric.
-    if (LNERF_REDUCE_XCD && Smax == 1 && (nb & 7) == 0) b = (local & 7) * (nb >> 3) + (local >> 3);
+    if (Smax == 1 && (nb & 7) == 0) b = (local & 7) * (nb >> 3) + (local >> 3);
     const int tid = threadIdx.x, lane = tid & 63;
     // (uniform, and known to be: everything derived from it -- the wave's items, their chunk addresses -- stays in
     // scalar registers; as a function of threadIdx it was per-lane 64-bit address arithmetic and spilled)
@@ -318,11 +287,7 @@ __device__ __forceinline__ void scatter_reduce_one(int wg, const GridMeta &meta,
     // records waits for the slowest wave anyway, and the loads travel meanwhile.  (Requested ahead of the record stream
     // they were measured 35 us slower: the records queue behind them.)
     constexpr int NQ = (BK_ROWS / 2 + RT - 1) / RT;  // row pairs per lane
-#ifdef LNERF_EXP_RED_NOADAM     // timing-only experiment build: the workgroup ends behind its record loop
-    const bool fast = false;
-#else
     const bool fast = fuse && direct && !fu.grad_out && ((R0 | rows) & 1) == 0 && rows == BK_ROWS && (BK_ROWS / 2) % RT == 0;
-#endif
     float4 P[NQ], Mv[NQ], V[NQ];
     float4 *p4 = reinterpret_cast<float4 *>(reinterpret_cast<float2 *>(fu.p) + R0);
     float4 *m4 = reinterpret_cast<float4 *>(reinterpret_cast<float2 *>(fu.m) + R0);
@@ -347,70 +312,21 @@ __device__ __forceinline__ void scatter_reduce_one(int wg, const GridMeta &meta,
         // rounds of loads in flight per lane.  A 12-byte record is three registers: five rounds in flight are what the
         // 64 registers of two resident workgroups leave room for (eight spilled 20-36 bytes per lane to scratch, whose
         // traffic shares the vector-memory queue with the very loads the loop waits for)
-        constexpr int U = REC::kPacked ? LNERF_REDUCE_ROUNDS : (LNERF_REDUCE_ROUNDS < 5 ? LNERF_REDUCE_ROUNDS : 5);
-#ifdef LNERF_EXP_RED_NOREC   // timing-only experiment build: no record loop
-        for (int kb = 0; kb < 0; kb += 64) {
-#else
+        constexpr int U = REC::kPacked ? REDUCE_ROUNDS : (REDUCE_ROUNDS < 5 ? REDUCE_ROUNDS : 5);
         for (int kb = 0; kb < nmy; kb += 64) {                        // (one pass for up to 64 x 16 = 1024 items)
-#endif
             uint32_t e = e_first;
             if (kb > 0) e = kb + lane < nmy ? tab[(int64_t)(first + NW * (kb + lane)) * nb] : 0u;
-            const int cnt = nmy - kb < 64 ? nmy - kb : 64;            // segments held by the lanes (uniform)
-            const int T = __builtin_amdgcn_readlane(wave_inclusive_sum_i((int)(e >> 16)), 63);   // their records
+            const int T = __builtin_amdgcn_readlane(wave_inclusive_sum_i((int)(e >> 16)), 63);   // the lanes' records
             // Walk the CONCATENATION of the segments 64 records per round: lane i of a round takes flat record f0 + i, so
             // every lane carries a record whatever the segment sizes are (~32 on a hashed level, thousands on a
-            // one-bucket level).  Which segment a lane is in comes from a SCALAR walk: (sj, sp) = first segment that
-            // reaches into the round and its flat start; a round visits the 2-3 segments it spans, each visit two scalar
-            // readlanes and three vector instructions -- no cross-lane traffic on the LDS pipe, which the two 64-bit
-            // atomics of every record need (a binary search through ds_bpermute was 12 us slower).
-#if LNERF_REDUCE_WALK == 0
-            int sj = 0, sp = 0;
-            // record index (inside the level's region) of flat record fb + lane; called with increasing fb
-            auto locate = [&](int fb) __attribute__((always_inline)) -> uint32_t {
-                const int f = fb + lane;
-                uint32_t at = 0u;
-                for (;;) {
-                    const uint32_t ej = (uint32_t)__builtin_amdgcn_readlane((int)e, sj);
-                    const int cj = (int)(ej >> 16);
-                    // (chunk of item `first + NW (kb + sj)`, its segment's first slot, minus the flat start)
-                    const uint32_t base = (uint32_t)(first + NW * (kb + sj)) * (uint32_t)ITEM_RECS + (ej & 0xFFFFu) -
-                                          (uint32_t)sp;
-                    at = (f >= sp && f < sp + cj) ? base + (uint32_t)f : at;
-                    if (sp + cj >= fb + 64 || sj + 1 >= cnt) break;   // the round ends inside this segment
-                    sp += cj;
-                    ++sj;
-                }
-                return f < T ? at : 0u;                               // (slot 0 exists: the load is unconditional)
-            };
-            // software pipeline over the rounds: U loads are in flight at ALL times -- a round's record is consumed and
-            // its register immediately re-armed with the load of the round U ahead (a plain "issue U, consume U" loop
-            // drains to zero loads in flight at the end of every batch)
-            const int nr = (T + 63) >> 6;                             // rounds (uniform)
-            REC r[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-                if (u < nr) r[u] = ld_rec(lrec + locate(64 * u));
-            for (int rb = 0; rb < nr; rb += U) {
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int rd = rb + u;                            // uniform
-                    if (rd < nr) {
-                        pin_record(r[u]);                             // (keeps the load outside the predicated block)
-                        const REC cur = r[u];
-                        if (rd + U < nr) r[u] = ld_rec(lrec + locate(64 * (rd + U)));
-                        if (64 * rd + lane < T) add(cur);
-                    }
-                }
-            }
-#else
-            // Which segment a lane's record is in comes from a BITMAP of the segment starts: bit p = "flat record p is the
-            // first of its segment"; lane k keeps bits [64 k, 64 k + 64).  A round reads its 64 bits with two scalar
-            // readlanes; a lane's segment is the number of starts at or below its position (mbcnt), its record's slot
-            // one LDS read of that segment's (chunk slot - flat start) plus its position: ~10 instructions per round
-            // instead of a scalar walk over the 2-3 segments a round spans (~150: the pass was bound by instruction issue,
-            // not by HBM -- without the Adam phase it took 87 us for 240 MB).  The bitmap covers SUB = 4096 records (64
-            // rounds): a window of 64 segments is taken in sub-batches of whole segments with at most SUB records.
-            (void)cnt;
+            // one-bucket level).  Which segment a lane's record is in comes from a BITMAP of the segment starts: bit p =
+            // "flat record p is the first of its segment"; lane k keeps bits [64 k, 64 k + 64).  A round reads its 64 bits
+            // with two scalar readlanes; a lane's segment is the number of starts at or below its position (mbcnt), its
+            // record's slot one LDS read of that segment's (chunk slot - flat start) plus its position: ~10 instructions
+            // per round instead of a scalar walk over the 2-3 segments a round spans (~150: the pass was bound by
+            // instruction issue, not by HBM -- without the Adam phase it took 87 us for 240 MB).  The bitmap covers SUB =
+            // 4096 records (64 rounds): a window of 64 segments is taken in sub-batches of whole segments with at most SUB
+            // records.
             constexpr int SUB = 4096;
             static_assert(ITEM_RECS <= SUB, "a segment must fit a sub-batch");
             const int c = (int)(e >> 16);                             // records of the lane's segment
@@ -454,12 +370,13 @@ __device__ __forceinline__ void scatter_reduce_one(int wg, const GridMeta &meta,
                     return f < Ts ? at : 0u;                          // (slot 0 exists: the load is unconditional)
                 };
                 // software pipeline over the rounds: U loads are in flight at ALL times -- a round's record is consumed
-                // and its register immediately re-armed with the load of the round U ahead
+                // and its register immediately re-armed with the load of the round U ahead (a plain "issue U, consume U"
+                // loop drains to zero loads in flight at the end of every batch)
                 const int nr = (Ts + 63) >> 6;                        // rounds (uniform)
                 REC r[U];
 #pragma unroll
                 for (int u = 0; u < U; ++u)
-                    if (u < nr) r[u] = ld_rec(lrec + locate(64 * u));
+                    if (u < nr) r[u] = lrec[locate(64 * u)];
                 for (int rb = 0; rb < nr; rb += U) {
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
@@ -467,7 +384,7 @@ __device__ __forceinline__ void scatter_reduce_one(int wg, const GridMeta &meta,
                         if (rd < nr) {
                             pin_record(r[u]);                         // (keeps the load outside the predicated block)
                             const REC cur = r[u];
-                            if (rd + U < nr) r[u] = ld_rec(lrec + locate(64 * (rd + U)));
+                            if (rd + U < nr) r[u] = lrec[locate(64 * (rd + U))];
                             if (64 * rd + lane < Ts) add(cur);
                         }
                     }
@@ -475,7 +392,6 @@ __device__ __forceinline__ void scatter_reduce_one(int wg, const GridMeta &meta,
                 a = bnd;
                 a_base += Ts;
             }
-#endif
         }
         RED_STAMP(11);
         if (fast) {
@@ -553,9 +469,6 @@ __device__ __forceinline__ void scatter_reduce_one(int wg, const GridMeta &meta,
         __syncthreads();
     }
     float *dst = dtable + R0 * 2;
-#ifdef LNERF_EXP_RED_NOADAM
-    if (fuse) return;
-#endif
     if (fuse) {
         AdamArgs a = fu.a;
         if (have_step) adam_bias_at(a, __builtin_amdgcn_readfirstlane(step_now));   // (the closing launch: see the kernel)
@@ -627,11 +540,9 @@ __device__ __forceinline__ void scatter_reduce_one(int wg, const GridMeta &meta,
 // One workgroup per (bucket, slice) unit.  (PERSISTENT workgroups striding over the units were built and measured: the
 // loop keeps the three kernel-argument structs live across iterations, 77 VGPRs spill at the 64 the two-workgroups-per-CU
 // occupancy allows, and the pass went from 0.211 to 0.27 ms per scatter call: profiles/r03_exp_scatter.jsonl.)
-#ifndef LNERF_FUSED_RT          // threads per workgroup of the fused pass (experiment knob: 512 with LNERF_BK_SHIFT = 11)
-#define LNERF_FUSED_RT 1024
-#endif
+constexpr int FUSED_RT = 1024;   // threads per workgroup of the fused pass
 template <int RT, typename REC, bool FUSE>
-__global__ void __launch_bounds__(RT, (LNERF_BK_SHIFT < 12 && RT == 512) ? 8 : RT / 128)
+__global__ void __launch_bounds__(RT, RT / 128)
 k_scatter_reduce(GridMeta meta, BucketMeta bm, const int32_t *__restrict__ items_dev, const uint32_t *__restrict__ segtab,
                  int32_t *__restrict__ bucket_n, int32_t *__restrict__ slice_arrive, unsigned int *gmax,
                  const REC *__restrict__ recs, float *__restrict__ dtable, long long *__restrict__ partials, int wg_lo,
@@ -687,14 +598,12 @@ k_step_tail(unsigned int *__restrict__ gmax, AdamArgs a, SlabAdam sa, int32_t *_
     }
 }
 
-extern int g_mlp_fwd_blocks, g_mlp_fwd_wps, g_mlp_bwd_blocks, g_mlp_bwd_variant;  // mlp.hip
+extern int g_mlp_fwd_blocks, g_mlp_fwd_wps, g_mlp_bwd_blocks;  // mlp.hip
 
 // levels up to this resolution merge per-wave runs before binning (tunable: lnerf_set_tuning)
 int g_compact_max_res = 512;
 // gather: fetch x-adjacent vertices with one load where they are adjacent rows (2: also aligned groups of four rows)
 int g_gather_pairs = 2;
-// gather variant 2: workgroups per XCD (each strides over the tiles of its XCD's levels)
-int g_gather_wgs_per_xcd = 256;
 // gather: levels with resolution <= this fetch a cell's vertices once per run of lanes in that cell (0 = off)
 int g_gather_dedup_res = 512;
 // gather: bytes of (unused) dynamic LDS per workgroup -- an EXPERIMENT knob that caps the resident wavefronts (160 KiB per CU:
@@ -804,11 +713,6 @@ int lnerf_set_tuning(const char *key, int value) {
         g_gather_dedup_res = value;
         return LNERF_OK;
     }
-    if (strcmp(key, "gather_wgs_per_xcd") == 0) {
-        LNERF_REQUIRE(value >= 1 && value <= 4096, "set_tuning: gather_wgs_per_xcd out of range");
-        g_gather_wgs_per_xcd = value;
-        return LNERF_OK;
-    }
     if (strcmp(key, "gather_lds_pad") == 0) {
         LNERF_REQUIRE(value >= 0 && value <= 65536, "set_tuning: gather_lds_pad must be in [0, 65536] bytes");
         g_gather_lds_pad = value;
@@ -819,24 +723,13 @@ int lnerf_set_tuning(const char *key, int value) {
         g_gather_pairs = value;
         return LNERF_OK;
     }
-    if (strcmp(key, "mlp_bwd_variant") == 0) {
-        LNERF_REQUIRE(value >= 0 && value <= 2, "set_tuning: mlp_bwd_variant must be 0, 1 or 2");
-#ifndef LNERF_EXPERIMENTS
-        LNERF_REQUIRE(value == 0, "set_tuning: mlp_bwd_variant %d is an experiment variant (build with -DLNERF_EXPERIMENTS)", value);
-#endif
-        g_mlp_bwd_variant = value;
-        return LNERF_OK;
-    }
     if (strcmp(key, "mlp_bwd_blocks") == 0) {
         LNERF_REQUIRE(value >= 1 && value <= 512, "set_tuning: mlp_bwd_blocks must be in 1 .. 512");
         g_mlp_bwd_blocks = value;
         return LNERF_OK;
     }
     if (strcmp(key, "mlp_fwd_wps") == 0) {
-        LNERF_REQUIRE(value >= 2 && value <= 4, "set_tuning: mlp_fwd_wps must be 2, 3 or 4");
-#ifndef LNERF_EXPERIMENTS
-        LNERF_REQUIRE(value <= 3, "set_tuning: mlp_fwd_wps 4 is an experiment variant (build with -DLNERF_EXPERIMENTS)");
-#endif
+        LNERF_REQUIRE(value == 2 || value == 3, "set_tuning: mlp_fwd_wps must be 2 or 3");
         g_mlp_fwd_wps = value;
         return LNERF_OK;
     }
@@ -981,12 +874,9 @@ static int scatter_backward(const float *xyzs, float bound, const void *dfeat, i
                       "grid_encode_backward: the closing form needs the fused whole-table call");
         tj0 = *tail;
         tj0.arrive = (int32_t *)(wsb + HDR_ARRIVE_OFF);
-        tj0.blocks = tj0.sa.slabs ? (int)div_up(div_up(MLP_SLAB, TAIL_P), LNERF_FUSED_RT / 256) : 0;   // four slab blocks per workgroup
+        tj0.blocks = tj0.sa.slabs ? (int)div_up(div_up(MLP_SLAB, TAIL_P), FUSED_RT / 256) : 0;   // four slab blocks per workgroup
     }
-#ifndef LNERF_REDUCE_ORDER
-#define LNERF_REDUCE_ORDER 1
-#endif
-    if (LNERF_REDUCE_ORDER) {   // whole-table launches only (a level-range launch keeps the plain order)
+    {   // the un-sliced levels heaviest first (whole-table launches only: a level-range launch keeps the plain order)
         int lf = 0;
         for (int l = 0; l < num_levels; ++l) if (bm.slices[l] > 1) lf = l + 1;
         tj0.rev_lo = bm.wgstart[lf];
@@ -1001,8 +891,8 @@ static int scatter_backward(const float *xyzs, float bound, const void *dfeat, i
                        st, meta, bm, items_dev, segtab, bucket_n, slice_arrive, gmax, (const REC *)rec, dtable, partials, \
                        w0, fu0, tj0)
         // (the fused pass with 512-thread workgroups: 118 us against 108, profiles/r03_exp_scatter.jsonl)
-        if (fu && packed) LAUNCH_RED(LNERF_FUSED_RT, Rec8, true);
-        else if (fu) LAUNCH_RED(LNERF_FUSED_RT, Rec12, true);
+        if (fu && packed) LAUNCH_RED(FUSED_RT, Rec8, true);
+        else if (fu) LAUNCH_RED(FUSED_RT, Rec12, true);
         else if (packed && g_reduce_threads == 512) LAUNCH_RED(512, Rec8, false);
         else if (packed) LAUNCH_RED(1024, Rec8, false);
         else if (g_reduce_threads == 512) LAUNCH_RED(512, Rec12, false);

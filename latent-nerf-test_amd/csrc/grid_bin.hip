@@ -129,12 +129,9 @@ k_scatter_bin(const float *__restrict__ xyzs, float bound, const float *__restri
         n_g = make_float2(0.f, 0.f);
         if (mm < M) {
             const float2 *gp = reinterpret_cast<const float2 *>(dfeat) + ((int64_t)lv * level_stride + mm);
-            if (LNERF_BIN_NT & 1) {   // (read once per step: keep it out of the caches the table and the records use)
-                const nt_f2 v = __builtin_nontemporal_load(reinterpret_cast<const nt_f2 *>(gp));
-                n_g = make_float2(v.x, v.y);
-            } else {
-                n_g = *gp;
-            }
+            // (read once per step: keep it out of the caches the table and the records use)
+            const nt_f2 v = __builtin_nontemporal_load(reinterpret_cast<const nt_f2 *>(gp));
+            n_g = make_float2(v.x, v.y);
             n_x = xyzs[(int64_t)mm * 3]; n_y = xyzs[(int64_t)mm * 3 + 1]; n_z = xyzs[(int64_t)mm * 3 + 2];
         }
     };
@@ -312,13 +309,9 @@ k_scatter_bin(const float *__restrict__ xyzs, float bound, const float *__restri
             const uint4 *srcq = reinterpret_cast<const uint4 *>(s_stage);
             const int n16 = (total * (int)sizeof(REC) + 15) >> 4;
             for (int i = tid; i < n16; i += BIN_T) {
-                if (LNERF_BIN_NT & 2) {
-                    const uint4 q = srcq[i];
-                    nt_u4 v = {q.x, q.y, q.z, q.w};
-                    __builtin_nontemporal_store(v, reinterpret_cast<nt_u4 *>(dst + i));
-                } else {
-                    dst[i] = srcq[i];
-                }
+                const uint4 q = srcq[i];
+                nt_u4 v = {q.x, q.y, q.z, q.w};
+                __builtin_nontemporal_store(v, reinterpret_cast<nt_u4 *>(dst + i));
             }
             if (tid < nb)
                 segtab[(int64_t)lv.b0 * bm.n_items + (int64_t)tile * nb + tid] =

@@ -3,13 +3,7 @@
 // Forward is the roofline kernel of the path: per sample and level it gathers
 // 8 vertices x 2 features.  One thread handles one (sample, level); a wavefront handles 64
 // consecutive samples of ONE level, so its 8 gather instructions hit one level's table and its
-// output is 512 contiguous bytes (level-major feature layout).
-//
-// variant 0: blockIdx.y = level.
-// variant 1: XCD-aware.  Workgroups are dealt round-robin over the 8 XCDs (observed, used for
-//            speed only -- correctness never depends on it), so workgroup b serves levels
-//            {b % 8, b % 8 + 8, ...}: each XCD's private 4 MiB L2 then only ever holds the
-//            tables of its own levels instead of all 16.
+// output is 512 contiguous bytes (level-major feature layout).  The level is blockIdx.y.
 #include "grid_shared.h"
 
 namespace lnerf {
@@ -74,37 +68,15 @@ template <> struct CellRaw<float> {
     __device__ __forceinline__ float2 get(int c) const { return d[c]; }
 };
 
-// variant 2: every XCD serves a fixed SET of levels (workgroups are dealt round-robin over the 8 XCDs -- observed, used
-// for speed only): the 4 MiB L2 of an XCD then holds the whole table of its one fine level (2 MiB bf16) instead of a
-// sixth of all sixteen, and the gather -- bound by the L1's miss concurrency x the latency of a miss -- waits for L2 hits
-// instead of Infinity-Cache hits.  The sets are balanced on the host from a per-level cost estimate.
-struct XcdPlan {
-    int n[8];
-    int lv[8][LNERF_MAX_LEVELS / 8 + 2];
-};
-
 template <typename TT, typename TO>
 __global__ void __launch_bounds__(256)
 k_grid_forward(const float *__restrict__ xyzs, float bound, const TT *__restrict__ table, GridMeta meta, int64_t m_host,
-               const int32_t *__restrict__ m_dev, int64_t level_stride, TO *__restrict__ feat, int variant,
-               int pair_loads, int dedup_max_res, XcdPlan plan) {
-#ifndef LNERF_EXPERIMENTS
-    variant = 0;   // (the XCD-pinned mappings 1 / 2 are compiled into experiment builds only)
-#endif
+               const int32_t *__restrict__ m_dev, int64_t level_stride, TO *__restrict__ feat, int pair_loads,
+               int dedup_max_res) {
     int64_t M = m_host;
     if (m_dev) { const int64_t md = *m_dev; M = md < M ? md : M; }
-    TileMap tm = tile_map(variant == 2 ? 0 : variant, meta.num_levels);
-    int n_lv = 1;
-    const int xcd = blockIdx.x & 7;
-    if (variant == 2) {
-        n_lv = plan.n[xcd];
-        tm.tile0 = blockIdx.x >> 3;
-        tm.tstep = gridDim.x >> 3;
-        tm.ok = true;
-    }
-    if (!tm.ok) return;
-  for (int li = 0; li < n_lv; ++li) {
-    const int l = variant == 2 ? plan.lv[xcd][li] : tm.level;
+    const TileMap tm = tile_map(0, meta.num_levels);
+    const int l = tm.level;
     const float scale = meta.scales[l];
     const uint32_t res = (uint32_t)meta.res[l];
     const uint32_t off = (uint32_t)meta.offsets[l];
@@ -175,7 +147,6 @@ k_grid_forward(const float *__restrict__ xyzs, float bound, const TT *__restrict
         }
         if (valid) Feat2<TO>::store(feat, (int64_t)l * level_stride + m, a0, a1);
     }
-  }
 }
 
 // Backward, variant 0: one (sample, level) per thread, 16 global float atomics each.
@@ -254,44 +225,19 @@ int lnerf_grid_encode_forward(const float *xyzs, float bound, const void *table,
     if (rc) return rc;
     LNERF_REQUIRE(m_host >= 0 && level_stride >= m_host, "grid_encode_forward: need 0 <= m_host <= level_stride");
     LNERF_REQUIRE(bound > 0.f, "grid_encode_forward: bound must be > 0");
-    LNERF_REQUIRE(variant >= 0 && variant <= 2, "grid_encode_forward: unknown variant %d", variant);
-#ifndef LNERF_EXPERIMENTS   // (XCD-pinned levels / XCD-owned level sets: measured no faster; experiment builds only)
-    LNERF_REQUIRE(variant == 0, "grid_encode_forward: variant %d is an experiment variant (build with -DLNERF_EXPERIMENTS)", variant);
-#endif
+    // (XCD-pinned levels and XCD-owned level sets, variants 1 / 2, were measured no faster and removed)
+    LNERF_REQUIRE(variant == 0, "grid_encode_forward: unknown variant %d", variant);
     LNERF_REQUIRE((table_dtype == LNERF_F32 || table_dtype == LNERF_BF16) &&
                       (feat_dtype == LNERF_F32 || feat_dtype == LNERF_BF16),
                   "grid_encode_forward: bad dtype tag");
     if (m_host == 0) return LNERF_OK;
     LNERF_REQUIRE(xyzs && table && feat, "grid_encode_forward: null pointer");
     dim3 grid;
-    launch_dims(variant == 2 ? 0 : variant, num_levels, m_host, grid);
-    XcdPlan plan;
-    memset(&plan, 0, sizeof(plan));
-    if (variant == 2) {
-        // longest-processing-time assignment of levels to XCDs; cost ~ cache lines a sample touches on the level
-        double cost[LNERF_MAX_LEVELS], load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        int order[LNERF_MAX_LEVELS];
-        for (int l = 0; l < num_levels; ++l) {
-            const double r = (double)res_host[l];
-            cost[l] = res_host[l] > g_gather_dedup_res ? 1.0 : (r < 64 ? 0.05 : r / (double)(g_gather_dedup_res > 0 ? g_gather_dedup_res : 512) * 0.9);
-            order[l] = l;
-        }
-        for (int a = 0; a < num_levels; ++a)
-            for (int b = a + 1; b < num_levels; ++b)
-                if (cost[order[b]] > cost[order[a]]) { const int t = order[a]; order[a] = order[b]; order[b] = t; }
-        for (int a = 0; a < num_levels; ++a) {
-            int best = -1;
-            for (int x = 0; x < 8; ++x)
-                if (plan.n[x] < LNERF_MAX_LEVELS / 8 + 2 && (best < 0 || load[x] < load[best])) best = x;
-            plan.lv[best][plan.n[best]++] = order[a];
-            load[best] += cost[order[a]];
-        }
-        grid = dim3((unsigned)(8 * g_gather_wgs_per_xcd), 1, 1);
-    }
+    launch_dims(0, num_levels, m_host, grid);
     hipStream_t s = as_stream(stream);
 #define LAUNCH_FWD(TT, TO)                                                                                         \
     hipLaunchKernelGGL((k_grid_forward<TT, TO>), grid, dim3(256), (size_t)g_gather_lds_pad, s, xyzs, bound, (const TT *)table, meta, m_host, \
-                       m_dev, level_stride, (TO *)feat, variant, g_gather_pairs, g_gather_dedup_res, plan)
+                       m_dev, level_stride, (TO *)feat, g_gather_pairs, g_gather_dedup_res)
     if (table_dtype == LNERF_F32 && feat_dtype == LNERF_F32) LAUNCH_FWD(float, float);
     else if (table_dtype == LNERF_F32) LAUNCH_FWD(float, uint16_t);
     else if (feat_dtype == LNERF_F32) LAUNCH_FWD(uint16_t, float);

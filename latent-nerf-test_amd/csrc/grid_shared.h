@@ -219,10 +219,7 @@ __device__ __forceinline__ RunInfo wave_cell_runs(uint32_t gx, uint32_t gy, uint
 // Every record has a fixed place that depends on the input only, every sum is an exact integer sum: the
 // result is bitwise reproducible for ANY input (round 2's layout reserved spans with global atomics and fell back to
 // float atomics when a bucket's region overflowed).
-#ifndef LNERF_BK_SHIFT
-#define LNERF_BK_SHIFT 12
-#endif
-constexpr int BK_SHIFT = LNERF_BK_SHIFT, BK_ROWS = 1 << BK_SHIFT;  // 4096 rows * 2 features * 8 B = 64 KiB of accumulators
+constexpr int BK_SHIFT = 12, BK_ROWS = 1 << BK_SHIFT;  // 4096 rows * 2 features * 8 B = 64 KiB of accumulators
 // threads (= samples) per binning tile: template parameter BIN_T of k_scatter_bin (256 or 512)
 constexpr int BK_MAX_PER_LEVEL = 256;                   // LDS counters per workgroup tile
 
@@ -248,16 +245,12 @@ struct Rec12 {
 // (native vector types: what __builtin_nontemporal_load / _store take)
 typedef float nt_f4 __attribute__((ext_vector_type(4)));
 typedef float nt_f2 __attribute__((ext_vector_type(2)));
-typedef uint32_t nt_u2 __attribute__((ext_vector_type(2)));
 typedef uint32_t nt_u4 __attribute__((ext_vector_type(4)));
-// LNERF_BIN_NT (bit mask): non-temporal policy in the binning pass -- 1: dfeat loads (read once per step),
-// 2: record stores (216 MB per frame: more than the Infinity Cache keeps until pass 2 reads them).  Measured together
-// with LNERF_REDUCE_NT below, same box, three interleaved rounds (profiles/r03_exp_scatter.jsonl, steps Q / R):
-// 2411 -> 2548 frames/s; bin 94.1 -> 86.5 us, reduce 124.5 -> 117.3, and the GATHER 78.5 -> 75.1 (its 24 MB table
-// is no longer pushed out of the caches by the scatter's streams between two frames)
-#ifndef LNERF_BIN_NT
-#define LNERF_BIN_NT 3
-#endif
+// The binning pass loads dfeat (read once per step) and stores the records (216 MB per frame: more than the Infinity
+// Cache keeps until pass 2 reads them) non-temporally.  Measured together with the reduce pass's non-temporal parameter
+// streams (grid.hip), same box, three interleaved rounds (profiles/r03_exp_scatter.jsonl, steps Q / R): 2411 -> 2548
+// frames/s; bin 94.1 -> 86.5 us, reduce 124.5 -> 117.3, and the GATHER 78.5 -> 75.1 (its 24 MB table is no longer pushed
+// out of the caches by the scatter's streams between two frames)
 struct alignas(8) Rec8 {
     uint32_t lo, hi;  // bits [0,12) row in bucket, [12,38) value 0, [38,64) value 1
     static constexpr bool kPacked = true;
@@ -286,10 +279,7 @@ __device__ __forceinline__ void pin_record(Rec12 &r) { asm volatile("" : "+v"(r.
 
 // Distance between two levels' maxima in uint32 words: one 128-byte line each (device-scope atomics that hit ONE line
 // are served one after the other at the memory side, whatever words they name).
-#ifndef LNERF_CUR_STRIDE
-#define LNERF_CUR_STRIDE 32
-#endif
-constexpr int CUR_STRIDE = LNERF_CUR_STRIDE;
+constexpr int CUR_STRIDE = 32;
 constexpr int ITEM_SAMPLES = 512;                 // samples per work item of pass 1 (= threads per workgroup)
 constexpr int ITEM_RECS = ITEM_SAMPLES * 8;       // record slots of an item's chunk
 // workspace header (bytes): [0, HDR_GMAX) level maxima (cleared before pass 1), then the item count of the last pass 1,
@@ -370,7 +360,7 @@ static __device__ unsigned long long g_wg_log[4 * 4096];
 
 
 // ---- tunables (lnerf_set_tuning; defined in grid.hip)
-extern int g_compact_max_res, g_gather_pairs, g_gather_wgs_per_xcd, g_gather_dedup_res, g_bin_per_cu, g_bin_wgs, g_skip_zero,
+extern int g_compact_max_res, g_gather_pairs, g_gather_dedup_res, g_bin_per_cu, g_bin_wgs, g_skip_zero,
     g_reduce_threads, g_scatter_groups, g_gather_lds_pad;
 
 static inline int fill_meta(const char *who, GridMeta &meta, int num_levels, int level_dim, const int32_t *offsets_host,

@@ -386,8 +386,7 @@ k_mlp_reduce_slabs(const float *__restrict__ slabs, int n_slabs, int out_dim, in
 
 int g_mlp_fwd_blocks = 768;   // 3 per CU: measured 24.5 us vs 28.1 (512) and 29.8 (1024) at the bench step
 int g_mlp_fwd_wps = 3;   // wavefronts per SIMD the bf16 forward is compiled for: 3 (768 workgroups = 3 per CU; the
-                         // register allocation is held at <= 168 so that they are co-resident), 2 or 4
-int g_mlp_bwd_variant = 0;  // bf16 backward: 0 = shared staging images (barriers), 1 / 2 = operand-swap form at 1 / 2 waves per SIMD
+                         // register allocation is held at <= 168 so that they are co-resident) or 2
 int g_mlp_bwd_blocks = MLP_BWD_MAX_BLOCKS;  // persistent workgroups of the backward (<= MLP_BWD_MAX_BLOCKS slabs)
 
 static int mlp_common_checks(const char *who, const void *feat, int feat_dtype, int64_t level_stride, const float *xyzs,
@@ -511,7 +510,7 @@ int lnerf_mlp_backward(const void *feat, int feat_dtype, int64_t level_stride, c
         int rc2 = fragments_ready ? LNERF_OK : launch_mlp_fragments_bf16(a, workspace, true, s);   // once per launch, not once per workgroup
         if (rc2) return rc2;
         a.frag_global = workspace;
-        rc2 = launch_mlp_backward_bf16(a, sigmas, dsigmas, drgbs, dfeat, slabs, (int)blocks, g_mlp_bwd_variant, s);
+        rc2 = launch_mlp_backward_bf16(a, sigmas, dsigmas, drgbs, dfeat, slabs, (int)blocks, s);
         if (rc2) return rc2;
     } else {
         hipLaunchKernelGGL(k_mlp_backward_f32, dim3((unsigned)blocks), dim3(256), 0, s, a, sigmas, dsigmas, drgbs,

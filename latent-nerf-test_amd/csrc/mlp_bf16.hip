@@ -100,7 +100,21 @@ __global__ void __launch_bounds__(256) k_mlp_fragment_maps(int out_dim, int32_t 
 // The fragments of a launch, built ONCE into global memory (k_mlp_build_fragments) and copied into LDS by every
 // workgroup with coalesced 16-byte loads: a workgroup building its own took 28 (forward) / 60 (backward) dependent
 // scattered weight loads per thread before its first tile -- a quarter of the kernels' time at ~6 tiles per workgroup.
-__device__ __forceinline__ void build_selectors(__bf16 *frag, int tid, int nthreads);
+// Behind the weight fragments the build appends three 0/1 SELECTION fragments, F_SELX .. F_SW.  They were the inputs'
+// transposes of the operand-swap backward, which was measured slower than the staging images and removed (DESIGN.md
+// section 4 H7); a backward launch's fragment build still writes all F_SW slots.
+constexpr int F_SELX = 30;   // [nt 0..1]  B[k = 8q+jj][j = c] = (8q + jj == 16nt + c)
+constexpr int F_SEL3 = 32;   //            B[k = 8q+jj][j = c] = (jj < 4 && 4q + jj == c)
+constexpr int F_SW = 33;
+static_assert((size_t)F_SW * 1024 <= MLP_FRAG_BYTES, "fragment cache");
+__device__ __forceinline__ void build_selectors(__bf16 *frag, int tid, int nthreads) {
+    for (int e = tid; e < (F_SW - F_SELX) * 512; e += nthreads) {
+        const int f = F_SELX + (e >> 9), l = (e >> 3) & 63, jj = e & 7;
+        const int q = l >> 4, c = l & 15;
+        const bool one = f < F_SEL3 ? (8 * q + jj == 16 * (f - F_SELX) + c) : (jj < 4 && 4 * q + jj == c);
+        frag[F_SELX * 512 + e] = (__bf16)(one ? 1.0f : 0.0f);
+    }
+}
 __global__ void __launch_bounds__(256) k_mlp_build_fragments(MlpArgs a, __bf16 *out, int n_frag) {
     build_fragments(a, out, n_frag < F_ALL ? n_frag : F_ALL, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
     if (n_frag > F_ALL) build_selectors(out, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
@@ -290,7 +304,8 @@ __device__ __forceinline__ void forward_hidden(const __bf16 *frag, const float *
 }
 
 // ------------------------------------------------------------------ forward
-// WPS: wavefronts per SIMD the register allocation aims at (4 = four workgroups per CU, 128 VGPRs)
+// WPS: wavefronts per SIMD the register allocation aims at, 3 or 2 (mlp_fwd_wps).  Four (128 VGPRs) spilled 396 bytes
+// per lane to scratch and was measured slower.
 template <int WPS>
 __global__ void __launch_bounds__(256, WPS)
 k_mlp_forward_bf16(MlpArgs a, float *__restrict__ sigmas, float *__restrict__ rgbs) {
@@ -655,296 +670,6 @@ k_mlp_backward_bf16(MlpArgs a, const float *__restrict__ sigmas, const float *__
     }
 }
 
-// ------------------------------------------------------------------ backward, operand-swap form
-// The weight gradients contract over SAMPLES, so their MFMA operands need the feature on the lane and samples in the
-// registers -- the transpose of what the sample-on-the-lane chain holds.  Instead of transposing through LDS, every
-// activation / pre-activation gradient the weight gradients need is computed a second time with the two MFMA operands
-// SWAPPED: A[i][k] and B[k][j] have the same lane map (index on the lane, k in the registers), so
-// MFMA(W-fragment, X^T-fragment) = Z^T (feature rows, sample columns: the chain) and MFMA(X^T-fragment, W-fragment) = Z
-// (sample rows 4q+r in the registers, feature column c on the lane) use the very same registers.  Two 16-sample
-// tiles of Z give 8 samples per lane = one k-step of dW = dZ^T (x) H (the k-slot -> sample map is the same for both
-// operands, which is all a contraction needs).  +54 MFMAs per 32 samples (a few us chip-wide), and in exchange: no
-// staging images, no transposing reads, no LDS round trips and NO BARRIER in the loop -- a wave carries its own 32
-// samples from load to store; the next step's inputs are requested before the current step is computed.
-// X and dZ3 (inputs, no weight to swap with) are transposed exactly by MFMAs against 0/1 selection fragments.
-constexpr int F_SELX = 30;   // [nt 0..1]  B[k = 8q+jj][j = c] = (8q + jj == 16nt + c)
-constexpr int F_SEL3 = 32;   //            B[k = 8q+jj][j = c] = (jj < 4 && 4q + jj == c)
-constexpr int F_SW = 33;
-constexpr int SW_TILES = 31;                                     // dW2 16 | dW1 8 | dW3 4 | biases 3 (db2 4, db1 4, db3 1 floats)
-static_assert((size_t)F_SW * 1024 <= MLP_FRAG_BYTES, "fragment cache");
-static_assert(SW_TILES * 1024 <= F_SW * 1024, "final reduction reuses the fragment area");
-
-// the three selection fragments (appended to the weight fragments by k_mlp_build_fragments)
-__device__ __forceinline__ void build_selectors(__bf16 *frag, int tid, int nthreads) {
-    for (int e = tid; e < (F_SW - F_SELX) * 512; e += nthreads) {
-        const int f = F_SELX + (e >> 9), l = (e >> 3) & 63, jj = e & 7;
-        const int q = l >> 4, c = l & 15;
-        const bool one = f < F_SEL3 ? (8 * q + jj == 16 * (f - F_SELX) + c) : (jj < 4 && 4 * q + jj == c);
-        frag[F_SELX * 512 + e] = (__bf16)(one ? 1.0f : 0.0f);
-    }
-}
-
-// (operand-swap form of the backward: measured slower than the default at either occupancy, spills at two waves per
-// SIMD -- DESIGN.md section 4 H7; compiled only into experiment builds: -DLNERF_EXPERIMENTS)
-#ifdef LNERF_EXPERIMENTS
-template <int WPS>
-__global__ void __launch_bounds__(256, WPS)
-k_mlp_backward_bf16_sw(MlpArgs a, const float *__restrict__ sigmas, const float *__restrict__ dsigmas,
-                       const float *__restrict__ drgbs, float *__restrict__ dfeat, float *__restrict__ slabs) {
-    __shared__ __attribute__((aligned(16))) __bf16 frag[F_SW * 512];
-    __shared__ float sB1[MLP_HID], sB2[MLP_HID];
-    int64_t M = a.m_host;
-    if (a.m_dev) { const int64_t md = *a.m_dev; M = md < M ? md : M; }
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, q = lane >> 4, c = lane & 15;
-    fetch_fragments(a, frag, F_SW, tid, 256);
-    if (tid < MLP_HID) { sB1[tid] = a.b1[tid]; sB2[tid] = a.b2[tid]; }
-    __syncthreads();
-    const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
-    f32x4 gW2[16], gW1[8], gW3[4];
-    float gb2[4], gb1[4], gb3 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) gW2[i] = zero4;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) gW1[i] = zero4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { gW3[i] = zero4; gb2[i] = 0.f; gb1[i] = 0.f; }
-
-    const int64_t stride = (int64_t)gridDim.x * 4 * 32;
-    int64_t m0 = ((int64_t)blockIdx.x * 4 + w) * 32;
-    Upstream<2> up = load_upstream<2>(a, sigmas, dsigmas, drgbs, m0, M, q, c);
-    bf16x8 xB[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) xB[t] = load_x(a, clamp_row(m0 + 16 * t + c, M), q);
-
-    while (m0 < M) {   // wave-uniform
-        asm volatile("" ::: "memory");   // the weight fragments are re-read from LDS every step, not hoisted into ~130 registers
-        const int64_t m1 = m0 + stride;
-        const Upstream<2> up_n = load_upstream<2>(a, sigmas, dsigmas, drgbs, m1, M, q, c);
-        bf16x8 xB_n[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) xB_n[t] = load_x(a, clamp_row(m1 + 16 * t + c, M), q);
-
-        bf16x8 d3B[2];
-        bool live = false;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) live = upstream_fragment(up.v[t], up.sg[t], q, d3B[t]) || live;
-        if (!__any(live ? 1 : 0)) {
-            // 32 samples whose upstream gradient is exactly zero (rays past their termination point: the compositing
-            // backward writes zeros there) contribute nothing to any gradient: dfeat = 0, done
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const int64_t m = m0 + 16 * t + c;
-                if (m < M) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        reinterpret_cast<float2 *>(dfeat)[(int64_t)(4 * q + k) * a.level_stride + m] = make_float2(0.f, 0.f);
-                }
-            }
-        } else {
-            bf16x8 h1B[2][2], h2B[2][2], H1f[4], H2f[4], dZf[4];
-            // ---- layer 1, both forms (the fragment of W1 rows 16mt.. is A of the chain and B of the swap)
-            {
-                f32x4 acc[4][2];
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt) {
-                    const bf16x8 wf = ld_frag(frag, F_W1A + mt, lane);
-                    const f32x4 b = ld_bias4(sB1, 16 * mt + 4 * q);
-                    acc[mt][0] = MFMA32(wf, xB[0], b);
-                    acc[mt][1] = MFMA32(wf, xB[1], b);
-                    const float bc = sB1[16 * mt + c];
-                    const f32x4 bT = (f32x4){bc, bc, bc, bc};
-                    H1f[mt] = pack_relu_pk(MFMA32(xB[0], wf, bT), MFMA32(xB[1], wf, bT));
-                }
-#pragma unroll
-                for (int s = 0; s < 2; ++s)
-#pragma unroll
-                    for (int t = 0; t < 2; ++t) h1B[s][t] = pack_relu_pk(acc[2 * s][t], acc[2 * s + 1][t]);
-            }
-            // ---- layer 2, both forms
-            {
-                f32x4 acc[4][2];
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt) {
-                    const f32x4 b = ld_bias4(sB2, 16 * mt + 4 * q);
-                    const float bc = sB2[16 * mt + c];
-                    f32x4 t0 = (f32x4){bc, bc, bc, bc}, t1 = t0;
-                    acc[mt][0] = b;
-                    acc[mt][1] = b;
-#pragma unroll
-                    for (int s = 0; s < 2; ++s) {
-                        const bf16x8 wf = ld_frag(frag, F_W2A + 2 * mt + s, lane);
-                        acc[mt][0] = MFMA32(wf, h1B[s][0], acc[mt][0]);
-                        acc[mt][1] = MFMA32(wf, h1B[s][1], acc[mt][1]);
-                        t0 = MFMA32(h1B[s][0], wf, t0);
-                        t1 = MFMA32(h1B[s][1], wf, t1);
-                    }
-                    H2f[mt] = pack_relu_pk(t0, t1);
-                }
-#pragma unroll
-                for (int s = 0; s < 2; ++s)
-#pragma unroll
-                    for (int t = 0; t < 2; ++t) h2B[s][t] = pack_relu_pk(acc[2 * s][t], acc[2 * s + 1][t]);
-            }
-            // ---- dW3 += dZ3^T (x) H2 ; db3
-            {
-                const bf16x8 sel = ld_frag(frag, F_SEL3, lane);
-                const bf16x8 d3f = pack_plain_pk(MFMA32(d3B[0], sel, zero4), MFMA32(d3B[1], sel, zero4));
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) gW3[nt] = MFMA32(d3f, H2f[nt], gW3[nt]);
-                gb3 = sum8(d3f, gb3);
-            }
-            // ---- dA2 = dZ3 W3, both forms ; dZ2 = dA2 masked by H2 > 0 ; dW2 += dZ2^T (x) H1 ; db2
-            bf16x8 dzB[2][2];
-            {
-                f32x4 acc[4][2];
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt) {
-                    const bf16x8 wf = ld_frag(frag, F_W3T + mt, lane);
-                    acc[mt][0] = MFMA32(wf, d3B[0], zero4);
-                    acc[mt][1] = MFMA32(wf, d3B[1], zero4);
-                    dZf[mt] = pack_masked_pk(MFMA32(d3B[0], wf, zero4), MFMA32(d3B[1], wf, zero4), H2f[mt]);
-                }
-#pragma unroll
-                for (int s = 0; s < 2; ++s)
-#pragma unroll
-                    for (int t = 0; t < 2; ++t) dzB[s][t] = pack_masked_pk(acc[2 * s][t], acc[2 * s + 1][t], h2B[s][t]);
-            }
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) gW2[4 * mt + nt] = MFMA32(dZf[mt], H1f[nt], gW2[4 * mt + nt]);
-                gb2[mt] = sum8(dZf[mt], gb2[mt]);
-            }
-            // ---- dA1 = dZ2 W2, both forms ; dZ1 = dA1 masked by H1 > 0   (dzB is overwritten by dZ1)
-            {
-                f32x4 acc[4][2];
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt) {
-                    f32x4 t0 = zero4, t1 = zero4;
-                    acc[mt][0] = acc[mt][1] = zero4;
-#pragma unroll
-                    for (int s = 0; s < 2; ++s) {
-                        const bf16x8 wf = ld_frag(frag, F_W2T + 2 * mt + s, lane);
-                        acc[mt][0] = MFMA32(wf, dzB[s][0], acc[mt][0]);
-                        acc[mt][1] = MFMA32(wf, dzB[s][1], acc[mt][1]);
-                        t0 = MFMA32(dzB[s][0], wf, t0);
-                        t1 = MFMA32(dzB[s][1], wf, t1);
-                    }
-                    dZf[mt] = pack_masked_pk(t0, t1, H1f[mt]);
-                }
-#pragma unroll
-                for (int s = 0; s < 2; ++s)
-#pragma unroll
-                    for (int t = 0; t < 2; ++t) dzB[s][t] = pack_masked_pk(acc[2 * s][t], acc[2 * s + 1][t], h1B[s][t]);
-            }
-            // ---- dW1 += dZ1^T (x) X ; db1
-            {
-                bf16x8 Xf[2];
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt) {
-                    const bf16x8 sel = ld_frag(frag, F_SELX + nt, lane);
-                    Xf[nt] = pack_plain_pk(MFMA32(xB[0], sel, zero4), MFMA32(xB[1], sel, zero4));
-                }
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt) {
-#pragma unroll
-                    for (int nt = 0; nt < 2; ++nt) gW1[2 * mt + nt] = MFMA32(dZf[mt], Xf[nt], gW1[2 * mt + nt]);
-                    gb1[mt] = sum8(dZf[mt], gb1[mt]);
-                }
-            }
-            // ---- dX = W1^T dZ1 -> dfeat (level-major f32): lane holds features 16mt + 4q + r of its sample
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) {
-                f32x4 ax[2] = {zero4, zero4};
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    const bf16x8 wf = ld_frag(frag, F_W1T + 2 * mt + s, lane);
-                    ax[0] = MFMA32(wf, dzB[s][0], ax[0]);
-                    ax[1] = MFMA32(wf, dzB[s][1], ax[1]);
-                }
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    const int64_t m = m0 + 16 * t + c;
-                    if (m < M) {
-                        const int lv = 8 * mt + 2 * q;  // features 16mt+4q+{0,1} = level lv, {2,3} = level lv+1
-                        reinterpret_cast<float2 *>(dfeat)[(int64_t)lv * a.level_stride + m] = make_float2(ax[t][0], ax[t][1]);
-                        reinterpret_cast<float2 *>(dfeat)[(int64_t)(lv + 1) * a.level_stride + m] =
-                            make_float2(ax[t][2], ax[t][3]);
-                    }
-                }
-            }
-        }
-        up = up_n;
-        xB[0] = xB_n[0];
-        xB[1] = xB_n[1];
-        m0 = m1;
-    }
-
-    // ---- bias partials: a lane holds feature c of the samples of its q group -> sum the four groups
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        gb2[i] += __shfl_xor(gb2[i], 16);
-        gb2[i] += __shfl_xor(gb2[i], 32);
-        gb1[i] += __shfl_xor(gb1[i], 16);
-        gb1[i] += __shfl_xor(gb1[i], 32);
-    }
-    gb3 += __shfl_xor(gb3, 16);
-    gb3 += __shfl_xor(gb3, 32);
-    f32x4 gB[3] = {(f32x4){gb2[0], gb2[1], gb2[2], gb2[3]}, (f32x4){gb1[0], gb1[1], gb1[2], gb1[3]},
-                   (f32x4){gb3, 0.f, 0.f, 0.f}};
-    // ---- sum the four waves' tiles in the fixed order 0 + 1 + 2 + 3 (through the fragment area, now idle)
-    f32x4 *red = reinterpret_cast<f32x4 *>(frag);
-    for (int src = 1; src < 4; ++src) {
-        __syncthreads();
-        if (w == src) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) red[i * 64 + lane] = gW2[i];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) red[(16 + i) * 64 + lane] = gW1[i];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) red[(24 + i) * 64 + lane] = gW3[i];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) red[(28 + i) * 64 + lane] = gB[i];
-        }
-        __syncthreads();
-        if (w == 0) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) gW2[i] += red[i * 64 + lane];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) gW1[i] += red[(16 + i) * 64 + lane];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) gW3[i] += red[(24 + i) * 64 + lane];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) gB[i] += red[(28 + i) * 64 + lane];
-        }
-    }
-    if (w != 0) return;
-    float *slab = slabs + (int64_t)blockIdx.x * MLP_SLAB;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-            const int o = 16 * mt + 4 * q + r;  // row of dW2 / dW1
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) slab[MLP_SL_W2 + o * MLP_HID + 16 * nt + c] = gW2[4 * mt + nt][r];
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) slab[MLP_SL_W1 + o * MLP_IN + 16 * nt + c] = gW1[2 * mt + nt][r];
-        }
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) slab[MLP_SL_W3 + (4 * q + r) * MLP_HID + 16 * nt + c] = gW3[nt][r];
-    }
-    // biases: lane c (of q group 0) holds db[16 mt + c]
-    if (q == 0) {
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-            slab[MLP_SL_B2 + 16 * mt + c] = gB[0][mt];
-            slab[MLP_SL_B1 + 16 * mt + c] = gB[1][mt];
-        }
-        slab[MLP_SL_B3 + c] = gB[2][0];
-    }
-}
-#endif  // LNERF_EXPERIMENTS
-
 }  // namespace lnerf
 
 namespace lnerf {
@@ -978,10 +703,6 @@ int launch_mlp_fragments_bf16(const MlpArgs &a, void *frag_out, bool backward_to
 }
 
 int launch_mlp_forward_bf16(const MlpArgs &a, float *sigmas, float *rgbs, int blocks, int wps, hipStream_t stream) {
-#ifdef LNERF_EXPERIMENTS   // (four waves per SIMD: 128 registers, 396 bytes of scratch per lane -- measured slower)
-    if (wps >= 4) hipLaunchKernelGGL(k_mlp_forward_bf16<4>, dim3((unsigned)blocks), dim3(256), 0, stream, a, sigmas, rgbs);
-    else
-#endif
     if (wps >= 3) hipLaunchKernelGGL(k_mlp_forward_bf16<3>, dim3((unsigned)blocks), dim3(256), 0, stream, a, sigmas, rgbs);
     else hipLaunchKernelGGL(k_mlp_forward_bf16<2>, dim3((unsigned)blocks), dim3(256), 0, stream, a, sigmas, rgbs);
     LNERF_CHECK_LAUNCH("mlp_forward(bf16)");
@@ -989,22 +710,7 @@ int launch_mlp_forward_bf16(const MlpArgs &a, float *sigmas, float *rgbs, int bl
 }
 
 int launch_mlp_backward_bf16(const MlpArgs &a, const float *sigmas, const float *dsigmas, const float *drgbs,
-                             float *dfeat, float *slabs, int blocks, int variant, hipStream_t stream) {
-#ifdef LNERF_EXPERIMENTS
-    if (variant == 2) {
-        hipLaunchKernelGGL(k_mlp_backward_bf16_sw<2>, dim3((unsigned)blocks), dim3(256), 0, stream, a, sigmas, dsigmas,
-                           drgbs, dfeat, slabs);
-        LNERF_CHECK_LAUNCH("mlp_backward(bf16, operand swap)");
-        return LNERF_OK;
-    }
-    if (variant == 1) {
-        hipLaunchKernelGGL(k_mlp_backward_bf16_sw<1>, dim3((unsigned)blocks), dim3(256), 0, stream, a, sigmas, dsigmas,
-                           drgbs, dfeat, slabs);
-        LNERF_CHECK_LAUNCH("mlp_backward(bf16, operand swap)");
-        return LNERF_OK;
-    }
-#endif
-    (void)variant;
+                             float *dfeat, float *slabs, int blocks, hipStream_t stream) {
     hipLaunchKernelGGL((k_mlp_backward_bf16<4, 2>), dim3((unsigned)blocks), dim3(256), 0, stream, a, sigmas, dsigmas,
                        drgbs, dfeat, slabs);
     LNERF_CHECK_LAUNCH("mlp_backward(bf16)");

@@ -39,7 +39,7 @@ int launch_mlp_fragments_bf16(const MlpArgs &a, void *frag_out, bool backward_to
 int launch_mlp_fragment_maps(int out_dim, int32_t *m1, int32_t *m2, int32_t *m3, hipStream_t stream);
 int launch_mlp_forward_bf16(const MlpArgs &a, float *sigmas, float *rgbs, int blocks, int wps, hipStream_t stream);
 int launch_mlp_backward_bf16(const MlpArgs &a, const float *sigmas, const float *dsigmas, const float *drgbs,
-                             float *dfeat, float *slabs, int blocks, int variant, hipStream_t stream);
+                             float *dfeat, float *slabs, int blocks, hipStream_t stream);
 
 #ifdef LNERF_STAMPS
 int mlp_stamps_read(unsigned long long *out32);   // diagnostic builds only (mlp_bf16.hip)

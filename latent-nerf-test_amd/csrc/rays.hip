@@ -177,10 +177,7 @@ __device__ __forceinline__ float march_noise(const MarchNoise &nz, int64_t n) {
 // Totals of a training march from the per-ray counts, by ONE wavefront (every lane must call it): what k_march_scan
 // writes to `counter`, by the same rule -- a ray is dropped when the samples of all rays before it (dropped or not) plus
 // its own exceed the capacity.  64 rays per round: inclusive wave scan + running carry.  Advances the jitter counter.
-#ifndef LNERF_MARCH_FUSED_MAX_RAYS
-#define LNERF_MARCH_FUSED_MAX_RAYS 8192   // above: the per-wavefront prefix (N^2 / 2 loads) loses to the scan kernel
-#endif
-constexpr int64_t MARCH_FUSED_MAX_RAYS = LNERF_MARCH_FUSED_MAX_RAYS;
+constexpr int64_t MARCH_FUSED_MAX_RAYS = 8192;   // above: the per-wavefront prefix (N^2 / 2 loads) loses to the scan kernel
 // counter[3]: running maximum, over the marches since the caller last zeroed it, of  M | (rays dropped ? 2^30 : 0)  --
 // what a training loop that sizes its sample buffers from observed marches reads back once in a while
 // (NeRFRenderer.update_sample_budget), kept by the ONE thread that writes the totals: no launch, no atomics
@@ -227,10 +224,7 @@ __device__ __forceinline__ void march_totals(const int32_t *__restrict__ cnt, in
 }
 
 // chunks of 64 lattice points whose occupancy bytes one round of the uniform-step march requests together
-#ifndef LNERF_MARCH_CHUNKS
-#define LNERF_MARCH_CHUNKS 4
-#endif
-constexpr int MARCH_CHUNKS = LNERF_MARCH_CHUNKS;
+constexpr int MARCH_CHUNKS = 4;
 // One wavefront per ray.  Each iteration tests 64 consecutive lattice points of the ray;
 // ballot + popcount gives the count (pass 1) or, with mbcnt, each sample's slot (pass 2).
 template <bool WRITE, bool UNIFORM_DT>

@@ -66,7 +66,8 @@ class RenderConfig:
     # 64-byte-line blocks are cut for 4-byte rows; measured: gather 75 -> 67 us at equal or better training error,
     # profiles/r04_ab_layout.jsonl) and "hash" with the f32 parity configuration; a bare RenderConfig means "hash"
     gridtype: str = "auto"
-    # workgroup -> (level, tile) mapping of the gather/scatter: 0 = level on grid.y (measured 1.8x faster), 1 = XCD-pinned levels
+    # workgroup -> (level, tile) mapping of the gather: 0 = level on grid.y, the only one built (XCD-pinned levels measured
+    # 1.8x slower and were removed)
     gather_variant: int = 0
     # hash-grid backward: 0/1 = global float atomics, 2 = two-pass bucketed scatter (LDS reduction, exact f32
     # records), 3 = the same with packed 8-byte records (values rounded to 17 mantissa bits),

@@ -183,7 +183,7 @@ def test_cross_workgroup_handoffs_are_scoped_accesses():
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
 def test_no_kernel_of_the_product_build_spills():
     """Scratch traffic shares the vector-memory queue with the loads a streaming loop waits for: a spilling kernel is a
-    slow kernel on this path.  The product build (no -DLNERF_EXPERIMENTS) compiles every kernel without scratch."""
+    slow kernel on this path.  Every kernel of the library compiles without scratch."""
     import importlib.util
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     spec = importlib.util.spec_from_file_location("resource_usage", os.path.join(root, "tools", "resource_usage.py"))

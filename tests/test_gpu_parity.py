@@ -216,7 +216,6 @@ def _rand_points(M, bound=1.0, seed=0):
 @pytest.mark.parametrize("cfg", ["small", "full"])
 def test_grid_encode_forward_backward(dev, variant, cfg):
     from src.latent_nerf.models import encoding as E
-    from src.latent_nerf.raymarching import backend as B
     if cfg == "small":
         kw = dict(num_levels=16, base_resolution=4, desired_resolution=128, log2_hashmap_size=12)
         M = 3001
@@ -235,9 +234,7 @@ def test_grid_encode_forward_backward(dev, variant, cfg):
     ref = O.grid_encode((x + 1.0) / 2.0, tref, lv)                      # [M, 32]
     stride = M + 37                                                      # level_stride > M on purpose
     m_dev = torch.tensor([M], dtype=torch.int32, device=dev)
-    # (gather mapping 1 -- levels pinned to XCDs -- exists in experiment builds only)
-    gv = min(variant, 1) if "experiments" in B.get_lib().lnerf_build_info().decode() else 0
-    feat = E.grid_encode_forward(x.to(dev), 1.0, table.to(dev), levels, stride, m_dev, stride, variant=gv)
+    feat = E.grid_encode_forward(x.to(dev), 1.0, table.to(dev), levels, stride, m_dev, stride, variant=0)
     got = feat[:, :M, :].permute(1, 0, 2).reshape(M, 32)
     _close(got, ref, 1e-4, 1e-6, "features")
     # backward (scatter-add) vs autograd of the oracle
@@ -528,43 +525,6 @@ def test_occ_sample_matches_oracle(dev):
             occ = int((level > 0).sum())
             assert len(set(ref_idx[n_rand:].tolist())) == min(occ, n_rand)    # fewer occupied cells than draws: ALL of them
             assert 0.2 < float((ref_idx[:n_rand].float() / G3).mean()) < 0.8
-
-
-def test_mlp_backward_operand_swap_variant_matches_the_default(dev):
-    """`mlp_bwd_variant` 1 (operand-swap form: the activations the weight gradients need are recomputed with the two
-    MFMA operands swapped, no LDS transposes, no barriers) against the default backward on the same inputs: the data
-    chain is the same arithmetic (dfeat bit-identical), the weight gradients differ by summation order only."""
-    from src.latent_nerf.models.network_grid import _SigmaLatentMLP
-    from src.latent_nerf.raymarching import backend as B
-    if "experiments" not in B.get_lib().lnerf_build_info().decode():
-        # the product build leaves the rejected variants out: asking for one must fail loudly
-        with pytest.raises(B.LnerfError, match="experiment variant"):
-            B.call("lnerf_set_tuning", b"mlp_bwd_variant", 1)
-        pytest.skip("operand-swap backward: experiment builds only (LNERF_EXPERIMENTS=1 python latent-nerf-test_amd/build.py)")
-    M = 70001
-    feat, xyz, p = _mlp_inputs(M, seed=5)
-    lm0 = feat.reshape(M, 16, 2).permute(1, 0, 2).contiguous().to(dev).to(torch.bfloat16)
-    m_dev = torch.tensor([M], dtype=torch.int32, device=dev)
-    gs, gc = (torch.randn(M) * 0.1).to(dev), torch.randn(M, 4).to(dev)
-    gs[1000:5000] = 0      # a stretch of dead samples (skipped steps)
-    gc[1000:5000] = 0
-    res = {}
-    try:
-        for var in (0, 1):
-            B.call("lnerf_set_tuning", b"mlp_bwd_variant", var)
-            lm = lm0.clone().requires_grad_()
-            pg = {k: v.clone().to(dev).requires_grad_() for k, v in p.items()}
-            sig, rgb = _SigmaLatentMLP.apply(lm, xyz.to(dev), pg["w1"], pg["b1"], pg["w2"], pg["b2"], pg["w3"], pg["b3"],
-                                             M, m_dev, M, 5.0, 0.2, B.BF16, None)
-            torch.autograd.backward([sig, rgb], [gs, gc])
-            res[var] = (lm.grad.clone(), {k: pg[k].grad.clone() for k in pg})
-    finally:
-        B.call("lnerf_set_tuning", b"mlp_bwd_variant", 0)
-    assert torch.equal(res[0][0], res[1][0])
-    assert float(res[0][0][:, 1000:5000].abs().max()) == 0.0
-    for k in res[0][1]:
-        a, b = res[0][1][k], res[1][1][k]
-        assert float((a - b).abs().max()) <= 1e-5 * float(a.abs().max()) + 1e-9, k
 
 
 def test_mlp_trunc_exp_clamp_and_rgb_mode_shapes(dev):

@@ -72,16 +72,6 @@ def main():
                 return f
             fns["f32tab_bf16out_dedup%d_pairs%d" % (dd, pl)] = mk(table, bf16o)
             fns["bf16tab_bf16out_dedup%d_pairs%d" % (dd, pl)] = mk(table_bf, bf16o)
-        for wg in (64, 128, 256, 512):
-            def mk2(tab, out, wg=wg):
-                def f():
-                    B.call("lnerf_set_tuning", b"gather_dedup_max_res", 512)
-                    B.call("lnerf_set_tuning", b"gather_pair_loads", 1)
-                    B.call("lnerf_set_tuning", b"gather_wgs_per_xcd", wg)
-                    E.grid_encode_forward(xyzs, 1.0, tab, levels, cap, m_dev, cap, out, variant=2)
-                return f
-            fns["bf16tab_bf16out_xcdsets_wg%d" % wg] = mk2(table_bf, bf16o)
-            fns["f32tab_bf16out_xcdsets_wg%d" % wg] = mk2(table, bf16o)
         t = timed(fns)
         B.call("lnerf_set_tuning", b"gather_pair_loads", 1)
         res["gather_ms(median,min)"] = t
@@ -181,7 +171,7 @@ def main():
         from src.latent_nerf.models.network_grid import _SigmaLatentMLP
         featb = (torch.randn(16, cap, 2, device=dev) * 0.3).to(torch.bfloat16)
         fns = {}
-        for wps, nb in ((2, 512), (2, 768), (2, 1024), (4, 1024), (2, 1280)):
+        for wps, nb in ((2, 512), (2, 768), (2, 1024), (2, 1280)):
             def f(n=nb, wps=wps):
                 B.call("lnerf_set_tuning", b"mlp_fwd_blocks", n)
                 B.call("lnerf_set_tuning", b"mlp_fwd_wps", wps)
@@ -218,28 +208,14 @@ def main():
                                                          (netb.w1, netb.b1, netb.w2, netb.b2, netb.w3, netb.b3)]
         for i, t_ in enumerate(mine):
             args[18 + i] = t_.data_ptr()
-        Mb = int(out3["counter"][0])
         fns = {}
-        for var, nb in ((0, 512), (0, 448), (1, 256)):
-            def f(nb=nb, var=var):
-                B.call("lnerf_set_tuning", b"mlp_bwd_variant", var)
+        for nb in (512, 448):
+            def f(nb=nb):
                 B.call("lnerf_set_tuning", b"mlp_bwd_blocks", nb)
                 B.call("lnerf_mlp_backward", *args)
-            fns["mlp_bwd_bf16_v%d_blocks%d" % (var, nb)] = f
-        # the variants against each other: dfeat and the six weight gradients of the same inputs
-        outs = {}
-        for k, f in fns.items():
-            for t_ in mine:
-                t_.fill_(float("nan"))
-            f()
-            torch.cuda.synchronize()
-            outs[k] = [mine[0][:, :Mb].clone()] + [t_.clone() for t_ in mine[1:]]
-        base = outs["mlp_bwd_bf16_v0_blocks512"]
-        res["mlp_bwd_vs_v0(max_abs_diff / max_abs)"] = {
-            k: [[float((a_ - b_).abs().max()), float(b_.abs().max())] for a_, b_ in zip(v, base)] for k, v in outs.items()}
+            fns["mlp_bwd_bf16_blocks%d" % nb] = f
         res["mlp_bwd_ms(median,min)"] = timed(fns)
         B.call("lnerf_set_tuning", b"mlp_bwd_blocks", 512)
-        B.call("lnerf_set_tuning", b"mlp_bwd_variant", 0)
 
     print(json.dumps(res))
 

@@ -1,15 +1,24 @@
 #!/bin/bash
 # Diagnostic build of the library with phase stamps in the binning pass (-DLNERF_STAMPS); never the product library.
+# Compiles the sources of latent-nerf-test_amd/build.py with its flags.
 set -eu
 R=$(cd "$(dirname "$0")/.." && pwd)
 C=$R/latent-nerf-test_amd/csrc
 O=$R/latent-nerf-test_amd/lib/stamps
+HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 mkdir -p $O
-FLAGS="-O3 --offload-arch=gfx950 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function -DLNERF_STAMPS -DLNERF_BUILD_TAG=\"stamps\""
-for f in rays grid_gather grid_bin grid mlp mlp_bf16 composite optim bg mesh raster guidance; do
-  /opt/rocm/bin/hipcc $FLAGS -c $C/$f.hip -o $O/$f.o &
+build_list() { (cd $R/latent-nerf-test_amd && python3 -B -c "import build; print(' '.join(build.$1))"); }
+read -r -a SOURCES <<< "$(build_list SOURCES)"
+read -r -a FLAGS <<< "$(build_list FLAGS)"
+FLAGS+=(-DLNERF_STAMPS '-DLNERF_BUILD_TAG="stamps"')
+objs=() pids=()
+for f in "${SOURCES[@]}"; do
+  flags=()
+  for fl in "${FLAGS[@]}"; do [[ $f == *.cc && $fl == --offload-arch=* ]] || flags+=("$fl"); done   # (host-only, as build.py)
+  objs+=("$O/${f%.*}.o")
+  $HIPCC "${flags[@]}" -c "$C/$f" -o "${objs[-1]}" &
+  pids+=($!)
 done
-g++ -O2 -std=c++17 -fPIC -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ -DLNERF_BUILD_TAG=\"stamps\" -c $C/api.cc -o $O/api.o 2>/dev/null || /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -DLNERF_BUILD_TAG=\"stamps\" -c $C/api.cc -o $O/api.o
-wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $R/latent-nerf-test_amd/lib/liblnerf_hip_stamps.so $O/*.o
+for p in "${pids[@]}"; do wait $p; done
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o $R/latent-nerf-test_amd/lib/liblnerf_hip_stamps.so "${objs[@]}"
 echo built $R/latent-nerf-test_amd/lib/liblnerf_hip_stamps.so

@@ -507,6 +507,45 @@ int lnerf_marching_cubes(const float *vol, int nx, int ny, int nz, float iso, fl
                          float *verts, float *normals, int64_t max_verts, int32_t *faces, int64_t max_faces,
                          int64_t *counts_dev, lnerf_stream_t stream);
 
+/* ---- texture baking over a UV atlas: NeRFRenderer.bake_texture's kernels (csrc/uvbake.hip).  Additive to ABI 7.
+ * lnerf_uv_raster: which texel of an R x R texture each face covers, and the surface point there.
+ *   verts [n_verts,3] f32, faces [n_faces,3] int32 (into verts), vt [n_vt,2] f32, ft [n_faces,3] int32 (into vt);
+ *   1 <= R <= LNERF_UV_MAX_RES.
+ *   Texel (row i, column j) of a [C,R,R] texture has its centre at u = (j + 0.5) / R, v = 1 - (i + 0.5) / R: the
+ *   convention of lnerf_texture_map_forward (grid_sample, align_corners=False, on (u, 1 - v)).  In pixel space a UV
+ *   corner is X = u * R, Y = (1 - v) * R and the texel centre is p = (j + 0.5, i + 0.5).  All f32, no fused multiply-adds.
+ *   E_ab(p) = (X_b - X_a) * (p_y - Y_a) - (Y_b - Y_a) * (p_x - X_a);  area = E_01(corner 2).
+ *   Candidates of a face: columns max(0, floor(min X) - 1) .. min(R - 1, floor(max X) + 1), rows likewise from Y (none
+ *   when that range is empty, or the area is NaN, infinite or 0).  A candidate texel is COVERED iff E_12, E_20 and E_01
+ *   at p each have the sign of the area or are 0 (inclusive edges, both windings).  Where several faces cover a
+ *   texel the largest face index wins.  Barycentrics b_k = E_opposite(p) / area (b0 = E_12 / area, b1 = E_20 / area,
+ *   b2 = E_01 / area), surface point = b0 * P0 + b1 * P1 + b2 * P2 evaluated left to right.  Fully deterministic.
+ * Outputs: texel_face [R*R] int32 (winning face, -1 = none); the P covered texels in ascending linear order (i*R + j):
+ *   texel_idx [P] int32 and pos [P,3] f32 (entries at index >= max_texels are not written).
+ * counts_dev int64[3]: {candidate items, faces with an index out of range, P}.  A face with an index out of range
+ *   covers nothing and reads no vertex through it.  Scratch: lnerf_uv_raster_scratch_bytes() (16-byte aligned; 0 =
+ *   arguments out of range).  `stages`, run in this order, each from the scratch state of the previous one (same inputs):
+ *   LNERF_UV_ITEMS  the per-face candidate counts and their prefix -> counts[0], counts[1];
+ *   LNERF_UV_COVER  texel_face, then counts[2]; n_items: the item total of counts[0] or any upper bound of it (one lane
+ *                   per item; launches of at most 2^30 items each);
+ *   LNERF_UV_EMIT   texel_idx and pos. */
+#define LNERF_UV_ITEMS 1
+#define LNERF_UV_COVER 2
+#define LNERF_UV_EMIT 4
+#define LNERF_UV_MAX_RES 8192
+size_t lnerf_uv_raster_scratch_bytes(int n_faces, int R);
+int lnerf_uv_raster(const float *verts, int n_verts, const int32_t *faces, const float *vt, int n_vt,
+                    const int32_t *ft, int n_faces, int R, int stages, int64_t n_items, void *scratch,
+                    size_t scratch_bytes, int32_t *texel_face, int32_t *texel_idx, float *pos, int64_t max_texels,
+                    int64_t *counts_dev, lnerf_stream_t stream);
+/* lnerf_uv_dilate: `passes` gutter rounds over texture [C,R,R] f32 and mask [R,R] uint8 (2 = covered, 1 = filled by a
+ * round, 0 = empty), in place.  In a round every texel that was empty before the round and has k > 0 neighbours
+ * (of its 8) that were non-empty before the round takes their mean per channel: their sum in f32 in the order
+ * (-1,-1), (-1,0), (-1,1), (0,-1), (0,1), (1,-1), (1,0), (1,1) (row, column offsets), divided by k; its mask becomes 1.
+ * Every other texel keeps its value and mask.  tmp_texture / tmp_mask: buffers of the same sizes (ping-pong). */
+int lnerf_uv_dilate(float *texture, uint8_t *mask, int C, int R, int passes, float *tmp_texture, uint8_t *tmp_mask,
+                    lnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

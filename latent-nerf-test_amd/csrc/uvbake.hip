@@ -1,0 +1,394 @@
+// Texture baking over a mesh's UV atlas: NeRFRenderer.bake_texture's kernels.  Contract: include/lnerf_hip.h,
+// lnerf_uv_raster / lnerf_uv_dilate; numpy restatement: tests/uv_reference.py.
+//
+// lnerf_uv_raster, stage by stage (every pass linear in its work, no cross-workgroup waiting):
+//   ITEMS  k_uv_setup  one lane per face: pixel-space corners, area, candidate box; items = box area; an in-block
+//                      exclusive prefix of the items (int64) and per-block item / bad-index totals
+//          k_uv_scan   ONE workgroup: exclusive prefix of the block totals (in place) -> counts[0] items, [1] bad faces
+//   COVER  k_uv_cover  one lane per (face, box texel) item, so one big UV triangle does not serialise on one lane:
+//                      the item's face by binary search over the item prefix, the edge test, atomicMax of the face
+//                      index into texel_face (the largest covering index wins, whatever the order)
+//          k_uv_count  one lane per texel: covered texels per block of UV_THREADS texels
+//          k_uv_scan   exclusive prefix of those -> counts[2] = P
+//   EMIT   k_uv_emit   one lane per texel: rank among the block's covered texels (ballot / mbcnt + wave totals in LDS),
+//                      texel_idx and the surface point at block prefix + rank (ascending linear order)
+// lnerf_uv_dilate: one launch per gutter round (k_uv_dilate), ping-ponging between the caller's two buffers.
+#include "common.h"
+
+namespace lnerf {
+
+constexpr int UV_THREADS = 256;
+constexpr int UV_LOG2 = 8;
+constexpr int UV_WAVES = UV_THREADS / LNERF_WAVE;
+constexpr int UV_SCAN_THREADS = 1024;
+constexpr int64_t UV_ITEMS_PER_LAUNCH = int64_t(1) << 30;
+
+struct UvMesh {
+    const float *verts;
+    const int32_t *faces;
+    const float *vt;
+    const int32_t *ft;
+    int n_verts, n_vt, n_faces, R;
+    float Rf;
+};
+
+// one face in pixel space: corners, area (= E_01 at corner 2), candidate box [j0, j0 + w) x [i0, i0 + h)
+struct UvTri {
+    float X[3], Y[3], area;
+    int j0, i0, w, h;
+};
+
+__device__ __forceinline__ bool uv_indices_ok(const UvMesh &m, int f) {
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int v = m.faces[(int64_t)f * 3 + k], t = m.ft[(int64_t)f * 3 + k];
+        ok = ok && v >= 0 && v < m.n_verts && t >= 0 && t < m.n_vt;
+    }
+    return ok;
+}
+
+// corners, area and box of face f (its ft indices must be valid); w = h = 0 when it covers nothing
+__device__ __forceinline__ void uv_tri(const UvMesh &m, int f, UvTri &t) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int q = m.ft[(int64_t)f * 3 + k];
+        t.X[k] = m.vt[(int64_t)q * 2] * m.Rf;
+        t.Y[k] = (1.0f - m.vt[(int64_t)q * 2 + 1]) * m.Rf;
+    }
+    t.area = (t.X[1] - t.X[0]) * (t.Y[2] - t.Y[0]) - (t.Y[1] - t.Y[0]) * (t.X[2] - t.X[0]);
+    t.j0 = t.i0 = t.w = t.h = 0;
+    if (!(fabsf(t.area) <= 3.402823466e38f) || t.area == 0.f) return;     // NaN, infinite or degenerate
+    const float top = m.Rf - 1.0f;
+    const float xl = floorf(fminf(fminf(t.X[0], t.X[1]), t.X[2])) - 1.0f;
+    const float xh = floorf(fmaxf(fmaxf(t.X[0], t.X[1]), t.X[2])) + 1.0f;
+    const float yl = floorf(fminf(fminf(t.Y[0], t.Y[1]), t.Y[2])) - 1.0f;
+    const float yh = floorf(fmaxf(fmaxf(t.Y[0], t.Y[1]), t.Y[2])) + 1.0f;
+    if (xh < 0.f || yh < 0.f || xl > top || yl > top) return;
+    t.j0 = (int)fmaxf(xl, 0.f);
+    t.i0 = (int)fmaxf(yl, 0.f);
+    t.w = (int)fminf(xh, top) - t.j0 + 1;
+    t.h = (int)fminf(yh, top) - t.i0 + 1;
+}
+
+// E_ab at the centre of texel (i, j): (X_b - X_a) * (p_y - Y_a) - (Y_b - Y_a) * (p_x - X_a)
+__device__ __forceinline__ float uv_edge(const UvTri &t, int a, int b, float px, float py) {
+    return (t.X[b] - t.X[a]) * (py - t.Y[a]) - (t.Y[b] - t.Y[a]) * (px - t.X[a]);
+}
+
+// edge values (E_12, E_20, E_01) at texel (i, j); true iff each has the sign of the area or is 0
+__device__ __forceinline__ bool uv_cover(const UvTri &t, int i, int j, float e[3]) {
+    const float px = (float)j + 0.5f, py = (float)i + 0.5f;
+    e[0] = uv_edge(t, 1, 2, px, py);
+    e[1] = uv_edge(t, 2, 0, px, py);
+    e[2] = uv_edge(t, 0, 1, px, py);
+    return t.area > 0.f ? (e[0] >= 0.f && e[1] >= 0.f && e[2] >= 0.f) : (e[0] <= 0.f && e[1] <= 0.f && e[2] <= 0.f);
+}
+
+__device__ __forceinline__ long long uv_wave_incl(long long x) {
+    const int lane = lane_id();
+#pragma unroll
+    for (int o = 1; o < LNERF_WAVE; o <<= 1) {
+        const long long u = __shfl_up(x, o, LNERF_WAVE);
+        if (lane >= o) x += u;
+    }
+    return x;
+}
+
+__global__ void __launch_bounds__(UV_THREADS)
+k_uv_setup(UvMesh m, int64_t *__restrict__ face_off, int64_t *__restrict__ blk_items, int64_t *__restrict__ blk_bad) {
+    __shared__ long long s_items[UV_WAVES];
+    __shared__ int s_bad[UV_WAVES];
+    const int f = blockIdx.x * UV_THREADS + threadIdx.x;
+    long long items = 0;
+    int bad = 0;
+    if (f < m.n_faces) {
+        if (uv_indices_ok(m, f)) {
+            UvTri t;
+            uv_tri(m, f, t);
+            items = (long long)t.w * t.h;
+        } else {
+            bad = 1;
+        }
+    }
+    const long long incl = uv_wave_incl(items);
+    const int nbad = (int)__popcll(__ballot(bad));
+    const int w = threadIdx.x / LNERF_WAVE;
+    if (lane_id() == LNERF_WAVE - 1) { s_items[w] = incl; s_bad[w] = nbad; }
+    __syncthreads();
+    long long before = 0, total = 0;
+    int tbad = 0;
+#pragma unroll
+    for (int k = 0; k < UV_WAVES; ++k) {
+        if (k < w) before += s_items[k];
+        total += s_items[k];
+        tbad += s_bad[k];
+    }
+    if (f < m.n_faces) face_off[f] = before + incl - items;
+    if (threadIdx.x == 0) {
+        blk_items[blockIdx.x] = total;
+        blk_bad[blockIdx.x] = tbad;
+    }
+}
+
+// exclusive prefix of a[0, nb) in place, its total -> *total_a; the sum of b[0, nb) -> *total_b (b may be NULL)
+__global__ void __launch_bounds__(UV_SCAN_THREADS)
+k_uv_scan(int64_t *__restrict__ a, const int64_t *__restrict__ b, int64_t nb, int64_t *__restrict__ total_a,
+          int64_t *__restrict__ total_b) {
+    __shared__ long long s_a[UV_SCAN_THREADS / LNERF_WAVE], s_b[UV_SCAN_THREADS / LNERF_WAVE];
+    const int64_t chunk = (nb + UV_SCAN_THREADS - 1) / UV_SCAN_THREADS;
+    const int64_t b0 = min((int64_t)threadIdx.x * chunk, nb), b1 = min(b0 + chunk, nb);
+    long long sa = 0, sb = 0;
+    for (int64_t k = b0; k < b1; ++k) {
+        sa += a[k];
+        if (b) sb += b[k];
+    }
+    const long long ai = uv_wave_incl(sa), bi = uv_wave_incl(sb);
+    const int w = threadIdx.x / LNERF_WAVE;
+    if (lane_id() == LNERF_WAVE - 1) { s_a[w] = ai; s_b[w] = bi; }
+    __syncthreads();
+    long long run = ai - sa, ta = 0, tb = 0;
+    for (int k = 0; k < UV_SCAN_THREADS / LNERF_WAVE; ++k) {
+        if (k < w) run += s_a[k];
+        ta += s_a[k];
+        tb += s_b[k];
+    }
+    for (int64_t k = b0; k < b1; ++k) {
+        const long long v = a[k];
+        a[k] = run;
+        run += v;
+    }
+    if (threadIdx.x == 0) {
+        *total_a = ta;
+        if (total_b) *total_b = tb;
+    }
+}
+
+// items [base, base + n) of the stage's item list; lanes past the device total (counts[0]) do nothing
+__global__ void __launch_bounds__(UV_THREADS)
+k_uv_cover(UvMesh m, const int64_t *__restrict__ face_off, const int64_t *__restrict__ blk_items, int64_t nb,
+           const int64_t *__restrict__ counts, int64_t base, int64_t n, int32_t *__restrict__ texel_face) {
+    const int64_t t = base + (int64_t)blockIdx.x * UV_THREADS + threadIdx.x;
+    if (t >= base + n || t >= counts[0]) return;
+    // the block: largest b with blk_items[b] <= t (an empty block shares its prefix with the next one)
+    int64_t lo = 0, hi = nb - 1;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (blk_items[mid] <= t) lo = mid; else hi = mid - 1;
+    }
+    const int64_t local = t - blk_items[lo];
+    int flo = (int)(lo << UV_LOG2), fhi = min(flo + UV_THREADS, m.n_faces) - 1;
+    while (flo < fhi) {
+        const int mid = (flo + fhi + 1) >> 1;
+        if (face_off[mid] <= local) flo = mid; else fhi = mid - 1;
+    }
+    const int f = flo;
+    UvTri tri;
+    uv_tri(m, f, tri);
+    const int r = (int)(local - face_off[f]);          // < w * h <= R^2
+    const int di = r / tri.w;
+    const int i = tri.i0 + di, j = tri.j0 + (r - di * tri.w);
+    float e[3];
+    if (uv_cover(tri, i, j, e)) atomicMax(&texel_face[(int64_t)i * m.R + j], f);
+}
+
+__global__ void __launch_bounds__(UV_THREADS)
+k_uv_count(const int32_t *__restrict__ texel_face, int64_t n, int64_t *__restrict__ blk_texels) {
+    __shared__ int s_n[UV_WAVES];
+    const int64_t p = (int64_t)blockIdx.x * UV_THREADS + threadIdx.x;
+    const bool c = p < n && texel_face[p] >= 0;
+    const int cnt = (int)__popcll(__ballot(c));
+    if (lane_id() == 0) s_n[threadIdx.x / LNERF_WAVE] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int s = 0;
+#pragma unroll
+        for (int k = 0; k < UV_WAVES; ++k) s += s_n[k];
+        blk_texels[blockIdx.x] = s;
+    }
+}
+
+__global__ void __launch_bounds__(UV_THREADS)
+k_uv_emit(UvMesh m, const int32_t *__restrict__ texel_face, const int64_t *__restrict__ blk_texels,
+          int32_t *__restrict__ texel_idx, float *__restrict__ pos, int64_t max_texels) {
+    __shared__ int s_n[UV_WAVES];
+    const int64_t n = (int64_t)m.R * m.R;
+    const int64_t p = (int64_t)blockIdx.x * UV_THREADS + threadIdx.x;
+    const int f = p < n ? texel_face[p] : -1;
+    const unsigned long long mask = __ballot(f >= 0);
+    const int w = threadIdx.x / LNERF_WAVE;
+    if (lane_id() == 0) s_n[w] = (int)__popcll(mask);
+    __syncthreads();
+    if (f < 0) return;
+    int before = 0;
+#pragma unroll
+    for (int k = 0; k < UV_WAVES; ++k)
+        if (k < w) before += s_n[k];
+    const int64_t q = blk_texels[blockIdx.x] + before + mbcnt(mask);
+    if (q >= max_texels) return;
+    const int i = (int)(p / m.R), j = (int)(p - (int64_t)i * m.R);
+    UvTri tri;
+    uv_tri(m, f, tri);
+    float e[3];
+    uv_cover(tri, i, j, e);
+    const float b0 = e[0] / tri.area, b1 = e[1] / tri.area, b2 = e[2] / tri.area;
+    const int64_t v0 = m.faces[(int64_t)f * 3], v1 = m.faces[(int64_t)f * 3 + 1], v2 = m.faces[(int64_t)f * 3 + 2];
+    texel_idx[q] = (int32_t)p;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+        pos[q * 3 + a] = b0 * m.verts[v0 * 3 + a] + b1 * m.verts[v1 * 3 + a] + b2 * m.verts[v2 * 3 + a];
+}
+
+// one gutter round: covered / filled texels are copied, an empty one takes the mean of its non-empty 8-neighbours
+__global__ void __launch_bounds__(UV_THREADS)
+k_uv_dilate(const float *__restrict__ src, const uint8_t *__restrict__ msrc, float *__restrict__ dst,
+            uint8_t *__restrict__ mdst, int C, int R) {
+    const int64_t n = (int64_t)R * R;
+    const int64_t p = (int64_t)blockIdx.x * UV_THREADS + threadIdx.x;
+    if (p >= n) return;
+    const uint8_t mk = msrc[p];
+    if (mk != 0) {
+        for (int c = 0; c < C; ++c) dst[c * n + p] = src[c * n + p];
+        mdst[p] = mk;
+        return;
+    }
+    const int i = (int)(p / R), j = (int)(p - (int64_t)i * R);
+    uint32_t nb = 0;
+    int cnt = 0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        if (k == 4) continue;
+        const int ii = i + k / 3 - 1, jj = j + k % 3 - 1;
+        if (ii >= 0 && ii < R && jj >= 0 && jj < R && msrc[(int64_t)ii * R + jj] != 0) {
+            nb |= 1u << k;
+            ++cnt;
+        }
+    }
+    for (int c = 0; c < C; ++c) {
+        const float *s = src + c * n;
+        float v = s[p];
+        if (cnt > 0) {
+            float sum = 0.f;
+#pragma unroll
+            for (int k = 0; k < 9; ++k)
+                if ((nb >> k) & 1u) sum += s[(int64_t)(i + k / 3 - 1) * R + (j + k % 3 - 1)];
+            v = sum / (float)cnt;
+        }
+        dst[c * n + p] = v;
+    }
+    mdst[p] = cnt > 0 ? 1 : 0;
+}
+
+struct UvLayout {
+    int64_t nbF, nbT;
+    size_t off_bytes, blk_bytes, bytes;
+};
+
+static UvLayout uv_layout(int n_faces, int R) {
+    UvLayout L;
+    L.nbF = div_up(n_faces, UV_THREADS);
+    L.nbT = div_up((int64_t)R * R, UV_THREADS);
+    L.off_bytes = (size_t)div_up((int64_t)n_faces * 8, 256) * 256;
+    L.blk_bytes = (size_t)div_up(L.nbF * 8, 256) * 256;
+    L.bytes = L.off_bytes + 2 * L.blk_bytes + (size_t)L.nbT * 8;
+    return L;
+}
+
+}  // namespace lnerf
+
+using namespace lnerf;
+
+extern "C" {
+
+size_t lnerf_uv_raster_scratch_bytes(int n_faces, int R) {
+    if (n_faces < 0 || R < 1 || R > LNERF_UV_MAX_RES) return 0;
+    return uv_layout(n_faces, R).bytes;
+}
+
+int lnerf_uv_raster(const float *verts, int n_verts, const int32_t *faces, const float *vt, int n_vt,
+                    const int32_t *ft, int n_faces, int R, int stages, int64_t n_items, void *scratch,
+                    size_t scratch_bytes, int32_t *texel_face, int32_t *texel_idx, float *pos, int64_t max_texels,
+                    int64_t *counts_dev, lnerf_stream_t stream) {
+    LNERF_REQUIRE(R >= 1 && R <= LNERF_UV_MAX_RES, "uv_raster: resolution %d outside [1, %d]", R, LNERF_UV_MAX_RES);
+    LNERF_REQUIRE(n_faces >= 0 && n_verts >= 0 && n_vt >= 0, "uv_raster: negative count");
+    LNERF_REQUIRE((stages & ~(LNERF_UV_ITEMS | LNERF_UV_COVER | LNERF_UV_EMIT)) == 0 && stages != 0,
+                  "uv_raster: bad stage bits 0x%x", stages);
+    LNERF_REQUIRE(scratch && counts_dev, "uv_raster: null pointer");
+    LNERF_REQUIRE(n_faces == 0 || (verts && faces && vt && ft), "uv_raster: null mesh pointer");
+    LNERF_REQUIRE(!(stages & (LNERF_UV_COVER | LNERF_UV_EMIT)) || texel_face, "uv_raster: null texel_face");
+    LNERF_REQUIRE(!(stages & LNERF_UV_COVER) || n_items >= 0, "uv_raster: negative item count");
+    LNERF_REQUIRE(!(stages & LNERF_UV_EMIT) || (max_texels >= 0 && (max_texels == 0 || (texel_idx && pos))),
+                  "uv_raster: null output buffer with a non-zero capacity");
+    const UvLayout L = uv_layout(n_faces, R);
+    LNERF_REQUIRE(scratch_bytes >= L.bytes, "uv_raster: scratch of %zu bytes, need %zu", scratch_bytes, L.bytes);
+    LNERF_REQUIRE(((uintptr_t)scratch & 15) == 0, "uv_raster: scratch must be 16-byte aligned");
+    UvMesh m;
+    m.verts = verts; m.faces = faces; m.vt = vt; m.ft = ft;
+    m.n_verts = n_verts; m.n_vt = n_vt; m.n_faces = n_faces; m.R = R;
+    m.Rf = (float)R;
+    int64_t *face_off = reinterpret_cast<int64_t *>(scratch);
+    int64_t *blk_items = reinterpret_cast<int64_t *>(reinterpret_cast<char *>(scratch) + L.off_bytes);
+    int64_t *blk_bad = reinterpret_cast<int64_t *>(reinterpret_cast<char *>(blk_items) + L.blk_bytes);
+    int64_t *blk_texels = reinterpret_cast<int64_t *>(reinterpret_cast<char *>(blk_bad) + L.blk_bytes);
+    const int64_t n_texels = (int64_t)R * R;
+    hipStream_t s = as_stream(stream);
+    if (stages & LNERF_UV_ITEMS) {
+        if (n_faces > 0) {
+            hipLaunchKernelGGL(k_uv_setup, dim3((unsigned)L.nbF), dim3(UV_THREADS), 0, s, m, face_off, blk_items, blk_bad);
+            LNERF_CHECK_LAUNCH("uv_raster(setup)");
+        }
+        hipLaunchKernelGGL(k_uv_scan, dim3(1), dim3(UV_SCAN_THREADS), 0, s, blk_items, blk_bad, L.nbF, counts_dev,
+                           counts_dev + 1);
+        LNERF_CHECK_LAUNCH("uv_raster(scan items)");
+    }
+    if (stages & LNERF_UV_COVER) {
+        if (hipMemsetAsync(texel_face, 0xff, (size_t)n_texels * 4, s) != hipSuccess) {
+            set_error("uv_raster: clearing texel_face failed");
+            return LNERF_ERR_HIP;
+        }
+        for (int64_t base = 0; base < n_items; base += UV_ITEMS_PER_LAUNCH) {
+            const int64_t n = min(n_items - base, UV_ITEMS_PER_LAUNCH);
+            hipLaunchKernelGGL(k_uv_cover, dim3((unsigned)div_up(n, UV_THREADS)), dim3(UV_THREADS), 0, s, m, face_off,
+                               blk_items, L.nbF, counts_dev, base, n, texel_face);
+            LNERF_CHECK_LAUNCH("uv_raster(cover)");
+        }
+        hipLaunchKernelGGL(k_uv_count, dim3((unsigned)L.nbT), dim3(UV_THREADS), 0, s, texel_face, n_texels, blk_texels);
+        LNERF_CHECK_LAUNCH("uv_raster(count)");
+        hipLaunchKernelGGL(k_uv_scan, dim3(1), dim3(UV_SCAN_THREADS), 0, s, blk_texels, (const int64_t *)nullptr,
+                           L.nbT, counts_dev + 2, (int64_t *)nullptr);
+        LNERF_CHECK_LAUNCH("uv_raster(scan texels)");
+    }
+    if ((stages & LNERF_UV_EMIT) && max_texels > 0) {
+        hipLaunchKernelGGL(k_uv_emit, dim3((unsigned)L.nbT), dim3(UV_THREADS), 0, s, m, texel_face, blk_texels,
+                           texel_idx, pos, max_texels);
+        LNERF_CHECK_LAUNCH("uv_raster(emit)");
+    }
+    return LNERF_OK;
+}
+
+int lnerf_uv_dilate(float *texture, uint8_t *mask, int C, int R, int passes, float *tmp_texture, uint8_t *tmp_mask,
+                    lnerf_stream_t stream) {
+    LNERF_REQUIRE(R >= 1 && R <= LNERF_UV_MAX_RES, "uv_dilate: resolution %d outside [1, %d]", R, LNERF_UV_MAX_RES);
+    LNERF_REQUIRE(C >= 1 && passes >= 0, "uv_dilate: C = %d, passes = %d", C, passes);
+    LNERF_REQUIRE(texture && mask && (passes == 0 || (tmp_texture && tmp_mask)), "uv_dilate: null pointer");
+    const int64_t n = (int64_t)R * R;
+    hipStream_t s = as_stream(stream);
+    float *a = texture, *b = tmp_texture;
+    uint8_t *ma = mask, *mb = tmp_mask;
+    for (int r = 0; r < passes; ++r) {
+        hipLaunchKernelGGL(k_uv_dilate, dim3((unsigned)div_up(n, UV_THREADS)), dim3(UV_THREADS), 0, s, a, ma, b, mb, C, R);
+        LNERF_CHECK_LAUNCH("uv_dilate");
+        float *t = a; a = b; b = t;
+        uint8_t *mt = ma; ma = mb; mb = mt;
+    }
+    if (a != texture) {
+        if (hipMemcpyAsync(texture, a, (size_t)n * C * 4, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(mask, ma, (size_t)n, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+            set_error("uv_dilate: copy-back failed");
+            return LNERF_ERR_HIP;
+        }
+    }
+    return LNERF_OK;
+}
+
+}  // extern "C"

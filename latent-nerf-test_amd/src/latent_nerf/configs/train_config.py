@@ -87,6 +87,9 @@ class LogConfig:
     eval_size: int = 10
     full_eval_size: int = 100
     save_mesh: bool = False
+    # with save_mesh: > 0 exports a textured mesh (per-triangle UV atlas, the field baked at this texture side) instead
+    # of per-vertex colours; its latent_texture.pt starts Latent-Paint (guide.init_texture)
+    mesh_texture_resolution: int = 0
     max_keep_ckpts: int = 2
     # no progress lines on stdout (log.txt in the experiment directory is still written)
     quiet: bool = False

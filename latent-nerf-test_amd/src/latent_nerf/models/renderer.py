@@ -405,15 +405,58 @@ class NeRFRenderer(nn.Module):
                     vol[x0:x0 + S, y0:y0 + S, z0:z0 + S] = (sigmas * self.density_scale).view(len(xs), len(ys), len(zs))
         return vol
 
+    def _latent_preview(self, feats):
+        """[N,C] field features -> [N,3] RGB in [0, 1]: latent mode, the linear latent->RGB preview; RGB mode, the
+        first three channels."""
+        from ..training.guidance import LATENT_TO_RGB
+        if self.latent_mode and feats.shape[-1] == 4:
+            m = torch.tensor(LATENT_TO_RGB, device=feats.device, dtype=torch.float32)
+            rgb = (feats.float() @ m) / 2 + 0.5
+        else:
+            rgb = feats[:, :3].float()
+        return rgb.clamp(0, 1)
+
     @torch.no_grad()
-    def export_mesh(self, path, resolution=None, S=128, thresh=None):
+    def bake_texture(self, verts, faces, vt, ft, resolution=1024, gutter=4, S=128, fn=None):
+        """Sample the field over a mesh's UV atlas.  Every texel whose centre a face covers (lnerf_uv_raster: the
+        face with the largest index where charts overlap) gets fn(surface point), fn(pts [P,3]) -> [P,C] queried in
+        S^3-point chunks (default: the field's features, 4-channel latents or RGB); then `gutter` dilation rounds
+        (lnerf_uv_dilate) spread the chart borders outwards so that bilinear lookups there do not blend in zeros.
+        Texel (i, j) sits at u = (j + 0.5) / R, v = 1 - (i + 0.5) / R, the convention Latent-Paint's texture lookup uses.
+        -> dict(texture [C,R,R] f32, mask [R,R] uint8 (2 covered, 1 gutter, 0 empty), rgb [3,R,R] in [0, 1])."""
+        if fn is None:
+            def fn(pts):
+                return self.field(pts, pts.shape[0])[1]
+        R = int(resolution)
+        verts = verts.to(torch.float32).contiguous()
+        dev = verts.device
+        texel_face, texel_idx, pos = rm.uv_raster(verts, faces, vt, ft, R)
+        P = pos.shape[0]
+        chunk = int(S) ** 3
+        feats = [fn(pos[s:s + chunk].contiguous()).float() for s in range(0, P, chunk)]
+        C = feats[0].shape[-1] if feats else (4 if self.latent_mode else 3)
+        texture = torch.zeros(C, R * R, device=dev, dtype=torch.float32)
+        if P > 0:
+            texture[:, texel_idx.long()] = torch.cat(feats).T
+        mask = (texel_face.reshape(-1) >= 0).to(torch.uint8) * 2
+        texture, mask = texture.view(C, R, R), mask.view(R, R)
+        rm.uv_dilate(texture, mask, gutter)
+        rgb = self._latent_preview(texture.reshape(C, -1).T).T.reshape(3, R, R).contiguous()
+        return {"texture": texture, "mask": mask, "rgb": rgb}
+
+    @torch.no_grad()
+    def export_mesh(self, path, resolution=None, S=128, thresh=None, texture_resolution=0, gutter=4):
         """Triangle mesh of the density field -> `path`/mesh.obj (the upstream renderer's export_mesh(path, resolution,
         S)): the density on a `resolution`^3 lattice over [-bound, bound]^3 (density_lattice), marching cubes on the GPU
         at iso `thresh` (default min(mean density, density_thresh), as upstream) with the box capped, vertex colours
         from the field at the vertices (latent mode: the linear latent->RGB preview), clamped to [0, 1].
-        Returns dict(verts [V,3], faces [F,3] int32, normals [V,3], colors [V,3], iso, path) with device tensors."""
+        texture_resolution > 0: a textured mesh instead -- the per-triangle UV atlas, the field baked into it at that
+        side (bake_texture, `gutter` dilation rounds), mesh.obj with v / vt / vn / f v/vt/vn, mesh.mtl, albedo.png
+        (the RGB preview) and, in latent mode, latent_texture.pt ([4,R,R] f32, what Latent-Paint's guide.init_texture
+        reads).
+        Returns dict(verts [V,3], faces [F,3] int32, normals [V,3], colors [V,3], iso, path) with device tensors, plus
+        vt, ft, texture, mask, rgb when textured."""
         from .mesh_io import write_obj
-        from ..training.guidance import LATENT_TO_RGB
         vol = self.density_lattice(resolution, S)
         if thresh is None:
             iso = float(torch.clamp(self.mean_density_dev.reshape(-1)[0], max=float(self.density_thresh)))
@@ -426,15 +469,41 @@ class NeRFRenderer(nn.Module):
         for s in range(0, verts.shape[0], chunk):
             pts = verts[s:s + chunk].contiguous()
             _, feats = self.field(pts, pts.shape[0])
-            if self.latent_mode and feats.shape[-1] == 4:
-                m = torch.tensor(LATENT_TO_RGB, device=feats.device, dtype=torch.float32)
-                rgb = (feats.float() @ m) / 2 + 0.5
-            else:
-                rgb = feats[:, :3].float()
-            colors[s:s + chunk] = rgb.clamp(0, 1)
+            colors[s:s + chunk] = self._latent_preview(feats)
         out = os.path.join(str(path), "mesh.obj")
-        write_obj(out, verts.cpu().numpy(), faces.cpu().numpy(), normals.cpu().numpy(), colors.cpu().numpy())
-        return {"verts": verts, "faces": faces, "normals": normals, "colors": colors, "iso": iso, "path": out}
+        result = {"verts": verts, "faces": faces, "normals": normals, "colors": colors, "iso": iso, "path": out}
+        if int(texture_resolution) > 0:
+            result.update(self._export_textured(str(path), verts, faces, normals, int(texture_resolution), gutter, S))
+        else:
+            write_obj(out, verts.cpu().numpy(), faces.cpu().numpy(), normals.cpu().numpy(), colors.cpu().numpy())
+        return result
+
+    def _export_textured(self, path, verts, faces, normals, R, gutter, S):
+        """The textured half of export_mesh: atlas, bake, mesh.obj + mesh.mtl + albedo.png (+ latent_texture.pt)."""
+        import warnings
+
+        import numpy as np
+        from PIL import Image
+
+        from ...uv_atlas import MIN_TEXELS_PER_CELL, atlas_cells, atlas_min_resolution, per_triangle_atlas
+        from .mesh_io import write_textured_obj
+        F = faces.shape[0]
+        need = atlas_min_resolution(F)
+        if F > 0 and R < need:
+            warnings.warn("export_mesh: texture_resolution %d gives the per-triangle atlas of %d faces %.1f texels per "
+                          "chart cell (fewer than %d): use texture_resolution >= %d"
+                          % (R, F, R / atlas_cells(F), MIN_TEXELS_PER_CELL, need), stacklevel=3)
+        vt, ft = per_triangle_atlas(F, verts.device)
+        baked = self.bake_texture(verts, faces, vt, ft, resolution=R, gutter=gutter, S=S)
+        os.makedirs(path, exist_ok=True)
+        out = os.path.join(path, "mesh.obj")
+        write_textured_obj(out, verts.cpu().numpy(), faces.cpu().numpy(), vt.cpu().numpy(), ft.cpu().numpy(),
+                           normals.cpu().numpy(), material="mesh.mtl", texture="albedo.png")
+        albedo = (baked["rgb"].permute(1, 2, 0).cpu().numpy() * 255).round().astype(np.uint8)
+        Image.fromarray(albedo).save(os.path.join(path, "albedo.png"))
+        if self.latent_mode and baked["texture"].shape[0] == 4:
+            torch.save(baked["texture"].cpu(), os.path.join(path, "latent_texture.pt"))
+        return dict(baked, vt=vt, ft=ft)
 
     def shadow_extra_state(self):
         """Context manager: inside it the occupancy state (density grid, bitfield, mean) is a SHADOW copy, so

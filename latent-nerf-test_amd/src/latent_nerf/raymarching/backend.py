@@ -24,6 +24,8 @@ GRID_BLOCKED = 0x400          # flag on the gather's / scatter's variant: blocke
 GRID_TILED = 0x800            # ... the upstream's `tiled` layout (dense index wrapped instead of hashed)
 SCATTER_CLEARED = 0x100       # flag on the scatter's variant: the caller cleared the cursors (lnerf_grid_scatter_clear_bytes)
 MC_CLOSE_BOUNDARY, MC_COUNT_ONLY, MC_REUSE_COUNT = 1, 2, 4   # LNERF_MC_* flags of lnerf_marching_cubes
+UV_ITEMS, UV_COVER, UV_EMIT = 1, 2, 4                         # LNERF_UV_* stages of lnerf_uv_raster
+UV_MAX_RES = 8192                                             # LNERF_UV_MAX_RES
 
 
 class LnerfLibraryError(RuntimeError):
@@ -110,6 +112,9 @@ _SIGNATURES = {
                                              _F, _P, _Z, _I, _I, _P, _P, _P, _F, _P, _F, _F, _F, _I, _P, _F, _I, _P],
     "lnerf_marching_cubes_scratch_bytes": [_I, _I, _I, _I],
     "lnerf_marching_cubes": [_P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _I, _P, _Z, _P, _P, _L, _P, _L, _P, _P],
+    "lnerf_uv_raster_scratch_bytes": [_I, _I],
+    "lnerf_uv_raster": [_P, _I, _P, _P, _I, _P, _I, _I, _I, _L, _P, _Z, _P, _P, _P, _L, _P, _P],
+    "lnerf_uv_dilate": [_P, _P, _I, _I, _I, _P, _P, _P],
     "lnerf_step_tail": [_I, _I, _P, _P, _P, _L, _I, _P, _Z, _P, _P, _P, _P, _P, _F, _P, _Z, _I, _I, _P, _P, _P, _F, _P,
                         _F, _F, _F, _I, _P, _F, _I, _P],
 }
@@ -122,6 +127,7 @@ _RESTYPES = {
     "lnerf_march_counter_len": _L,
     "lnerf_grid_encode_backward_workspace_bytes": _Z,
     "lnerf_marching_cubes_scratch_bytes": _Z,
+    "lnerf_uv_raster_scratch_bytes": _Z,
 }
 
 _lib = None

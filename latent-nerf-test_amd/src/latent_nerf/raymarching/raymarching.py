@@ -336,3 +336,79 @@ def marching_cubes(volume, iso, lo, hi, close_boundary=True):
         _b.call("lnerf_marching_cubes", *args, flags | _b.MC_REUSE_COUNT, _p(scratch), nbytes, _p(verts), _p(normals), V,
                 _p(faces), F, _p(counts), _stream())
     return verts, faces, normals
+
+
+# ------------------------------------------------------------------------------ texture baking
+def _uv_index(t, name, dev):
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError("uv_raster: %s must be a [F,3] index tensor" % name)
+    if t.dtype.is_floating_point:
+        raise TypeError("uv_raster: %s must hold integers" % name)
+    if t.dtype != torch.int32 and t.numel() and (int(t.min()) < -2 ** 31 or int(t.max()) >= 2 ** 31):
+        raise ValueError("uv_raster: %s has indices outside int32" % name)   # (a wrapped index could be a valid one)
+    return t.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def uv_raster(verts, faces, vt, ft, R):
+    """Which texel of an R x R texture each face of a UV-mapped mesh covers (lnerf_uv_raster, include/lnerf_hip.h).
+    verts [V,3], faces [F,3] (into verts), vt [T,2], ft [F,3] (into vt), all on the GPU.
+    -> texel_face [R,R] int32 (covering face with the largest index, -1 = none), texel_idx [P] int32 (the covered
+    texels' linear indices i * R + j, ascending) and pos [P,3] f32 (the surface point at each covered texel's centre).
+    Texel (i, j) has its centre at u = (j + 0.5) / R, v = 1 - (i + 0.5) / R, the convention texture_map samples with.
+    Two host synchronisations: the candidate count sizes the cover launch, the covered count sizes the outputs."""
+    R = int(R)
+    if not 1 <= R <= _b.UV_MAX_RES:
+        raise ValueError("uv_raster: resolution %d outside [1, %d]" % (R, _b.UV_MAX_RES))
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError("uv_raster: verts must be [V,3]")
+    if not isinstance(vt, torch.Tensor) or vt.dim() != 2 or vt.shape[1] != 2:
+        raise ValueError("uv_raster: vt must be [T,2]")
+    dev = verts.device
+    verts = verts.to(torch.float32).contiguous()
+    vt = vt.to(device=dev, dtype=torch.float32).contiguous()
+    faces, ft = _uv_index(faces, "faces", dev), _uv_index(ft, "ft", dev)
+    if faces.shape[0] != ft.shape[0]:
+        raise ValueError("uv_raster: faces has %d rows, ft %d" % (faces.shape[0], ft.shape[0]))
+    _chk(verts, "verts")
+    _chk(vt, "vt")
+    F, V, T = faces.shape[0], verts.shape[0], vt.shape[0]
+    if max(F, V, T) >= 2 ** 31:
+        raise ValueError("uv_raster: %d faces / %d vertices / %d texture vertices exceed int32" % (F, V, T))
+    nbytes = _b.get_lib().lnerf_uv_raster_scratch_bytes(F, R)
+    scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    counts = torch.zeros(3, device=dev, dtype=torch.int64)
+    texel_face = torch.empty(R, R, device=dev, dtype=torch.int32)
+    mesh = (_p(verts), V, _p(faces), _p(vt), T, _p(ft), F, R)
+    _b.call("lnerf_uv_raster", *mesh, _b.UV_ITEMS, 0, _p(scratch), nbytes, None, None, None, 0, _p(counts), _stream())
+    items, bad = (int(v) for v in counts[:2].tolist())
+    if bad:
+        raise ValueError("uv_raster: %d faces index outside verts (%d) or vt (%d)" % (bad, V, T))
+    _b.call("lnerf_uv_raster", *mesh, _b.UV_COVER, items, _p(scratch), nbytes, _p(texel_face), None, None, 0,
+            _p(counts), _stream())
+    P = int(counts[2])
+    texel_idx = torch.empty(P, device=dev, dtype=torch.int32)
+    pos = torch.empty(P, 3, device=dev, dtype=torch.float32)
+    if P > 0:
+        _b.call("lnerf_uv_raster", *mesh, _b.UV_EMIT, 0, _p(scratch), nbytes, _p(texel_face), _p(texel_idx), _p(pos),
+                P, _p(counts), _stream())
+    return texel_face, texel_idx, pos
+
+
+def uv_dilate(texture, mask, passes):
+    """`passes` gutter rounds, in place, over texture [C,R,R] f32 and mask [R,R] uint8 (2 covered, 1 filled, 0 empty)
+    on the GPU (lnerf_uv_dilate): a texel that is empty before a round takes the mean of its 8-neighbours that were
+    non-empty before it.  Returns (texture, mask)."""
+    if not isinstance(texture, torch.Tensor) or texture.dim() != 3 or texture.shape[1] != texture.shape[2]:
+        raise ValueError("uv_dilate: texture must be [C,R,R]")
+    C, R = int(texture.shape[0]), int(texture.shape[1])
+    if not isinstance(mask, torch.Tensor) or tuple(mask.shape) != (R, R):
+        raise ValueError("uv_dilate: mask must be [R,R] = [%d,%d]" % (R, R))
+    _chk(texture, "texture")
+    _chk(mask, "mask", dtype=torch.uint8)
+    passes = int(passes)
+    if passes < 0:
+        raise ValueError("uv_dilate: passes must be >= 0")
+    if passes > 0:
+        tmp, tmp_mask = torch.empty_like(texture), torch.empty_like(mask)
+        _b.call("lnerf_uv_dilate", _p(texture), _p(mask), C, R, passes, _p(tmp), _p(tmp_mask), _stream())
+    return texture, mask

@@ -471,7 +471,8 @@ class Trainer:
         frames = self.evaluate(self.dataloaders["val_large"], self.final_renders_path, save_as_video=True)
         if getattr(self.cfg.log, "save_mesh", False) and self.rank == 0:
             # the density field as a triangle mesh (NeRFRenderer.export_mesh) -> <exp_dir>/mesh/mesh.obj
-            mesh = self.nerf.export_mesh(self.exp_path / "mesh")
+            tex = int(getattr(self.cfg.log, "mesh_texture_resolution", 0))
+            mesh = self.nerf.export_mesh(self.exp_path / "mesh", texture_resolution=tex)
             self.log("exported %s (%d vertices, %d triangles, iso %.4g)"
                      % (mesh["path"], mesh["verts"].shape[0], mesh["faces"].shape[0], mesh["iso"]))
         return frames

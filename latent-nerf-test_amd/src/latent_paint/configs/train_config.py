@@ -32,6 +32,8 @@ GuideConfig = _cli.make_section("GuideConfig", (
     ("dy", float, 0.25, "lift of the mesh along +y"),
     ("texture_resolution", int, 128, "side of the square latent texture"),
     ("texture_interpolation_mode", str, "nearest", " | ".join(INTERPOLATION_MODES)),
+    ("init_texture", Optional[str], None, "latent texture [4,R,R] or [1,4,R,R] (torch.save) to start from, e.g. the "
+                                          "latent_texture.pt of the NeRF's textured mesh export; R = texture_resolution"),
     ("guidance", str, "synthetic", "'synthetic' (seeded offline stand-in) or 'stable-diffusion' (diffusers adapter)"),
 ), doc="guidance")
 

@@ -16,6 +16,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ...uv_atlas import per_triangle_atlas
 from .mesh import Mesh
 from .render import Renderer
 
@@ -24,21 +25,19 @@ LATENT_RGB_ROWS = ((0.298, 0.207, 0.208), (0.187, 0.286, 0.173), (-0.158, 0.189,
 LATENT_SIDE = 64   # side of the latent image the diffusion model consumes (src/stable_diffusion.py:259)
 
 
-def per_triangle_atlas(n_faces, device):
-    """UV atlas that needs no unwrapping library: the unit square is cut into n x n cells, two triangles per cell
-    (lower-left and upper-right half, with a margin so neighbouring charts do not bleed).  Every face gets three
-    texture vertices of its own: vt [3F,2], ft [F,3]."""
-    n = int(np.ceil(np.sqrt((n_faces + 1) // 2)))
-    k = torch.arange(n_faces, device=device)
-    cell, upper = k // 2, (k % 2).float()[:, None]
-    org = torch.stack([(cell % n).float(), (cell // n).float()], -1)
-    lo, hi, m = 0.08, 0.92, 0.06
-    lower_tri = torch.tensor([[lo, lo], [hi - m, lo], [lo, hi - m]], device=device)
-    upper_tri = torch.tensor([[hi, hi], [lo + m, hi], [hi, lo + m]], device=device)
-    corners = lower_tri[None] * (1 - upper[..., None]) + upper_tri[None] * upper[..., None]   # [F,3,2]
-    vt = ((org[:, None, :] + corners) / n).reshape(-1, 2)
-    ft = torch.arange(3 * n_faces, device=device).reshape(n_faces, 3)
-    return vt.float(), ft.long()
+def load_init_texture(path, R):
+    """A latent texture saved with torch.save, [4,R,R] or [1,4,R,R] -> [1,4,R,R] f32 (CPU)."""
+    tex = torch.load(path, map_location="cpu", weights_only=True)
+    if not torch.is_tensor(tex):
+        raise ValueError("guide.init_texture %s does not hold a tensor" % path)
+    if tex.dim() == 3:
+        tex = tex[None]
+    if tex.dim() != 4 or tex.shape[:2] != (1, 4) or tex.shape[2] != tex.shape[3]:
+        raise ValueError("guide.init_texture %s has shape %s; expected [4,R,R] or [1,4,R,R]" % (path, tuple(tex.shape)))
+    if tex.shape[-1] != R:
+        raise ValueError("guide.init_texture %s is %d x %d but guide.texture_resolution is %d: set "
+                         "--guide.texture_resolution %d" % (path, tex.shape[-2], tex.shape[-1], R, tex.shape[-1]))
+    return tex.float().contiguous()
 
 
 class TexturedMeshModel(nn.Module):
@@ -77,7 +76,8 @@ class TexturedMeshModel(nn.Module):
 
     def init_paint(self, init_rgb_color=(1.0, 0.0, 0.0)):
         """Learnable state: background colours ~ U(0,1); latent texture = 0.3 x (the latent whose linear RGB
-        estimate is `init_rgb_color`, ridge-regularised least squares) + 0.4 x N(0,1); an RGB texture that is only
+        estimate is `init_rgb_color`, ridge-regularised least squares) + 0.4 x N(0,1), or the file named by
+        `guide.init_texture` (a baked texture; the mesh's own UVs then line it up); an RGB texture that is only
         used by the 'texture-rgb-mesh' fine-tuning backbone (filled from a checkpoint)."""
         dev, R = self.device, self.texture_resolution
         sky = nn.Parameter(torch.rand(1, self.env_sphere.faces.shape[0], 3, 4, device=dev))
@@ -85,6 +85,9 @@ class TexturedMeshModel(nn.Module):
         ridge = M @ M.T + 1e-2 * torch.eye(4, device=dev)
         seed_latent = torch.linalg.pinv(ridge) @ M @ torch.tensor(init_rgb_color, device=dev)
         latent_tex = nn.Parameter(0.3 * seed_latent.view(1, 4, 1, 1) + 0.4 * torch.randn(1, 4, R, R, device=dev))
+        init = getattr(self.opt.guide, "init_texture", None)
+        if init:
+            latent_tex = nn.Parameter(load_init_texture(init, R).to(dev))
         rgb_tex = nn.Parameter(torch.zeros(1, 3, R, R, device=dev))
         return sky, latent_tex, rgb_tex
 

@@ -291,7 +291,8 @@ class NeRFRenderer(nn.Module):
             rays_t = nears.clone()
             n_alive, step = N, 0
             while step < max_steps and n_alive > 0:
-                n_step = max(min(N // n_alive, 8), 1)
+                # the last chunk stops at max_steps: a live ray never takes more samples than the training march
+                n_step = min(max(min(N // n_alive, 8), 1), max_steps - step)
                 xyzs, dirs, deltas = rm.march_rays(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, self.bound,
                                                    self.density_bitfield, self.cascade, self.grid_size, fars,
                                                    dt_gamma, max_steps)

@@ -34,6 +34,9 @@ class _InterpAttr(torch.autograd.Function):
 class _TextureMap(torch.autograd.Function):
     @staticmethod
     def forward(ctx, tex, uv, face_idx, mode):
+        if tex.dim() != 4 or tex.shape[0] != 1 or tex.shape[2] != tex.shape[3]:
+            # the kernels read one square [C,R,R] texture
+            raise ValueError("texture_map: texture must be [1,C,R,R] (got %s)" % (tuple(tex.shape),))
         C, R = tex.shape[1], tex.shape[2]
         P = uv.shape[0]
         tex = tex.contiguous()

@@ -117,7 +117,9 @@ def get_rays(c2w: torch.Tensor, fx: float, fy: float, cx: float, cy: float, H: i
     xs = (i.reshape(-1) + 0.5 - cx) / fx
     ys = (j.reshape(-1) + 0.5 - cy) / fy
     zs = torch.ones_like(xs)
-    inv = 1.0 / torch.sqrt(xs * xs + ys * ys + zs * zs)
+    # the square root through numpy, which lowers it to the correctly rounded hardware instruction: torch's CPU
+    # float32 sqrt goes through a vendor math library whose result is off by an ulp on some CPUs
+    inv = torch.from_numpy(np.float32(1.0) / np.sqrt((xs * xs + ys * ys + zs * zs).numpy()))
     d = torch.stack([xs * inv, ys * inv, zs * inv], dim=-1)  # [HW,3]
     R = c2w[:, :3, :3]  # [B,3,3]
     rays_d = (d[None, :, 0:1] * R[:, None, :, 0] + d[None, :, 1:2] * R[:, None, :, 1]
@@ -324,6 +326,62 @@ def march_rays_train(rays_o, rays_d, nears, fars, bitfield, bound: float, cascad
     deltas = torch.stack([dt.reshape(-1)[sel], t.reshape(-1)[sel]], -1)
     rays = torch.stack([torch.arange(N, dtype=torch.int64), offsets, counts], -1).to(torch.int32)
     return xyzs, dirs, deltas, rays, M
+
+
+# --------------------------------------------------------------------------------------
+# H4  occupancy-pruned ray march (inference: march / composite / compact, one chunk per call)
+# --------------------------------------------------------------------------------------
+def march_rays_infer(rays_alive, n_step: int, rays_t, rays_o, rays_d, fars, bitfield, bound: float, cascade: int,
+                     G: int, max_steps: int = 1024, dt_gamma: float = 0.0):
+    """k_march_rays.  For every entry i of rays_alive [n_alive] (a ray id, or < 0 for a dead entry) walk the
+    lattice of ray n = rays_alive[i] from t = rays_t[n] with t = t + clamp(t*dt_gamma, dt_min, dt_max) while
+    t < fars[n], and emit the first n_step occupied points (clamped to the box).  Rows after the last sample are
+    padding: xyz 0, dir (0,0,1), deltas (0, -1).  f32 throughout, un-fused, in the kernel's order.
+    Returns xyzs, dirs [n_alive*n_step, 3] and deltas [n_alive*n_step, 2] = (dt, t)."""
+    f32 = torch.float32
+    alive = rays_alive.to(torch.int64)
+    A = alive.shape[0]
+    xyzs = torch.zeros(A, n_step, 3, dtype=f32)
+    dirs = torch.zeros(A, n_step, 3, dtype=f32)
+    dirs[..., 2] = 1.0
+    deltas = torch.zeros(A, n_step, 2, dtype=f32)
+    deltas[..., 1] = -1.0
+    dt_min = torch.tensor(2.0 * SQRT3 / max_steps, dtype=f32)
+    dt_max = torch.tensor(2.0 * SQRT3 * (2 ** (cascade - 1)) / G, dtype=f32)
+    gam = torch.tensor(dt_gamma, dtype=f32)
+    bits = bitfield.to(torch.int64)
+    rows = (alive >= 0).nonzero(as_tuple=False).squeeze(-1)
+    ids = alive[rows]
+    o = rays_o.to(f32)[ids]
+    d = rays_d.to(f32)[ids]
+    far = fars.to(f32)[ids]
+    t = rays_t.to(f32)[ids].clone()
+    step = torch.zeros(rows.shape[0], dtype=torch.int64)
+    while True:
+        act = (t < far) & (step < n_step)
+        if not bool(act.any()):
+            break
+        r = act.nonzero(as_tuple=False).squeeze(-1)
+        ta = t[r]
+        dt = torch.clamp(ta * gam, dt_min, dt_max)
+        x = d[r] * ta[:, None]
+        x = x + o[r]
+        x = x.clamp(-bound, bound)
+        idx = march_cell_index(x, dt, bound, cascade, G)
+        occ = ((bits[idx >> 3] >> (idx & 7)) & 1).bool()
+        e = r[occ]
+        xyzs[rows[e], step[e]] = x[occ]
+        dirs[rows[e], step[e]] = d[e]
+        deltas[rows[e], step[e]] = torch.stack([dt[occ], ta[occ]], -1)
+        step[e] += 1
+        t[r] = ta + dt
+    return xyzs.reshape(-1, 3), dirs.reshape(-1, 3), deltas.reshape(-1, 2)
+
+
+def compact_rays(rays_alive, n: int):
+    """k_compact_rays: the entries >= 0 of rays_alive[:n], in order."""
+    a = rays_alive[:n]
+    return a[a >= 0].clone()
 
 
 # --------------------------------------------------------------------------------------
@@ -589,6 +647,47 @@ def composite_rays_train(sigmas, rgbs, deltas, rays, T_thresh: float = 1e-4, bg_
     return ws, depth, image
 
 
+def composite_rays_infer(rays_alive, n_step: int, rays_t, sigmas, rgbs, deltas, weights_sum, depth, image,
+                         transmittance, T_thresh: float = 1e-4):
+    """k_composite_rays in float64.  Entry i of rays_alive owns rows [i*n_step, (i+1)*n_step) of sigmas / rgbs /
+    deltas and composites them into the state of ray n = rays_alive[i] (entries < 0 are skipped, their state rows
+    untouched).  Front to back: a padding row (t < 0) ends the ray; otherwise alpha = 1 - exp(-sigma dt),
+    w = alpha T is added to weights_sum, w t to depth, w rgb to image, T *= 1 - alpha, rays_t[n] becomes the f32
+    t + dt of that sample, and the ray ends after the sample that takes T below T_thresh.  Entries of rays that end
+    become -1.  Returns new (rays_alive int32, rays_t f32, weights_sum, depth, image, transmittance f64)."""
+    f64 = torch.float64
+    alive = rays_alive.clone()
+    rt = rays_t.to(torch.float32).clone()
+    ws, dp = weights_sum.to(f64).clone(), depth.to(f64).clone()
+    img, T = image.to(f64).clone(), transmittance.to(f64).clone()
+    C = img.shape[1]
+    A = alive.shape[0]
+    sg = sigmas.reshape(A, n_step).to(f64)
+    rg = rgbs.reshape(A, n_step, C).to(f64)
+    dl = deltas.reshape(A, n_step, 2)
+    rows = (alive >= 0).nonzero(as_tuple=False).squeeze(-1)
+    ids = alive[rows].to(torch.int64)
+    go = torch.ones(rows.shape[0], dtype=torch.bool)
+    for s in range(n_step):
+        dt32, t32 = dl[rows, s, 0], dl[rows, s, 1]
+        pad = go & (t32 < 0)
+        go = go & ~pad
+        alive[rows[pad]] = -1
+        r, n = rows[go], ids[go]
+        dt, t = dt32[go].to(f64), t32[go].to(f64)
+        alpha = 1.0 - torch.exp(-sg[r, s] * dt)
+        w = alpha * T[n]
+        ws[n] += w
+        dp[n] += w * t
+        img[n] += w[:, None] * rg[r, s]
+        T[n] = T[n] * (1.0 - alpha)
+        rt[n] = t32[go] + dt32[go]
+        kill = T[n] < T_thresh
+        alive[r[kill]] = -1
+        go[go.clone()] = ~kill
+    return alive, rt, ws, dp, img, T
+
+
 # --------------------------------------------------------------------------------------
 # H10  occupancy grid refresh
 # --------------------------------------------------------------------------------------
@@ -716,6 +815,81 @@ def render_frame(rays_o, rays_d, table, mlp_params, lv: GridLevels, bitfield, *,
     ws, depth, image = composite_rays_train(sigmas, rgbs, deltas, rays, T_thresh, bg_color)
     return {"image": image, "depth": depth, "weights_sum": ws, "xyzs": xyzs, "dirs": dirs, "deltas": deltas,
             "rays": rays, "sigmas": sigmas, "rgbs": rgbs, "feat": feat, "M": M, "nears": nears, "fars": fars}
+
+
+def renderer_schedule(N: int, n_alive: int, step: int, max_steps: int) -> int:
+    """Samples per live ray of the next march of NeRFRenderer.run_cuda's eval loop."""
+    return min(max(min(N // n_alive, 8), 1), max_steps - step)
+
+
+def render_frame_infer(rays_o, rays_d, field=None, *, table=None, mlp_params=None, lv: Optional[GridLevels] = None,
+                       bitfield=None, bound=1.0, cascade=1, G=128, min_near=0.1, max_steps=1024, dt_gamma=0.0,
+                       bg_color=None, T_thresh=1e-4, blob_scale=5.0, blob_std=0.2, schedule=None):
+    """H0 at inference: the eval loop of NeRFRenderer.run_cuda (march_rays_infer -> field -> composite_rays_infer ->
+    compact_rays), every ray taking at most `max_steps` samples.  field(xyzs [M,3]) -> (sigmas [M], rgbs [M,C]);
+    default: render_frame's grid encoder + MLP.  schedule=None marches every ray to its end in one call;
+    schedule(N, n_alive, step) -> n_step drives the oracle kernels in chunks instead (renderer_schedule is the
+    renderer's), carrying the per-ray state from one call to the next.  The composite is float64; returns
+    {'image', 'depth', 'weights_sum', 'transmittance', 'counts' (samples composited per ray)}."""
+    if field is None:
+        def field(x):
+            feat = grid_encode((x + bound) / (2.0 * bound), table, lv)
+            return sigma_latent_mlp(feat, x, mlp_params, blob_scale, blob_std)
+    rays_o = rays_o.to(torch.float32)
+    rays_d = rays_d.to(torch.float32)
+    N = rays_o.shape[0]
+    aabb = [-bound, -bound, -bound, bound, bound, bound]
+    nears, fars = near_far_from_aabb(rays_o, rays_d, aabb, min_near)
+    rays_t = nears.clone()
+    alive = torch.arange(N, dtype=torch.int32)
+    ws = depth = image = T = None
+    counts = torch.zeros(N, dtype=torch.int64)
+    step = 0
+    with torch.no_grad():
+        while step < max_steps and alive.shape[0] > 0:
+            n_alive = alive.shape[0]
+            n_step = max_steps - step if schedule is None else schedule(N, n_alive, step)
+            xyzs, dirs, deltas = march_rays_infer(alive, n_step, rays_t, rays_o, rays_d, fars, bitfield, bound,
+                                                  cascade, G, max_steps, dt_gamma)
+            real = deltas[:, 1] >= 0   # the field only sees real samples (padding rows are never composited)
+            sg = torch.zeros(xyzs.shape[0], dtype=torch.float64)
+            s_r, c_r = field(xyzs[real])
+            rg = torch.zeros(xyzs.shape[0], c_r.shape[1], dtype=torch.float64)
+            sg[real] = s_r.detach().to(torch.float64)
+            rg[real] = c_r.detach().to(torch.float64)
+            if ws is None:
+                C = rg.shape[1]
+                ws, depth = torch.zeros(N, dtype=torch.float64), torch.zeros(N, dtype=torch.float64)
+                image, T = torch.zeros(N, C, dtype=torch.float64), torch.ones(N, dtype=torch.float64)
+            before = T.clone()
+            new_alive, rays_t, ws, depth, image, T = composite_rays_infer(alive, n_step, rays_t, sg, rg, deltas, ws,
+                                                                          depth, image, T, T_thresh)
+            # samples consumed: real rows up to the first padding row or the one that took T below T_thresh
+            used = _consumed(deltas.reshape(n_alive, n_step, 2), sg.reshape(n_alive, n_step), before[alive.long()],
+                             T_thresh)
+            counts.index_add_(0, alive.long(), used)
+            alive = compact_rays(new_alive, n_alive)
+            step += n_step
+    if ws is None:
+        ws, depth = torch.zeros(N, dtype=torch.float64), torch.zeros(N, dtype=torch.float64)
+        image, T = torch.zeros(N, 0, dtype=torch.float64), torch.ones(N, dtype=torch.float64)
+    if bg_color is not None:
+        image = image + (1.0 - ws)[:, None] * bg_color.to(torch.float64)
+    return {"image": image, "depth": depth, "weights_sum": ws, "transmittance": T, "counts": counts}
+
+
+def _consumed(deltas, sigmas, T0, T_thresh):
+    """Per entry: how many of its rows composite_rays_infer composites (float64 T, same kill rule)."""
+    T = T0.clone()
+    used = torch.zeros(deltas.shape[0], dtype=torch.int64)
+    go = torch.ones(deltas.shape[0], dtype=torch.bool)
+    for s in range(deltas.shape[1]):
+        go = go & (deltas[:, s, 1] >= 0)
+        used += go.to(torch.int64)
+        alpha = 1.0 - torch.exp(-sigmas[:, s] * deltas[:, s, 0].to(torch.float64))
+        T = torch.where(go, T * (1.0 - alpha), T)
+        go = go & (T >= T_thresh)
+    return used
 
 
 def sphere_density_grid(G=128, cascade=1, bound=1.0, radius=0.5, value=10.0) -> torch.Tensor:

@@ -36,7 +36,9 @@ def prepare_vertices(verts, faces, rot, pos, fov=math.pi / 3):
 
 
 def rasterize(H, W, face_z, face_xy):
-    """-> face_idx [H*W] (long, -1 background), bary [H*W,3] perspective-correct."""
+    """-> face_idx [H*W] (long, -1 background), bary [H*W,3] perspective-correct.  f32 in k_rasterize's operation
+    order (w = e * (1 / area), q = w / z, z = 1 / (q0 + q1 + q2), b = q * z; every division correctly rounded), so
+    on the kernel's own face_z / face_xy the result is bit-exact."""
     j = torch.arange(W, dtype=torch.float32)
     i = torch.arange(H, dtype=torch.float32)
     px = ((2 * j + 1) / W - 1)[None, :].expand(H, W).reshape(-1)
@@ -48,15 +50,17 @@ def rasterize(H, W, face_z, face_xy):
     area = (x1 - x0) * (y2 - y0) - (x2 - x0) * (y1 - y0)
     e0 = (x1 - PX) * (y2 - PY) - (x2 - PX) * (y1 - PY)
     e1 = (x2 - PX) * (y0 - PY) - (x0 - PX) * (y2 - PY)
-    w0 = e0 / area
-    w1 = e1 / area
+    inv = 1.0 / area                                  # the kernel's order: one reciprocal, then products
+    w0 = e0 * inv
+    w1 = e1 * inv
     w2 = 1 - w0 - w1
     z0, z1, z2 = face_z[:, 0][None], face_z[:, 1][None], face_z[:, 2][None]
     ok = (w0 >= 0) & (w1 >= 0) & (w2 >= 0) & (area != 0) & (z0 < 0) & (z1 < 0) & (z2 < 0)
     q0, q1, q2 = w0 / z0, w1 / z1, w2 / z2
     z = 1.0 / (q0 + q1 + q2)
     z = torch.where(ok, z, torch.full_like(z, -3.0e38))
-    best_z, best_f = z.max(dim=1)                     # first max = lowest face index on ties
+    best_z = z.max(dim=1).values
+    best_f = (z == best_z[:, None]).to(torch.uint8).argmax(dim=1)   # ties go to the lowest face index
     hit = best_z > -1.0e38
     idx = torch.where(hit, best_f, torch.full_like(best_f, -1))
     g = best_f[:, None]

@@ -216,3 +216,111 @@ def test_trunc_exp_and_adam():
         opt.step()
         q, m, v = O.adam_step(q, g, m, v, step, 1e-2)
     assert torch.allclose(q, ref.detach(), atol=1e-6)
+
+
+def _infer_scene(N=400, seed=3, bound=2.0, miss_every=5):
+    """Rays from a sphere of radius 2.5*bound towards jittered points inside the box; every `miss_every`-th ray
+    points away from the box (near = far = FLT_MAX)."""
+    g = torch.Generator().manual_seed(seed)
+    eye = torch.randn(N, 3, generator=g)
+    ro = 2.5 * bound * eye / eye.norm(dim=-1, keepdim=True)
+    tgt = (torch.rand(N, 3, generator=g) - 0.5) * bound
+    rd = tgt - ro
+    rd[::miss_every] = ro[::miss_every]
+    rd = rd / rd.norm(dim=-1, keepdim=True)
+    return ro.float(), rd.float()
+
+
+def _march_in_chunks(n_step, ro, rd, nears, fars, bits, bound, cascade, G, max_steps, dt_gamma):
+    """Drive march_rays_infer the way the eval loop does (sigma 0: no ray dies before its padding), collecting the
+    samples of every ray across the calls."""
+    N = ro.shape[0]
+    alive = torch.arange(N, dtype=torch.int32)
+    rays_t = nears.clone()
+    per_ray = [[] for _ in range(N)]
+    ws, depth, image, T = torch.zeros(N), torch.zeros(N), torch.zeros(N, 1), torch.ones(N)
+    step = 0
+    while step < max_steps and alive.shape[0] > 0:
+        k = min(n_step, max_steps - step)
+        xyzs, dirs, deltas = O.march_rays_infer(alive, k, rays_t, ro, rd, fars, bits, bound, cascade, G, max_steps,
+                                                dt_gamma)
+        rows = torch.cat([xyzs, dirs, deltas], -1).reshape(alive.shape[0], k, 8)
+        for i, n in enumerate(alive.tolist()):
+            per_ray[n] += [r for r in rows[i] if float(r[7]) >= 0]
+        new_alive, rays_t, ws, depth, image, T = O.composite_rays_infer(
+            alive, k, rays_t, torch.zeros(alive.shape[0] * k), torch.zeros(alive.shape[0] * k, 1), deltas, ws, depth,
+            image, T)
+        alive = O.compact_rays(new_alive, alive.shape[0])
+        step += k
+    return per_ray
+
+
+@pytest.mark.parametrize("bound,cascade,dt_gamma", [(1.0, 1, 1.0 / 64), (2.0, 2, 1.0 / 128)])
+def test_infer_march_in_chunks_equals_training_march(bound, cascade, dt_gamma):
+    """With dt_gamma > 0 both marches walk t = t + clamp(t*dt_gamma, dt_min, dt_max) from near: the inference march,
+    restarted from the handed-over rays_t every n_step samples, emits exactly the training march's samples."""
+    G, max_steps = 16, 96
+    g = torch.Generator().manual_seed(11)
+    bits = O.packbits((torch.rand(cascade * G ** 3, generator=g) < 0.8).float(), 0.5)
+    ro, rd = _infer_scene(N=120, bound=bound)
+    nears, fars = O.near_far_from_aabb(ro, rd, [-bound] * 3 + [bound] * 3, 0.1)
+    xyzs, dirs, deltas, rays, M = O.march_rays_train(ro, rd, nears, fars, bits, bound, cascade, G, max_steps,
+                                                     dt_gamma, None)
+    # rays span several calls of every n_step, and with bound 2 the per-ray cap binds
+    assert int(rays[:, 2].max()) == max_steps if bound > 1 else int(rays[:, 2].max()) > 3 * 8
+    assert int((rays[:, 2] == 0).sum()) >= 120 // 5  # and the misses have no samples
+    want = torch.cat([xyzs, dirs, deltas], -1)
+    for n_step in (1, 3, 8):
+        per_ray = _march_in_chunks(n_step, ro, rd, nears, fars, bits, bound, cascade, G, max_steps, dt_gamma)
+        for n in range(ro.shape[0]):
+            o, c = int(rays[n, 1]), int(rays[n, 2])
+            assert len(per_ray[n]) == c, (n_step, n, len(per_ray[n]), c)
+            if c:
+                assert torch.equal(torch.stack(per_ray[n]), want[o:o + c]), (n_step, n)
+
+
+def test_infer_march_padding_and_dead_entries():
+    G, bound = 16, 1.0
+    bits = O.packbits(torch.ones(G ** 3), 0.5)
+    ro, rd = _infer_scene(N=16, bound=bound, miss_every=4)
+    nears, fars = O.near_far_from_aabb(ro, rd, [-bound] * 3 + [bound] * 3, 0.1)
+    alive = torch.tensor([5, -1, 0, 3, -1, 4], dtype=torch.int32)
+    xyzs, dirs, deltas = O.march_rays_infer(alive, 4, nears, ro, rd, fars, bits, bound, 1, G, 64, 0.0)
+    pad = torch.tensor([0.0, 0, 0, 0, 0, 1, 0, -1])
+    rows = torch.cat([xyzs, dirs, deltas], -1).reshape(6, 4, 8)
+    for i, n in enumerate(alive.tolist()):
+        if n < 0 or n % 4 == 0:   # dead entry, or a ray that misses the box: padding only
+            assert torch.equal(rows[i], pad.expand(4, 8)), i
+        else:
+            assert bool((rows[i, :, 7] >= nears[n]).all()) and bool((rows[i, :, 6] > 0).all())
+    assert torch.equal(O.compact_rays(alive, 6), torch.tensor([5, 0, 3, 4], dtype=torch.int32))
+    assert torch.equal(O.compact_rays(alive, 2), torch.tensor([5], dtype=torch.int32))
+
+
+def _fake_field(x):
+    """Deterministic elementwise field (mul/add only): low density in a shell, higher near the centre."""
+    r2 = x[:, 0] * x[:, 0] + x[:, 1] * x[:, 1] + x[:, 2] * x[:, 2]
+    sigma = 0.25 + 16.0 / (1.0 + 4.0 * r2)
+    rgb = torch.stack([0.5 + 0.25 * x[:, 0], 0.5 - 0.25 * x[:, 1], 0.25 + 0.125 * x[:, 2], 0.125 * r2], -1)
+    return sigma, rgb
+
+
+def test_render_frame_infer_is_independent_of_the_chunking():
+    """The eval loop's per-call state (rays_t, T, weights_sum, depth, image) is carried so that how the samples of a
+    ray are split over calls does not change a bit of its result; no ray takes more than max_steps samples."""
+    G, bound, cascade, max_steps = 16, 2.0, 2, 48
+    bits = O.packbits(torch.ones(cascade * G ** 3), 0.5)
+    ro, rd = _infer_scene(N=200, bound=bound)
+    bg = torch.rand(200, 4, generator=torch.Generator().manual_seed(2))
+    kw = dict(bitfield=bits, bound=bound, cascade=cascade, G=G, max_steps=max_steps, dt_gamma=1.0 / 128, bg_color=bg)
+    ref = O.render_frame_infer(ro, rd, _fake_field, **kw)
+    assert int(ref["counts"].max()) == max_steps                   # the cap binds on some rays,
+    assert bool((ref["transmittance"] < 1e-4).any())               # some die by T_thresh,
+    assert int((ref["counts"] == 0).sum()) >= 200 // 5             # and the misses take no sample
+    scheds = [lambda N, a, s: 1, lambda N, a, s: min(3, max_steps - s), lambda N, a, s: min(8, max_steps - s),
+              lambda N, a, s: O.renderer_schedule(N, a, s, max_steps),
+              lambda N, a, s: min(1 + (s % 7), max_steps - s)]
+    for sched in scheds:
+        out = O.render_frame_infer(ro, rd, _fake_field, schedule=sched, **kw)
+        for k in ("image", "depth", "weights_sum", "transmittance", "counts"):
+            assert torch.equal(out[k], ref[k]), k

@@ -3,6 +3,7 @@ extension of the absent src/latent_nerf/models/encoders (SURVEY.md Appendix A); 
 table follows the align_corners=False convention recorded there."""
 import ctypes
 import math
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -51,6 +52,13 @@ class GridLevels:
         self.c_res = (ctypes.c_int32 * num_levels)(*ress)
 
 
+def _grid_args(levels: GridLevels, xyzs, bound, m_host, m_dev, level_stride, src, src_dtype=_b.F32):
+    """The arguments every gather / scatter entry point starts with (src: the table of a gather, dfeat of a scatter)."""
+    return (_chk(xyzs, "xyzs"), float(bound), src, src_dtype, levels.num_levels, levels.level_dim, levels.c_offsets,
+            levels.c_scales, levels.c_res, int(m_host), _chk(m_dev, "m_dev", torch.int32, allow_none=True),
+            int(level_stride))
+
+
 def grid_encode_forward(xyzs, bound, table, levels: GridLevels, m_host, m_dev, level_stride, out=None,
                         out_dtype=torch.float32, variant=0):
     """xyzs [>=m_host,3] world positions -> level-major features [L, level_stride, 2]."""
@@ -60,10 +68,9 @@ def grid_encode_forward(xyzs, bound, table, levels: GridLevels, m_host, m_dev, l
     if out is None:
         out = torch.empty(levels.num_levels, level_stride, 2, device=xyzs.device, dtype=out_dtype)
     odt = _b.F32 if out.dtype == torch.float32 else _b.BF16
-    _b.call("lnerf_grid_encode_forward", _chk(xyzs, "xyzs"), float(bound), _chk(table, "table", table.dtype), tdt,
-            levels.num_levels, levels.level_dim, levels.c_offsets, levels.c_scales, levels.c_res, int(m_host),
-            _chk(m_dev, "m_dev", torch.int32, allow_none=True), int(level_stride), _chk(out, "feat", out.dtype), odt,
-            int(variant) | levels.flag, _stream())
+    _b.call("lnerf_grid_encode_forward", *_grid_args(levels, xyzs, bound, m_host, m_dev, level_stride,
+                                                     _chk(table, "table", table.dtype), tdt),
+            _chk(out, "feat", out.dtype), odt, int(variant) | levels.flag, _stream())
     return out
 
 
@@ -149,10 +156,9 @@ def grid_encode_backward(xyzs, bound, dfeat, levels: GridLevels, m_host, m_dev, 
         wst = scatter_workspace(levels, m_host, xyzs.device)
         ws, ws_bytes = _p(wst), wst.numel()
         ws_mark_dirty(xyzs.device)      # (this call leaves its level maxima in the shared workspace)
-    _b.call("lnerf_grid_encode_backward", _chk(xyzs, "xyzs"), float(bound), _chk(dfeat, "dfeat"), _b.F32,
-            levels.num_levels, levels.level_dim, levels.c_offsets, levels.c_scales, levels.c_res, int(m_host),
-            _chk(m_dev, "m_dev", torch.int32, allow_none=True), int(level_stride), _chk(dtable, "dtable"),
-            int(variant) | levels.flag, ws, ws_bytes, _stream())
+    _b.call("lnerf_grid_encode_backward", *_grid_args(levels, xyzs, bound, m_host, m_dev, level_stride,
+                                                      _chk(dfeat, "dfeat")),
+            _chk(dtable, "dtable"), int(variant) | levels.flag, ws, ws_bytes, _stream())
     return dtable
 
 
@@ -179,13 +185,6 @@ class FusedTableUpdate:
         self.closed = False
         self.inline_tail = False            # set by FusedAdam: the tail may run inside the scatter (no other small parameter)
 
-    def take(self):
-        """True once per arm(): the caller (a backward pass) then owes the fused update."""
-        if self.armed:
-            self.armed = False
-            return True
-        return False
-
 
 def grid_encode_backward_adam(xyzs, bound, dfeat, encoder, m_host, m_dev, level_stride, variant):
     """Scatter of dfeat fused with the Adam step of encoder.embeddings (see include/lnerf_hip.h)."""
@@ -195,15 +194,12 @@ def grid_encode_backward_adam(xyzs, bound, dfeat, encoder, m_host, m_dev, level_
         raise _b.LnerfError("the fused table update needs the bucketed scatter (variant 2 or 3)")
     wst = scatter_workspace(levels, m_host, xyzs.device)
     opt = fu.optimizer
-    table = encoder.embeddings.data
-    shadow = encoder.shadow()
     b1, b2 = fu.betas
-    _b.call("lnerf_grid_encode_backward_adam", _chk(xyzs, "xyzs"), float(bound), _chk(dfeat, "dfeat"), _b.F32,
-            levels.num_levels, levels.level_dim, levels.c_offsets, levels.c_scales, levels.c_res, int(m_host),
-            _chk(m_dev, "m_dev", torch.int32, allow_none=True), int(level_stride), _p(fu.zero), int(variant) | levels.flag,
-            _p(wst), wst.numel(), _p(table), _p(fu.exp_avg), _p(fu.exp_avg_sq), _p(shadow), fu.lr, b1, b2, fu.eps,
-            opt.step_no + 1, _p(opt.step_dev), float(opt.grad_scale), _stream())
-    fu.applied += 1
+    _b.call("lnerf_grid_encode_backward_adam", *_grid_args(levels, xyzs, bound, m_host, m_dev, level_stride,
+                                                           _chk(dfeat, "dfeat")),
+            _p(fu.zero), int(variant) | levels.flag, _p(wst), wst.numel(), _p(encoder.embeddings.data), _p(fu.exp_avg),
+            _p(fu.exp_avg_sq), _p(encoder.shadow()), fu.lr, b1, b2, fu.eps, opt.step_no + 1, _p(opt.step_dev),
+            float(opt.grad_scale), _stream())
     ws_mark_dirty(xyzs.device)
 
 
@@ -218,15 +214,12 @@ def grid_encode_backward_adam_tail(xyzs, bound, dfeat, encoder, m_host, m_dev, l
     t = opt.tail_args()
     wst = scatter_workspace(levels, m_host, xyzs.device)
     b1, b2 = fu.betas
-    _b.call("lnerf_grid_encode_backward_adam_tail", _chk(xyzs, "xyzs"), float(bound), _chk(dfeat, "dfeat"), _b.F32,
-            levels.num_levels, levels.level_dim, levels.c_offsets, levels.c_scales, levels.c_res, int(m_host),
-            _chk(m_dev, "m_dev", torch.int32, allow_none=True), int(level_stride), _p(fu.zero), int(variant) | levels.flag,
-            _p(wst), wst.numel(), _p(encoder.embeddings.data), _p(fu.exp_avg), _p(fu.exp_avg_sq), _p(encoder.shadow()),
-            fu.lr, _p(mlp_ws), mlp_ws.numel(), int(precision), int(out_dim), t["p"], t["m"], t["v"], float(t["lr"]),
-            t["maps"], b1, b2, fu.eps, opt.step_no + 1, _p(opt.step_dev), float(opt.grad_scale),
-            _b.TAIL_TICK | _b.TAIL_CLEAR_SCATTER, _stream())
-    fu.applied += 1
-    fu.closed = True                 # optimizer.step() has nothing left to launch
+    _b.call("lnerf_grid_encode_backward_adam_tail", *_grid_args(levels, xyzs, bound, m_host, m_dev, level_stride,
+                                                                _chk(dfeat, "dfeat")),
+            _p(fu.zero), int(variant) | levels.flag, _p(wst), wst.numel(), _p(encoder.embeddings.data), _p(fu.exp_avg),
+            _p(fu.exp_avg_sq), _p(encoder.shadow()), fu.lr, _p(mlp_ws), mlp_ws.numel(), int(precision), int(out_dim),
+            t["p"], t["m"], t["v"], float(t["lr"]), t["maps"], b1, b2, fu.eps, opt.step_no + 1, _p(opt.step_dev),
+            float(opt.grad_scale), _b.TAIL_TICK | _b.TAIL_CLEAR_SCATTER, _stream())
     ws_mark_clean(wst)               # (level maxima zero again when the launch ends)
 
 
@@ -242,7 +235,6 @@ class GradSink:
     def __init__(self, table, groups=None):
         self.wire = torch.zeros(table.shape, device=table.device, dtype=torch.bfloat16)
         self.zero = torch.zeros(table.shape, device=table.device, dtype=torch.float32)  # overflow records only
-        self.written = 0
         self.groups = groups
         self.pending = None   # (bound, levels, m_host, level_stride, variant, workspace) of a binned, not yet summed backward
         # {data_ptr of a small parameter: its view of GradSync's flat bucket}: a backward pass may write such a gradient
@@ -269,25 +261,22 @@ def level_groups(levels: GridLevels, n_groups=4):
     return out
 
 
-def grid_encode_backward_bf16(xyzs, bound, dfeat, encoder, m_host, m_dev, level_stride, variant):
+def grid_encode_backward_bf16(xyzs, bound, dfeat, encoder, m_host, m_dev, level_stride, variant, binned=False):
+    """encoder.grad_sink.wire = the table gradient in bf16 (written, not accumulated).  binned: pass 1 only
+    (lnerf_grid_scatter_bin), grid_scatter_reduce_group sums the records later.  Returns the scatter workspace."""
     sink = encoder.grad_sink
     levels = encoder.levels
     if variant < 2:
         raise _b.LnerfError("the bf16 gradient output needs the bucketed scatter (variant 2 or 3)")
     wst = scatter_workspace(levels, m_host, xyzs.device)
     ws_mark_dirty(xyzs.device)
-    if sink.groups:   # pipelined: pass 1 now, pass 2 per level group inside GradSync.allreduce_pipelined()
-        _b.call("lnerf_grid_scatter_bin", _chk(xyzs, "xyzs"), float(bound), _chk(dfeat, "dfeat"), _b.F32,
-                levels.num_levels, levels.level_dim, levels.c_offsets, levels.c_scales, levels.c_res, int(m_host),
-                _chk(m_dev, "m_dev", torch.int32, allow_none=True), int(level_stride), _p(sink.zero),
-                int(variant) | levels.flag, _p(wst), wst.numel(), _stream())
-        sink.pending = (float(bound), levels, int(m_host), int(level_stride), int(variant), wst)
-        return
-    _b.call("lnerf_grid_encode_backward_bf16", _chk(xyzs, "xyzs"), float(bound), _chk(dfeat, "dfeat"), _b.F32,
-            levels.num_levels, levels.level_dim, levels.c_offsets, levels.c_scales, levels.c_res, int(m_host),
-            _chk(m_dev, "m_dev", torch.int32, allow_none=True), int(level_stride), _p(sink.zero),
-            int(variant) | levels.flag, _p(wst), wst.numel(), _p(sink.wire), _stream())
-    sink.written += 1
+    args = (*_grid_args(levels, xyzs, bound, m_host, m_dev, level_stride, _chk(dfeat, "dfeat")), _p(sink.zero),
+            int(variant) | levels.flag, _p(wst), wst.numel())
+    if binned:
+        _b.call("lnerf_grid_scatter_bin", *args, _stream())
+    else:
+        _b.call("lnerf_grid_encode_backward_bf16", *args, _p(sink.wire), _stream())
+    return wst
 
 
 def grid_scatter_reduce_group(sink: GradSink, level_lo, level_hi):
@@ -301,42 +290,111 @@ def grid_scatter_reduce_group(sink: GradSink, level_lo, level_hi):
             _p(wst), wst.numel(), _p(sink.wire), _stream())
 
 
+class Route(NamedTuple):
+    """What one backward through the encoder does with the table gradient (`name`), and what the fused MLP launch in
+    front of its scatter owes for it -- see backward_route:
+      plain              lnerf_grid_encode_backward into a fresh f32 gradient of the table
+      wire               lnerf_grid_encode_backward_bf16 into GradSink.wire (data parallel, bf16 on the wire)
+      bin                lnerf_grid_scatter_bin; pass 2 follows per level group in GradSync.allreduce_pipelined()
+      adam               lnerf_grid_encode_backward_adam: the table's Adam step inside the scatter (FusedAdam.arm())
+      adam_tail          the same; FusedAdam.step() closes the step (lnerf_step_tail)
+      adam_closing_tail  lnerf_grid_encode_backward_adam_tail: the scatter's pass 2 closes the step itself
+    On a tail route the MLP launch writes no weight gradient: the step's tail sums its gradient slabs."""
+    name: str
+    variant: int                          # the scatter's variant, SCATTER_CLEARED included
+    clear: bool = False                   # the MLP launch clears the scatter's cursors on the side
+    views: Optional[list] = None          # ... and writes its weight gradients into these views of the exchange bucket
+    ws: Optional[torch.Tensor] = None     # the scatter workspace (plan_backward)
+
+    @property
+    def tail(self):
+        return self.name in ("adam_tail", "adam_closing_tail")
+
+    def mlp_args(self, levels: GridLevels, m_host):
+        """(flags OR-ed into the MLP backward's precision tag, clear_ptr, clear_bytes)."""
+        clear = (_p(self.ws), scatter_clear_bytes(levels, m_host)) if self.clear else (None, 0)
+        return (_b.MLP_DEFER_REDUCE if self.tail else 0,) + clear
+
+
+def backward_route(fu, sink, variant, m_host, mlp=None, own_ws=False, ws_clean=False):
+    """The Route of one backward through an encoder (reads its arguments, changes nothing).  fu, sink: the encoder's
+    FusedTableUpdate and GradSink or None; variant: its scatter variant; mlp: the six tensors of the fused MLP node whose
+    launch precedes the scatter (None: the bare encoder); own_ws: that launch runs in the node's own workspace (the tail
+    reads the gradient slabs there); ws_clean: the scatter workspace's level maxima are zero (ws_is_clean)."""
+    bucketed = variant >= 2 and m_host > 0
+    armed = fu is not None and fu.armed
+    if armed and fu.tail and mlp is not None and own_ws and bucketed:
+        return Route("adam_closing_tail" if fu.inline_tail else "adam_tail",
+                     variant | (_b.SCATTER_CLEARED if ws_clean else 0))
+    clear = mlp is not None and bucketed       # (one dispatch less per step than the scatter's own fill)
+    views = None
+    if mlp is not None and sink is not None and sink.groups and sink.small_direct:
+        # pipelined exchange: no `.grad`, no pack copy into the flat bucket the all-reduce sends (one dispatch less)
+        found = [sink.small_direct.get(t.data_ptr()) for t in mlp]
+        if all(v is not None and v.shape == t.shape for v, t in zip(found, mlp)):
+            views = found
+    name = "adam" if armed else "plain" if sink is None else "bin" if sink.groups else "wire"
+    return Route(name, variant | (_b.SCATTER_CLEARED if clear else 0), clear, views)
+
+
+def plan_backward(encoder, m_host, device, mlp=None, own_ws=False):
+    """backward_route() of a backward through `encoder` now (arguments as there), with the scatter workspace."""
+    sv = encoder.scatter_variant
+    ws = scatter_workspace(encoder.levels, m_host, device) if (mlp is not None and sv >= 2 and m_host > 0) else None
+    return backward_route(encoder.fused_update, encoder.grad_sink, sv, m_host, mlp, own_ws,
+                          ws is not None and ws_is_clean(ws))._replace(ws=ws)
+
+
+def run_backward(route, xyzs, bound, dfeat, encoder, m_host, m_dev, level_stride, mlp_ws=None, precision=0, out_dim=0):
+    """Issues the scatter of a planned `route` and the bookkeeping it owes (each scatter call marks the shared workspace
+    itself); mlp_ws, precision, out_dim: the fused MLP's, for the tail.  -> the f32 table gradient of the plain route."""
+    fu, sink, levels = encoder.fused_update, encoder.grad_sink, encoder.levels
+    args = (xyzs, bound, dfeat, encoder, m_host, m_dev, level_stride, route.variant)
+    if route.name == "plain":
+        return grid_encode_backward(xyzs, bound, dfeat, levels, m_host, m_dev, level_stride,
+                                    torch.zeros(encoder.embeddings.shape, device=xyzs.device), route.variant)
+    if route.name == "wire":
+        grid_encode_backward_bf16(*args)
+    elif route.name == "bin":
+        # (`pending` stays after the exchange: a replayed hipGraph bins again without running any Python)
+        sink.pending = (float(bound), levels, int(m_host), int(level_stride), int(route.variant),
+                        grid_encode_backward_bf16(*args, binned=True))
+    else:
+        fu.armed = False
+        if route.name == "adam_closing_tail":
+            grid_encode_backward_adam_tail(*args, mlp_ws, precision, out_dim)
+            fu.closed = True         # optimizer.step() has nothing left to launch
+        else:
+            grid_encode_backward_adam(*args)
+            if route.name == "adam_tail":
+                fu.pending_tail = (levels, int(m_host), int(encoder.scatter_variant), route.ws, mlp_ws, int(precision),
+                                   int(out_dim))
+        fu.applied += 1
+    if route.views is not None:
+        sink.small_written = True
+
+
 class _GridEncode(torch.autograd.Function):
     """feat = encode(xyzs; table).  `table` is the f32 master parameter (gradient target);
     `shadow` an optional bf16 copy that the gather actually reads."""
 
     @staticmethod
-    def forward(ctx, xyzs, table, shadow, levels, bound, m_host, m_dev, level_stride, feat_dtype, variant,
-                scatter_variant, encoder=None):
+    def forward(ctx, xyzs, table, shadow, encoder, bound, m_host, m_dev, level_stride, feat_dtype):
         src = table if shadow is None else shadow
-        feat = grid_encode_forward(xyzs, bound, src.detach(), levels, m_host, m_dev, level_stride, None, feat_dtype,
-                                   variant)
+        feat = grid_encode_forward(xyzs, bound, src.detach(), encoder.levels, m_host, m_dev, level_stride, None,
+                                   feat_dtype, encoder.variant)
         ctx.save_for_backward(xyzs, m_dev if m_dev is not None else torch.empty(0))
-        ctx.has_mdev = m_dev is not None
-        ctx.meta = (levels, bound, m_host, level_stride, scatter_variant, table.shape, table.device)
-        ctx.encoder = encoder
+        ctx.meta = (encoder, bound, m_host, m_dev is not None, level_stride)
         return feat
 
     @staticmethod
     def backward(ctx, dfeat):
         xyzs, m_dev = ctx.saved_tensors
-        levels, bound, m_host, level_stride, variant, shape, dev = ctx.meta
-        dfeat = dfeat.contiguous()
-        if dfeat.dtype != torch.float32:
-            dfeat = dfeat.float()
-        enc = ctx.encoder
-        if enc is not None and enc.fused_update is not None and enc.fused_update.take():
-            grid_encode_backward_adam(xyzs, bound, dfeat, enc, m_host, m_dev if ctx.has_mdev else None, level_stride,
-                                      variant)
-            return (None,) * 12
-        if enc is not None and enc.grad_sink is not None:
-            grid_encode_backward_bf16(xyzs, bound, dfeat, enc, m_host, m_dev if ctx.has_mdev else None, level_stride,
-                                      variant)
-            return (None,) * 12
-        dtable = torch.zeros(shape, device=dev, dtype=torch.float32)
-        grid_encode_backward(xyzs, bound, dfeat, levels, m_host, m_dev if ctx.has_mdev else None, level_stride,
-                             dtable, variant)
-        return None, dtable, None, None, None, None, None, None, None, None, None, None
+        encoder, bound, m_host, has_mdev, level_stride = ctx.meta
+        dfeat = dfeat.contiguous().float()
+        route = plan_backward(encoder, m_host, xyzs.device)
+        dtable = run_backward(route, xyzs, bound, dfeat, encoder, m_host, m_dev if has_mdev else None, level_stride)
+        return None, dtable, None, None, None, None, None, None, None
 
 
 class GridEncoder(nn.Module):
@@ -384,8 +442,8 @@ class GridEncoder(nn.Module):
         """Level-major features [L, level_stride, 2] (differentiable w.r.t. embeddings)."""
         if level_stride is None:
             level_stride = xyzs.shape[0]
-        return _GridEncode.apply(xyzs, self.embeddings, self.shadow(), self.levels, bound, m_host, m_dev, level_stride,
-                                 feat_dtype, self.variant, self.scatter_variant, self)
+        return _GridEncode.apply(xyzs, self.embeddings, self.shadow(), self, bound, m_host, m_dev, level_stride,
+                                 feat_dtype)
 
     def forward(self, inputs, bound=1.0):
         """inputs [..., 3] in [-bound, bound] -> [..., L*2] (sample-major view, as the upstream encoder)."""

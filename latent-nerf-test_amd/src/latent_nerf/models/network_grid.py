@@ -8,55 +8,76 @@ import torch.nn as nn
 
 from ..raymarching import backend as _b
 from ..raymarching.raymarching import _chk, _p, _stream
+from . import encoding as E
 from .encoding import GridEncoder
 from .nerf_utils import NeRFType
 from .renderer import NeRFRenderer
 
 _PREC = {"f32": _b.F32, "bf16": _b.BF16}
+_W = ("w1", "b1", "w2", "b2", "w3", "b3")
+
+
+def _mlp_forward(ctx, feat, xyzs, W, m_host, m_dev, level_stride, blob_scale, blob_std, precision, workspace,
+                 frag_ready=False):
+    """lnerf_mlp_forward -> sigmas [level_stride], rgbs [level_stride, out_dim - 1] (f32); saves ctx for the backward."""
+    out_dim = W[4].shape[0]
+    sigmas = torch.empty(level_stride, device=xyzs.device, dtype=torch.float32)
+    rgbs = torch.empty(level_stride, out_dim - 1, device=xyzs.device, dtype=torch.float32)
+    _b.call("lnerf_mlp_forward", _chk(feat, "feat", feat.dtype), _b.F32 if feat.dtype == torch.float32 else _b.BF16,
+            int(level_stride), _chk(xyzs, "xyzs"), *[_chk(t, n) for t, n in zip(W, _W)], out_dim, float(blob_scale),
+            float(blob_std), int(m_host), _chk(m_dev, "m_dev", torch.int32, allow_none=True), _p(sigmas), _p(rgbs),
+            precision | (_b.MLP_FRAGMENTS_READY if (frag_ready and precision == _b.BF16) else 0), _p(workspace),
+            0 if workspace is None else workspace.numel(), _stream())
+    ctx.save_for_backward(feat, xyzs, *W, sigmas, m_dev if m_dev is not None else torch.empty(0))
+    ctx.meta = (m_host, m_dev is not None, level_stride, blob_scale, blob_std, precision, workspace)
+    ctx.set_materialize_grads(False)
+    return sigmas, rgbs
+
+
+def _mlp_backward_workspace(workspace, precision, out_dim, device):
+    """(workspace, precision tag, own): the node's own workspace when it is large enough, else a fresh one."""
+    need = _b.get_lib().lnerf_mlp_backward_workspace_bytes(out_dim)
+    if workspace is None or workspace.numel() < need:
+        return torch.empty(need, device=device, dtype=torch.uint8), precision, False
+    if precision == _b.BF16:
+        # this node's forward left the weight fragments at the head of the same workspace, and autograd's version check
+        # on the saved weights guarantees they have not changed since
+        precision |= _b.MLP_FRAGMENTS_READY
+    return workspace, precision, True
+
+
+def _mlp_backward(feat, xyzs, W, sigmas, m_host, m_dev, level_stride, blob_scale, blob_std, dsigmas, drgbs, grads,
+                  workspace, precision, clear_ptr=None, clear_bytes=0):
+    """lnerf_mlp_backward -> dfeat (f32); writes the weight gradients into `grads` (Nones: the step's tail sums them)."""
+    out_dim = W[4].shape[0]
+    dev = xyzs.device
+    dsigmas = torch.zeros_like(sigmas) if dsigmas is None else dsigmas.contiguous()
+    drgbs = torch.zeros(level_stride, out_dim - 1, device=dev) if drgbs is None else drgbs.contiguous()
+    dfeat = torch.empty(feat.shape, device=dev, dtype=torch.float32)
+    _b.call("lnerf_mlp_backward", _p(feat), _b.F32 if feat.dtype == torch.float32 else _b.BF16, int(level_stride),
+            _p(xyzs), *[_p(t) for t in W], out_dim, float(blob_scale), float(blob_std), int(m_host), _p(m_dev),
+            _p(sigmas), _chk(dsigmas, "dsigmas"), _chk(drgbs, "drgbs"), _p(dfeat), *[_p(g) for g in grads], 0,
+            _p(workspace), workspace.numel(), precision, clear_ptr, clear_bytes, _stream())
+    return dfeat
 
 
 class _SigmaLatentMLP(torch.autograd.Function):
+    """sigmas, rgbs = MLP(feat) of given level-major features."""
+
     @staticmethod
     def forward(ctx, feat, xyzs, w1, b1, w2, b2, w3, b3, m_host, m_dev, level_stride, blob_scale, blob_std,
                 precision, workspace):
-        out_dim = w3.shape[0]
-        dev = xyzs.device
-        sigmas = torch.empty(level_stride, device=dev, dtype=torch.float32)
-        rgbs = torch.empty(level_stride, out_dim - 1, device=dev, dtype=torch.float32)
-        fdt = _b.F32 if feat.dtype == torch.float32 else _b.BF16
-        _b.call("lnerf_mlp_forward", _chk(feat, "feat", feat.dtype), fdt, int(level_stride), _chk(xyzs, "xyzs"),
-                _chk(w1, "w1"), _chk(b1, "b1"), _chk(w2, "w2"), _chk(b2, "b2"), _chk(w3, "w3"), _chk(b3, "b3"),
-                out_dim, float(blob_scale), float(blob_std), int(m_host),
-                _chk(m_dev, "m_dev", torch.int32, allow_none=True), _p(sigmas), _p(rgbs), precision, _p(workspace),
-                0 if workspace is None else workspace.numel(), _stream())
-        ctx.save_for_backward(feat, xyzs, w1, b1, w2, b2, w3, b3, sigmas,
-                              m_dev if m_dev is not None else torch.empty(0))
-        ctx.meta = (m_host, m_dev is not None, level_stride, blob_scale, blob_std, precision, workspace)
-        ctx.set_materialize_grads(False)
-        return sigmas, rgbs
+        return _mlp_forward(ctx, feat, xyzs, (w1, b1, w2, b2, w3, b3), m_host, m_dev, level_stride, blob_scale,
+                            blob_std, precision, workspace)
 
     @staticmethod
     def backward(ctx, dsigmas, drgbs):
-        feat, xyzs, w1, b1, w2, b2, w3, b3, sigmas, m_dev = ctx.saved_tensors
+        feat, xyzs, *W, sigmas, m_dev = ctx.saved_tensors
         m_host, has_mdev, level_stride, blob_scale, blob_std, precision, workspace = ctx.meta
-        out_dim = w3.shape[0]
-        dev = xyzs.device
-        dsigmas = torch.zeros_like(sigmas) if dsigmas is None else dsigmas.contiguous()
-        drgbs = torch.zeros(level_stride, out_dim - 1, device=dev) if drgbs is None else drgbs.contiguous()
-        dfeat = torch.empty(feat.shape, device=dev, dtype=torch.float32)
-        grads = [torch.empty_like(t) for t in (w1, b1, w2, b2, w3, b3)]  # overwritten (accumulate = 0)
-        need = _b.get_lib().lnerf_mlp_backward_workspace_bytes(out_dim)
-        if workspace is None or workspace.numel() < need:
-            workspace = torch.empty(need, device=dev, dtype=torch.uint8)
-        elif precision == _b.BF16:
-            # this node's forward left the weight fragments at the head of the same workspace, and autograd's
-            # version check on the saved weights guarantees they have not changed since
-            precision |= _b.MLP_FRAGMENTS_READY
-        fdt = _b.F32 if feat.dtype == torch.float32 else _b.BF16
-        _b.call("lnerf_mlp_backward", _p(feat), fdt, int(level_stride), _p(xyzs), _p(w1), _p(b1), _p(w2), _p(b2),
-                _p(w3), _p(b3), out_dim, float(blob_scale), float(blob_std), int(m_host),
-                _p(m_dev) if has_mdev else None, _p(sigmas), _chk(dsigmas, "dsigmas"), _chk(drgbs, "drgbs"),
-                _p(dfeat), *[_p(g) for g in grads], 0, _p(workspace), workspace.numel(), precision, None, 0, _stream())
+        grads = [torch.empty_like(t) for t in W]
+        workspace, precision, _own = _mlp_backward_workspace(workspace, precision, W[4].shape[0], xyzs.device)
+        dfeat = _mlp_backward(feat, xyzs, W, sigmas, m_host, m_dev if has_mdev else None, level_stride, blob_scale,
+                              blob_std, dsigmas, drgbs, grads, workspace, precision)
         return (dfeat, None, *grads, None, None, None, None, None, None, None)
 
 
@@ -64,108 +85,35 @@ class _HashMLPField(torch.autograd.Function):
     """sigma, latent = MLP(hash_encode(xyzs)) as ONE autograd node: the level-major feature tensor (f32 or
     bf16) and its f32 gradient stay internal, so autograd never re-casts or copies them.
     forward : gather (lnerf_grid_encode_forward) -> MLP (lnerf_mlp_forward)
-    backward: MLP backward (-> dfeat f32, weight grads) -> scatter (lnerf_grid_encode_backward)."""
+    backward: MLP backward (-> dfeat f32, weight grads) -> scatter, as the route of encoding.plan_backward says."""
 
     @staticmethod
     def forward(ctx, xyzs, table, shadow, w1, b1, w2, b2, w3, b3, encoder, bound, m_host, m_dev, level_stride,
                 blob_scale, blob_std, precision, workspace, frag_ready):
-        from . import encoding as E
-        levels = encoder.levels
         src = table if shadow is None else shadow
         feat_dtype = torch.bfloat16 if precision == _b.BF16 else torch.float32
-        feat = E.grid_encode_forward(xyzs, bound, src.detach(), levels, m_host, m_dev, level_stride, None, feat_dtype,
-                                     encoder.variant)
-        out_dim = w3.shape[0]
-        dev = xyzs.device
-        sigmas = torch.empty(level_stride, device=dev, dtype=torch.float32)
-        rgbs = torch.empty(level_stride, out_dim - 1, device=dev, dtype=torch.float32)
-        fdt = _b.F32 if feat.dtype == torch.float32 else _b.BF16
-        _b.call("lnerf_mlp_forward", _p(feat), fdt, int(level_stride), _chk(xyzs, "xyzs"), _chk(w1, "w1"),
-                _chk(b1, "b1"), _chk(w2, "w2"), _chk(b2, "b2"), _chk(w3, "w3"), _chk(b3, "b3"), out_dim,
-                float(blob_scale), float(blob_std), int(m_host), _chk(m_dev, "m_dev", torch.int32, allow_none=True),
-                _p(sigmas), _p(rgbs), precision | (_b.MLP_FRAGMENTS_READY if (frag_ready and precision == _b.BF16) else 0),
-                _p(workspace), 0 if workspace is None else workspace.numel(), _stream())
-        ctx.save_for_backward(xyzs, feat, w1, b1, w2, b2, w3, b3, sigmas,
-                              m_dev if m_dev is not None else torch.empty(0))
-        ctx.meta = (encoder, bound, m_host, m_dev is not None, level_stride, blob_scale, blob_std, precision, workspace,
-                    table.shape)
-        ctx.set_materialize_grads(False)
-        return sigmas, rgbs
+        feat = E.grid_encode_forward(xyzs, bound, src.detach(), encoder.levels, m_host, m_dev, level_stride, None,
+                                     feat_dtype, encoder.variant)
+        ctx.field = (encoder, bound)
+        return _mlp_forward(ctx, feat, xyzs, (w1, b1, w2, b2, w3, b3), m_host, m_dev, level_stride, blob_scale,
+                            blob_std, precision, workspace, frag_ready)
 
     @staticmethod
     def backward(ctx, dsigmas, drgbs):
-        from . import encoding as E
-        xyzs, feat, w1, b1, w2, b2, w3, b3, sigmas, m_dev = ctx.saved_tensors
-        (encoder, bound, m_host, has_mdev, level_stride, blob_scale, blob_std, precision, workspace,
-         tshape) = ctx.meta
+        feat, xyzs, *W, sigmas, m_dev = ctx.saved_tensors
+        m_host, has_mdev, level_stride, blob_scale, blob_std, precision, workspace = ctx.meta
+        encoder, bound = ctx.field
         m_dev = m_dev if has_mdev else None
-        out_dim = w3.shape[0]
-        dev = xyzs.device
-        dsigmas = torch.zeros_like(sigmas) if dsigmas is None else dsigmas.contiguous()
-        drgbs = torch.zeros(level_stride, out_dim - 1, device=dev) if drgbs is None else drgbs.contiguous()
-        dfeat = torch.empty(feat.shape, device=dev, dtype=torch.float32)
-        need = _b.get_lib().lnerf_mlp_backward_workspace_bytes(out_dim)
-        own_ws = workspace is not None and workspace.numel() >= need
-        base_precision = precision
-        if not own_ws:
-            workspace = torch.empty(need, device=dev, dtype=torch.uint8)
-        elif precision == _b.BF16:
-            # this node's forward left the weight fragments at the head of the same workspace, and autograd's
-            # version check on the saved weights guarantees they have not changed since
-            precision |= _b.MLP_FRAGMENTS_READY
-        fdt = _b.F32 if feat.dtype == torch.float32 else _b.BF16
-        fu = encoder.fused_update
-        sv = encoder.scatter_variant
-        # TAIL mode (FusedAdam(tail=True), armed, m_host > 0): the slab sum and the Adam step of the six MLP tensors are
-        # left to the scatter's own pass 2 (or, with other small parameters around, to ONE launch in optimizer.step():
-        # lnerf_step_tail): no weight gradients here
-        tail = fu is not None and fu.armed and fu.tail and own_ws and sv >= 2 and m_host > 0
-        if tail:
-            wst = E.scatter_workspace(encoder.levels, m_host, dev)
-            _b.call("lnerf_mlp_backward", _p(feat), fdt, int(level_stride), _p(xyzs), _p(w1), _p(b1), _p(w2), _p(b2),
-                    _p(w3), _p(b3), out_dim, float(blob_scale), float(blob_std), int(m_host), _p(m_dev), _p(sigmas),
-                    _chk(dsigmas, "dsigmas"), _chk(drgbs, "drgbs"), _p(dfeat), None, None, None, None, None, None, 0,
-                    _p(workspace), workspace.numel(), precision | _b.MLP_DEFER_REDUCE, None, 0, _stream())
-            fu.take()
-            flags = _b.SCATTER_CLEARED if E.ws_is_clean(wst) else 0
-            if fu.inline_tail:   # the scatter's pass 2 closes the step: no launch behind it
-                E.grid_encode_backward_adam_tail(xyzs, bound, dfeat, encoder, m_host, m_dev, level_stride, sv | flags,
-                                                 workspace, base_precision, out_dim)
-            else:
-                E.grid_encode_backward_adam(xyzs, bound, dfeat, encoder, m_host, m_dev, level_stride, sv | flags)
-                fu.pending_tail = (encoder.levels, int(m_host), int(sv), wst, workspace, int(base_precision), int(out_dim))
-            return (None,) * 19
-        # data parallel, pipelined exchange: the six weight gradients are written straight into their views of the flat
-        # bucket the all-reduce sends (no `.grad`, no pack copy: one dispatch less per step)
-        sink, direct = encoder.grad_sink, None
-        if sink is not None and sink.groups and sink.small_direct:
-            views = [sink.small_direct.get(t.data_ptr()) for t in (w1, b1, w2, b2, w3, b3)]
-            if all(v is not None and v.shape == t.shape for v, t in zip(views, (w1, b1, w2, b2, w3, b3))):
-                direct = views
-        grads = direct if direct is not None else [torch.empty_like(t) for t in (w1, b1, w2, b2, w3, b3)]  # overwritten (accumulate = 0)
-        # the bucketed scatter that follows needs its level maxima cleared: the MLP's slab-reduction launch does it on the
-        # side (one dispatch less per step than the scatter's own fill)
-        clear_ptr, clear_bytes = None, 0
-        if sv >= 2 and m_host > 0:
-            wst = E.scatter_workspace(encoder.levels, m_host, dev)
-            clear_bytes = E.scatter_clear_bytes(encoder.levels, m_host)
-            clear_ptr, sv = _p(wst), sv | _b.SCATTER_CLEARED
-        _b.call("lnerf_mlp_backward", _p(feat), fdt, int(level_stride), _p(xyzs), _p(w1), _p(b1), _p(w2), _p(b2),
-                _p(w3), _p(b3), out_dim, float(blob_scale), float(blob_std), int(m_host), _p(m_dev), _p(sigmas),
-                _chk(dsigmas, "dsigmas"), _chk(drgbs, "drgbs"), _p(dfeat), *[_p(g) for g in grads], 0, _p(workspace),
-                workspace.numel(), precision, clear_ptr, clear_bytes, _stream())
-        if fu is not None and fu.take():  # armed: the scatter applies the table's Adam step
-            E.grid_encode_backward_adam(xyzs, bound, dfeat, encoder, m_host, m_dev, level_stride, sv)
-            dtable = None
-        elif encoder.grad_sink is not None:  # data parallel: the gradient goes straight into the bf16 wire buffer
-            E.grid_encode_backward_bf16(xyzs, bound, dfeat, encoder, m_host, m_dev, level_stride, sv)
-            dtable = None
-        else:
-            dtable = torch.zeros(tshape, device=dev, dtype=torch.float32)
-            E.grid_encode_backward(xyzs, bound, dfeat, encoder.levels, m_host, m_dev, level_stride, dtable, sv)
-        if direct is not None:
-            sink.small_written = True
-            grads = [None] * 6
+        dev, out_dim = xyzs.device, W[4].shape[0]
+        workspace, tag, own_ws = _mlp_backward_workspace(workspace, precision, out_dim, dev)
+        route = E.plan_backward(encoder, m_host, dev, W, own_ws)
+        grads = route.views or [None if route.tail else torch.empty_like(t) for t in W]
+        flags, clear_ptr, clear_bytes = route.mlp_args(encoder.levels, m_host)
+        dfeat = _mlp_backward(feat, xyzs, W, sigmas, m_host, m_dev, level_stride, blob_scale, blob_std, dsigmas, drgbs,
+                              grads, workspace, tag | flags, clear_ptr, clear_bytes)
+        dtable = E.run_backward(route, xyzs, bound, dfeat, encoder, m_host, m_dev, level_stride, workspace, precision,
+                                out_dim)
+        grads = grads if route.views is None else [None] * 6       # (views: in the exchange bucket already)
         return (None, dtable, None, *grads, None, None, None, None, None, None, None, None, None, None)
 
 

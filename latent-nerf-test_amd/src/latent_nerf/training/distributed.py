@@ -347,7 +347,6 @@ class GradSync:
                 ra, rb = sink.shard_rest   # the table's last few rows: replicated (see _plan_shards)
                 work = dist.all_reduce(sink.wire[ra:rb], group=self.group, async_op=True) if self.active else None
                 groups.append((ra, rb, work))
-        sink.written += 1     # (`pending` stays: a replayed hipGraph bins again without running any Python)
         small_work = None
         if self.small:
             flat = self._pack_small()

@@ -7,6 +7,7 @@ import ctypes
 
 import torch
 
+from ..models import encoding as E
 from ..raymarching import backend as _b
 from ..raymarching.raymarching import _p, _stream
 
@@ -47,12 +48,7 @@ class FusedAdam:
         if len(self.small) > 16:
             raise ValueError("FusedAdam handles at most 16 small tensors per launch")
         n = len(self.small)
-        self._pp = (ctypes.c_void_p * n)()
-        self._gp = (ctypes.c_void_p * n)()
-        self._mp = (ctypes.c_void_p * n)(*[e[1].data_ptr() for e in self.small])
-        self._vp = (ctypes.c_void_p * n)(*[e[2].data_ptr() for e in self.small])
-        self._n = (ctypes.c_int64 * n)(*[e[0].numel() for e in self.small])
-        self._lr = (ctypes.c_float * n)(*[e[3] for e in self.small])
+        self._multi = self._multi_arrays(range(n))   # every small parameter (the ordinary step)
         self.mlp, self._maps, self._map_tensors = None, None, None
         if mlp is not None and getattr(mlp, "precision", None) == "bf16" and self.small:
             dev0 = self.small[0][0].device
@@ -87,10 +83,9 @@ class FusedAdam:
         if fuse_table_update:
             if encoder is None:
                 raise ValueError("fuse_table_update needs the encoder")
-            from ..models.encoding import FusedTableUpdate
             for p, m, v, lr in self.big:
                 if p is encoder.embeddings:
-                    self.fused = FusedTableUpdate(m, v, lr, betas, eps, self)
+                    self.fused = E.FusedTableUpdate(m, v, lr, betas, eps, self)
                     encoder.fused_update = self.fused
             if self.fused is None:
                 raise ValueError("fuse_table_update: encoder.embeddings is not among the parameters")
@@ -110,16 +105,40 @@ class FusedAdam:
             lrs = {self.small[k][3] for k in idx}
             if len(lrs) != 1:
                 raise ValueError("FusedAdam(tail=True): the MLP's six tensors must share one learning rate")
-            self._tail = {"idx": idx, "lr": lrs.pop(), "net": mlp,
-                          "p": (ctypes.c_void_p * 6)(), "m": (ctypes.c_void_p * 6)(*[self.small[k][1].data_ptr() for k in idx]),
-                          "v": (ctypes.c_void_p * 6)(*[self.small[k][2].data_ptr() for k in idx]),
-                          "maps": None if self._map_tensors is None else
-                          (ctypes.c_void_p * 3)(*[self._map_tensors[n].data_ptr() for n in ("w1", "w2", "w3")])}
+            # `rest`: the small parameters outside the MLP (a background net), stepped by the launch in front of the tail
+            self._tail = dict(self._multi_arrays(idx), lr=lrs.pop(),
+                              rest=self._multi_arrays([k for k in range(n) if k not in idx]),
+                              maps=None if self._map_tensors is None else
+                              (ctypes.c_void_p * 3)(*[self._map_tensors[n].data_ptr() for n in ("w1", "w2", "w3")]))
             self.fused.tail = True
             # no other small parameter and a device step counter: the armed scatter closes the step ITSELF (its pass 2 runs
             # the slab sums, the MLP's Adam step and the tick: lnerf_grid_encode_backward_adam_tail); else the tail is the
             # step's last launch (lnerf_step_tail, behind the ordinary Adam launch of the other small parameters)
             self.fused.inline_tail = len(idx) == len(self.small) and self.step_dev is not None
+
+    def _multi_arrays(self, idx):
+        """ctypes arrays of a multi-tensor Adam launch over self.small[k], k in idx (_adam_multi fills in `p` and `g`)."""
+        n = len(idx)
+        return {"idx": list(idx), "p": (ctypes.c_void_p * n)(), "g": (ctypes.c_void_p * n)(),
+                "m": (ctypes.c_void_p * n)(*[self.small[k][1].data_ptr() for k in idx]),
+                "v": (ctypes.c_void_p * n)(*[self.small[k][2].data_ptr() for k in idx]),
+                "n": (ctypes.c_int64 * n)(*[self.small[k][0].numel() for k in idx]),
+                "lrs": (ctypes.c_float * n)(*[self.small[k][3] for k in idx])}
+
+    def _adam_multi(self, a, grads, grad_scale, flags, maps=None, frag=None):
+        """ONE lnerf_adam_step_multi_shadow launch over the parameters of _multi_arrays() `a` (grads: as in step())."""
+        for j, k in enumerate(a["idx"]):
+            p = self.small[k][0]
+            g = p.grad if grads is None else grads.get(p, p.grad)
+            if g is None:
+                raise RuntimeError("FusedAdam: parameter %d has no gradient" % k)
+            if g.dtype != torch.float32 or g.numel() != p.numel() or not g.is_contiguous():
+                raise ValueError("FusedAdam: the gradient of a small parameter must be a contiguous f32 tensor")
+            a["p"][j] = p.data.data_ptr()
+            a["g"][j] = g.data_ptr()
+        b1, b2 = self.betas
+        _b.call("lnerf_adam_step_multi_shadow", len(a["idx"]), a["p"], a["g"], a["m"], a["v"], a["n"], a["lrs"], b1, b2,
+                self.eps, self.step_no, _p(self.step_dev), float(grad_scale), flags, maps, frag, _stream())
 
     def arm(self):
         """Let the NEXT backward through the encoder apply the table's Adam step (no-op without fuse_table_update)."""
@@ -177,22 +196,12 @@ class FusedAdam:
         if self.fused is not None and self.fused.closed:
             self.fused.closed = False      # the armed backward closed the step: nothing left to launch
         elif pend is not None:
-            self._step_tail(pend, float(grad_scale))
+            self._step_tail(pend, grads, float(grad_scale))
         elif self.small:
-            for k, (p, m, v, lr) in enumerate(self.small):
-                g = p.grad if grads is None else grads.get(p, p.grad)
-                if g is None:
-                    raise RuntimeError("FusedAdam: parameter %d has no gradient" % k)
-                if g.dtype != torch.float32 or g.numel() != p.numel() or not g.is_contiguous():
-                    raise ValueError("FusedAdam: the gradient of a small parameter must be a contiguous f32 tensor")
-                self._pp[k] = p.data.data_ptr()
-                self._gp[k] = g.data_ptr()
             # (with the device counter this launch, the step's last Adam launch, also advances it: LNERF_ADAM_TICK = 2)
             frag = None if self.mlp is None else self.mlp.mlp_workspace(self.small[0][0].device)
-            _b.call("lnerf_adam_step_multi_shadow", len(self.small), self._pp, self._gp, self._mp, self._vp, self._n,
-                    self._lr, b1, b2, self.eps, self.step_no, _p(self.step_dev), float(grad_scale),
-                    2 if self.step_dev is not None else 0, None if frag is None else self._maps,
-                    None if frag is None else _p(frag), _stream())
+            self._adam_multi(self._multi, grads, grad_scale, 2 if self.step_dev is not None else 0, self._maps,
+                             _p(frag))
         elif self.step_dev is not None:
             _b.call("lnerf_adam_tick", _p(self.step_dev), _stream())
         # the multi-tensor launch wrote through raw pointers: tell torch, so that anything that cached a function of a
@@ -214,28 +223,14 @@ class FusedAdam:
             t["p"][j] = self.small[k][0].data.data_ptr()
         return t
 
-    def _step_tail(self, pend, grad_scale):
+    def _step_tail(self, pend, grads, grad_scale):
         """The armed step's last launch (see __init__): lnerf_step_tail.  Small parameters outside the MLP (a background
         net) take the ordinary multi-tensor launch first; the tail ticks the step counter, so it goes last."""
-        t = self._tail
         levels, m_host, variant, wst, mlp_ws, precision, out_dim = pend
         b1, b2 = self.betas
-        rest = [k for k in range(len(self.small)) if k not in t["idx"]]
-        if rest:
-            n = len(rest)
-            pp, gp = (ctypes.c_void_p * n)(), (ctypes.c_void_p * n)()
-            mp, vp = (ctypes.c_void_p * n)(), (ctypes.c_void_p * n)()
-            nn, lr = (ctypes.c_int64 * n)(), (ctypes.c_float * n)()
-            for j, k in enumerate(rest):
-                p, m, v, lr_k = self.small[k]
-                if p.grad is None:
-                    raise RuntimeError("FusedAdam: parameter %d has no gradient" % k)
-                pp[j], gp[j], mp[j], vp[j] = p.data.data_ptr(), p.grad.data_ptr(), m.data_ptr(), v.data_ptr()
-                nn[j], lr[j] = p.numel(), lr_k
-            _b.call("lnerf_adam_step_multi_shadow", n, pp, gp, mp, vp, nn, lr, b1, b2, self.eps, self.step_no,
-                    _p(self.step_dev), grad_scale, 0, None, None, _stream())
-        for j, k in enumerate(t["idx"]):
-            t["p"][j] = self.small[k][0].data.data_ptr()
+        t = self.tail_args()
+        if t["rest"]["idx"]:
+            self._adam_multi(t["rest"], grads, grad_scale, 0)
         fu = self.fused
         enc = self.encoder
         # (tick and clearing epilogue need the device counter pair: without it -- capturable=False -- the next scatter
@@ -247,7 +242,6 @@ class FusedAdam:
                 t["p"], t["m"], t["v"], float(t["lr"]), t["maps"], b1, b2, self.eps, self.step_no, _p(self.step_dev),
                 grad_scale, flags, _stream())
         fu.pending_tail = None
-        from ..models import encoding as E
         if flags & _b.TAIL_CLEAR_SCATTER:
             E.ws_mark_clean(wst)
 

@@ -250,6 +250,28 @@ def test_grid_encode_forward_backward(dev, variant, cfg):
     _close(dtable, 2 * tref.grad, 1e-3, 2e-5, "dtable accumulates")
 
 
+@pytest.mark.parametrize("scatter_variant", [2, 3])
+def test_grid_encoder_module_is_the_gather_and_the_scatter(dev, scatter_variant):
+    """GridEncoder.forward (the upstream encoder's surface: [..., 3] -> [..., L * 2]) is the gather, and the `.grad` of
+    its backward (the bare encoder's route) is grid_encode_backward on the same inputs, bit for bit."""
+    from src.latent_nerf.models import encoding as E
+    torch.manual_seed(2)
+    enc = E.GridEncoder(base_resolution=4, desired_resolution=128, log2_hashmap_size=12,
+                        scatter_variant=scatter_variant).to(dev)
+    M = 3001
+    x = _rand_points(M).to(dev)
+    out = enc(x.reshape(1, M, 3))
+    assert out.shape == (1, M, 32)
+    feat = E.grid_encode_forward(x, 1.0, enc.embeddings.detach(), enc.levels, M, None, M)
+    assert torch.equal(out[0], feat.permute(1, 0, 2).reshape(M, 32))
+    g = torch.randn(1, M, 32, device=dev)
+    out.backward(g)
+    ref = torch.zeros_like(enc.embeddings)
+    E.grid_encode_backward(x, 1.0, g[0].reshape(M, 16, 2).permute(1, 0, 2).contiguous(), enc.levels, M, None, M, ref,
+                           variant=scatter_variant)
+    assert float(ref.abs().max()) > 0 and torch.equal(enc.embeddings.grad, ref)
+
+
 @pytest.mark.parametrize("gridtype", ["blocked", "tiled"])
 @pytest.mark.parametrize("table_dtype", ["f32", "bf16"])
 @pytest.mark.parametrize("cfg", ["small", "full"])

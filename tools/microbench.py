@@ -128,7 +128,6 @@ def main():
         zero = torch.zeros_like(emb.data)
 
         def fused():
-            opt.fused.armed = False
             Emod.grid_encode_backward_adam(xyzs, 1.0, dfeat, enc, cap, m_dev, cap, 3)
 
         def sink_path():

@@ -546,6 +546,52 @@ int lnerf_uv_raster(const float *verts, int n_verts, const int32_t *faces, const
 int lnerf_uv_dilate(float *texture, uint8_t *mask, int C, int R, int passes, float *tmp_texture, uint8_t *tmp_mask,
                     lnerf_stream_t stream);
 
+/* ---- mesh decimation: rounds of independent quadric-error (Garland-Heckbert) edge collapses, NeRFRenderer.export_mesh's
+ * `target_faces` (csrc/decimate.hip).  Additive to ABI 7.  Fully deterministic; the C call is synchronous (one host
+ * read of the counts before round 1, one per round).
+ *   verts [n_verts,3] f32, faces [n_faces,3] int32.  A face with an index outside [0, n_verts) fails the call
+ *   (LNERF_ERR_INVALID_ARG) before any kernel reads through it; faces that repeat an index are dropped first.
+ *   f64 and f32 arithmetic below is + - * / and sqrt only, evaluated left to right (no fused multiply-adds).
+ * Quadrics (once, from the input): face quadric = w * (n0n0, n0n1, n0n2, n1n1, n1n2, n2n2, n0d, n1d, n2d, dd) in f64,
+ *   m = (p1 - p0) x (p2 - p0), l = sqrt(m.m), n = m / l, d = -(n.p0), w = l * 0.5 (all ten 0 when l = 0); a vertex sums
+ *   those of its faces in ascending face index (vertex -> face lists built on the device: count, scan, fill, sort).
+ *   A collapse's survivor takes Q_u + Q_v.
+ * A round, on the current faces:
+ *   locked vertex: no faces, an edge at it not in exactly one face each way round, or faces that are not one closed
+ *     fan.  Open borders and non-manifold parts therefore keep their exact positions.
+ *   candidates: half-edge e = 3 f + k from faces[f][k] = u to faces[f][(k+1)%3] = v with u < v.  Invalid if u or v is
+ *     locked; both have 3 faces (a tetrahedron); u and v have other than exactly 2 common neighbours (link condition);
+ *     the cost is not finite or (as f32) > max_error; a face around u or v that does not hold both has normal m before
+ *     and m' after the move with m != 0 and m.m' <= 0 (a flip), or m == 0 and m' != 0 (a zero-area face gaining area:
+ *     its plane is in no quadric, so the move would look free).  Normals m in f64 from the f32 positions.
+ *   v*: A x = -b by cofactors (c00 = a11a22 - a12a12, c01 = a02a12 - a01a22, c02 = a01a12 - a02a11, c11 = a00a22 -
+ *     a02a02, c12 = a01a02 - a00a12, c22 = a00a11 - a01a01, det = a00c00 + a01c01 + a02c02, x_i = -(c_i0 b0 + c_i1 b1 +
+ *     c_i2 b2) / det), rounded to f32; used iff |det| > LNERF_DECIMATE_SINGULAR_REL * tr^3 (tr = a00 + a11 + a22) and x
+ *     is finite, else the cheapest of p_u, p_v, (p_u + p_v) * 0.5f (earlier wins a tie).
+ *   cost(x) = (t0 x0 + t1 x1 + t2 x2) + (b0 x0 + b1 x1 + b2 x2) + c,  t_i = a_i0 x0 + a_i1 x1 + a_i2 x2 + b_i  (f64 at
+ *     the f32 point; below or at 0 -> +0), rounded to f32.
+ *   key = f32 cost bits << 32 | tag(e) (u64), tag = a fixed bijection of the 32-bit edge id (x *= 0x9E3779B1,
+ *     x ^= x >> 16, x *= 0x85EBCA6B, x ^= x >> 13): costs tie often (a flat region's are all 0) and ids ordered along
+ *     the lattice would leave one local minimum per region per round.
+ *   selection: K1[w] = min key at w (atomic min), face key = min K1 of its corners, K2[w] = min face key at w; e
+ *     collapses iff K2[u] == K2[v] == key.  No face touches the ends of two selected edges, so the checks hold together.
+ *     In the round that would pass target_faces only the ceil((F - target_faces) / 2) smallest keys collapse.
+ *   apply: p_u = v*, Q_u += Q_v, v -> u in every face; the two faces of each collapse go; stable compaction.
+ * Stop when F <= target_faces, a round selects nothing, or after max_rounds rounds.  Then: the referenced vertices in
+ *   their old order, faces in their old order, normals = the f32 sum over the vertex's faces in ascending order of
+ *   (p1 - p0) x (p2 - p0), times 1.0f / sqrtf(l2) (0 for l2 = 0).
+ * Outputs (capacity n_verts / n_faces; normals may be NULL): counts_dev int64[4] = {V_out, F_out, rounds, collapses}.
+ * Scratch: lnerf_decimate_scratch_bytes() (0 = arguments out of range; 16-byte aligned).
+ * Constants: SINGULAR_REL the solve's threshold above; DEFAULT_ROUNDS the host side's max_rounds default; MAX_FACES the
+ * largest n_faces (3 n_faces half-edge ids and scan totals stay in int32). */
+#define LNERF_DECIMATE_SINGULAR_REL 1e-10
+#define LNERF_DECIMATE_DEFAULT_ROUNDS 128
+#define LNERF_DECIMATE_MAX_FACES (1 << 28)
+size_t lnerf_decimate_scratch_bytes(int n_verts, int n_faces);
+int lnerf_decimate(const float *verts, int n_verts, const int32_t *faces, int n_faces, int target_faces, float max_error,
+                   int max_rounds, void *scratch, size_t scratch_bytes, float *verts_out, int32_t *faces_out,
+                   float *normals_out, int64_t *counts_dev, lnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -90,6 +90,8 @@ class LogConfig:
     # with save_mesh: > 0 exports a textured mesh (per-triangle UV atlas, the field baked at this texture side) instead
     # of per-vertex colours; its latent_texture.pt starts Latent-Paint (guide.init_texture)
     mesh_texture_resolution: int = 0
+    # with save_mesh: > 0 decimates the marching-cubes mesh to this many faces (or one fewer) before the colours / bake
+    mesh_target_faces: int = 0
     max_keep_ckpts: int = 2
     # no progress lines on stdout (log.txt in the experiment directory is still written)
     quiet: bool = False

@@ -446,7 +446,7 @@ class NeRFRenderer(nn.Module):
         return {"texture": texture, "mask": mask, "rgb": rgb}
 
     @torch.no_grad()
-    def export_mesh(self, path, resolution=None, S=128, thresh=None, texture_resolution=0, gutter=4):
+    def export_mesh(self, path, resolution=None, S=128, thresh=None, texture_resolution=0, gutter=4, target_faces=0):
         """Triangle mesh of the density field -> `path`/mesh.obj (the upstream renderer's export_mesh(path, resolution,
         S)): the density on a `resolution`^3 lattice over [-bound, bound]^3 (density_lattice), marching cubes on the GPU
         at iso `thresh` (default min(mean density, density_thresh), as upstream) with the box capped, vertex colours
@@ -455,8 +455,10 @@ class NeRFRenderer(nn.Module):
         side (bake_texture, `gutter` dilation rounds), mesh.obj with v / vt / vn / f v/vt/vn, mesh.mtl, albedo.png
         (the RGB preview) and, in latent mode, latent_texture.pt ([4,R,R] f32, what Latent-Paint's guide.init_texture
         reads).
-        Returns dict(verts [V,3], faces [F,3] int32, normals [V,3], colors [V,3], iso, path) with device tensors, plus
-        vt, ft, texture, mask, rgb when textured."""
+        target_faces > 0: the marching-cubes mesh is decimated on the GPU to that many faces or one fewer first
+        (raymarching.decimate_mesh); the colours, the atlas and the bake are then the decimated mesh's.
+        Returns dict(verts [V,3], faces [F,3] int32, normals [V,3], colors [V,3], iso, path, faces_before (the
+        marching-cubes face count)) with device tensors, plus vt, ft, texture, mask, rgb when textured."""
         from .mesh_io import write_obj
         vol = self.density_lattice(resolution, S)
         if thresh is None:
@@ -465,6 +467,10 @@ class NeRFRenderer(nn.Module):
             iso = float(thresh)
         b = self.bound
         verts, faces, normals = rm.marching_cubes(vol, iso, (-b, -b, -b), (b, b, b), close_boundary=True)
+        faces_before = int(faces.shape[0])
+        if int(target_faces) > 0:
+            del vol
+            verts, faces, normals = rm.decimate_mesh(verts, faces, int(target_faces))
         colors = torch.empty(verts.shape[0], 3, device=verts.device)
         chunk = S ** 3
         for s in range(0, verts.shape[0], chunk):
@@ -472,7 +478,8 @@ class NeRFRenderer(nn.Module):
             _, feats = self.field(pts, pts.shape[0])
             colors[s:s + chunk] = self._latent_preview(feats)
         out = os.path.join(str(path), "mesh.obj")
-        result = {"verts": verts, "faces": faces, "normals": normals, "colors": colors, "iso": iso, "path": out}
+        result = {"verts": verts, "faces": faces, "normals": normals, "colors": colors, "iso": iso, "path": out,
+                  "faces_before": faces_before}
         if int(texture_resolution) > 0:
             result.update(self._export_textured(str(path), verts, faces, normals, int(texture_resolution), gutter, S))
         else:
@@ -492,8 +499,9 @@ class NeRFRenderer(nn.Module):
         need = atlas_min_resolution(F)
         if F > 0 and R < need:
             warnings.warn("export_mesh: texture_resolution %d gives the per-triangle atlas of %d faces %.1f texels per "
-                          "chart cell (fewer than %d): use texture_resolution >= %d"
-                          % (R, F, R / atlas_cells(F), MIN_TEXELS_PER_CELL, need), stacklevel=3)
+                          "chart cell (fewer than %d): use texture_resolution >= %d, or target_faces <= %d"
+                          % (R, F, R / atlas_cells(F), MIN_TEXELS_PER_CELL, need, 2 * (R // MIN_TEXELS_PER_CELL) ** 2),
+                          stacklevel=3)
         vt, ft = per_triangle_atlas(F, verts.device)
         baked = self.bake_texture(verts, faces, vt, ft, resolution=R, gutter=gutter, S=S)
         os.makedirs(path, exist_ok=True)

@@ -26,6 +26,7 @@ SCATTER_CLEARED = 0x100       # flag on the scatter's variant: the caller cleare
 MC_CLOSE_BOUNDARY, MC_COUNT_ONLY, MC_REUSE_COUNT = 1, 2, 4   # LNERF_MC_* flags of lnerf_marching_cubes
 UV_ITEMS, UV_COVER, UV_EMIT = 1, 2, 4                         # LNERF_UV_* stages of lnerf_uv_raster
 UV_MAX_RES = 8192                                             # LNERF_UV_MAX_RES
+DECIMATE_DEFAULT_ROUNDS = 128                                 # LNERF_DECIMATE_DEFAULT_ROUNDS
 
 
 class LnerfLibraryError(RuntimeError):
@@ -115,6 +116,8 @@ _SIGNATURES = {
     "lnerf_uv_raster_scratch_bytes": [_I, _I],
     "lnerf_uv_raster": [_P, _I, _P, _P, _I, _P, _I, _I, _I, _L, _P, _Z, _P, _P, _P, _L, _P, _P],
     "lnerf_uv_dilate": [_P, _P, _I, _I, _I, _P, _P, _P],
+    "lnerf_decimate_scratch_bytes": [_I, _I],
+    "lnerf_decimate": [_P, _I, _P, _I, _I, _F, _I, _P, _Z, _P, _P, _P, _P, _P],
     "lnerf_step_tail": [_I, _I, _P, _P, _P, _L, _I, _P, _Z, _P, _P, _P, _P, _P, _F, _P, _Z, _I, _I, _P, _P, _P, _F, _P,
                         _F, _F, _F, _I, _P, _F, _I, _P],
 }
@@ -128,6 +131,7 @@ _RESTYPES = {
     "lnerf_grid_encode_backward_workspace_bytes": _Z,
     "lnerf_marching_cubes_scratch_bytes": _Z,
     "lnerf_uv_raster_scratch_bytes": _Z,
+    "lnerf_decimate_scratch_bytes": _Z,
 }
 
 _lib = None

@@ -338,6 +338,47 @@ def marching_cubes(volume, iso, lo, hi, close_boundary=True):
     return verts, faces, normals
 
 
+def decimate_mesh(verts, faces, target_faces, max_error=float("inf"), max_rounds=_b.DECIMATE_DEFAULT_ROUNDS, stats=None):
+    """Quadric-error decimation on the GPU (lnerf_decimate, include/lnerf_hip.h): rounds of independent edge collapses until
+    at most `target_faces` faces are left -- target_faces or one fewer, unless a round finds no valid collapse, max_rounds
+    runs out or `max_error` (a quadric-cost ceiling) blocks.  Open borders and non-manifold parts stay where they are.
+    verts [V,3] f32, faces [F,3] (into verts), on the GPU -> verts [V',3] f32, faces [F',3] int32, normals [V',3] f32 on
+    the device; the vertices still referenced and the faces left keep their order.  `stats` (a dict) receives rounds
+    and collapses.  Synchronous: one host read of the counts per round."""
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError("decimate_mesh: verts must be [V,3]")
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("decimate_mesh: faces must be a [F,3] index tensor")
+    if faces.dtype.is_floating_point:
+        raise TypeError("decimate_mesh: faces must hold integers")
+    target_faces, max_rounds, max_error = int(target_faces), int(max_rounds), float(max_error)
+    if target_faces < 0 or max_rounds < 0:
+        raise ValueError("decimate_mesh: target_faces (%d) and max_rounds (%d) must be >= 0" % (target_faces, max_rounds))
+    if not max_error >= 0:
+        raise ValueError("decimate_mesh: max_error must be >= 0 (inf: no ceiling)")
+    verts = verts.contiguous()
+    _chk(verts, "verts")
+    dev = verts.device
+    if faces.dtype != torch.int32 and faces.numel() and (int(faces.min()) < -2 ** 31 or int(faces.max()) >= 2 ** 31):
+        raise ValueError("decimate_mesh: faces has indices outside int32")   # (a wrapped index could be a valid one)
+    faces = faces.to(device=dev, dtype=torch.int32).contiguous()
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    nbytes = _b.get_lib().lnerf_decimate_scratch_bytes(V, F)
+    if nbytes == 0:
+        raise ValueError("decimate_mesh: %d vertices / %d faces out of range" % (V, F))
+    scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    counts = torch.zeros(4, device=dev, dtype=torch.int64)
+    out_v = torch.empty(V, 3, device=dev, dtype=torch.float32)
+    out_f = torch.empty(F, 3, device=dev, dtype=torch.int32)
+    out_n = torch.empty(V, 3, device=dev, dtype=torch.float32)
+    _b.call("lnerf_decimate", _p(verts), V, _p(faces), F, target_faces, max_error, max_rounds, _p(scratch), nbytes,
+            _p(out_v), _p(out_f), _p(out_n), _p(counts), _stream())
+    Vo, Fo, rounds, collapses = (int(c) for c in counts.tolist())
+    if stats is not None:
+        stats.update(rounds=rounds, collapses=collapses)
+    return out_v[:Vo], out_f[:Fo], out_n[:Vo]
+
+
 # ------------------------------------------------------------------------------ texture baking
 def _uv_index(t, name, dev):
     if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 3:

@@ -472,9 +472,10 @@ class Trainer:
         if getattr(self.cfg.log, "save_mesh", False) and self.rank == 0:
             # the density field as a triangle mesh (NeRFRenderer.export_mesh) -> <exp_dir>/mesh/mesh.obj
             tex = int(getattr(self.cfg.log, "mesh_texture_resolution", 0))
-            mesh = self.nerf.export_mesh(self.exp_path / "mesh", texture_resolution=tex)
-            self.log("exported %s (%d vertices, %d triangles, iso %.4g)"
-                     % (mesh["path"], mesh["verts"].shape[0], mesh["faces"].shape[0], mesh["iso"]))
+            target = int(getattr(self.cfg.log, "mesh_target_faces", 0))
+            mesh = self.nerf.export_mesh(self.exp_path / "mesh", texture_resolution=tex, target_faces=target)
+            self.log("exported %s (%d vertices, %d triangles; %d before decimation; iso %.4g)"
+                     % (mesh["path"], mesh["verts"].shape[0], mesh["faces"].shape[0], mesh["faces_before"], mesh["iso"]))
         return frames
 
     def preview_rgb(self, latents):

@@ -8,7 +8,11 @@ Field: bench.py's (seed 0, Linear-default MLP, table N(0, 0.1), density blob; bf
 density_thresh (10).  Times are HIP events around the call (median of --reps after one warm-up call per size).
 mc_bytes is the marching-cubes traffic model: the volume read by the count and the emit pass (2 x 4 B per working point),
 the per-point words (written, rewritten and read: 4 x 4 B), and the outputs (24 B per vertex with its normal, 12 B per
-triangle); mc_GBps = mc_bytes / mc time."""
+triangle); mc_GBps = mc_bytes / mc time.
+--target-faces N[,N...]: also time the decimation of each marching-cubes mesh to N faces (raymarching.decimate_mesh: one
+host read per round, so the time includes those synchronisations) with its round and collapse counts, and, on the
+largest lattice, Latent-Paint's rasteriser (lnerf_raster_prepare + lnerf_rasterize at 512 x 512, one view) on the
+undecimated and on each decimated mesh."""
 import argparse
 import json
 import os
@@ -48,29 +52,56 @@ def timed(fn, reps):
     return statistics.median(times), out
 
 
+def raster_ms(dev, verts, faces, reps):
+    """Latent-Paint's rasteriser on one view of the mesh, scaled into the unit box: prepare + rasterize, 512 x 512."""
+    from src.latent_paint.models.render import Renderer
+    r = Renderer(dev, dim=(512, 512))
+    v = (verts / verts.abs().max()).contiguous()
+    t, _ = timed(lambda: r._rasterize(v, faces, 1.0, 0.5, 2.0, 0.0, (512, 512)), reps)
+    return t
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--precision", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sizes", default="128,256,512")
+    ap.add_argument("--target-faces", default="", help="comma-separated face targets of a decimation leg (empty: none)")
     args = ap.parse_args()
-    from src.latent_nerf.raymarching import marching_cubes
+    from src.latent_nerf.raymarching import decimate_mesh, marching_cubes
     assert torch.cuda.is_available(), "bench_mesh_export needs the GPU"
     dev = torch.device("cuda:0")
     net, cfg = field(dev, args.precision)
     iso = float(cfg.density_thresh)
     b = net.bound
+    targets = [int(t) for t in args.target_faces.split(",") if t.strip()]
+    sizes = [int(s) for s in args.sizes.split(",")]
     res = []
-    for R in (int(s) for s in args.sizes.split(",")):
+    for R in sizes:
         t_q, vol = timed(lambda: net.density_lattice(R, S=128), args.reps)
         t_mc, (v, f, n) = timed(lambda: marching_cubes(vol, iso, (-b,) * 3, (b,) * 3, close_boundary=True), args.reps)
         N = (R + 2) ** 3
         V, F = int(v.shape[0]), int(f.shape[0])
         mc_bytes = 8 * N + 16 * N + 24 * V + 12 * F
-        res.append({"resolution": R, "points": R ** 3, "query_ms": round(t_q, 4), "mc_ms": round(t_mc, 4), "V": V, "F": F,
-                    "mc_bytes": mc_bytes, "mc_GBps": round(mc_bytes / (t_mc * 1e-3) / 1e9, 1),
-                    "query_Mpts_per_s": round(R ** 3 / (t_q * 1e-3) / 1e6, 1)})
-        del vol, v, f, n
+        row = {"resolution": R, "points": R ** 3, "query_ms": round(t_q, 4), "mc_ms": round(t_mc, 4), "V": V, "F": F,
+               "mc_bytes": mc_bytes, "mc_GBps": round(mc_bytes / (t_mc * 1e-3) / 1e9, 1),
+               "query_Mpts_per_s": round(R ** 3 / (t_q * 1e-3) / 1e6, 1)}
+        del vol
+        meshes = [(F, v, f)]
+        for N in targets:
+            if N >= F:
+                continue
+            st = {}
+            t_d, (dv, df, _) = timed(lambda: decimate_mesh(v, f, N, stats=st), args.reps)
+            row.setdefault("decimate", []).append({"target": N, "ms": round(t_d, 3), "F_out": int(df.shape[0]),
+                                                   "V_out": int(dv.shape[0]), "rounds": st["rounds"],
+                                                   "collapses": st["collapses"]})
+            meshes.append((N, dv, df))
+        if targets and R == sizes[-1]:
+            row["raster_512_ms"] = {str(int(m[2].shape[0])): round(raster_ms(dev, m[1], m[2], args.reps), 3)
+                                    for m in meshes}
+        res.append(row)
+        del v, f, n, meshes
         torch.cuda.empty_cache()
     print(json.dumps({"tool": "bench_mesh_export", "precision": args.precision, "iso": iso, "reps": args.reps,
                       "device": torch.cuda.get_device_name(0), "results": res}))

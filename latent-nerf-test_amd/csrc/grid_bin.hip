@@ -57,30 +57,78 @@ __device__ __forceinline__ unsigned int wave_max_u32(unsigned int v) {
 // lies before its run's first lane is multiplied by 0.  Unlike "wave prefix sum minus the prefix before the run" it
 // needs no lane permutes, no subtraction (and has none of its cancellation), and a wave whose longest run is short
 // skips the long-distance steps: all conditions are wave-uniform scalar tests on the run-head mask.
+//
+// The six steps are ONE asm statement: the 16 sums stay in the registers they arrive in from the first step to the last.
+// (As six statements, each behind its own `if`, every scalar branch was a merge of 16 "+v" values for the register
+// allocator, which copied them there: 64 v_mov for 96 adds.)  A skipped step is a scalar branch inside the statement, on
+// one bit of `steps`; the 0/1 factor of a step is made inside from `d` and `lane`, in one early-clobber temporary.
+// Wait states (a DPP instruction reading a VGPR needs two behind the VALU write of it; nothing is padded for us here):
+//  * factor -> first add of the step: `s_nop 1` (kept);
+//  * a sum written by step k -> read by step k + 1 (or by a later one, when steps between are skipped): the write and
+//    the next read of ONE register always have the 15 adds of the other sums between them, in either step's half of
+//    the distance, whichever path the branches take -- the nops between steps are dropped;
+//  * the sums arriving in the statement: the head of the statement up to the first add is at least 4 instructions
+//    on every path (bit test, branch, compare, select, nop);
+//  * last add -> whatever follows the statement: `s_nop 1` (kept, once, at the end).
 __device__ __forceinline__ void wave_run_sums_x16(float (&a)[8], float (&b)[8], const RunInfo &r, int lane) {
     const int d = lane - r.start;  // lanes of the run before this one
     const unsigned long long H = r.heads;
     const unsigned long long H2 = H | (H << 1), H4 = H2 | (H2 << 2), H8 = H4 | (H4 << 4);
-#define LNERF_SEG_STEP(ctrl, cond)                                                                                  \
-    {                                                                                                               \
-        const float f = (cond) ? 1.0f : 0.0f;                                                                       \
-        asm volatile("s_nop 1" ::: );                                                                               \
-        _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                                             \
-            asm volatile("v_fmac_f32_dpp %0, %0, %1 " ctrl : "+v"(a[i]) : "v"(f));                                  \
-            asm volatile("v_fmac_f32_dpp %0, %0, %1 " ctrl : "+v"(b[i]) : "v"(f));                                  \
-        }                                                                                                           \
-        asm volatile("s_nop 1" ::: );                                                                               \
-    }
-    if (H != ~0ull) LNERF_SEG_STEP("row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0", d >= 1)
-    if (H2 != ~0ull) LNERF_SEG_STEP("row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:0", d >= 2)
-    if (H4 != ~0ull) LNERF_SEG_STEP("row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:0", d >= 4)
-    if (H8 != ~0ull) LNERF_SEG_STEP("row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:0", d >= 8)
-    // runs that continue over a row of 16 lanes: the previous row's last lane holds the run's sum so far
-    if ((H & 0x0001000000010000ull) != 0x0001000000010000ull)
-        LNERF_SEG_STEP("row_bcast:15 row_mask:0xa bank_mask:0xf", d > (lane & 15))
-    if (!((H >> 32) & 1ull)) LNERF_SEG_STEP("row_bcast:31 row_mask:0xc bank_mask:0xf", r.start < 32)
-#undef LNERF_SEG_STEP
+    // bit k: step k is needed by some run of the wave (steps 0..3: a run longer than 2^k lanes; 4, 5: a run that
+    // continues over a row of 16 lanes / over lane 32)
+    const unsigned int steps = (H != ~0ull ? 1u : 0u) | (H2 != ~0ull ? 2u : 0u) | (H4 != ~0ull ? 4u : 0u) |
+                               (H8 != ~0ull ? 8u : 0u) |
+                               ((H & 0x0001000000010000ull) != 0x0001000000010000ull ? 16u : 0u) |
+                               (!((H >> 32) & 1ull) ? 32u : 0u);
+    float f;  // 1.0 where the lane's source lies inside its run, else 0.0
+#define LNERF_SEG_ADD(i, ctrl) "v_fmac_f32_dpp %" #i ", %" #i ", %16 " ctrl "\n\t"
+#define LNERF_SEG_ADDS(ctrl)                                                                                        \
+    "s_nop 1\n\t"                                                                                                   \
+    LNERF_SEG_ADD(0, ctrl) LNERF_SEG_ADD(8, ctrl) LNERF_SEG_ADD(1, ctrl) LNERF_SEG_ADD(9, ctrl)                     \
+    LNERF_SEG_ADD(2, ctrl) LNERF_SEG_ADD(10, ctrl) LNERF_SEG_ADD(3, ctrl) LNERF_SEG_ADD(11, ctrl)                   \
+    LNERF_SEG_ADD(4, ctrl) LNERF_SEG_ADD(12, ctrl) LNERF_SEG_ADD(5, ctrl) LNERF_SEG_ADD(13, ctrl)                   \
+    LNERF_SEG_ADD(6, ctrl) LNERF_SEG_ADD(14, ctrl) LNERF_SEG_ADD(7, ctrl) LNERF_SEG_ADD(15, ctrl)
+// steps inside a row of 16 lanes: factor = (d >= dist); a wave without a run longer than dist has none longer than
+// 2 * dist either: skip straight to the steps over rows
+#define LNERF_SEG_ROW(bit, dist)                                                                                    \
+    "s_bitcmp1_b32 %19, " #bit "\n\t"                                                                               \
+    "s_cbranch_scc0 .Lrun_sums_rows_%=\n\t"                                                                         \
+    "v_cmp_le_i32_e32 vcc, " #dist ", %17\n\t"                                                                      \
+    "v_cndmask_b32_e64 %16, 0, 1.0, vcc\n\t"                                                                        \
+    LNERF_SEG_ADDS("row_shr:" #dist " row_mask:0xf bank_mask:0xf bound_ctrl:0")
+    asm volatile(
+        LNERF_SEG_ROW(0, 1) LNERF_SEG_ROW(1, 2) LNERF_SEG_ROW(2, 4) LNERF_SEG_ROW(3, 8)
+        // runs that continue over a row of 16 lanes: the previous row's last lane holds the run's sum so far
+        ".Lrun_sums_rows_%=:\n\t"
+        "s_bitcmp1_b32 %19, 4\n\t"
+        "s_cbranch_scc0 .Lrun_sums_half_%=\n\t"
+        "v_and_b32_e32 %16, 15, %18\n\t"
+        "v_cmp_gt_i32_e32 vcc, %17, %16\n\t"          // d > (lane & 15)
+        "v_cndmask_b32_e64 %16, 0, 1.0, vcc\n\t"
+        LNERF_SEG_ADDS("row_bcast:15 row_mask:0xa bank_mask:0xf")
+        ".Lrun_sums_half_%=:\n\t"
+        "s_bitcmp1_b32 %19, 5\n\t"
+        "s_cbranch_scc0 .Lrun_sums_done_%=\n\t"
+        "v_sub_u32_e32 %16, %18, %17\n\t"             // the run's first lane
+        "v_cmp_gt_i32_e32 vcc, 32, %16\n\t"
+        "v_cndmask_b32_e64 %16, 0, 1.0, vcc\n\t"
+        LNERF_SEG_ADDS("row_bcast:31 row_mask:0xc bank_mask:0xf")
+        ".Lrun_sums_done_%=:\n\t"
+        "s_nop 1"
+        : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]),
+          "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(b[4]), "+v"(b[5]), "+v"(b[6]), "+v"(b[7]), "=&v"(f)
+        : "v"(d), "v"(lane), "s"(steps)
+        : "vcc", "scc");
+#undef LNERF_SEG_ROW
+#undef LNERF_SEG_ADDS
+#undef LNERF_SEG_ADD
 }
+
+// Eight registers defined without an instruction, for values that are never looked at.  ONE statement with eight outputs:
+// eight identical statements `asm("" : "=v"(x[c]))` are merged into one by the compiler (same text, no input), and the
+// one register is then copied into the other seven -- 7 v_mov for values nobody reads.
+#define LNERF_UNDEF8(x)                                                                                              \
+    asm("" : "=v"((x)[0]), "=v"((x)[1]), "=v"((x)[2]), "=v"((x)[3]), "=v"((x)[4]), "=v"((x)[5]), "=v"((x)[6]), "=v"((x)[7]))
 
 // what the binning pass needs to know about a level (read from the kernel arguments in the kernel body only: the
 // lambdas below take it by value, so the argument structs are never copied to scratch)
@@ -121,24 +169,30 @@ k_scatter_bin(const float *__restrict__ xyzs, float bound, const float *__restri
     if (tid < LNERF_MAX_LEVELS) s_lmax[tid] = 0u;
     if (blockIdx.x == 0 && tid == 0) *items_out = (M + BIN_T - 1) / BIN_T;  // pass 2 walks exactly these items
     // ---- inputs of an item (5 dwords per lane), fetched while the previous item is processed
-    float n_x = 0.f, n_y = 0.f, n_z = 0.f;
+    // (the position is ONE three-register value, the registers its 12-byte load writes: as three floats the third was
+    // copied out of the load's registers at the merge behind `if (mm < M)`, and the copy waited for the load right
+    // where it was issued -- s_waitcnt vmcnt in the middle of the item, no prefetch)
+    nt_f3 n_p = {0.f, 0.f, 0.f};
     float2 n_g = make_float2(0.f, 0.f);
     auto fetch = [&](int lv, int tl) __attribute__((always_inline)) {
         const int mm = tl * BIN_T + tid;
-        n_x = n_y = n_z = 0.f;
+        n_p = nt_f3{0.f, 0.f, 0.f};
         n_g = make_float2(0.f, 0.f);
         if (mm < M) {
             const float2 *gp = reinterpret_cast<const float2 *>(dfeat) + ((int64_t)lv * level_stride + mm);
             // (read once per step: keep it out of the caches the table and the records use)
             const nt_f2 v = __builtin_nontemporal_load(reinterpret_cast<const nt_f2 *>(gp));
             n_g = make_float2(v.x, v.y);
-            n_x = xyzs[(int64_t)mm * 3]; n_y = xyzs[(int64_t)mm * 3 + 1]; n_z = xyzs[(int64_t)mm * 3 + 2];
+            n_p = nt_f3{xyzs[(int64_t)mm * 3], xyzs[(int64_t)mm * 3 + 1], xyzs[(int64_t)mm * 3 + 2]};
         }
     };
     int l = lv_lo + (int)(blockIdx.x % L);
     int tile = (int)(blockIdx.x / L);
     bool have = tile * BIN_T < M;
     if (have) fetch(l, tile);
+    // (the first item's inputs are waited for HERE: a load still pending at the loop's entry makes the compiler wait
+    // with s_waitcnt vmcnt(0) at the top of EVERY item -- in the loop that is a wait for the previous item's stores)
+    asm volatile("" : "+v"(n_g.x), "+v"(n_g.y), "+v"(n_p));
     BIN_STAMP_INIT();
     __syncthreads();
     int hk = 0;  // items so far (selects the counter set)
@@ -166,7 +220,7 @@ k_scatter_bin(const float *__restrict__ xyzs, float bound, const float *__restri
         bool emit = false;
         if (wave_live) {
             {   // (lanes past the end hold zeros from the fetch: same arithmetic, nothing emitted)
-                float px = n_x + bound, py = n_y + bound, pz = n_z + bound;
+                float px = n_p.x + bound, py = n_p.y + bound, pz = n_p.z + bound;
                 if (pow2_bound) { px *= inv_two_b; py *= inv_two_b; pz *= inv_two_b; }   // == the division, exactly
                 else { px /= two_b; py /= two_b; pz /= two_b; }
                 px = px * lv.scale; py = py * lv.scale; pz = pz * lv.scale;
@@ -188,8 +242,7 @@ k_scatter_bin(const float *__restrict__ xyzs, float bound, const float *__restri
                 emit = valid && (!skip_zero || nzg);
             }
         } else {  // nothing is emitted: rows and position are never looked at (defined without an instruction)
-#pragma unroll
-            for (int c = 0; c < 8; ++c) asm("" : "=v"(row[c]));
+            LNERF_UNDEF8(row);
             asm("" : "=v"(p.gx), "=v"(p.gy), "=v"(p.gz), "=v"(p.fx), "=v"(p.fy), "=v"(p.fz));
         }
         // ---- D (a lambda: placed behind the ranking atomics): the values w * g (run sums on coarse levels), packed
@@ -254,9 +307,19 @@ k_scatter_bin(const float *__restrict__ xyzs, float bound, const float *__restri
         if (nb <= 32 && !lv.compact) {  // wave-uniform: every lane emits into one or two buckets
 #pragma unroll
             for (int c = 0; c < 8; ++c) rank_by_ballot(s_cnt[cur], c);
-        } else if (emit) {
+        } else {
+            // (only the atomics are predicated: the ranks are merged into the rows by every lane -- a lane that emits
+            // nothing never looks at its rows -- so that this arm and the one above define the ranked rows in the
+            // same registers.  With the insert under `if (emit)` the rows kept their registers here and were copied,
+            // 8 v_mov per item, to where the other arm leaves them.)
+            uint32_t rk[8];
+            LNERF_UNDEF8(rk);
+            if (emit) {
 #pragma unroll
-            for (int c = 0; c < 8; ++c) row[c] |= (uint32_t)atomicAdd(&s_cnt[cur][row[c] >> BK_SHIFT], 1) << 20;
+                for (int c = 0; c < 8; ++c) rk[c] = (uint32_t)atomicAdd(&s_cnt[cur][row[c] >> BK_SHIFT], 1);
+            }
+#pragma unroll
+            for (int c = 0; c < 8; ++c) row[c] |= rk[c] << 20;
         }
         BIN_STAMP(2);
         // the next item's inputs go into the memory queue now; they are consumed at the top of the next iteration
@@ -301,7 +364,7 @@ k_scatter_bin(const float *__restrict__ xyzs, float bound, const float *__restri
         BIN_STAMP(7);
         // the prefetched inputs are pinned in registers here, so that the next item starts without waiting for the
         // stores below to be acknowledged (one in-order memory counter covers loads and stores)
-        asm volatile("" : "+v"(n_g.x), "+v"(n_g.y), "+v"(n_x), "+v"(n_y), "+v"(n_z));
+        asm volatile("" : "+v"(n_g.x), "+v"(n_g.y), "+v"(n_p));
         // ---- G: the chunk, 16 bytes per lane (a chunk starts on a multiple of 16 bytes; the last unit may carry one
         // stale record behind the item's last one: never read), and the segment table entries of the item
         {
@@ -327,6 +390,7 @@ k_scatter_bin(const float *__restrict__ xyzs, float bound, const float *__restri
     BIN_STAMP_FLUSH();
 }
 #undef LNERF_BIN_LEVEL
+#undef LNERF_UNDEF8
 
 
 void launch_scatter_bin(bool packed, const float *xyzs, float bound, const float *dfeat, const GridMeta &meta,

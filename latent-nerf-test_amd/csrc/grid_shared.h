@@ -245,6 +245,7 @@ struct Rec12 {
 // (native vector types: what __builtin_nontemporal_load / _store take)
 typedef float nt_f4 __attribute__((ext_vector_type(4)));
 typedef float nt_f2 __attribute__((ext_vector_type(2)));
+typedef float nt_f3 __attribute__((ext_vector_type(3)));
 typedef uint32_t nt_u4 __attribute__((ext_vector_type(4)));
 // The binning pass loads dfeat (read once per step) and stores the records (216 MB per frame: more than the Infinity
 // Cache keeps until pass 2 reads them) non-temporally.  Measured together with the reduce pass's non-temporal parameter

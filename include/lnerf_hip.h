@@ -252,6 +252,20 @@ int lnerf_grid_encode_backward_adam(const float *xyzs, float bound, const void *
                                     void *shadow_bf16, float lr, float beta1, float beta2, float eps, int step,
                                     const int32_t *step_dev, float grad_scale, lnerf_stream_t stream);
 
+/* Gradient of the hash-grid features with respect to the sample POSITION (the upstream encoder's `grid_backward_input`).
+ * `dfeat` is f32, level-major [L, level_stride, 2]: exactly what lnerf_mlp_backward writes.  For every row
+ * m < min(m_host, *m_dev) the kernel WRITES (does not accumulate)
+ *   dxyz[m, a] = sum_l scale_l / (2 bound) * sum_c sum_f dfeat[l, m, f] * table[row_c, f] * d w_c / d frac_a
+ * with w_c = (wx wy) wz the forward's corner weight and d w_c / d frac_x = (bx ? +1 : -1) wy wz (likewise y, z); rows at or
+ * beyond that limit are not touched.  Cell, fractions and rows are the forward's (one shared definition): on a lattice
+ * plane the result is the one-sided derivative of the cell the forward put the sample in.  `table` is the table the
+ * forward read (f32 or bf16, table_dtype); `variant` must be 0, optionally with LNERF_GRID_BLOCKED / LNERF_GRID_TILED.
+ * One lane per sample sums its levels in the fixed order 0 .. L-1: no atomics, no workspace, bitwise reproducible. */
+int lnerf_grid_encode_backward_input(const float *xyzs, float bound, const void *table, int table_dtype, int num_levels,
+                                     int level_dim, const int32_t *offsets_host, const float *scales_host,
+                                     const int32_t *res_host, int64_t m_host, const int32_t *m_dev, int64_t level_stride,
+                                     const float *dfeat, float *dxyz, int variant, lnerf_stream_t stream);
+
 /* ---- H7 helper: inverse of the bf16 weight-fragment layout at the head of the MLP workspace: map_wK[2 i], map_wK[2 i + 1] = the two
  * bf16 elements of that image which hold weight i of wK (forward / transposed fragments).  map_w1 int32[64*32*2],
  * map_w2 int32[64*64*2], map_w3 int32[out_dim*64*2].  For lnerf_adam_step_multi_shadow. */
@@ -295,6 +309,17 @@ int lnerf_mlp_backward(const void *feat, int feat_dtype, int64_t level_stride, c
                        const float *dsigmas, const float *drgbs, float *dfeat, float *dw1, float *db1, float *dw2,
                        float *db2, float *dw3, float *db3, int accumulate, void *workspace, size_t workspace_bytes,
                        int precision, void *clear_ptr, size_t clear_bytes, lnerf_stream_t stream);
+
+/* Density gradient and surface normal of the field (the upstream renderer's `normal()`, analytic instead of six finite
+ * differences).  `dxyz_enc` [m, 3] is lnerf_grid_encode_backward_input of the `dfeat` that lnerf_mlp_backward produced
+ * with dsigmas == 1, drgbs == 0: it already carries the trunc-exp factor e = exp(min(pre, 15)) = min(sigma, exp(15)).
+ * This elementwise finish adds the density blob's share and normalises:
+ *   grad_sigma = dxyz_enc + e * blob_scale * exp(-|x|^2 / denom) * (-2 x / denom),   denom = (2 blob_std) blob_std
+ *   normal     = -grad_sigma / sqrt(max(|grad_sigma|^2, 1e-20)), a NaN component becomes 0   (upstream safe_normalize)
+ * for rows m < min(m_host, *m_dev); the other rows are not touched.  grad_sigma and normals (f32 [m, 3]) may each be NULL. */
+int lnerf_density_normals(const float *dxyz_enc, const float *xyzs, const float *sigmas, float blob_scale,
+                          float blob_std, int64_t m_host, const int32_t *m_dev, float *grad_sigma, float *normals,
+                          lnerf_stream_t stream);
 
 /* ---- trainer helper: gradient of the opacity-entropy regulariser of the NeRF trainer (sparsity term) w.r.t.
  * weights_sum [N], in one launch:  L = scale * mean_i H(clamp(ws_i, eps, 1 - eps)),  H(p) = -p log2 p - (1-p) log2(1-p);

@@ -92,6 +92,11 @@ class LogConfig:
     mesh_texture_resolution: int = 0
     # with save_mesh: > 0 decimates the marching-cubes mesh to this many faces (or one fewer) before the colours / bake
     mesh_target_faces: int = 0
+    # with save_mesh: the exported normals (and, textured, an object-space normal map normal_object.png) come from the
+    # field's density gradient at the final vertices instead of the lattice / the decimated faces
+    mesh_field_normals: bool = False
+    # evaluation also writes a normal-shaded render (*_normals.png / *_normals video) beside every *_rgb one
+    eval_normals: bool = False
     max_keep_ckpts: int = 2
     # no progress lines on stdout (log.txt in the experiment directory is still written)
     quiet: bool = False

@@ -74,6 +74,21 @@ def grid_encode_forward(xyzs, bound, table, levels: GridLevels, m_host, m_dev, l
     return out
 
 
+def grid_encode_backward_input(xyzs, bound, table, levels: GridLevels, dfeat, m_host, m_dev, level_stride, out=None):
+    """Gradient of the features with respect to the sample positions (lnerf_grid_encode_backward_input): dfeat f32
+    [L, level_stride, 2] level-major, `table` the table the forward read (f32 or bf16) -> dxyz [rows of xyzs, 3]; rows
+    below min(m_host, *m_dev) are written, the others are zero (or keep what `out` held)."""
+    if table.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("table must be float32 or bfloat16")
+    tdt = _b.F32 if table.dtype == torch.float32 else _b.BF16
+    if out is None:
+        out = torch.zeros(xyzs.shape[0], 3, device=xyzs.device, dtype=torch.float32)
+    _b.call("lnerf_grid_encode_backward_input", *_grid_args(levels, xyzs, bound, m_host, m_dev, level_stride,
+                                                            _chk(table, "table", table.dtype), tdt),
+            _chk(dfeat, "dfeat"), _chk(out, "dxyz"), levels.flag, _stream())
+    return out
+
+
 _scatter_ws = {}   # device -> [workspaces, ascending size]
 
 
@@ -385,6 +400,8 @@ class _GridEncode(torch.autograd.Function):
                                    feat_dtype, encoder.variant)
         ctx.save_for_backward(xyzs, m_dev if m_dev is not None else torch.empty(0))
         ctx.meta = (encoder, bound, m_host, m_dev is not None, level_stride)
+        # the position gradient reads the table the gather read (the bf16 shadow where there is one)
+        ctx.src = src.detach() if ctx.needs_input_grad[0] else None
         return feat
 
     @staticmethod
@@ -394,7 +411,11 @@ class _GridEncode(torch.autograd.Function):
         dfeat = dfeat.contiguous().float()
         route = plan_backward(encoder, m_host, xyzs.device)
         dtable = run_backward(route, xyzs, bound, dfeat, encoder, m_host, m_dev if has_mdev else None, level_stride)
-        return None, dtable, None, None, None, None, None, None, None
+        dxyz = None
+        if ctx.needs_input_grad[0]:
+            dxyz = grid_encode_backward_input(xyzs, bound, ctx.src, encoder.levels, dfeat, m_host,
+                                              m_dev if has_mdev else None, level_stride)
+        return dxyz, dtable, None, None, None, None, None, None, None
 
 
 class GridEncoder(nn.Module):
@@ -439,7 +460,8 @@ class GridEncoder(nn.Module):
         self._shadow_version = self.embeddings._version
 
     def encode(self, xyzs, bound, m_host, m_dev=None, level_stride=None, feat_dtype=torch.float32):
-        """Level-major features [L, level_stride, 2] (differentiable w.r.t. embeddings)."""
+        """Level-major features [L, level_stride, 2] (differentiable w.r.t. embeddings, and w.r.t. xyzs when it
+        requires grad: first order only)."""
         if level_stride is None:
             level_stride = xyzs.shape[0]
         return _GridEncode.apply(xyzs, self.embeddings, self.shadow(), self, bound, m_host, m_dev, level_stride,

@@ -155,6 +155,7 @@ class NeRFNetwork(NeRFRenderer):
                 nn.init.uniform_(w, -bound, bound)
                 nn.init.uniform_(b, -bound, bound)
         self._mlp_ws = None
+        self._normal_ws = None        # MLP workspace of the normal queries (density_gradient / normal): their own
         # bf16 weight fragments at the head of the MLP workspace: which weights they were built from, in which buffer the
         # full image (constants included) was last built, and the optimiser that keeps them current (FusedAdam(mlp=...))
         self._frag_versions = None
@@ -214,6 +215,77 @@ class NeRFNetwork(NeRFRenderer):
     def density(self, x):
         sigmas, rgbs = self.forward(x)
         return {"sigma": sigmas, "albedo": rgbs}
+
+    # ---- surface normals ----------------------------------------------------------------
+    def _density_query(self, x, want_grad, want_normals):
+        """sigma, grad sigma and / or the normal at x [M,3] (contiguous f32), analytically, in five launches:
+        gather -> lnerf_mlp_forward -> lnerf_mlp_backward with dsigmas == 1, drgbs == 0 (its dfeat is d sigma / d feat;
+        LNERF_MLP_DEFER_REDUCE: no weight gradient is reduced or written) -> lnerf_grid_encode_backward_input ->
+        lnerf_density_normals.  Everything runs in a workspace of its own and through no autograd node: the fragment
+        image at the head of the training workspace, the scatter workspace and every `.grad` stay as they are."""
+        dev, M = x.device, x.shape[0]
+        enc, prec = self.encoder, _PREC[self.precision]
+        out_dim = self.w3.shape[0]
+        W = [t.detach() for t in (self.w1, self.b1, self.w2, self.b2, self.w3, self.b3)]
+        need = _b.get_lib().lnerf_mlp_backward_workspace_bytes(out_dim)
+        if self._normal_ws is None or self._normal_ws.device != dev or self._normal_ws.numel() < need:
+            self._normal_ws = torch.empty(need, device=dev, dtype=torch.uint8)
+        ws = self._normal_ws
+        shadow = enc.shadow()
+        src = enc.embeddings.detach() if shadow is None else shadow
+        feat = E.grid_encode_forward(x, self.bound, src, enc.levels, M, None, M, None,
+                                     torch.bfloat16 if prec == _b.BF16 else torch.float32, enc.variant)
+        fdt = _b.BF16 if prec == _b.BF16 else _b.F32
+        sigmas = torch.empty(M, device=dev)
+        rgbs = torch.empty(M, out_dim - 1, device=dev)
+        _b.call("lnerf_mlp_forward", _p(feat), fdt, M, _p(x), *[_p(t) for t in W], out_dim, float(self.blob_scale),
+                float(self.blob_std), M, None, _p(sigmas), _p(rgbs), prec, _p(ws), ws.numel(), _stream())
+        ones = torch.ones(M, device=dev)
+        rgbs.zero_()                                    # (re-used as drgbs == 0)
+        dfeat = torch.empty(feat.shape, device=dev, dtype=torch.float32)
+        # (bf16: the forward above left the fragments of these very weights at the head of `ws`)
+        tag = prec | _b.MLP_DEFER_REDUCE | (_b.MLP_FRAGMENTS_READY if prec == _b.BF16 else 0)
+        _b.call("lnerf_mlp_backward", _p(feat), fdt, M, _p(x), *[_p(t) for t in W], out_dim, float(self.blob_scale),
+                float(self.blob_std), M, None, _p(sigmas), _p(ones), _p(rgbs), _p(dfeat), None, None, None, None, None,
+                None, 0, _p(ws), ws.numel(), tag, None, 0, _stream())
+        dxyz = E.grid_encode_backward_input(x, self.bound, src, enc.levels, dfeat, M, None, M, out=ones.new_empty(M, 3))
+        grad = torch.empty(M, 3, device=dev) if want_grad else None
+        normals = torch.empty(M, 3, device=dev) if want_normals else None
+        _b.call("lnerf_density_normals", _p(dxyz), _p(x), _p(sigmas), float(self.blob_scale), float(self.blob_std), M,
+                None, _p(grad), _p(normals), _stream())
+        if self.density_scale != 1.0:
+            sigmas = self.density_scale * sigmas
+        return sigmas, grad, normals
+
+    def _density_query_chunked(self, x, want_grad, want_normals):
+        x = x.reshape(-1, 3).contiguous().float()
+        M, step = x.shape[0], self.MAX_BF16_STRIDE      # (the bf16 MLP kernels' limit; field() cuts there too)
+        if M == 0:
+            z = torch.zeros(0, 3, device=x.device)
+            return torch.zeros(0, device=x.device), (z if want_grad else None), (z.clone() if want_normals else None)
+        if M <= step:
+            return self._density_query(x, want_grad, want_normals)
+        outs = [self._density_query(x[s:s + step], want_grad, want_normals) for s in range(0, M, step)]
+        return tuple(None if outs[0][k] is None else torch.cat([o[k] for o in outs]) for k in range(3))
+
+    @torch.no_grad()
+    def density_normals(self, xyzs):
+        sigmas, _, normals = self._density_query_chunked(xyzs, False, True)
+        return sigmas, normals
+
+    @torch.no_grad()
+    def density_gradient(self, x):
+        """x [..., 3] -> (sigmas [M] (x density_scale), grad sigma [M, 3]): the exact gradient of the trilinear field
+        (one-sided on lattice planes), the density blob included.  Outside the training graph: nothing here is
+        differentiable and no training state is touched."""
+        sigmas, grad, _ = self._density_query_chunked(x, True, False)
+        return sigmas, grad
+
+    @torch.no_grad()
+    def normal(self, x):
+        """x [..., 3] -> unit surface normals [M, 3] = -grad sigma / |grad sigma| (the zero vector where the gradient
+        vanishes): the upstream renderer's `normal()`, analytic instead of six finite-difference queries."""
+        return self._density_query_chunked(x, False, True)[2]
 
     def background(self, d):
         from .bg import background_net

@@ -118,6 +118,23 @@ class NeRFRenderer(nn.Module):
     def background(self, d):
         raise NotImplementedError()
 
+    def normal(self, x):
+        raise NotImplementedError()
+
+    def density_normals(self, xyzs):
+        """xyzs [M,3] -> (sigmas [M] (x density_scale), unit normals [M,3]), outside autograd."""
+        raise NotImplementedError()
+
+    def _check_shading(self, shading):
+        if shading not in ("albedo", "normal"):
+            raise ValueError("shading must be 'albedo' or 'normal' (got %r)" % (shading,))
+        if shading == "normal" and self.training:
+            # a normal inside the training graph needs the second-order backward of the encoder, which is not built:
+            # refuse rather than hand back an image whose gradient is wrong
+            raise ValueError("shading='normal' is an evaluation render: call .eval() first (normals are not "
+                             "differentiable here)")
+        return shading == "normal"
+
     def reset_extra_state(self):
         self.density_grid.zero_()
         self.density_bitfield.zero_()
@@ -254,12 +271,16 @@ class NeRFRenderer(nn.Module):
         return PreparedRays(march, bg, prefix, N, cap)
 
     def run_cuda(self, rays_o, rays_d, dt_gamma=0.0, bg_color=None, perturb=False, force_all_rays=False,
-                 max_steps=1024, T_thresh=1e-4, prepared=None, **kwargs):
+                 max_steps=1024, T_thresh=1e-4, prepared=None, shading="albedo", **kwargs):
         """rays_o, rays_d [B,N,3] -> dict(image [B,N,C], depth [B,N], weights_sum [B,N]).
         Training mode: march -> hash gather -> MLP -> composite, all on device, no host sync;
         additionally returns the capacity-sized 'xyzs'/'sigmas' with the device counter 'counter'.
-        prepared: a PreparedRays of prepare_rays() (rays_o / rays_d are then ignored and may be None)."""
-        C = self.img_dims
+        prepared: a PreparedRays of prepare_rays() (rays_o / rays_d are then ignored and may be None).
+        shading="normal" (evaluation only): the per-sample colours are (n + 1) / 2 of the field's surface normal n --
+        3 channels whatever img_dims is -- and no background is added; the densities, hence the march, depth and
+        weights_sum, are those of the albedo render."""
+        shade_normal = self._check_shading(shading)
+        C = 3 if shade_normal else self.img_dims
         results = {}
         if self.training:
             if prepared is None:
@@ -279,7 +300,7 @@ class NeRFRenderer(nn.Module):
             rays_d = rays_d.contiguous().view(-1, 3).float()
             N = rays_o.shape[0]
             nears, fars = self._near_far(rays_o, rays_d)
-            bg = self._bg_tensor(bg_color, rays_d, N, C)
+            bg = None if shade_normal else self._bg_tensor(bg_color, rays_d, N, C)
             dev = rays_o.device
             weights_sum = torch.zeros(N, device=dev)
             depth = torch.zeros(N, device=dev)
@@ -296,16 +317,21 @@ class NeRFRenderer(nn.Module):
                 xyzs, dirs, deltas = rm.march_rays(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, self.bound,
                                                    self.density_bitfield, self.cascade, self.grid_size, fars,
                                                    dt_gamma, max_steps)
-                with torch.no_grad():
-                    sigmas, rgbs = self.field(xyzs, xyzs.shape[0])
-                sigmas = self.density_scale * sigmas if self.density_scale != 1.0 else sigmas
+                if shade_normal:
+                    sigmas, rgbs = self.density_normals(xyzs)       # (sigmas: scaled already)
+                    rgbs = (rgbs + 1.0) / 2.0
+                else:
+                    with torch.no_grad():
+                        sigmas, rgbs = self.field(xyzs, xyzs.shape[0])
+                    sigmas = self.density_scale * sigmas if self.density_scale != 1.0 else sigmas
                 rm.composite_rays(n_alive, n_step, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum, depth, image,
                                   trans, T_thresh)
                 spare, n_dev = rm.compact_rays(rays_alive, n_alive, spare, n_dev)
                 rays_alive, spare = spare, rays_alive
                 n_alive = int(n_dev.item())  # live-ray count decides the next launch shape
                 step += n_step
-            image = image + (1.0 - weights_sum)[:, None] * bg
+            if not shade_normal:
+                image = image + (1.0 - weights_sum)[:, None] * bg
         results["image"] = image.view(*prefix, C)
         results["depth"] = depth.view(*prefix)
         results["weights_sum"] = weights_sum.view(*prefix)
@@ -319,15 +345,18 @@ class NeRFRenderer(nn.Module):
             setattr(self, key, cached)
         return cached[1]
 
-    def run(self, rays_o, rays_d, num_steps=128, upsample_steps=0, bg_color=None, perturb=False, **kwargs):
+    def run(self, rays_o, rays_d, num_steps=128, upsample_steps=0, bg_color=None, perturb=False, shading="albedo",
+            **kwargs):
         """Uniform-sampling renderer (`cuda_ray=False`): num_steps samples in [near, far] per ray, optionally refined
         by `upsample_steps` importance samples drawn from the coarse pass's weights (inverse-CDF sampling between
         the mid-points of the coarse samples, stratified when not training), evaluated with the same HIP gather/MLP
-        kernels and composited with the same HIP kernels (every ray owns a fixed span of samples)."""
+        kernels and composited with the same HIP kernels (every ray owns a fixed span of samples).
+        shading="normal" (evaluation only): as in run_cuda."""
+        shade_normal = self._check_shading(shading)
         prefix = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3).float()
         rays_d = rays_d.contiguous().view(-1, 3).float()
-        N, C, dev = rays_o.shape[0], self.img_dims, rays_o.device
+        N, C, dev = rays_o.shape[0], (3 if shade_normal else self.img_dims), rays_o.device
         aabb = self._aabb_host(self.aabb_train if self.training else self.aabb_infer)
         nears, fars = rm.near_far_from_aabb(rays_o, rays_d, aabb, self.min_near)
         hit = nears < fars
@@ -361,9 +390,14 @@ class NeRFRenderer(nn.Module):
         ar = torch.arange(N, device=dev)
         rays = torch.stack([ar, ar * S, torch.full((N,), S, device=dev)], -1).to(torch.int32)
         flat = positions(z).reshape(-1, 3).contiguous()
-        sigmas, rgbs = self.field(flat, flat.shape[0])
-        sigmas = self.density_scale * sigmas if self.density_scale != 1.0 else sigmas
-        bg = self._bg_tensor(bg_color, rays_d, N, C)
+        if shade_normal:
+            sigmas, rgbs = self.density_normals(flat)
+            rgbs = (rgbs + 1.0) / 2.0
+            bg = torch.zeros(N, C, device=dev)            # (no background under a normal render)
+        else:
+            sigmas, rgbs = self.field(flat, flat.shape[0])
+            sigmas = self.density_scale * sigmas if self.density_scale != 1.0 else sigmas
+            bg = self._bg_tensor(bg_color, rays_d, N, C)
         weights_sum, depth, image = rm.composite_rays_train(sigmas, rgbs, deltas, rays, 0.0, bg)
         return {"image": image.view(*prefix, C), "depth": depth.view(*prefix),
                 "weights_sum": weights_sum.view(*prefix)}
@@ -446,7 +480,8 @@ class NeRFRenderer(nn.Module):
         return {"texture": texture, "mask": mask, "rgb": rgb}
 
     @torch.no_grad()
-    def export_mesh(self, path, resolution=None, S=128, thresh=None, texture_resolution=0, gutter=4, target_faces=0):
+    def export_mesh(self, path, resolution=None, S=128, thresh=None, texture_resolution=0, gutter=4, target_faces=0,
+                    field_normals=False):
         """Triangle mesh of the density field -> `path`/mesh.obj (the upstream renderer's export_mesh(path, resolution,
         S)): the density on a `resolution`^3 lattice over [-bound, bound]^3 (density_lattice), marching cubes on the GPU
         at iso `thresh` (default min(mean density, density_thresh), as upstream) with the box capped, vertex colours
@@ -457,6 +492,10 @@ class NeRFRenderer(nn.Module):
         reads).
         target_faces > 0: the marching-cubes mesh is decimated on the GPU to that many faces or one fewer first
         (raymarching.decimate_mesh); the colours, the atlas and the bake are then the decimated mesh's.
+        field_normals: `normals` / the `vn` lines are the FIELD's normals at the final vertices (self.normal: the exact
+        gradient of the density, after the decimation when there is one) instead of the lattice's central differences
+        or the decimated mesh's face sums; a textured export also bakes an object-space normal map, stored as
+        (n + 1) / 2 -- `normal_map` [3,R,R] in the result and normal_object.png beside albedo.png (mesh.mtl unchanged).
         Returns dict(verts [V,3], faces [F,3] int32, normals [V,3], colors [V,3], iso, path, faces_before (the
         marching-cubes face count)) with device tensors, plus vt, ft, texture, mask, rgb when textured."""
         from .mesh_io import write_obj
@@ -477,17 +516,22 @@ class NeRFRenderer(nn.Module):
             pts = verts[s:s + chunk].contiguous()
             _, feats = self.field(pts, pts.shape[0])
             colors[s:s + chunk] = self._latent_preview(feats)
+        if field_normals:
+            normals = (torch.cat([self.normal(verts[s:s + chunk].contiguous()) for s in range(0, verts.shape[0], chunk)])
+                       if verts.shape[0] > 0 else torch.zeros(0, 3, device=verts.device))
         out = os.path.join(str(path), "mesh.obj")
         result = {"verts": verts, "faces": faces, "normals": normals, "colors": colors, "iso": iso, "path": out,
                   "faces_before": faces_before}
         if int(texture_resolution) > 0:
-            result.update(self._export_textured(str(path), verts, faces, normals, int(texture_resolution), gutter, S))
+            result.update(self._export_textured(str(path), verts, faces, normals, int(texture_resolution), gutter, S,
+                                                bool(field_normals)))
         else:
             write_obj(out, verts.cpu().numpy(), faces.cpu().numpy(), normals.cpu().numpy(), colors.cpu().numpy())
         return result
 
-    def _export_textured(self, path, verts, faces, normals, R, gutter, S):
-        """The textured half of export_mesh: atlas, bake, mesh.obj + mesh.mtl + albedo.png (+ latent_texture.pt)."""
+    def _export_textured(self, path, verts, faces, normals, R, gutter, S, normal_map=False):
+        """The textured half of export_mesh: atlas, bake, mesh.obj + mesh.mtl + albedo.png (+ latent_texture.pt;
+        normal_map: + normal_object.png, the field's normals over the same atlas)."""
         import warnings
 
         import numpy as np
@@ -512,6 +556,12 @@ class NeRFRenderer(nn.Module):
         Image.fromarray(albedo).save(os.path.join(path, "albedo.png"))
         if self.latent_mode and baked["texture"].shape[0] == 4:
             torch.save(baked["texture"].cpu(), os.path.join(path, "latent_texture.pt"))
+        if normal_map:
+            nmap = self.bake_texture(verts, faces, vt, ft, resolution=R, gutter=gutter, S=S,
+                                     fn=lambda pts: (self.normal(pts) + 1.0) / 2.0)["texture"]
+            img = (nmap.clamp(0, 1).permute(1, 2, 0).cpu().numpy() * 255).round().astype(np.uint8)
+            Image.fromarray(img).save(os.path.join(path, "normal_object.png"))
+            baked = dict(baked, normal_map=nmap)
         return dict(baked, vt=vt, ft=ft)
 
     def shadow_extra_state(self):
@@ -633,7 +683,7 @@ class NeRFRenderer(nn.Module):
         if staged and not self.cuda_ray:
             dev = rays_o.device
             depth = torch.empty(B, N, device=dev)
-            image = torch.empty(B, N, self.img_dims, device=dev)
+            image = torch.empty(B, N, 3 if kwargs.get("shading", "albedo") == "normal" else self.img_dims, device=dev)
             wsum = torch.empty(B, N, device=dev)
             for b in range(B):
                 for head in range(0, N, max_ray_batch):

@@ -451,20 +451,39 @@ class Trainer:
         return pred, depth
 
     @torch.no_grad()
+    def eval_normals_render(self, data):
+        """uint8 [H,W,3]: the view rendered with shading='normal' ((n + 1) / 2 composited, no background)."""
+        H, W = data["H"], data["W"]
+        out = self.nerf.render(data["rays_o"], data["rays_d"], staged=True, perturb=False, bg_color=None,
+                               shading="normal")
+        img = out["image"].reshape(H, W, 3).float().clamp(0, 1)
+        return (img * 255).round().to(torch.uint8).cpu().numpy()
+
+    @torch.no_grad()
     def evaluate(self, dataset, save_path: Path, save_as_video=False):
         """One render per evaluation pose: PNG files during training, one video for the final pass (file names of
         src/latent_paint/training/trainer.py:146-172)."""
         from PIL import Image
         self.nerf.eval()
-        frames = []
+        frames, normal_frames = [], []
+        with_normals = bool(getattr(self.cfg.log, "eval_normals", False))
         for i, data in enumerate(dataset):
             pred, depth = self.eval_render(data)
             rgb = self.preview_rgb(pred)
             frames.append(rgb)
             if self.rank == 0 and not save_as_video:
                 Image.fromarray(rgb).save(save_path / ("step_%05d_%04d_rgb.png" % (self.train_step, i)))
+            if with_normals:
+                # the normal-shaded render the upstream trainers write beside the colour (shading='normal', no
+                # background): it tells a solid from a billboard where the latent preview cannot
+                nrm = self.eval_normals_render(data)
+                normal_frames.append(nrm)
+                if self.rank == 0 and not save_as_video:
+                    Image.fromarray(nrm).save(save_path / ("step_%05d_%04d_normals.png" % (self.train_step, i)))
         if self.rank == 0 and save_as_video and frames:
             write_video(save_path / ("step_%05d_rgb" % self.train_step), frames)
+            if normal_frames:
+                write_video(save_path / ("step_%05d_normals" % self.train_step), normal_frames)
         return frames
 
     def full_eval(self):
@@ -473,7 +492,8 @@ class Trainer:
             # the density field as a triangle mesh (NeRFRenderer.export_mesh) -> <exp_dir>/mesh/mesh.obj
             tex = int(getattr(self.cfg.log, "mesh_texture_resolution", 0))
             target = int(getattr(self.cfg.log, "mesh_target_faces", 0))
-            mesh = self.nerf.export_mesh(self.exp_path / "mesh", texture_resolution=tex, target_faces=target)
+            mesh = self.nerf.export_mesh(self.exp_path / "mesh", texture_resolution=tex, target_faces=target,
+                                         field_normals=bool(getattr(self.cfg.log, "mesh_field_normals", False)))
             self.log("exported %s (%d vertices, %d triangles; %d before decimation; iso %.4g)"
                      % (mesh["path"], mesh["verts"].shape[0], mesh["faces"].shape[0], mesh["faces_before"], mesh["iso"]))
         return frames

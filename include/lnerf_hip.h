@@ -67,6 +67,8 @@ const char *lnerf_build_info(void);
  *                              2 (default) = additionally one aligned 16-byte load per 4-row group of a bf16 table.
  *   "gather_dedup_max_res":    levels with resolution <= value fetch a cell's 8 vertices once per run of
  *                              lanes (consecutive samples of a ray) in that cell (default 512; 0 = off).
+ *   "gather_lds_pad":          experiment knob: bytes of unused dynamic LDS per gather workgroup, 0 .. 65536 (default 0).
+ *   "scatter_level_groups":    experiment knob: bin + reduce per level group, 1 .. 32 (default 1); the closing-scatter form refuses > 1.
  *   "mlp_fwd_blocks":          persistent workgroups of the bf16 MLP forward (default 768).
  *   "mlp_fwd_wps":             wavefronts per SIMD the bf16 forward is compiled for, 3 (default) or 2.
  *   "mlp_bwd_blocks":          persistent workgroups of the MLP backward (default and maximum 512 = slab count).

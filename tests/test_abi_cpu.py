@@ -138,6 +138,26 @@ def test_scatter_planning_and_new_entry_points_validate(built_lib):
     assert lib.lnerf_set_tuning(b"scatter_bin_debug", 0) == -1 and b"unknown key" in lib.lnerf_last_error()
 
 
+def test_every_tuning_key_accepts_its_default_and_refuses_out_of_range(built_lib):
+    """All twelve keys of lnerf_set_tuning: accepted at the default (tests/exact_grid.py TUNING_DEFAULTS, which the CPU
+    suite checks against the initialisers in the sources) and refused one step outside the documented range, with the
+    key named in the message.  A refused value changes nothing, so the process-wide state stays the default table."""
+    from tests import exact_grid as X
+    lib = B.get_lib()
+    assert sorted(X.TUNING_DEFAULTS) == sorted(X.TUNING_REFUSED) and len(X.TUNING_DEFAULTS) == 12
+    header = open(B.HEADER_PATH).read()
+    for key, value in X.TUNING_DEFAULTS.items():
+        assert '"%s"' % key in header, "include/lnerf_hip.h does not list the key %s" % key
+        assert lib.lnerf_set_tuning(key.encode(), value) == 0, (key, value, lib.lnerf_last_error())
+        for bad in X.TUNING_REFUSED[key]:
+            assert lib.lnerf_set_tuning(key.encode(), bad) == -1, (key, bad)
+            assert key.encode() in lib.lnerf_last_error(), (key, bad, lib.lnerf_last_error())
+        assert lib.lnerf_set_tuning(key.encode(), value) == 0
+    # a flag without a range: any value is taken as on / off
+    assert lib.lnerf_set_tuning(b"scatter_skip_zero", 7) == 0 and lib.lnerf_set_tuning(b"scatter_skip_zero", 1) == 0
+    assert lib.lnerf_set_tuning(None, 1) == -1 and b"null key" in lib.lnerf_last_error()
+
+
 def _device_asm(src):
     """gfx950 assembly of one HIP source (device side only), as text."""
     import subprocess

@@ -278,9 +278,13 @@ def test_grid_encoder_module_is_the_gather_and_the_scatter(dev, scatter_variant)
 def test_blocked_and_tiled_layouts_forward_backward(dev, cfg, table_dtype, gridtype):
     """gridtype = "blocked" (LNERF_GRID_BLOCKED: hashed levels keep 4 x 2 x 2 vertex blocks in 16 consecutive rows) and
     gridtype = "tiled" (LNERF_GRID_TILED: the upstream encoder's other layout, the dense index wrapped into the table --
-    SURVEY.md Appendix A suggests {hash, tiled} x {16, 19}): the gather with every load path (single / pair / aligned
-    quad), the atomic scatter and the bucketed scatter (12- and 8-byte records) against the oracle's restatement of the
-    same layout; dense levels unchanged."""
+    SURVEY.md Appendix A suggests {hash, tiled} x {16, 19}): the gather, the atomic scatter and the bucketed scatter (12- and
+    8-byte records) against the oracle's restatement of the same layout; dense levels unchanged.  Load paths of the gather
+    reached here, at the default gather_pair_loads = 2 and on uniformly random points (runs of one lane: the run
+    de-duplication never has a second lane to serve): the dense pair; tiled: single loads; blocked, f32 table: the
+    aligned pair with its swap (x even) and single loads (x odd); blocked, bf16 table: the aligned quad (x mod 4 != 3)
+    and single loads -- NOT the bf16 pair-and-swap branch, which the quad branch shadows.  That branch, pair_loads 0 / 1,
+    de-duplication on real runs and off, and level sizes that are no power of two: tests/test_gpu_tuning_paths.py."""
     from src.latent_nerf.models import encoding as E
     if cfg == "small":
         kw = dict(num_levels=16, base_resolution=4, desired_resolution=128, log2_hashmap_size=12)

@@ -73,7 +73,7 @@ def main():
             fns["f32tab_bf16out_dedup%d_pairs%d" % (dd, pl)] = mk(table, bf16o)
             fns["bf16tab_bf16out_dedup%d_pairs%d" % (dd, pl)] = mk(table_bf, bf16o)
         t = timed(fns)
-        B.call("lnerf_set_tuning", b"gather_pair_loads", 1)
+        B.call("lnerf_set_tuning", b"gather_pair_loads", 2)   # (the default: csrc/grid.hip g_gather_pairs)
         res["gather_ms(median,min)"] = t
         bps = lambda k: (1024 if k.startswith("f32tab") else 512) + 12 + (128 if "f32out" in k else 64)
         res["gather_GBps_algorithmic"] = {k: round(M * bps(k) / (v[0] * 1e-3) / 1e9, 1) for k, v in t.items()}
@@ -180,7 +180,7 @@ def main():
             fns["mlp_fwd_bf16_wps%d_blocks%d" % (wps, nb)] = f
         res["mlp_ms(median,min)"] = timed(fns)
         B.call("lnerf_set_tuning", b"mlp_fwd_blocks", 768)
-        B.call("lnerf_set_tuning", b"mlp_fwd_wps", 2)
+        B.call("lnerf_set_tuning", b"mlp_fwd_wps", 3)   # (the default: csrc/mlp.hip g_mlp_fwd_wps)
         # backward (recomputes the forward): real upstream gradients of the bench step
         import src.latent_nerf.models.network_grid as NG
         store, keep = {}, {}

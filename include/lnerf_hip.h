@@ -276,6 +276,11 @@ int lnerf_mlp_fragment_maps(int out_dim, int32_t *map_w1, int32_t *map_w2, int32
 /* ---- H7: fused sigma/latent MLP  32 -> 64 -> 64 -> out_dim (= 1 + C), ReLU hidden.
  * Weights are PyTorch nn.Linear layout: w1 [64,32], b1 [64], w2 [64,64], b2 [64], w3 [out_dim,64],
  * b3 [out_dim], all f32.  sigma = exp(h0 + blob_scale*exp(-|x|^2/(2 blob_std^2))), rgbs = h[1:].
+ * out_dim is 2 .. 8 (anything else: LNERF_ERR_INVALID_ARG); the weight-gradient outputs dw3 / db3 hold out_dim rows and
+ * nothing beyond them is written.
+ * Rows m < min(m_host, *m_dev) are computed (m_dev may be NULL: m_host rows; *m_dev above m_host counts as m_host).  Rows
+ * at or beyond that count are NOT written in sigmas, rgbs and dfeat, and what the inputs hold there (stale samples of
+ * an earlier step, NaN included) reaches no output and no gradient.
  * precision: LNERF_F32 -> exact-f32 MFMA (v_mfma_f32_16x16x4_f32), LNERF_BF16 -> bf16 MFMA, f32 acc.
  * level_stride <= 2^24 samples with LNERF_BF16 (32-bit byte offsets inside the bf16 kernels; the exact-f32 kernels take
  * any stride below 2^30); with out_dim == 5 the bf16 path moves the

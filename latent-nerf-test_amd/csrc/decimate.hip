@@ -13,18 +13,18 @@
 //              k_dc_rank     (only in the round that would pass the target) keep the m smallest keys
 //              k_dc_apply, k_dc_remap, (scan), k_dc_compact_faces, lists of the new faces
 //   output     k_dc_count, k_dc_used, (scan), k_dc_out_verts, k_dc_out_faces, lists, k_dc_normals, k_dc_counts
-// scan = k_dc_scan_blocks, k_dc_scan_top (one workgroup), k_dc_scan_add: exclusive int32 prefix with the total at [n].
+// scan = k_dc_scan_blocks, k_scan_top (scan.h, one workgroup), k_dc_scan_add: exclusive int32 prefix with the total at [n].
 #include <algorithm>
 #include <utility>
 
 #include "common.h"
+#include "scan.h"
 
 namespace lnerf {
 
 constexpr int DC_THREADS = 256;
 constexpr int DC_PPT = 16;
 constexpr int DC_BLOCK = DC_THREADS * DC_PPT;
-constexpr int DC_SCAN_THREADS = 1024;
 constexpr unsigned long long DC_NONE = ~0ull;
 
 __device__ __forceinline__ int dc_gid() { return blockIdx.x * DC_THREADS + threadIdx.x; }
@@ -32,51 +32,18 @@ __device__ __forceinline__ int dc_gid() { return blockIdx.x * DC_THREADS + threa
 // ---------------------------------------------------------------- exclusive scan, int32, total at out[n]
 __global__ void __launch_bounds__(DC_THREADS)
 k_dc_scan_blocks(const int32_t *__restrict__ in, int n, int32_t *__restrict__ out, int32_t *__restrict__ blk) {
-    __shared__ int s_w[DC_THREADS / LNERF_WAVE];
     const int base = blockIdx.x * DC_BLOCK + threadIdx.x * DC_PPT;
-    int sum = 0;
+    int sum[1] = {0}, run[1], tot[1];
     for (int q = 0; q < DC_PPT; ++q)
-        if (base + q < n) sum += in[base + q];
-    const int incl = wave_inclusive_sum_i(sum);
-    const int w = threadIdx.x / LNERF_WAVE;
-    if (lane_id() == LNERF_WAVE - 1) s_w[w] = incl;
-    __syncthreads();
-    int run = incl - sum, tot = 0;
-    for (int k = 0; k < DC_THREADS / LNERF_WAVE; ++k) {
-        if (k < w) run += s_w[k];
-        tot += s_w[k];
-    }
+        if (base + q < n) sum[0] += in[base + q];
+    block_exclusive_scan<DC_THREADS>(sum, run, tot);
     for (int q = 0; q < DC_PPT; ++q)
         if (base + q < n) {
             const int x = in[base + q];
-            out[base + q] = run;
-            run += x;
+            out[base + q] = run[0];
+            run[0] += x;
         }
-    if (threadIdx.x == 0) blk[blockIdx.x] = tot;
-}
-
-__global__ void __launch_bounds__(DC_SCAN_THREADS)
-k_dc_scan_top(int32_t *__restrict__ blk, int nb) {
-    __shared__ int s_w[DC_SCAN_THREADS / LNERF_WAVE];
-    const int chunk = (nb + DC_SCAN_THREADS - 1) / DC_SCAN_THREADS;
-    const int b0 = min((int)threadIdx.x * chunk, nb), b1 = min(b0 + chunk, nb);
-    int s = 0;
-    for (int b = b0; b < b1; ++b) s += blk[b];
-    const int incl = wave_inclusive_sum_i(s);
-    const int w = threadIdx.x / LNERF_WAVE;
-    if (lane_id() == LNERF_WAVE - 1) s_w[w] = incl;
-    __syncthreads();
-    int run = incl - s, tot = 0;
-    for (int k = 0; k < DC_SCAN_THREADS / LNERF_WAVE; ++k) {
-        if (k < w) run += s_w[k];
-        tot += s_w[k];
-    }
-    for (int b = b0; b < b1; ++b) {
-        const int x = blk[b];
-        blk[b] = run;
-        run += x;
-    }
-    if (threadIdx.x == 0) blk[nb] = tot;
+    if (threadIdx.x == 0) blk[blockIdx.x] = tot[0];
 }
 
 __global__ void __launch_bounds__(DC_THREADS)
@@ -509,14 +476,12 @@ struct DcLayout {
     size_t pos, Q, fa, fb, cnt, off, list, locked, remap, K1, K2, FK, keys, vstar, flag, at, sel, keep, blk, dev, bytes;
 };
 
-static size_t dc_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static DcLayout dc_layout(int V, int F) {
     const int64_t n = std::max(3 * (int64_t)F, (int64_t)V) + 1;     // longest scan input, plus its total
     const int64_t nb = div_up(n, DC_BLOCK) + 1;
     DcLayout L;
     size_t o = 0;
-    auto take = [&o](size_t bytes) { const size_t at = o; o += dc_align(bytes); return at; };
+    auto take = [&o](size_t bytes) { const size_t at = o; o += align256(bytes); return at; };
     L.pos = take((size_t)V * 12);
     L.Q = take((size_t)V * 80);
     L.fa = take((size_t)F * 12);
@@ -570,7 +535,10 @@ static int dc_scan(const DcRun &r, const int32_t *in, int n, int32_t *out) {
     const int nb = (int)div_up(std::max(n, 1), DC_BLOCK);
     int32_t *blk = r.at<int32_t>(r.L.blk);
     hipLaunchKernelGGL(k_dc_scan_blocks, dim3(nb), dim3(DC_THREADS), 0, r.s, in, n, out, blk);
-    hipLaunchKernelGGL(k_dc_scan_top, dim3(1), dim3(DC_SCAN_THREADS), 0, r.s, blk, nb);
+    // (int32: more than 1024 blocks, where a thread of k_scan_top owns several entries, takes over 1.4 M faces, too many
+    // for a test through the Python restatement; the int64 instantiation of the same template is tested on that side)
+    hipLaunchKernelGGL(k_scan_top<int32_t>, dim3(1), dim3(SCAN_TOP_THREADS), 0, r.s, blk, (int32_t *)nullptr, (int64_t)nb,
+                       blk + nb, (int32_t *)nullptr);
     hipLaunchKernelGGL(k_dc_scan_add, dim3(dc_grid(std::max(n, 1))), dim3(DC_THREADS), 0, r.s, out, n, blk, nb);
     LNERF_CHECK_LAUNCH("decimate(scan)");
     return LNERF_OK;

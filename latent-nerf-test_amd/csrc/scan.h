@@ -1,0 +1,92 @@
+// Prefix sums shared by the mesh-export kernels (isosurface.hip, uvbake.hip, decimate.hip): a compaction there is
+//   per block   block_exclusive_scan inside the kernel that counts, its block total -> blk[block]
+//   k_scan_top  ONE workgroup: exclusive prefix of the block totals (in place) and the grand total
+//   per block   block prefix + position in the block
+// Integer sums only, so every order of addition gives the same bits.
+#pragma once
+#include "common.h"
+
+namespace lnerf {
+
+constexpr int SCAN_TOP_THREADS = 1024;
+
+static inline size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+// inclusive wave scan (sum) of a 64-bit value: wave_inclusive_sum_i's DPP steps move 32 bits, so this one shuffles
+__device__ __forceinline__ long long wave_inclusive_sum_ll(long long x) {
+    const int lane = lane_id();
+#pragma unroll
+    for (int o = 1; o < LNERF_WAVE; o <<= 1) {
+        const long long u = __shfl_up(x, o, LNERF_WAVE);
+        if (lane >= o) x += u;
+    }
+    return x;
+}
+template <typename T>
+__device__ __forceinline__ T wave_inclusive_sum_int(T x) {
+    if constexpr (sizeof(T) == 4) return (T)wave_inclusive_sum_i((int)x);
+    else return (T)wave_inclusive_sum_ll((long long)x);
+}
+
+// Exclusive prefix over a workgroup of THREADS threads of N counters carried together (one barrier for all of them):
+// excl[c] = sum of v[c] over the threads before this one, total[c] = sum over the workgroup.
+//   - EVERY thread of the workgroup calls it: there is a barrier inside.
+//   - The per-wave slots are the function's own (declared here, not passed in: a pointer parameter loses the LDS
+//     address space, see grid.hip scatter_reduce_one), one set per <THREADS, T, N>.  A second call with the same
+//     arguments in one kernel reuses them, so it needs a __syncthreads() between the two calls.
+template <int THREADS, typename T, int N>
+__device__ __forceinline__ void block_exclusive_scan(const T (&v)[N], T (&excl)[N], T (&total)[N]) {
+    constexpr int WAVES = THREADS / LNERF_WAVE;
+    __shared__ T s_w[N][WAVES];
+    const int w = threadIdx.x / LNERF_WAVE;
+    T incl[N];
+#pragma unroll
+    for (int c = 0; c < N; ++c) incl[c] = wave_inclusive_sum_int(v[c]);
+    if (lane_id() == LNERF_WAVE - 1) {
+#pragma unroll
+        for (int c = 0; c < N; ++c) s_w[c][w] = incl[c];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+        T before = 0, all = 0;
+#pragma unroll
+        for (int k = 0; k < WAVES; ++k) {
+            const T x = s_w[c][k];
+            if (k < w) before += x;
+            all += x;
+        }
+        excl[c] = before + incl[c] - v[c];
+        total[c] = all;
+    }
+}
+
+// ONE workgroup: exclusive prefix of a[0, nb) in place and its total -> *total_a; the same for b and *total_b unless b is
+// NULL.  Thread t owns the ceil(nb / SCAN_TOP_THREADS) consecutive entries from t * that on.  total_a may be a + nb.
+template <typename T>
+__global__ void __launch_bounds__(SCAN_TOP_THREADS)
+k_scan_top(T *__restrict__ a, T *__restrict__ b, int64_t nb, T *__restrict__ total_a, T *__restrict__ total_b) {
+    const int64_t chunk = (nb + SCAN_TOP_THREADS - 1) / SCAN_TOP_THREADS;
+    const int64_t b0 = min((int64_t)threadIdx.x * chunk, nb), b1 = min(b0 + chunk, nb);
+    T sum[2] = {0, 0}, run[2], total[2];
+    for (int64_t k = b0; k < b1; ++k) {
+        sum[0] += a[k];
+        if (b) sum[1] += b[k];
+    }
+    block_exclusive_scan<SCAN_TOP_THREADS>(sum, run, total);
+    for (int64_t k = b0; k < b1; ++k) {
+        const T x = a[k], y = b ? b[k] : 0;
+        a[k] = run[0];
+        run[0] += x;
+        if (b) {
+            b[k] = run[1];
+            run[1] += y;
+        }
+    }
+    if (threadIdx.x == 0) {
+        *total_a = total[0];
+        if (b) *total_b = total[1];
+    }
+}
+
+}  // namespace lnerf

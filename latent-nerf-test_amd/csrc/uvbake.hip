@@ -4,23 +4,24 @@
 // lnerf_uv_raster, stage by stage (every pass linear in its work, no cross-workgroup waiting):
 //   ITEMS  k_uv_setup  one lane per face: pixel-space corners, area, candidate box; items = box area; an in-block
 //                      exclusive prefix of the items (int64) and per-block item / bad-index totals
-//          k_uv_scan   ONE workgroup: exclusive prefix of the block totals (in place) -> counts[0] items, [1] bad faces
+//          k_scan_top  (scan.h) ONE workgroup: exclusive prefix of the block totals (in place) -> counts[0] items,
+//                      [1] bad faces
 //   COVER  k_uv_cover  one lane per (face, box texel) item, so one big UV triangle does not serialise on one lane:
 //                      the item's face by binary search over the item prefix, the edge test, atomicMax of the face
 //                      index into texel_face (the largest covering index wins, whatever the order)
 //          k_uv_count  one lane per texel: covered texels per block of UV_THREADS texels
-//          k_uv_scan   exclusive prefix of those -> counts[2] = P
+//          k_scan_top  exclusive prefix of those -> counts[2] = P
 //   EMIT   k_uv_emit   one lane per texel: rank among the block's covered texels (ballot / mbcnt + wave totals in LDS),
 //                      texel_idx and the surface point at block prefix + rank (ascending linear order)
 // lnerf_uv_dilate: one launch per gutter round (k_uv_dilate), ping-ponging between the caller's two buffers.
 #include "common.h"
+#include "scan.h"
 
 namespace lnerf {
 
 constexpr int UV_THREADS = 256;
 constexpr int UV_LOG2 = 8;
 constexpr int UV_WAVES = UV_THREADS / LNERF_WAVE;
-constexpr int UV_SCAN_THREADS = 1024;
 constexpr int64_t UV_ITEMS_PER_LAUNCH = int64_t(1) << 30;
 
 struct UvMesh {
@@ -85,23 +86,10 @@ __device__ __forceinline__ bool uv_cover(const UvTri &t, int i, int j, float e[3
     return t.area > 0.f ? (e[0] >= 0.f && e[1] >= 0.f && e[2] >= 0.f) : (e[0] <= 0.f && e[1] <= 0.f && e[2] <= 0.f);
 }
 
-__device__ __forceinline__ long long uv_wave_incl(long long x) {
-    const int lane = lane_id();
-#pragma unroll
-    for (int o = 1; o < LNERF_WAVE; o <<= 1) {
-        const long long u = __shfl_up(x, o, LNERF_WAVE);
-        if (lane >= o) x += u;
-    }
-    return x;
-}
-
 __global__ void __launch_bounds__(UV_THREADS)
 k_uv_setup(UvMesh m, int64_t *__restrict__ face_off, int64_t *__restrict__ blk_items, int64_t *__restrict__ blk_bad) {
-    __shared__ long long s_items[UV_WAVES];
-    __shared__ int s_bad[UV_WAVES];
     const int f = blockIdx.x * UV_THREADS + threadIdx.x;
-    long long items = 0;
-    int bad = 0;
+    long long items = 0, bad = 0;
     if (f < m.n_faces) {
         if (uv_indices_ok(m, f)) {
             UvTri t;
@@ -111,56 +99,13 @@ k_uv_setup(UvMesh m, int64_t *__restrict__ face_off, int64_t *__restrict__ blk_i
             bad = 1;
         }
     }
-    const long long incl = uv_wave_incl(items);
-    const int nbad = (int)__popcll(__ballot(bad));
-    const int w = threadIdx.x / LNERF_WAVE;
-    if (lane_id() == LNERF_WAVE - 1) { s_items[w] = incl; s_bad[w] = nbad; }
-    __syncthreads();
-    long long before = 0, total = 0;
-    int tbad = 0;
-#pragma unroll
-    for (int k = 0; k < UV_WAVES; ++k) {
-        if (k < w) before += s_items[k];
-        total += s_items[k];
-        tbad += s_bad[k];
-    }
-    if (f < m.n_faces) face_off[f] = before + incl - items;
+    const long long n[2] = {items, bad};
+    long long excl[2], total[2];
+    block_exclusive_scan<UV_THREADS>(n, excl, total);
+    if (f < m.n_faces) face_off[f] = excl[0];
     if (threadIdx.x == 0) {
-        blk_items[blockIdx.x] = total;
-        blk_bad[blockIdx.x] = tbad;
-    }
-}
-
-// exclusive prefix of a[0, nb) in place, its total -> *total_a; the sum of b[0, nb) -> *total_b (b may be NULL)
-__global__ void __launch_bounds__(UV_SCAN_THREADS)
-k_uv_scan(int64_t *__restrict__ a, const int64_t *__restrict__ b, int64_t nb, int64_t *__restrict__ total_a,
-          int64_t *__restrict__ total_b) {
-    __shared__ long long s_a[UV_SCAN_THREADS / LNERF_WAVE], s_b[UV_SCAN_THREADS / LNERF_WAVE];
-    const int64_t chunk = (nb + UV_SCAN_THREADS - 1) / UV_SCAN_THREADS;
-    const int64_t b0 = min((int64_t)threadIdx.x * chunk, nb), b1 = min(b0 + chunk, nb);
-    long long sa = 0, sb = 0;
-    for (int64_t k = b0; k < b1; ++k) {
-        sa += a[k];
-        if (b) sb += b[k];
-    }
-    const long long ai = uv_wave_incl(sa), bi = uv_wave_incl(sb);
-    const int w = threadIdx.x / LNERF_WAVE;
-    if (lane_id() == LNERF_WAVE - 1) { s_a[w] = ai; s_b[w] = bi; }
-    __syncthreads();
-    long long run = ai - sa, ta = 0, tb = 0;
-    for (int k = 0; k < UV_SCAN_THREADS / LNERF_WAVE; ++k) {
-        if (k < w) run += s_a[k];
-        ta += s_a[k];
-        tb += s_b[k];
-    }
-    for (int64_t k = b0; k < b1; ++k) {
-        const long long v = a[k];
-        a[k] = run;
-        run += v;
-    }
-    if (threadIdx.x == 0) {
-        *total_a = ta;
-        if (total_b) *total_b = tb;
+        blk_items[blockIdx.x] = total[0];
+        blk_bad[blockIdx.x] = total[1];
     }
 }
 
@@ -288,8 +233,8 @@ static UvLayout uv_layout(int n_faces, int R) {
     UvLayout L;
     L.nbF = div_up(n_faces, UV_THREADS);
     L.nbT = div_up((int64_t)R * R, UV_THREADS);
-    L.off_bytes = (size_t)div_up((int64_t)n_faces * 8, 256) * 256;
-    L.blk_bytes = (size_t)div_up(L.nbF * 8, 256) * 256;
+    L.off_bytes = align256((size_t)n_faces * 8);
+    L.blk_bytes = align256((size_t)L.nbF * 8);
     L.bytes = L.off_bytes + 2 * L.blk_bytes + (size_t)L.nbT * 8;
     return L;
 }
@@ -337,8 +282,8 @@ int lnerf_uv_raster(const float *verts, int n_verts, const int32_t *faces, const
             hipLaunchKernelGGL(k_uv_setup, dim3((unsigned)L.nbF), dim3(UV_THREADS), 0, s, m, face_off, blk_items, blk_bad);
             LNERF_CHECK_LAUNCH("uv_raster(setup)");
         }
-        hipLaunchKernelGGL(k_uv_scan, dim3(1), dim3(UV_SCAN_THREADS), 0, s, blk_items, blk_bad, L.nbF, counts_dev,
-                           counts_dev + 1);
+        hipLaunchKernelGGL(k_scan_top<int64_t>, dim3(1), dim3(SCAN_TOP_THREADS), 0, s, blk_items, blk_bad, L.nbF,
+                           counts_dev, counts_dev + 1);
         LNERF_CHECK_LAUNCH("uv_raster(scan items)");
     }
     if (stages & LNERF_UV_COVER) {
@@ -354,7 +299,7 @@ int lnerf_uv_raster(const float *verts, int n_verts, const int32_t *faces, const
         }
         hipLaunchKernelGGL(k_uv_count, dim3((unsigned)L.nbT), dim3(UV_THREADS), 0, s, texel_face, n_texels, blk_texels);
         LNERF_CHECK_LAUNCH("uv_raster(count)");
-        hipLaunchKernelGGL(k_uv_scan, dim3(1), dim3(UV_SCAN_THREADS), 0, s, blk_texels, (const int64_t *)nullptr,
+        hipLaunchKernelGGL(k_scan_top<int64_t>, dim3(1), dim3(SCAN_TOP_THREADS), 0, s, blk_texels, (int64_t *)nullptr,
                            L.nbT, counts_dev + 2, (int64_t *)nullptr);
         LNERF_CHECK_LAUNCH("uv_raster(scan texels)");
     }

@@ -338,6 +338,17 @@ def marching_cubes(volume, iso, lo, hi, close_boundary=True):
     return verts, faces, normals
 
 
+def _face_index(t, op, name, dev):
+    """`t` as a contiguous int32 [F,3] index tensor on `dev`; `op` and `name` go into the messages."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError("%s: %s must be a [F,3] index tensor" % (op, name))
+    if t.dtype.is_floating_point:
+        raise TypeError("%s: %s must hold integers" % (op, name))
+    if t.dtype != torch.int32 and t.numel() and (int(t.min()) < -2 ** 31 or int(t.max()) >= 2 ** 31):
+        raise ValueError("%s: %s has indices outside int32" % (op, name))   # (a wrapped index could be a valid one)
+    return t.to(device=dev, dtype=torch.int32).contiguous()
+
+
 def decimate_mesh(verts, faces, target_faces, max_error=float("inf"), max_rounds=_b.DECIMATE_DEFAULT_ROUNDS, stats=None):
     """Quadric-error decimation on the GPU (lnerf_decimate, include/lnerf_hip.h): rounds of independent edge collapses until
     at most `target_faces` faces are left -- target_faces or one fewer, unless a round finds no valid collapse, max_rounds
@@ -347,10 +358,7 @@ def decimate_mesh(verts, faces, target_faces, max_error=float("inf"), max_rounds
     and collapses.  Synchronous: one host read of the counts per round."""
     if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3:
         raise ValueError("decimate_mesh: verts must be [V,3]")
-    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError("decimate_mesh: faces must be a [F,3] index tensor")
-    if faces.dtype.is_floating_point:
-        raise TypeError("decimate_mesh: faces must hold integers")
+    faces = _face_index(faces, "decimate_mesh", "faces", verts.device)
     target_faces, max_rounds, max_error = int(target_faces), int(max_rounds), float(max_error)
     if target_faces < 0 or max_rounds < 0:
         raise ValueError("decimate_mesh: target_faces (%d) and max_rounds (%d) must be >= 0" % (target_faces, max_rounds))
@@ -359,9 +367,6 @@ def decimate_mesh(verts, faces, target_faces, max_error=float("inf"), max_rounds
     verts = verts.contiguous()
     _chk(verts, "verts")
     dev = verts.device
-    if faces.dtype != torch.int32 and faces.numel() and (int(faces.min()) < -2 ** 31 or int(faces.max()) >= 2 ** 31):
-        raise ValueError("decimate_mesh: faces has indices outside int32")   # (a wrapped index could be a valid one)
-    faces = faces.to(device=dev, dtype=torch.int32).contiguous()
     V, F = int(verts.shape[0]), int(faces.shape[0])
     nbytes = _b.get_lib().lnerf_decimate_scratch_bytes(V, F)
     if nbytes == 0:
@@ -380,16 +385,6 @@ def decimate_mesh(verts, faces, target_faces, max_error=float("inf"), max_rounds
 
 
 # ------------------------------------------------------------------------------ texture baking
-def _uv_index(t, name, dev):
-    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 3:
-        raise ValueError("uv_raster: %s must be a [F,3] index tensor" % name)
-    if t.dtype.is_floating_point:
-        raise TypeError("uv_raster: %s must hold integers" % name)
-    if t.dtype != torch.int32 and t.numel() and (int(t.min()) < -2 ** 31 or int(t.max()) >= 2 ** 31):
-        raise ValueError("uv_raster: %s has indices outside int32" % name)   # (a wrapped index could be a valid one)
-    return t.to(device=dev, dtype=torch.int32).contiguous()
-
-
 def uv_raster(verts, faces, vt, ft, R):
     """Which texel of an R x R texture each face of a UV-mapped mesh covers (lnerf_uv_raster, include/lnerf_hip.h).
     verts [V,3], faces [F,3] (into verts), vt [T,2], ft [F,3] (into vt), all on the GPU.
@@ -407,7 +402,7 @@ def uv_raster(verts, faces, vt, ft, R):
     dev = verts.device
     verts = verts.to(torch.float32).contiguous()
     vt = vt.to(device=dev, dtype=torch.float32).contiguous()
-    faces, ft = _uv_index(faces, "faces", dev), _uv_index(ft, "ft", dev)
+    faces, ft = _face_index(faces, "uv_raster", "faces", dev), _face_index(ft, "uv_raster", "ft", dev)
     if faces.shape[0] != ft.shape[0]:
         raise ValueError("uv_raster: faces has %d rows, ft %d" % (faces.shape[0], ft.shape[0]))
     _chk(verts, "verts")

@@ -1,6 +1,7 @@
 """Mesh export on the MI355X: lnerf_marching_cubes against the numpy restatement (tests/mc_reference.py: faces equal,
 vertices bit for bit), its edge cases and geometry, a real shape (teddy's winding-number grid), NeRFRenderer.export_mesh
 end to end (f32 and the bf16 `blocked` default) and the trainer's `log.save_mesh`."""
+import functools
 import math
 import os
 
@@ -36,6 +37,7 @@ def _grid(shape, lo, hi):
     return np.meshgrid(*axes, indexing="ij")
 
 
+@functools.lru_cache(maxsize=None)
 def _volumes():
     rng = np.random.default_rng(5)
     X, Y, Z = _grid((32, 32, 32), (-1, -1, -1), (1, 1, 1))
@@ -46,11 +48,14 @@ def _volumes():
     aniso = (np.sin(3 * X2) * np.cos(2 * Y2) + 0.8 * Z2 - 0.3).astype(np.float32)
     ties = rng.integers(0, 3, (17, 13, 19)).astype(np.float32)       # many values exactly at iso 1
     ties[3, 4, 5] = np.nan
+    # a plane through 1088 blocks of points (closed; 1039 open): over 1024, a thread of the top-level scan owns two
+    slab = (np.float32(0.31) - _grid((62, 254, 270), (-1, -1, -1), (1, 1, 1))[0]).astype(np.float32)
     return [("sphere", sphere, 0.0, (-1, -1, -1), (1, 1, 1)),
             ("torus", torus, 0.0, (-1, -1, -1), (1, 1, 1)),
             ("noise", noise, 0.1, (0, 0, 0), (1, 1, 1)),
             ("aniso", aniso, 0.0, (-1.0, -0.5, 0.0), (1.0, 2.0, 0.75)),
-            ("ties", ties, 1.0, (0, 0, 0), (2, 3, 4))]
+            ("ties", ties, 1.0, (0, 0, 0), (2, 3, 4)),
+            ("slab", slab, 0.0, (-1, -1, -1), (1, 1, 1))]
 
 
 @pytest.mark.parametrize("close", [True, False])
@@ -60,6 +65,9 @@ def test_op_matches_restatement_bit_for_bit(dev, case, close):
     v, f, n = _mc(torch.from_numpy(vol).to(dev), iso, lo, hi, close)
     rv, rf, rn = R.marching_cubes(vol, iso, lo, hi, close_boundary=close)
     assert len(f) > 0
+    if case == "slab":
+        assert np.prod(np.add(vol.shape, 2 if close else 0)) > 1024 * 4096          # over 1024 blocks either way
+        assert (len(rv), len(rf)) == ((179080, 358156) if close else (68580, 136114))
     assert np.array_equal(f, rf)
     assert v.shape == rv.shape and np.array_equal(v.view(np.uint32), rv.view(np.uint32))
     ok = np.isfinite(rn).all(1)

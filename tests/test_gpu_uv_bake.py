@@ -62,12 +62,17 @@ def _cases(dev):
     ovt = (rng.uniform(-0.4, 1.4, (F, 1, 2)) + rng.uniform(-0.15, 0.15, (F, 3, 2))).reshape(-1, 2).astype(np.float32)
     ovt[0:3] = [[-5.0, -5.0], [6.0, -5.0], [0.5, 7.0]]          # one triangle much larger than the texture
     ovt[3:6] = [[2.0, 2.0], [3.0, 2.0], [2.0, 3.0]]             # nowhere near it
+    # two triangles over most of a 1024 x 1024 texture: 4096 blocks of texels, so a thread of the top-level scan owns four
+    qv = np.float32([[0, 0, 0], [1, 0, 0], [1, 1, 0], [0, 1, 0]])
+    qvt = np.float32([[0.05, 0.05], [0.95, 0.05], [0.95, 0.95], [0.05, 0.95]])
+    qf = np.array([[0, 1, 2], [0, 2, 3]])
     return [("blub256", bv, bf, bvt, bft, 256), ("blub300", bv, bf, bvt, bft, 300),
             ("sphere_atlas", sv, sf, svt.numpy(), sft.numpy(), atlas_min_resolution(len(sf))),
-            ("overlap", rv, rf, rvt, rf, 97), ("degenerate", rv, rf, dvt, rf, 64), ("outside", rv, rf, ovt, rf, 50)]
+            ("overlap", rv, rf, rvt, rf, 97), ("degenerate", rv, rf, dvt, rf, 64), ("outside", rv, rf, ovt, rf, 50),
+            ("quad1024", qv, qf, qvt, qf, 1024)]
 
 
-CASE_NAMES = ["blub256", "blub300", "sphere_atlas", "overlap", "degenerate", "outside"]
+CASE_NAMES = ["blub256", "blub300", "sphere_atlas", "overlap", "degenerate", "outside", "quad1024"]
 
 
 def _bits(a):
@@ -92,6 +97,10 @@ def test_op_matches_restatement_bit_for_bit(dev, case):
         assert not np.isin([0, 1, 2, 3, 4, 6], rtf).any()             # zero-area / non-finite faces cover nothing
     if case == "outside":
         assert rtf.reshape(-1)[ridx].tolist().count(0) > 0 and 1 not in rtf
+    if case == "quad1024":
+        per_block = (rtf >= 0).reshape(-1, 256).sum(1)                # empty, partly covered and full blocks of texels
+        assert [(per_block == 0).sum(), ((per_block > 0) & (per_block < 256)).sum(), (per_block == 256).sum()] \
+            == [408, 1844, 1844] and len(ridx) == 850084
     # a gutter over a random texture (C = 4 and C = 3) against the restatement
     rng = np.random.default_rng(R)
     for C, passes in ((4, 4), (3, 3)):

@@ -366,6 +366,30 @@ int lnerf_composite_rays_train_backward(const float *grad_weights_sum, const flo
                                         int C, float T_thresh, float *grad_sigmas, float *grad_rgbs, float *grad_bg,
                                         lnerf_stream_t stream);
 
+/* ---- RGB refinement stage (render.nerf_type = latent_tune): the C = 4 compositing above with a linear latent -> RGB
+ * decoder D (f32 [3][4], row-major `decoder[12]`, no bias) behind it.  Per sample c_k = (D z_k + 1) / 2, no clamp; the
+ * kernels compute the per-ray regrouping of the same sum:
+ *   latent_image = sum_k w_k z_k  (no background),   image = (D latent_image + ws) / 2 + (1 - ws) bg_color
+ * bg_color is RGB, [N,3] or NULL.  latents, latent_image (and grad_latents) must be 16-byte aligned. */
+int lnerf_composite_rays_train_decode_forward(const float *sigmas, const float *latents, const float *deltas,
+                                              const int32_t *rays, int64_t N, float T_thresh, const float *decoder,
+                                              const float *bg_color, float *weights_sum, float *depth,
+                                              float *latent_image, float *image, lnerf_stream_t stream);
+/* grad_weights_sum / grad_depth / grad_bg may be NULL; grad_image is [N,3].  grad_sigmas [.], grad_latents [.,4] as in
+ * lnerf_composite_rays_train_backward.  grad_decoder[c][j] = 1/2 sum_rays grad_image[.][c] latent_image[.][j] is
+ * OVERWRITTEN, by a second launch of one workgroup that adds in a fixed order: the same bits on every run. */
+int lnerf_composite_rays_train_decode_backward(const float *grad_weights_sum, const float *grad_depth,
+                                               const float *grad_image, const float *sigmas, const float *latents,
+                                               const float *deltas, const int32_t *rays, const float *weights_sum,
+                                               const float *depth, const float *latent_image, const float *decoder,
+                                               const float *bg_color, int64_t N, float T_thresh, float *grad_sigmas,
+                                               float *grad_latents, float *grad_bg, float *grad_decoder,
+                                               lnerf_stream_t stream);
+/* The same epilogue per pixel, for the inference loop (which composites the 4 latent channels with lnerf_composite_rays):
+ * image [N,3] from latent_image [N,4] and weights_sum [N].  Forward only. */
+int lnerf_decode_image(const float *latent_image, const float *weights_sum, const float *decoder, const float *bg_color,
+                       int64_t N, float *image, lnerf_stream_t stream);
+
 /* ---- H10: occupancy grid refresh pieces (`update_extra_state`): cell sample points,
  * decayed max update, mean, then lnerf_packbits.  Update and mean are ORDER-INDEPENDENT (replicas of a data-parallel
  * run refresh their grids redundantly and must stay bit-identical): a cell listed several times takes the maximum of

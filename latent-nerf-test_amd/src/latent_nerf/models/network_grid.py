@@ -123,7 +123,11 @@ class NeRFNetwork(NeRFRenderer):
         super().__init__(cfg, latent_mode=cfg.nerf_type == NeRFType.latent)
         if hidden_dim != 64 or num_levels * level_dim != 32:
             raise ValueError("the fused HIP MLP is built for 32 -> 64 -> 64 -> 1+C")
+        # latent_tune: the RGB refinement stage -- the latent field (4 latents per sample, no sigmoid) with a linear
+        # latent -> RGB decoder behind the compositing; the renders are RGB
+        self.tuned = cfg.nerf_type == NeRFType.latent_tune
         self.img_dims = 3 + 1 if self.latent_mode else 3
+        self.field_dims = 4 if self.tuned else self.img_dims      # channels field() returns per sample
         self.blob_scale, self.blob_std = blob_scale, blob_std
         self.precision = cfg.precision("mlp_precision")
         table_dtype = torch.bfloat16 if cfg.precision("table_dtype") == "bf16" else torch.float32
@@ -132,7 +136,7 @@ class NeRFNetwork(NeRFRenderer):
                                    scatter_variant=(cfg.scatter_variant if cfg.scatter_variant >= 0
                                                     else (3 if self.precision == "bf16" else 2)),
                                    gridtype=cfg.layout() if hasattr(cfg, "layout") else getattr(cfg, "gridtype", "hash"))
-        in_dim, out_dim = self.encoder.out_dim, 1 + self.img_dims
+        in_dim, out_dim = self.encoder.out_dim, 1 + self.field_dims
         # nn.Linear default init, kept as bare parameters: the fused kernel takes all six at once
         self.w1 = nn.Parameter(torch.empty(hidden_dim, in_dim))
         self.b1 = nn.Parameter(torch.empty(hidden_dim))
@@ -144,6 +148,11 @@ class NeRFNetwork(NeRFRenderer):
             bound = 1.0 / math.sqrt(w.shape[1])
             nn.init.uniform_(w, -bound, bound)
             nn.init.uniform_(b, -bound, bound)
+        if self.tuned:
+            from ..training.guidance import LATENT_TO_RGB
+            # D [3,4], no bias: starts as the known linear latent -> RGB estimate, so a latent checkpoint renders as its
+            # preview did
+            self.decoder = nn.Parameter(torch.tensor(LATENT_TO_RGB, dtype=torch.float32).T.contiguous())
         self.bg_radius = cfg.bg_radius
         if self.bg_radius > 0:
             self.bg_w1 = nn.Parameter(torch.empty(64, 39))
@@ -185,7 +194,8 @@ class NeRFNetwork(NeRFRenderer):
 
     # ---- per-sample field -------------------------------------------------------------
     def field(self, xyzs, m_host, m_dev=None, level_stride=None):
-        """xyzs [cap,3] -> sigmas [cap], latents [cap,C] for the first min(m_host, *m_dev) rows."""
+        """xyzs [cap,3] -> sigmas [cap], latents [cap,C] for the first min(m_host, *m_dev) rows (C = 4 latents in the
+        latent and latent_tune types, 3 sigmoid colours in the rgb type)."""
         if level_stride is None:
             level_stride = xyzs.shape[0]
         if self.precision == "bf16" and level_stride > self.MAX_BF16_STRIDE and m_dev is None \
@@ -204,9 +214,16 @@ class NeRFNetwork(NeRFRenderer):
         if not ready and self.precision == "bf16" and int(m_host) > 0:   # that forward built the whole image
             self._frag_built_in = ws.data_ptr()
             self._frag_versions = self.weight_versions()
-        if not self.latent_mode:
+        if not (self.latent_mode or self.tuned):
             rgbs = torch.sigmoid(rgbs)
         return sigmas, rgbs
+
+    def decode_points(self, latents):
+        """latents [M,4] -> RGB [M,3] = (z D^T + 1) / 2 clamped to [0, 1]: the decoder for per-point uses (vertex
+        colours, baked textures).  latent_tune only."""
+        if not self.tuned:
+            raise RuntimeError("decode_points needs render.nerf_type = latent_tune (this model has no decoder)")
+        return ((latents.float() @ self.decoder.detach().T + 1.0) / 2.0).clamp(0, 1)
 
     def forward(self, x, d=None):
         x = x.reshape(-1, 3).contiguous().float()
@@ -294,6 +311,8 @@ class NeRFNetwork(NeRFRenderer):
     def get_params(self, lr):
         params = [{"params": [self.encoder.embeddings], "lr": lr * 10},
                   {"params": [self.w1, self.b1, self.w2, self.b2, self.w3, self.b3], "lr": lr}]
+        if self.tuned:
+            params.append({"params": [self.decoder], "lr": lr})
         if self.bg_radius > 0:
             params.append({"params": [self.bg_w1, self.bg_b1, self.bg_w2, self.bg_b2], "lr": lr})
         return params

@@ -72,6 +72,7 @@ class NeRFRenderer(nn.Module):
         super().__init__()
         self.cfg = cfg
         self.latent_mode = latent_mode
+        self.tuned = False            # NeRFNetwork: render.nerf_type = latent_tune (4 latents per sample + a decoder)
         self.bound = float(cfg.bound)
         self.cascade = 1 + math.ceil(math.log2(cfg.bound)) if cfg.bound > 1 else 1
         self.grid_size = int(cfg.grid_size)
@@ -119,6 +120,9 @@ class NeRFRenderer(nn.Module):
         raise NotImplementedError()
 
     def normal(self, x):
+        raise NotImplementedError()
+
+    def decode_points(self, latents):
         raise NotImplementedError()
 
     def density_normals(self, xyzs):
@@ -273,7 +277,8 @@ class NeRFRenderer(nn.Module):
     def run_cuda(self, rays_o, rays_d, dt_gamma=0.0, bg_color=None, perturb=False, force_all_rays=False,
                  max_steps=1024, T_thresh=1e-4, prepared=None, shading="albedo", **kwargs):
         """rays_o, rays_d [B,N,3] -> dict(image [B,N,C], depth [B,N], weights_sum [B,N]).
-        Training mode: march -> hash gather -> MLP -> composite, all on device, no host sync;
+        Training mode: march -> hash gather -> MLP -> composite, all on device, no host sync (latent_tune: the fused
+        composite + decode, image in RGB);
         additionally returns the capacity-sized 'xyzs'/'sigmas' with the device counter 'counter'.
         prepared: a PreparedRays of prepare_rays() (rays_o / rays_d are then ignored and may be None).
         shading="normal" (evaluation only): the per-sample colours are (n + 1) / 2 of the field's surface normal n --
@@ -281,6 +286,7 @@ class NeRFRenderer(nn.Module):
         weights_sum, are those of the albedo render."""
         shade_normal = self._check_shading(shading)
         C = 3 if shade_normal else self.img_dims
+        decode = self.tuned and not shade_normal   # composite 4 latent channels, decode per ray (bg_color is RGB)
         results = {}
         if self.training:
             if prepared is None:
@@ -291,7 +297,11 @@ class NeRFRenderer(nn.Module):
             m_dev = march.counter[0:1]
             sigmas, rgbs = self.field(march.xyzs, cap, m_dev, cap)
             sigmas = self.density_scale * sigmas if self.density_scale != 1.0 else sigmas
-            weights_sum, depth, image = rm.composite_rays_train(sigmas, rgbs, march.deltas, march.rays, T_thresh, bg)
+            if decode:
+                weights_sum, depth, image, _ = rm.composite_rays_train_decode(sigmas, rgbs, march.deltas, march.rays,
+                                                                             self.decoder, T_thresh, bg)
+            else:
+                weights_sum, depth, image = rm.composite_rays_train(sigmas, rgbs, march.deltas, march.rays, T_thresh, bg)
             results.update(xyzs=march.xyzs, sigmas=sigmas, counter=march.counter, rays=march.rays,
                            deltas=march.deltas)
         else:
@@ -304,7 +314,7 @@ class NeRFRenderer(nn.Module):
             dev = rays_o.device
             weights_sum = torch.zeros(N, device=dev)
             depth = torch.zeros(N, device=dev)
-            image = torch.zeros(N, C, device=dev)
+            image = torch.zeros(N, 4 if decode else C, device=dev)
             trans = torch.ones(N, device=dev)
             rays_alive = torch.arange(N, dtype=torch.int32, device=dev)
             spare = torch.empty_like(rays_alive)
@@ -330,7 +340,9 @@ class NeRFRenderer(nn.Module):
                 rays_alive, spare = spare, rays_alive
                 n_alive = int(n_dev.item())  # live-ray count decides the next launch shape
                 step += n_step
-            if not shade_normal:
+            if decode:
+                image = rm.decode_image(image, weights_sum, self.decoder, bg)
+            elif not shade_normal:
                 image = image + (1.0 - weights_sum)[:, None] * bg
         results["image"] = image.view(*prefix, C)
         results["depth"] = depth.view(*prefix)
@@ -398,7 +410,10 @@ class NeRFRenderer(nn.Module):
             sigmas, rgbs = self.field(flat, flat.shape[0])
             sigmas = self.density_scale * sigmas if self.density_scale != 1.0 else sigmas
             bg = self._bg_tensor(bg_color, rays_d, N, C)
-        weights_sum, depth, image = rm.composite_rays_train(sigmas, rgbs, deltas, rays, 0.0, bg)
+        if self.tuned and not shade_normal:
+            weights_sum, depth, image, _ = rm.composite_rays_train_decode(sigmas, rgbs, deltas, rays, self.decoder, 0.0, bg)
+        else:
+            weights_sum, depth, image = rm.composite_rays_train(sigmas, rgbs, deltas, rays, 0.0, bg)
         return {"image": image.view(*prefix, C), "depth": depth.view(*prefix),
                 "weights_sum": weights_sum.view(*prefix)}
 
@@ -441,9 +456,11 @@ class NeRFRenderer(nn.Module):
         return vol
 
     def _latent_preview(self, feats):
-        """[N,C] field features -> [N,3] RGB in [0, 1]: latent mode, the linear latent->RGB preview; RGB mode, the
-        first three channels."""
+        """[N,C] field features -> [N,3] RGB in [0, 1]: latent mode, the linear latent->RGB preview; latent_tune, the
+        model's decoder; RGB mode, the first three channels."""
         from ..training.guidance import LATENT_TO_RGB
+        if self.tuned and feats.shape[-1] == 4:
+            return self.decode_points(feats)
         if self.latent_mode and feats.shape[-1] == 4:
             m = torch.tensor(LATENT_TO_RGB, device=feats.device, dtype=torch.float32)
             rgb = (feats.float() @ m) / 2 + 0.5
@@ -455,7 +472,7 @@ class NeRFRenderer(nn.Module):
     def bake_texture(self, verts, faces, vt, ft, resolution=1024, gutter=4, S=128, fn=None):
         """Sample the field over a mesh's UV atlas.  Every texel whose centre a face covers (lnerf_uv_raster: the
         face with the largest index where charts overlap) gets fn(surface point), fn(pts [P,3]) -> [P,C] queried in
-        S^3-point chunks (default: the field's features, 4-channel latents or RGB); then `gutter` dilation rounds
+        S^3-point chunks (default: the field's features, 4-channel latents -- latent_tune included -- or RGB); then `gutter` dilation rounds
         (lnerf_uv_dilate) spread the chart borders outwards so that bilinear lookups there do not blend in zeros.
         Texel (i, j) sits at u = (j + 0.5) / R, v = 1 - (i + 0.5) / R, the convention Latent-Paint's texture lookup uses.
         -> dict(texture [C,R,R] f32, mask [R,R] uint8 (2 covered, 1 gutter, 0 empty), rgb [3,R,R] in [0, 1])."""
@@ -469,7 +486,7 @@ class NeRFRenderer(nn.Module):
         P = pos.shape[0]
         chunk = int(S) ** 3
         feats = [fn(pos[s:s + chunk].contiguous()).float() for s in range(0, P, chunk)]
-        C = feats[0].shape[-1] if feats else (4 if self.latent_mode else 3)
+        C = feats[0].shape[-1] if feats else (4 if (self.latent_mode or self.tuned) else 3)
         texture = torch.zeros(C, R * R, device=dev, dtype=torch.float32)
         if P > 0:
             texture[:, texel_idx.long()] = torch.cat(feats).T
@@ -485,11 +502,12 @@ class NeRFRenderer(nn.Module):
         """Triangle mesh of the density field -> `path`/mesh.obj (the upstream renderer's export_mesh(path, resolution,
         S)): the density on a `resolution`^3 lattice over [-bound, bound]^3 (density_lattice), marching cubes on the GPU
         at iso `thresh` (default min(mean density, density_thresh), as upstream) with the box capped, vertex colours
-        from the field at the vertices (latent mode: the linear latent->RGB preview), clamped to [0, 1].
+        from the field at the vertices (latent mode: the linear latent->RGB preview; latent_tune: the model's decoder,
+        decode_points), clamped to [0, 1].
         texture_resolution > 0: a textured mesh instead -- the per-triangle UV atlas, the field baked into it at that
         side (bake_texture, `gutter` dilation rounds), mesh.obj with v / vt / vn / f v/vt/vn, mesh.mtl, albedo.png
-        (the RGB preview) and, in latent mode, latent_texture.pt ([4,R,R] f32, what Latent-Paint's guide.init_texture
-        reads).
+        (the RGB preview; latent_tune: the decoder's colours) and, in latent and latent_tune mode, latent_texture.pt
+        ([4,R,R] f32, what Latent-Paint's guide.init_texture reads).
         target_faces > 0: the marching-cubes mesh is decimated on the GPU to that many faces or one fewer first
         (raymarching.decimate_mesh); the colours, the atlas and the bake are then the decimated mesh's.
         field_normals: `normals` / the `vn` lines are the FIELD's normals at the final vertices (self.normal: the exact
@@ -554,7 +572,7 @@ class NeRFRenderer(nn.Module):
                            normals.cpu().numpy(), material="mesh.mtl", texture="albedo.png")
         albedo = (baked["rgb"].permute(1, 2, 0).cpu().numpy() * 255).round().astype(np.uint8)
         Image.fromarray(albedo).save(os.path.join(path, "albedo.png"))
-        if self.latent_mode and baked["texture"].shape[0] == 4:
+        if (self.latent_mode or self.tuned) and baked["texture"].shape[0] == 4:
             torch.save(baked["texture"].cpu(), os.path.join(path, "latent_texture.pt"))
         if normal_map:
             nmap = self.bake_texture(verts, faces, vt, ft, resolution=R, gutter=gutter, S=S,

@@ -88,6 +88,10 @@ _SIGNATURES = {
                            _P, _P, _P, _I, _P, _Z, _I, _P, _Z, _P],
     "lnerf_composite_rays_train_forward": [_P, _P, _P, _P, _L, _I, _F, _P, _P, _P, _P, _P],
     "lnerf_composite_rays_train_backward": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _F, _P, _P, _P, _P],
+    "lnerf_composite_rays_train_decode_forward": [_P, _P, _P, _P, _L, _F, _P, _P, _P, _P, _P, _P, _P],
+    "lnerf_composite_rays_train_decode_backward": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _F, _P, _P, _P, _P,
+                                                   _P],
+    "lnerf_decode_image": [_P, _P, _P, _P, _L, _P, _P],
     "lnerf_opacity_entropy_grad": [_P, _L, _F, _F, _P, _P],
     "lnerf_synthetic_guidance": [_P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _F, _U, _P, _P, _P, _F, _F, _P, _P],
     "lnerf_occ_cell_points": [_P, _L, _I, _I, _F, _P, _P, _P],

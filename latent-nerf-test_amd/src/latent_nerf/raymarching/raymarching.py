@@ -301,6 +301,74 @@ def composite_rays_train(sigmas, rgbs, deltas, rays, T_thresh=1e-4, bg_color=Non
     return _CompositeRaysTrain.apply(sigmas, rgbs, deltas, rays, T_thresh, bg_color)
 
 
+class _CompositeRaysTrainDecode(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, sigmas, latents, deltas, rays, decoder, T_thresh, bg_color):
+        sigmas = sigmas.contiguous()
+        latents = latents.contiguous()
+        decoder = decoder.contiguous()
+        if latents.shape[1] != 4 or tuple(decoder.shape) != (3, 4):
+            raise ValueError("composite_rays_train_decode: latents must be [M,4] and the decoder [3,4]")
+        N = rays.shape[0]
+        dev = sigmas.device
+        weights_sum = torch.empty(N, device=dev, dtype=torch.float32)
+        depth = torch.empty(N, device=dev, dtype=torch.float32)
+        latent_image = torch.empty(N, 4, device=dev, dtype=torch.float32)
+        image = torch.empty(N, 3, device=dev, dtype=torch.float32)
+        bg = None if bg_color is None else bg_color.contiguous()
+        _b.call("lnerf_composite_rays_train_decode_forward", _chk(sigmas, "sigmas"), _chk(latents, "latents"),
+                _chk(deltas, "deltas"), _chk(rays, "rays", torch.int32), N, float(T_thresh), _chk(decoder, "decoder"),
+                _chk(bg, "bg_color", allow_none=True), _p(weights_sum), _p(depth), _p(latent_image), _p(image), _stream())
+        ctx.save_for_backward(sigmas, latents, deltas, rays, decoder, weights_sum, depth, latent_image, bg)
+        ctx.set_materialize_grads(False)  # unused outputs (depth, weights_sum) arrive as None, not as zero fills
+        ctx.mark_non_differentiable(latent_image)
+        ctx.T_thresh = float(T_thresh)
+        ctx.bg_needs_grad = bg_color is not None and bg_color.requires_grad
+        return weights_sum, depth, image, latent_image
+
+    @staticmethod
+    def backward(ctx, g_ws, g_depth, g_image, _g_latent_image):
+        sigmas, latents, deltas, rays, decoder, weights_sum, depth, latent_image, bg = ctx.saved_tensors
+        N = rays.shape[0]
+        g_image = torch.zeros(N, 3, device=sigmas.device) if g_image is None else g_image.contiguous()
+        g_ws = None if g_ws is None else g_ws.contiguous()
+        g_depth = None if g_depth is None else g_depth.contiguous()
+        d_sigmas = torch.empty_like(sigmas)
+        d_latents = torch.empty_like(latents)
+        d_bg = torch.empty_like(bg) if ctx.bg_needs_grad else None
+        # (N == 0: the library launches nothing, and the sum over no rays is zero)
+        d_decoder = torch.empty_like(decoder) if N > 0 else torch.zeros_like(decoder)
+        _b.call("lnerf_composite_rays_train_decode_backward", _chk(g_ws, "grad_weights_sum", allow_none=True),
+                _chk(g_depth, "grad_depth", allow_none=True), _chk(g_image, "grad_image"), _p(sigmas), _p(latents),
+                _p(deltas), _p(rays), _p(weights_sum), _p(depth), _p(latent_image), _p(decoder), _p(bg), N, ctx.T_thresh,
+                _p(d_sigmas), _p(d_latents), _p(d_bg), _p(d_decoder), _stream())
+        return d_sigmas, d_latents, None, None, d_decoder, None, d_bg
+
+
+def composite_rays_train_decode(sigmas, latents, deltas, rays, decoder, T_thresh=1e-4, bg_color=None):
+    """The RGB refinement stage's compositing: sigmas [M], latents [M,4], deltas [M,2], rays int32 [N,3], decoder [3,4]
+    -> weights_sum [N], depth [N], image [N,3] = sum_k w_k (D z_k + 1) / 2 + (1 - weights_sum) * bg_color (RGB), and the
+    composited latents latent_image [N,4] (no background; not differentiable).  sigmas, latents, decoder and bg_color
+    receive gradients; the decoder's is the same bits on every run."""
+    return _CompositeRaysTrainDecode.apply(sigmas, latents, deltas, rays, decoder, T_thresh, bg_color)
+
+
+def decode_image(latent_image, weights_sum, decoder, bg_color=None):
+    """latent_image [N,4], weights_sum [N], decoder [3,4] -> image [N,3] = (D L + ws) / 2 + (1 - ws) * bg_color: the
+    epilogue of composite_rays_train_decode per pixel (lnerf_decode_image), for the inference loop.  Forward only."""
+    latent_image = latent_image.contiguous()
+    weights_sum = weights_sum.contiguous()
+    decoder = decoder.detach().contiguous()
+    N = latent_image.shape[0]
+    if latent_image.shape[1] != 4 or tuple(decoder.shape) != (3, 4):
+        raise ValueError("decode_image: latent_image must be [N,4] and the decoder [3,4]")
+    bg = None if bg_color is None else bg_color.contiguous()
+    image = torch.empty(N, 3, device=latent_image.device, dtype=torch.float32)
+    _b.call("lnerf_decode_image", _chk(latent_image, "latent_image"), _chk(weights_sum, "weights_sum"),
+            _chk(decoder, "decoder"), _chk(bg, "bg_color", allow_none=True), N, _p(image), _stream())
+    return image
+
+
 # ------------------------------------------------------------------------------ mesh export
 def marching_cubes(volume, iso, lo, hi, close_boundary=True):
     """Iso-surface of a dense f32 volume [nx, ny, nz] (z fastest) on the GPU (lnerf_marching_cubes, include/lnerf_hip.h).

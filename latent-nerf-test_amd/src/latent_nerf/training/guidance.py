@@ -229,14 +229,30 @@ class StableDiffusionGuidance(Guidance):
         imgs = self.vae.decode(latents.to(self.device) / VAE_SCALE).sample
         return (imgs / 2 + 0.5).clamp(0, 1)
 
-    @torch.no_grad()
-    def encode_imgs(self, imgs):
-        """[B,3,H,W] in [0,1] -> latents [B,4,H/8,W/8]: posterior sample of vae.encode(2 imgs - 1) x 0.18215
-        (src/stable_diffusion.py:482-489)."""
+    def _encode(self, imgs):
         if self.vae is None:
             raise NotImplementedError("this checkpoint has no VAE: encode_imgs is unavailable")
         posterior = self.vae.encode(2 * imgs.to(self.device) - 1).latent_dist
         return posterior.sample() * VAE_SCALE
+
+    @torch.no_grad()
+    def encode_imgs(self, imgs):
+        """[B,3,H,W] in [0,1] -> latents [B,4,H/8,W/8]: posterior sample of vae.encode(2 imgs - 1) x 0.18215
+        (src/stable_diffusion.py:482-489)."""
+        return self._encode(imgs)
+
+    def train_step_rgb(self, text_z, pred_rgb, dirs=None):
+        """The RGB mode of the reference's train_step (src/stable_diffusion.py:265-268, 320-334): pred_rgb [B,3,H,W] in
+        [0,1] is up-sampled bilinearly to 512 x 512 and encoded WITH autograd, the SDS gradient is taken on those
+        latents, and what comes back is its pull-back through the encoder: the gradient w.r.t. pred_rgb, same shape (the
+        caller injects it with `pred.backward(gradient=grad)` like the latent one).  Parity unpinned: driven by stub
+        modules only."""
+        with torch.enable_grad():
+            x = pred_rgb.detach().requires_grad_(True)
+            up = torch.nn.functional.interpolate(x, (512, 512), mode="bilinear", align_corners=False)
+            latents = self._encode(up)
+        grad = self.train_step(text_z, latents.detach())
+        return torch.autograd.grad(latents, x, grad)[0]
 
 
 def sparsity_loss_grad(weights_sum, scale, eps=1e-5):

@@ -170,11 +170,14 @@ class Trainer:
         """dirs: the views' direction buckets (host ints).  Direction-specific prompts: one guidance call per view."""
         if isinstance(self.diffusion, SyntheticGuidance):
             return self.diffusion.train_step(self.text_z, pred, dirs=torch.as_tensor(dirs, dtype=torch.long))
+        step = self.diffusion.train_step
+        if not self.nerf.latent_mode and hasattr(self.diffusion, "train_step_rgb"):
+            step = self.diffusion.train_step_rgb      # an RGB prediction: the gradient comes back through the encoder
         if not isinstance(self.text_z, list):
-            return self.diffusion.train_step(self.text_z, pred)
+            return step(self.text_z, pred)
         if pred.shape[0] == 1:
-            return self.diffusion.train_step(self.text_z[int(dirs[0])], pred)
-        return torch.cat([self.diffusion.train_step(self.text_z[int(d)], pred[i:i + 1]) for i, d in enumerate(dirs)])
+            return step(self.text_z[int(dirs[0])], pred)
+        return torch.cat([step(self.text_z[int(d)], pred[i:i + 1]) for i, d in enumerate(dirs)])
 
     def _backward(self, out, pred, grad, grad_ws=None):
         """SDS: d(loss)/d(pred) = grad (src/latent_paint_mesh/training/trainer.py:657-658).  The sparsity term's gradient
@@ -499,13 +502,17 @@ class Trainer:
         return frames
 
     def preview_rgb(self, latents):
-        """[1,C,H,W] latents -> uint8 [H',W',3].  With `log.decode_eval` the guidance model's decoder turns the latents
+        """[1,C,H,W] latents (latent_tune: the decoded RGB prediction) -> uint8 [H',W',3].  With `log.decode_eval` the guidance model's decoder turns the latents
         into the image (vae.decode, src/stable_diffusion.py:462-470; a guidance object without a decoder gives the
         linear preview at 8x); default: the linear latent->RGB estimate at the render resolution (no VAE offline)."""
         if getattr(self.cfg.log, "decode_eval", False) and self.nerf.latent_mode:
             rgb = decode_with(self.diffusion, latents.float())[0].permute(1, 2, 0).cpu()
             return tensor2numpy(rgb)
         x = latents[0].permute(1, 2, 0).float().cpu()
+        if self.nerf.tuned and x.shape[-1] == 3:
+            # a decoded prediction is RGB in [0, 1] already (unclamped): tensor2numpy takes a non-negative array as that
+            # and would read one negative value as "this image is in [-1, 1]"
+            return tensor2numpy(x.clamp(0, 1))
         rgb = x @ _LATENT_TO_RGB if x.shape[-1] == 4 else x[..., :3]
         return tensor2numpy(rgb.clamp(-1, 1))
 

@@ -137,8 +137,12 @@ __device__ __forceinline__ bf16x8 ld_frag(const __bf16 *frag, int f, int lane) {
 // `m` is CLAMPED into the valid samples by the callers (no exec-masked branch around the loads): a row past the end
 // reads the last sample's features, which nothing consumes -- its outputs are not stored (forward) and its upstream
 // gradient is zero (backward).
+// FB16 (compile time: a run-time test of a.feat_bf16 here puts two load forms on two arms inside the step loops, and the
+// merge of the arms waits for everything in flight).  bf16 features are RAW loads -- four dwords that are the operand
+// as they arrive; f32 features are converted where they are loaded.
+template <bool FB16>
 __device__ __forceinline__ bf16x8 load_x(const MlpArgs &a, int64_t m, int q) {
-    if (a.feat_bf16) {
+    if (FB16) {
         // 32-bit byte offsets from the (uniform) base: `global_load_dword v, v_off, s[base]` instead of three 64-bit
         // VALU operations per address (the launcher checks 16 * level_stride * 8 < 2^32)
         const char *f = reinterpret_cast<const char *>(a.feat);
@@ -266,16 +270,36 @@ struct Stamps {
 };
 #endif
 
-// shared forward: xB[T] -> h1B[2][T], h2B[2][T] (packed, relu'd; T 16-sample column tiles); weights from LDS fragments
+// The loop-invariant operands of layers 1 and 2 that the forward keeps in registers across its steps: the twelve weight
+// fragments and layer 1's biases, read from LDS ONCE in front of the step loop (the loop holds an asm volatile, behind
+// which the optimiser re-reads anything it has not been handed as a value).  Layer 2's biases and layer 3's fragments
+// are re-read every step: with them the kernel would not fit the 168 registers of three waves per SIMD.
+struct HeldFragments {
+    bf16x8 w1[4], w2[8];
+    f32x4 b1[4];
+    __device__ __forceinline__ void read(const __bf16 *frag, const float *sB1, int lane) {
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+            w1[mt] = ld_frag(frag, F_W1A + mt, lane);
+            b1[mt] = ld_bias4(sB1, 16 * mt + 4 * (lane >> 4));
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) w2[i] = ld_frag(frag, F_W2A + i, lane);
+    }
+};
+
+// shared forward: xB[T] -> h1B[2][T], h2B[2][T] (packed, relu'd; T 16-sample column tiles); weights from LDS fragments,
+// or from `held` where the caller keeps them in registers
 template <int T>
 __device__ __forceinline__ void forward_hidden(const __bf16 *frag, const float *sB1, const float *sB2, int lane,
-                                               const bf16x8 xB[T], bf16x8 h1B[2][T], bf16x8 h2B[2][T], Stamps &st) {
+                                               const bf16x8 xB[T], bf16x8 h1B[2][T], bf16x8 h2B[2][T], Stamps &st,
+                                               const HeldFragments *held = nullptr) {
     const int q = lane >> 4;
     f32x4 acc[4][T];
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) {
-        const bf16x8 w = ld_frag(frag, F_W1A + mt, lane);
-        const f32x4 b = ld_bias4(sB1, 16 * mt + 4 * q);
+        const bf16x8 w = held ? held->w1[mt] : ld_frag(frag, F_W1A + mt, lane);
+        const f32x4 b = held ? held->b1[mt] : ld_bias4(sB1, 16 * mt + 4 * q);
 #pragma unroll
         for (int t = 0; t < T; ++t) acc[mt][t] = MFMA32(w, xB[t], b);
     }
@@ -291,7 +315,7 @@ __device__ __forceinline__ void forward_hidden(const __bf16 *frag, const float *
         for (int t = 0; t < T; ++t) acc[mt][t] = b;
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            const bf16x8 w = ld_frag(frag, F_W2A + 2 * mt + s, lane);
+            const bf16x8 w = held ? held->w2[2 * mt + s] : ld_frag(frag, F_W2A + 2 * mt + s, lane);
 #pragma unroll
             for (int t = 0; t < T; ++t) acc[mt][t] = MFMA32(w, h1B[s][t], acc[mt][t]);
         }
@@ -304,9 +328,25 @@ __device__ __forceinline__ void forward_hidden(const __bf16 *frag, const float *
 }
 
 // ------------------------------------------------------------------ forward
+// "These registers are needed HERE": an empty asm that reads and rewrites them.  The compiler places its wait for the
+// loads that fill the first group in front of it, and what is stored from the second group is stored behind it.  Both
+// step loops use it ONCE per step, behind the step's last MFMA and in front of its stores: the next step's inputs were
+// requested at the top of the step and have had all of its arithmetic to arrive; the stores go out behind the wait, so
+// that the wait of the NEXT step does not cover their acknowledgements too (a wave has one in-order counter for loads
+// and stores).  Without it the compiler waits where a value is first touched -- at the selects behind a load, at the
+// merge of two arms that load differently, at the first MFMA of the next step with vmcnt(0), i.e. for the stores.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void pin_x(bf16x8 &a, bf16x8 &b) {
+    u32x4 ua = __builtin_bit_cast(u32x4, a), ub = __builtin_bit_cast(u32x4, b);
+    asm volatile("" : "+v"(ua), "+v"(ub));
+    a = __builtin_bit_cast(bf16x8, ua);
+    b = __builtin_bit_cast(bf16x8, ub);
+}
+
 // WPS: wavefronts per SIMD the register allocation aims at, 3 or 2 (mlp_fwd_wps).  Four (128 VGPRs) spilled 396 bytes
-// per lane to scratch and was measured slower.
-template <int WPS>
+// per lane to scratch and was measured slower.  FB16 / OUT5: a.feat_bf16 and a.out_dim == 5 at compile time (the
+// launcher picks): no run-time branch around a load or a store form inside the step loop.
+template <int WPS, bool FB16, bool OUT5>
 __global__ void __launch_bounds__(256, WPS)
 k_mlp_forward_bf16(MlpArgs a, float *__restrict__ sigmas, float *__restrict__ rgbs) {
     __shared__ __attribute__((aligned(16))) __bf16 frag[F_FWD * 512];
@@ -319,52 +359,74 @@ k_mlp_forward_bf16(MlpArgs a, float *__restrict__ sigmas, float *__restrict__ rg
     if (tid < 16) sB3[tid] = tid < a.out_dim ? a.b3[tid] : 0.f;
     __syncthreads();
     const int nrgb = a.out_dim - 1;
+    // The inputs of a step -- features and positions of this wave's two 16-sample tiles -- are requested one step ahead:
+    // raw loads by EVERY lane (the four q lanes of a sample read the same position) of rows clamped into the valid
+    // samples, no lane predicate and no arithmetic on them until the step that consumes them.
     bf16x8 xB[2];
+    Pos3 pos[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-        const int64_t m = (int64_t)blockIdx.x * 128 + w * 32 + 16 * t + c;
-        xB[t] = load_x(a, clamp_row(m, M), q);
+        const int64_t mc = clamp_row((int64_t)blockIdx.x * 128 + w * 32 + 16 * t + c, M);
+        xB[t] = load_x<FB16>(a, mc, q);
+        pos[t] = load_pos(a, mc);
     }
+    // (waited for HERE: a load still pending at the loop's entry makes the compiler wait at the top of every step)
+    pin_x(xB[0], xB[1]);
+    asm volatile("" : "+v"(pos[0].x), "+v"(pos[0].y), "+v"(pos[0].z), "+v"(pos[1].x), "+v"(pos[1].y), "+v"(pos[1].z));
+    HeldFragments held;
+    held.read(frag, sB1, lane);
     Stamps st;
     st.init();
     for (int64_t tile = blockIdx.x; tile * 128 < M; tile += gridDim.x) {
         const int64_t m0 = tile * 128 + w * 32;
-        // the next tile's features are requested now and waited for after this tile's arithmetic
+        // this step's density blobs, from the positions that arrived during the previous step
+        float blob[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) blob[t] = blob_at(a, pos[t]);
+        // the next step's inputs: requested now, pinned behind this step's last MFMA
         bf16x8 xB_n[2], h1B[2][2], h2B[2][2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            const int64_t m = m0 + (int64_t)gridDim.x * 128 + 16 * t + c;
-            xB_n[t] = load_x(a, clamp_row(m, M), q);
+            const int64_t mc = clamp_row(m0 + (int64_t)gridDim.x * 128 + 16 * t + c, M);
+            xB_n[t] = load_x<FB16>(a, mc, q);
+            pos[t] = load_pos(a, mc);
         }
+        // (the instruction scheduler may not move anything over this line: left alone it sinks the loads to the end of
+        // the step, next to their wait)
+        __builtin_amdgcn_sched_barrier(0);
         st.mark(0);
-        forward_hidden<2>(frag, sB1, sB2, lane, xB, h1B, h2B, st);
+        forward_hidden<2>(frag, sB1, sB2, lane, xB, h1B, h2B, st, &held);
         const f32x4 b3 = ld_bias4(sB3, 4 * q);
-        // (the loop-invariant fragments of layers 1 and 2 live in registers; layer 3's two are re-read from LDS every
-        // tile through an index the optimiser cannot see through: hoisted as well they cost the third wave per SIMD)
-        int lane3 = lane;
-        asm("" : "+v"(lane3) : "s"((int)tile));   // no side effects (the other fragment reads stay hoisted), varies per tile
-        const bf16x8 w3a = ld_frag(frag, F_W3A, lane3), w3b = ld_frag(frag, F_W3A + 1, lane3);
+        const bf16x8 w3a = ld_frag(frag, F_W3A, lane), w3b = ld_frag(frag, F_W3A + 1, lane);
+        f32x4 o[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            f32x4 o = b3;
-            o = MFMA32(w3a, h2B[0][t], o);
-            o = MFMA32(w3b, h2B[1][t], o);
+            o[t] = MFMA32(w3a, h2B[0][t], b3);
+            o[t] = MFMA32(w3b, h2B[1][t], o[t]);
+        }
+        // ---- the one wait of the step: the next step's inputs, behind the last MFMA and in front of the stores
+        __builtin_amdgcn_sched_barrier(0);
+        pin_x(xB_n[0], xB_n[1]);
+        asm volatile("" : "+v"(pos[0].x), "+v"(pos[0].y), "+v"(pos[0].z), "+v"(pos[1].x), "+v"(pos[1].y), "+v"(pos[1].z),
+                          "+v"(o[0]), "+v"(o[1]));
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
             const int64_t m = m0 + 16 * t + c;  // lane holds h[4q + r] of sample m
-            if (a.out_dim == 5) {
+            if (OUT5) {
                 // sigma + four latent channels: the q = 0 lane of a sample collects channel 4 from its q = 1 lane and
                 // writes ONE 16-byte row (16 lanes = 256 contiguous bytes) instead of four scattered dwords -- the
                 // store tail is where this kernel spends its time (tools/mlp_stamps.py)
-                const float r3 = __shfl_down(o[0], 16, 64);
+                const float r3 = __shfl_down(o[t][0], 16, 64);
                 if (q == 0 && m < M) {
-                    sigmas[m] = expf(o[0] + blob_of(a, m));
-                    reinterpret_cast<float4 *>(rgbs)[m] = make_float4(o[1], o[2], o[3], r3);
+                    sigmas[m] = expf(o[t][0] + blob[t]);
+                    reinterpret_cast<float4 *>(rgbs)[m] = make_float4(o[t][1], o[t][2], o[t][3], r3);
                 }
             } else if (m < M) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int n = 4 * q + r;
-                    if (n == 0) sigmas[m] = expf(o[r] + blob_of(a, m));
-                    else if (n < a.out_dim) rgbs[m * nrgb + (n - 1)] = o[r];
+                    if (n == 0) sigmas[m] = expf(o[t][r] + blob[t]);
+                    else if (n < a.out_dim) rgbs[m * nrgb + (n - 1)] = o[t][r];
                 }
             }
         }
@@ -375,50 +437,55 @@ k_mlp_forward_bf16(MlpArgs a, float *__restrict__ sigmas, float *__restrict__ rg
     st.flush(0);
 }
 
-// upstream gradient of one lane (outputs 4q .. 4q+3 of its T samples), requested one step ahead of its use: raw
-// loads only -- d(sigma)/d(pre-activation) = sigma is applied when the values are consumed, so nothing waits here
+// Upstream gradient of one lane (outputs 4q .. 4q+3 of its T samples), requested one step ahead of its use.
+// OUT5 (sigma + four latent channels, the form that is trained): RAW registers only -- every lane loads its sample's
+// dsigma, sigma and the 16-byte row of latent gradients from a row clamped into the valid samples (the four q groups
+// of a sample read the same addresses: one access), with no lane predicate around any word and no select behind a
+// load: a select consumes the value where it stands, i.e. the wave waits for the load it has just issued, and a word
+// used under a predicate only (g.w, for q = 1) is split off its row and loaded inside the predicated block.  The
+// q = 0 / q = 1 shares and d(sigma)/d(pre-activation) = sigma are applied by upstream_fragment, a step later.
+// Other widths: the generic arm, predicated dword loads consumed where they are loaded.
+template <int T, bool OUT5>
+struct Upstream;
 template <int T>
-struct Upstream { float v[T][4], sg[T]; };
+struct Upstream<T, true> { f32x4 g[T]; float ds[T], sg[T]; };
+template <int T>
+struct Upstream<T, false> { float v[T][4], sg[T]; };
 
 template <int T>
-__device__ __forceinline__ Upstream<T> load_upstream(const MlpArgs &a, const float *__restrict__ sigmas,
-                                                     const float *__restrict__ dsigmas, const float *__restrict__ drgbs,
-                                                     int64_t m0, int64_t M, int q, int c) {
+__device__ __forceinline__ void load_upstream(Upstream<T, true> &u, const MlpArgs &a, const float *__restrict__ sigmas,
+                                              const float *__restrict__ dsigmas, const float *__restrict__ drgbs,
+                                              int64_t m0, int64_t M, int q, int c) {
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        const int64_t mc = clamp_row(m0 + 16 * t + c, M);
+        u.ds[t] = dsigmas[mc];
+        u.sg[t] = sigmas[mc];
+        u.g[t] = reinterpret_cast<const f32x4 *>(drgbs)[mc];
+    }
+}
+template <int T>
+__device__ __forceinline__ void load_upstream(Upstream<T, false> &u, const MlpArgs &a, const float *__restrict__ sigmas,
+                                              const float *__restrict__ dsigmas, const float *__restrict__ drgbs,
+                                              int64_t m0, int64_t M, int q, int c) {
     const int nrgb = a.out_dim - 1;
-    Upstream<T> u;
 #pragma unroll
     for (int t = 0; t < T; ++t) {
         const int64_t m = m0 + 16 * t + c;
         const bool in = m < M;
-        const int64_t mc = clamp_row(m, M);
-        if (a.out_dim == 5) {
-            // sigma + four latent channels: every lane reads its sample's dsigma, sigma and the 16-byte row of latent
-            // gradients (the four q groups of a sample read the same addresses: one access), then keeps its share --
-            // no exec-masked branches around the loads, three loads per tile
-            const float ds = dsigmas[mc], sg = sigmas[mc];
-            const float4 g = reinterpret_cast<const float4 *>(drgbs)[mc];
-            const bool q0 = in && q == 0, q1 = in && q == 1;
-            u.sg[t] = sg;
-            u.v[t][0] = q0 ? ds : (q1 ? g.w : 0.f);
-            u.v[t][1] = q0 ? g.x : 0.f;
-            u.v[t][2] = q0 ? g.y : 0.f;
-            u.v[t][3] = q0 ? g.z : 0.f;
-        } else {
-            u.sg[t] = 1.0f;
+        u.sg[t] = 1.0f;
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj) u.v[t][jj] = 0.f;
-            if (in && q == 0) { u.v[t][0] = dsigmas[m]; u.sg[t] = sigmas[m]; }
+        for (int jj = 0; jj < 4; ++jj) u.v[t][jj] = 0.f;
+        if (in && q == 0) { u.v[t][0] = dsigmas[m]; u.sg[t] = sigmas[m]; }
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {
-                const int n = 4 * q + jj;
-                if (in && n >= 1 && n < a.out_dim) u.v[t][jj] = drgbs[m * nrgb + (n - 1)];
-            }
+        for (int jj = 0; jj < 4; ++jj) {
+            const int n = 4 * q + jj;
+            if (in && n >= 1 && n < a.out_dim) u.v[t][jj] = drgbs[m * nrgb + (n - 1)];
         }
     }
-    return u;
 }
-// the B fragment of dZ3^T (slot (q, jj < 4) <-> output 4q + jj) of one column tile; returns whether any value is non-zero
-__device__ __forceinline__ bool upstream_fragment(const float v[4], float sg, int q, bf16x8 &d3) {
+// the B fragment of dZ3^T (slot (q, jj < 4) <-> output 4q + jj) of one column tile
+__device__ __forceinline__ void upstream_fragment(const float v[4], float sg, int q, bf16x8 &d3) {
     const float e15 = 3269017.3724721107f;  // exp(15)
     const float v0 = q == 0 ? v[0] * fminf(sg, e15) : v[0];
     Pk8 d;
@@ -427,7 +494,35 @@ __device__ __forceinline__ bool upstream_fragment(const float v[4], float sg, in
     d.u[2] = 0u;
     d.u[3] = 0u;
     d3 = d.v;
-    return (v0 != 0.f) || (v[1] != 0.f) || (v[2] != 0.f) || (v[3] != 0.f);
+}
+// (`in`: the lane's sample m0 + 16 t + c of the step that CONSUMES the values is a valid one)
+template <int T>
+__device__ __forceinline__ void upstream_fragment(const Upstream<T, true> &u, int t, bool in, int q, bf16x8 &d3) {
+    const bool q0 = in && q == 0, q1 = in && q == 1;
+    const float v[4] = {q0 ? u.ds[t] : (q1 ? u.g[t][3] : 0.f), q0 ? u.g[t][0] : 0.f, q0 ? u.g[t][1] : 0.f,
+                        q0 ? u.g[t][2] : 0.f};
+    upstream_fragment(v, u.sg[t], q, d3);
+}
+template <int T>
+__device__ __forceinline__ void upstream_fragment(const Upstream<T, false> &u, int t, bool, int q, bf16x8 &d3) {
+    upstream_fragment(u.v[t], u.sg[t], q, d3);
+}
+// the one wait of a backward step (pin_x above): the next step's features and upstream gradient, and the dX tiles that
+// the stores behind it write
+__device__ __forceinline__ void pin_step(bf16x8 x[2], Upstream<2, true> &u, f32x4 ax[2][2]) {
+    u32x4 x0 = __builtin_bit_cast(u32x4, x[0]), x1 = __builtin_bit_cast(u32x4, x[1]);
+    asm volatile("" : "+v"(x0), "+v"(x1), "+v"(u.g[0]), "+v"(u.g[1]), "+v"(u.ds[0]), "+v"(u.ds[1]), "+v"(u.sg[0]),
+                      "+v"(u.sg[1]), "+v"(ax[0][0]), "+v"(ax[0][1]), "+v"(ax[1][0]), "+v"(ax[1][1]));
+    x[0] = __builtin_bit_cast(bf16x8, x0);
+    x[1] = __builtin_bit_cast(bf16x8, x1);
+}
+__device__ __forceinline__ void pin_step(bf16x8 x[2], Upstream<2, false> &u, f32x4 ax[2][2]) {
+    u32x4 x0 = __builtin_bit_cast(u32x4, x[0]), x1 = __builtin_bit_cast(u32x4, x[1]);
+    asm volatile("" : "+v"(x0), "+v"(x1), "+v"(u.v[0][0]), "+v"(u.v[0][1]), "+v"(u.v[0][2]), "+v"(u.v[0][3]),
+                      "+v"(u.v[1][0]), "+v"(u.v[1][1]), "+v"(u.v[1][2]), "+v"(u.v[1][3]), "+v"(u.sg[0]), "+v"(u.sg[1]),
+                      "+v"(ax[0][0]), "+v"(ax[0][1]), "+v"(ax[1][0]), "+v"(ax[1][1]));
+    x[0] = __builtin_bit_cast(bf16x8, x0);
+    x[1] = __builtin_bit_cast(bf16x8, x1);
 }
 
 // ------------------------------------------------------------------ backward
@@ -468,7 +563,8 @@ __device__ __forceinline__ bf16x8 ld_tr(const __bf16 *img, int k, int f0, int la
 // Ownership of the weight gradients (r = w & 3, h = w >> 2, NH = NW / 4): rows 16r..16r+15 of dW2 / dW1, their column
 // tiles split over h; db2 with h = 0, db1 with h = NH - 1; dW3 columns 16r.. with h = 0; db3 with the first wave of
 // the last h.  No cross-wave reduction.
-template <int NW, int T>
+// FB16 / OUT5: a.feat_bf16 and a.out_dim == 5 at compile time, as in the forward.
+template <int NW, int T, bool FB16, bool OUT5>
 __global__ void __launch_bounds__(NW * 64, (NW == 4 ? 2 : 4))
 k_mlp_backward_bf16(MlpArgs a, const float *__restrict__ sigmas, const float *__restrict__ dsigmas,
                     const float *__restrict__ drgbs, float *__restrict__ dfeat, float *__restrict__ slabs) {
@@ -498,33 +594,39 @@ k_mlp_backward_bf16(MlpArgs a, const float *__restrict__ sigmas, const float *__
     const bool own_b2 = h == 0, own_b1 = h == NH - 1, own_w3 = h == 0, own_b3 = w == NW - 4;
 
     // this wave's inputs of the first step; every later step's are requested one step ahead
+    static_assert(T == 2, "pin_step");
     const int64_t wofs = (int64_t)w * 16 * T;
-    Upstream<T> up = load_upstream<T>(a, sigmas, dsigmas, drgbs, (int64_t)blockIdx.x * STEP + wofs, M, q, c);
+    Upstream<T, OUT5> up;
+    load_upstream<T>(up, a, sigmas, dsigmas, drgbs, (int64_t)blockIdx.x * STEP + wofs, M, q, c);
     bf16x8 xB[T];
 #pragma unroll
     for (int t = 0; t < T; ++t) {
         const int64_t m = (int64_t)blockIdx.x * STEP + wofs + 16 * t + c;
-        xB[t] = load_x(a, clamp_row(m, M), q);
+        xB[t] = load_x<FB16>(a, clamp_row(m, M), q);
+    }
+    {   // (waited for HERE: a load still pending at the loop's entry makes the compiler wait at the top of every step)
+        f32x4 none[2][T] = {{zero4, zero4}, {zero4, zero4}};
+        pin_step(xB, up, none);
     }
     Stamps st;
     st.init();
     for (int64_t tile = blockIdx.x; tile * STEP < M; tile += gridDim.x) {
         const int64_t m0 = tile * STEP + wofs, m1 = m0 + (int64_t)gridDim.x * STEP;
-        const Upstream<T> up_c = up;
+        const Upstream<T, OUT5> up_c = up;
         bf16x8 xC[T], h1B[2][T], h2B[2][T], dzB[2][T], d3B[T];
 #pragma unroll
         for (int t = 0; t < T; ++t) xC[t] = xB[t];
-        up = load_upstream<T>(a, sigmas, dsigmas, drgbs, m1, M, q, c);
+        // the next step's upstream gradient and features: requested now, in flight across the whole step, pinned behind
+        // its last MFMA
+        load_upstream<T>(up, a, sigmas, dsigmas, drgbs, m1, M, q, c);
 #pragma unroll
-        for (int t = 0; t < T; ++t) xB[t] = load_x(a, clamp_row(m1 + 16 * t + c, M), q);
-        bool live = false;
+        for (int t = 0; t < T; ++t) xB[t] = load_x<FB16>(a, clamp_row(m1 + 16 * t + c, M), q);
 #pragma unroll
-        for (int t = 0; t < T; ++t) live = upstream_fragment(up_c.v[t], up_c.sg[t], q, d3B[t]) || live;
+        for (int t = 0; t < T; ++t) upstream_fragment<T>(up_c, t, m0 + 16 * t + c < M, q, d3B[t]);
         // (A step whose upstream gradient is exactly zero -- rays past their termination point, 8 % of the bench's
         // samples -- used to be skipped behind a __syncthreads_or.  The skip made every accumulator live across a branch:
         // ~130 register copies per step at the merge, more than the skipped arithmetic was worth; a dead step now flows
         // through and produces its zeros: dfeat = +0, nothing added to any weight gradient.)
-        (void)live;
         st.mark(4);   // __syncthreads_or
         forward_hidden<T>(frag, sB1, sB2, lane, xC, h1B, h2B, st);   // marks 1, 2
         // ================= stage 1: dW3 += dZ3^T (x) H2^T
@@ -624,17 +726,23 @@ k_mlp_backward_bf16(MlpArgs a, const float *__restrict__ sigmas, const float *__
         }
         st.mark(13);  // dW1
         // ---- dX = W1^T dZ1 -> dfeat (level-major f32): lane holds features 16mt + 4q + r of its sample
+        f32x4 ax[2][T];
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
-            f32x4 ax[T];
 #pragma unroll
-            for (int t = 0; t < T; ++t) ax[t] = zero4;
+            for (int t = 0; t < T; ++t) ax[mt][t] = zero4;
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 const bf16x8 wf = ld_frag(frag, F_W1T + 2 * mt + s, lane);
 #pragma unroll
-                for (int t = 0; t < T; ++t) ax[t] = MFMA32(wf, dzB[s][t], ax[t]);
+                for (int t = 0; t < T; ++t) ax[mt][t] = MFMA32(wf, dzB[s][t], ax[mt][t]);
             }
+        }
+        // ---- the one wait of the step: behind its last MFMA, in front of the dfeat stores
+        __builtin_amdgcn_sched_barrier(0);
+        pin_step(xB, up, ax);
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
 #pragma unroll
             for (int t = 0; t < T; ++t) {
                 const int64_t m = m0 + 16 * t + c;
@@ -642,8 +750,8 @@ k_mlp_backward_bf16(MlpArgs a, const float *__restrict__ sigmas, const float *__
                     const int lv = 8 * mt + 2 * q;  // features 16mt+4q+{0,1} = level lv, {2,3} = level lv+1
                     char *df = reinterpret_cast<char *>(dfeat);
                     const uint32_t ls = (uint32_t)a.level_stride, o0 = (((uint32_t)lv) * ls + (uint32_t)m) << 3;
-                    *reinterpret_cast<float2 *>(df + (size_t)o0) = make_float2(ax[t][0], ax[t][1]);
-                    *reinterpret_cast<float2 *>(df + (size_t)(o0 + (ls << 3))) = make_float2(ax[t][2], ax[t][3]);
+                    *reinterpret_cast<float2 *>(df + (size_t)o0) = make_float2(ax[mt][t][0], ax[mt][t][1]);
+                    *reinterpret_cast<float2 *>(df + (size_t)(o0 + (ls << 3))) = make_float2(ax[mt][t][2], ax[mt][t][3]);
                 }
             }
         }
@@ -702,17 +810,38 @@ int launch_mlp_fragments_bf16(const MlpArgs &a, void *frag_out, bool backward_to
     return LNERF_OK;
 }
 
+template <int WPS>
+static void launch_forward_wps(const MlpArgs &a, float *sigmas, float *rgbs, int blocks, hipStream_t stream) {
+    const dim3 g((unsigned)blocks), b(256);
+    if (a.feat_bf16) {
+        if (a.out_dim == 5) hipLaunchKernelGGL((k_mlp_forward_bf16<WPS, true, true>), g, b, 0, stream, a, sigmas, rgbs);
+        else hipLaunchKernelGGL((k_mlp_forward_bf16<WPS, true, false>), g, b, 0, stream, a, sigmas, rgbs);
+    } else {
+        if (a.out_dim == 5) hipLaunchKernelGGL((k_mlp_forward_bf16<WPS, false, true>), g, b, 0, stream, a, sigmas, rgbs);
+        else hipLaunchKernelGGL((k_mlp_forward_bf16<WPS, false, false>), g, b, 0, stream, a, sigmas, rgbs);
+    }
+}
 int launch_mlp_forward_bf16(const MlpArgs &a, float *sigmas, float *rgbs, int blocks, int wps, hipStream_t stream) {
-    if (wps >= 3) hipLaunchKernelGGL(k_mlp_forward_bf16<3>, dim3((unsigned)blocks), dim3(256), 0, stream, a, sigmas, rgbs);
-    else hipLaunchKernelGGL(k_mlp_forward_bf16<2>, dim3((unsigned)blocks), dim3(256), 0, stream, a, sigmas, rgbs);
+    if (wps >= 3) launch_forward_wps<3>(a, sigmas, rgbs, blocks, stream);
+    else launch_forward_wps<2>(a, sigmas, rgbs, blocks, stream);
     LNERF_CHECK_LAUNCH("mlp_forward(bf16)");
     return LNERF_OK;
 }
 
 int launch_mlp_backward_bf16(const MlpArgs &a, const float *sigmas, const float *dsigmas, const float *drgbs,
                              float *dfeat, float *slabs, int blocks, hipStream_t stream) {
-    hipLaunchKernelGGL((k_mlp_backward_bf16<4, 2>), dim3((unsigned)blocks), dim3(256), 0, stream, a, sigmas, dsigmas,
-                       drgbs, dfeat, slabs);
+    const dim3 g((unsigned)blocks), b(256);
+    if (a.feat_bf16) {
+        if (a.out_dim == 5)
+            hipLaunchKernelGGL((k_mlp_backward_bf16<4, 2, true, true>), g, b, 0, stream, a, sigmas, dsigmas, drgbs, dfeat, slabs);
+        else
+            hipLaunchKernelGGL((k_mlp_backward_bf16<4, 2, true, false>), g, b, 0, stream, a, sigmas, dsigmas, drgbs, dfeat, slabs);
+    } else {
+        if (a.out_dim == 5)
+            hipLaunchKernelGGL((k_mlp_backward_bf16<4, 2, false, true>), g, b, 0, stream, a, sigmas, dsigmas, drgbs, dfeat, slabs);
+        else
+            hipLaunchKernelGGL((k_mlp_backward_bf16<4, 2, false, false>), g, b, 0, stream, a, sigmas, dsigmas, drgbs, dfeat, slabs);
+    }
     LNERF_CHECK_LAUNCH("mlp_backward(bf16)");
     return LNERF_OK;
 }

@@ -28,11 +28,16 @@ struct MlpArgs {
 };
 constexpr size_t MLP_FRAG_BYTES = LNERF_MLP_FRAGMENT_BYTES;  // room for the 33 one-KiB fragments of the bf16 path at the head of a workspace
 
-__device__ __forceinline__ float blob_of(const MlpArgs &a, int64_t m) {
-    const float x = a.xyzs[m * 3], y = a.xyzs[m * 3 + 1], z = a.xyzs[m * 3 + 2];
-    const float d2 = (x * x + y * y) + z * z;
+// (split into the load and the arithmetic: the bf16 forward requests a position one step before it evaluates the blob)
+struct Pos3 { float x, y, z; };
+__device__ __forceinline__ Pos3 load_pos(const MlpArgs &a, int64_t m) {
+    return Pos3{a.xyzs[m * 3], a.xyzs[m * 3 + 1], a.xyzs[m * 3 + 2]};
+}
+__device__ __forceinline__ float blob_at(const MlpArgs &a, const Pos3 &p) {
+    const float d2 = (p.x * p.x + p.y * p.y) + p.z * p.z;
     return a.blob_scale * expf(-d2 / a.blob_denom);
 }
+__device__ __forceinline__ float blob_of(const MlpArgs &a, int64_t m) { return blob_at(a, load_pos(a, m)); }
 
 // bf16 path launchers (mlp_bf16.hip)
 int launch_mlp_fragments_bf16(const MlpArgs &a, void *frag_out, bool backward_too, hipStream_t stream);

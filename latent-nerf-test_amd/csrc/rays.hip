@@ -174,26 +174,57 @@ __device__ __forceinline__ float march_noise(const MarchNoise &nz, int64_t n) {
     return march_hash_uniform((uint32_t)n, nz.seed, (uint32_t)(*nz.counter - nz.bias));
 }
 
-// Totals of a training march from the per-ray counts, by ONE wavefront (every lane must call it): what k_march_scan
-// writes to `counter`, by the same rule -- a ray is dropped when the samples of all rays before it (dropped or not) plus
-// its own exceed the capacity.  64 rays per round: inclusive wave scan + running carry.  Advances the jitter counter.
-constexpr int64_t MARCH_FUSED_MAX_RAYS = 8192;   // above: the per-wavefront prefix (N^2 / 2 loads) loses to the scan kernel
-// counter[3]: running maximum, over the marches since the caller last zeroed it, of  M | (rays dropped ? 2^30 : 0)  --
-// what a training loop that sizes its sample buffers from observed marches reads back once in a while
-// (NeRFRenderer.update_sample_budget), kept by the ONE thread that writes the totals: no launch, no atomics
-__device__ __forceinline__ void march_note_peak(int32_t *__restrict__ counter, int32_t m, int dropped) {
-    const int32_t word = m | (dropped > 0 ? (1 << 30) : 0);
-    const int32_t old = counter[3];
-    counter[3] = word > old ? word : old;
+// ---- the training march in its parts.  k_march_train reads top to bottom: load the ray (march_ray), find its span
+// (march_span), walk it (MarchWalk::chunk per 64 lattice points), record it; the capacity rule is march_dropped, the
+// totals have one writer (march_write_totals).
+struct MarchRays {   // where the rays come from (by value)
+    const float *o, *d;          // [N,3]; with gen.on the count pass writes them (gen.ro / gen.rd are these buffers)
+    const float *nears, *fars;   // [N] from lnerf_near_far_from_aabb -- or null: clip against `box` here
+    RayBox box;
+    RayGen gen;
+};
+struct MarchOut {   // where the march goes (by value)
+    float *xyzs, *dirs, *deltas;   // [capacity, 3 / 3 / 2]
+    int32_t *rays;                 // [N,3] = (ray, offset, count)
+    int32_t *cnt;                  // scan-free form: [N] counts + [ceil(N / 4)] workgroup sums; null: k_march_scan runs
+    int64_t capacity;
+    int32_t *counter;              // [4] = M, live rays, dropped rays, running peak
+    int32_t *noise_counter;        // the jitter generator's device counter or null
+};
+
+// The capacity rule: a ray is dropped when the samples of all rays before it (dropped or not) plus its own exceed the
+// capacity.
+__device__ __forceinline__ bool march_dropped(int count, long long samples_before, int64_t capacity) {
+    return count > 0 && samples_before + count > capacity;
 }
-__device__ __forceinline__ void march_totals(const int32_t *__restrict__ cnt, int64_t N, int64_t capacity,
-                                             int32_t *__restrict__ counter, int32_t *__restrict__ noise_counter) {
+// The totals of a march, by the ONE thread that has them: all samples, the largest end of a kept span, kept non-empty
+// rays, dropped rays.  Word 3 is the running maximum, over the marches since the caller last zeroed it, of
+// M | (rays dropped ? 2^30 : 0)  -- what a training loop that sizes its sample buffers from observed marches reads back
+// once in a while (NeRFRenderer.update_sample_budget): no launch, no atomics.  Advances the jitter counter: the count
+// pass has drawn this call's jitter (the scan-free write pass takes it from rays[][1]; behind k_march_scan the write
+// pass undoes the step: bias 1).
+__device__ __forceinline__ void march_write_totals(const MarchOut &out, long long total, long long best, int live,
+                                                   int drop) {
+    // M: all samples when nothing was dropped, else the end of the last kept span
+    const int32_t m = drop > 0 ? (int32_t)best : (int32_t)(total > out.capacity ? out.capacity : total);
+    out.counter[0] = m;
+    out.counter[1] = live;
+    out.counter[2] = drop;
+    const int32_t word = m | (drop > 0 ? (1 << 30) : 0);
+    const int32_t old = out.counter[3];
+    out.counter[3] = word > old ? word : old;
+    if (out.noise_counter) *out.noise_counter += 1;
+}
+// Totals of a training march from the per-ray counts, by ONE wavefront (every lane must call it): what k_march_scan
+// writes to `counter`.  64 rays per round: inclusive wave scan + running carry.
+constexpr int64_t MARCH_FUSED_MAX_RAYS = 8192;   // above: the per-wavefront prefix (N^2 / 2 loads) loses to the scan kernel
+__device__ __forceinline__ void march_totals(const MarchOut &out, int64_t N) {
     const int lane = lane_id();
     long long carry = 0, best = 0;
     int live = 0, drop = 0;
     for (int64_t base = 0; base < N; base += 64) {
         const int64_t i = base + lane;
-        const int c = i < N ? cnt[i] : 0;   // (one round trip per 64 rays: this is the rare overflow path)
+        const int c = i < N ? out.cnt[i] : 0;   // (one round trip per 64 rays: this is the rare overflow path)
         long long inc = c;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -201,7 +232,7 @@ __device__ __forceinline__ void march_totals(const int32_t *__restrict__ cnt, in
             if (lane >= o) inc += u;
         }
         const long long off = carry + inc - c;
-        const bool dropped = (c > 0) && (off + c > capacity);
+        const bool dropped = march_dropped(c, off, out.capacity);
         if (c > 0 && !dropped) { ++live; best = off + c > best ? off + c : best; }
         drop += dropped ? 1 : 0;
         carry += __shfl(inc, 63, 64);
@@ -213,40 +244,16 @@ __device__ __forceinline__ void march_totals(const int32_t *__restrict__ cnt, in
         const long long u = __shfl_xor(best, o, 64);
         best = u > best ? u : best;
     }
-    if (lane == 0) {
-        // M: all samples when nothing was dropped, else the end of the last kept span
-        counter[0] = drop > 0 ? (int32_t)best : (int32_t)(carry > capacity ? capacity : carry);
-        counter[1] = live;
-        counter[2] = drop;
-        march_note_peak(counter, counter[0], drop);
-        if (noise_counter) *noise_counter += 1;   // (this pass took its jitter from rays[][1], not from the counter)
-    }
+    if (lane == 0) march_write_totals(out, carry, best, live, drop);
 }
 
-// chunks of 64 lattice points whose occupancy bytes one round of the uniform-step march requests together
-constexpr int MARCH_CHUNKS = 4;
-// One wavefront per ray.  Each iteration tests 64 consecutive lattice points of the ray;
-// ballot + popcount gives the count (pass 1) or, with mbcnt, each sample's slot (pass 2).
-template <bool WRITE, bool UNIFORM_DT>
-__global__ void __launch_bounds__(256)
-k_march_train(const float *__restrict__ rays_o, const float *__restrict__ rays_d, const float *__restrict__ nears,
-              const float *__restrict__ fars, RayBox box, int clip, RayGen gen, int64_t N, const uint8_t *__restrict__ bitfield, MarchParams P,
-              MarchNoise noises, float *__restrict__ xyzs, float *__restrict__ dirs,
-              float *__restrict__ deltas, int32_t *__restrict__ rays, int32_t *__restrict__ cnt, int64_t capacity,
-              int32_t *__restrict__ counter, int32_t *__restrict__ noise_counter) {
-    const int64_t n = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;  // wave-uniform
-    __shared__ int s_count[4];
-    if (n >= N) {
-        if (!WRITE && cnt) {   // (the workgroup's other wavefronts wait for this one at the barrier below)
-            if ((threadIdx.x & 63) == 0) s_count[threadIdx.x >> 6] = 0;
-            __syncthreads();
-        }
-        return;
-    }
-    const int lane = lane_id();
-    // the ray: generated here by the count pass of the `_pose` form (k_get_rays' arithmetic; written out for the write
-    // pass and the caller), else read
-    float ro[3], rd[3];
+// The ray of wavefront n and its [near, far).  The ray: generated here by the count pass of the `_pose` / `_camera`
+// forms (k_get_rays' arithmetic; written out for the write pass and the caller), else read.  The span: the AABB clip of
+// lnerf_near_far_from_aabb, here (one dispatch less per view, same arithmetic), or that call's table.
+template <bool WRITE>
+__device__ __forceinline__ void march_ray(const MarchRays &R, int64_t n, int lane, float ro[3], float rd[3], float &near,
+                                          float &far) {
+    const RayGen &gen = R.gen;
     if (!WRITE && gen.on) {
         float fx = gen.fx, fy = gen.fy, cx = gen.cx, cy = gen.cy;
         if (gen.intr) {   // (wave-uniform: one ray per wavefront)
@@ -260,176 +267,185 @@ k_march_train(const float *__restrict__ rays_o, const float *__restrict__ rays_d
         }
     } else {
 #pragma unroll
-        for (int r = 0; r < 3; ++r) { ro[r] = rays_o[n * 3 + r]; rd[r] = rays_d[n * 3 + r]; }
+        for (int r = 0; r < 3; ++r) { ro[r] = R.o[n * 3 + r]; rd[r] = R.d[n * 3 + r]; }
     }
-    float near, far;
-    if (clip) {   // the AABB clip of lnerf_near_far_from_aabb, here: one dispatch less per view (same arithmetic)
-        ray_box(ro[0], ro[1], ro[2], rd[0], rd[1], rd[2], box, near, far);
+    if (!R.nears) {
+        ray_box(ro[0], ro[1], ro[2], rd[0], rd[1], rd[2], R.box, near, far);
     } else {
-        near = nears[n]; far = fars[n];
+        near = R.nears[n]; far = R.fars[n];
     }
+}
+
+// Where a ray's samples go, how many it may write, and its jitter.
+struct MarchSpan {
+    int64_t offset;
+    int budget;   // 0 if the ray was dropped for capacity
+    float jitter;
+};
+// The span of ray n in the write pass of the scan-free form (N <= MARCH_FUSED_MAX_RAYS): the count pass left every
+// ray's count in `cnt`, every workgroup's (4 rays') sum and number of non-empty rays in cnt[N + workgroup], and the
+// ray's jitter in rays[n][1]; this wavefront sums what lies before its ray -- what the single-workgroup scan kernel
+// between the two passes did, without that dispatch (7 us of launch latency for 2 us of work).  One batch of loads for
+// 4096 rays.  `cnt` is never modified here, so every wavefront sees the original counts whatever the others have already
+// written.  The jitter is taken out of rays[n][1] and the offset put there; the last ray's wavefront writes the totals.
+__device__ __forceinline__ MarchSpan march_span(const MarchOut &out, int64_t n, int64_t N, int lane) {
+    const int32_t *wg = out.cnt + N;
+    const int64_t w = n >> 2;
+    long long part = 0;
+    int nonempty = 0;
+    for (int64_t j0 = 0; j0 < w; j0 += 1024) {   // sixteen loads in flight per lane
+        int v[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const int64_t j = j0 + k * 64 + lane;
+            v[k] = j < w ? wg[j] : 0;
+        }
+#pragma unroll
+        for (int k = 0; k < 16; ++k) { part += v[k] & 0xFFFFFF; nonempty += v[k] >> 28; }
+    }
+    {   // the rays of this ray's own workgroup that come before it
+        const int64_t i = 4 * w + lane;
+        const int c = (lane < 4 && i < n) ? out.cnt[i] : 0;
+        part += c;
+        nonempty += c > 0 ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        part += __shfl_xor(part, o, 64);
+        nonempty += __shfl_xor(nonempty, o, 64);
+    }
+    const int c = out.cnt[n];
+    const bool dropped = march_dropped(c, part, out.capacity);
+    const MarchSpan span{dropped ? 0 : part, dropped ? 0 : c, __int_as_float(out.rays[n * 3 + 1])};
+    if (lane == 0) {
+        out.rays[n * 3 + 1] = (int32_t)span.offset;
+        if (dropped) out.rays[n * 3 + 2] = 0;
+    }
+    if (n == N - 1) {   // the last ray's wavefront has the totals at hand
+        if (part + c <= out.capacity) {
+            if (lane == 0) march_write_totals(out, part + c, 0, nonempty + (c > 0 ? 1 : 0), 0);
+        } else {
+            march_totals(out, N);   // rays were dropped: the scan's bookkeeping
+        }
+    }
+    return span;
+}
+
+// chunks of 64 lattice points whose occupancy bytes one round of the uniform-step march requests together
+constexpr int MARCH_CHUNKS = 4;
+// The chunk rule, once.  A wavefront has tested 64 consecutive lattice points of its ray: ballot + popcount gives the
+// count (pass 1) or, with mbcnt, each sample's slot (pass 2), until the ray's budget is used up.
+template <bool WRITE>
+struct MarchWalk {
+    int count, budget;
+    int64_t offset;
+    float dx, dy, dz;
+    // valid: this lane's point lies before `far`; occupied: the cell of (x, y, z), the clamped point, is.  True: the
+    // ray is finished.
+    __device__ __forceinline__ bool chunk(const MarchOut &out, bool valid, bool occupied, float x, float y, float z,
+                                          float dt, float t) {
+        if (__ballot(valid) == 0ull) return true;  // lattice is monotone: nothing further is valid
+        const bool occ = valid && occupied;
+        const unsigned long long mask = __ballot(occ);
+        const int rank = count + mbcnt(mask);
+        if (WRITE && occ && rank < budget) {
+            const int64_t s = offset + rank;
+            // one 12-byte store per position / direction, one 8-byte store per (dt, t) pair
+            *reinterpret_cast<float3 *>(out.xyzs + s * 3) = make_float3(x, y, z);
+            *reinterpret_cast<float3 *>(out.dirs + s * 3) = make_float3(dx, dy, dz);
+            *reinterpret_cast<float2 *>(out.deltas + s * 2) = make_float2(dt, t);
+        }
+        count += __popcll(mask);
+        if (count < budget) return false;
+        count = budget;
+        return true;
+    }
+};
+
+// One wavefront per ray, two passes: count (WRITE = false), then write.
+template <bool WRITE, bool UNIFORM_DT>
+__global__ void __launch_bounds__(256)
+k_march_train(MarchRays R, int64_t N, const uint8_t *__restrict__ bitfield, MarchParams P, MarchNoise noises,
+              MarchOut out) {
+    const int64_t n = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;  // wave-uniform
+    const int lane = lane_id();
     int count = 0;
-    int64_t offset = 0;
-    int budget = P.max_steps;
-    float noise_in = 0.f;
-    if (WRITE && cnt) {
-        // Scan-free form (N <= MARCH_FUSED_MAX_RAYS): the count pass left every ray's count in `cnt`, every workgroup's
-        // (4 rays') sum and number of non-empty rays in cnt[N + workgroup], and the ray's jitter in rays[n][1]; this
-        // wavefront sums what lies before its ray -- what the single-workgroup scan kernel between the two passes did,
-        // without that dispatch (7 us of launch latency for 2 us of work).  One batch of loads for 4096 rays.  `cnt` is
-        // never modified here, so every wavefront sees the original counts whatever the others have already written.
-        const int32_t *wg = cnt + N;
-        const int64_t w = n >> 2;
-        long long part = 0;
-        int nonempty = 0;
-        for (int64_t j0 = 0; j0 < w; j0 += 1024) {   // sixteen loads in flight per lane
-            int v[16];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                const int64_t j = j0 + k * 64 + lane;
-                v[k] = j < w ? wg[j] : 0;
-            }
-#pragma unroll
-            for (int k = 0; k < 16; ++k) { part += v[k] & 0xFFFFFF; nonempty += v[k] >> 28; }
-        }
-        {   // the rays of this ray's own workgroup that come before it
-            const int64_t i = 4 * w + lane;
-            const int c = (lane < 4 && i < n) ? cnt[i] : 0;
-            part += c;
-            nonempty += c > 0 ? 1 : 0;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            part += __shfl_xor(part, o, 64);
-            nonempty += __shfl_xor(nonempty, o, 64);
-        }
-        const int c = cnt[n];
-        const bool dropped = (c > 0) && (part + c > capacity);   // (k_march_scan's rule)
-        offset = dropped ? 0 : part;
-        budget = dropped ? 0 : c;
-        noise_in = __int_as_float(rays[n * 3 + 1]);
-        if (lane == 0) {
-            rays[n * 3 + 1] = (int32_t)offset;
-            if (dropped) rays[n * 3 + 2] = 0;
-        }
-        if (n == N - 1) {   // the last ray's wavefront has the totals at hand
-            const long long total = part + c;
-            if (total <= capacity) {
-                if (lane == 0) {
-                    counter[0] = (int32_t)total;
-                    counter[1] = nonempty + (c > 0 ? 1 : 0);
-                    counter[2] = 0;
-                    march_note_peak(counter, (int32_t)total, 0);
-                    if (noise_counter) *noise_counter += 1;   // (this pass took its jitter from rays[][1])
-                }
-            } else {
-                march_totals(cnt, N, capacity, counter, noise_counter);   // rays were dropped: the scan's bookkeeping
-            }
-        }
-    } else if (WRITE) {
-        offset = rays[n * 3 + 1];
-        budget = rays[n * 3 + 2];  // 0 if the ray was dropped for capacity
-    }
-    if (near < far && budget > 0) {
-        const float ox = ro[0], oy = ro[1], oz = ro[2];
-        const float dx = rd[0], dy = rd[1], dz = rd[2];
-        const float dt0 = clampf(near * P.dt_gamma, P.dt_min, P.dt_max);
-        const float noise = (WRITE && cnt) ? noise_in : march_noise(noises, n);
-        if (!WRITE && cnt && lane == 0) rays[n * 3 + 1] = __float_as_int(noise);   // hand the jitter to the write pass
-        const float t0 = near + dt0 * noise;
-        float t = t0;
-        if (!UNIFORM_DT) {  // lane l starts at lattice point l
-            for (int i = 0; i < lane; ++i) t = t + clampf(t * P.dt_gamma, P.dt_min, P.dt_max);
-        }
-        if (UNIFORM_DT) {
-            // Closed-form lattice: MARCH_CHUNKS chunks of 64 lattice points per round, their occupancy bytes requested together
-            // -- the pass is a chain of dependent L2 round trips (one per chunk, ~16 per ray), this makes it ~16 / MARCH_CHUNKS.  Chunks
-            // past the ray's end read a clamped (valid) cell and are ignored; the decisions and their order are those
-            // of the one-chunk loop below.
-            const float dt = P.dt_min;
-            bool done = false;
-            for (int base = 0; base < (1 << 22) && !done; base += 64 * MARCH_CHUNKS) {  // bound: a non-finite `far` must not spin
-                float tj[MARCH_CHUNKS], xj[MARCH_CHUNKS], yj[MARCH_CHUNKS], zj[MARCH_CHUNKS];
-                bool vj[MARCH_CHUNKS], oj[MARCH_CHUNKS];
-#pragma unroll
-                for (int j = 0; j < MARCH_CHUNKS; ++j) {
-                    float tt = (float)(base + 64 * j + lane) * dt;
-                    tt = tt + t0;
-                    tj[j] = tt;
-                    vj[j] = tt < far;
-                    float x = dx * tt, y = dy * tt, z = dz * tt;
-                    x = x + ox; y = y + oy; z = z + oz;
-                    xj[j] = clampf(x, -P.bound, P.bound);
-                    yj[j] = clampf(y, -P.bound, P.bound);
-                    zj[j] = clampf(z, -P.bound, P.bound);
-                }
-#pragma unroll
-                for (int j = 0; j < MARCH_CHUNKS; ++j) oj[j] = cell_occupied(xj[j], yj[j], zj[j], dt, P, bitfield);
-#pragma unroll
-                for (int j = 0; j < MARCH_CHUNKS; ++j) {
-                    if (done) break;
-                    if (__ballot(vj[j]) == 0ull) { done = true; break; }  // lattice is monotone: nothing further is valid
-                    const bool occ = vj[j] && oj[j];
-                    const unsigned long long mask = __ballot(occ);
-                    const int rank = count + mbcnt(mask);
-                    if (WRITE && occ && rank < budget) {
-                        const int64_t s = offset + rank;
-                        // one 12-byte store per position / direction, one 8-byte store per (dt, t) pair
-                        *reinterpret_cast<float3 *>(xyzs + s * 3) = make_float3(xj[j], yj[j], zj[j]);
-                        *reinterpret_cast<float3 *>(dirs + s * 3) = make_float3(dx, dy, dz);
-                        *reinterpret_cast<float2 *>(deltas + s * 2) = make_float2(dt, tj[j]);
-                    }
-                    count += __popcll(mask);
-                    if (count >= budget) { count = budget; done = true; }
-                }
-            }
-        }
-        for (int base = 0; !UNIFORM_DT && base < (1 << 22); base += 64) {  // bound: a non-finite `far` must not spin
-            float dt;
+    if (n < N) {
+        float ro[3], rd[3], near, far;
+        march_ray<WRITE>(R, n, lane, ro, rd, near, far);
+        MarchSpan span{0, P.max_steps, 0.f};
+        if (WRITE && out.cnt) span = march_span(out, n, N, lane);
+        else if (WRITE) span = MarchSpan{out.rays[n * 3 + 1], out.rays[n * 3 + 2], 0.f};   // (k_march_scan's)
+        if (near < far && span.budget > 0) {
+            const float ox = ro[0], oy = ro[1], oz = ro[2];
+            const float dx = rd[0], dy = rd[1], dz = rd[2];
+            const float dt0 = clampf(near * P.dt_gamma, P.dt_min, P.dt_max);
+            const float noise = (WRITE && out.cnt) ? span.jitter : march_noise(noises, n);
+            if (!WRITE && out.cnt && lane == 0) out.rays[n * 3 + 1] = __float_as_int(noise);   // hand the jitter to the write pass
+            const float t0 = near + dt0 * noise;
+            MarchWalk<WRITE> walk{0, span.budget, span.offset, dx, dy, dz};
             if (UNIFORM_DT) {
-                dt = P.dt_min;
-                t = (float)(base + lane) * dt;
-                t = t + t0;
+                // Closed-form lattice: MARCH_CHUNKS chunks of 64 lattice points per round, their occupancy bytes requested together
+                // -- the pass is a chain of dependent L2 round trips (one per chunk, ~16 per ray), this makes it ~16 / MARCH_CHUNKS.  Chunks
+                // past the ray's end read a clamped (valid) cell and are ignored; the decisions and their order are those
+                // of the one-chunk loop below.
+                const float dt = P.dt_min;
+                bool done = false;
+                for (int base = 0; base < (1 << 22) && !done; base += 64 * MARCH_CHUNKS) {  // bound: a non-finite `far` must not spin
+                    float tj[MARCH_CHUNKS], xj[MARCH_CHUNKS], yj[MARCH_CHUNKS], zj[MARCH_CHUNKS];
+                    bool vj[MARCH_CHUNKS], oj[MARCH_CHUNKS];
+#pragma unroll
+                    for (int j = 0; j < MARCH_CHUNKS; ++j) {
+                        float tt = (float)(base + 64 * j + lane) * dt;
+                        tt = tt + t0;
+                        tj[j] = tt;
+                        vj[j] = tt < far;
+                        float x = dx * tt, y = dy * tt, z = dz * tt;
+                        x = x + ox; y = y + oy; z = z + oz;
+                        xj[j] = clampf(x, -P.bound, P.bound);
+                        yj[j] = clampf(y, -P.bound, P.bound);
+                        zj[j] = clampf(z, -P.bound, P.bound);
+                    }
+#pragma unroll
+                    for (int j = 0; j < MARCH_CHUNKS; ++j) oj[j] = cell_occupied(xj[j], yj[j], zj[j], dt, P, bitfield);
+#pragma unroll
+                    for (int j = 0; j < MARCH_CHUNKS && !done; ++j)
+                        done = walk.chunk(out, vj[j], oj[j], xj[j], yj[j], zj[j], dt, tj[j]);
+                }
             } else {
-                dt = clampf(t * P.dt_gamma, P.dt_min, P.dt_max);
+                // The step recurrence t = t + clamp(t * dt_gamma): lane l starts at lattice point l and moves 64 points per chunk
+                float t = t0;
+                for (int i = 0; i < lane; ++i) t = t + clampf(t * P.dt_gamma, P.dt_min, P.dt_max);
+                for (int base = 0; base < (1 << 22); base += 64) {  // bound: a non-finite `far` must not spin
+                    const float dt = clampf(t * P.dt_gamma, P.dt_min, P.dt_max);
+                    const bool valid = t < far;
+                    float x = dx * t, y = dy * t, z = dz * t;
+                    x = x + ox; y = y + oy; z = z + oz;
+                    x = clampf(x, -P.bound, P.bound);
+                    y = clampf(y, -P.bound, P.bound);
+                    z = clampf(z, -P.bound, P.bound);
+                    if (walk.chunk(out, valid, valid && cell_occupied(x, y, z, dt, P, bitfield), x, y, z, dt, t)) break;
+                    for (int i = 0; i < 64; ++i) t = t + clampf(t * P.dt_gamma, P.dt_min, P.dt_max);
+                }
             }
-            const bool valid = t < far;
-            if (__ballot(valid) == 0ull) break;  // lattice is monotone: nothing further is valid
-            float x = dx * t, y = dy * t, z = dz * t;
-            x = x + ox; y = y + oy; z = z + oz;
-            x = clampf(x, -P.bound, P.bound);
-            y = clampf(y, -P.bound, P.bound);
-            z = clampf(z, -P.bound, P.bound);
-            const bool occ = valid && cell_occupied(x, y, z, dt, P, bitfield);
-            const unsigned long long mask = __ballot(occ);
-            const int rank = count + mbcnt(mask);
-            if (WRITE && occ && rank < budget) {
-                const int64_t s = offset + rank;
-                xyzs[s * 3] = x; xyzs[s * 3 + 1] = y; xyzs[s * 3 + 2] = z;
-                dirs[s * 3] = dx; dirs[s * 3 + 1] = dy; dirs[s * 3 + 2] = dz;
-                deltas[s * 2] = dt; deltas[s * 2 + 1] = t;
-            }
-            count += __popcll(mask);
-            if (count >= budget) { count = budget; break; }
-            if (!UNIFORM_DT) {
-                for (int i = 0; i < 64; ++i) t = t + clampf(t * P.dt_gamma, P.dt_min, P.dt_max);
-            }
+            count = walk.count;
+        }
+        if (!WRITE && lane == 0) {
+            out.rays[n * 3] = (int32_t)n;
+            if (!(out.cnt && near < far)) out.rays[n * 3 + 1] = 0;   // (scan-free form: the jitter of a marched ray sits here)
+            out.rays[n * 3 + 2] = count;
+            if (out.cnt) out.cnt[n] = count;
         }
     }
-    if (!WRITE && lane == 0) {
-        rays[n * 3] = (int32_t)n;
-        if (!(cnt && near < far)) rays[n * 3 + 1] = 0;   // (scan-free form: the jitter of a marched ray sits here)
-        rays[n * 3 + 2] = count;
-        if (cnt) cnt[n] = count;
-    }
-    if (!WRITE && cnt) {   // per workgroup: samples in bits [0,24) (4 rays x <= 65536 steps), non-empty rays in [28,31)
+    if (!WRITE && out.cnt) {   // per workgroup: samples in bits [0,24) (4 rays x <= 65536 steps), non-empty rays in [28,31)
+        __shared__ int s_count[4];   // (a wavefront past the last ray counts 0: every wavefront meets the barrier)
         if (lane == 0) s_count[threadIdx.x >> 6] = count;
         __syncthreads();
         if (threadIdx.x == 0) {
             int sum = 0, ne = 0;
 #pragma unroll
             for (int k = 0; k < 4; ++k) { sum += s_count[k]; ne += s_count[k] > 0 ? 1 : 0; }
-            cnt[N + blockIdx.x] = sum | (ne << 28);
+            out.cnt[N + blockIdx.x] = sum | (ne << 28);
         }
     }
 }
@@ -439,14 +455,12 @@ k_march_train(const float *__restrict__ rays_o, const float *__restrict__ rays_d
 // Every thread owns K = ceil(N / 1024) CONSECUTIVE rays: a local sum, ONE block-wide scan of the 1024 sums, then the
 // thread walks its rays again with its base offset -- two barriers for any N (a chunk-of-1024 loop met at three barriers
 // per chunk; the kernel is latency from end to end).
-__global__ void __launch_bounds__(1024) k_march_scan(int32_t *__restrict__ rays, int64_t N, int64_t capacity,
-                                                     int32_t *__restrict__ counter, int32_t *__restrict__ noise_counter) {
+__global__ void __launch_bounds__(1024) k_march_scan(MarchOut out, int64_t N) {
+    int32_t *__restrict__ rays = out.rays;
     __shared__ long long wave_tot[16];
     __shared__ int wave_live[16], wave_drop[16];
     __shared__ long long wave_best[16];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    // the count pass has drawn this call's jitter; advance the generator (the write pass undoes the step: bias 1)
-    if (tid == 0 && noise_counter) *noise_counter += 1;
     const int64_t K = (N + 1023) / 1024;
     const int64_t n0 = (int64_t)tid * K, n1 = (n0 + K < N) ? n0 + K : N;
     long long mine = 0;
@@ -466,7 +480,7 @@ __global__ void __launch_bounds__(1024) k_march_scan(int32_t *__restrict__ rays,
     long long best = 0;
     for (int64_t n = n0; n < n1; ++n) {
         const int c = rays[n * 3 + 2];
-        const bool dropped = (c > 0) && (off + c > capacity);
+        const bool dropped = march_dropped(c, off, out.capacity);
         rays[n * 3 + 1] = (int32_t)(dropped ? 0 : off);
         if (dropped) rays[n * 3 + 2] = 0;
         if (c > 0 && !dropped) { ++live; best = off + c; }   // (empty rays carry a meaningless offset)
@@ -491,11 +505,7 @@ __global__ void __launch_bounds__(1024) k_march_scan(int32_t *__restrict__ rays,
             dr += wave_drop[w];
             bmax = wave_best[w] > bmax ? wave_best[w] : bmax;
         }
-        // M: all samples when nothing was dropped, else the end of the last kept span
-        counter[0] = dr > 0 ? (int32_t)bmax : (int32_t)(total > capacity ? capacity : total);
-        counter[1] = lv;
-        counter[2] = dr;
-        march_note_peak(counter, counter[0], dr);
+        march_write_totals(out, total, bmax, lv, dr);
     }
 }
 
@@ -897,8 +907,8 @@ static int check_march_common(const char *who, float bound, int cascade, int gri
     return LNERF_OK;
 }
 
-static int march_train_impl(const float *rays_o, const float *rays_d, const float *nears, const float *fars,
-                            const RayBox *clip_box, const RayGen *raygen, int64_t N, const uint8_t *bitfield, float bound, int cascade,
+// `clip`: R.box instead of the nears / fars tables (the forms that went through march_source)
+static int march_train_impl(MarchRays R, bool clip, int64_t N, const uint8_t *bitfield, float bound, int cascade,
                             int grid_size, int max_steps, float dt_gamma, const float *noises, uint32_t noise_seed,
                             int32_t *noise_counter, int64_t capacity, float *xyzs, float *dirs, float *deltas,
                             int32_t *rays, int32_t *counter, lnerf_stream_t stream) {
@@ -912,40 +922,27 @@ static int march_train_impl(const float *rays_o, const float *rays_d, const floa
         (void)hipMemsetAsync(counter, 0, 4 * sizeof(int32_t), as_stream(stream));
         return LNERF_OK;
     }
-    LNERF_REQUIRE(rays_o && rays_d && (clip_box || (nears && fars)) && bitfield && rays, "march_rays_train: null pointer");
+    LNERF_REQUIRE(R.o && R.d && (clip || (R.nears && R.fars)) && bitfield && rays, "march_rays_train: null pointer");
     LNERF_REQUIRE(capacity == 0 || (xyzs && dirs && deltas), "march_rays_train: null sample buffers");
     const MarchParams P = make_params(bound, cascade, grid_size, max_steps, dt_gamma);
     const dim3 block(256), grid((unsigned)div_up(N, 4));  // 4 wavefronts (rays) per workgroup
     hipStream_t s = as_stream(stream);
-    RayBox box{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const int clip = clip_box ? 1 : 0;
-    if (clip_box) box = *clip_box;
-    RayGen gen;
-    memset(&gen, 0, sizeof(gen));
-    if (raygen) gen = *raygen;
-    MarchNoise nz;
-    nz.values = noises; nz.counter = noise_counter; nz.seed = noise_seed; nz.bias = 0;
+    MarchNoise nz{noises, noise_counter, noise_seed, 0};
     // up to MARCH_FUSED_MAX_RAYS rays: two dispatches (the write pass sums the counts before its ray itself; the counts
     // live behind the four totals in `counter`, see lnerf_march_counter_len); more: count, scan, write
-    int32_t *cnt = N <= MARCH_FUSED_MAX_RAYS ? counter + 4 : nullptr;
-    if (dt_gamma == 0.f)
-        hipLaunchKernelGGL((k_march_train<false, true>), grid, block, 0, s, rays_o, rays_d, nears, fars, box, clip, gen, N,
-                           bitfield, P, nz, xyzs, dirs, deltas, rays, cnt, capacity, counter, noise_counter);
-    else
-        hipLaunchKernelGGL((k_march_train<false, false>), grid, block, 0, s, rays_o, rays_d, nears, fars, box, clip, gen, N,
-                           bitfield, P, nz, xyzs, dirs, deltas, rays, cnt, capacity, counter, noise_counter);
+    const MarchOut out{xyzs, dirs, deltas, rays, N <= MARCH_FUSED_MAX_RAYS ? counter + 4 : nullptr, capacity, counter,
+                       noise_counter};
+    auto pass = [&](auto uniform_dt, auto recurrence) {
+        hipLaunchKernelGGL(dt_gamma == 0.f ? uniform_dt : recurrence, grid, block, 0, s, R, N, bitfield, P, nz, out);
+    };
+    pass(k_march_train<false, true>, k_march_train<false, false>);
     LNERF_CHECK_LAUNCH("march_rays_train(count)");
-    if (!cnt) {
-        hipLaunchKernelGGL(k_march_scan, dim3(1), dim3(1024), 0, s, rays, N, capacity, counter, noise_counter);
+    if (!out.cnt) {
+        hipLaunchKernelGGL(k_march_scan, dim3(1), dim3(1024), 0, s, out, N);
         LNERF_CHECK_LAUNCH("march_rays_train(scan)");
         nz.bias = 1;
     }
-    if (dt_gamma == 0.f)
-        hipLaunchKernelGGL((k_march_train<true, true>), grid, block, 0, s, rays_o, rays_d, nears, fars, box, clip, gen, N,
-                           bitfield, P, nz, xyzs, dirs, deltas, rays, cnt, capacity, counter, noise_counter);
-    else
-        hipLaunchKernelGGL((k_march_train<true, false>), grid, block, 0, s, rays_o, rays_d, nears, fars, box, clip, gen, N,
-                           bitfield, P, nz, xyzs, dirs, deltas, rays, cnt, capacity, counter, noise_counter);
+    pass(k_march_train<true, true>, k_march_train<true, false>);
     LNERF_CHECK_LAUNCH("march_rays_train(write)");
     return LNERF_OK;
 }
@@ -957,9 +954,27 @@ int lnerf_march_rays_train(const float *rays_o, const float *rays_d, const float
                            float dt_gamma, const float *noises, uint32_t noise_seed, int32_t *noise_counter,
                            int64_t capacity, float *xyzs, float *dirs, float *deltas, int32_t *rays, int32_t *counter,
                            lnerf_stream_t stream) {
-    return march_train_impl(rays_o, rays_d, nears, fars, nullptr, nullptr, N, bitfield, bound, cascade, grid_size, max_steps,
-                            dt_gamma, noises, noise_seed, noise_counter, capacity, xyzs, dirs, deltas, rays, counter,
-                            stream);
+    MarchRays R{};
+    R.o = rays_o; R.d = rays_d; R.nears = nears; R.fars = fars;
+    return march_train_impl(R, false, N, bitfield, bound, cascade, grid_size, max_steps, dt_gamma, noises, noise_seed,
+                            noise_counter, capacity, xyzs, dirs, deltas, rays, counter, stream);
+}
+
+// The ray source of the forms that clip inside the march passes, checked in the name of entry point `who`: the box and
+// -- `cam`, B views -- the camera of the forms whose count pass generates the rays into cam->ro / cam->rd (`bad_camera`:
+// how that form words a bad camera; intr_in_memory: it reads its intrinsics from cam->intr).
+static int march_source(const char *who, MarchRays &R, float xmin, float ymin, float zmin, float xmax, float ymax,
+                        float zmax, float min_near, const RayGen *cam = nullptr, int B = 0,
+                        const char *bad_camera = nullptr, bool intr_in_memory = false) {
+    LNERF_REQUIRE(!cam || (B >= 0 && cam->H >= 1 && cam->W >= 1 && cam->fx != 0.f && cam->fy != 0.f), "%s: %s", who,
+                  bad_camera);
+    LNERF_REQUIRE(xmin <= xmax && ymin <= ymax && zmin <= zmax, "%s: inverted aabb", who);
+    LNERF_REQUIRE(!cam || B == 0 || (cam->c2w && (cam->intr || !intr_in_memory) && cam->ro && cam->rd),
+                  "%s: null pointer", who);
+    R.nears = R.fars = nullptr;
+    R.box = RayBox{xmin, ymin, zmin, xmax, ymax, zmax, min_near};
+    if (cam) { R.gen = *cam; R.o = cam->ro; R.d = cam->rd; }
+    return LNERF_OK;
 }
 
 int lnerf_march_rays_train_aabb(const float *rays_o, const float *rays_d, float xmin, float ymin, float zmin, float xmax,
@@ -967,11 +982,12 @@ int lnerf_march_rays_train_aabb(const float *rays_o, const float *rays_d, float 
                                 int cascade, int grid_size, int max_steps, float dt_gamma, const float *noises,
                                 uint32_t noise_seed, int32_t *noise_counter, int64_t capacity, float *xyzs, float *dirs,
                                 float *deltas, int32_t *rays, int32_t *counter, lnerf_stream_t stream) {
-    LNERF_REQUIRE(xmin <= xmax && ymin <= ymax && zmin <= zmax, "march_rays_train_aabb: inverted aabb");
-    const RayBox box{xmin, ymin, zmin, xmax, ymax, zmax, min_near};
-    return march_train_impl(rays_o, rays_d, nullptr, nullptr, &box, nullptr, N, bitfield, bound, cascade, grid_size, max_steps,
-                            dt_gamma, noises, noise_seed, noise_counter, capacity, xyzs, dirs, deltas, rays, counter,
-                            stream);
+    MarchRays R{};
+    R.o = rays_o; R.d = rays_d;
+    int rc = march_source("march_rays_train_aabb", R, xmin, ymin, zmin, xmax, ymax, zmax, min_near);
+    if (rc) return rc;
+    return march_train_impl(R, true, N, bitfield, bound, cascade, grid_size, max_steps, dt_gamma, noises, noise_seed,
+                            noise_counter, capacity, xyzs, dirs, deltas, rays, counter, stream);
 }
 
 int lnerf_march_rays_train_pose(const float *c2w, int B, int H, int W, float fx, float fy, float cx, float cy,
@@ -980,16 +996,12 @@ int lnerf_march_rays_train_pose(const float *c2w, int B, int H, int W, float fx,
                                 int grid_size, int max_steps, float dt_gamma, const float *noises, uint32_t noise_seed,
                                 int32_t *noise_counter, int64_t capacity, float *xyzs, float *dirs, float *deltas,
                                 int32_t *rays, int32_t *counter, lnerf_stream_t stream) {
-    LNERF_REQUIRE(B >= 0 && H >= 1 && W >= 1 && fx != 0.f && fy != 0.f, "march_rays_train_pose: bad camera");
-    LNERF_REQUIRE(xmin <= xmax && ymin <= ymax && zmin <= zmax, "march_rays_train_pose: inverted aabb");
-    LNERF_REQUIRE(B == 0 || (c2w && rays_o_out && rays_d_out), "march_rays_train_pose: null pointer");
-    const RayBox box{xmin, ymin, zmin, xmax, ymax, zmax, min_near};
-    RayGen gen;
-    gen.c2w = c2w; gen.intr = nullptr; gen.on = 1; gen.H = H; gen.W = W; gen.fx = fx; gen.fy = fy; gen.cx = cx; gen.cy = cy;
-    gen.ro = rays_o_out; gen.rd = rays_d_out;
-    return march_train_impl(rays_o_out, rays_d_out, nullptr, nullptr, &box, &gen, (int64_t)B * H * W, bitfield, bound,
-                            cascade, grid_size, max_steps, dt_gamma, noises, noise_seed, noise_counter, capacity, xyzs,
-                            dirs, deltas, rays, counter, stream);
+    const RayGen cam{c2w, nullptr, 1, H, W, fx, fy, cx, cy, rays_o_out, rays_d_out};
+    MarchRays R{};
+    int rc = march_source("march_rays_train_pose", R, xmin, ymin, zmin, xmax, ymax, zmax, min_near, &cam, B, "bad camera");
+    if (rc) return rc;
+    return march_train_impl(R, true, (int64_t)B * H * W, bitfield, bound, cascade, grid_size, max_steps, dt_gamma, noises,
+                            noise_seed, noise_counter, capacity, xyzs, dirs, deltas, rays, counter, stream);
 }
 
 int lnerf_march_rays_train_camera(const float *c2w, const float *intrinsics, int B, int H, int W, float *rays_o_out,
@@ -998,16 +1010,13 @@ int lnerf_march_rays_train_camera(const float *c2w, const float *intrinsics, int
                                   int grid_size, int max_steps, float dt_gamma, const float *noises, uint32_t noise_seed,
                                   int32_t *noise_counter, int64_t capacity, float *xyzs, float *dirs, float *deltas,
                                   int32_t *rays, int32_t *counter, lnerf_stream_t stream) {
-    LNERF_REQUIRE(B >= 0 && H >= 1 && W >= 1, "march_rays_train_camera: bad image size");
-    LNERF_REQUIRE(xmin <= xmax && ymin <= ymax && zmin <= zmax, "march_rays_train_camera: inverted aabb");
-    LNERF_REQUIRE(B == 0 || (c2w && intrinsics && rays_o_out && rays_d_out), "march_rays_train_camera: null pointer");
-    const RayBox box{xmin, ymin, zmin, xmax, ymax, zmax, min_near};
-    RayGen gen;
-    gen.c2w = c2w; gen.intr = intrinsics; gen.on = 1; gen.H = H; gen.W = W; gen.fx = gen.fy = 1.f; gen.cx = gen.cy = 0.f;
-    gen.ro = rays_o_out; gen.rd = rays_d_out;
-    return march_train_impl(rays_o_out, rays_d_out, nullptr, nullptr, &box, &gen, (int64_t)B * H * W, bitfield, bound,
-                            cascade, grid_size, max_steps, dt_gamma, noises, noise_seed, noise_counter, capacity, xyzs,
-                            dirs, deltas, rays, counter, stream);
+    const RayGen cam{c2w, intrinsics, 1, H, W, 1.f, 1.f, 0.f, 0.f, rays_o_out, rays_d_out};   // (by-value ones: unused)
+    MarchRays R{};
+    int rc = march_source("march_rays_train_camera", R, xmin, ymin, zmin, xmax, ymax, zmax, min_near, &cam, B,
+                          "bad image size", true);
+    if (rc) return rc;
+    return march_train_impl(R, true, (int64_t)B * H * W, bitfield, bound, cascade, grid_size, max_steps, dt_gamma, noises,
+                            noise_seed, noise_counter, capacity, xyzs, dirs, deltas, rays, counter, stream);
 }
 
 int lnerf_march_rays(int64_t n_alive, int n_step, const int32_t *rays_alive, const float *rays_t, const float *rays_o,

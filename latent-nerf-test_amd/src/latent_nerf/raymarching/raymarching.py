@@ -179,6 +179,7 @@ def march_rays_train(rays_o, rays_d, bound, density_bitfield, C, H, nears, fars,
         # (four totals + the scratch the two-launch form of the march keeps its per-ray counts in; ZEROED: word 3 is a
         # running peak the library only ever raises -- MarchResult.take_peak() reads and clears it)
         counter = torch.zeros(int(_b.get_lib().lnerf_march_counter_len(N)), device=dev, dtype=torch.int32)
+    # the four entry points differ in where the rays come from (their leading arguments) and end alike
     if camera is not None:
         if aabb is None or nears is not None:
             raise ValueError("march_rays_train(camera=...) needs aabb= and no nears/fars")
@@ -192,33 +193,23 @@ def march_rays_train(rays_o, rays_d, bound, density_bitfield, C, H, nears, fars,
             intr = intr.view(-1, 4)
             if intr.shape[0] != poses.shape[0]:
                 raise ValueError("intrinsics tensor must be [B,4]")
-            _b.call("lnerf_march_rays_train_camera", _chk(poses, "poses"), _chk(intr, "intrinsics"), int(poses.shape[0]),
-                    int(him), int(wim), _chk(rays_o, "rays_o"), _chk(rays_d, "rays_d"), *[float(v) for v in aabb],
-                    float(min_near), _chk(density_bitfield, "density_bitfield", torch.uint8), float(bound), int(C), int(H),
-                    int(max_steps), float(dt_gamma), _chk(noises, "noises", allow_none=True), seed,
-                    _chk(noise_counter, "noise_counter", torch.int32, allow_none=True), int(capacity), _p(xyzs), _p(dirs),
-                    _p(deltas), _p(rays), _p(counter), _stream())
-            return MarchResult(xyzs, dirs, deltas, rays, counter, capacity)
-        fx, fy, cx, cy = [float(v) for v in intr]
-        _b.call("lnerf_march_rays_train_pose", _chk(poses, "poses"), int(poses.shape[0]), int(him), int(wim), fx, fy, cx,
-                cy, _chk(rays_o, "rays_o"), _chk(rays_d, "rays_d"), *[float(v) for v in aabb], float(min_near),
-                _chk(density_bitfield, "density_bitfield", torch.uint8), float(bound), int(C), int(H), int(max_steps),
-                float(dt_gamma), _chk(noises, "noises", allow_none=True), seed,
-                _chk(noise_counter, "noise_counter", torch.int32, allow_none=True), int(capacity), _p(xyzs), _p(dirs),
-                _p(deltas), _p(rays), _p(counter), _stream())
-        return MarchResult(xyzs, dirs, deltas, rays, counter, capacity)
-    if nears is None and aabb is not None:
-        _b.call("lnerf_march_rays_train_aabb", _chk(rays_o, "rays_o"), _chk(rays_d, "rays_d"),
-                *[float(v) for v in aabb], float(min_near), N, _chk(density_bitfield, "density_bitfield", torch.uint8),
-                float(bound), int(C), int(H), int(max_steps), float(dt_gamma), _chk(noises, "noises", allow_none=True),
-                seed, _chk(noise_counter, "noise_counter", torch.int32, allow_none=True), int(capacity), _p(xyzs),
-                _p(dirs), _p(deltas), _p(rays), _p(counter), _stream())
-        return MarchResult(xyzs, dirs, deltas, rays, counter, capacity)
-    _b.call("lnerf_march_rays_train", _chk(rays_o, "rays_o"), _chk(rays_d, "rays_d"), _chk(nears, "nears"),
-            _chk(fars, "fars"), N, _chk(density_bitfield, "density_bitfield", torch.uint8), float(bound), int(C),
-            int(H), int(max_steps), float(dt_gamma), _chk(noises, "noises", allow_none=True), seed,
-            _chk(noise_counter, "noise_counter", torch.int32, allow_none=True), int(capacity), _p(xyzs),
-            _p(dirs), _p(deltas), _p(rays), _p(counter), _stream())
+            entry = "lnerf_march_rays_train_camera"
+            head = (_chk(poses, "poses"), _chk(intr, "intrinsics"), int(poses.shape[0]), int(him), int(wim))
+        else:
+            entry = "lnerf_march_rays_train_pose"
+            fx, fy, cx, cy = [float(v) for v in intr]
+            head = (_chk(poses, "poses"), int(poses.shape[0]), int(him), int(wim), fx, fy, cx, cy)
+        head += (_chk(rays_o, "rays_o"), _chk(rays_d, "rays_d"), *[float(v) for v in aabb], float(min_near))
+    elif nears is None and aabb is not None:
+        entry = "lnerf_march_rays_train_aabb"
+        head = (_chk(rays_o, "rays_o"), _chk(rays_d, "rays_d"), *[float(v) for v in aabb], float(min_near), N)
+    else:
+        entry = "lnerf_march_rays_train"
+        head = (_chk(rays_o, "rays_o"), _chk(rays_d, "rays_d"), _chk(nears, "nears"), _chk(fars, "fars"), N)
+    _b.call(entry, *head, _chk(density_bitfield, "density_bitfield", torch.uint8), float(bound), int(C), int(H),
+            int(max_steps), float(dt_gamma), _chk(noises, "noises", allow_none=True), seed,
+            _chk(noise_counter, "noise_counter", torch.int32, allow_none=True), int(capacity), _p(xyzs), _p(dirs),
+            _p(deltas), _p(rays), _p(counter), _stream())
     return MarchResult(xyzs, dirs, deltas, rays, counter, capacity)
 
 

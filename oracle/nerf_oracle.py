@@ -328,6 +328,25 @@ def march_rays_train(rays_o, rays_d, nears, fars, bitfield, bound: float, cascad
     return xyzs, dirs, deltas, rays, M
 
 
+def apply_capacity(rays: torch.Tensor, capacity: int):
+    """The capacity rule of the training march on `rays` [N,3] = (id, offset, count) of march_rays_train: walking the
+    rays in order, a non-empty ray is dropped -- (offset, count) = (0, 0) -- when the samples of ALL rays before it
+    (dropped or not) plus its own exceed `capacity`; kept and empty rays keep their offsets.  Returns (rays', M, live
+    rays, dropped rays); M is the end of the last kept span if a ray was dropped, else min(all samples, capacity)."""
+    out = rays.clone()
+    before, best, live, dropped = 0, 0, 0, 0
+    for n, c in enumerate(rays[:, 2].tolist()):
+        if c > 0 and before + c > capacity:
+            out[n, 1] = 0
+            out[n, 2] = 0
+            dropped += 1
+        elif c > 0:
+            live += 1
+            best = max(best, before + c)
+        before += c
+    return out, (best if dropped else min(before, int(capacity))), live, dropped
+
+
 # --------------------------------------------------------------------------------------
 # H4  occupancy-pruned ray march (inference: march / composite / compact, one chunk per call)
 # --------------------------------------------------------------------------------------

@@ -6,6 +6,7 @@ Tolerances (fp32 path, stated per SURVEY.md §7):
   * forward floats: rtol 1e-4, atol 1e-5    * gradients: rtol 1e-3, atol 1e-5 (float atomics
     reorder sums); weight gradients that sum 1e5 terms: relative-to-max 1e-4.
 """
+import functools
 import math
 
 import numpy as np
@@ -91,21 +92,40 @@ def test_morton_and_packbits_bit_exact(dev, bits_oracle):
 
 
 # ------------------------------------------------------------------------------ H4
-def _march_both(dev, ro, rd, bits, bound, cascade, G, max_steps, dt_gamma, noises, capacity=None):
+_POISON = 0x7FC0BEEF   # a NaN no march computes: what a sample buffer holds where nothing was written
+
+
+def _poisoned_buffers(dev, N, capacity):
+    """A fresh MarchResult to march into through `out=`: sample buffers full of _POISON words, counter zero."""
+    from src.latent_nerf.raymarching import backend as B, raymarching as rm
+    buf = lambda c: torch.full((capacity, c), _POISON, dtype=torch.int32, device=dev).view(torch.float32)
+    return rm.MarchResult(buf(3), buf(3), buf(2), torch.empty(N, 3, dtype=torch.int32, device=dev),
+                          torch.zeros(int(B.get_lib().lnerf_march_counter_len(N)), dtype=torch.int32, device=dev), capacity)
+
+
+def _march_both(dev, ro, rd, bits, bound, cascade, G, max_steps, dt_gamma, noises, capacity=None, ref=None, poison=False):
+    """(oracle march with the capacity rule applied, GPU march).  ref: the oracle's march of these rays, if the caller
+    has it already; poison: march into _poisoned_buffers instead of uninitialised ones."""
     from src.latent_nerf.raymarching import raymarching as rm
     aabb = [-bound] * 3 + [bound] * 3
     nears, fars = O.near_far_from_aabb(ro, rd, aabb, 0.1)
-    ref = O.march_rays_train(ro, rd, nears, fars, bits, bound, cascade, G, max_steps, dt_gamma, noises)
+    if ref is None:
+        ref = O.march_rays_train(ro, rd, nears, fars, bits, bound, cascade, G, max_steps, dt_gamma, noises)
+    if capacity is not None:
+        ref = tuple(ref[:3]) + O.apply_capacity(ref[3], capacity)[:2]
+    size = capacity if capacity is not None else max(ro.shape[0] * min(max_steps, 256), 64)   # (the default)
+    out = [_poisoned_buffers(dev, ro.shape[0], size) if poison else None for _ in range(2)]
     res = rm.march_rays_train(ro.to(dev), rd.to(dev), bound, bits.to(dev), cascade, G, nears.to(dev), fars.to(dev),
                               dt_gamma=dt_gamma, max_steps=max_steps, capacity=capacity,
-                              noises=None if noises is None else noises.to(dev))
+                              noises=None if noises is None else noises.to(dev), out=out[0])
     # the form that clips against the box inside the march passes (lnerf_march_rays_train_aabb) is the same march
     res2 = rm.march_rays_train(ro.to(dev), rd.to(dev), bound, bits.to(dev), cascade, G, None, None,
                                dt_gamma=dt_gamma, max_steps=max_steps, capacity=capacity,
-                               noises=None if noises is None else noises.to(dev), aabb=aabb, min_near=0.1)
-    M = int(res.counter[0])
+                               noises=None if noises is None else noises.to(dev), aabb=aabb, min_near=0.1, out=out[1])
+    M = int(res.counter[0]) if not poison else size   # (poisoned buffers are defined, hence comparable, to their end)
     assert torch.equal(res2.counter.cpu(), res.counter.cpu()) and torch.equal(res2.rays.cpu(), res.rays.cpu())
-    assert torch.equal(res2.xyzs[:M].cpu(), res.xyzs[:M].cpu()) and torch.equal(res2.deltas[:M].cpu(), res.deltas[:M].cpu())
+    for a, b in ((res2.xyzs, res.xyzs), (res2.dirs, res.dirs), (res2.deltas, res.deltas)):
+        assert torch.equal(a[:M].view(torch.int32).cpu(), b[:M].view(torch.int32).cpu())
     return ref, res
 
 
@@ -200,6 +220,159 @@ def test_march_above_8192_rays_takes_the_scan_kernel(dev):
     assert res_h.counter.numel() == 4 + h + (h + 3) // 4
     assert torch.equal(res_h.rays.cpu(), res_c.rays[:h].cpu())
     assert int(res_c.counter[2]) >= int(res_h.counter[2]) > 0 and int(res_c.counter[0]) == int(res_h.counter[0]) <= cap
+
+
+# ---- every corner of the training march against the oracle: ragged ray counts, both forms at their boundary, the step
+# recurrence, the capacity rule, the jitter hand-over, generated rays of several views.  One scene: 96 x 96 rays at a
+# 32^3 sphere, 128 steps -- dt_gamma = 1/32 is where the step really varies there (with 1/128 every step clamps to
+# dt_min) --, rays in pixel order from one that hits the sphere, so that a single ray still has samples.
+_SPLIT_G, _SPLIT_STEPS, _SPLIT_SEED = 32, 128, 0x5EED
+_CAPACITIES = {"default": lambda M: None, "half": lambda M: M // 2, "third": lambda M: M // 3, "zero": lambda M: 0}
+
+
+@functools.lru_cache(maxsize=None)
+def _split_scene():
+    _, bits, _, _, ro, rd = _scene(G=_SPLIT_G, HW=96)
+    first = 48 * 96 + 46
+    torch.manual_seed(1)
+    return bits, torch.roll(ro, -first, 0), torch.roll(rd, -first, 0), torch.rand(ro.shape[0])
+
+
+@functools.lru_cache(maxsize=None)
+def _split_case(N, dt_gamma, noise_step=None):
+    """(rays, jitter table, the oracle's march of them) of the first N rays; computed once, never modified.  noise_step:
+    the jitter of call `noise_step` of the counter-based generator instead of the table."""
+    bits, ro, rd, noises = _split_scene()
+    ro, rd = ro[:N].contiguous(), rd[:N].contiguous()
+    noises = noises[:N].contiguous() if noise_step is None else O.march_noise(N, _SPLIT_SEED, noise_step)
+    nears, fars = O.near_far_from_aabb(ro, rd, [-1.0] * 3 + [1.0] * 3, 0.1)
+    ref = O.march_rays_train(ro, rd, nears, fars, bits, 1.0, 1, _SPLIT_G, _SPLIT_STEPS, dt_gamma, noises)
+    # the case must not pass vacuously
+    assert ref[4] > 0
+    assert N < 1023 or int((ref[3][:, 2] == 0).sum()) > 0
+    assert dt_gamma == 0.0 or ref[2][:, 0].unique().numel() > 1
+    return ro, rd, noises, ref
+
+
+def _assert_march_is_the_oracles(dev, N, dt_gamma, capacity):
+    """The GPU march of a _split_case under a capacity: spans, totals, peak word, every kept sample, and nothing written
+    outside the kept spans."""
+    bits = _split_scene()[0]
+    ro, rd, noises, full = _split_case(N, dt_gamma)
+    cap = _CAPACITIES[capacity](full[4])
+    (xyzs, dirs, deltas, rays, M), res = _march_both(dev, ro, rd, bits, 1.0, 1, _SPLIT_G, _SPLIT_STEPS, dt_gamma, noises,
+                                                     capacity=cap, ref=full, poison=True)
+    kept = rays[:, 2] > 0
+    live, dropped = int(kept.sum()), int(((full[3][:, 2] > 0) & ~kept).sum())
+    if cap is None:
+        assert dropped == 0 and M == full[4]
+    elif capacity == "third" and N >= 5:
+        assert live > 0 and dropped > 0
+    elif capacity == "zero":
+        assert live == 0 and dropped > 0 and res.xyzs.numel() == 0
+    assert torch.equal(res.rays.cpu(), rays)
+    assert res.counter[:4].tolist() == [M, live, dropped, M | ((1 << 30) if dropped else 0)]
+    # kept rays keep the oracle's offsets: their spans hold the oracle's samples, the rest of the buffers is untouched
+    written = torch.zeros(max(res.capacity, full[4]), dtype=torch.bool)
+    for o, c in rays[kept][:, 1:].tolist():
+        written[o:o + c] = True
+    assert int(written.sum()) == int(rays[:, 2].sum())
+    for got, want in ((res.xyzs, xyzs), (res.dirs, dirs), (res.deltas, deltas)):
+        got = got.cpu()
+        assert torch.equal(got[written[:res.capacity]], want[written[:full[4]]])
+        assert bool((got.view(torch.int32)[~written[:res.capacity]] == _POISON).all())
+    return res
+
+
+@pytest.mark.parametrize("capacity", list(_CAPACITIES))
+@pytest.mark.parametrize("dt_gamma", [0.0, 1.0 / 32])
+@pytest.mark.parametrize("N", [1, 3, 5, 1023])
+def test_march_ragged_last_workgroup(dev, N, dt_gamma, capacity):
+    """Ray counts that leave the last workgroup 1-3 wavefronts short (the count pass's barrier), down to one ray, in the
+    two-launch form; with capacity 0 the sample buffers are empty tensors (null pointers at the C ABI)."""
+    res = _assert_march_is_the_oracles(dev, N, dt_gamma, capacity)
+    assert res.counter.numel() == 4 + N + (N + 3) // 4
+
+
+def test_march_of_no_rays_clears_the_totals(dev):
+    from src.latent_nerf.raymarching import raymarching as rm
+    bits = _split_scene()[0].to(dev)
+    out = _poisoned_buffers(dev, 0, 64)
+    out.counter.fill_(7)
+    none = torch.empty(0, 3, device=dev)
+    for kw in (dict(nears=torch.empty(0, device=dev), fars=torch.empty(0, device=dev)),
+               dict(nears=None, fars=None, aabb=[-1.0] * 3 + [1.0] * 3, min_near=0.1)):
+        res = rm.march_rays_train(none, none, 1.0, bits, 1, _SPLIT_G, max_steps=_SPLIT_STEPS, out=out, **kw)
+        assert res.counter is out.counter and res.counter.tolist() == [0, 0, 0, 0]
+        out.counter.fill_(7)
+
+
+@pytest.mark.parametrize("capacity", ["default", "third"])
+@pytest.mark.parametrize("dt_gamma", [0.0, 1.0 / 32])
+@pytest.mark.parametrize("N", [8192, 8193])
+def test_march_at_the_boundary_between_the_forms(dev, N, dt_gamma, capacity):
+    """8192 rays: the last count the write pass prefixes itself; 8193: the scan kernel, with a ragged last workgroup, the
+    step recurrence and overflow under the recurrence."""
+    res = _assert_march_is_the_oracles(dev, N, dt_gamma, capacity)
+    assert res.counter.numel() == (4 + N + (N + 3) // 4 if N == 8192 else 4)
+
+
+@pytest.mark.parametrize("dt_gamma", [0.0, 1.0 / 32])
+def test_march_counter_based_jitter_through_the_scan_kernel(dev, dt_gamma):
+    """Above 8192 rays the scan kernel advances the jitter counter BETWEEN the passes and the write pass steps back by
+    one: call k still marches the jitter hash(n, seed, k), and the counter reads k + 1 after it."""
+    from src.latent_nerf.raymarching import raymarching as rm
+    bits = _split_scene()[0]
+    N = 9216
+    counter = torch.zeros(1, dtype=torch.int32, device=dev)
+    for k in range(2):
+        ro, rd, _, (xyzs, dirs, deltas, rays, M) = _split_case(N, dt_gamma, noise_step=k)
+        nears, fars = O.near_far_from_aabb(ro, rd, [-1.0] * 3 + [1.0] * 3, 0.1)
+        res = rm.march_rays_train(ro.to(dev), rd.to(dev), 1.0, bits.to(dev), 1, _SPLIT_G, nears.to(dev), fars.to(dev),
+                                  perturb=True, dt_gamma=dt_gamma, max_steps=_SPLIT_STEPS, noise_state=(_SPLIT_SEED, counter))
+        assert int(counter[0]) == k + 1 and res.counter.numel() == 4
+        assert res.counter.tolist() == [M, int((rays[:, 2] > 0).sum()), 0, M] and torch.equal(res.rays.cpu(), rays)
+        assert torch.equal(res.xyzs[:M].cpu(), xyzs) and torch.equal(res.dirs[:M].cpu(), dirs)
+        assert torch.equal(res.deltas[:M].cpu(), deltas)
+
+
+@pytest.mark.parametrize("dt_gamma", [0.0, 1.0 / 32])
+def test_march_generates_the_rays_of_several_views(dev, dt_gamma):
+    """Rays generated inside the count pass for B = 3 views of 5 x 7 pixels (105 rays: a ragged last workgroup), intrinsics
+    by value (one tuple, lnerf_march_rays_train_pose) and from device memory (one row PER VIEW,
+    lnerf_march_rays_train_camera): the rays are get_rays' of each view with its intrinsics, the march is the table
+    form's of those rays -- and the oracle's."""
+    from src.latent_nerf.raymarching import raymarching as rm
+    B, H, W = 3, 5, 7
+    bits = _split_scene()[0]
+    aabb = [-1.0] * 3 + [1.0] * 3
+    poses = torch.stack([O.pose_from_angles(math.radians(60), math.radians(20), 1.25), O.pose_from_angles(0.9, 4.0, 1.2),
+                         O.pose_from_angles(2.0, 1.0, 1.4)]).to(dev)
+    f = W / (2 * math.tan(math.radians(55) / 2))
+    rows = [(f, f, W / 2, H / 2), (1.2 * f, 0.9 * f, W / 2 + 0.3, H / 2 - 0.2), (0.8 * f, 1.1 * f, W / 2 - 0.4, H / 2 + 0.1)]
+    torch.manual_seed(3)
+    noises = torch.rand(B * H * W)
+    for intr, per_view in ((rows[0], [rows[0]] * B), (torch.tensor(rows, dtype=torch.float32, device=dev), rows)):
+        views = [rm.get_rays(poses[b], per_view[b], H, W) for b in range(B)]
+        ro = torch.cat([v[0].view(-1, 3) for v in views])
+        rd = torch.cat([v[1].view(-1, 3) for v in views])
+        nears, fars = rm.near_far_from_aabb(ro, rd, aabb, 0.1)
+        want = rm.march_rays_train(ro, rd, 1.0, bits.to(dev), 1, _SPLIT_G, nears, fars, dt_gamma=dt_gamma,
+                                   max_steps=_SPLIT_STEPS, noises=noises.to(dev))
+        xyzs, dirs, deltas, rays, M = O.march_rays_train(ro.cpu(), rd.cpu(), nears.cpu(), fars.cpu(), bits, 1.0, 1, _SPLIT_G,
+                                                         _SPLIT_STEPS, dt_gamma, noises)
+        assert M > 0 and (dt_gamma == 0.0 or deltas[:, 0].unique().numel() > 1)
+        assert all(int(rays[b * H * W:(b + 1) * H * W, 2].sum()) > 0 for b in range(B))   # every view sees the sphere
+        go = torch.full((B * H * W, 3), float("nan"), device=dev)
+        gd = torch.full_like(go, float("nan"))
+        res = rm.march_rays_train(go, gd, 1.0, bits.to(dev), 1, _SPLIT_G, None, None, dt_gamma=dt_gamma,
+                                  max_steps=_SPLIT_STEPS, noises=noises.to(dev), aabb=aabb, min_near=0.1,
+                                  camera=(poses, intr, H, W))
+        assert torch.equal(go, ro) and torch.equal(gd, rd)
+        assert torch.equal(res.rays, want.rays) and torch.equal(res.counter[:4], want.counter[:4])
+        assert torch.equal(res.rays.cpu(), rays) and res.counter[:4].tolist() == [M, int((rays[:, 2] > 0).sum()), 0, M]
+        for got, ref, gpu in ((res.xyzs, xyzs, want.xyzs), (res.dirs, dirs, want.dirs), (res.deltas, deltas, want.deltas)):
+            assert torch.equal(got[:M], gpu[:M]) and torch.equal(got[:M].cpu(), ref)
 
 
 # ------------------------------------------------------------------------------ H5 / H6

@@ -124,6 +124,23 @@ def test_march_properties(dt_gamma):
     assert int(cnt[nears >= fars].sum()) == 0
 
 
+def test_apply_capacity_keeps_all_or_drops_all():
+    G = 32
+    _, bits, ro, rd = _small_scene(G)
+    nears, fars = O.near_far_from_aabb(ro, rd, [-1, -1, -1, 1, 1, 1], 0.1)
+    rays, M = O.march_rays_train(ro, rd, nears, fars, bits, 1.0, 1, G, 256, 0.0, None)[3:]
+    live = int((rays[:, 2] > 0).sum())
+    assert M > 0 and 0 < live < rays.shape[0]
+    for cap in (M, M + 1, 10 * M):   # room for everything: the input, untouched
+        out, m, lv, dr = O.apply_capacity(rays, cap)
+        assert torch.equal(out, rays) and (m, lv, dr) == (M, live, 0)
+    out, m, lv, dr = O.apply_capacity(rays, 0)   # room for nothing: every non-empty ray goes, empty ones stay as they are
+    assert (m, lv, dr) == (0, 0, live) and int(out[:, 2].sum()) == 0
+    empty = rays[:, 2] == 0
+    assert torch.equal(out[empty], rays[empty]) and int(out[~empty, 1].abs().sum()) == 0
+    assert torch.equal(out[:, 0], rays[:, 0])
+
+
 def test_march_max_steps_cap():
     # bound 2 (two cascades), fully occupied: the lattice has up to 2x max_steps points per ray,
     # so the per-ray sample cap binds

@@ -223,7 +223,7 @@ int lnerf_grid_encode_backward_bf16(const float *xyzs, float bound, const void *
                                     int64_t level_stride, float *dtable_zero, int variant, void *workspace,
                                     size_t workspace_bytes, void *grad_bf16, lnerf_stream_t stream);
 /* Split form of lnerf_grid_encode_backward_bf16 for a PIPELINED data-parallel exchange: pass 1 once for all levels
- * (lnerf_grid_scatter_bin; clears the bucket cursors), then pass 2 + the finishing pass per level range
+ * (lnerf_grid_scatter_bin; clears the level maxima), then pass 2 per level range
  * (lnerf_grid_scatter_reduce_bf16: writes rows offsets[level_lo] .. offsets[level_hi] of grad_bf16), so that the
  * all-reduce of a level group can be launched while the next group is still being summed.  Same workspace, same
  * arithmetic, same bits as the one-call form. */
@@ -238,7 +238,7 @@ int lnerf_grid_scatter_reduce_bf16(float bound, int num_levels, int level_dim, c
 
 /* Backward of the hash grid fused with the table's optimiser step (single-GPU training: no gradient
  * exchange sits between the two).  Same scatter as above (variant 2 or 3), but the kernel that
- * finishes a row's sum (pass 2, or the finishing kernel of the sliced coarse levels) applies
+ * finishes a row's sum (pass 2: a bucket's only workgroup, or the last of its slices to arrive) applies
  * Adam(beta1, beta2, eps) to it straight from the fixed-point sum -- `table`, `exp_avg`, `exp_avg_sq`
  * (f32 [rows, 2]) and the optional bf16 `shadow_bf16` are updated in place and the gradient never
  * reaches HBM.  `dtable_zero` (f32 [rows, 2]) only carries the records of overflowing buckets; it

@@ -16,9 +16,9 @@ namespace lnerf {
 // records per slice workgroup of pass 2 (a bucket with fewer records is reduced by one workgroup)
 constexpr int REDUCE_SLICE_RECS = 16384;
 
-// Optional fused table update (lnerf_grid_encode_backward_adam): where pass 2 (or its finishing kernel) owns a
-// row outright it applies the Adam step straight from the fixed-point sum: the gradient of the table never travels
-// through HBM (42 -> 26 bytes per table entry and step).
+// Optional fused table update (lnerf_grid_encode_backward_adam): the workgroup of pass 2 that finishes a bucket (its
+// only one, or the last slice to arrive) applies the Adam step straight from the fixed-point sum: the gradient of the
+// table never travels through HBM (42 -> 26 bytes per table entry and step).
 struct FusedUpdate {
     float *p, *m, *v;
     uint16_t *shadow;    // optional bf16 copy of p, refreshed in the same pass
@@ -56,18 +56,7 @@ __device__ __forceinline__ int active_slices(int n, int smax) {
     return S < 1 ? 1 : (S > smax ? smax : S);
 }
 
-// A bucket summed by ONE workgroup: the workgroup adds its tile to dtable (or applies the Adam step, FUSE).
-// A bucket cut into slices (few, heavily loaded coarse buckets): every slice stores its EXACT 64-bit partial sums
-// as a tile of `partials`, and the slice that arrives last adds the tiles up -- integer addition, so the result does not depend
-// on how many slices there were or in which order they ran: the whole gradient is bitwise reproducible.
-//
-// The records of bucket b are the segments (first slot, count) = segtab entry of (item, b), one per item of pass 1, inside
-// the items' chunks.  Wave w of the workgroup takes items w, w + 16, ...: it reads 64 of its entries with one load and
-// walks the concatenation of those segments 64 records per round (see the loop).  REDUCE_ROUNDS rounds of loads are
-// in flight per lane.  Built and measured on the way (profiles/r03_exp_scatter.jsonl): the segment of a lane found by
-// a binary search through ds_bpermute (+12 us: the permutes share the LDS pipe with the atomics); one segment per round
-// (half-empty waves: three times the instructions, 2-3x the time).
-constexpr int REDUCE_ROUNDS = 8;
+constexpr int REDUCE_ROUNDS = 8;   // rounds of record loads in flight per lane (accumulate)
 // ---- the step's TAIL: what is left of a single-GPU step besides the scatter.  In a replayed graph a dependent dispatch
 // costs ~4.5 us whatever it computes, and three of them sat behind pass 2 for a few microseconds of work: the finishing
 // pass of the sliced buckets (pass 2 does it itself now), the sum of the MLP's gradient slabs and the Adam step of the
@@ -187,7 +176,6 @@ struct TailJob {
     SlabAdam sa;
     int blocks;            // leading workgroups of the launch that run slab blocks (four each)
     int32_t *tick;         // device step counter pair
-    int32_t *arrive;       // arrival counters (workspace header)
     int do_tick, clear_gmax;
     int rev_lo, rev_hi;    // work units [rev_lo, rev_hi) are taken in DESCENDING order (0, 0: none)
 };
@@ -204,336 +192,381 @@ __device__ __forceinline__ void st_f4(float4 *p, const float4 &x) {
     __builtin_nontemporal_store(v, reinterpret_cast<nt_f4 *>(p));
 }
 
-template <int RT, typename REC, bool FUSE>
-__device__ __forceinline__ void scatter_reduce_one(int wg, const GridMeta &meta, const BucketMeta &bm,
-                                                   const int32_t *__restrict__ items_dev,
-                                                   const uint32_t *__restrict__ segtab, int32_t *__restrict__ bucket_n,
-                                                   int32_t *__restrict__ slice_arrive,
-                                                   unsigned int *gmax, const REC *__restrict__ recs,
-                                                   float *__restrict__ dtable, long long *__restrict__ partials,
-                                                   const FusedUpdate &fu, const SlabAdam &sa, int32_t step_now,
-                                                   bool have_step) {
-    // (declared HERE, not passed in: a pointer parameter loses the LDS address space and every ds_add_u64 becomes a
-    // flat atomic -- measured 0.211 -> 0.275 ms for the scatter call)
-    __shared__ long long acc[BK_ROWS * 2];  // [feature][row]: a wave's 64 random rows spread over 32 bank pairs
-    __shared__ int s_red[RT / 64];
-    __shared__ uint32_t s_bmp[RT / 64][128];            // per wave: segment-start bitmap of a sub-batch (4096 records)
-    __shared__ uint32_t s_soff[RT / 64][64];            // per wave: (chunk slot - flat start) of its non-empty segments
-    constexpr int NW = RT / 64;
-    if (wg < 0) {
-        // a SLAB workgroup of the closing launch (wg = -1 - index): RT / 256 slab blocks, their 1 KiB of LDS each carved
-        // out of the accumulator tile (used HERE, through the array itself: see above)
-        const int sub = (int)threadIdx.x >> 8, lt = (int)threadIdx.x & 255;
-        float (*part)[TAIL_P] = reinterpret_cast<float (*)[TAIL_P]>(acc) + sub * TAIL_G;
-        slab_block<8>((-1 - wg) * (RT / 256) + sub, lt, sa, fu.a, step_now, part, [] { __syncthreads(); });
-        return;
-    }
-    // locate (level, bucket, slice) of this work unit
-    int l = 0;
-    while (l + 1 < meta.num_levels && wg >= bm.wgstart[l + 1]) ++l;
-    const int Smax = bm.slices[l];
-    const int local = wg - bm.wgstart[l];
-    int b = local / Smax;
-    const int s = local - b * Smax;
-    const int nb = bm.nb[l];
+// ---- pass 2 in its parts.  k_scatter_reduce / reduce_bucket read top to bottom: which unit is this workgroup (reduce_unit),
+// how is its bucket cut (the slice decision), add the records up (accumulate: sub_batch -> sub_locate -> pipelined rounds
+// of add_record), request the rows' state (RowState::prefetch), hand a slice over (merge_slices), finish the rows (one of
+// finish_add / finish_wire / RowState::finish / finish_adam, all through unfix).  The workgroup's LDS is at namespace scope
+// so that every part names the __shared__ array ITSELF (through a pointer that had lost the LDS address space every
+// ds_add_u64 became a flat atomic -- measured 0.211 -> 0.275 ms for the scatter call; tests/test_abi_cpu.py looks at the
+// compiled kernels).  s_acc lives from the clear to the finisher (a slab workgroup carves its scratch out of it).
+__shared__ long long s_acc[BK_ROWS * 2];                   // [feature][row]: a wave's 64 random rows spread over 32 bank pairs
+template <int NW> __shared__ int s_red[NW];                 // the slice decision's record count; merge_slices' arrival value
+template <int NW> __shared__ uint32_t s_bmp[NW][128];      // per wave: segment-start bitmap of a sub-batch (4096 records)
+template <int NW> __shared__ uint32_t s_soff[NW][64];      // per wave: (chunk slot - flat start) of its non-empty segments
+// The workspace as both passes and the step's tail see it (by value; built once per call on the host: scatter_ws)
+struct ScatterWs {
+    unsigned int *gmax;                // level maxima, CUR_STRIDE words apart (raised by pass 1)
+    int32_t *items_dev;                // items of the pass 1 that filled the workspace
+    int32_t *arrive, *slice_arrive;    // arrival counters: the step's tail (root + 8 shards) / one word per bucket (slices)
+    uint32_t *segtab;                  // (first slot, count) per (item, bucket)
+    void *recs; long long *partials;   // the items' chunks of Rec8 / Rec12; tiles of the sliced levels
+};
+struct ReduceOut { float *dtable; FusedUpdate fu; };   // un-fused: dtable += sums / fused: the Adam step or the wire output
+
+// Which unit block x of the launch takes -- the ONE definition.  wg < 0: slab workgroup -1 - wg of a closing launch (they
+// sit in front of the buckets); else workgroup wg of the whole table's (level, bucket, slice) units, level-major.
+struct ReduceUnit { int wg, l, b, s, Smax, nb; };   // .. level, bucket, slice; slices planned per bucket, buckets of the level
+template <bool FUSE>
+__device__ __forceinline__ ReduceUnit reduce_unit(int block, int wg_lo, const TailJob &tj, int num_levels, const BucketMeta &bm) {
+    ReduceUnit u = {};
+    int unit = block - (FUSE ? tj.blocks : 0);
+    // heaviest first: the un-merged fine levels carry the most records per bucket; taken in level order they ran LAST
+    // and the launch's tail was its heaviest workgroups (the sliced coarse levels keep their place at the front)
+    if (unit + wg_lo >= tj.rev_lo && unit + wg_lo < tj.rev_hi) unit = tj.rev_lo + (tj.rev_hi - 1 - (unit + wg_lo)) - wg_lo;
+    u.wg = unit < 0 ? unit : unit + wg_lo;
+    if (u.wg < 0) return u;
+    while (u.l + 1 < num_levels && u.wg >= bm.wgstart[u.l + 1]) ++u.l;
+    u.Smax = bm.slices[u.l];
+    const int local = u.wg - bm.wgstart[u.l];
+    u.b = local / u.Smax;
+    u.s = local - u.b * u.Smax;
+    u.nb = bm.nb[u.l];
     // Workgroups are dealt round-robin over the 8 XCDs (observed; used for speed only): on an un-sliced level whose
     // bucket count is a multiple of 8 the workgroups of one XCD take CONTIGUOUS buckets.  The segments of neighbouring
     // buckets are neighbours inside every chunk and share 128-byte lines at their seams: read by workgroups of one XCD at
     // about the same time, those lines come from that XCD's L2 the second time instead of twice through the fabric.
-    if (Smax == 1 && (nb & 7) == 0) b = (local & 7) * (nb >> 3) + (local >> 3);
-    const int tid = threadIdx.x, lane = tid & 63;
+    if (u.Smax == 1 && (u.nb & 7) == 0) u.b = (local & 7) * (u.nb >> 3) + (local >> 3);
+    return u;
+}
+// The accumulator's one writer.
+template <typename REC> __device__ __forceinline__ void add_record(const REC &r, const FixScale &fs) {
+    constexpr int FB = FixBits<REC>::kBits;
+    unsigned long long *ua = reinterpret_cast<unsigned long long *>(s_acc);
+    const uint32_t a0 = r.row_in_bucket();
+    atomicAdd(&ua[a0], (unsigned long long)to_fixed<FB>((r.a() * fs.sc_a) * fs.sc_b));
+    atomicAdd(&ua[a0 + BK_ROWS], (unsigned long long)to_fixed<FB>((r.b() * fs.sc_a) * fs.sc_b));
+}
+
+// A SUB-BATCH of a window of 64 segment entries: whole segments from lane `a` on with at most REDUCE_SUB records.  Walk the
+// CONCATENATION of the segments 64 records per round: lane i of a round takes flat record f0 + i, so every lane carries a
+// record whatever the segment sizes are (~32 on a hashed level, thousands on a one-bucket level).  Which segment a lane's
+// record is in comes from a BITMAP of the segment starts: bit p = "flat record p is the first of its segment"; lane k
+// keeps bits [64 k, 64 k + 64).  A round reads its 64 bits with two scalar readlanes; a lane's segment is the number of
+// starts at or below its position (mbcnt), its record's slot one LDS read of that segment's (chunk slot - flat start) plus
+// its position: ~10 instructions per round instead of a scalar walk over the 2-3 segments a round spans (~150: the pass
+// was bound by instruction issue, not by HBM -- without the Adam phase it took 87 us for 240 MB).  The bitmap covers
+// REDUCE_SUB = 4096 records (64 rounds).
+constexpr int REDUCE_SUB = 4096;
+static_assert(ITEM_RECS <= REDUCE_SUB, "a segment must fit a sub-batch");
+struct SubBatch {   // bnd: one past its last lane (> a); Ts: its records; bm_lo / bm_hi: lane k keeps bits [64 k, 64 k + 64)
+    int bnd, Ts, bm_lo, bm_hi, nstart;   // of the bitmap; nstart: segment starts before the next round (advanced by sub_locate)
+};
+// builds the bitmap and the segments' (chunk slot - flat start) of the sub-batch that starts at lane a / flat record a_base
+// of the window.  e = the lane's entry, inc = the inclusive sum of the lanes' record counts, slot0 = its item's chunk slot
+__device__ __forceinline__ SubBatch sub_batch(uint32_t e, int inc, int a, int a_base, uint32_t slot0, int lane,
+                                              uint32_t (&bmp)[128], uint32_t (&soff)[64]) {
+    SubBatch sb;
+    const int c = (int)(e >> 16);                             // records of the lane's segment
+    const bool in = lane >= a && inc - a_base <= REDUCE_SUB;  // (inc is monotone: a contiguous run from lane a)
+    sb.bnd = a + (int)__popcll(__ballot(in));
+    sb.Ts = __builtin_amdgcn_readlane(inc, sb.bnd - 1) - a_base;
+    const bool seg = in && c > 0;
+    const int ci = (int)mbcnt(__ballot(seg));                 // index among the non-empty segments
+    const int start = inc - c - a_base;                       // flat start inside the sub-batch
+    bmp[2 * lane] = 0u; bmp[2 * lane + 1] = 0u;
+    if (seg) {
+        atomicOr(&bmp[start >> 5], 1u << (start & 31));
+        soff[ci] = slot0 + (e & 0xFFFFu) - (uint32_t)start;
+    }
+    // the lanes exchange data through LDS: a wave's LDS operations execute in order, but the COMPILER reasons
+    // per thread -- without the fence pair a lane that set no bit "knows" its words are still zero and never
+    // reads them back (measured: the read was sunk into the `if (seg)` block above)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    sb.bm_lo = (int)bmp[2 * lane]; sb.bm_hi = (int)bmp[2 * lane + 1]; sb.nstart = 0;
+    return sb;
+}
+// record index (inside the level's region) of flat record fb + lane of the sub-batch; call with increasing fb
+__device__ __forceinline__ uint32_t sub_locate(SubBatch &sb, const uint32_t (&soff)[64], int fb, int lane) {
+    const int k = __builtin_amdgcn_readfirstlane(fb >> 6);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane(sb.bm_lo, k);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane(sb.bm_hi, k);
+    const unsigned long long m1 = (((unsigned long long)hi << 32) | lo) >> 1;
+    // starts at positions 1..lane = bits below `lane` of (M >> 1); position 0 = bit 0 of M
+    const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m1, 0u));
+    const int j = sb.nstart + (int)(lo & 1u) - 1 + below;
+    sb.nstart += __popc(lo) + __popc(hi);
+    const int f = fb + lane;
+    const uint32_t at = soff[j < 0 ? 0 : j] + (uint32_t)f;
+    return f < sb.Ts ? at : 0u;                               // (slot 0 exists: the load is unconditional)
+}
+
+// The record loop of one wave.  The records of bucket b are the segments (first slot, count) = segtab entry of (item, b),
+// one per item of pass 1, inside the items' chunks (entry of item t: tab[t * nb]).  Wave w takes items first = i0 + w,
+// first + NW, ... (nmy of them): it reads 64 of its entries with one load (a WINDOW; e_first: the first one's, requested
+// by the caller in front of the clear) and walks the concatenation of those segments in sub-batches, each in pipelined
+// rounds of 64 records.  Built and measured on the way (profiles/r03_exp_scatter.jsonl): the segment of a lane found by a
+// binary search through ds_bpermute (+12 us: the permutes share the LDS pipe with the atomics); one segment per round
+// (half-empty waves: three times the instructions, 2-3x the time).
+template <int RT, typename REC>
+__device__ __forceinline__ void accumulate(const uint32_t *tab, int nb, int first, int nmy, uint32_t e_first, const REC *lrec,
+                                           const FixScale &fs, int lane, int wave) {
+    constexpr int NW = RT / 64;
+    // rounds of loads in flight per lane.  A 12-byte record is three registers: five rounds in flight are what the
+    // 64 registers of two resident workgroups leave room for (eight spilled 20-36 bytes per lane to scratch, whose
+    // traffic shares the vector-memory queue with the very loads the loop waits for)
+    constexpr int U = REC::kPacked ? REDUCE_ROUNDS : (REDUCE_ROUNDS < 5 ? REDUCE_ROUNDS : 5);
+    for (int kb = 0; kb < nmy; kb += 64) {                            // (one pass for up to 64 x 16 = 1024 items)
+        uint32_t e = e_first;
+        if (kb > 0) e = kb + lane < nmy ? tab[(int64_t)(first + NW * (kb + lane)) * nb] : 0u;
+        const int inc = wave_inclusive_sum_i((int)(e >> 16));         // the lanes' records, summed
+        const int T = __builtin_amdgcn_readlane(inc, 63);
+        const uint32_t slot0 = (uint32_t)(first + NW * (kb + lane)) * (uint32_t)ITEM_RECS;
+        int a = 0, a_base = 0;                                        // first lane / flat start of the sub-batch (uniform)
+        while (a_base < T) {
+            SubBatch sb = sub_batch(e, inc, a, a_base, slot0, lane, s_bmp<NW>[wave], s_soff<NW>[wave]);
+            // software pipeline over the rounds: U loads are in flight at ALL times -- a round's record is consumed
+            // and its register immediately re-armed with the load of the round U ahead (a plain "issue U, consume U"
+            // loop drains to zero loads in flight at the end of every batch)
+            const int nr = (sb.Ts + 63) >> 6;                         // rounds (uniform)
+            REC r[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (u < nr) r[u] = lrec[sub_locate(sb, s_soff<NW>[wave], 64 * u, lane)];
+            for (int rb = 0; rb < nr; rb += U) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int rd = rb + u;                            // uniform
+                    if (rd < nr) {
+                        pin_record(r[u]);                             // (keeps the load outside the predicated block)
+                        const REC cur = r[u];
+                        if (rd + U < nr) r[u] = lrec[sub_locate(sb, s_soff<NW>[wave], 64 * (rd + U), lane)];
+                        if (64 * rd + lane < sb.Ts) add_record(cur, fs);
+                    }
+                }
+            }
+            a = sb.bnd;
+            a_base += sb.Ts;
+        }
+    }
+}
+
+// Sliced bucket: every slice publishes its EXACT 64-bit partial sums as a tile of `partials`; the slice that arrives LAST
+// adds the other tiles to its own sums and finishes the rows like the only workgroup of an unsliced bucket (integer sums:
+// neither the slicing nor the arrival order changes a bit of the result).  The heavily loaded coarse buckets come first in
+// the grid, so this happens early in the launch, under the other buckets' work -- as its own pass behind the launch it was
+// a chain of dependent round trips (~9 us) at the end of the step.  Tiles travel with device-scope (write-through /
+// cache-bypassing) accesses: slices run on different XCDs, whose L2s are not coherent for plain stores, and the addresses
+// are the same every step.
+// ORDERING -- by construction on the ISA, not by C++ memory orders (every atomic below is RELAXED):
+//   writer   tile stores = `global_store_dwordx2 ... sc1` (write-through to device scope); `s_waitcnt vmcnt(0)`:
+//            every store of the wave ACKNOWLEDGED, i.e. visible at device scope; workgroup barrier: true of all
+//            16 waves; then ONE returning `global_atomic_add ... sc0` on the bucket's arrival word.
+//   reader   (the arrival that returned S - 1) its value reaches the other waves through LDS + a barrier, so every
+//            tile load is issued behind the atomic's return; tile loads = `global_load_dwordx2 ... sc1`: they
+//            miss this XCD's non-coherent L2 and see the acknowledged stores.
+// A release / acquire pair at agent scope would be correct by the letter and costs a `buffer_wbl2` -- a write-back
+// of the XCD's whole L2 -- per workgroup: 106 -> 273 us for this pass.  tests/test_abi_cpu.py
+// (test_cross_workgroup_handoffs_are_scoped_accesses) checks the compiled kernel for exactly these instructions
+// and for the absence of L2 write-backs / invalidates, so a compiler that chose otherwise fails the CPU suite.
+// Returns whether this workgroup arrived last (uniform): then s_acc holds the bucket's whole sums.
+template <int RT>
+__device__ __forceinline__ bool merge_slices(const ReduceUnit &u, int S, const BucketMeta &bm, const ScatterWs &ws, int tid) {
+    unsigned long long *tiles = reinterpret_cast<unsigned long long *>(ws.partials) +
+                                ((int64_t)bm.pstart[u.l] + (int64_t)u.b * u.Smax) * (BK_ROWS * 2);
+    unsigned long long *pt = tiles + (int64_t)u.s * (BK_ROWS * 2);
+    const unsigned long long *ul = reinterpret_cast<const unsigned long long *>(s_acc);
+    for (int i = tid; i < BK_ROWS * 2; i += RT) __hip_atomic_store(&pt[i], ul[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's part of the tile has been written
+    __syncthreads();
+    int32_t *arr = ws.slice_arrive + bm.bstart[u.l] + u.b;
+    if (tid == 0) {
+        const int old = __hip_atomic_fetch_add(arr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (old == S - 1) __hip_atomic_store(arr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // clean for the next call
+        s_red<RT / 64>[0] = old;
+    }
+    __syncthreads();
+    if (s_red<RT / 64>[0] != S - 1) return false;   // uniform: an earlier arrival, somebody else finishes the bucket
+    // (one tile at a time, ALL of the lane's elements of it in flight: element by element the sum was a chain of
+    // 8 (S - 1) dependent round trips -- 94 us for a six-slice bucket, the longest workgroup of the launch)
+    constexpr int NI = BK_ROWS * 2 / RT, NB = NI < 4 ? NI : 4;   // (four 64-bit loads in flight: no spill at 64 registers)
+    for (int k0 = 0; k0 < NI; k0 += NB) {
+        unsigned long long q[NB];
+#pragma unroll
+        for (int k = 0; k < NB; ++k) q[k] = ul[tid + (k0 + k) * RT];
+        for (int s2 = 0; s2 < S; ++s2) {
+            if (s2 == u.s) continue;     // uniform
+            const unsigned long long *ot = tiles + (int64_t)s2 * (BK_ROWS * 2) + tid + k0 * RT;
+            unsigned long long t[NB];
+#pragma unroll
+            for (int k = 0; k < NB; ++k) t[k] = __hip_atomic_load(&ot[k * RT], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+            for (int k = 0; k < NB; ++k) q[k] += t[k];
+        }
+#pragma unroll
+        for (int k = 0; k < NB; ++k) s_acc[tid + (k0 + k) * RT] = (long long)q[k];
+    }
+    __syncthreads();
+    return true;
+}
+__device__ __forceinline__ uint32_t bf16_pair(float x, float y) {
+    return (uint32_t)f32_to_bf16(x) | ((uint32_t)f32_to_bf16(y) << 16);
+}
+// Row r's two sums back from fixed point -- the ONE conversion (scale + whether the bucket had records at all: without,
+// s_acc was never cleared and the gradient is zero).
+struct UnFix { FixScale fs; bool have; };
+__device__ __forceinline__ float2 unfix(const UnFix &t, int r) {
+    if (!t.have) return make_float2(0.f, 0.f);
+    return make_float2(((float)s_acc[r] * t.fs.un_a) * t.fs.un_b, ((float)s_acc[r + BK_ROWS] * t.fs.un_a) * t.fs.un_b);
+}
+// The four ways to finish `rows` rows from row R0 of the table; chosen ONCE per workgroup, in reduce_bucket (uniform).
+enum Finisher { FIN_ADD, FIN_WIRE, FIN_ADAM_FAST, FIN_ADAM };
+// sole owner of these rows in this launch: plain read-modify-write, 8 B per lane
+template <int RT> __device__ __forceinline__ void finish_add(const UnFix &t, float *dtable, int64_t R0, int rows, int tid) {
+    float2 *dst = reinterpret_cast<float2 *>(dtable) + R0;
+    for (int r = tid; r < rows; r += RT) {
+        const float2 d = dst[r], g = unfix(t, r);
+        dst[r] = make_float2(d.x + g.x, d.y + g.y);
+    }
+}
+// gradient output in the wire format: one bf16 pair per row, WRITTEN (stale content before; zeros without records)
+template <int RT> __device__ __forceinline__ void finish_wire(const UnFix &t, uint16_t *grad_out, int64_t R0, int rows, int tid) {
+    uint32_t *go = reinterpret_cast<uint32_t *>(grad_out) + R0;
+    for (int r = tid; r < rows; r += RT) {
+        const float2 g = unfix(t, r);
+        go[r] = bf16_pair(g.x, g.y);
+    }
+}
+// the Adam step row by row (a partial bucket, an odd first row, the last arriver of a sliced bucket)
+template <int RT>
+__device__ __forceinline__ void finish_adam(const UnFix &t, const FusedUpdate &fu, const AdamArgs &a, int64_t R0, int rows,
+                                            int tid) {
+    float2 *p2 = reinterpret_cast<float2 *>(fu.p) + R0, *m2 = reinterpret_cast<float2 *>(fu.m) + R0;
+    float2 *v2 = reinterpret_cast<float2 *>(fu.v) + R0;
+    uint32_t *sh = fu.shadow ? reinterpret_cast<uint32_t *>(fu.shadow) + R0 : nullptr;
+    for (int r = tid; r < rows; r += RT) {
+        float2 Pr = p2[r], Mr = m2[r], Vr = v2[r];
+        float2 g = unfix(t, r);
+        adam_one(Pr.x, g.x, Mr.x, Vr.x, a);
+        adam_one(Pr.y, g.y, Mr.y, Vr.y, a);
+        p2[r] = Pr; m2[r] = Mr; v2[r] = Vr;
+        if (sh) sh[r] = bf16_pair(Pr.x, Pr.y);
+    }
+}
+// FIN_ADAM_FAST: the lane's row pairs q = tid + j RT, their parameters and moments in registers between prefetch() and
+// finish().  The prefetch is issued BEHIND the record loop and IN FRONT of the barrier that ends it: a wave that is done
+// with its records waits for the slowest wave anyway, and the loads travel meanwhile.  (Requested ahead of the record
+// stream they were measured 35 us slower: the records queue behind them.)
+template <int RT> struct RowState {
+    static constexpr int NQ = (BK_ROWS / 2 + RT - 1) / RT;  // row pairs per lane
+    float4 P[NQ], Mv[NQ], V[NQ];
+    float4 *p4, *m4, *v4;
+    __device__ __forceinline__ RowState(const FusedUpdate &fu, int64_t R0)
+        : p4(reinterpret_cast<float4 *>(reinterpret_cast<float2 *>(fu.p) + R0)),
+          m4(reinterpret_cast<float4 *>(reinterpret_cast<float2 *>(fu.m) + R0)),
+          v4(reinterpret_cast<float4 *>(reinterpret_cast<float2 *>(fu.v) + R0)) {}
+    __device__ __forceinline__ void prefetch(int tid) {
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) {  // all of the lane's loads: six 16-byte loads in flight behind the barrier
+            const int q = tid + j * RT;
+            P[j] = ld_f4(p4 + q); Mv[j] = ld_f4(m4 + q); V[j] = ld_f4(v4 + q);
+        }
+    }
+    __device__ __forceinline__ void finish(const UnFix &t, const FusedUpdate &fu, const AdamArgs &a, int64_t R0, int tid) {
+        uint2 *sh2 = fu.shadow ? reinterpret_cast<uint2 *>(reinterpret_cast<uint32_t *>(fu.shadow) + R0) : nullptr;
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) {
+            const int q = tid + j * RT;
+            float2 g0 = unfix(t, 2 * q), g1 = unfix(t, 2 * q + 1);
+            adam_one(P[j].x, g0.x, Mv[j].x, V[j].x, a);
+            adam_one(P[j].y, g0.y, Mv[j].y, V[j].y, a);
+            adam_one(P[j].z, g1.x, Mv[j].z, V[j].z, a);
+            adam_one(P[j].w, g1.y, Mv[j].w, V[j].w, a);
+            st_f4(p4 + q, P[j]); st_f4(m4 + q, Mv[j]); st_f4(v4 + q, V[j]);
+            if (sh2) sh2[q] = make_uint2(bf16_pair(P[j].x, P[j].y), bf16_pair(P[j].z, P[j].w));
+        }
+    }
+};
+
+// One (level, bucket, slice) unit, the parts in order.  A return leaves through the kernel's end.
+template <int RT, typename REC, bool FUSE>
+__device__ __forceinline__ void reduce_bucket(const ReduceUnit &u, const GridMeta &meta, const BucketMeta &bm, const ScatterWs &ws,
+                                              const ReduceOut &out, int32_t step_now, bool have_step) {
+    constexpr int NW = RT / 64;
+    const int l = u.l, nb = u.nb, tid = threadIdx.x, lane = tid & 63;
     // (uniform, and known to be: everything derived from it -- the wave's items, their chunk addresses -- stays in
     // scalar registers; as a function of threadIdx it was per-lane 64-bit address arithmetic and spilled)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int I = *items_dev;                       // items of the pass 1 that filled the workspace
+    int I = *ws.items_dev;                       // items of the pass 1 that filled the workspace
     I = I < bm.n_items ? I : bm.n_items;
-    const uint32_t *tab = segtab + (int64_t)bm.bstart[l] * bm.n_items + b;   // entry of item t: tab[t * nb]
+    const uint32_t *tab = ws.segtab + (int64_t)bm.bstart[l] * bm.n_items + u.b;   // entry of item t: tab[t * nb]
+    // The slice decision -- the ONE place that defines `direct`.  A level whose buckets MAY be sliced (Smax > 1, uniform
+    // per level) counts the bucket's records first: S slices are active, slice s takes items [i0, i1).
     int S = 1, i0 = 0, i1 = I;
-    if (Smax > 1) {  // (uniform per level) a level whose buckets MAY be sliced: count the bucket's records first
+    if (u.Smax > 1) {
         int cnt = 0;
         for (int t = tid; t < I; t += RT) cnt += (int)(tab[(int64_t)t * nb] >> 16);
         cnt = wave_inclusive_sum_i(cnt);
-        if (lane == 63) s_red[wave] = cnt;
+        if (lane == 63) s_red<NW>[wave] = cnt;
         __syncthreads();
         int n = 0;
 #pragma unroll
-        for (int k = 0; k < NW; ++k) n += s_red[k];
-        S = active_slices(n, Smax);
-        if (s == 0 && tid == 0) bucket_n[bm.bstart[l] + b] = n;   // for the finishing pass
-        if (s >= S) return;    // uniform per workgroup
-        i0 = (int)(((long long)I * s) / S);
-        i1 = (int)(((long long)I * (s + 1)) / S);
+        for (int k = 0; k < NW; ++k) n += s_red<NW>[k];
+        S = active_slices(n, u.Smax);
+        if (u.s >= S) return;    // uniform per workgroup
+        i0 = (int)(((long long)I * u.s) / S);
+        i1 = (int)(((long long)I * (u.s + 1)) / S);
     }
     const bool direct = S == 1;        // this workgroup sums the whole bucket: it finishes the rows itself
-    const bool fuse = FUSE;            // (whoever finishes a bucket -- its only workgroup, or the last slice to arrive)
     // uniform.  (An active slice always has items: S > 1 means more than REDUCE_SLICE_RECS >= ITEM_RECS records, i.e.
-    // at least S items.)
+    // at least S items.)  Whoever finishes a bucket -- its only workgroup, or the last slice to arrive -- owes a fused
+    // bucket without records the Adam step (g = 0) and a wire bucket its zeros.
     const bool have = i1 > i0 || !direct;
-    if (!have && !fuse) return;  // (a fused bucket without records still owes its rows the Adam step, g = 0)
-    constexpr int FB = FixBits<REC>::kBits;
+    if (!have && !FUSE) return;
     // from the bound of |value| of the LEVEL (found by pass 1).  One device-scope atomic load: the last workgroup of a
     // closing launch to arrive ZEROES the maxima (tail_arrive) -- ordered behind this read by the arrival, but a plain
     // load the compiler might re-issue later would be a data race on paper
-    const FixScale fs = fix_scale(__hip_atomic_load(&gmax[l * CUR_STRIDE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
-                                  REC::kPacked ? FB : bm.fix_bits);
+    const UnFix t = {fix_scale(__hip_atomic_load(&ws.gmax[l * CUR_STRIDE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
+                               REC::kPacked ? FixBits<REC>::kBits : bm.fix_bits), have};
     RED_STAMP_INIT();
-    const int hsize = meta.offsets[l + 1] - meta.offsets[l];
-    const int row0 = b << BK_SHIFT;
-    int rows = hsize - row0;
+    const int row0 = u.b << BK_SHIFT;
+    int rows = meta.offsets[l + 1] - meta.offsets[l] - row0;
     rows = rows < BK_ROWS ? rows : BK_ROWS;
     const int64_t R0 = (int64_t)meta.offsets[l] + row0;
-    // the usual fused case (full bucket, even first row): two rows per lane and access (16 B).  Their parameters and
-    // moments are requested BEHIND the record loop and IN FRONT of the barrier that ends it: a wave that is done with its
-    // records waits for the slowest wave anyway, and the loads travel meanwhile.  (Requested ahead of the record stream
-    // they were measured 35 us slower: the records queue behind them.)
-    constexpr int NQ = (BK_ROWS / 2 + RT - 1) / RT;  // row pairs per lane
-    const bool fast = fuse && direct && !fu.grad_out && ((R0 | rows) & 1) == 0 && rows == BK_ROWS && (BK_ROWS / 2) % RT == 0;
-    float4 P[NQ], Mv[NQ], V[NQ];
-    float4 *p4 = reinterpret_cast<float4 *>(reinterpret_cast<float2 *>(fu.p) + R0);
-    float4 *m4 = reinterpret_cast<float4 *>(reinterpret_cast<float2 *>(fu.m) + R0);
-    float4 *v4 = reinterpret_cast<float4 *>(reinterpret_cast<float2 *>(fu.v) + R0);
+    // FIN_ADAM_FAST, the usual fused case: a full bucket with an even first row, summed by this workgroup alone
+    const bool pairs = direct && ((R0 | rows) & 1) == 0 && rows == BK_ROWS && (BK_ROWS / 2) % RT == 0;
+    const Finisher fin = !FUSE ? FIN_ADD : out.fu.grad_out ? FIN_WIRE : pairs ? FIN_ADAM_FAST : FIN_ADAM;
+    RowState<RT> rs(out.fu, R0);
     if (have) {
         const int first = i0 + wave;                                  // this wave's items: first, first + NW, ...
         const int nmy = first < i1 ? (i1 - first + NW - 1) / NW : 0;
         // (the first 64 segment entries are requested before the accumulators are cleared: one round trip hidden)
         uint32_t e_first = 0u;
         if (lane < nmy) e_first = tab[(int64_t)(first + NW * lane) * nb];
-        for (int i = tid; i < BK_ROWS * 2; i += RT) acc[i] = 0ll;
+        for (int i = tid; i < BK_ROWS * 2; i += RT) s_acc[i] = 0ll;
         __syncthreads();
         step_now = __builtin_amdgcn_readfirstlane(step_now);   // (returned by now: into a scalar register for the loop)
         RED_STAMP(10);
-        const REC *lrec = recs + (int64_t)l * bm.n_items * ITEM_RECS;
-        unsigned long long *ua = reinterpret_cast<unsigned long long *>(acc);
-        auto add = [&](const REC &r) {
-            const uint32_t a0 = r.row_in_bucket();
-            atomicAdd(&ua[a0], (unsigned long long)to_fixed<FB>((r.a() * fs.sc_a) * fs.sc_b));
-            atomicAdd(&ua[a0 + BK_ROWS], (unsigned long long)to_fixed<FB>((r.b() * fs.sc_a) * fs.sc_b));
-        };
-        // rounds of loads in flight per lane.  A 12-byte record is three registers: five rounds in flight are what the
-        // 64 registers of two resident workgroups leave room for (eight spilled 20-36 bytes per lane to scratch, whose
-        // traffic shares the vector-memory queue with the very loads the loop waits for)
-        constexpr int U = REC::kPacked ? REDUCE_ROUNDS : (REDUCE_ROUNDS < 5 ? REDUCE_ROUNDS : 5);
-        for (int kb = 0; kb < nmy; kb += 64) {                        // (one pass for up to 64 x 16 = 1024 items)
-            uint32_t e = e_first;
-            if (kb > 0) e = kb + lane < nmy ? tab[(int64_t)(first + NW * (kb + lane)) * nb] : 0u;
-            const int T = __builtin_amdgcn_readlane(wave_inclusive_sum_i((int)(e >> 16)), 63);   // the lanes' records
-            // Walk the CONCATENATION of the segments 64 records per round: lane i of a round takes flat record f0 + i, so
-            // every lane carries a record whatever the segment sizes are (~32 on a hashed level, thousands on a
-            // one-bucket level).  Which segment a lane's record is in comes from a BITMAP of the segment starts: bit p =
-            // "flat record p is the first of its segment"; lane k keeps bits [64 k, 64 k + 64).  A round reads its 64 bits
-            // with two scalar readlanes; a lane's segment is the number of starts at or below its position (mbcnt), its
-            // record's slot one LDS read of that segment's (chunk slot - flat start) plus its position: ~10 instructions
-            // per round instead of a scalar walk over the 2-3 segments a round spans (~150: the pass was bound by
-            // instruction issue, not by HBM -- without the Adam phase it took 87 us for 240 MB).  The bitmap covers SUB =
-            // 4096 records (64 rounds): a window of 64 segments is taken in sub-batches of whole segments with at most SUB
-            // records.
-            constexpr int SUB = 4096;
-            static_assert(ITEM_RECS <= SUB, "a segment must fit a sub-batch");
-            const int c = (int)(e >> 16);                             // records of the lane's segment
-            const int inc = wave_inclusive_sum_i(c);
-            int a = 0, a_base = 0;                                    // first lane / flat start of the sub-batch (uniform)
-            while (a_base < T) {
-                const bool in = lane >= a && inc - a_base <= SUB;     // (inc is monotone: a contiguous run from lane a)
-                const int bnd = a + (int)__popcll(__ballot(in));      // one past the sub-batch's last lane, > a
-                const int Ts = __builtin_amdgcn_readlane(inc, bnd - 1) - a_base;   // its records
-                const bool seg = in && c > 0;
-                const int ci = (int)mbcnt(__ballot(seg));             // index among the non-empty segments
-                const int start = inc - c - a_base;                   // flat start inside the sub-batch
-                s_bmp[wave][2 * lane] = 0u;
-                s_bmp[wave][2 * lane + 1] = 0u;
-                if (seg) {
-                    atomicOr(&s_bmp[wave][start >> 5], 1u << (start & 31));
-                    s_soff[wave][ci] = (uint32_t)(first + NW * (kb + lane)) * (uint32_t)ITEM_RECS + (e & 0xFFFFu) -
-                                       (uint32_t)start;
-                }
-                // the lanes exchange data through LDS: a wave's LDS operations execute in order, but the COMPILER reasons
-                // per thread -- without the fence pair a lane that set no bit "knows" its words are still zero and never
-                // reads them back (measured: the read was sunk into the `if (seg)` block above)
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                const int bm_lo = (int)s_bmp[wave][2 * lane], bm_hi = (int)s_bmp[wave][2 * lane + 1];
-                int nstart = 0;                                       // segment starts before the round (uniform)
-                // record index (inside the level's region) of flat record fb + lane; called with increasing fb
-                auto locate = [&](int fb) __attribute__((always_inline)) -> uint32_t {
-                    const int k = __builtin_amdgcn_readfirstlane(fb >> 6);
-                    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane(bm_lo, k);
-                    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane(bm_hi, k);
-                    const unsigned long long m1 = (((unsigned long long)hi << 32) | lo) >> 1;
-                    // starts at positions 1..lane = bits below `lane` of (M >> 1); position 0 = bit 0 of M
-                    const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m1 >> 32),
-                                                                     __builtin_amdgcn_mbcnt_lo((uint32_t)m1, 0u));
-                    const int j = nstart + (int)(lo & 1u) - 1 + below;
-                    nstart += __popc(lo) + __popc(hi);
-                    const int f = fb + lane;
-                    const uint32_t at = s_soff[wave][j < 0 ? 0 : j] + (uint32_t)f;
-                    return f < Ts ? at : 0u;                          // (slot 0 exists: the load is unconditional)
-                };
-                // software pipeline over the rounds: U loads are in flight at ALL times -- a round's record is consumed
-                // and its register immediately re-armed with the load of the round U ahead (a plain "issue U, consume U"
-                // loop drains to zero loads in flight at the end of every batch)
-                const int nr = (Ts + 63) >> 6;                        // rounds (uniform)
-                REC r[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-                    if (u < nr) r[u] = lrec[locate(64 * u)];
-                for (int rb = 0; rb < nr; rb += U) {
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        const int rd = rb + u;                        // uniform
-                        if (rd < nr) {
-                            pin_record(r[u]);                         // (keeps the load outside the predicated block)
-                            const REC cur = r[u];
-                            if (rd + U < nr) r[u] = lrec[locate(64 * (rd + U))];
-                            if (64 * rd + lane < Ts) add(cur);
-                        }
-                    }
-                }
-                a = bnd;
-                a_base += Ts;
-            }
-        }
+        accumulate<RT, REC>(tab, nb, first, nmy, e_first, static_cast<const REC *>(ws.recs) + (int64_t)l * bm.n_items * ITEM_RECS,
+                            t.fs, lane, wave);
         RED_STAMP(11);
-        if (fast) {
-#pragma unroll
-            for (int j = 0; j < NQ; ++j) {  // all of the lane's loads: six 16-byte loads in flight behind the barrier
-                const int q = tid + j * RT;
-                P[j] = ld_f4(p4 + q); Mv[j] = ld_f4(m4 + q); V[j] = ld_f4(v4 + q);
-            }
-        }
+        if (fin == FIN_ADAM_FAST) rs.prefetch(tid);
         __syncthreads();
         RED_STAMP(12);
-    } else if (fast) {
-#pragma unroll
-        for (int j = 0; j < NQ; ++j) {
-            const int q = tid + j * RT;
-            P[j] = ld_f4(p4 + q); Mv[j] = ld_f4(m4 + q); V[j] = ld_f4(v4 + q);
-        }
+    } else if (fin == FIN_ADAM_FAST) {
+        rs.prefetch(tid);
     }
-    if (!direct) {
-        // Sliced bucket: every slice publishes its EXACT 64-bit partial sums as a tile of `partials`; the slice that
-        // arrives LAST adds the other tiles to its own sums and finishes the rows like the only workgroup of an unsliced
-        // bucket (integer sums: neither the slicing nor the arrival order changes a bit of the result).  The heavily
-        // loaded coarse buckets come first in the grid, so this happens early in the launch, under the other buckets'
-        // work -- as its own pass behind the launch it was a chain of dependent round trips (~9 us) at the end of the
-        // step.  Tiles travel with device-scope (write-through / cache-bypassing) accesses: slices run on different
-        // XCDs, whose L2s are not coherent for plain stores, and the addresses are the same every step.
-        //
-        // ORDERING -- by construction on the ISA, not by C++ memory orders (every atomic below is RELAXED):
-        //   writer   tile stores = `global_store_dwordx2 ... sc1` (write-through to device scope); `s_waitcnt vmcnt(0)`:
-        //            every store of the wave ACKNOWLEDGED, i.e. visible at device scope; workgroup barrier: true of all
-        //            16 waves; then ONE returning `global_atomic_add ... sc0` on the bucket's arrival word.
-        //   reader   (the arrival that returned S - 1) its value reaches the other waves through LDS + a barrier, so every
-        //            tile load is issued behind the atomic's return; tile loads = `global_load_dwordx2 ... sc1`: they
-        //            miss this XCD's non-coherent L2 and see the acknowledged stores.
-        // A release / acquire pair at agent scope would be correct by the letter and costs a `buffer_wbl2` -- a write-back
-        // of the XCD's whole L2 -- per workgroup: 106 -> 273 us for this pass.  tests/test_abi_cpu.py
-        // (test_cross_workgroup_handoffs_are_scoped_accesses) checks the compiled kernel for exactly these instructions
-        // and for the absence of L2 write-backs / invalidates, so a compiler that chose otherwise fails the CPU suite.
-        unsigned long long *tiles = reinterpret_cast<unsigned long long *>(partials) +
-                                    ((int64_t)bm.pstart[l] + (int64_t)b * Smax) * (BK_ROWS * 2);
-        unsigned long long *pt = tiles + (int64_t)s * (BK_ROWS * 2);
-        const unsigned long long *ul = reinterpret_cast<const unsigned long long *>(acc);
-        for (int i = tid; i < BK_ROWS * 2; i += RT)
-            __hip_atomic_store(&pt[i], ul[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's part of the tile has been written
-        __syncthreads();
-        int32_t *arr = slice_arrive + bm.bstart[l] + b;
-        if (tid == 0) {
-            const int old = __hip_atomic_fetch_add(arr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (old == S - 1) __hip_atomic_store(arr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // clean for the next call
-            s_red[0] = old;
-        }
-        __syncthreads();
-        if (s_red[0] != S - 1) return;     // uniform: an earlier arrival, somebody else finishes the bucket
-        // (one tile at a time, ALL of the lane's elements of it in flight: element by element the sum was a chain of
-        // 8 (S - 1) dependent round trips -- 94 us for a six-slice bucket, the longest workgroup of the launch)
-        constexpr int NI = BK_ROWS * 2 / RT, NB = NI < 4 ? NI : 4;   // (four 64-bit loads in flight: no spill at 64 registers)
-        for (int k0 = 0; k0 < NI; k0 += NB) {
-            unsigned long long q[NB];
-#pragma unroll
-            for (int k = 0; k < NB; ++k) q[k] = ul[tid + (k0 + k) * RT];
-            for (int s2 = 0; s2 < S; ++s2) {
-                if (s2 == s) continue;     // uniform
-                const unsigned long long *ot = tiles + (int64_t)s2 * (BK_ROWS * 2) + tid + k0 * RT;
-                unsigned long long t[NB];
-#pragma unroll
-                for (int k = 0; k < NB; ++k)
-                    t[k] = __hip_atomic_load(&ot[k * RT], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-                for (int k = 0; k < NB; ++k) q[k] += t[k];
-            }
-#pragma unroll
-            for (int k = 0; k < NB; ++k) acc[tid + (k0 + k) * RT] = (long long)q[k];
-        }
-        __syncthreads();
-    }
-    float *dst = dtable + R0 * 2;
-    if (fuse) {
-        AdamArgs a = fu.a;
-        if (have_step) adam_bias_at(a, __builtin_amdgcn_readfirstlane(step_now));   // (the closing launch: see the kernel)
-        else adam_bias(a);
-        a.zero_grad = 0;
-        float2 *p2 = reinterpret_cast<float2 *>(fu.p) + R0, *m2 = reinterpret_cast<float2 *>(fu.m) + R0;
-        float2 *v2 = reinterpret_cast<float2 *>(fu.v) + R0;
-        uint32_t *sh = fu.shadow ? reinterpret_cast<uint32_t *>(fu.shadow) + R0 : nullptr;
-        auto grad_of = [&](int r, float &g0, float &g1) {
-            g0 = 0.f; g1 = 0.f;
-            if (have) {
-                g0 = ((float)acc[r] * fs.un_a) * fs.un_b;
-                g1 = ((float)acc[r + BK_ROWS] * fs.un_a) * fs.un_b;
-            }
-        };
-        if (fu.grad_out) {  // gradient output in the wire format: one bf16 pair per row
-            uint32_t *go = reinterpret_cast<uint32_t *>(fu.grad_out) + R0;
-            for (int r = tid; r < rows; r += RT) {
-                float g0, g1;
-                grad_of(r, g0, g1);
-                go[r] = (uint32_t)f32_to_bf16(g0) | ((uint32_t)f32_to_bf16(g1) << 16);
-            }
-            return;
-        }
-        if (fast) {
-            uint2 *sh2 = reinterpret_cast<uint2 *>(sh);
-#pragma unroll
-            for (int j = 0; j < NQ; ++j) {
-                const int q = tid + j * RT;
-                float ga, gb, gc, gd;
-                grad_of(2 * q, ga, gb);
-                grad_of(2 * q + 1, gc, gd);
-                adam_one(P[j].x, ga, Mv[j].x, V[j].x, a);
-                adam_one(P[j].y, gb, Mv[j].y, V[j].y, a);
-                adam_one(P[j].z, gc, Mv[j].z, V[j].z, a);
-                adam_one(P[j].w, gd, Mv[j].w, V[j].w, a);
-                st_f4(p4 + q, P[j]); st_f4(m4 + q, Mv[j]); st_f4(v4 + q, V[j]);
-                if (sh) {
-                    uint2 w;
-                    w.x = (uint32_t)f32_to_bf16(P[j].x) | ((uint32_t)f32_to_bf16(P[j].y) << 16);
-                    w.y = (uint32_t)f32_to_bf16(P[j].z) | ((uint32_t)f32_to_bf16(P[j].w) << 16);
-                    sh2[q] = w;
-                }
-            }
-            RED_STAMP(13);
-            RED_STAMP_FLUSH();
-            return;
-        }
-        for (int r = tid; r < rows; r += RT) {
-            float2 Pr = p2[r], Mr = m2[r], Vr = v2[r];
-            float g0, g1;
-            grad_of(r, g0, g1);
-            adam_one(Pr.x, g0, Mr.x, Vr.x, a);
-            adam_one(Pr.y, g1, Mr.y, Vr.y, a);
-            p2[r] = Pr; m2[r] = Mr; v2[r] = Vr;
-            if (sh) sh[r] = (uint32_t)f32_to_bf16(Pr.x) | ((uint32_t)f32_to_bf16(Pr.y) << 16);
-        }
-        return;
-    }
-    // sole owner of these rows in this launch: plain read-modify-write, 8 B per lane
-    for (int r = tid; r < rows; r += RT) {
-        float2 d = reinterpret_cast<float2 *>(dst)[r];
-        d.x += ((float)acc[r] * fs.un_a) * fs.un_b;
-        d.y += ((float)acc[r + BK_ROWS] * fs.un_a) * fs.un_b;
-        reinterpret_cast<float2 *>(dst)[r] = d;
+    if (!direct && !merge_slices<RT>(u, S, bm, ws, tid)) return;
+    AdamArgs a = out.fu.a;   // (once, in front of the choice; have_step: the closing launch, see the kernel)
+    if (FUSE && have_step) adam_bias_at(a, __builtin_amdgcn_readfirstlane(step_now));
+    else if (FUSE) adam_bias(a);
+    a.zero_grad = 0;
+    switch (fin) {
+    case FIN_ADD: finish_add<RT>(t, out.dtable, R0, rows, tid); break;
+    case FIN_WIRE: finish_wire<RT>(t, out.fu.grad_out, R0, rows, tid); break;
+    case FIN_ADAM: finish_adam<RT>(t, out.fu, a, R0, rows, tid); break;
+    case FIN_ADAM_FAST: rs.finish(t, out.fu, a, R0, tid); RED_STAMP(13); RED_STAMP_FLUSH(); break;
     }
 }
 
@@ -543,10 +576,7 @@ __device__ __forceinline__ void scatter_reduce_one(int wg, const GridMeta &meta,
 constexpr int FUSED_RT = 1024;   // threads per workgroup of the fused pass
 template <int RT, typename REC, bool FUSE>
 __global__ void __launch_bounds__(RT, RT / 128)
-k_scatter_reduce(GridMeta meta, BucketMeta bm, const int32_t *__restrict__ items_dev, const uint32_t *__restrict__ segtab,
-                 int32_t *__restrict__ bucket_n, int32_t *__restrict__ slice_arrive, unsigned int *gmax,
-                 const REC *__restrict__ recs, float *__restrict__ dtable, long long *__restrict__ partials, int wg_lo,
-                 FusedUpdate fu, TailJob tj) {
+k_scatter_reduce(GridMeta meta, BucketMeta bm, ScatterWs ws, ReduceOut out, int wg_lo, TailJob tj) {
     // (closing the step: the counter is read ONCE per wave, with a device-scope atomic load, before anything else --
     // the last workgroup of the launch to arrive rewrites it)
 #ifdef LNERF_STAMPS
@@ -555,13 +585,16 @@ k_scatter_reduce(GridMeta meta, BucketMeta bm, const int32_t *__restrict__ items
     int32_t step_now = 0;
     const bool closing = FUSE && (tj.do_tick || tj.clear_gmax || tj.blocks > 0);
     // (requested here, consumed behind the workgroup's first barrier: no stall in front of the record stream)
-    if (closing && fu.a.step_dev) step_now = __hip_atomic_load(fu.a.step_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    int unit = (int)blockIdx.x - (FUSE ? tj.blocks : 0);
-    // heaviest first: the un-merged fine levels carry the most records per bucket; taken in level order they ran LAST
-    // and the launch's tail was its heaviest workgroups (the sliced coarse levels keep their place at the front)
-    if (unit + wg_lo >= tj.rev_lo && unit + wg_lo < tj.rev_hi) unit = tj.rev_lo + (tj.rev_hi - 1 - (unit + wg_lo)) - wg_lo;
-    scatter_reduce_one<RT, REC, FUSE>(unit < 0 ? unit : unit + wg_lo, meta, bm, items_dev, segtab, bucket_n, slice_arrive,
-                                      gmax, recs, dtable, partials, fu, tj.sa, step_now, closing && fu.a.step_dev != nullptr);
+    if (closing && out.fu.a.step_dev) step_now = __hip_atomic_load(out.fu.a.step_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const ReduceUnit u = reduce_unit<FUSE>((int)blockIdx.x, wg_lo, tj, meta.num_levels, bm);
+    if (u.wg < 0) {
+        // a SLAB workgroup of the closing launch: RT / 256 slab blocks, their 1 KiB of LDS each carved out of the tile
+        const int sub = (int)threadIdx.x >> 8, lt = (int)threadIdx.x & 255;
+        float (*part)[TAIL_P] = reinterpret_cast<float (*)[TAIL_P]>(s_acc) + sub * TAIL_G;
+        slab_block<8>((-1 - u.wg) * (RT / 256) + sub, lt, tj.sa, out.fu.a, step_now, part, [] { __syncthreads(); });
+    } else {
+        reduce_bucket<RT, REC, FUSE>(u, meta, bm, ws, out, step_now, closing && out.fu.a.step_dev != nullptr);
+    }
 #ifdef LNERF_STAMPS
     if (blockIdx.x < 4096) {   // (exit = the LAST wave's, with its stores acknowledged: the slot is free after that)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -572,7 +605,7 @@ k_scatter_reduce(GridMeta meta, BucketMeta bm, const int32_t *__restrict__ items
             asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
             g_wg_log[4 * blockIdx.x] = wg_t0;
             g_wg_log[4 * blockIdx.x + 2] = ((unsigned long long)xcc << 32) | hw;
-            g_wg_log[4 * blockIdx.x + 3] = (unsigned long long)(unsigned int)unit;
+            g_wg_log[4 * blockIdx.x + 3] = (unsigned long long)(unsigned int)(u.wg < 0 ? u.wg : u.wg - wg_lo);
         }
     }
 #endif
@@ -580,7 +613,7 @@ k_scatter_reduce(GridMeta meta, BucketMeta bm, const int32_t *__restrict__ items
         // (this wave is done.  The workgroup's other waves requested the counter as their first instruction and the
         // level maximum in front of the record loop; a workgroup's barriers wait for a wave's outstanding loads, and
         // a workgroup that leaves before its first barrier has not used either value)
-        tail_arrive(tj.arrive, (int)gridDim.x, (int)blockIdx.x, tj.tick, step_now, gmax, tj.do_tick, tj.clear_gmax);
+        tail_arrive(ws.arrive, (int)gridDim.x, (int)blockIdx.x, tj.tick, step_now, ws.gmax, tj.do_tick, tj.clear_gmax);
 }
 
 // the slab blocks + the closing arrival as a launch of their own (lnerf_step_tail)
@@ -621,7 +654,8 @@ int g_reduce_threads = 1024;
 // level groups of the whole-frame scatter: bin(group) -> reduce(group) per group (1 = bin everything, then reduce)
 int g_scatter_groups = 1;
 
-// workspace: [header: level maxima | item count | record count per bucket] [segment table] [record chunks] [partial tiles]
+// workspace: [header: level maxima | item count | arrival counters | unused] [segment table] [record chunks] [partial tiles]
+// (the header's last region, one word per bucket from HDR_BUCKETN_OFF on, is unused: it can go with the next ABI change)
 static_assert(BK_MAX_PER_LEVEL == 256 && HDR_BUCKETN_OFF <= LNERF_SCATTER_ZERO_HEAD_BYTES,
               "the counters of the header must lie inside the head a caller zeroes");
 static size_t header_bytes(int n_buckets) {
@@ -631,13 +665,12 @@ static size_t header_bytes(int n_buckets) {
 struct ScatterPlan {
     int buckets, wgs;   // buckets / pass-2 workgroups over all levels
     int ptiles;         // partial-sum tiles (sliced levels: buckets x slices)
-    int fbuckets;       // buckets of sliced levels (grid of the finishing pass)
     size_t header_bytes, seg_bytes, rec_bytes, partial_bytes;
     size_t total() const { return header_bytes + seg_bytes + rec_bytes + partial_bytes; }
 };
 
 static int fill_bucket_meta(const GridMeta &meta, int64_t m_host, BucketMeta &bm, ScatterPlan &plan) {
-    int total_buckets = 0, total_wgs = 0, total_ptiles = 0, total_fb = 0;
+    int total_buckets = 0, total_wgs = 0, total_ptiles = 0;
     const int64_t n_items = m_host > 0 ? div_up(m_host, (int64_t)ITEM_SAMPLES) : 1;
     if (n_items >= (1 << 19)) return -1;   // (pass 2 addresses a level's records with 32-bit record indices)
     for (int l = 0; l < meta.num_levels; ++l) {
@@ -654,11 +687,7 @@ static int fill_bucket_meta(const GridMeta &meta, int64_t m_host, BucketMeta &bm
         bm.compact[l] = meta.res[l] <= g_compact_max_res ? 1 : 0;
         bm.wgstart[l] = total_wgs;
         bm.pstart[l] = slices > 1 ? total_ptiles : -1;
-        bm.fstart[l] = slices > 1 ? total_fb : -1;
-        if (slices > 1) {
-            total_ptiles += nb * slices;
-            total_fb += nb;
-        }
+        if (slices > 1) total_ptiles += nb * slices;
         total_buckets += nb;
         total_wgs += nb * slices;
     }
@@ -675,7 +704,6 @@ static int fill_bucket_meta(const GridMeta &meta, int64_t m_host, BucketMeta &bm
     plan.buckets = total_buckets;
     plan.wgs = total_wgs;
     plan.ptiles = total_ptiles;
-    plan.fbuckets = total_fb;
     plan.header_bytes = header_bytes(total_buckets);
     plan.seg_bytes = ((size_t)total_buckets * (size_t)n_items * sizeof(uint32_t) + 4095) / 4096 * 4096;
     // one chunk of ITEM_RECS slots per (level, item): exactly what the item's samples can emit (sized for the 12-byte
@@ -683,6 +711,23 @@ static int fill_bucket_meta(const GridMeta &meta, int64_t m_host, BucketMeta &bm
     plan.rec_bytes = (size_t)meta.num_levels * (size_t)n_items * ITEM_RECS * sizeof(Rec12);
     plan.partial_bytes = (size_t)total_ptiles * BK_ROWS * 2 * sizeof(long long);
     return 0;
+}
+
+// the plan of a level table known by its offsets alone (what the two size queries are given); false: not plannable
+static bool plan_from_offsets(int num_levels, const int32_t *offsets_host, int64_t m_host, ScatterPlan &plan) {
+    if (num_levels < 1 || num_levels > LNERF_MAX_LEVELS || !offsets_host || m_host < 0) return false;
+    GridMeta meta = {};
+    meta.num_levels = num_levels;
+    for (int l = 0; l <= num_levels; ++l) meta.offsets[l] = offsets_host[l];
+    BucketMeta bm;
+    return fill_bucket_meta(meta, m_host, bm, plan) == 0;
+}
+
+// where the regions of a workspace are
+static ScatterWs scatter_ws(void *workspace, const ScatterPlan &plan) {
+    char *hdr = (char *)workspace, *seg = hdr + plan.header_bytes, *rec = seg + plan.seg_bytes;
+    return {(unsigned int *)hdr, (int32_t *)(hdr + HDR_ITEMS_OFF), (int32_t *)(hdr + HDR_ARRIVE_OFF),
+            (int32_t *)(hdr + HDR_SLICE_ARRIVE_OFF), (uint32_t *)seg, rec, (long long *)(rec + plan.rec_bytes)};
 }
 
 }  // namespace lnerf
@@ -777,225 +822,204 @@ int lnerf_debug_bin_stamps(unsigned long long *out16) {   // pass 1's totals (gr
 #endif
 
 size_t lnerf_grid_scatter_clear_bytes(int num_levels, const int32_t *offsets_host, int64_t m_host) {
-    if (num_levels < 1 || num_levels > LNERF_MAX_LEVELS || !offsets_host || m_host < 0) return 0;
-    GridMeta meta;
-    meta.num_levels = num_levels;
-    meta.blocked = 0;
-    for (int l = 0; l <= num_levels; ++l) meta.offsets[l] = offsets_host[l];
-    for (int l = 0; l < num_levels; ++l) meta.res[l] = 0;
-    BucketMeta bm;
     ScatterPlan plan;
-    if (fill_bucket_meta(meta, m_host, bm, plan) != 0) return 0;
+    if (!plan_from_offsets(num_levels, offsets_host, m_host, plan)) return 0;
     return HDR_GMAX_BYTES;   // the level maxima (pass 1 raises them with atomicMax)
 }
 
 size_t lnerf_grid_encode_backward_workspace_bytes(int num_levels, const int32_t *offsets_host, int64_t m_host) {
-    if (num_levels < 1 || num_levels > LNERF_MAX_LEVELS || !offsets_host || m_host < 0) return 0;
-    GridMeta meta;
-    meta.num_levels = num_levels;
-    meta.blocked = 0;
-    for (int l = 0; l <= num_levels; ++l) meta.offsets[l] = offsets_host[l];
-    for (int l = 0; l < num_levels; ++l) meta.res[l] = 0;
-    BucketMeta bm;
     ScatterPlan plan;
-    if (fill_bucket_meta(meta, m_host, bm, plan) != 0) return 0;
+    if (!plan_from_offsets(num_levels, offsets_host, m_host, plan)) return 0;
     return plan.total();  // header, segment table, record chunks, partial-sum tiles of the sliced levels
 }
 
-// fu == nullptr: dtable += scatter.  fu != nullptr: every row's Adam step is applied by whichever kernel finishes its
-// sum (pass 2 on unsliced levels, the finishing pass on sliced ones); dtable only carries overflow records.
-// phases: 1 = pass 1 (binning, all levels; clears the cursors), 2 = pass 2 + finishing pass of levels [lv_lo, lv_hi)
-static int scatter_backward(const float *xyzs, float bound, const void *dfeat, int dfeat_dtype, int num_levels,
-                            int level_dim, const int32_t *offsets_host, const float *scales_host,
-                            const int32_t *res_host, int64_t m_host, const int32_t *m_dev, int64_t level_stride,
-                            float *dtable, int variant, void *workspace, size_t workspace_bytes,
-                            lnerf_stream_t stream, FusedUpdate *fu, int phases = 3, int lv_lo = 0, int lv_hi = -1,
-                            const TailJob *tail = nullptr) {
+// One call of the scatter: the C ABI's common arguments in their order, then what only some entry points set.
+struct ScatterCall {
+    const float *xyzs; float bound; const void *dfeat; int dfeat_dtype;                                         // samples
+    int num_levels, level_dim; const int32_t *offsets_host; const float *scales_host; const int32_t *res_host;  // levels
+    int64_t m_host; const int32_t *m_dev; int64_t level_stride;
+    float *dtable; int variant; void *workspace; size_t workspace_bytes; lnerf_stream_t stream;
+    const FusedUpdate *fu = nullptr;   // set: every row's Adam step (or its bf16 wire output, fu->grad_out) is applied by the
+                                       // workgroup of pass 2 that finishes its bucket; not set: dtable += scatter
+    const TailJob *tail = nullptr;     // set: the launch of pass 2 closes the step
+    int phases = 3;                    // 1 = pass 1 (binning, all levels), 2 = pass 2 of levels [lv_lo, lv_hi)
+    int lv_lo = 0, lv_hi = -1;         // (-1: all levels)
+};
+
+static int scatter_backward(ScatterCall c) {
     // LNERF_SCATTER_CLEARED: the caller zeroed the head of the workspace (lnerf_grid_scatter_clear_bytes()) with
     // something it was launching anyway -- the fill dispatch of this call is skipped
-    const bool cleared = (variant & LNERF_SCATTER_CLEARED) != 0;
+    const bool cleared = (c.variant & LNERF_SCATTER_CLEARED) != 0;
     // (LNERF_SCATTER_DEFER_FINISH: accepted, without effect -- pass 2 finishes the sliced buckets itself)
-    const int blocked = variant & (LNERF_GRID_BLOCKED | LNERF_GRID_TILED);
-    variant &= ~(LNERF_SCATTER_CLEARED | LNERF_SCATTER_DEFER_FINISH | LNERF_GRID_BLOCKED | LNERF_GRID_TILED);
+    const int blocked = c.variant & (LNERF_GRID_BLOCKED | LNERF_GRID_TILED);
+    const int variant = c.variant & ~(LNERF_SCATTER_CLEARED | LNERF_SCATTER_DEFER_FINISH | LNERF_GRID_BLOCKED | LNERF_GRID_TILED);
+    const int num_levels = c.num_levels, phases = c.phases;
+    const int64_t m_host = c.m_host;
     GridMeta meta;
-    int rc = fill_meta("grid_encode_backward", meta, num_levels, level_dim, offsets_host, scales_host, res_host, blocked);
-    if (rc) return rc;
-    LNERF_REQUIRE(m_host >= 0 && level_stride >= m_host, "grid_encode_backward: need 0 <= m_host <= level_stride");
+    if (int rc = fill_meta("grid_encode_backward", meta, num_levels, c.level_dim, c.offsets_host, c.scales_host, c.res_host,
+                           blocked)) return rc;
+    LNERF_REQUIRE(m_host >= 0 && c.level_stride >= m_host, "grid_encode_backward: need 0 <= m_host <= level_stride");
     LNERF_REQUIRE(m_host < (1ll << 30), "grid_encode_backward: m_host must be below 2^30 samples");
     LNERF_REQUIRE(variant < 2 || m_host < (1ll << 28), "grid_encode_backward: the bucketed scatter takes m_host below 2^28");
-    LNERF_REQUIRE(bound > 0.f, "grid_encode_backward: bound must be > 0");
+    LNERF_REQUIRE(c.bound > 0.f, "grid_encode_backward: bound must be > 0");
     LNERF_REQUIRE(variant >= 0 && variant <= 3, "grid_encode_backward: unknown variant %d", variant);
-    LNERF_REQUIRE(dfeat_dtype == LNERF_F32, "grid_encode_backward: dfeat must be f32");
-    LNERF_REQUIRE(!fu || (variant >= 2 && m_host > 0), "grid_encode_backward_adam: needs variant 2/3 and m_host > 0");
+    LNERF_REQUIRE(c.dfeat_dtype == LNERF_F32, "grid_encode_backward: dfeat must be f32");
+    LNERF_REQUIRE(!c.fu || (variant >= 2 && m_host > 0), "grid_encode_backward_adam: needs variant 2/3 and m_host > 0");
     if (m_host == 0) return LNERF_OK;
-    LNERF_REQUIRE(dtable && (!(phases & 1) || (xyzs && dfeat)), "grid_encode_backward: null pointer");
-    if (lv_hi < 0) lv_hi = num_levels;
+    LNERF_REQUIRE(c.dtable && (!(phases & 1) || (c.xyzs && c.dfeat)), "grid_encode_backward: null pointer");
+    const int lv_lo = c.lv_lo, lv_hi = c.lv_hi < 0 ? num_levels : c.lv_hi;
     LNERF_REQUIRE(lv_lo >= 0 && lv_lo <= lv_hi && lv_hi <= num_levels, "grid_encode_backward: bad level range");
     LNERF_REQUIRE(phases == 3 || variant >= 2, "grid_encode_backward: the split form needs the bucketed scatter");
-    hipStream_t s = as_stream(stream);
+    hipStream_t s = as_stream(c.stream);
     if (variant < 2) {
-        launch_grid_backward_atomic(xyzs, bound, (const float *)dfeat, meta, m_host, m_dev, level_stride, dtable, variant, s);
+        launch_grid_backward_atomic(c.xyzs, c.bound, (const float *)c.dfeat, meta, m_host, c.m_dev, c.level_stride, c.dtable,
+                                    variant, s);
         LNERF_CHECK_LAUNCH("grid_encode_backward");
         return LNERF_OK;
     }
+    // plan -> pointers -> bin -> reduce
     BucketMeta bm;
     ScatterPlan plan;
     LNERF_REQUIRE(fill_bucket_meta(meta, m_host, bm, plan) == 0,
                   "grid_encode_backward: level too large for the bucketed scatter (use variant 0/1)");
-    const size_t need = plan.total();
-    LNERF_REQUIRE(workspace && workspace_bytes >= need, "grid_encode_backward: workspace too small (%zu < %zu)",
-                  workspace_bytes, need);
-    LNERF_REQUIRE(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)dtable & 15) == 0,
+    LNERF_REQUIRE(c.workspace && c.workspace_bytes >= plan.total(), "grid_encode_backward: workspace too small (%zu < %zu)",
+                  c.workspace_bytes, plan.total());
+    LNERF_REQUIRE(((uintptr_t)c.workspace & 15) == 0 && ((uintptr_t)c.dtable & 15) == 0,
                   "grid_encode_backward: workspace/dtable must be 16-byte aligned");
-    char *wsb = (char *)workspace;
-    unsigned int *gmax = (unsigned int *)wsb;
-    int32_t *items_dev = (int32_t *)(wsb + HDR_ITEMS_OFF);
-    int32_t *slice_arrive = (int32_t *)(wsb + HDR_SLICE_ARRIVE_OFF);
-    int32_t *bucket_n = (int32_t *)(wsb + HDR_BUCKETN_OFF);
-    uint32_t *segtab = (uint32_t *)(wsb + plan.header_bytes);
-    void *rec = wsb + plan.header_bytes + plan.seg_bytes;
-    long long *partials = (long long *)(wsb + plan.header_bytes + plan.seg_bytes + plan.rec_bytes);
-    const bool packed = variant == 3;
-    if ((phases & 1) && !cleared && hipMemsetAsync(gmax, 0, HDR_GMAX_BYTES, s) != hipSuccess) {
+    const ScatterWs ws = scatter_ws(c.workspace, plan);
+    const bool packed = variant == 3, whole = lv_lo == 0 && lv_hi == num_levels;
+    ReduceOut out = {};
+    out.dtable = c.dtable;
+    if (c.fu) out.fu = *c.fu;
+    TailJob tj = {};
+    if (c.tail) {
+        LNERF_REQUIRE(c.fu && !c.fu->grad_out && phases == 3 && whole && g_scatter_groups <= 1,
+                      "grid_encode_backward: the closing form needs the fused whole-table call");
+        tj = *c.tail;
+        tj.blocks = tj.sa.slabs ? (int)div_up(div_up(MLP_SLAB, TAIL_P), FUSED_RT / 256) : 0;   // four slab blocks per workgroup
+    }
+    if ((phases & 1) && !cleared && hipMemsetAsync(ws.gmax, 0, HDR_GMAX_BYTES, s) != hipSuccess) {
         set_error("grid_encode_backward: hipMemsetAsync failed");
         return LNERF_ERR_HIP;
     }
     auto launch_bin = [&](int l0, int l1) {   // pass 1 (grid_bin.hip)
-        launch_scatter_bin(packed, xyzs, bound, (const float *)dfeat, meta, bm, m_host, m_dev, level_stride, gmax, items_dev,
-                           segtab, rec, l0, l1, s);
+        launch_scatter_bin(packed, c.xyzs, c.bound, (const float *)c.dfeat, meta, bm, m_host, c.m_dev, c.level_stride, ws.gmax,
+                           ws.items_dev, ws.segtab, ws.recs, l0, l1, s);
     };
-    FusedUpdate fu0;
-    memset(&fu0, 0, sizeof(fu0));
-    if (fu) fu0 = *fu;
-    TailJob tj0;
-    memset(&tj0, 0, sizeof(tj0));
-    if (tail) {
-        LNERF_REQUIRE(fu && !fu->grad_out && phases == 3 && lv_lo == 0 && lv_hi == num_levels && g_scatter_groups <= 1,
-                      "grid_encode_backward: the closing form needs the fused whole-table call");
-        tj0 = *tail;
-        tj0.arrive = (int32_t *)(wsb + HDR_ARRIVE_OFF);
-        tj0.blocks = tj0.sa.slabs ? (int)div_up(div_up(MLP_SLAB, TAIL_P), FUSED_RT / 256) : 0;   // four slab blocks per workgroup
-    }
-    {   // the un-sliced levels heaviest first (whole-table launches only: a level-range launch keeps the plain order)
-        int lf = 0;
-        for (int l = 0; l < num_levels; ++l) if (bm.slices[l] > 1) lf = l + 1;
-        tj0.rev_lo = bm.wgstart[lf];
-        tj0.rev_hi = bm.wgstart[num_levels];
-    }
-    auto launch_reduce = [&](hipStream_t st, int l0, int l1) {
+    auto launch_reduce = [&](int l0, int l1) {   // pass 2 of levels [l0, l1)
         const int w0 = bm.wgstart[l0], w1 = bm.wgstart[l1];
-        if (l0 != 0 || l1 != num_levels) { tj0.rev_lo = tj0.rev_hi = 0; }
-        if (w1 <= w0 && tj0.blocks == 0) return;
-#define LAUNCH_RED(T, REC, FUSE)                                                                                  \
-    hipLaunchKernelGGL((k_scatter_reduce<T, REC, FUSE>), dim3((unsigned)(w1 - w0 + (FUSE ? tj0.blocks : 0))), dim3(T), 0,  \
-                       st, meta, bm, items_dev, segtab, bucket_n, slice_arrive, gmax, (const REC *)rec, dtable, partials, \
-                       w0, fu0, tj0)
-        // (the fused pass with 512-thread workgroups: 118 us against 108, profiles/r03_exp_scatter.jsonl)
-        if (fu && packed) LAUNCH_RED(FUSED_RT, Rec8, true);
-        else if (fu) LAUNCH_RED(FUSED_RT, Rec12, true);
-        else if (packed && g_reduce_threads == 512) LAUNCH_RED(512, Rec8, false);
-        else if (packed) LAUNCH_RED(1024, Rec8, false);
-        else if (g_reduce_threads == 512) LAUNCH_RED(512, Rec12, false);
-        else LAUNCH_RED(1024, Rec12, false);
-#undef LAUNCH_RED
-    };
-    if (phases == 3 && g_scatter_groups > 1 && lv_lo == 0 && lv_hi == num_levels) {
-        // level GROUPS: bin(group) -> reduce(group) -> bin(next group) ...  A group's records (1/groups of the 216 MB a
-        // frame writes) are read back right behind their writes, while they still sit in the 256 MiB Infinity Cache:
-        // the whole-frame form streams them out to HBM and back.  Measured slower at every group count, and slower
-        // still with reduce(g) on a side stream beside bin(g + 1): default 1
-        const int ng = g_scatter_groups < num_levels ? g_scatter_groups : num_levels;
-        for (int gi = 0; gi < ng; ++gi) {
-            const int l0 = (int)((int64_t)num_levels * gi / ng), l1 = (int)((int64_t)num_levels * (gi + 1) / ng);
-            launch_bin(l0, l1);
-            LNERF_CHECK_LAUNCH("grid_encode_backward(bin)");
-            launch_reduce(s, l0, l1);
-            LNERF_CHECK_LAUNCH("grid_encode_backward(reduce)");
+        // the un-sliced levels heaviest first (whole-table launches only: a level-range launch keeps the plain order)
+        tj.rev_lo = tj.rev_hi = 0;
+        if (l0 == 0 && l1 == num_levels) {
+            int lf = 0;
+            for (int l = 0; l < num_levels; ++l) if (bm.slices[l] > 1) lf = l + 1;
+            tj.rev_lo = bm.wgstart[lf];
+            tj.rev_hi = bm.wgstart[num_levels];
         }
-        return LNERF_OK;
-    }
-    if (phases & 1) {
-        launch_bin(0, num_levels);
-        LNERF_CHECK_LAUNCH("grid_encode_backward(bin)");
-    }
-    if (phases & 2) {
-        launch_reduce(s, lv_lo, lv_hi);
-        LNERF_CHECK_LAUNCH("grid_encode_backward(reduce)");
+        if (w1 <= w0 && tj.blocks == 0) return;
+        // (the fused pass with 512-thread workgroups: 118 us against 108, profiles/r03_exp_scatter.jsonl)
+        const int rt = c.fu ? FUSED_RT : g_reduce_threads == 512 ? 512 : 1024;
+        void (*const k)(GridMeta, BucketMeta, ScatterWs, ReduceOut, int, TailJob) =
+            c.fu ? (packed ? k_scatter_reduce<FUSED_RT, Rec8, true> : k_scatter_reduce<FUSED_RT, Rec12, true>)
+            : rt == 512 ? (packed ? k_scatter_reduce<512, Rec8, false> : k_scatter_reduce<512, Rec12, false>)
+                        : (packed ? k_scatter_reduce<1024, Rec8, false> : k_scatter_reduce<1024, Rec12, false>);
+        hipLaunchKernelGGL(k, dim3((unsigned)(w1 - w0 + tj.blocks)), dim3(rt), 0, s, meta, bm, ws, out, w0, tj);
+    };
+    // level GROUPS (whole-table calls with scatter_level_groups > 1): bin(group) -> reduce(group) -> bin(next group) ...  A
+    // group's records (1/groups of the 216 MB a frame writes) are read back right behind their writes, while they still sit
+    // in the 256 MiB Infinity Cache: the whole-frame form streams them out to HBM and back.  Measured slower at every group
+    // count, and slower still with reduce(g) on a side stream beside bin(g + 1): default 1
+    const bool grouped = phases == 3 && g_scatter_groups > 1 && whole;
+    const int ng = !grouped ? 1 : g_scatter_groups < num_levels ? g_scatter_groups : num_levels;
+    for (int gi = 0; gi < ng; ++gi) {
+        const int l0 = (int)((int64_t)num_levels * gi / ng), l1 = (int)((int64_t)num_levels * (gi + 1) / ng);
+        if (phases & 1) launch_bin(l0, l1);   // (not grouped: all levels)
+        if (phases & 1) LNERF_CHECK_LAUNCH("grid_encode_backward(bin)");
+        if (phases & 2) launch_reduce(grouped ? l0 : lv_lo, grouped ? l1 : lv_hi);
+        if (phases & 2) LNERF_CHECK_LAUNCH("grid_encode_backward(reduce)");
     }
     return LNERF_OK;
 }
 
 int lnerf_grid_encode_backward(const float *xyzs, float bound, const void *dfeat, int dfeat_dtype, int num_levels,
-                               int level_dim, const int32_t *offsets_host, const float *scales_host,
-                               const int32_t *res_host, int64_t m_host, const int32_t *m_dev, int64_t level_stride,
-                               float *dtable, int variant, void *workspace, size_t workspace_bytes,
-                               lnerf_stream_t stream) {
-    return scatter_backward(xyzs, bound, dfeat, dfeat_dtype, num_levels, level_dim, offsets_host, scales_host, res_host,
-                            m_host, m_dev, level_stride, dtable, variant, workspace, workspace_bytes, stream, nullptr);
+                               int level_dim, const int32_t *offsets_host, const float *scales_host, const int32_t *res_host,
+                               int64_t m_host, const int32_t *m_dev, int64_t level_stride, float *dtable, int variant,
+                               void *workspace, size_t workspace_bytes, lnerf_stream_t stream) {
+    return scatter_backward({xyzs, bound, dfeat, dfeat_dtype, num_levels, level_dim, offsets_host, scales_host, res_host,
+                             m_host, m_dev, level_stride, dtable, variant, workspace, workspace_bytes, stream});
+}
+
+// the wire mode's checks and its descriptor (the Adam arguments are unused in this mode)
+static int fill_wire_output(const char *who, FusedUpdate &fu, void *grad_bf16, const float *dtable_zero) {
+    LNERF_REQUIRE(grad_bf16 && dtable_zero, "%s: null output", who);
+    LNERF_REQUIRE((((uintptr_t)grad_bf16 | (uintptr_t)dtable_zero) & 15) == 0, "%s: buffers must be 16-byte aligned", who);
+    memset(&fu, 0, sizeof(fu));
+    adam_host_args(fu.a, 0.f, 0.5f, 0.5f, 1.f, 1, nullptr, 1.f, 0);
+    fu.grad_out = (uint16_t *)grad_bf16;
+    return LNERF_OK;
 }
 
 int lnerf_grid_encode_backward_bf16(const float *xyzs, float bound, const void *dfeat, int dfeat_dtype, int num_levels,
                                     int level_dim, const int32_t *offsets_host, const float *scales_host,
-                                    const int32_t *res_host, int64_t m_host, const int32_t *m_dev,
-                                    int64_t level_stride, float *dtable_zero, int variant, void *workspace,
-                                    size_t workspace_bytes, void *grad_bf16, lnerf_stream_t stream) {
-    LNERF_REQUIRE(grad_bf16 && dtable_zero, "grid_encode_backward_bf16: null output");
-    LNERF_REQUIRE((((uintptr_t)grad_bf16 | (uintptr_t)dtable_zero) & 15) == 0,
-                  "grid_encode_backward_bf16: buffers must be 16-byte aligned");
+                                    const int32_t *res_host, int64_t m_host, const int32_t *m_dev, int64_t level_stride,
+                                    float *dtable_zero, int variant, void *workspace, size_t workspace_bytes,
+                                    void *grad_bf16, lnerf_stream_t stream) {
     FusedUpdate fu;
-    memset(&fu, 0, sizeof(fu));
-    adam_host_args(fu.a, 0.f, 0.5f, 0.5f, 1.f, 1, nullptr, 1.f, 0);  // (unused in this mode)
-    fu.grad_out = (uint16_t *)grad_bf16;
-    return scatter_backward(xyzs, bound, dfeat, dfeat_dtype, num_levels, level_dim, offsets_host, scales_host, res_host,
-                            m_host, m_dev, level_stride, dtable_zero, variant, workspace, workspace_bytes, stream, &fu);
+    if (int rc = fill_wire_output("grid_encode_backward_bf16", fu, grad_bf16, dtable_zero)) return rc;
+    return scatter_backward({xyzs, bound, dfeat, dfeat_dtype, num_levels, level_dim, offsets_host, scales_host, res_host,
+                             m_host, m_dev, level_stride, dtable_zero, variant, workspace, workspace_bytes, stream, &fu});
 }
 
-int lnerf_grid_scatter_bin(const float *xyzs, float bound, const void *dfeat, int dfeat_dtype, int num_levels,
-                           int level_dim, const int32_t *offsets_host, const float *scales_host, const int32_t *res_host,
-                           int64_t m_host, const int32_t *m_dev, int64_t level_stride, float *dtable_zero, int variant,
-                           void *workspace, size_t workspace_bytes, lnerf_stream_t stream) {
+int lnerf_grid_scatter_bin(const float *xyzs, float bound, const void *dfeat, int dfeat_dtype, int num_levels, int level_dim,
+                           const int32_t *offsets_host, const float *scales_host, const int32_t *res_host, int64_t m_host,
+                           const int32_t *m_dev, int64_t level_stride, float *dtable_zero, int variant, void *workspace,
+                           size_t workspace_bytes, lnerf_stream_t stream) {
     LNERF_REQUIRE(dtable_zero, "grid_scatter_bin: null output");
-    return scatter_backward(xyzs, bound, dfeat, dfeat_dtype, num_levels, level_dim, offsets_host, scales_host, res_host,
-                            m_host, m_dev, level_stride, dtable_zero, variant, workspace, workspace_bytes, stream, nullptr,
-                            1);
+    ScatterCall c = {xyzs, bound, dfeat, dfeat_dtype, num_levels, level_dim, offsets_host, scales_host, res_host,
+                     m_host, m_dev, level_stride, dtable_zero, variant, workspace, workspace_bytes, stream};
+    c.phases = 1;
+    return scatter_backward(c);
 }
 
 int lnerf_grid_scatter_reduce_bf16(float bound, int num_levels, int level_dim, const int32_t *offsets_host,
-                                   const float *scales_host, const int32_t *res_host, int64_t m_host,
-                                   int64_t level_stride, int level_lo, int level_hi, float *dtable_zero, int variant,
-                                   void *workspace, size_t workspace_bytes, void *grad_bf16, lnerf_stream_t stream) {
-    LNERF_REQUIRE(grad_bf16 && dtable_zero, "grid_scatter_reduce_bf16: null output");
-    LNERF_REQUIRE((((uintptr_t)grad_bf16 | (uintptr_t)dtable_zero) & 15) == 0,
-                  "grid_scatter_reduce_bf16: buffers must be 16-byte aligned");
+                                   const float *scales_host, const int32_t *res_host, int64_t m_host, int64_t level_stride,
+                                   int level_lo, int level_hi, float *dtable_zero, int variant, void *workspace,
+                                   size_t workspace_bytes, void *grad_bf16, lnerf_stream_t stream) {
     FusedUpdate fu;
+    if (int rc = fill_wire_output("grid_scatter_reduce_bf16", fu, grad_bf16, dtable_zero)) return rc;
+    ScatterCall c = {nullptr, bound, nullptr, LNERF_F32, num_levels, level_dim, offsets_host, scales_host, res_host,
+                     m_host, nullptr, level_stride, dtable_zero, variant, workspace, workspace_bytes, stream, &fu};
+    c.phases = 2; c.lv_lo = level_lo; c.lv_hi = level_hi;
+    return scatter_backward(c);
+}
+
+// what the Adam-mode entry points check alike (behind their own checks of the step), and the kernel-side descriptor
+static int fill_fused_adam(const char *who, FusedUpdate &fu, float *table, float *exp_avg, float *exp_avg_sq,
+                           const float *dtable_zero, void *shadow_bf16, float lr, float beta1, float beta2, float eps,
+                           int step, const int32_t *step_dev, float grad_scale) {
+    LNERF_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "%s: betas must be in [0,1)", who);
+    LNERF_REQUIRE((((uintptr_t)table | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)dtable_zero) & 15) == 0,
+                  "%s: buffers must be 16-byte aligned", who);
+    LNERF_REQUIRE(!shadow_bf16 || ((uintptr_t)shadow_bf16 & 7) == 0, "%s: shadow must be 8-byte aligned", who);
     memset(&fu, 0, sizeof(fu));
-    adam_host_args(fu.a, 0.f, 0.5f, 0.5f, 1.f, 1, nullptr, 1.f, 0);  // (unused in this mode)
-    fu.grad_out = (uint16_t *)grad_bf16;
-    return scatter_backward(nullptr, bound, nullptr, LNERF_F32, num_levels, level_dim, offsets_host, scales_host, res_host,
-                            m_host, nullptr, level_stride, dtable_zero, variant, workspace, workspace_bytes, stream, &fu, 2,
-                            level_lo, level_hi);
+    fu.p = table; fu.m = exp_avg; fu.v = exp_avg_sq; fu.shadow = (uint16_t *)shadow_bf16;
+    adam_host_args(fu.a, lr, beta1, beta2, eps, step, step_dev, grad_scale, 0);
+    return LNERF_OK;
 }
 
 int lnerf_grid_encode_backward_adam(const float *xyzs, float bound, const void *dfeat, int dfeat_dtype, int num_levels,
                                     int level_dim, const int32_t *offsets_host, const float *scales_host,
-                                    const int32_t *res_host, int64_t m_host, const int32_t *m_dev,
-                                    int64_t level_stride, float *dtable_zero, int variant, void *workspace,
-                                    size_t workspace_bytes, float *table, float *exp_avg, float *exp_avg_sq,
-                                    void *shadow_bf16, float lr, float beta1, float beta2, float eps, int step,
-                                    const int32_t *step_dev, float grad_scale, lnerf_stream_t stream) {
+                                    const int32_t *res_host, int64_t m_host, const int32_t *m_dev, int64_t level_stride,
+                                    float *dtable_zero, int variant, void *workspace, size_t workspace_bytes, float *table,
+                                    float *exp_avg, float *exp_avg_sq, void *shadow_bf16, float lr, float beta1, float beta2,
+                                    float eps, int step, const int32_t *step_dev, float grad_scale, lnerf_stream_t stream) {
     LNERF_REQUIRE(table && exp_avg && exp_avg_sq, "grid_encode_backward_adam: null optimiser state");
     LNERF_REQUIRE(step_dev || step >= 1, "grid_encode_backward_adam: step must be >= 1 (got %d)", step);
-    LNERF_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f,
-                  "grid_encode_backward_adam: betas must be in [0,1)");
-    LNERF_REQUIRE((((uintptr_t)table | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)dtable_zero) & 15) == 0,
-                  "grid_encode_backward_adam: buffers must be 16-byte aligned");
-    LNERF_REQUIRE(!shadow_bf16 || ((uintptr_t)shadow_bf16 & 7) == 0, "grid_encode_backward_adam: shadow must be 8-byte aligned");
     FusedUpdate fu;
-    fu.p = table; fu.m = exp_avg; fu.v = exp_avg_sq; fu.shadow = (uint16_t *)shadow_bf16;
-    fu.grad_out = nullptr;
-    adam_host_args(fu.a, lr, beta1, beta2, eps, step, step_dev, grad_scale, 0);
-    return scatter_backward(xyzs, bound, dfeat, dfeat_dtype, num_levels, level_dim, offsets_host, scales_host, res_host,
-                            m_host, m_dev, level_stride, dtable_zero, variant, workspace, workspace_bytes, stream, &fu);
+    if (int rc = fill_fused_adam("grid_encode_backward_adam", fu, table, exp_avg, exp_avg_sq, dtable_zero, shadow_bf16, lr, beta1,
+                                 beta2, eps, step, step_dev, grad_scale)) return rc;
+    return scatter_backward({xyzs, bound, dfeat, dfeat_dtype, num_levels, level_dim, offsets_host, scales_host, res_host,
+                             m_host, m_dev, level_stride, dtable_zero, variant, workspace, workspace_bytes, stream, &fu});
 }
 
 // the MLP half of a step tail: argument checks + the kernel-side descriptor
@@ -1029,41 +1053,30 @@ static int fill_slab_adam(const char *who, SlabAdam &sa, const void *mlp_workspa
 
 int lnerf_grid_encode_backward_adam_tail(const float *xyzs, float bound, const void *dfeat, int dfeat_dtype, int num_levels,
                                          int level_dim, const int32_t *offsets_host, const float *scales_host,
-                                         const int32_t *res_host, int64_t m_host, const int32_t *m_dev,
-                                         int64_t level_stride, float *dtable_zero, int variant, void *workspace,
-                                         size_t workspace_bytes, float *table, float *exp_avg, float *exp_avg_sq,
-                                         void *shadow_bf16, float lr, const void *mlp_workspace,
-                                         size_t mlp_workspace_bytes, int mlp_precision, int out_dim,
-                                         float *const *params_host, float *const *exp_avg_host,
+                                         const int32_t *res_host, int64_t m_host, const int32_t *m_dev, int64_t level_stride,
+                                         float *dtable_zero, int variant, void *workspace, size_t workspace_bytes,
+                                         float *table, float *exp_avg, float *exp_avg_sq, void *shadow_bf16, float lr,
+                                         const void *mlp_workspace, size_t mlp_workspace_bytes, int mlp_precision,
+                                         int out_dim, float *const *params_host, float *const *exp_avg_host,
                                          float *const *exp_avg_sq_host, float mlp_lr, const int32_t *const *maps_host,
                                          float beta1, float beta2, float eps, int step, int32_t *step_dev, float grad_scale,
                                          int flags, lnerf_stream_t stream) {
     LNERF_REQUIRE(table && exp_avg && exp_avg_sq, "grid_encode_backward_adam_tail: null optimiser state");
     LNERF_REQUIRE(step_dev, "grid_encode_backward_adam_tail: needs the device counter pair (int32[2])");
     LNERF_REQUIRE(m_host > 0, "grid_encode_backward_adam_tail: needs m_host > 0 (use lnerf_step_tail for an empty frame)");
-    LNERF_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f,
-                  "grid_encode_backward_adam_tail: betas must be in [0,1)");
-    LNERF_REQUIRE((((uintptr_t)table | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)dtable_zero) & 15) == 0,
-                  "grid_encode_backward_adam_tail: buffers must be 16-byte aligned");
-    LNERF_REQUIRE(!shadow_bf16 || ((uintptr_t)shadow_bf16 & 7) == 0,
-                  "grid_encode_backward_adam_tail: shadow must be 8-byte aligned");
     FusedUpdate fu;
-    fu.p = table; fu.m = exp_avg; fu.v = exp_avg_sq; fu.shadow = (uint16_t *)shadow_bf16;
-    fu.grad_out = nullptr;
-    adam_host_args(fu.a, lr, beta1, beta2, eps, step, step_dev, grad_scale, 0);
-    TailJob tj;
-    memset(&tj, 0, sizeof(tj));
+    if (int rc = fill_fused_adam("grid_encode_backward_adam_tail", fu, table, exp_avg, exp_avg_sq, dtable_zero, shadow_bf16, lr,
+                                 beta1, beta2, eps, step, step_dev, grad_scale)) return rc;
+    TailJob tj = {};
     if (mlp_workspace) {
-        int rc = fill_slab_adam("grid_encode_backward_adam_tail", tj.sa, mlp_workspace, mlp_workspace_bytes, mlp_precision,
-                                out_dim, m_host, params_host, exp_avg_host, exp_avg_sq_host, mlp_lr, maps_host);
-        if (rc) return rc;
+        if (int rc = fill_slab_adam("grid_encode_backward_adam_tail", tj.sa, mlp_workspace, mlp_workspace_bytes, mlp_precision,
+                                    out_dim, m_host, params_host, exp_avg_host, exp_avg_sq_host, mlp_lr, maps_host)) return rc;
     }
     tj.tick = step_dev;
     tj.do_tick = (flags & LNERF_TAIL_TICK) ? 1 : 0;
     tj.clear_gmax = (flags & LNERF_TAIL_CLEAR_SCATTER) ? 1 : 0;
-    return scatter_backward(xyzs, bound, dfeat, dfeat_dtype, num_levels, level_dim, offsets_host, scales_host, res_host,
-                            m_host, m_dev, level_stride, dtable_zero, variant, workspace, workspace_bytes, stream, &fu, 3, 0,
-                            -1, &tj);
+    return scatter_backward({xyzs, bound, dfeat, dfeat_dtype, num_levels, level_dim, offsets_host, scales_host, res_host,
+                             m_host, m_dev, level_stride, dtable_zero, variant, workspace, workspace_bytes, stream, &fu, &tj});
 }
 
 int lnerf_step_tail(int num_levels, int level_dim, const int32_t *offsets_host, const float *scales_host,
@@ -1079,41 +1092,30 @@ int lnerf_step_tail(int num_levels, int level_dim, const int32_t *offsets_host, 
     LNERF_REQUIRE(!(flags & (LNERF_TAIL_TICK | LNERF_TAIL_CLEAR_SCATTER)) || step_dev,
                   "step_tail: the tick / the clearing epilogue need the device counter pair (int32[2])");
     LNERF_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "step_tail: betas must be in [0,1)");
-    GridMeta meta;
-    BucketMeta bm;
-    ScatterPlan plan;
-    memset(&meta, 0, sizeof(meta));
-    memset(&bm, 0, sizeof(bm));
-    memset(&plan, 0, sizeof(plan));
-    FusedUpdate fu;
-    memset(&fu, 0, sizeof(fu));
-    adam_host_args(fu.a, table_lr, beta1, beta2, eps, step, step_dev, grad_scale, 0);
-    unsigned int *gmax = nullptr;
-    int32_t *arrive = nullptr;
-    const bool packed = (variant & 0xFF) == 3;
+    AdamArgs a;   // (the table's: k_step_tail takes the step and the bias corrections from it)
+    adam_host_args(a, table_lr, beta1, beta2, eps, step, step_dev, grad_scale, 0);
+    ScatterWs ws = {};
     if (with_scatter) {
-        int rc = fill_meta("step_tail", meta, num_levels, level_dim, offsets_host, scales_host, res_host);
-        if (rc) return rc;
-        LNERF_REQUIRE(((variant & 0xFF) == 2 || packed) && m_host > 0, "step_tail: needs scatter variant 2 / 3 and m_host > 0");
+        GridMeta meta;
+        BucketMeta bm;
+        ScatterPlan plan;
+        if (int rc = fill_meta("step_tail", meta, num_levels, level_dim, offsets_host, scales_host, res_host)) return rc;
+        const int v = variant & 0xFF;
+        LNERF_REQUIRE((v == 2 || v == 3) && m_host > 0, "step_tail: needs scatter variant 2 / 3 and m_host > 0");
         LNERF_REQUIRE(fill_bucket_meta(meta, m_host, bm, plan) == 0, "step_tail: level too large for the bucketed scatter");
         LNERF_REQUIRE(scatter_workspace && scatter_workspace_bytes >= plan.total(), "step_tail: scatter workspace too small");
         LNERF_REQUIRE(table && exp_avg && exp_avg_sq && dtable_zero, "step_tail: null optimiser state");
         LNERF_REQUIRE((((uintptr_t)table | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)scatter_workspace) & 15) == 0,
                       "step_tail: buffers must be 16-byte aligned");
-        char *wsb = (char *)scatter_workspace;
-        gmax = (unsigned int *)wsb;
-        arrive = (int32_t *)(wsb + HDR_ARRIVE_OFF);
-        fu.p = table; fu.m = exp_avg; fu.v = exp_avg_sq; fu.shadow = (uint16_t *)shadow_bf16;
+        ws = scatter_ws(scatter_workspace, plan);
     }
     LNERF_REQUIRE(!(flags & (LNERF_TAIL_CLEAR_SCATTER | LNERF_TAIL_TICK)) || with_scatter,
                   "step_tail: the tick / the clearing epilogue keep their arrival counters in the scatter workspace");
-    SlabAdam sa;
-    memset(&sa, 0, sizeof(sa));
+    SlabAdam sa = {};
     int n_slab_blocks = 0;
     if (with_mlp) {
-        int rc = fill_slab_adam("step_tail", sa, mlp_workspace, mlp_workspace_bytes, mlp_precision, out_dim, m_host,
-                                params_host, exp_avg_host, exp_avg_sq_host, mlp_lr, maps_host);
-        if (rc) return rc;
+        if (int rc = fill_slab_adam("step_tail", sa, mlp_workspace, mlp_workspace_bytes, mlp_precision, out_dim, m_host,
+                                    params_host, exp_avg_host, exp_avg_sq_host, mlp_lr, maps_host)) return rc;
         n_slab_blocks = (int)div_up(MLP_SLAB, TAIL_P);
     }
     const int do_tick = (flags & LNERF_TAIL_TICK) ? 1 : 0, clr = (flags & LNERF_TAIL_CLEAR_SCATTER) ? 1 : 0;
@@ -1122,8 +1124,7 @@ int lnerf_step_tail(int num_levels, int level_dim, const int32_t *offsets_host, 
     if (n_slab_blocks == 0 && (do_tick || clr)) n_slab_blocks = 1;
     const dim3 g((unsigned)n_slab_blocks);
     if (g.x == 0) return LNERF_OK;
-    hipStream_t s = as_stream(stream);
-    hipLaunchKernelGGL(k_step_tail, g, dim3(256), 0, s, gmax, fu.a, sa, step_dev, arrive, do_tick, clr);
+    hipLaunchKernelGGL(k_step_tail, g, dim3(256), 0, as_stream(stream), ws.gmax, a, sa, step_dev, ws.arrive, do_tick, clr);
     LNERF_CHECK_LAUNCH("step_tail");
     return LNERF_OK;
 }

@@ -284,7 +284,7 @@ constexpr int CUR_STRIDE = 32;
 constexpr int ITEM_SAMPLES = 512;                 // samples per work item of pass 1 (= threads per workgroup)
 constexpr int ITEM_RECS = ITEM_SAMPLES * 8;       // record slots of an item's chunk
 // workspace header (bytes): [0, HDR_GMAX) level maxima (cleared before pass 1), then the item count of the last pass 1,
-// then one record count per bucket (written by pass 2 for the finishing pass)
+// the arrival counters, then one word per bucket that nothing uses any more (it keeps the header's size)
 constexpr size_t HDR_GMAX_BYTES = (size_t)LNERF_MAX_LEVELS * CUR_STRIDE * sizeof(uint32_t);
 constexpr size_t HDR_ITEMS_OFF = HDR_GMAX_BYTES;            // int32 [1] (+ padding to 128 bytes)
 constexpr size_t HDR_ARRIVE_OFF = HDR_GMAX_BYTES + 128;     // int32 [9 x CUR_STRIDE]: arrival counters of the step's tail
@@ -301,8 +301,7 @@ struct BucketMeta {
     int slices[LNERF_MAX_LEVELS];        // pass-2 workgroups per bucket (worst case; the active count is decided on the device)
     int compact[LNERF_MAX_LEVELS];       // 1: merge runs of equal rows inside a wavefront before binning
     int wgstart[LNERF_MAX_LEVELS + 1];   // first pass-2 workgroup of the level
-    int pstart[LNERF_MAX_LEVELS];        // sliced levels: first partial-sum tile of the level (pass 2 -> finish)
-    int fstart[LNERF_MAX_LEVELS];        // sliced levels: first bucket index in the finishing pass's grid
+    int pstart[LNERF_MAX_LEVELS];        // sliced levels: first partial-sum tile of the level (slice -> last arriver)
     int n_items;                         // item capacity: ceil(m_host / ITEM_SAMPLES)
     int fix_bits;                        // exact 12-byte records: bits of the fixed-point addends (<= 44), chosen so that
                                          // m_host addends of the level's bound cannot overflow an int64 (see fix_scale)

@@ -190,9 +190,9 @@ class FusedTableUpdate:
         self.zero = torch.zeros_like(exp_avg)  # dtable scratch argument of the fused entry points (never written)
         self.applied = 0                    # fused updates since the last optimizer.step()
         self.armed = False
-        # tail mode (FusedAdam(tail=True)): the armed backward leaves the finishing pass of the scatter and the sum of
-        # the MLP's gradient slabs to ONE launch in optimizer.step() (lnerf_step_tail), which also steps the MLP's
-        # parameters, ticks the step counter and leaves the scatter's level maxima zero for the next step
+        # tail mode (FusedAdam(tail=True)): the armed backward leaves the sum of the MLP's gradient slabs to ONE launch
+        # in optimizer.step() (lnerf_step_tail), which also steps the MLP's parameters, ticks the step counter and
+        # leaves the scatter's level maxima zero for the next step
         self.tail = False
         self.pending_tail = None            # (levels, m_host, variant, scatter workspace, mlp workspace, precision, out_dim)
         # the armed backward closed the step itself (grid_encode_backward_adam_tail): slab sums, the MLP's Adam step, the
@@ -295,7 +295,7 @@ def grid_encode_backward_bf16(xyzs, bound, dfeat, encoder, m_host, m_dev, level_
 
 
 def grid_scatter_reduce_group(sink: GradSink, level_lo, level_hi):
-    """Pass 2 (+ finishing pass) of levels [level_lo, level_hi) of the backward that sink.pending describes: writes rows
+    """Pass 2 of levels [level_lo, level_hi) of the backward that sink.pending describes: writes rows
     offsets[level_lo] .. offsets[level_hi] of sink.wire."""
     if sink.pending is None:
         raise _b.LnerfError("no binned backward pass is pending on this gradient sink")

@@ -17,7 +17,7 @@ F32, BF16 = 0, 1
 MLP_FRAGMENTS_READY = 0x100   # flag on lnerf_mlp_backward's precision tag (include/lnerf_hip.h)
 SCATTER_ZERO_HEAD_BYTES = 64 * 1024  # LNERF_SCATTER_ZERO_HEAD_BYTES: head of a fresh scatter workspace that must be zero
 MLP_FRAGMENT_BYTES = 36 * 1024  # LNERF_MLP_FRAGMENT_BYTES: the bf16 weight-fragment image at the head of the MLP workspace
-SCATTER_DEFER_FINISH = 0x200  # flag on the scatter's variant: lnerf_step_tail runs the finishing pass
+SCATTER_DEFER_FINISH = 0x200  # flag on the scatter's variant: accepted and ignored (pass 2 finishes the sliced buckets itself)
 MLP_DEFER_REDUCE = 0x200      # flag on lnerf_mlp_backward's precision tag: lnerf_step_tail sums the slabs
 TAIL_TICK, TAIL_CLEAR_SCATTER = 1, 2
 GRID_BLOCKED = 0x400          # flag on the gather's / scatter's variant: blocked layout of the hashed levels

@@ -153,6 +153,24 @@ def exact_case(gridtype):
     return dict(J=J, x=x, table=table, grad=grad, lv=lv, feat=feat, dtable=dtable, dxyz=dxyz)
 
 
+@functools.lru_cache(maxsize=None)
+def first_ray_case(gridtype):
+    """The exact inputs with m_dev = EXACT_PER_RAY: only the first ray is scattered, so most buckets receive NO record.
+    dict(dtable, empty): the float64 oracle with the gradient rows >= EXACT_PER_RAY zeroed, and per level the list of
+    (first row, one past the last row) of its buckets of 4096 rows that no non-zero record reaches (sum of |w g|)."""
+    _, x, table, grad = exact_inputs()
+    g1 = grad.clone()
+    g1[EXACT_PER_RAY:] = 0.0
+    lv = exact_oracle_levels(gridtype)
+    _, dtable = oracle_forward_backward(x, table, g1, lv, torch.float64)
+    _, dabs = oracle_forward_backward(x, torch.zeros_like(table), g1.abs(), lv, torch.float64)
+    empty = []
+    for a, b in zip(EXACT_OFFSETS[:-1], EXACT_OFFSETS[1:]):
+        spans = [(r, min(r + 4096, b)) for r in range(a, b, 4096)]
+        empty.append([s for s in spans if float(dabs[s[0]:s[1]].sum()) == 0.0])
+    return dict(dtable=dtable, empty=empty)
+
+
 def level_major(g, L, stride):
     """[M, 2 L] sample-major -> [L, stride, 2] level-major (rows >= M zero)."""
     M = g.shape[0]

@@ -180,8 +180,16 @@ def test_cross_workgroup_handoffs_are_scoped_accesses():
     agent-scope fence (an L2 write-back / invalidate per workgroup: 2.6 x the pass's time) has crept in."""
     import re
     asm = _device_asm("grid.hip")
-    kernels = re.findall(r"^(_ZN5lnerf16k_scatter_reduceILi1024E\w+):.*?\n(.*?)^\.Lfunc_end", asm, flags=re.S | re.M)
-    fused = [(n, body) for n, body in kernels if "Lb1E" in n]          # FUSE = true: the closing form
+    kernels = re.findall(r"^(_ZN5lnerf16k_scatter_reduceILi\d+E\w+):.*?\n(.*?)^\.Lfunc_end", asm, flags=re.S | re.M)
+    # The accumulator tile must reach its atomics as the __shared__ array itself: through a pointer that has lost the
+    # LDS address space every ds_add_u64 becomes a flat atomic (0.211 -> 0.275 ms per scatter call).  All six
+    # instantiations: {1024, 512} x {Rec8, Rec12} un-fused, 1024 x {Rec8, Rec12} fused.
+    assert len(kernels) == 6, [n for n, _ in kernels]
+    for name, body in kernels:
+        ops = [l.split()[0] for l in body.splitlines() if l.strip() and not l.lstrip().startswith((";", "."))]
+        assert ops.count("ds_add_u64") == (16 if "Rec8" in name else 10), name       # (one add path gone flat would show here)
+        assert [o for o in ops if o.startswith("flat_")] == [], name
+    fused = [(n, body) for n, body in kernels if "Lb1E" in n and "Li1024E" in n]   # FUSE = true: the closing form
     assert len(fused) == 2                                            # Rec8 and Rec12
     for name, body in fused:
         lines = [l.strip() for l in body.splitlines()]

@@ -295,6 +295,61 @@ def test_exact_scatter_fused_adam(dev, gridtype, variant):
         assert float(zero.abs().max()) == 0.0, name
 
 
+@pytest.mark.parametrize("variant", [2, 3])
+@pytest.mark.parametrize("gridtype", X.LAYOUTS)
+def test_exact_scatter_buckets_without_records(dev, gridtype, variant):
+    """m_dev = EXACT_PER_RAY: only the first ray is scattered.  Eight of the dense level's ten buckets (the partial last
+    one among them) and two of the fourth level's receive no record, and the one-bucket level, planned sliced, is summed
+    by one workgroup (tests/test_tuning_inputs_cpu.py asserts all of it on the reference).  Every way pass 2 finishes a
+    bucket is held to the float64 oracle with the gradient rows >= EXACT_PER_RAY zeroed, bit for bit: the plain add leaves
+    an empty bucket alone (and doubles on a second call), the wire form overwrites its stale content with zeros, the
+    fused form still owes its rows the Adam step with g = 0 -- equal to the separate launches, and different from the
+    initial table."""
+    from src.latent_nerf.models import encoding as E
+    from src.latent_nerf.raymarching import backend as B
+    from src.latent_nerf.raymarching.raymarching import _p, _stream
+    d = _exact_device(dev, gridtype)
+    d["m_dev"] = torch.tensor([X.EXACT_PER_RAY], dtype=torch.int32, device=dev)
+    one = X.first_ray_case(gridtype)
+    ref = one["dtable"].float().to(dev)
+    assert torch.equal(ref.double().cpu(), one["dtable"])
+    levels, cap, offs = d["levels"], X.EXACT_CAPACITY, X.EXACT_OFFSETS
+    # plain dtable +=
+    once, twice = _scatter_twice(dev, d, variant)
+    assert torch.equal(once, ref), _where(once, ref, offs)
+    assert torch.equal(twice, 2 * ref), _where(twice, 2 * ref, offs)
+    # the wire format: stale content before
+    enc = types.SimpleNamespace(levels=levels, grad_sink=E.GradSink(d["table"]))
+    enc.grad_sink.wire.fill_(7.0)
+    E.grid_encode_backward_bf16(d["x"], 1.0, d["dfeat"], enc, cap, d["m_dev"], cap, variant)
+    want = ref.to(torch.bfloat16)
+    assert torch.equal(enc.grad_sink.wire, want), _where(enc.grad_sink.wire.float(), want.float(), offs)
+    # fused Adam against the separate launches (the moments of test_exact_scatter_fused_adam)
+    lr, b1, b2, eps, step = 1e-2, 0.9, 0.99, 1e-15, 3
+    g = torch.Generator().manual_seed(17)
+    p0 = (torch.randn(levels.n_rows, 2, generator=g) * 0.1).to(dev)
+    m0 = (torch.randn(levels.n_rows, 2, generator=g) * 0.01).to(dev)
+    v0 = (torch.rand(levels.n_rows, 2, generator=g) * 1e-3).to(dev)
+    pr, mr, vr = p0.clone(), m0.clone(), v0.clone()
+    sr = torch.zeros(levels.n_rows, 2, device=dev, dtype=torch.bfloat16)
+    B.call("lnerf_adam_step", _p(pr), _p(once), B.F32, _p(mr), _p(vr), _p(sr), pr.numel(), lr, b1, b2, eps, step, None,
+           1.0, 0, _stream())
+    pf, mf, vf = p0.clone(), m0.clone(), v0.clone()
+    sf = torch.zeros(levels.n_rows, 2, device=dev, dtype=torch.bfloat16)
+    zero = torch.zeros(levels.n_rows, 2, device=dev)
+    ws = E.scatter_workspace(levels, cap, dev)
+    B.call("lnerf_grid_encode_backward_adam", *E._grid_args(levels, d["x"], 1.0, cap, d["m_dev"], cap, _p(d["dfeat"])),
+           _p(zero), variant | levels.flag, _p(ws), ws.numel(), _p(pf), _p(mf), _p(vf), _p(sf), lr, b1, b2, eps, step, None,
+           1.0, _stream())
+    E.ws_mark_dirty(dev)
+    for what, a, b in (("table", pf, pr), ("exp_avg", mf, mr), ("exp_avg_sq", vf, vr), ("shadow", sf, sr)):
+        assert torch.equal(a, b), "%s: %s" % (what, _where(a.float(), b.float(), offs))
+    spans = [s for level in one["empty"] for s in level]
+    assert len(spans) >= 10
+    for a, b in spans:      # the g = 0 step really ran: m' = beta1 m everywhere, and the table moved
+        assert bool((mf[a:b] != m0[a:b]).all()) and bool((pf[a:b] != p0[a:b]).any()), (a, b)
+
+
 # ------------------------------------------------------------------------------ 2. ordinary inputs
 @pytest.mark.parametrize("table_dtype", ["f32", "bf16"])
 @pytest.mark.parametrize("gridtype", X.LAYOUTS)

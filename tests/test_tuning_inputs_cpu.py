@@ -130,6 +130,30 @@ def test_exact_inputs_are_exact_in_f32():
     assert 3 < worst < 2 ** 17 / 512          # (above 3: larger than any single record, i.e. runs do add up)
 
 
+def test_first_ray_case_leaves_buckets_without_records():
+    """m_dev = EXACT_PER_RAY (test_exact_scatter_buckets_without_records): the no-records arm of every finisher of pass 2
+    needs buckets that receive nothing, next to buckets that do, and the one-bucket level planned sliced but summed by
+    one workgroup."""
+    assert X.EXACT_PER_RAY == 97
+    for gridtype in X.LAYOUTS:
+        full, one = X.exact_case(gridtype)["dtable"], X.first_ray_case(gridtype)
+        dt, empty = one["dtable"], one["empty"]
+        assert float(dt.abs().max()) > 0 and not torch.equal(dt, full)
+        assert torch.equal(dt.float().double(), dt)                               # exact in f32, as the whole case is
+        nb = [-(-s // 4096) for s in X.EXACT_SIZES]
+        # the dense level: a full bucket and the partial last bucket stay empty
+        assert any(b - a == 4096 for a, b in empty[0]), gridtype
+        assert (X.EXACT_OFFSETS[1] - X.EXACT_SIZES[0] % 4096, X.EXACT_OFFSETS[1]) in empty[0], gridtype
+        assert len(empty[0]) == 8 and len(empty[2]) == 0 and len(empty[3]) == 2, (gridtype, [len(e) for e in empty])
+        # every level keeps a bucket with records, the one-bucket level among them
+        assert all(len(e) < n for e, n in zip(empty, nb)), gridtype
+        for spans in empty:
+            for a, b in spans:
+                assert float(dt[a:b].abs().max()) == 0.0
+    # the one-bucket level is still PLANNED sliced (8 m_host / nb > 65536) and holds far less than one slice's records
+    assert 8 * X.EXACT_CAPACITY // 1 > 65536 and 8 * X.EXACT_PER_RAY < 16384
+
+
 def test_ordinary_inputs_shape():
     x, grad = X.ordinary_inputs()
     assert x.shape == (29100, 3) and x.shape[0] <= 30000 and grad.shape == (29100, 32)

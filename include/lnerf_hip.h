@@ -648,6 +648,41 @@ int lnerf_decimate(const float *verts, int n_verts, const int32_t *faces, int n_
                    int max_rounds, void *scratch, size_t scratch_bytes, float *verts_out, int32_t *faces_out,
                    float *normals_out, int64_t *counts_dev, lnerf_stream_t stream);
 
+/* ---- shaded renders (shading = "lambertian" / "textureless"): the kernels around the field (csrc/shade.hip).  Additive
+ * to ABI 7.  The normal is the upstream renderer's training normal, a central finite difference of sigma at six offset
+ * points; its gradient is the field's ordinary backward at 7 m points.  All arithmetic is f32 + - * / sqrt in the order
+ * written here, no fused multiply-adds (numpy restatement: tests/shading_reference.py).
+ *
+ * lnerf_fd_points: sample i < m = min(m_host, *m_dev) (m_dev may be NULL) at x = xyzs[i] -> rows 7 i .. 7 i + 6 of pts7
+ *   [7 cap, 3]: row 7 i = x; rows 7 i + 1 .. 7 i + 6 = x with ONE coordinate replaced by clamp(x_a +- eps, -bound, bound),
+ *   in the order +x, -x, +y, -y, +z, -z.  m7_dev[0] = 7 m (may be NULL).  Rows >= 7 m are not touched; m_host == 0 launches
+ *   nothing (m7_dev is then not written either).
+ *
+ * lnerf_shade_fd_forward: one wavefront per ray, rays[r] = (id, off, cnt) as in the compositing; for sample s = off + i,
+ *   i < cnt, with sg = sigmas7[7 s .. 7 s + 6] (the UNSCALED densities) and albedo = rgbs7[7 s] (C channels, 1 <= C <= 4):
+ *     g_a = (sg[1 + 2 a] - sg[2 + 2 a]) * inv_2eps,   s2 = (g_x g_x + g_y g_y) + g_z g_z,
+ *     r = 1 / sqrt(fmax(s2, 1e-20)),   n_a = -(g_a r), a NaN component becomes 0,
+ *     d = (n_x l_x + n_y l_y) + n_z l_z,   lam = ambient + (1 - ambient) * (d > 0 ? d : 0),
+ *     colours[s][c] = textureless ? lam : albedo_c * lam,   sigma_c[s] = sg[0]
+ *   with (l_x, l_y, l_z, ambient, textureless) = shade[min(id / rays_per_view, B - 1)] (f32 [B, 5]; l a unit vector toward
+ *   the light, textureless 0 or 1).  A ray with cnt = 0 writes nothing; samples outside every span are not touched.
+ *
+ * lnerf_shade_fd_backward: the same launch shape; recomputes n and lam from sigmas7.  With dcol = dcolours[s], per sample
+ *     dlam = textureless ? ((dcol_0 + dcol_1) + ..) : ((dcol_0 albedo_0 + dcol_1 albedo_1) + ..),
+ *     dalbedo_c = textureless ? 0 : dcol_c * lam,   k = (1 - ambient) * dlam,   dn_a = d > 0 ? k * l_a : 0,
+ *     q = (n_x dn_x + n_y dn_y) + n_z dn_z,   dg_a = -(r * (s2 > 1e-20 ? dn_a - n_a q : dn_a)),
+ *     dsigmas7[7 s] = dsigma_c[s],   dsigmas7[7 s + 1 + 2 a] = dg_a * inv_2eps,   dsigmas7[7 s + 2 + 2 a] = -(dg_a * inv_2eps),
+ *     drgbs7[7 s] = dalbedo,   drgbs7[7 s + 1 .. 7 s + 6] = 0.
+ *   Every element has exactly one writer (no atomics, the same bits on every run); every row of a span is written. */
+int lnerf_fd_points(const float *xyzs, float bound, float eps, int64_t m_host, const int32_t *m_dev, float *pts7,
+                    int32_t *m7_dev, lnerf_stream_t stream);
+int lnerf_shade_fd_forward(const float *sigmas7, const float *rgbs7, int C, const int32_t *rays, int64_t N,
+                           int rays_per_view, const float *shade, int B, float inv_2eps, float *sigma_c, float *colours,
+                           lnerf_stream_t stream);
+int lnerf_shade_fd_backward(const float *sigmas7, const float *rgbs7, int C, const int32_t *rays, int64_t N,
+                            int rays_per_view, const float *shade, int B, float inv_2eps, const float *dsigma_c,
+                            const float *dcolours, float *dsigmas7, float *drgbs7, lnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

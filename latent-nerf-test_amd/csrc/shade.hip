@@ -1,0 +1,336 @@
+// Shaded training renders (shading = "lambertian" / "textureless"): the kernels around the field.
+// Contract: include/lnerf_hip.h, "shaded renders"; numpy restatement: tests/shading_reference.py.
+//
+//   k_fd_points   sample -> itself + its six +-eps neighbours (clamped to the box), rows 7 i .. 7 i + 6, and m7 = 7 m
+//   k_shade_fwd   the seven densities of a sample -> finite-difference normal -> Lambert term -> colour
+//   k_shade_bwd   recomputes the normal and the Lambert term, writes the gradient of all seven rows (one writer each)
+//
+// All arithmetic is f32 + - * / sqrt in the stated order: the library is built with -ffp-contract=off and nothing here
+// is an explicit fmaf, so the numpy restatement matches bit for bit.
+#include "common.h"
+
+namespace lnerf {
+
+constexpr int FD_ROWS = 7;                   // the sample and its six neighbours
+constexpr int FD_BLOCK = 256;
+constexpr int FD_FLOATS = FD_ROWS * 3;       // floats of pts7 per sample
+
+// One lane per sample.  The 21 floats of a sample are contiguous in pts7, so the 64 samples of a wave own one
+// contiguous span of 64 * 84 bytes: it is staged in LDS and stored with consecutive lanes on consecutive floats.
+__global__ void __launch_bounds__(FD_BLOCK)
+k_fd_points(const float *__restrict__ xyzs, float bound, float eps, int64_t m_host, const int32_t *__restrict__ m_dev,
+            float *__restrict__ pts7, int32_t *__restrict__ m7_dev) {
+    __shared__ float stage[FD_BLOCK * FD_FLOATS];
+    int64_t M = m_host;
+    if (m_dev) { const int64_t md = *m_dev; M = md < M ? md : M; }
+    if (M < 0) M = 0;
+    if (m7_dev && blockIdx.x == 0 && threadIdx.x == 0) m7_dev[0] = (int32_t)(FD_ROWS * M);
+    for (int64_t base = (int64_t)blockIdx.x * FD_BLOCK; base < M; base += (int64_t)gridDim.x * FD_BLOCK) {   // block-uniform
+        const int64_t i = base + threadIdx.x;
+        if (i < M) {
+            const float p[3] = {xyzs[i * 3], xyzs[i * 3 + 1], xyzs[i * 3 + 2]};
+            float *row = stage + threadIdx.x * FD_FLOATS;
+#pragma unroll
+            for (int k = 0; k < FD_ROWS; ++k) {
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    float v = p[a];
+                    if (k == 1 + 2 * a) v = clampf(p[a] + eps, -bound, bound);
+                    if (k == 2 + 2 * a) v = clampf(p[a] - eps, -bound, bound);
+                    row[k * 3 + a] = v;
+                }
+            }
+        }
+        __syncthreads();
+        const int64_t left = M - base;
+        const int n = (int)(left < FD_BLOCK ? left : FD_BLOCK) * FD_FLOATS;
+        float *dst = pts7 + base * FD_FLOATS;
+        for (int j = threadIdx.x; j < n; j += FD_BLOCK) dst[j] = stage[j];
+        __syncthreads();
+    }
+}
+
+// per-view record: unit vector toward the light, ambient share, textureless flag
+struct Light {
+    float l[3], ambient, diffuse;   // diffuse = 1 - ambient
+    bool textureless;
+};
+__device__ __forceinline__ Light load_light(const float *__restrict__ shade, int64_t id, int rays_per_view, int B) {
+    int64_t b = id / rays_per_view;
+    b = b < 0 ? 0 : (b >= B ? B - 1 : b);          // (a ray id past the last view reads the last record, never past it)
+    const float *s = shade + b * 5;
+    Light L;
+    L.l[0] = s[0]; L.l[1] = s[1]; L.l[2] = s[2];
+    L.ambient = s[3];
+    L.diffuse = 1.0f - s[3];
+    L.textureless = s[4] != 0.f;
+    return L;
+}
+
+// one lane's sample: the seven densities and the albedo (row 7 i of the field's colours)
+template <int C>
+struct Sample7 {
+    float sg[FD_ROWS], alb[C];
+};
+template <int C>
+__device__ __forceinline__ Sample7<C> load_sample7(const float *__restrict__ sigmas7, const float *__restrict__ rgbs7,
+                                                   int64_t off, int cnt, int i) {
+    Sample7<C> k;
+#pragma unroll
+    for (int j = 0; j < FD_ROWS; ++j) k.sg[j] = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) k.alb[c] = 0.f;
+    if (i < cnt) {
+        const int64_t s7 = (off + i) * FD_ROWS;
+#pragma unroll
+        for (int j = 0; j < FD_ROWS; ++j) k.sg[j] = sigmas7[s7 + j];
+        if (C == 4) {
+            const float4 v = reinterpret_cast<const float4 *>(rgbs7)[s7];
+            k.alb[0] = v.x; k.alb[1] = v.y; k.alb[2] = v.z; k.alb[C - 1] = v.w;
+        } else {
+#pragma unroll
+            for (int c = 0; c < C; ++c) k.alb[c] = rgbs7[s7 * C + c];
+        }
+    }
+    return k;
+}
+
+// finite-difference normal of one sample and its Lambert term
+struct Lambert {
+    float n[3], s, r, d, lam;
+};
+__device__ __forceinline__ Lambert lambert_of(const float (&sg)[FD_ROWS], float inv_2eps, const Light &L) {
+    Lambert o;
+    float g[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) g[a] = (sg[1 + 2 * a] - sg[2 + 2 * a]) * inv_2eps;
+    o.s = (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
+    o.r = 1.0f / sqrtf(fmaxf(o.s, 1e-20f));          // (fmaxf: a NaN s gives the floor)
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float v = -(g[a] * o.r);
+        o.n[a] = v != v ? 0.f : v;
+    }
+    o.d = (o.n[0] * L.l[0] + o.n[1] * L.l[1]) + o.n[2] * L.l[2];
+    o.lam = L.ambient + L.diffuse * (o.d > 0.f ? o.d : 0.f);
+    return o;
+}
+
+// One wavefront per ray, lanes striding over the ray's samples; the next 64 samples' loads are requested before this
+// chunk's arithmetic (the kernel is a few memory round trips long, nothing else).
+template <int C>
+__global__ void __launch_bounds__(256)
+k_shade_fwd(const float *__restrict__ sigmas7, const float *__restrict__ rgbs7, const int32_t *__restrict__ rays, int64_t N,
+            int rays_per_view, const float *__restrict__ shade, int B, float inv_2eps, float *__restrict__ sigma_c,
+            float *__restrict__ colours) {
+    const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (r >= N) return;
+    const int lane = lane_id();
+    const int64_t id = rays[r * 3];
+    const int64_t off = rays[r * 3 + 1];
+    const int cnt = rays[r * 3 + 2];
+    if (cnt <= 0) return;
+    const Light L = load_light(shade, id, rays_per_view, B);
+    Sample7<C> cur = load_sample7<C>(sigmas7, rgbs7, off, cnt, lane);
+    for (int base = 0; base < cnt; base += 64) {
+        Sample7<C> nxt = cur;
+        if (base + 64 < cnt) nxt = load_sample7<C>(sigmas7, rgbs7, off, cnt, base + 64 + lane);
+        const int i = base + lane;
+        if (i < cnt) {
+            const int64_t s = off + i;
+            const Lambert o = lambert_of(cur.sg, inv_2eps, L);
+            sigma_c[s] = cur.sg[0];
+            float col[C];
+#pragma unroll
+            for (int c = 0; c < C; ++c) col[c] = L.textureless ? o.lam : cur.alb[c] * o.lam;
+            if (C == 4) {
+                reinterpret_cast<float4 *>(colours)[s] = make_float4(col[0], col[1], col[2], col[C - 1]);
+            } else {
+#pragma unroll
+                for (int c = 0; c < C; ++c) colours[s * C + c] = col[c];
+            }
+        }
+        cur = nxt;
+    }
+}
+
+// one lane's upstream gradient
+template <int C>
+struct Grad7 {
+    float dsig, dcol[C];
+};
+template <int C>
+__device__ __forceinline__ Grad7<C> load_grad7(const float *__restrict__ dsigma_c, const float *__restrict__ dcolours,
+                                               int64_t off, int cnt, int i) {
+    Grad7<C> k;
+    k.dsig = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) k.dcol[c] = 0.f;
+    if (i < cnt) {
+        const int64_t s = off + i;
+        k.dsig = dsigma_c[s];
+        if (C == 4) {
+            const float4 v = reinterpret_cast<const float4 *>(dcolours)[s];
+            k.dcol[0] = v.x; k.dcol[1] = v.y; k.dcol[2] = v.z; k.dcol[C - 1] = v.w;
+        } else {
+#pragma unroll
+            for (int c = 0; c < C; ++c) k.dcol[c] = dcolours[s * C + c];
+        }
+    }
+    return k;
+}
+
+// Same launch shape as the forward.  Every element of rows 7 (off + i) .. 7 (off + i) + 6 of dsigmas7 and drgbs7 is
+// written by the lane that owns sample i: no atomics.
+template <int C>
+__global__ void __launch_bounds__(256)
+k_shade_bwd(const float *__restrict__ sigmas7, const float *__restrict__ rgbs7, const int32_t *__restrict__ rays, int64_t N,
+            int rays_per_view, const float *__restrict__ shade, int B, float inv_2eps, const float *__restrict__ dsigma_c,
+            const float *__restrict__ dcolours, float *__restrict__ dsigmas7, float *__restrict__ drgbs7) {
+    const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (r >= N) return;
+    const int lane = lane_id();
+    const int64_t id = rays[r * 3];
+    const int64_t off = rays[r * 3 + 1];
+    const int cnt = rays[r * 3 + 2];
+    if (cnt <= 0) return;
+    const Light L = load_light(shade, id, rays_per_view, B);
+    Sample7<C> cur = load_sample7<C>(sigmas7, rgbs7, off, cnt, lane);
+    Grad7<C> gcur = load_grad7<C>(dsigma_c, dcolours, off, cnt, lane);
+    for (int base = 0; base < cnt; base += 64) {
+        Sample7<C> nxt = cur;
+        Grad7<C> gnxt = gcur;
+        if (base + 64 < cnt) {
+            nxt = load_sample7<C>(sigmas7, rgbs7, off, cnt, base + 64 + lane);
+            gnxt = load_grad7<C>(dsigma_c, dcolours, off, cnt, base + 64 + lane);
+        }
+        const int i = base + lane;
+        if (i < cnt) {
+            const int64_t s7 = (off + i) * FD_ROWS;
+            const Lambert o = lambert_of(cur.sg, inv_2eps, L);
+            float dlam, dalb[C];
+            if (L.textureless) {
+                dlam = gcur.dcol[0];
+#pragma unroll
+                for (int c = 1; c < C; ++c) dlam = dlam + gcur.dcol[c];
+#pragma unroll
+                for (int c = 0; c < C; ++c) dalb[c] = 0.f;
+            } else {
+                dlam = gcur.dcol[0] * cur.alb[0];
+#pragma unroll
+                for (int c = 1; c < C; ++c) dlam = dlam + gcur.dcol[c] * cur.alb[c];
+#pragma unroll
+                for (int c = 0; c < C; ++c) dalb[c] = gcur.dcol[c] * o.lam;
+            }
+            const float k = L.diffuse * dlam;
+            float dn[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) dn[a] = o.d > 0.f ? k * L.l[a] : 0.f;
+            const float ndn = (o.n[0] * dn[0] + o.n[1] * dn[1]) + o.n[2] * dn[2];
+            const bool project = o.s > 1e-20f;
+            float ds[FD_ROWS];
+            ds[0] = gcur.dsig;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const float t = project ? dn[a] - o.n[a] * ndn : dn[a];
+                const float dg = -(o.r * t);
+                const float v = dg * inv_2eps;
+                ds[1 + 2 * a] = v;
+                ds[2 + 2 * a] = -v;
+            }
+#pragma unroll
+            for (int j = 0; j < FD_ROWS; ++j) dsigmas7[s7 + j] = ds[j];
+            if (C == 4) {
+                float4 *row = reinterpret_cast<float4 *>(drgbs7) + s7;
+                row[0] = make_float4(dalb[0], dalb[1], dalb[2], dalb[C - 1]);
+#pragma unroll
+                for (int j = 1; j < FD_ROWS; ++j) row[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+            } else {
+                float *row = drgbs7 + s7 * C;
+#pragma unroll
+                for (int c = 0; c < C; ++c) row[c] = dalb[c];
+#pragma unroll
+                for (int j = C; j < FD_ROWS * C; ++j) row[j] = 0.f;
+            }
+        }
+        cur = nxt;
+        gcur = gnxt;
+    }
+}
+
+}  // namespace lnerf
+
+using namespace lnerf;
+
+extern "C" {
+
+int lnerf_fd_points(const float *xyzs, float bound, float eps, int64_t m_host, const int32_t *m_dev, float *pts7,
+                    int32_t *m7_dev, lnerf_stream_t stream) {
+    LNERF_REQUIRE(m_host >= 0, "fd_points: m_host must be >= 0");
+    LNERF_REQUIRE(eps > 0.f, "fd_points: eps must be > 0");
+    LNERF_REQUIRE(bound > 0.f, "fd_points: bound must be > 0");
+    LNERF_REQUIRE(m_host <= (int64_t)0x7FFFFFFF / FD_ROWS, "fd_points: 7 * m_host must fit int32");
+    if (m_host == 0) return LNERF_OK;
+    LNERF_REQUIRE(xyzs && pts7, "fd_points: null pointer");
+    int64_t blocks = div_up(m_host, (int64_t)FD_BLOCK);
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(k_fd_points, dim3((unsigned)blocks), dim3(FD_BLOCK), 0, as_stream(stream), xyzs, bound, eps, m_host,
+                       m_dev, pts7, m7_dev);
+    LNERF_CHECK_LAUNCH("fd_points");
+    return LNERF_OK;
+}
+
+int lnerf_shade_fd_forward(const float *sigmas7, const float *rgbs7, int C, const int32_t *rays, int64_t N,
+                           int rays_per_view, const float *shade, int B, float inv_2eps, float *sigma_c, float *colours,
+                           lnerf_stream_t stream) {
+    LNERF_REQUIRE(N >= 0, "shade_fd_forward: negative N");
+    LNERF_REQUIRE(C >= 1 && C <= 4, "shade_fd_forward: C must be 1..4 (got %d)", C);
+    LNERF_REQUIRE(rays_per_view > 0, "shade_fd_forward: rays_per_view must be > 0");
+    if (N == 0) return LNERF_OK;
+    LNERF_REQUIRE(B > 0, "shade_fd_forward: B must be > 0");
+    LNERF_REQUIRE(sigmas7 && rgbs7 && rays && shade && sigma_c && colours, "shade_fd_forward: null pointer");
+    LNERF_REQUIRE(C != 4 || (((uintptr_t)rgbs7 | (uintptr_t)colours) & 15) == 0,
+                  "shade_fd_forward: (C = 4) rgbs7 / colours must be 16-byte aligned");
+    const dim3 grid((unsigned)div_up(N, 4)), block(256);
+#define LNERF_SHADE_FWD(CC)                                                                                            \
+    hipLaunchKernelGGL(k_shade_fwd<CC>, grid, block, 0, as_stream(stream), sigmas7, rgbs7, rays, N, rays_per_view, shade, \
+                       B, inv_2eps, sigma_c, colours)
+    switch (C) {
+        case 1: LNERF_SHADE_FWD(1); break;
+        case 2: LNERF_SHADE_FWD(2); break;
+        case 3: LNERF_SHADE_FWD(3); break;
+        default: LNERF_SHADE_FWD(4); break;
+    }
+#undef LNERF_SHADE_FWD
+    LNERF_CHECK_LAUNCH("shade_fd_forward");
+    return LNERF_OK;
+}
+
+int lnerf_shade_fd_backward(const float *sigmas7, const float *rgbs7, int C, const int32_t *rays, int64_t N,
+                            int rays_per_view, const float *shade, int B, float inv_2eps, const float *dsigma_c,
+                            const float *dcolours, float *dsigmas7, float *drgbs7, lnerf_stream_t stream) {
+    LNERF_REQUIRE(N >= 0, "shade_fd_backward: negative N");
+    LNERF_REQUIRE(C >= 1 && C <= 4, "shade_fd_backward: C must be 1..4 (got %d)", C);
+    LNERF_REQUIRE(rays_per_view > 0, "shade_fd_backward: rays_per_view must be > 0");
+    if (N == 0) return LNERF_OK;
+    LNERF_REQUIRE(B > 0, "shade_fd_backward: B must be > 0");
+    LNERF_REQUIRE(sigmas7 && rgbs7 && rays && shade && dsigma_c && dcolours && dsigmas7 && drgbs7,
+                  "shade_fd_backward: null pointer");
+    LNERF_REQUIRE(C != 4 || (((uintptr_t)rgbs7 | (uintptr_t)dcolours | (uintptr_t)drgbs7) & 15) == 0,
+                  "shade_fd_backward: (C = 4) rgbs7 / dcolours / drgbs7 must be 16-byte aligned");
+    const dim3 grid((unsigned)div_up(N, 4)), block(256);
+#define LNERF_SHADE_BWD(CC)                                                                                            \
+    hipLaunchKernelGGL(k_shade_bwd<CC>, grid, block, 0, as_stream(stream), sigmas7, rgbs7, rays, N, rays_per_view, shade, \
+                       B, inv_2eps, dsigma_c, dcolours, dsigmas7, drgbs7)
+    switch (C) {
+        case 1: LNERF_SHADE_BWD(1); break;
+        case 2: LNERF_SHADE_BWD(2); break;
+        case 3: LNERF_SHADE_BWD(3); break;
+        default: LNERF_SHADE_BWD(4); break;
+    }
+#undef LNERF_SHADE_BWD
+    LNERF_CHECK_LAUNCH("shade_fd_backward");
+    return LNERF_OK;
+}
+
+}  // extern "C"

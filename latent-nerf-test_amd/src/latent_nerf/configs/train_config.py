@@ -76,6 +76,11 @@ class OptimConfig:
     # equal yet (parity unpinned at N > 1); "true" / LNERF_GRAPH_COLLECTIVES=1 opt in (bench.py does so after a
     # supervised pre-flight of exactly that comparison on the job's own ranks)
     graph_collectives: str = "auto"
+    # from this step on (1-based) most training renders are SHADED, as in the upstream trainers: per step, 40 % lambertian
+    # (albedo x a diffuse term from the density's finite-difference normal), 40 % textureless (the diffuse term alone),
+    # 20 % plain albedo, under a random light near the camera (ambient 0.1) -- the defence against flat, "painted-on"
+    # geometry.  A shaded step evaluates the field at 7 points per sample.  None: every step renders the plain albedo
+    start_shading_iter: Optional[int] = None
 
 
 @dataclass

@@ -129,15 +129,38 @@ class NeRFRenderer(nn.Module):
         """xyzs [M,3] -> (sigmas [M] (x density_scale), unit normals [M,3]), outside autograd."""
         raise NotImplementedError()
 
-    def _check_shading(self, shading):
+    SHADED = ("lambertian", "textureless")
+
+    def _check_shading(self, shading, light_d=None, sampler="run_cuda"):
+        """Validates `shading` before any tensor is touched.  -> (normal render?, shaded render?)."""
+        if shading in self.SHADED:
+            if light_d is None:
+                # there is no random light inside the renderer: a render is a function of its arguments
+                raise ValueError("shading must be 'albedo' or 'normal' unless light_d is given: shading=%r needs "
+                                 "light_d=[3] / [B,3] (direction toward the light)" % (shading,))
+            if sampler != "run_cuda":
+                raise ValueError("shading=%r is built for the occupancy-marched renderer (cuda_ray = true); the uniform "
+                                 "sampler renders 'albedo' and 'normal'" % (shading,))
+            if self.tuned:
+                raise ValueError("shading=%r is not available with render.nerf_type = latent_tune (the decoded colours "
+                                 "are composited per ray)" % (shading,))
+            return False, True
         if shading not in ("albedo", "normal"):
-            raise ValueError("shading must be 'albedo' or 'normal' (got %r)" % (shading,))
+            raise ValueError("shading must be 'albedo', 'normal', or 'lambertian' / 'textureless' with light_d "
+                             "(got %r)" % (shading,))
         if shading == "normal" and self.training:
-            # a normal inside the training graph needs the second-order backward of the encoder, which is not built:
-            # refuse rather than hand back an image whose gradient is wrong
+            # the analytic normal inside the training graph would need the encoder's second-order backward, which is
+            # not built (training renders shade with the finite-difference normal instead: 'lambertian' /
+            # 'textureless'): refuse rather than hand back an image whose gradient is wrong
             raise ValueError("shading='normal' is an evaluation render: call .eval() first (normals are not "
                              "differentiable here)")
-        return shading == "normal"
+        return shading == "normal", False
+
+    def _check_fd_stride(self, cap):
+        """The shaded render evaluates the field at 7 points per sample in ONE node: its level stride is 7 * cap."""
+        if getattr(self, "precision", "f32") == "bf16" and 7 * int(cap) > (1 << 24):
+            raise ValueError("a shaded bf16 render evaluates the field at 7 x %d samples, past the bf16 kernels' level "
+                             "stride limit of 2^24: set render.max_samples <= %d" % (int(cap), (1 << 24) // 7))
 
     def reset_extra_state(self):
         self.density_grid.zero_()
@@ -275,7 +298,8 @@ class NeRFRenderer(nn.Module):
         return PreparedRays(march, bg, prefix, N, cap)
 
     def run_cuda(self, rays_o, rays_d, dt_gamma=0.0, bg_color=None, perturb=False, force_all_rays=False,
-                 max_steps=1024, T_thresh=1e-4, prepared=None, shading="albedo", **kwargs):
+                 max_steps=1024, T_thresh=1e-4, prepared=None, shading="albedo", light_d=None, ambient_ratio=0.1,
+                 normal_eps=1e-2, **kwargs):
         """rays_o, rays_d [B,N,3] -> dict(image [B,N,C], depth [B,N], weights_sum [B,N]).
         Training mode: march -> hash gather -> MLP -> composite, all on device, no host sync (latent_tune: the fused
         composite + decode, image in RGB);
@@ -283,11 +307,26 @@ class NeRFRenderer(nn.Module):
         prepared: a PreparedRays of prepare_rays() (rays_o / rays_d are then ignored and may be None).
         shading="normal" (evaluation only): the per-sample colours are (n + 1) / 2 of the field's surface normal n --
         3 channels whatever img_dims is -- and no background is added; the densities, hence the march, depth and
-        weights_sum, are those of the albedo render."""
-        shade_normal = self._check_shading(shading)
+        weights_sum, are those of the albedo render.
+        shading="lambertian" / "textureless" with light_d (training and evaluation): the per-sample colours are albedo x
+        lam, or lam alone, lam = ambient_ratio + (1 - ambient_ratio) max(n . l, 0), n the FINITE-DIFFERENCE normal of the
+        density at distance normal_eps (the upstream renderer's training normal: six more field queries per sample, whose
+        gradient is the field's ordinary backward at 7 M points).  light_d: [3] or [B,3], the direction toward the light
+        of each of the B views (normalised here) -- or a ready device record [B,5] = (unit l, ambient, textureless 0 / 1)
+        (raymarching.shade_record), taken as it is: the kind and the ambient share are then the record's."""
+        shade_normal, shaded = self._check_shading(shading, light_d)
         C = 3 if shade_normal else self.img_dims
         decode = self.tuned and not shade_normal   # composite 4 latent channels, decode per ray (bg_color is RGB)
         results = {}
+        if shaded and self.training:
+            # the capacity is known before any tensor is read: refuse the stride the bf16 kernels cannot address here
+            if prepared is not None:
+                self._check_fd_stride(prepared.cap)
+            else:
+                cam = kwargs.get("camera")
+                n_rays = (int(cam[0].numel() // 16) * int(cam[2]) * int(cam[3]) if cam is not None
+                          else int(rays_o.numel() // 3))
+                self._check_fd_stride(self._capacity(n_rays, max_steps))
         if self.training:
             if prepared is None:
                 prepared = self.prepare_rays(rays_o, rays_d, dt_gamma=dt_gamma, bg_color=bg_color, perturb=perturb,
@@ -295,7 +334,15 @@ class NeRFRenderer(nn.Module):
             march, bg, prefix, N, cap = prepared.march, prepared.bg, prepared.prefix, prepared.N, prepared.cap
             self.local_step += 1
             m_dev = march.counter[0:1]
-            sigmas, rgbs = self.field(march.xyzs, cap, m_dev, cap)
+            if shaded:
+                # stencil -> ONE field node over the 7 cap rows (every backward route applies as it stands) -> shade
+                n_views = prefix[0] if len(prefix) == 2 else 1
+                shade = rm.shade_record(light_d, ambient_ratio, shading == "textureless", n_views, march.xyzs.device)
+                pts7, m7_dev = rm.fd_points(march.xyzs, self.bound, normal_eps, cap, m_dev)
+                sigmas7, rgbs7 = self.field(pts7, 7 * cap, m7_dev, 7 * cap)
+                sigmas, rgbs = rm.shade_fd(sigmas7, rgbs7, march.rays, shade, max(N // n_views, 1), normal_eps)
+            else:
+                sigmas, rgbs = self.field(march.xyzs, cap, m_dev, cap)
             sigmas = self.density_scale * sigmas if self.density_scale != 1.0 else sigmas
             if decode:
                 weights_sum, depth, image, _ = rm.composite_rays_train_decode(sigmas, rgbs, march.deltas, march.rays,
@@ -320,6 +367,9 @@ class NeRFRenderer(nn.Module):
             spare = torch.empty_like(rays_alive)
             n_dev = torch.empty(1, dtype=torch.int32, device=dev)
             rays_t = nears.clone()
+            if shaded:
+                n_views = prefix[0] if len(prefix) == 2 else 1
+                shade = rm.shade_record(light_d, ambient_ratio, shading == "textureless", n_views, dev)
             n_alive, step = N, 0
             while step < max_steps and n_alive > 0:
                 # the last chunk stops at max_steps: a live ray never takes more samples than the training march
@@ -330,6 +380,15 @@ class NeRFRenderer(nn.Module):
                 if shade_normal:
                     sigmas, rgbs = self.density_normals(xyzs)       # (sigmas: scaled already)
                     rgbs = (rgbs + 1.0) / 2.0
+                elif shaded:
+                    # the training definition per chunk: ray j of the chunk owns samples j n_step .. (j + 1) n_step - 1
+                    with torch.no_grad():
+                        pts7, _ = rm.fd_points(xyzs, self.bound, normal_eps, xyzs.shape[0])
+                        sigmas7, rgbs7 = self.field(pts7, pts7.shape[0])
+                        j = torch.arange(n_alive, dtype=torch.int32, device=dev)
+                        table = torch.stack([rays_alive[:n_alive], j * n_step, torch.full_like(j, n_step)], -1).contiguous()
+                        sigmas, rgbs = rm.shade_fd(sigmas7, rgbs7, table, shade, max(N // n_views, 1), normal_eps)
+                    sigmas = self.density_scale * sigmas if self.density_scale != 1.0 else sigmas
                 else:
                     with torch.no_grad():
                         sigmas, rgbs = self.field(xyzs, xyzs.shape[0])
@@ -363,8 +422,9 @@ class NeRFRenderer(nn.Module):
         by `upsample_steps` importance samples drawn from the coarse pass's weights (inverse-CDF sampling between
         the mid-points of the coarse samples, stratified when not training), evaluated with the same HIP gather/MLP
         kernels and composited with the same HIP kernels (every ray owns a fixed span of samples).
-        shading="normal" (evaluation only): as in run_cuda."""
-        shade_normal = self._check_shading(shading)
+        shading="normal" (evaluation only): as in run_cuda; the shaded renders ('lambertian' / 'textureless') are
+        run_cuda's alone."""
+        shade_normal, _ = self._check_shading(shading, kwargs.get("light_d"), sampler="run")
         prefix = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3).float()
         rays_d = rays_d.contiguous().view(-1, 3).float()

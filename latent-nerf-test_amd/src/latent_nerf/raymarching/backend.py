@@ -124,6 +124,9 @@ _SIGNATURES = {
     "lnerf_uv_dilate": [_P, _P, _I, _I, _I, _P, _P, _P],
     "lnerf_decimate_scratch_bytes": [_I, _I],
     "lnerf_decimate": [_P, _I, _P, _I, _I, _F, _I, _P, _Z, _P, _P, _P, _P, _P],
+    "lnerf_fd_points": [_P, _F, _F, _L, _P, _P, _P, _P],
+    "lnerf_shade_fd_forward": [_P, _P, _I, _P, _L, _I, _P, _I, _F, _P, _P, _P],
+    "lnerf_shade_fd_backward": [_P, _P, _I, _P, _L, _I, _P, _I, _F, _P, _P, _P, _P, _P],
     "lnerf_step_tail": [_I, _I, _P, _P, _P, _L, _I, _P, _Z, _P, _P, _P, _P, _P, _F, _P, _Z, _I, _I, _P, _P, _P, _F, _P,
                         _F, _F, _F, _I, _P, _F, _I, _P],
 }

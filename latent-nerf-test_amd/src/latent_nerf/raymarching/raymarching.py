@@ -360,6 +360,100 @@ def decode_image(latent_image, weights_sum, decoder, bg_color=None):
     return image
 
 
+# ------------------------------------------------------------------------------ shaded renders
+def fd_points(xyzs, bound, eps, m_host, m_dev=None, out=None):
+    """The finite-difference stencil of the shaded renders (lnerf_fd_points): sample i < min(m_host, *m_dev) of xyzs
+    [cap,3] -> rows 7 i .. 7 i + 6 of pts7 [7 cap, 3] (itself, then +x, -x, +y, -y, +z, -z at distance eps, clamped to
+    [-bound, bound]) and the device counter m7_dev [1] = 7 m.  `out` = (pts7, m7_dev) of an earlier call re-uses its
+    buffers.  -> (pts7, m7_dev); rows >= 7 m keep what they held."""
+    _chk(xyzs, "xyzs")
+    if xyzs.dim() != 2 or xyzs.shape[1] != 3:
+        raise ValueError("fd_points: xyzs must be [cap,3]")
+    cap, dev = xyzs.shape[0], xyzs.device
+    if int(m_host) > cap:
+        raise ValueError("fd_points: m_host %d exceeds the %d rows of xyzs" % (int(m_host), cap))
+    if out is not None and out[0].shape[0] == 7 * cap and out[0].device == dev:
+        pts7, m7 = out
+        torch.autograd.graph.increment_version(pts7)   # rewritten through raw pointers (see march_rays_train)
+        torch.autograd.graph.increment_version(m7)
+    else:
+        pts7 = torch.empty(7 * cap, 3, device=dev, dtype=torch.float32)
+        # (the launch writes the counter; with no work there is no launch)
+        m7 = (torch.empty if int(m_host) > 0 else torch.zeros)(1, device=dev, dtype=torch.int32)
+    _b.call("lnerf_fd_points", _p(xyzs), float(bound), float(eps), int(m_host),
+            _chk(m_dev, "m_dev", torch.int32, allow_none=True), _p(pts7), _p(m7), _stream())
+    return pts7, m7
+
+
+def shade_record(light_d, ambient_ratio, textureless, n_views, device):
+    """The per-view record shade_fd reads, f32 [n_views, 5] = (l_x, l_y, l_z, ambient, textureless 0 / 1) on `device`.
+    light_d: [3] (every view) or [n_views, 3], the direction toward the light (list or tensor; normalised here, in
+    f32) -- or a record [n_views, 5] already, which is returned as it is (ambient_ratio and textureless are then its own)."""
+    n_views = int(n_views)
+    t = light_d if torch.is_tensor(light_d) else torch.tensor(light_d, dtype=torch.float32)
+    if t.dim() == 2 and t.shape[1] == 5:
+        if t.shape[0] != n_views or not t.is_cuda or t.dtype != torch.float32:
+            raise ValueError("a shade record must be f32 [%d, 5] on the GPU (got %s %s on %s)"
+                             % (n_views, t.dtype, tuple(t.shape), t.device))
+        return t.contiguous()
+    t = t.detach().to(torch.float32).reshape(-1, 3)
+    if t.shape[0] not in (1, n_views):
+        raise ValueError("light_d must be [3] or [%d, 3] (got %s)" % (n_views, tuple(t.shape)))
+    t = t.cpu()
+    t = (t / t.norm(dim=-1, keepdim=True)).expand(n_views, 3)
+    rec = torch.cat([t, torch.full((n_views, 1), float(ambient_ratio)),
+                     torch.full((n_views, 1), 1.0 if textureless else 0.0)], -1)
+    return rec.to(device).contiguous()
+
+
+class _ShadeFD(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, sigmas7, rgbs7, rays, shade, rays_per_view, eps):
+        sigmas7 = sigmas7.contiguous()
+        rgbs7 = rgbs7.contiguous()
+        shade = shade.contiguous()
+        if sigmas7.shape[0] % 7 != 0 or rgbs7.shape[0] != sigmas7.shape[0]:
+            raise ValueError("shade_fd: sigmas7 [7 cap] and rgbs7 [7 cap, C] must hold seven rows per sample")
+        if shade.dim() != 2 or shade.shape[1] != 5:
+            raise ValueError("shade_fd: shade must be [B,5] = (l_x, l_y, l_z, ambient, textureless)")
+        cap, C, N, B = sigmas7.shape[0] // 7, rgbs7.shape[1], rays.shape[0], shade.shape[0]
+        dev = sigmas7.device
+        inv_2eps = 1.0 / (2.0 * float(eps))
+        # (rows outside every ray's span are not written, as with the field's own outputs: no fill launch in the step)
+        sigma_c = torch.empty(cap, device=dev, dtype=torch.float32)
+        colours = torch.empty(cap, C, device=dev, dtype=torch.float32)
+        _b.call("lnerf_shade_fd_forward", _chk(sigmas7, "sigmas7"), _chk(rgbs7, "rgbs7"), C,
+                _chk(rays, "rays", torch.int32), N, int(rays_per_view), _chk(shade, "shade"), B, inv_2eps, _p(sigma_c),
+                _p(colours), _stream())
+        ctx.save_for_backward(sigmas7, rgbs7, rays, shade)
+        ctx.set_materialize_grads(False)
+        ctx.meta = (int(rays_per_view), inv_2eps)
+        return sigma_c, colours
+
+    @staticmethod
+    def backward(ctx, dsigma_c, dcolours):
+        sigmas7, rgbs7, rays, shade = ctx.saved_tensors
+        rays_per_view, inv_2eps = ctx.meta
+        cap, C, N, B = sigmas7.shape[0] // 7, rgbs7.shape[1], rays.shape[0], shade.shape[0]
+        dsigma_c = torch.zeros(cap, device=sigmas7.device) if dsigma_c is None else dsigma_c.contiguous()
+        dcolours = torch.zeros(cap, C, device=sigmas7.device) if dcolours is None else dcolours.contiguous()
+        # every row below 7 m lies in a ray's span and is written by the kernel; the rows above are read by nobody
+        dsigmas7 = torch.empty_like(sigmas7)
+        drgbs7 = torch.empty_like(rgbs7)
+        _b.call("lnerf_shade_fd_backward", _p(sigmas7), _p(rgbs7), C, _p(rays), N, rays_per_view, _p(shade), B, inv_2eps,
+                _chk(dsigma_c, "dsigma_c"), _chk(dcolours, "dcolours"), _p(dsigmas7), _p(drgbs7), _stream())
+        return dsigmas7, drgbs7, None, None, None, None
+
+
+def shade_fd(sigmas7, rgbs7, rays, shade, rays_per_view, eps):
+    """Lambertian / textureless shading from the finite-difference normal (lnerf_shade_fd_forward / _backward, contract in
+    include/lnerf_hip.h): sigmas7 [7 cap] (unscaled densities), rgbs7 [7 cap, C] of the field at fd_points' rows, rays
+    int32 [N,3] = (id, offset, count), shade f32 [B,5] = (unit light direction, ambient, textureless 0 / 1) per view, the
+    view of ray id being id // rays_per_view -> sigma_c [cap] (row 7 i), colours [cap, C] (albedo x lam, or lam alone).
+    sigmas7 and rgbs7 receive gradients; there is no CPU path."""
+    return _ShadeFD.apply(sigmas7, rgbs7, rays, shade, rays_per_view, eps)
+
+
 # ------------------------------------------------------------------------------ mesh export
 def marching_cubes(volume, iso, lo, hi, close_boundary=True):
     """Iso-surface of a dense f32 volume [nx, ny, nz] (z fastest) on the GPU (lnerf_marching_cubes, include/lnerf_hip.h).

@@ -20,6 +20,7 @@ from ...utils import make_path, seed_everything, tensor2numpy, write_video
 from ..configs.train_config import TrainConfig
 from ..models.network_grid import NeRFNetwork
 from . import distributed as D
+from . import shading as SH
 from .guidance import (LATENT_TO_RGB, StableDiffusionGuidance, SyntheticGuidance, decode_with, sparsity_loss,
                        sparsity_loss_grad)
 from .nerf_dataset import NeRFDataset
@@ -79,8 +80,12 @@ class Trainer:
         # `torch.cuda.stream(trainer.stream)` (or set optim.graph_step = false).
         self.stream = torch.cuda.Stream(device=self.device)
         self._gstep, self._gstep_capacity, self._static, self._whole = None, None, None, False
-        # (host_s: host time spent enqueueing replayed steps -- pose, upload, graph launch; refreshes not included)
-        self.graph_stats = {"captures": 0, "replayed_steps": 0, "eager_steps": 0, "host_s": 0.0}
+        # optim.start_shading_iter: up to TWO captured steps per sample capacity, the plain one (`_gstep`) and the shaded
+        # one; `_shaded` says which form the current step takes (training/shading.py draws it)
+        self._gstep_shaded, self._gstep_ws, self._shaded = None, None, False
+        # (host_s: host time spent enqueueing replayed steps -- pose, upload, graph launch; refreshes not included;
+        # shaded_steps: steps rendered lambertian / textureless, eager or replayed)
+        self.graph_stats = {"captures": 0, "replayed_steps": 0, "eager_steps": 0, "host_s": 0.0, "shaded_steps": 0}
         small = [p for p in self.nerf.parameters() if p is not self.nerf.encoder.embeddings]
         # exchange: bf16 on the wire with the bf16 configuration (f32 otherwise); with one view per rank and step the
         # backward pass writes the wire buffer itself and the table travels in level groups (pipelined with the sums)
@@ -161,7 +166,8 @@ class Trainer:
     # ------------------------------------------------------------------ one optimisation step
     def _render_train(self, camera):
         """camera = (poses [B,4,4], intrinsics, H, W): B views as one batch -> (render dict, latents [B,C,H,W])."""
-        out = self.nerf.render(None, None, staged=False, perturb=True, bg_color=None, force_all_rays=True, camera=camera)
+        out = self.nerf.render(None, None, staged=False, perturb=True, bg_color=None, force_all_rays=True, camera=camera,
+                               **self._shading_args())
         H, W = int(camera[2]), int(camera[3])
         pred = out["image"].reshape(-1, H, W, out["image"].shape[-1]).permute(0, 3, 1, 2).contiguous()
         return out, pred
@@ -226,6 +232,20 @@ class Trainer:
             self.grad_sync.allreduce()
             self.optimizer.step(grad_scale=scale)
 
+    # ---- shading schedule (optim.start_shading_iter)
+    def shading_kind(self, step=None):
+        """'albedo', 'textureless' or 'lambertian': the shading of training step `step` (default: the current one).  The
+        schedule and the light distribution are the upstream trainers' (training/shading.py)."""
+        return SH.shading_kind(self.cfg.optim.seed, self.train_step if step is None else step,
+                               getattr(self.cfg.optim, "start_shading_iter", None))
+
+    def _shading_args(self):
+        """Keywords of the step's render: a shaded step reads its per-view record (light, ambient, textureless flag) from
+        the static buffers, so the kind inside the shaded form is DATA -- one captured graph serves both kinds."""
+        if not self._shaded:
+            return {}
+        return {"shading": "lambertian", "light_d": self._static_buffers()["shade"]}
+
     # ---- one step on this rank's views: camera upload -> batched render -> guidance -> backward -> exchange -> optimiser
     def _graph_ready(self):
         r = self.cfg.render
@@ -238,24 +258,24 @@ class Trainer:
         """Static device buffers the step reads its views from (eager and captured steps alike), and the ring of pinned
         upload slots: the host runs steps ahead of the GPU, a slot is rewritten only after the copy that read it has
         executed (event per slot).  Layout of a slot / of `cam`, k views: [k x 16 pose | k x 4 intrinsics | k view
-        buckets (int32 bit patterns)]."""
+        buckets (int32 bit patterns) | k x 5 shade record (unit light direction, ambient, textureless flag)]."""
         if self._static is None:
             k = len(self.views)
             r = self.cfg.render
-            host = torch.zeros(self.RING, 21 * k, dtype=torch.float32).pin_memory()
-            cam = torch.zeros(21 * k, device=self.device)
+            host = torch.zeros(self.RING, 26 * k, dtype=torch.float32).pin_memory()
+            cam = torch.zeros(26 * k, device=self.device)
             self._static = {"k": k, "host": host, "host_np": host.numpy(), "host_i32": host.view(torch.int32).numpy(),
                             "events": [None] * self.RING, "cam": cam,
                             "poses": cam[:16 * k].view(k, 4, 4), "intr": cam[16 * k:20 * k].view(k, 4),
-                            "dirs": cam[20 * k:21 * k].view(torch.int32),
+                            "dirs": cam[20 * k:21 * k].view(torch.int32), "shade": cam[21 * k:26 * k].view(k, 5),
                             "grad": torch.zeros(k, self.nerf.img_dims, r.train_h, r.train_w, device=self.device)}
         return self._static
 
     def _upload_views(self):
         """This step's views -- poses from the counter-based per-(step, view) stream every rank can reproduce,
         distribution of src/latent_paint/training/views_dataset.py:9-22 -- written into the next pinned slot with plain
-        Python arithmetic (no torch op per view) and sent to the static buffers with ONE asynchronous copy.  Returns the
-        views' direction buckets (host ints)."""
+        Python arithmetic (no torch op per view) and sent to the static buffers with ONE asynchronous copy; a shaded
+        step's lights (training/shading.py) travel in the same slot.  Returns the views' direction buckets (host ints)."""
         from ..models.nerf_utils import intrinsics_from_fov, pose_values
         st = self._static_buffers()
         k, ds = st["k"], self.dataloaders["train"]
@@ -264,9 +284,14 @@ class Trainer:
             st["events"][slot].synchronize()
         row, row_i = st["host_np"][slot], st["host_i32"][slot]
         dirs = []
+        kind = self.shading_kind() if self._shaded else None
         for j, v in enumerate(self.views):
             p = ds.sample_pose(0, uniforms=D.pose_uniforms(self.cfg.optim.seed, self.train_step, v))
-            row[16 * j:16 * j + 16] = pose_values(p["theta"], p["phi"], p["radius"])
+            pose = pose_values(p["theta"], p["phi"], p["radius"])
+            row[16 * j:16 * j + 16] = pose
+            if kind is not None:
+                row[21 * k + 5 * j:21 * k + 5 * j + 5] = SH.shade_row(self.cfg.optim.seed, self.train_step, v,
+                                                                      (pose[3], pose[7], pose[11]), kind)
             row[16 * k + 4 * j:16 * k + 4 * j + 4] = intrinsics_from_fov(p["fov"], ds.H, ds.W)
             row_i[20 * k + j] = p["dir_index"]
             dirs.append(p["dir_index"])
@@ -291,7 +316,7 @@ class Trainer:
         """render -> fused guidance + sparsity gradient -> backward (+ exchange + optimiser) on the static views."""
         st, r = self._static, self.cfg.render
         out = self.nerf.render(None, None, staged=False, perturb=True, bg_color=None, force_all_rays=True,
-                               camera=self._camera())
+                               camera=self._camera(), **self._shading_args())
         gi, gws = self.diffusion.train_step_image(out["image"], st["dirs"], r.train_h, r.train_w, self.optimizer.step_dev,
                                                   out["weights_sum"], float(self.cfg.optim.lambda_sparsity))
         self.optimizer.arm()          # no exchange: the scatter applies the table's Adam step (no-op otherwise)
@@ -322,9 +347,9 @@ class Trainer:
         return bool(int(flag.item()))
 
     def _capture(self):
-        """Capture the step for the current sample capacity: graph F (render) / eager guidance / graph B (backward,
-        exchange where it can be captured, optimiser) -- or ONE graph when the guidance is capturable too.  Runs no
-        kernel: the training state does not advance."""
+        """Capture the step for the current sample capacity, in the form `self._shaded` says (plain or shaded): graph F
+        (render) / eager guidance / graph B (backward, exchange where it can be captured, optimiser) -- or ONE graph when
+        the guidance is capturable too.  Runs no kernel: the training state does not advance."""
         from .graph_step import GraphedRenderStep
         st = self._static_buffers()
         solo = not self.exchange
@@ -374,17 +399,22 @@ class Trainer:
             return self._capture()
         if err is not None:
             raise err
-        self._gstep = gstep
+        if self._shaded:
+            self._gstep_shaded = gstep
+        else:
+            self._gstep = gstep
         self._gstep_capacity = self.nerf._march.capacity
-        self._gstep_ws = self._scatter_ws_state()
         self.graph_stats["captures"] += 1
+
+    def _have_gstep(self):
+        return self._gstep is not None or self._gstep_shaded is not None
 
     def _scatter_ws_state(self):
         from ..models import encoding as E
         return E.scatter_workspace_epoch(self.device)
 
     def _graphed_step(self):
-        st, g = self._static, self._gstep
+        st, g = self._static, (self._gstep_shaded if self._shaded else self._gstep)
         dirs = self._upload_views()
         if self._whole:
             grads = g.replay()
@@ -407,35 +437,48 @@ class Trainer:
         iters = self.cfg.optim.iters if iters is None else iters
         self.nerf.train()
         use_graph = self._graph_ready()
-        eager_left = 2          # eager steps before the first capture (lazy allocations, workspace sizes, autograd streams)
+        # eager steps before the first capture of each form, plain (False) and shaded (True): lazy allocations, workspace
+        # sizes (the shaded form's are its own: 7 x the samples), autograd streams
+        eager_left = {False: 2, True: 2}
         self.stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self.stream):
             while self.train_step < iters:
                 self.train_step += 1
                 if self.nerf.cuda_ray and (self.train_step - 1) % self.cfg.render.update_extra_interval == 0:
                     self.nerf.update_extra_state()
-                    if self._gstep is not None and self.nerf._capacity(*self.nerf._march_key) != self._gstep_capacity:
-                        self._gstep, eager_left = None, 1   # the sample budget moved: new buffers, capture again
-                if self._gstep is not None and self._scatter_ws_state() != self._gstep_ws:
-                    # somebody else scattered through this device's shared workspace since the last replay (a second
-                    # model, a backward through this net outside train()): the captured step assumes the level maxima
-                    # it left clean -- capture again (the new capture starts from a cleared header)
-                    self._gstep, eager_left = None, 1
-                if use_graph and self._gstep is None and eager_left <= 0:
+                    if self._have_gstep() and self.nerf._capacity(*self.nerf._march_key) != self._gstep_capacity:
+                        # the sample budget moved: new buffers, capture again (both forms)
+                        self._gstep, self._gstep_shaded, eager_left = None, None, {False: 1, True: 1}
+                if self._have_gstep() and self._scatter_ws_state() != self._gstep_ws:
+                    # somebody else scattered through this device's shared workspace since this trainer's last step (a
+                    # second model, a backward through this net outside train()): the captured steps assume the level
+                    # maxima they left clean -- capture again (the new captures start from a cleared header)
+                    self._gstep, self._gstep_shaded, eager_left = None, None, {False: 1, True: 1}
+                sh = self._shaded = self.shading_kind() != "albedo"
+                self.graph_stats["shaded_steps"] += int(sh)
+                if use_graph and (self._gstep_shaded if sh else self._gstep) is None and eager_left[sh] <= 0:
                     self._capture()
-                if use_graph and self._gstep is not None:
+                if use_graph and (self._gstep_shaded if sh else self._gstep) is not None:
                     t0 = time.perf_counter()
                     self._graphed_step()
                     self.graph_stats["host_s"] += time.perf_counter() - t0
                 else:
-                    eager_left -= 1
+                    eager_left[sh] -= 1
                     self.graph_stats["eager_steps"] += 1
                     self.optimizer.zero_grad()
                     self._eager_step()
+                # The epoch moves with every scatter issued from Python: this trainer's own eager steps and captures, not
+                # only a foreign call.  Neither disturbs what a captured step relies on -- a capture runs no kernel, and an
+                # eager step of either form ends as a replay of it does (its closing scatter leaves the header of the
+                # workspace it used clean; the plain and the shaded form may use different buffers of the device's list,
+                # each then only ever touched by its own form) -- so the note is taken again here, after the trainer's
+                # own step: alternating between the two forms triggers no recapture, a foreign scatter still does.
+                self._gstep_ws = self._scatter_ws_state()
                 if self.train_step % self.cfg.log.save_interval == 0:
                     self.save_checkpoint(full=True)
                     self.evaluate(self.dataloaders["val"], self.eval_renders_path)
                     self.nerf.train()
+        self._shaded = False    # (renders outside the loop -- train_render, evaluation -- are plain)
         torch.cuda.current_stream().wait_stream(self.stream)
         self.log("finished training at step %d (%s)" % (self.train_step, self.graph_stats))
         # the reference's trainers close with the full evaluation pass of the last model

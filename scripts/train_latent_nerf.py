@@ -2,6 +2,8 @@
 
     python -m scripts.train_latent_nerf --config_path demo_configs/latent_nerf/lego_man.yaml
     python -m scripts.train_latent_nerf --log.exp_name lego --guide.text "a lego man" --render.nerf_type latent
+    python -m scripts.train_latent_nerf --log.exp_name lego --guide.text "a lego man" --optim.start_shading_iter 1000
+        (shaded training renders from step 1000 on: lambertian / textureless / albedo per step, the upstream schedule)
 
 With pyrallis installed the reference's decorator form works unchanged on these dataclasses; here the same
 two input forms are parsed by src.latent_nerf.configs.train_config.load_config."""

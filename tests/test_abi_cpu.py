@@ -62,6 +62,60 @@ def test_argument_validation_fails_loudly(built_lib):
         B.call("lnerf_adam_step", P(16), P(16), B.F32, P(16), P(16), None, 8, 1e-3, 0.9, 0.99, 1e-15, 0, None, 1.0, 1, None)
 
 
+def test_adam_and_cast_entry_points_refuse_bad_arguments(built_lib):
+    """Every argument check of lnerf_adam_step, lnerf_adam_step_multi_shadow and lnerf_cast_f32_to_bf16 runs before the
+    launch: the pointers here are made up, and a call that got past its checks would need a GPU."""
+    lib = B.get_lib()
+    P = ctypes.c_void_p
+    ok = P(4096)
+
+    def arrays(count, n=8, map_at=None):
+        ptrs = lambda: (ctypes.c_void_p * count)(*([4096] * count))
+        maps = None if map_at is None else (ctypes.c_void_p * count)(*([map_at] * count))
+        return [ptrs(), ptrs(), ptrs(), ptrs(), (ctypes.c_int64 * count)(*([n] * count)),
+                (ctypes.c_float * count)(*([1e-3] * count))], maps
+
+    def multi(count, step, step_dev, flags, maps, shadow, n=8, map_at=None):
+        a, mp = arrays(count, n, map_at)
+        rc = lib.lnerf_adam_step_multi_shadow(count, *a, 0.9, 0.99, 1e-15, step, step_dev, 1.0, flags,
+                                              mp if maps else None, shadow, None)
+        return rc, lib.lnerf_last_error()
+
+    rc, msg = multi(17, 1, None, 1, False, None)
+    assert rc == -1 and b"count must be in [0,16]" in msg
+    rc, msg = multi(2, 1, None, 1, True, None, map_at=4096)                  # maps without a shadow
+    assert rc == -1 and b"maps and shadow go together" in msg
+    rc, msg = multi(2, 1, None, 1, False, ok)                                # a shadow without maps
+    assert rc == -1 and b"maps and shadow go together" in msg
+    rc, msg = multi(2, 1, None, 1 | 2, False, None)                          # LNERF_ADAM_TICK = 2 without a counter
+    assert rc == -1 and b"LNERF_ADAM_TICK needs the device step counter" in msg
+    rc, msg = multi(2, 0, None, 1, False, None)
+    assert rc == -1 and b"step must be >= 1" in msg
+    rc, msg = multi(2, 1, None, 1, False, None, n=-1)
+    assert rc == -1 and b"bad tensor 0" in msg
+    rc, msg = multi(2, 1, None, 1, True, ok, map_at=4096 + 4)
+    assert rc == -1 and b"map 0 must be 8-byte aligned" in msg
+
+    def step(p=4096, dtype=B.F32, beta1=0.9, beta2=0.99):
+        rc = lib.lnerf_adam_step(P(p), ok, dtype, ok, ok, None, 8, 1e-3, beta1, beta2, 1e-15, 1, None, 1.0, 1, None)
+        return rc, lib.lnerf_last_error()
+
+    rc, msg = step(p=4096 + 4)
+    assert rc == -1 and b"16-byte aligned" in msg
+    rc, msg = step(dtype=2)
+    assert rc == -1 and b"bad gradient dtype tag" in msg
+    for b1, b2 in ((1.0, 0.99), (0.9, 1.0)):
+        rc, msg = step(beta1=b1, beta2=b2)
+        assert rc == -1 and b"betas must be in [0,1)" in msg
+
+    rc = lib.lnerf_cast_f32_to_bf16(P(4096 + 4), ok, 8, None)
+    assert rc == -1 and b"misaligned" in lib.lnerf_last_error()
+    rc = lib.lnerf_cast_f32_to_bf16(ok, P(4096 + 4), 8, None)
+    assert rc == -1 and b"misaligned" in lib.lnerf_last_error()
+    rc = lib.lnerf_cast_f32_to_bf16(ok, ok, -1, None)
+    assert rc == -1 and b"negative n" in lib.lnerf_last_error()
+
+
 def test_ops_refuse_cpu_tensors(built_lib):
     import torch
     from src.latent_nerf.raymarching import raymarching as rm

@@ -100,24 +100,9 @@ __global__ void __launch_bounds__(256) k_mlp_fragment_maps(int out_dim, int32_t 
 // The fragments of a launch, built ONCE into global memory (k_mlp_build_fragments) and copied into LDS by every
 // workgroup with coalesced 16-byte loads: a workgroup building its own took 28 (forward) / 60 (backward) dependent
 // scattered weight loads per thread before its first tile -- a quarter of the kernels' time at ~6 tiles per workgroup.
-// Behind the weight fragments the build appends three 0/1 SELECTION fragments, F_SELX .. F_SW.  They were the inputs'
-// transposes of the operand-swap backward, which was measured slower than the staging images and removed (DESIGN.md
-// section 4 H7); a backward launch's fragment build still writes all F_SW slots.
-constexpr int F_SELX = 30;   // [nt 0..1]  B[k = 8q+jj][j = c] = (8q + jj == 16nt + c)
-constexpr int F_SEL3 = 32;   //            B[k = 8q+jj][j = c] = (jj < 4 && 4q + jj == c)
-constexpr int F_SW = 33;
-static_assert((size_t)F_SW * 1024 <= MLP_FRAG_BYTES, "fragment cache");
-__device__ __forceinline__ void build_selectors(__bf16 *frag, int tid, int nthreads) {
-    for (int e = tid; e < (F_SW - F_SELX) * 512; e += nthreads) {
-        const int f = F_SELX + (e >> 9), l = (e >> 3) & 63, jj = e & 7;
-        const int q = l >> 4, c = l & 15;
-        const bool one = f < F_SEL3 ? (8 * q + jj == 16 * (f - F_SELX) + c) : (jj < 4 && 4 * q + jj == c);
-        frag[F_SELX * 512 + e] = (__bf16)(one ? 1.0f : 0.0f);
-    }
-}
+static_assert((size_t)F_ALL * 1024 <= MLP_FRAG_BYTES, "fragment cache");
 __global__ void __launch_bounds__(256) k_mlp_build_fragments(MlpArgs a, __bf16 *out, int n_frag) {
-    build_fragments(a, out, n_frag < F_ALL ? n_frag : F_ALL, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
-    if (n_frag > F_ALL) build_selectors(out, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
+    build_fragments(a, out, n_frag, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
 }
 __device__ __forceinline__ void fetch_fragments(const MlpArgs &a, __bf16 *frag, int n_frag, int tid, int nthreads) {
     if (a.frag_global) {
@@ -166,7 +151,6 @@ __device__ __forceinline__ bf16x8 load_x(const MlpArgs &a, int64_t m, int q) {
 __device__ __forceinline__ int64_t clamp_row(int64_t m, int64_t M) { return m < M ? m : (M > 0 ? M - 1 : 0); }
 
 typedef short s16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 // v_cvt_pk_bf16_f32, left to the compiler: an inline-asm form hides the MFMA-result read from its hazard recogniser
@@ -193,7 +177,8 @@ union Pk8 {
     bf16x8 v;
     uint32_t u[4];
 };
-__device__ __forceinline__ bf16x8 pack_relu_pk(const f32x4 &lo, const f32x4 &hi) {
+// relu + pack two C tiles (2s, 2s+1) into the B fragment of k-step s
+__device__ __forceinline__ bf16x8 pack_relu(const f32x4 &lo, const f32x4 &hi) {
     Pk8 r;
     r.u[0] = relu_pk(cvt_pk(lo[0], lo[1]));
     r.u[1] = relu_pk(cvt_pk(lo[2], lo[3]));
@@ -201,7 +186,8 @@ __device__ __forceinline__ bf16x8 pack_relu_pk(const f32x4 &lo, const f32x4 &hi)
     r.u[3] = relu_pk(cvt_pk(hi[2], hi[3]));
     return r.v;
 }
-__device__ __forceinline__ bf16x8 pack_masked_pk(const f32x4 &lo, const f32x4 &hi, const bf16x8 &act) {
+// pack d(pre-activation) = d(activation) masked by the packed activation being positive
+__device__ __forceinline__ bf16x8 pack_masked(const f32x4 &lo, const f32x4 &hi, const bf16x8 &act) {
     Pk8 r, a;
     a.v = act;
     r.u[0] = cvt_pk(lo[0], lo[1]) & live_pk(a.u[0]);
@@ -209,32 +195,6 @@ __device__ __forceinline__ bf16x8 pack_masked_pk(const f32x4 &lo, const f32x4 &h
     r.u[2] = cvt_pk(hi[0], hi[1]) & live_pk(a.u[2]);
     r.u[3] = cvt_pk(hi[2], hi[3]) & live_pk(a.u[3]);
     return r.v;
-}
-__device__ __forceinline__ bf16x8 pack_plain_pk(const f32x4 &lo, const f32x4 &hi) {
-    Pk8 r;
-    r.u[0] = cvt_pk(lo[0], lo[1]);
-    r.u[1] = cvt_pk(lo[2], lo[3]);
-    r.u[2] = cvt_pk(hi[0], hi[1]);
-    r.u[3] = cvt_pk(hi[2], hi[3]);
-    return r.v;
-}
-// sum of the 8 bf16 of a fragment, added to acc (v_dot2c_f32_bf16 against ones)
-__device__ __forceinline__ float sum8(const bf16x8 &v, float acc) {
-    Pk8 a;
-    a.v = v;
-    bf16x2 ones;
-    ones[0] = (__bf16)1.0f;
-    ones[1] = (__bf16)1.0f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a.u[i]), ones, acc, false);
-    return acc;
-}
-
-// relu + pack two C tiles (2s, 2s+1) into the B fragment of k-step s
-__device__ __forceinline__ bf16x8 pack_relu(const f32x4 &lo, const f32x4 &hi) { return pack_relu_pk(lo, hi); }
-// pack d(pre-activation) = d(activation) masked by the packed activation being positive
-__device__ __forceinline__ bf16x8 pack_masked(const f32x4 &lo, const f32x4 &hi, const bf16x8 &act) {
-    return pack_masked_pk(lo, hi, act);
 }
 
 __device__ __forceinline__ f32x4 ld_bias4(const float *b, int base) {
@@ -557,18 +517,137 @@ __device__ __forceinline__ bf16x8 ld_tr(const __bf16 *img, int k, int f0, int la
     return u.v;
 }
 
-// NW wavefronts x T 16-sample column tiles per wavefront = one step of NW * 16 * T samples.  <4, 2> (two workgroups =
-// eight wavefronts per CU) is what runs; <8, 1> (half the registers per wavefront, four wavefronts per SIMD) measured
-// 65 us against 60: the kernel is not short of wavefronts but of LDS bandwidth and issue slots.
-// Ownership of the weight gradients (r = w & 3, h = w >> 2, NH = NW / 4): rows 16r..16r+15 of dW2 / dW1, their column
-// tiles split over h; db2 with h = 0, db1 with h = NH - 1; dW3 columns 16r.. with h = 0; db3 with the first wave of
-// the last h.  No cross-wave reduction.
+// One step of a workgroup: four wavefronts x two 16-sample column tiles each = 128 samples = four k-steps of the
+// weight gradients (two workgroups = eight wavefronts per CU; an eight-wave form with one tile each, half the registers
+// and four wavefronts per SIMD, measured 65 us against 60: the kernel is short of LDS bandwidth and issue slots, not of
+// wavefronts -- DESIGN.md).
+constexpr int STEP = 128, KS = STEP / 32;
+
+// the row of a lane's sample (tile t of wave w, column c) inside the step's images
+__device__ __forceinline__ int image_row(int w, int t, int c) { return 32 * w + 16 * t + c; }
+// the 64 hidden features of the wave's samples -- the packed B fragments v[k-step][tile] -- into an image
+__device__ __forceinline__ void stage_hidden(__bf16 *img, int w, int q, int c, const bf16x8 v[2][2]) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) stage_pair(img, image_row(w, t, c), 32 * s + 4 * q, 32 * s + 16 + 4 * q, v[s][t]);
+}
+
+// G[i] += D[:, d0 .. d0+15]^T (x) A[:, a0 + 16 i ..] for i < NC over the step's samples (D, A: [sample][feature]
+// images), and B += the column sums of that D (an MFMA against the ones fragment) where `bias` (wave-uniform) says so.
+// Per k-step the weights, then the bias; k ascending.
+template <int NC>
+__device__ __forceinline__ void accumulate(const __bf16 *imgD, int d0, const __bf16 *imgA, int a0, int lane,
+                                           const bf16x8 &ones, f32x4 *G, f32x4 &B, bool bias) {
+#pragma unroll
+    for (int k = 0; k < KS; ++k) {
+        const bf16x8 dA = ld_tr(imgD, k, d0, lane);   // A[i = row of G][k = sample]
+#pragma unroll
+        for (int i = 0; i < NC; ++i) G[i] = MFMA32(dA, ld_tr(imgA, k, a0 + 16 * i, lane), G[i]);   // B[k = sample][j = column]
+        if (bias) B = MFMA32(dA, ones, B);
+    }
+}
+
+// The weight-gradient tiles that wave w of the four holds across its steps, and who owns what: rows 16w .. 16w+15 of
+// dW2 (four column tiles), of dW1 (two), of db2 and of db1; columns 16w .. 16w+15 of dW3; db3 with wave 0.  Every tile
+// has one owner: no cross-wave reduction.
+struct WaveGrads {
+    f32x4 w2[4], w1[2], b2, b1, w3, b3;
+    __device__ __forceinline__ void clear() {
+        const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) w2[i] = zero4;
+        w1[0] = w1[1] = b2 = b1 = w3 = b3 = zero4;
+    }
+    // the three accumulations of a step; D / A: the two images as their stage has written them
+    __device__ __forceinline__ void add_w3(const __bf16 *dZ3, const __bf16 *H2, int w, int lane, const bf16x8 &ones) {
+        accumulate<1>(dZ3, 0, H2, 16 * w, lane, ones, &w3, b3, w == 0);
+    }
+    __device__ __forceinline__ void add_w2(const __bf16 *dZ2, const __bf16 *H1, int w, int lane, const bf16x8 &ones) {
+        accumulate<4>(dZ2, 16 * w, H1, 0, lane, ones, w2, b2, true);
+    }
+    __device__ __forceinline__ void add_w1(const __bf16 *dZ1, const __bf16 *X, int w, int lane, const bf16x8 &ones) {
+        accumulate<2>(dZ1, 16 * w, X, 0, lane, ones, w1, b1, true);
+    }
+    // the wave's tiles into the workgroup's slab (layout: mlp_shared.h); C/D lane map: register rr of lane (q, c) is
+    // row 4q + rr, column c of a tile
+    __device__ __forceinline__ void write_slab(float *slab, int w, int q, int c) const {
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const int o = 16 * w + 4 * q + rr;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) slab[MLP_SL_W2 + o * MLP_HID + 16 * i + c] = w2[i][rr];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) slab[MLP_SL_W1 + o * MLP_IN + 16 * i + c] = w1[i][rr];
+            if (c == 0) {
+                slab[MLP_SL_B2 + o] = b2[rr];
+                slab[MLP_SL_B1 + o] = b1[rr];
+            }
+            slab[MLP_SL_W3 + (4 * q + rr) * MLP_HID + 16 * w + c] = w3[rr];
+            if (w == 0 && c == 0) slab[MLP_SL_B3 + 4 * q + rr] = b3[rr];
+        }
+    }
+};
+
+// Gradient through a layer's transposed weights: acc[mt][t] = sum over s < NS of fragment(f0 + NS mt + s) . dz[s][t],
+// for MT 16-feature output tiles and both column tiles; every chain starts from zero, s ascending.
+template <int MT, int NS>
+__device__ __forceinline__ void through_transposed(const __bf16 *frag, int f0, int lane, const bf16x8 dz[NS][2],
+                                                   f32x4 acc[MT][2]) {
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) acc[mt][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const bf16x8 wf = ld_frag(frag, f0 + NS * mt + s, lane);
+#pragma unroll
+            for (int t = 0; t < 2; ++t) acc[mt][t] = MFMA32(wf, dz[s][t], acc[mt][t]);
+        }
+    }
+}
+// d(pre-activation) of a hidden layer: the gradient through the NEXT layer's transposed weights, masked by this layer's
+// activation `act` being positive and packed as the B fragments of the two k-steps of the layer below
+template <int NS>
+__device__ __forceinline__ void hidden_grad(const __bf16 *frag, int f0, int lane, const bf16x8 dz[NS][2],
+                                            const bf16x8 act[2][2], bf16x8 out[2][2]) {
+    f32x4 acc[4][2];
+    through_transposed<4, NS>(frag, f0, lane, dz, acc);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) out[s][t] = pack_masked(acc[2 * s][t], acc[2 * s + 1][t], act[s][t]);
+}
+
+// dX -> dfeat (level-major f32): the lane holds features 16mt + 4q + 0..3 of its samples m0 + 16t + c, i.e. levels
+// 8mt + 2q and 8mt + 2q + 1: one 8-byte store per level, at 32-bit byte offsets (load_x)
+__device__ __forceinline__ void store_dfeat(const MlpArgs &a, float *__restrict__ dfeat, int64_t m0, int64_t M, int q, int c,
+                                            const f32x4 ax[2][2]) {
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int64_t m = m0 + 16 * t + c;
+            if (m < M) {
+                const int lv = 8 * mt + 2 * q;
+                char *df = reinterpret_cast<char *>(dfeat);
+                const uint32_t ls = (uint32_t)a.level_stride, o0 = (((uint32_t)lv) * ls + (uint32_t)m) << 3;
+                *reinterpret_cast<float2 *>(df + (size_t)o0) = make_float2(ax[mt][t][0], ax[mt][t][1]);
+                *reinterpret_cast<float2 *>(df + (size_t)(o0 + (ls << 3))) = make_float2(ax[mt][t][2], ax[mt][t][3]);
+            }
+        }
+    }
+}
+
+// A step: recompute H1, H2 (forward_hidden); then three times "write two images, barrier, accumulate a weight gradient"
+// (dW3 from dZ3 and H2, dW2 from dZ2 and H1, dW1 from dZ1 and X) with the data chain dZ3 -> dZ2 -> dZ1 -> dX in
+// registers between them.  The kernel body holds what is about ORDER IN TIME -- the step-ahead loads, the barriers, the
+// pin, the stamps; the arithmetic is in the parts above.
 // FB16 / OUT5: a.feat_bf16 and a.out_dim == 5 at compile time, as in the forward.
-template <int NW, int T, bool FB16, bool OUT5>
-__global__ void __launch_bounds__(NW * 64, (NW == 4 ? 2 : 4))
+template <bool FB16, bool OUT5>
+__global__ void __launch_bounds__(256, 2)
 k_mlp_backward_bf16(MlpArgs a, const float *__restrict__ sigmas, const float *__restrict__ dsigmas,
                     const float *__restrict__ drgbs, float *__restrict__ dfeat, float *__restrict__ slabs) {
-    constexpr int STEP = NW * 16 * T, KS = STEP / 32, NH = NW / 4, C2 = 4 / NH, C1 = 2 / NH;
     __shared__ __attribute__((aligned(16))) __bf16 frag[F_ALL * 512];
     __shared__ __attribute__((aligned(16))) __bf16 imgA[STEP * RS];  // [sample][feature]: H2, then H1, then X
     __shared__ __attribute__((aligned(16))) __bf16 imgD[STEP * RS];  // [sample][feature]: dZ3, then dZ2, then dZ1
@@ -576,206 +655,89 @@ k_mlp_backward_bf16(MlpArgs a, const float *__restrict__ sigmas, const float *__
     int64_t M = a.m_host;
     if (a.m_dev) { const int64_t md = *a.m_dev; M = md < M ? md : M; }
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, q = lane >> 4, c = lane & 15;
-    const int r = w & 3, h = w >> 2;
-    fetch_fragments(a, frag, F_ALL, tid, NW * 64);
+    fetch_fragments(a, frag, F_ALL, tid, 256);
     if (tid < MLP_HID) { sB1[tid] = a.b1[tid]; sB2[tid] = a.b2[tid]; }
     __syncthreads();
-    const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
     bf16x8 ones;
 #pragma unroll
     for (int i = 0; i < 8; ++i) ones[i] = (__bf16)1.0f;
-
-    f32x4 gW2[C2], gW1[C1], gB = zero4, gW3 = zero4;   // gB: db2 (h = 0) or db1 (h = NH-1); NW = 4 keeps both
-    f32x4 gB1x = zero4, gB3 = zero4;
-#pragma unroll
-    for (int i = 0; i < C2; ++i) gW2[i] = zero4;
-#pragma unroll
-    for (int i = 0; i < C1; ++i) gW1[i] = zero4;
-    const bool own_b2 = h == 0, own_b1 = h == NH - 1, own_w3 = h == 0, own_b3 = w == NW - 4;
+    WaveGrads g;
+    g.clear();
 
     // this wave's inputs of the first step; every later step's are requested one step ahead
-    static_assert(T == 2, "pin_step");
-    const int64_t wofs = (int64_t)w * 16 * T;
-    Upstream<T, OUT5> up;
-    load_upstream<T>(up, a, sigmas, dsigmas, drgbs, (int64_t)blockIdx.x * STEP + wofs, M, q, c);
-    bf16x8 xB[T];
+    const int64_t wofs = 32 * w;
+    Upstream<2, OUT5> up;
+    load_upstream<2>(up, a, sigmas, dsigmas, drgbs, (int64_t)blockIdx.x * STEP + wofs, M, q, c);
+    bf16x8 xB[2];
 #pragma unroll
-    for (int t = 0; t < T; ++t) {
-        const int64_t m = (int64_t)blockIdx.x * STEP + wofs + 16 * t + c;
-        xB[t] = load_x<FB16>(a, clamp_row(m, M), q);
-    }
+    for (int t = 0; t < 2; ++t) xB[t] = load_x<FB16>(a, clamp_row((int64_t)blockIdx.x * STEP + wofs + 16 * t + c, M), q);
     {   // (waited for HERE: a load still pending at the loop's entry makes the compiler wait at the top of every step)
-        f32x4 none[2][T] = {{zero4, zero4}, {zero4, zero4}};
+        f32x4 none[2][2] = {};
         pin_step(xB, up, none);
     }
     Stamps st;
     st.init();
     for (int64_t tile = blockIdx.x; tile * STEP < M; tile += gridDim.x) {
         const int64_t m0 = tile * STEP + wofs, m1 = m0 + (int64_t)gridDim.x * STEP;
-        const Upstream<T, OUT5> up_c = up;
-        bf16x8 xC[T], h1B[2][T], h2B[2][T], dzB[2][T], d3B[T];
+        const Upstream<2, OUT5> up_c = up;
+        bf16x8 xC[2], h1B[2][2], h2B[2][2], dz3B[1][2], dz2B[2][2], dz1B[2][2];
 #pragma unroll
-        for (int t = 0; t < T; ++t) xC[t] = xB[t];
+        for (int t = 0; t < 2; ++t) xC[t] = xB[t];
         // the next step's upstream gradient and features: requested now, in flight across the whole step, pinned behind
         // its last MFMA
-        load_upstream<T>(up, a, sigmas, dsigmas, drgbs, m1, M, q, c);
+        load_upstream<2>(up, a, sigmas, dsigmas, drgbs, m1, M, q, c);
 #pragma unroll
-        for (int t = 0; t < T; ++t) xB[t] = load_x<FB16>(a, clamp_row(m1 + 16 * t + c, M), q);
-#pragma unroll
-        for (int t = 0; t < T; ++t) upstream_fragment<T>(up_c, t, m0 + 16 * t + c < M, q, d3B[t]);
+        for (int t = 0; t < 2; ++t) xB[t] = load_x<FB16>(a, clamp_row(m1 + 16 * t + c, M), q);
         // (A step whose upstream gradient is exactly zero -- rays past their termination point, 8 % of the bench's
-        // samples -- used to be skipped behind a __syncthreads_or.  The skip made every accumulator live across a branch:
-        // ~130 register copies per step at the merge, more than the skipped arithmetic was worth; a dead step now flows
-        // through and produces its zeros: dfeat = +0, nothing added to any weight gradient.)
-        st.mark(4);   // __syncthreads_or
-        forward_hidden<T>(frag, sB1, sB2, lane, xC, h1B, h2B, st);   // marks 1, 2
+        // samples -- is not skipped: a branch around the step makes every accumulator live across a merge, ~130 register
+        // copies per step, more than the skipped arithmetic is worth.  It flows through and produces its zeros: dfeat = +0,
+        // nothing added to any weight gradient.)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) upstream_fragment<2>(up_c, t, m0 + 16 * t + c < M, q, dz3B[0][t]);
+        st.mark(4);   // next step's loads issued, dZ3 fragment
+        forward_hidden<2>(frag, sB1, sB2, lane, xC, h1B, h2B, st);   // marks 1, 2
         // ================= stage 1: dW3 += dZ3^T (x) H2^T
         __syncthreads();  // previous step's readers of imgA/imgD are done
         st.mark(5);
+        stage_hidden(imgA, w, q, c, h2B);
 #pragma unroll
-        for (int t = 0; t < T; ++t) {
-            const int row = 16 * T * w + 16 * t + c;  // this lane's sample inside the step
-#pragma unroll
-            for (int s = 0; s < 2; ++s) stage_pair(imgA, row, 32 * s + 4 * q, 32 * s + 16 + 4 * q, h2B[s][t]);
-            stage_lo(imgD, row, 4 * q, d3B[t]);   // outputs 4q .. 4q+3 (columns 0..15; zero beyond out_dim)
-        }
+        for (int t = 0; t < 2; ++t) stage_lo(imgD, image_row(w, t, c), 4 * q, dz3B[0][t]);   // outputs 4q .. 4q+3 (columns 0..15; zero beyond out_dim)
         __syncthreads();
         st.mark(6);   // stage-1 images written + barrier
-        if (own_w3 || own_b3) {   // wave-uniform
-#pragma unroll
-            for (int k = 0; k < KS; ++k) {
-                const bf16x8 dA = ld_tr(imgD, k, 0, lane);        // A[i = output][k = sample]
-                if (own_w3) gW3 = MFMA32(dA, ld_tr(imgA, k, 16 * r, lane), gW3);   // B[k = sample][j = hidden 16r + c]
-                if (own_b3) gB3 = MFMA32(dA, ones, gB3);
-            }
-        }
+        g.add_w3(imgD, imgA, w, lane, ones);
         st.mark(7);   // dW3
-        // ---- dA2 = W3^T dZ3 ; dZ2 = dA2 masked by H2 > 0
-        {
-            f32x4 acc[4][T];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                const bf16x8 wf = ld_frag(frag, F_W3T + mt, lane);
-#pragma unroll
-                for (int t = 0; t < T; ++t) acc[mt][t] = MFMA32(wf, d3B[t], zero4);
-            }
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int t = 0; t < T; ++t) dzB[s][t] = pack_masked(acc[2 * s][t], acc[2 * s + 1][t], h2B[s][t]);
-        }
+        hidden_grad<1>(frag, F_W3T, lane, dz3B, h2B, dz2B);   // dZ2 = (W3^T dZ3) masked by H2 > 0
         st.mark(8);   // dA2 chain
         // ================= stage 2: dW2 += dZ2^T (x) H1^T
         __syncthreads();
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-            const int row = 16 * T * w + 16 * t + c;
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                stage_pair(imgA, row, 32 * s + 4 * q, 32 * s + 16 + 4 * q, h1B[s][t]);
-                stage_pair(imgD, row, 32 * s + 4 * q, 32 * s + 16 + 4 * q, dzB[s][t]);
-            }
-        }
+        stage_hidden(imgA, w, q, c, h1B);
+        stage_hidden(imgD, w, q, c, dz2B);
         __syncthreads();
         st.mark(9);   // stage-2 barrier + images + barrier
-#pragma unroll
-        for (int k = 0; k < KS; ++k) {
-            const bf16x8 dA = ld_tr(imgD, k, 16 * r, lane);
-#pragma unroll
-            for (int i = 0; i < C2; ++i) gW2[i] = MFMA32(dA, ld_tr(imgA, k, 16 * (C2 * h + i), lane), gW2[i]);
-            if (own_b2) gB = MFMA32(dA, ones, gB);
-        }
+        g.add_w2(imgD, imgA, w, lane, ones);
         st.mark(10);  // dW2
-        // ---- dA1 = W2^T dZ2 ; dZ1 = dA1 masked by H1 > 0   (dzB is overwritten by dZ1)
-        {
-            f32x4 acc[4][T];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-#pragma unroll
-                for (int t = 0; t < T; ++t) acc[mt][t] = zero4;
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    const bf16x8 wf = ld_frag(frag, F_W2T + 2 * mt + s, lane);
-#pragma unroll
-                    for (int t = 0; t < T; ++t) acc[mt][t] = MFMA32(wf, dzB[s][t], acc[mt][t]);
-                }
-            }
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int t = 0; t < T; ++t) dzB[s][t] = pack_masked(acc[2 * s][t], acc[2 * s + 1][t], h1B[s][t]);
-        }
+        hidden_grad<2>(frag, F_W2T, lane, dz2B, h1B, dz1B);   // dZ1 = (W2^T dZ2) masked by H1 > 0
         st.mark(11);  // dA1 chain
         // ================= stage 3: dW1 += dZ1^T (x) X^T
         __syncthreads();
 #pragma unroll
-        for (int t = 0; t < T; ++t) {
-            const int row = 16 * T * w + 16 * t + c;
-            stage_pair(imgA, row, 8 * q, 8 * q + 4, xC[t]);   // input features 8q .. 8q+7
-#pragma unroll
-            for (int s = 0; s < 2; ++s) stage_pair(imgD, row, 32 * s + 4 * q, 32 * s + 16 + 4 * q, dzB[s][t]);
-        }
+        for (int t = 0; t < 2; ++t) stage_pair(imgA, image_row(w, t, c), 8 * q, 8 * q + 4, xC[t]);   // input features 8q .. 8q+7
+        stage_hidden(imgD, w, q, c, dz1B);
         __syncthreads();
         st.mark(12);  // stage-3 barrier + images + barrier
-#pragma unroll
-        for (int k = 0; k < KS; ++k) {
-            const bf16x8 dA = ld_tr(imgD, k, 16 * r, lane);
-#pragma unroll
-            for (int i = 0; i < C1; ++i) gW1[i] = MFMA32(dA, ld_tr(imgA, k, 16 * (C1 * h + i), lane), gW1[i]);
-            if (own_b1) { if (NH == 1) gB1x = MFMA32(dA, ones, gB1x); else gB = MFMA32(dA, ones, gB); }
-        }
+        g.add_w1(imgD, imgA, w, lane, ones);
         st.mark(13);  // dW1
-        // ---- dX = W1^T dZ1 -> dfeat (level-major f32): lane holds features 16mt + 4q + r of its sample
-        f32x4 ax[2][T];
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-#pragma unroll
-            for (int t = 0; t < T; ++t) ax[mt][t] = zero4;
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const bf16x8 wf = ld_frag(frag, F_W1T + 2 * mt + s, lane);
-#pragma unroll
-                for (int t = 0; t < T; ++t) ax[mt][t] = MFMA32(wf, dzB[s][t], ax[mt][t]);
-            }
-        }
+        f32x4 ax[2][2];
+        through_transposed<2, 2>(frag, F_W1T, lane, dz1B, ax);   // dX = W1^T dZ1
         // ---- the one wait of the step: behind its last MFMA, in front of the dfeat stores
         __builtin_amdgcn_sched_barrier(0);
         pin_step(xB, up, ax);
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-                const int64_t m = m0 + 16 * t + c;
-                if (m < M) {
-                    const int lv = 8 * mt + 2 * q;  // features 16mt+4q+{0,1} = level lv, {2,3} = level lv+1
-                    char *df = reinterpret_cast<char *>(dfeat);
-                    const uint32_t ls = (uint32_t)a.level_stride, o0 = (((uint32_t)lv) * ls + (uint32_t)m) << 3;
-                    *reinterpret_cast<float2 *>(df + (size_t)o0) = make_float2(ax[mt][t][0], ax[mt][t][1]);
-                    *reinterpret_cast<float2 *>(df + (size_t)(o0 + (ls << 3))) = make_float2(ax[mt][t][2], ax[mt][t][3]);
-                }
-            }
-        }
+        store_dfeat(a, dfeat, m0, M, q, c, ax);
         st.mark(14);  // dX + stores issued
     }
 
     st.flush(16);
-    // ---- one slab per workgroup, every wave writes the tiles it owns (layout: mlp_shared.h)
-    float *slab = slabs + (int64_t)blockIdx.x * MLP_SLAB;
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-        const int o = 16 * r + 4 * q + rr;  // row of dW2 / dW1
-#pragma unroll
-        for (int i = 0; i < C2; ++i) slab[MLP_SL_W2 + o * MLP_HID + 16 * (C2 * h + i) + c] = gW2[i][rr];
-#pragma unroll
-        for (int i = 0; i < C1; ++i) slab[MLP_SL_W1 + o * MLP_IN + 16 * (C1 * h + i) + c] = gW1[i][rr];
-        if (c == 0) {
-            if (own_b2) slab[MLP_SL_B2 + o] = gB[rr];
-            if (own_b1) slab[MLP_SL_B1 + o] = NH == 1 ? gB1x[rr] : gB[rr];
-        }
-        // dW3: rows n3 = 4q + rr, columns (hidden) 16r + c
-        if (own_w3) slab[MLP_SL_W3 + (4 * q + rr) * MLP_HID + 16 * r + c] = gW3[rr];
-        if (own_b3 && c == 0) slab[MLP_SL_B3 + 4 * q + rr] = gB3[rr];
-    }
+    g.write_slab(slabs + (int64_t)blockIdx.x * MLP_SLAB, w, q, c);   // one slab per workgroup
 }
 
 }  // namespace lnerf
@@ -804,44 +766,30 @@ int launch_mlp_fragment_maps(int out_dim, int32_t *m1, int32_t *m2, int32_t *m3,
 }
 
 int launch_mlp_fragments_bf16(const MlpArgs &a, void *frag_out, bool backward_too, hipStream_t stream) {
-    const int n = backward_too ? F_SW : F_FWD;
+    const int n = backward_too ? F_ALL : F_FWD;
     hipLaunchKernelGGL(k_mlp_build_fragments, dim3((unsigned)(n * 2)), dim3(256), 0, stream, a, (__bf16 *)frag_out, n);
     LNERF_CHECK_LAUNCH("mlp(fragments)");
     return LNERF_OK;
 }
 
+// (the instantiation of a launch: a.feat_bf16 and a.out_dim == 5 are compile-time arms of both kernels)
 template <int WPS>
-static void launch_forward_wps(const MlpArgs &a, float *sigmas, float *rgbs, int blocks, hipStream_t stream) {
-    const dim3 g((unsigned)blocks), b(256);
-    if (a.feat_bf16) {
-        if (a.out_dim == 5) hipLaunchKernelGGL((k_mlp_forward_bf16<WPS, true, true>), g, b, 0, stream, a, sigmas, rgbs);
-        else hipLaunchKernelGGL((k_mlp_forward_bf16<WPS, true, false>), g, b, 0, stream, a, sigmas, rgbs);
-    } else {
-        if (a.out_dim == 5) hipLaunchKernelGGL((k_mlp_forward_bf16<WPS, false, true>), g, b, 0, stream, a, sigmas, rgbs);
-        else hipLaunchKernelGGL((k_mlp_forward_bf16<WPS, false, false>), g, b, 0, stream, a, sigmas, rgbs);
-    }
+static auto forward_kernel(const MlpArgs &a) {
+    return a.feat_bf16 ? (a.out_dim == 5 ? k_mlp_forward_bf16<WPS, true, true> : k_mlp_forward_bf16<WPS, true, false>)
+                       : (a.out_dim == 5 ? k_mlp_forward_bf16<WPS, false, true> : k_mlp_forward_bf16<WPS, false, false>);
 }
 int launch_mlp_forward_bf16(const MlpArgs &a, float *sigmas, float *rgbs, int blocks, int wps, hipStream_t stream) {
-    if (wps >= 3) launch_forward_wps<3>(a, sigmas, rgbs, blocks, stream);
-    else launch_forward_wps<2>(a, sigmas, rgbs, blocks, stream);
+    const auto k = wps >= 3 ? forward_kernel<3>(a) : forward_kernel<2>(a);
+    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(256), 0, stream, a, sigmas, rgbs);
     LNERF_CHECK_LAUNCH("mlp_forward(bf16)");
     return LNERF_OK;
 }
 
 int launch_mlp_backward_bf16(const MlpArgs &a, const float *sigmas, const float *dsigmas, const float *drgbs,
                              float *dfeat, float *slabs, int blocks, hipStream_t stream) {
-    const dim3 g((unsigned)blocks), b(256);
-    if (a.feat_bf16) {
-        if (a.out_dim == 5)
-            hipLaunchKernelGGL((k_mlp_backward_bf16<4, 2, true, true>), g, b, 0, stream, a, sigmas, dsigmas, drgbs, dfeat, slabs);
-        else
-            hipLaunchKernelGGL((k_mlp_backward_bf16<4, 2, true, false>), g, b, 0, stream, a, sigmas, dsigmas, drgbs, dfeat, slabs);
-    } else {
-        if (a.out_dim == 5)
-            hipLaunchKernelGGL((k_mlp_backward_bf16<4, 2, false, true>), g, b, 0, stream, a, sigmas, dsigmas, drgbs, dfeat, slabs);
-        else
-            hipLaunchKernelGGL((k_mlp_backward_bf16<4, 2, false, false>), g, b, 0, stream, a, sigmas, dsigmas, drgbs, dfeat, slabs);
-    }
+    const auto k = a.feat_bf16 ? (a.out_dim == 5 ? k_mlp_backward_bf16<true, true> : k_mlp_backward_bf16<true, false>)
+                               : (a.out_dim == 5 ? k_mlp_backward_bf16<false, true> : k_mlp_backward_bf16<false, false>);
+    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(256), 0, stream, a, sigmas, dsigmas, drgbs, dfeat, slabs);
     LNERF_CHECK_LAUNCH("mlp_backward(bf16)");
     return LNERF_OK;
 }

@@ -26,7 +26,7 @@ struct MlpArgs {
     const int32_t *m_dev;
     const void *frag_global;  // bf16 path: the weight fragments, built once per launch (NULL: every workgroup builds its own)
 };
-constexpr size_t MLP_FRAG_BYTES = LNERF_MLP_FRAGMENT_BYTES;  // room for the 33 one-KiB fragments of the bf16 path at the head of a workspace
+constexpr size_t MLP_FRAG_BYTES = LNERF_MLP_FRAGMENT_BYTES;  // room for the 30 one-KiB fragments of the bf16 path at the head of a workspace
 
 // (split into the load and the arithmetic: the bf16 forward requests a position one step before it evaluates the blob)
 struct Pos3 { float x, y, z; };

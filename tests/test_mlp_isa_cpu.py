@@ -7,7 +7,7 @@ select behind a load, a load used under a lane predicate only, a run-time branch
 pending at the back edge -- each puts a wait (mostly vmcnt(0), which also covers the previous stores) directly behind
 the loads it was meant to overlap, and the source looks the same.  So this test compiles the file to gfx950 assembly
 with the flags of the product build and reads the two loops that the benched configuration runs: the forward and the
-<4, 2> backward with bf16 features and out_dim 5.  No GPU is needed.
+backward (four waves of two tiles) with bf16 features and out_dim 5.  No GPU is needed.
 
 Terms.  The STEP LOOP of a kernel is the innermost loop (label .. backward branch to it) that holds all of the kernel's
 v_mfma.  The instructions that are RELEVANT to the vector-memory queue are vector-memory instructions (global_*,
@@ -45,7 +45,7 @@ VGPR_LIMIT = {"forward": 168, "backward": 256}
 # (mangled-name pattern of the instantiation the bench runs: bf16 features = Lb1, out_dim 5 = Lb1)
 BENCHED = {
     "forward": r"_ZN5lnerf18k_mlp_forward_bf16ILi3ELb1ELb1EEE\w+",
-    "backward": r"_ZN5lnerf19k_mlp_backward_bf16ILi4ELi2ELb1ELb1EEE\w+",
+    "backward": r"_ZN5lnerf19k_mlp_backward_bf16ILb1ELb1EEE\w+",
 }
 
 
@@ -198,3 +198,23 @@ def test_fewer_loads_than_the_parent(kernels, which):
     rep = loop_report(step_loop(_benched(kernels, which)[0]))
     assert rep["global_loads"] <= PARENT[which]["global_loads"], (rep, PARENT[which])
     assert rep["waits_under_loads"] < PARENT[which]["waits_under_loads"], (rep, PARENT[which])
+
+
+# The arithmetic of a step, counted in the source (csrc/mlp_bf16.hip).  Forward: layers 1-2 8 + 16, layer 3 4.  Backward:
+# layers 1-2 8 + 16; dW3 / db3 4 k-steps x 2; dA2 8; dW2 / db2 4 x 5; dA1 16; dW1 / db1 4 x 3; dX 8.  One pair of
+# barriers per weight-gradient stage.
+MFMA_PER_STEP = {"forward": 8 + 16 + 4, "backward": 8 + 16 + 4 * 2 + 8 + 4 * 5 + 16 + 4 * 3 + 8}   # 28, 96
+BARRIERS_PER_BACKWARD_STEP = 6
+
+
+@WHICH
+def test_arithmetic_of_a_step(kernels, which):
+    """f) The named parts of the step neither duplicate nor drop arithmetic: the step loop holds exactly the v_mfma the
+    source counts (28 forward, 96 backward), and the backward's its six s_barrier."""
+    loop = step_loop(_benched(kernels, which)[0])
+    mfma = sum(1 for ins in loop if ins.startswith("v_mfma"))
+    barriers = sum(1 for ins in loop if ins.startswith("s_barrier"))
+    print("%s step loop: %d v_mfma, %d s_barrier" % (which, mfma, barriers))
+    assert mfma == MFMA_PER_STEP[which], (which, mfma)
+    if which == "backward":
+        assert barriers == BARRIERS_PER_BACKWARD_STEP, barriers

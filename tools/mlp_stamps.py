@@ -19,10 +19,11 @@ import torch  # noqa: E402
 
 FWD = ["0 next step's loads issued", "1 layer 1 (8 MFMA) + relu/pack", "2 layer 2 (16 MFMA) + relu/pack",
        "3 layer 3 (4 MFMA) + exp + stores issued"]
-BWD = {0: "0 next loads issued, dZ3 fragment", 4: "4 __syncthreads_or", 1: "1 layer 1 + pack", 2: "2 layer 2 + pack",
-       5: "5 barrier (images free)", 6: "6 stage-1 images + barrier", 7: "7 dW3 (ld_tr + MFMA)", 8: "8 dA2 chain + mask/pack",
-       9: "9 barrier + stage-2 images + barrier", 10: "10 dW2", 11: "11 dA1 chain + mask/pack",
-       12: "12 barrier + stage-3 images + barrier", 13: "13 dW1", 14: "14 dX + stores issued"}
+BWD = {4: "4 next step's loads issued (load_upstream, load_x) + dZ3 fragment", 1: "1 layer 1 + pack", 2: "2 layer 2 + pack",
+       5: "5 barrier (images free)", 6: "6 stage-1 images (stage_hidden H2, dZ3) + barrier", 7: "7 dW3 / db3 (add_w3)",
+       8: "8 dZ2 (hidden_grad through W3^T)", 9: "9 barrier + stage-2 images (H1, dZ2) + barrier", 10: "10 dW2 / db2 (add_w2)",
+       11: "11 dZ1 (hidden_grad through W2^T)", 12: "12 barrier + stage-3 images (X, dZ1) + barrier", 13: "13 dW1 / db1 (add_w1)",
+       14: "14 dX (through_transposed W1^T) + the step's one wait + stores issued (store_dfeat)"}
 
 
 def main():
@@ -56,7 +57,7 @@ def main():
     for i, name in enumerate(FWD):
         res["forward_cycles_per_step"][name] = round(buf[i] / n / steps, 1)
     res["forward_cycles_per_step"]["total"] = round(sum(buf[i] for i in range(4)) / n / steps, 1)
-    for i in sorted(BWD, key=lambda k: [0, 4, 1, 2, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14].index(k)):
+    for i in sorted(BWD, key=lambda k: [4, 1, 2, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14].index(k)):
         res["backward_cycles_per_step"][BWD[i]] = round(buf[16 + i] / n / steps, 1)
     res["backward_cycles_per_step"]["total"] = round(sum(buf[16 + i] for i in range(16)) / n / steps, 1)
     print(json.dumps(res, indent=1))

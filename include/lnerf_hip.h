@@ -421,7 +421,9 @@ int lnerf_occ_update_mean(float *grid_level, int64_t n_cells, const uint32_t *in
                           lnerf_stream_t stream);
 int lnerf_occ_mean(const float *grid, int64_t n, float *mean_dev, float *scratch256, lnerf_stream_t stream);
 
-/* ---- H11: background net, frequency encoding (degree 6: 39 dims) -> 64 -> C, one thread per ray. */
+/* ---- H11: background net, frequency encoding (degree 6: 39 dims) -> 64 -> C (1..4), one thread per ray.
+ * out [N,C] is overwritten.  lnerf_bg_backward ACCUMULATES: it adds the gradients of the N rays to what dw1 [64,39],
+ * db1 [64], dw2 [C,64], db2 [C] hold (atomic adds per 64-ray tile), so the caller zeroes them for a plain gradient. */
 int lnerf_bg_forward(const float *dirs, int64_t N, const float *w1, const float *b1, const float *w2, const float *b2,
                      int C, float *out, lnerf_stream_t stream);
 int lnerf_bg_backward(const float *dirs, int64_t N, const float *w1, const float *b1, const float *w2, const float *b2,

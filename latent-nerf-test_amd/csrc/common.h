@@ -80,6 +80,9 @@ __device__ __forceinline__ float dpp_f(float v) {
 __device__ __forceinline__ int lane_prev_i(int v, int fill) {
     return __builtin_amdgcn_update_dpp(fill, v, 0x138, 0xf, 0xf, false);
 }
+__device__ __forceinline__ float lane_prev_f(float v, float fill) {
+    return __int_as_float(lane_prev_i(__float_as_int(v), __float_as_int(fill)));
+}
 
 // inclusive wave scan (sum) over 64 lanes: 4 row_shr steps inside each 16-lane row, then the row
 // totals are carried across rows with row_bcast:15 (rows 1,3) and row_bcast:31 (rows 2,3)

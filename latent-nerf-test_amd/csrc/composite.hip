@@ -37,6 +37,14 @@ __device__ __forceinline__ Chunk<C> load_chunk(const float *__restrict__ sigmas,
     return k;
 }
 
+// Optical depth in front of this lane's sample, from the chunk's inclusive scan `inc` and the depth `carry` of the chunks
+// before it: the NEIGHBOURING lane's inclusive sum (lane 0: nothing), never `inc - tau`.  The lane's own tau can be
+// arbitrarily large (sigma = exp(h) is unclamped, a surface sample has sigma dt ~ 1e4 and more); subtracting it back out
+// of a sum that contains it rounds the small prefix in front of it away (error 2^-24 tau in excl, i.e. in T and the
+// weight; inf - inf = NaN at sigma = +inf).  Forward and backward both call this: the backward's `keep` has to
+// reproduce the forward's decisions bit for bit.
+__device__ __forceinline__ float exclusive_depth(float inc, float carry) { return lane_prev_f(inc, 0.f) + carry; }
+
 // One ray's forward loop over its span: each lane's share of weights_sum, depth and the C colour sums (no background);
 // the caller adds them across the wave.
 template <int C>
@@ -58,7 +66,7 @@ __device__ __forceinline__ void composite_ray_fwd(const float *__restrict__ sigm
         const float dt = cur.dt, t = cur.t;
         const float tau = cur.sigma * dt;     // (invalid lanes carry zeros)
         const float inc = wave_inclusive_sum(tau);
-        const float excl = (inc - tau) + carry;
+        const float excl = exclusive_depth(inc, carry);
         const float T = expf(-excl);
         const float alpha = 1.0f - expf(-tau);
         const float w = (valid && T >= T_thresh) ? alpha * T : 0.f;
@@ -207,7 +215,7 @@ __device__ __forceinline__ void composite_ray_bwd(const float *__restrict__ sigm
         const float dt = cur.dt, t = cur.t;
         const float tau = cur.sigma * dt;
         const float inc = wave_inclusive_sum(tau);
-        const float excl = (inc - tau) + carry_tau;
+        const float excl = exclusive_depth(inc, carry_tau);
         const float T = expf(-excl);
         const float e = expf(-tau);
         const float alpha = 1.0f - e;

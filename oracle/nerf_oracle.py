@@ -649,7 +649,9 @@ def composite_rays_train(sigmas, rgbs, deltas, rays, T_thresh: float = 1e-4, bg_
         dt = torch.where(valid, deltas[idx, 0], torch.zeros(1))
         tt = torch.where(valid, deltas[idx, 1], torch.zeros(1))
         tau = sg * dt
-        csum = torch.cumsum(tau, 1) - tau  # exclusive
+        # exclusive prefix = the inclusive sum shifted by one slot (never `cumsum - tau`: a large tau would round the
+        # small prefix in front of it away, and tau = inf would give inf - inf)
+        csum = torch.cat([torch.zeros_like(tau[:, :1]), torch.cumsum(tau, 1)[:, :-1]], 1)
         T = torch.exp(-csum)
         alpha = 1.0 - torch.exp(-tau)
         keep = valid & (T >= T_thresh)

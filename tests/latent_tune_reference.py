@@ -24,7 +24,9 @@ def weights64(sigmas, deltas, rays, T_thresh=1e-4):
     sg = torch.where(valid, sigmas[idx], zero)
     dt = torch.where(valid, deltas[idx, 0], zero)
     tau = sg * dt
-    csum = torch.cumsum(tau, 1) - tau  # exclusive
+    # exclusive prefix = the inclusive sum shifted by one slot (never `cumsum - tau`: a large tau would round the
+    # small prefix in front of it away, and tau = inf would give inf - inf)
+    csum = torch.cat([torch.zeros_like(tau[:, :1]), torch.cumsum(tau, 1)[:, :-1]], 1)
     T = torch.exp(-csum)
     alpha = 1.0 - torch.exp(-tau)
     keep = valid & (T >= T_thresh)

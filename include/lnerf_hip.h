@@ -450,6 +450,32 @@ int lnerf_raster_prepare(const float *verts, int n_verts, const int32_t *faces, 
                          float *face_z, float *face_xy, lnerf_stream_t stream);
 int lnerf_rasterize(int H, int W, const float *face_z, const float *face_xy, int n_faces, int32_t *face_idx,
                     float *bary, lnerf_stream_t stream);
+/* ---- B views per call on a tile-culled rasteriser.  Additive to ABI 7.  lnerf_raster_prepare / lnerf_rasterize above
+ * stay as the definition these two are held to.
+ * lnerf_raster_prepare_batch: cams_dev = DEVICE [B,14] f32, each row laid out as cam_host.  face_z [B,F,3] and face_xy
+ *   [B,F,3,2] use lnerf_raster_prepare's arithmetic unchanged: slice b equals a single-view call with camera b bit for
+ *   bit.  face_box [B,F] x 4 int16 (8-byte aligned) = the face's inclusive pixel range (j_lo, j_hi, i_lo, i_hi) in the
+ *   H x W image, which is why H and W are arguments of THIS call (1 <= H, W <= 32767; 1 <= B <= 65535).
+ * The box rule, in f32, every operation rounded on its own (no fused multiply-add), in this order:
+ *   1. !(z0 < 0 && z1 < 0 && z2 < 0), or area == 0 with area = (x1-x0)*(y2-y0) - (x2-x0)*(y1-y0)  (the faces the
+ *      rasteriser rejects outright)                                   -> the empty box (0, -1, 0, -1);
+ *   2. any of the six xy coordinates NaN or infinite                  -> the whole image (0, W-1, 0, H-1);
+ *   3. with the pixel centres px = (2j+1)/W - 1, py = 1 - (2i+1)/H and min / max over the three corners:
+ *        j_lo = max(floor(((min_x + 1)*W - 1)*0.5) - 1, 0)      j_hi = min(ceil(((max_x + 1)*W - 1)*0.5) + 1, W-1)
+ *        i_lo = max(floor(((1 - max_y)*H - 1)*0.5) - 1, 0)      i_hi = min(ceil(((1 - min_y)*H - 1)*0.5) + 1, H-1)
+ *      (one pixel of padding each side, then clipped to the image; evaluated in f32 before the conversion to int16);
+ *   4. j_lo > j_hi or i_lo > i_hi (wholly off the image)              -> the empty box (0, -1, 0, -1).
+ * lnerf_rasterize_batch: face_idx [B,H*W], bary [B,H*W,3] = lnerf_rasterize's result restricted to the (pixel, face)
+ *   pairs whose pixel lies in the face's box: the same per-face test, the same depth, the same tie rule (the lower face
+ *   index wins an exact tie).  Where lnerf_rasterize accepts no pair outside a box the two agree bit for bit.  face_box
+ *   is an input: any boxes may be given (e.g. from another source than the call above).  A pixel no face reaches gets
+ *   face_idx = -1, bary = 0.
+ * Both: no allocation, no synchronisation, no host read-back; capturable. */
+int lnerf_raster_prepare_batch(const float *verts, int n_verts, const int32_t *faces, int n_faces,
+                               const float *cams_dev, int B, int H, int W, float *face_z, float *face_xy,
+                               int16_t *face_box, lnerf_stream_t stream);
+int lnerf_rasterize_batch(int B, int H, int W, const float *face_z, const float *face_xy, const int16_t *face_box,
+                          int n_faces, int32_t *face_idx, float *bary, lnerf_stream_t stream);
 int lnerf_interpolate_attributes(const int32_t *face_idx, const float *bary, const float *attr, int n_pixels, int D,
                                  float *feat, lnerf_stream_t stream);
 int lnerf_interpolate_attributes_backward(const int32_t *face_idx, const float *bary, const float *dfeat,

@@ -15,6 +15,18 @@ struct Cam {
     float fx, fy;   // 1 / tan(fov/2) (/ ratio)
 };
 
+// camera-space z and NDC xy of one face corner: the arithmetic both prepare kernels share
+__device__ __forceinline__ void prepare_corner(const float *__restrict__ verts, int v, const Cam &cam, float &cz,
+                                               float &ix, float &iy) {
+    const float x = verts[v * 3] - cam.pos[0], y = verts[v * 3 + 1] - cam.pos[1], z = verts[v * 3 + 2] - cam.pos[2];
+    const float cx = fmaf(cam.rot[0], x, fmaf(cam.rot[1], y, cam.rot[2] * z));
+    const float cy = fmaf(cam.rot[3], x, fmaf(cam.rot[4], y, cam.rot[5] * z));
+    cz = fmaf(cam.rot[6], x, fmaf(cam.rot[7], y, cam.rot[8] * z));
+    // image = (x * fx, y * fy) / (z * -1)
+    ix = cx * cam.fx / (-cz);
+    iy = cy * cam.fy / (-cz);
+}
+
 __global__ void __launch_bounds__(256)
 k_raster_prepare(const float *__restrict__ verts, const int32_t *__restrict__ faces, int F, Cam cam,
                  float *__restrict__ face_z, float *__restrict__ face_xy) {
@@ -22,19 +34,91 @@ k_raster_prepare(const float *__restrict__ verts, const int32_t *__restrict__ fa
     if (f >= F) return;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const int v = faces[f * 3 + k];
-        const float x = verts[v * 3] - cam.pos[0], y = verts[v * 3 + 1] - cam.pos[1], z = verts[v * 3 + 2] - cam.pos[2];
-        const float cx = fmaf(cam.rot[0], x, fmaf(cam.rot[1], y, cam.rot[2] * z));
-        const float cy = fmaf(cam.rot[3], x, fmaf(cam.rot[4], y, cam.rot[5] * z));
-        const float cz = fmaf(cam.rot[6], x, fmaf(cam.rot[7], y, cam.rot[8] * z));
+        float cz, ix, iy;
+        prepare_corner(verts, faces[f * 3 + k], cam, cz, ix, iy);
         face_z[f * 3 + k] = cz;
-        // image = (x * fx, y * fy) / (z * -1)
-        face_xy[(f * 3 + k) * 2] = cx * cam.fx / (-cz);
-        face_xy[(f * 3 + k) * 2 + 1] = cy * cam.fy / (-cz);
+        face_xy[(f * 3 + k) * 2] = ix;
+        face_xy[(f * 3 + k) * 2 + 1] = iy;
     }
 }
 
+// The pixel box of a face (the rule is stated in include/lnerf_hip.h): inclusive (j_lo, j_hi, i_lo, i_hi), padded by one
+// pixel and clipped to the image; (0, -1, 0, -1) when the face can win no pixel.  f32, no fused multiply-adds.
+struct alignas(8) Box { int16_t j_lo, j_hi, i_lo, i_hi; };
+
+__device__ __forceinline__ Box face_box(const float x[3], const float y[3], const float z[3], int H, int W) {
+    const Box empty = {0, -1, 0, -1};
+    if (!(z[0] < 0.f && z[1] < 0.f && z[2] < 0.f)) return empty;   // k_rasterize rejects it: behind the camera
+    const float area = (x[1] - x[0]) * (y[2] - y[0]) - (x[2] - x[0]) * (y[1] - y[0]);
+    if (area == 0.f) return empty;                                  // ... or degenerate
+    const float big = 3.4028234664e38f;
+    bool finite = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) finite = finite && fabsf(x[k]) <= big && fabsf(y[k]) <= big;
+    if (!finite) return Box{0, (int16_t)(W - 1), 0, (int16_t)(H - 1)};
+    const float xmin = fminf(fminf(x[0], x[1]), x[2]), xmax = fmaxf(fmaxf(x[0], x[1]), x[2]);
+    const float ymin = fminf(fminf(y[0], y[1]), y[2]), ymax = fmaxf(fmaxf(y[0], y[1]), y[2]);
+    const float Wf = (float)W, Hf = (float)H;
+    const float j_lo = fmaxf(floorf(((xmin + 1.0f) * Wf - 1.0f) * 0.5f) - 1.0f, 0.0f);
+    const float j_hi = fminf(ceilf(((xmax + 1.0f) * Wf - 1.0f) * 0.5f) + 1.0f, Wf - 1.0f);
+    const float i_lo = fmaxf(floorf(((1.0f - ymax) * Hf - 1.0f) * 0.5f) - 1.0f, 0.0f);
+    const float i_hi = fminf(ceilf(((1.0f - ymin) * Hf - 1.0f) * 0.5f) + 1.0f, Hf - 1.0f);
+    if (j_lo > j_hi || i_lo > i_hi) return empty;                   // wholly off the image
+    return Box{(int16_t)j_lo, (int16_t)j_hi, (int16_t)i_lo, (int16_t)i_hi};
+}
+
+// B views of one mesh: blockIdx.y = view; the cameras are read from device memory
+__global__ void __launch_bounds__(256)
+k_raster_prepare_batch(const float *__restrict__ verts, const int32_t *__restrict__ faces, int F,
+                       const float *__restrict__ cams, int H, int W, float *__restrict__ face_z,
+                       float *__restrict__ face_xy, Box *__restrict__ boxes) {
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    if (f >= F) return;
+    const int b = blockIdx.y;
+    Cam cam;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) cam.rot[i] = cams[b * 14 + i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) cam.pos[i] = cams[b * 14 + 9 + i];
+    cam.fx = cams[b * 14 + 12];
+    cam.fy = cams[b * 14 + 13];
+    const int64_t bf = (int64_t)b * F + f;
+    float x[3], y[3], z[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        prepare_corner(verts, faces[f * 3 + k], cam, z[k], x[k], y[k]);
+        face_z[bf * 3 + k] = z[k];
+        face_xy[(bf * 3 + k) * 2] = x[k];
+        face_xy[(bf * 3 + k) * 2 + 1] = y[k];
+    }
+    boxes[bf] = face_box(x, y, z, H, W);
+}
+
 constexpr int RTILE = 128;  // faces per LDS tile
+
+// What one pixel does with one face, shared by both rasterisers: inside test, perspective-correct weights and depth,
+// and the z-buffer update (strictly closer wins, so of equal depths the face tested first -- the lower index -- stays).
+__device__ __forceinline__ void raster_face_test(float px, float py, float x0, float y0, float x1, float y1, float x2,
+                                                 float y2, float z0, float z1, float z2, int f, float &best_z,
+                                                 int &best_f, float &bw0, float &bw1, float &bw2) {
+    if (!(z0 < 0.f && z1 < 0.f && z2 < 0.f)) return;  // behind the camera
+    const float area = (x1 - x0) * (y2 - y0) - (x2 - x0) * (y1 - y0);
+    if (area == 0.f) return;
+    const float e0 = (x1 - px) * (y2 - py) - (x2 - px) * (y1 - py);  // weight of vertex 0
+    const float e1 = (x2 - px) * (y0 - py) - (x0 - px) * (y2 - py);  // weight of vertex 1
+    const float inv = 1.0f / area;
+    const float w0 = e0 * inv, w1 = e1 * inv, w2 = 1.0f - w0 - w1;
+    if (w0 < 0.f || w1 < 0.f || w2 < 0.f) return;
+    // perspective-correct weights and depth
+    const float q0 = w0 / z0, q1 = w1 / z1, q2 = w2 / z2;
+    const float qs = q0 + q1 + q2;
+    const float z = 1.0f / qs;   // (sum w_k / z_k)^-1
+    if (z > best_z) {            // strictly closer; ties keep the lower face index
+        best_z = z;
+        best_f = f;
+        bw0 = q0 * z; bw1 = q1 * z; bw2 = q2 * z;
+    }
+}
 
 // one thread per pixel; faces stream through LDS
 __global__ void __launch_bounds__(256)
@@ -56,34 +140,129 @@ k_rasterize(int H, int W, const float *__restrict__ face_z, const float *__restr
         for (int k = threadIdx.x; k < nf * 6; k += 256) s_xy[k] = face_xy[(int64_t)f0 * 6 + k];
         for (int k = threadIdx.x; k < nf * 3; k += 256) s_z[k] = face_z[(int64_t)f0 * 3 + k];
         __syncthreads();
-        for (int f = 0; f < nf; ++f) {
-            const float x0 = s_xy[f * 6], y0 = s_xy[f * 6 + 1], x1 = s_xy[f * 6 + 2], y1 = s_xy[f * 6 + 3];
-            const float x2 = s_xy[f * 6 + 4], y2 = s_xy[f * 6 + 5];
-            const float z0 = s_z[f * 3], z1 = s_z[f * 3 + 1], z2 = s_z[f * 3 + 2];
-            if (!(z0 < 0.f && z1 < 0.f && z2 < 0.f)) continue;  // behind the camera
-            const float area = (x1 - x0) * (y2 - y0) - (x2 - x0) * (y1 - y0);
-            if (area == 0.f) continue;
-            const float e0 = (x1 - px) * (y2 - py) - (x2 - px) * (y1 - py);  // weight of vertex 0
-            const float e1 = (x2 - px) * (y0 - py) - (x0 - px) * (y2 - py);  // weight of vertex 1
-            const float inv = 1.0f / area;
-            const float w0 = e0 * inv, w1 = e1 * inv, w2 = 1.0f - w0 - w1;
-            if (w0 < 0.f || w1 < 0.f || w2 < 0.f) continue;
-            // perspective-correct weights and depth
-            const float q0 = w0 / z0, q1 = w1 / z1, q2 = w2 / z2;
-            const float qs = q0 + q1 + q2;
-            const float z = 1.0f / qs;   // (sum w_k / z_k)^-1
-            if (z > best_z) {            // strictly closer; ties keep the lower face index
-                best_z = z;
-                best_f = f0 + f;
-                bw0 = q0 * z; bw1 = q1 * z; bw2 = q2 * z;
-            }
-        }
+        for (int f = 0; f < nf; ++f)
+            raster_face_test(px, py, s_xy[f * 6], s_xy[f * 6 + 1], s_xy[f * 6 + 2], s_xy[f * 6 + 3], s_xy[f * 6 + 4],
+                             s_xy[f * 6 + 5], s_z[f * 3], s_z[f * 3 + 1], s_z[f * 3 + 2], f0 + f, best_z, best_f, bw0,
+                             bw1, bw2);
     }
     if (in) {
         face_idx[p] = best_f;
         bary[p * 3] = bw0; bary[p * 3 + 1] = bw1; bary[p * 3 + 2] = bw2;
     }
 }
+
+// Tile-culled rasteriser for B views: one workgroup of NW waves per (view, TS x TS pixel tile).  The workgroup walks the
+// view's faces in ascending order, 64 * NW at a time: each lane compares one face's box with the tile rectangle (8 bytes
+// per face, consecutive lanes read consecutive boxes), the survivors are compacted in ascending order into an LDS queue
+// of face records, and when the queue cannot take another round -- and once more at the end -- the pixels drain it with
+// raster_face_test.  The tile is G = TS * TS / 64 groups of 64 pixels, and S = NW / G waves share a group: wave slice s
+// takes the queue entries s, s + S, ... in ascending order, so each holds the lowest index among its own closest faces,
+// and the closing merge takes the closest of the S candidates, the lower face index on an exact tie: the result of one
+// ascending scan with k_rasterize's strict comparison.  No global lists, no atomics.
+struct alignas(16) QFace { float x0, y0, x1, y1, x2, y2, z0, z1, z2; int f; int pad[2]; };
+
+template <int TS, int NW>
+__global__ void __launch_bounds__(64 * NW)
+k_rasterize_tiles(int H, int W, const float *__restrict__ face_z, const float *__restrict__ face_xy,
+                  const Box *__restrict__ boxes, int F, int32_t *__restrict__ face_idx, float *__restrict__ bary) {
+    constexpr int NT = 64 * NW, G = TS * TS / 64, S = NW / G, Q = 2 * NT;
+    static_assert(TS * TS % 64 == 0 && NW % G == 0, "whole waves per pixel group");
+    static_assert(Q * sizeof(QFace) >= NT * 5 * sizeof(float), "the merge reuses the queue's memory");
+    __shared__ QFace s_q[Q];
+    __shared__ int s_cnt[2][NW];
+    const int t = threadIdx.x, wave = t >> 6;
+    const int slice = wave / G, pl = (wave % G) * 64 + (t & 63);   // this thread's queue slice and pixel of the tile
+    const int b = blockIdx.z;
+    const int tj0 = blockIdx.x * TS, ti0 = blockIdx.y * TS;
+    const int j = tj0 + pl % TS, i = ti0 + pl / TS;
+    const bool in = i < H && j < W;
+    const float px = (2.0f * (float)j + 1.0f) / (float)W - 1.0f;
+    const float py = 1.0f - (2.0f * (float)i + 1.0f) / (float)H;
+    face_z += (int64_t)b * F * 3;
+    face_xy += (int64_t)b * F * 6;
+    boxes += (int64_t)b * F;
+    float best_z = -3.0e38f;
+    int best_f = -1;
+    float bw0 = 0.f, bw1 = 0.f, bw2 = 0.f;
+    int qn = 0;   // queue length: the same value in every thread
+
+    auto drain = [&]() {
+        __syncthreads();
+        for (int q = slice; q < qn; q += S) {
+            const QFace r = s_q[q];   // every lane of the wave reads the same record: a broadcast
+            raster_face_test(px, py, r.x0, r.y0, r.x1, r.y1, r.x2, r.y2, r.z0, r.z1, r.z2, r.f, best_z, best_f, bw0,
+                             bw1, bw2);
+        }
+        __syncthreads();
+        qn = 0;
+    };
+
+    const Box none = {0, -1, 0, -1};
+    Box next = t < F ? boxes[t] : none;
+    int parity = 0;
+    for (int f0 = 0; f0 < F; f0 += NT, parity ^= 1) {
+        const Box box = next;
+        const int f = f0 + t, fn = f + NT;
+        next = fn < F ? boxes[fn] : none;   // in flight while this round is compacted
+        if (qn + NT > Q) drain();
+        const bool hit = box.j_lo <= tj0 + TS - 1 && box.j_hi >= tj0 && box.i_lo <= ti0 + TS - 1 && box.i_hi >= ti0;
+        const unsigned long long m = __ballot(hit);
+        int at = qn + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+        int total = __popcll(m);
+        if (NW > 1) {
+            if ((t & 63) == 0) s_cnt[parity][wave] = total;
+            __syncthreads();
+            total = 0;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) {
+                const int c = s_cnt[parity][w];
+                if (w < wave) at += c;
+                total += c;
+            }
+        }
+        if (hit) {
+            const float *xy = face_xy + (int64_t)f * 6, *z = face_z + (int64_t)f * 3;
+            QFace r;
+            r.x0 = xy[0]; r.y0 = xy[1]; r.x1 = xy[2]; r.y1 = xy[3]; r.x2 = xy[4]; r.y2 = xy[5];
+            r.z0 = z[0]; r.z1 = z[1]; r.z2 = z[2];
+            r.f = f; r.pad[0] = 0; r.pad[1] = 0;
+            s_q[at] = r;
+        }
+        qn += total;
+    }
+    drain();
+    if (S > 1) {   // the slices' candidates of a pixel -> slice 0 (the drain ended with a barrier: the queue is free)
+        float *mz = reinterpret_cast<float *>(s_q);
+        int *mf = reinterpret_cast<int *>(mz + NT);
+        float *mw = mz + 2 * NT;
+        const int slot = slice * (64 * G) + pl;
+        mz[slot] = best_z; mf[slot] = best_f;
+        mw[slot] = bw0; mw[NT + slot] = bw1; mw[2 * NT + slot] = bw2;
+        __syncthreads();
+        if (slice != 0) return;
+        for (int s2 = 1; s2 < S; ++s2) {
+            const int o = s2 * (64 * G) + pl;
+            const float z2 = mz[o];
+            const int f2 = mf[o];
+            if (z2 > best_z || (z2 == best_z && f2 < best_f)) {
+                best_z = z2; best_f = f2;
+                bw0 = mw[o]; bw1 = mw[NT + o]; bw2 = mw[2 * NT + o];
+            }
+        }
+    }
+    if (in) {
+        const int64_t p = ((int64_t)b * H + i) * W + j;
+        face_idx[p] = best_f;
+        bary[p * 3] = bw0; bary[p * 3 + 1] = bw1; bary[p * 3 + 2] = bw2;
+    }
+}
+
+// Two shapes of the kernel, chosen from the launch's size alone (measured: DESIGN.md, "Batched views on a tile-culled
+// rasteriser").  Up to RASTER_SMALL_MAX_TILES 8 x 8 tiles over all views there are fewer tiles than the chip has room
+// for: 8 x 8 tiles of 16 waves (each wave a sixteenth of the queue) put the most waves on every face walk and drain.
+// Beyond that the tiles alone fill the chip and the box walk dominates: 16 x 16 tiles of 4 waves walk a quarter of the
+// boxes per pixel.
+constexpr int RASTER_SMALL_MAX_TILES = 2048;
 
 // feat[p, :] = sum_k bary[p,k] * attr[face_idx[p], k, :]   (0 on background)
 __global__ void __launch_bounds__(256)
@@ -226,6 +405,40 @@ int lnerf_rasterize(int H, int W, const float *face_z, const float *face_xy, int
     hipLaunchKernelGGL(k_rasterize, dim3((unsigned)div_up((int64_t)H * W, 256)), dim3(256), 0, as_stream(stream), H, W,
                        face_z, face_xy, n_faces, face_idx, bary);
     LNERF_CHECK_LAUNCH("rasterize");
+    return LNERF_OK;
+}
+
+int lnerf_raster_prepare_batch(const float *verts, int n_verts, const int32_t *faces, int n_faces,
+                               const float *cams_dev, int B, int H, int W, float *face_z, float *face_xy,
+                               int16_t *face_box, lnerf_stream_t stream) {
+    LNERF_REQUIRE(n_verts > 0 && n_faces > 0, "raster_prepare_batch: empty mesh");
+    LNERF_REQUIRE(B >= 1 && B <= 65535, "raster_prepare_batch: B must be in [1, 65535]");
+    LNERF_REQUIRE(H >= 1 && W >= 1 && H <= 32767 && W <= 32767, "raster_prepare_batch: H and W must be in [1, 32767]");
+    LNERF_REQUIRE(verts && faces && cams_dev && face_z && face_xy && face_box, "raster_prepare_batch: null pointer");
+    hipLaunchKernelGGL(k_raster_prepare_batch, dim3((unsigned)div_up(n_faces, 256), (unsigned)B), dim3(256), 0,
+                       as_stream(stream), verts, faces, n_faces, cams_dev, H, W, face_z, face_xy,
+                       reinterpret_cast<Box *>(face_box));
+    LNERF_CHECK_LAUNCH("raster_prepare_batch");
+    return LNERF_OK;
+}
+
+int lnerf_rasterize_batch(int B, int H, int W, const float *face_z, const float *face_xy, const int16_t *face_box,
+                          int n_faces, int32_t *face_idx, float *bary, lnerf_stream_t stream) {
+    LNERF_REQUIRE(B >= 1 && B <= 65535, "rasterize_batch: B must be in [1, 65535]");
+    LNERF_REQUIRE(H >= 1 && W >= 1 && H <= 32767 && W <= 32767, "rasterize_batch: H and W must be in [1, 32767]");
+    LNERF_REQUIRE(n_faces > 0, "rasterize_batch: no faces");
+    LNERF_REQUIRE(face_z && face_xy && face_box && face_idx && bary, "rasterize_batch: null pointer");
+    LNERF_REQUIRE(((uintptr_t)face_box & 7) == 0, "rasterize_batch: face_box must be 8-byte aligned");
+    const Box *boxes = reinterpret_cast<const Box *>(face_box);
+    if ((int64_t)B * div_up(W, 8) * div_up(H, 8) <= RASTER_SMALL_MAX_TILES) {
+        hipLaunchKernelGGL((k_rasterize_tiles<8, 16>), dim3((unsigned)div_up(W, 8), (unsigned)div_up(H, 8), (unsigned)B),
+                           dim3(1024), 0, as_stream(stream), H, W, face_z, face_xy, boxes, n_faces, face_idx, bary);
+    } else {
+        hipLaunchKernelGGL((k_rasterize_tiles<16, 4>),
+                           dim3((unsigned)div_up(W, 16), (unsigned)div_up(H, 16), (unsigned)B), dim3(256), 0,
+                           as_stream(stream), H, W, face_z, face_xy, boxes, n_faces, face_idx, bary);
+    }
+    LNERF_CHECK_LAUNCH("rasterize_batch");
     return LNERF_OK;
 }
 

@@ -104,6 +104,8 @@ _SIGNATURES = {
     "lnerf_mesh_distance": [_P, _L, _P, _I, _P, _P],
     "lnerf_raster_prepare": [_P, _I, _P, _I, _P, _P, _P, _P],
     "lnerf_rasterize": [_I, _I, _P, _P, _I, _P, _P, _P],
+    "lnerf_raster_prepare_batch": [_P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P],
+    "lnerf_rasterize_batch": [_I, _I, _I, _P, _P, _P, _I, _P, _P, _P],
     "lnerf_interpolate_attributes": [_P, _P, _P, _I, _I, _P, _P],
     "lnerf_interpolate_attributes_backward": [_P, _P, _P, _I, _I, _P, _P],
     "lnerf_texture_map_forward": [_P, _P, _P, _I, _I, _I, _I, _P, _P],

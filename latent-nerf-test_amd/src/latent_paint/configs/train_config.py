@@ -20,6 +20,7 @@ RenderConfig = _cli.make_section("RenderConfig", (
     ("angle_overhead", float, 30, "elevations in [0, angle_overhead] degrees count as the overhead view bucket"),
     ("angle_front", float, 70, "azimuths within +-angle_front degrees count as the front view bucket"),
     ("backbone", str, "texture-mesh", "'texture-mesh' (latent texture) or 'texture-rgb-mesh' (RGB fine-tuning)"),
+    ("batch_size", int, 1, "views rendered and guided per optimisation step (their gradients are averaged)"),
 ), doc="mesh renderer")
 
 GuideConfig = _cli.make_section("GuideConfig", (
@@ -77,6 +78,8 @@ class TrainConfig:
             raise ValueError("required config fields not set: %s" % ", ".join(unset))
         if self.guide.texture_interpolation_mode not in INTERPOLATION_MODES:
             raise ValueError("guide.texture_interpolation_mode must be one of %s" % ", ".join(INTERPOLATION_MODES))
+        if self.render.batch_size < 1:
+            raise ValueError("render.batch_size must be >= 1 (got %s)" % self.render.batch_size)
         return self
 
 

@@ -1,6 +1,7 @@
 """HIP-backed counterpart of src/latent_paint/models/render.py (Renderer :5-69): same constructor, camera
 convention (:19-31) and the two render entry points (:34-47, :50-69), with the kaolin calls replaced by the
-C-ABI raster kernels (csrc/raster.hip)."""
+C-ABI raster kernels (csrc/raster.hip).  `render_views` / `render_views_texture` take B views per call (the fork's
+`render.batch_size`); the single-view methods are their B = 1 case, on the one tile-culled rasteriser."""
 import math
 
 import torch
@@ -84,37 +85,67 @@ class Renderer:
         import ctypes
         return (ctypes.c_float * 14)(*(x + y + z + pos + [f, f]))
 
-    def _rasterize(self, verts, faces, elev, azim, radius, look_at_height, dims):
+    def _cameras(self, elev, azim, radius, look_at_height):
+        """[B,14] f32 on the device: row b holds the very floats get_camera_from_view gives for view b."""
+        rows = [list(self.get_camera_from_view(e, a, r, look_at_height, self.fov)) for e, a, r in zip(elev, azim, radius)]
+        return torch.tensor(rows, dtype=torch.float32).to(self.device)
+
+    def _rasterize_views(self, verts, faces, elev, azim, radius, look_at_height, dims):
+        """B views of one mesh through the tile-culled rasteriser -> (face_idx [B*H*W], bary [B*H*W,3], B, H, W)."""
+        elev, azim, radius = list(elev), list(azim), list(radius)
+        B = len(elev)
+        if B < 1 or len(azim) != B or len(radius) != B:
+            raise ValueError("render_views: elev, azim and radius must be sequences of one length >= 1 (got %d, %d, %d)"
+                             % (B, len(azim), len(radius)))
         H, W = dims[1], dims[0]
-        cam = self.get_camera_from_view(elev, azim, radius, look_at_height, self.fov)
+        cams = self._cameras(elev, azim, radius, look_at_height)
         verts = verts.to(self.device).float().contiguous()
         faces32 = faces.to(self.device).to(torch.int32).contiguous()
         F = faces32.shape[0]
-        face_z = torch.empty(F, 3, device=self.device)
-        face_xy = torch.empty(F, 3, 2, device=self.device)
-        _b.call("lnerf_raster_prepare", _chk(verts, "verts"), verts.shape[0], _chk(faces32, "faces", torch.int32), F, cam,
-                _p(face_z), _p(face_xy), _stream())
-        face_idx = torch.empty(H * W, device=self.device, dtype=torch.int32)
-        bary = torch.empty(H * W, 3, device=self.device)
-        _b.call("lnerf_rasterize", H, W, _p(face_z), _p(face_xy), F, _p(face_idx), _p(bary), _stream())
+        face_z = torch.empty(B, F, 3, device=self.device)
+        face_xy = torch.empty(B, F, 3, 2, device=self.device)
+        face_box = torch.empty(B, F, 4, device=self.device, dtype=torch.int16)
+        _b.call("lnerf_raster_prepare_batch", _chk(verts, "verts"), verts.shape[0], _chk(faces32, "faces", torch.int32),
+                F, _chk(cams, "cams"), B, H, W, _p(face_z), _p(face_xy), _p(face_box), _stream())
+        face_idx = torch.empty(B * H * W, device=self.device, dtype=torch.int32)
+        bary = torch.empty(B * H * W, 3, device=self.device)
+        _b.call("lnerf_rasterize_batch", B, H, W, _p(face_z), _p(face_xy), _p(face_box), F, _p(face_idx), _p(bary),
+                _stream())
+        return face_idx, bary, B, H, W
+
+    def _rasterize(self, verts, faces, elev, azim, radius, look_at_height, dims):
+        face_idx, bary, _, H, W = self._rasterize_views(verts, faces, [elev], [azim], [radius], look_at_height, dims)
         return face_idx, bary, H, W
 
-    def render_single_view(self, mesh, face_attributes, elev=0, azim=0, radius=2, look_at_height=0.0):
-        """face_attributes [1,F,3,D] -> (image [1,D,H,W], mask [1,1,H,W]); differentiable w.r.t. the attributes."""
-        face_idx, bary, H, W = self._rasterize(mesh.vertices, mesh.faces, elev, azim, radius, look_at_height, self.dim)
+    def render_views(self, mesh, face_attributes, elev, azim, radius, look_at_height=0.0):
+        """B views in one call: elev, azim, radius are sequences of length B.  face_attributes [1,F,3,D] ->
+        (image [B,D,H,W], mask [B,1,H,W]); differentiable w.r.t. the attributes (their gradient sums over the views)."""
+        face_idx, bary, B, H, W = self._rasterize_views(mesh.vertices, mesh.faces, elev, azim, radius, look_at_height,
+                                                        self.dim)
         feat = _InterpAttr.apply(face_attributes[0], face_idx, bary)
-        mask = (face_idx > -1).float().reshape(1, H, W, 1)
-        return feat.reshape(1, H, W, -1).permute(0, 3, 1, 2), mask.permute(0, 3, 1, 2)
+        mask = (face_idx > -1).float().reshape(B, H, W, 1)
+        return feat.reshape(B, H, W, -1).permute(0, 3, 1, 2), mask.permute(0, 3, 1, 2)
 
-    def render_single_view_texture(self, verts, faces, uv_face_attr, texture_map, elev=0, azim=0, radius=2,
-                                   look_at_height=0.0, dims=None, white_background=False):
+    def render_views_texture(self, verts, faces, uv_face_attr, texture_map, elev, azim, radius, look_at_height=0.0,
+                             dims=None, white_background=False):
+        """B views of the textured mesh in one call -> (image [B,C,H,W], mask [B,1,H,W]).  The batch is B*H*W flat
+        pixels through the single-view kernels; the texture is shared, so its gradient sums over the views."""
         dims = self.dim if dims is None else dims
-        face_idx, bary, H, W = self._rasterize(verts, faces, elev, azim, radius, look_at_height, dims)
+        face_idx, bary, B, H, W = self._rasterize_views(verts, faces, elev, azim, radius, look_at_height, dims)
         with torch.no_grad():                          # uv_features.detach() in the reference (:61)
             uv = _InterpAttr.apply(uv_face_attr[0].detach(), face_idx, bary).contiguous()
         image = _TextureMap.apply(texture_map, uv, face_idx, _MODES[self.interpolation_mode])
-        mask = (face_idx > -1).float().reshape(1, H, W, 1)
-        image = image.reshape(1, H, W, -1) * mask
+        mask = (face_idx > -1).float().reshape(B, H, W, 1)
+        image = image.reshape(B, H, W, -1) * mask
         if white_background:
             image = image + 1 * (1 - mask)
         return image.permute(0, 3, 1, 2), mask.permute(0, 3, 1, 2)
+
+    def render_single_view(self, mesh, face_attributes, elev=0, azim=0, radius=2, look_at_height=0.0):
+        """face_attributes [1,F,3,D] -> (image [1,D,H,W], mask [1,1,H,W]); differentiable w.r.t. the attributes."""
+        return self.render_views(mesh, face_attributes, [elev], [azim], [radius], look_at_height)
+
+    def render_single_view_texture(self, verts, faces, uv_face_attr, texture_map, elev=0, azim=0, radius=2,
+                                   look_at_height=0.0, dims=None, white_background=False):
+        return self.render_views_texture(verts, faces, uv_face_attr, texture_map, [elev], [azim], [radius],
+                                         look_at_height, dims=dims, white_background=white_background)

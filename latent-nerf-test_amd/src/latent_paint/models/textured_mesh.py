@@ -131,15 +131,24 @@ class TexturedMeshModel(nn.Module):
 
     # ------------------------------------------------------------------ rendering
     def _view(self, theta, phi, radius):
-        return {"elev": theta, "azim": phi, "radius": radius, "look_at_height": self.dy}
+        """Scalars (one view) or sequences of one length B -> the keyword arguments of Renderer.render_views*."""
+        seq = [isinstance(a, (list, tuple)) or (torch.is_tensor(a) and a.dim() > 0) or
+               (isinstance(a, np.ndarray) and a.ndim > 0) for a in (theta, phi, radius)]
+        if any(seq) and not all(seq):
+            raise ValueError("render: theta, phi and radius must be all scalars or all sequences")
+        if not seq[0]:
+            theta, phi, radius = [theta], [phi], [radius]
+        as_floats = lambda a: [float(v) for v in a]
+        return {"elev": as_floats(theta), "azim": as_floats(phi), "radius": as_floats(radius), "look_at_height": self.dy}
 
     def render(self, theta, phi, radius, decode_func=None, test=False, dims=None):
+        """theta, phi, radius: scalars (one view, [1,...] results) or sequences of length B ([B,...] results)."""
         if test:
             return self.render_test(theta, phi, radius, decode_func, dims=dims)
         return self.render_train(theta, phi, radius)
 
     def render_train(self, theta, phi, radius):
-        """-> {'image' [1,C,h,w], 'mask' [1,1,h,w], 'background', 'foreground'}; C = 4 latents (or 3 RGB when
+        """-> {'image' [B,C,h,w], 'mask' [B,1,h,w], 'background', 'foreground'}; C = 4 latents (or 3 RGB when
         fine-tuning).  The rasterisation itself carries no gradient: 'image' is differentiable w.r.t. the texture
         (under the mesh) and the background colours (elsewhere)."""
         if self.latent_mode:
@@ -148,9 +157,9 @@ class TexturedMeshModel(nn.Module):
             texture = self.texture_img_rgb_finetune
             sky_colors = self.background_sphere_colors @ self.linear_rgb_estimator
         view = self._view(theta, phi, radius)
-        foreground, coverage = self.renderer.render_single_view_texture(
+        foreground, coverage = self.renderer.render_views_texture(
             self.mesh.vertices, self.mesh.faces, self.face_attributes, texture, **view)
-        background, _ = self.renderer.render_single_view(self.env_sphere, sky_colors, **view)
+        background, _ = self.renderer.render_views(self.env_sphere, sky_colors, **view)
         coverage = coverage.detach()
         image = background * (1 - coverage) + foreground * coverage
         out = {"image": image, "mask": coverage, "background": background, "foreground": foreground}
@@ -168,7 +177,7 @@ class TexturedMeshModel(nn.Module):
             texture = decode_func(self.texture_img)
         else:
             texture = self.texture_img_rgb_finetune
-        image, coverage = self.renderer.render_single_view_texture(
+        image, coverage = self.renderer.render_views_texture(
             self.mesh.vertices, self.mesh.faces, self.face_attributes, texture, dims=dims, white_background=True,
             **self._view(theta, phi, radius))
         return {"image": image, "texture_map": texture, "mask": coverage}

@@ -120,17 +120,27 @@ class Trainer:
         self.full_eval()
 
     def train_render(self, data):
-        """One view: render, ask the guidance for d(loss)/d(pred) and push it through the render graph."""
+        """One step's views (`render.batch_size` of them, rendered as one batch): ask the guidance for d(loss)/d(pred)
+        and push grad / k through the render graph.  That is the MEAN over the k views, the NeRF trainer's convention
+        for `optim.views_per_step`; the fork sums instead.  With Adam at eps = 1e-15 the update is invariant to the
+        gradient's scale, so only the convention differs.  k = 1 is the single-view step unchanged."""
         out = self.mesh_model.render(theta=data["theta"], phi=data["phi"], radius=data["radius"])
         pred = out["image"]
-        if self.cfg.guide.append_direction:
-            text_z = self.text_z[int(data["dir"][0])]
-        else:
-            text_z = self.text_z
+        k = pred.shape[0]
         if isinstance(self.diffusion, SyntheticGuidance):
-            grad = self.diffusion.train_step(text_z, pred, dirs=data["dir"])
-        else:
+            text_z = self.text_z[int(data["dir"][0])] if self.cfg.guide.append_direction else self.text_z
+            grad = self.diffusion.train_step(text_z, pred, dirs=data["dir"])     # one call: latents [k,C,h,w], dirs [k]
+        elif k == 1 or not self.cfg.guide.append_direction:
+            text_z = self.text_z[int(data["dir"][0])] if self.cfg.guide.append_direction else self.text_z
             grad = self.diffusion.train_step(text_z, pred)
+        else:   # one text embedding per call: the views grouped by direction
+            dirs = [int(d) for d in data["dir"]]
+            grad = torch.empty_like(pred)
+            for d in sorted(set(dirs)):
+                rows = torch.tensor([n for n, v in enumerate(dirs) if v == d], device=pred.device)
+                grad[rows] = self.diffusion.train_step(self.text_z[d], pred[rows])
+        if k > 1:
+            grad = grad / k
         pred.backward(gradient=grad)
         return pred, grad
 

@@ -676,6 +676,73 @@ int lnerf_decimate(const float *verts, int n_verts, const int32_t *faces, int n_
                    int max_rounds, void *scratch, size_t scratch_bytes, float *verts_out, int32_t *faces_out,
                    float *normals_out, int64_t *counts_dev, lnerf_stream_t stream);
 
+/* ---- chart atlas: a UV map of connected, axis-projected patches, raymarching.chart_atlas's kernels (csrc/atlas.hip).
+ * Additive to ABI 7.  All device arithmetic is f32 + - * / in the order written, no fused multiply-adds; the scale search
+ * and the packing are host code in f64 and integers (src/uv_atlas.py).  Every result is independent of the order in
+ * which the integer atomics land, so the atlas is bit-reproducible (numpy restatement: tests/atlas_reference.py).
+ *   verts [n_verts,3] f32, faces [n_faces,3] int32, n_faces <= LNERF_ATLAS_MAX_FACES.
+ * lnerf_atlas_buckets: for face f with corners P0, P1, P2:  m = (P1 - P0) x (P2 - P0)  (m_x = a_y b_z - a_z b_y, ...),
+ *   scores (m_x, -m_x, m_y, -m_y, m_z, -m_z); b starts at 0 and becomes k whenever score_k > score_b, so the first maximum
+ *   wins and m = 0 or NaN gives 0.  The unit normal then has n . axis >= 1/sqrt(3).  bucket[f] = b, label[f] = f.  A face
+ *   with an index outside [0, n_verts) gets bucket -1, is counted in counts_dev int64[1] and reads nothing through the
+ *   index; every later stage skips it (the host side refuses the mesh).
+ *   Plane coordinates (p, q) of (x, y, z) in bucket b, p x q = axis, so a non-degenerate face is counter-clockwise:
+ *     0 (+x): (y, z)   1 (-x): (z, y)   2 (+y): (z, x)   3 (-y): (x, z)   4 (+z): (x, y)   5 (-z): (y, x)
+ * Links (the caller's, twin [3 n_faces] int32): half-edge 3 f + k runs from faces[f][k] to faces[f][(k+1)%3]; its twin is
+ *   the one half-edge the other way round, present only if the undirected edge occurs in exactly two half-edges, one
+ *   each way, and its ends differ; otherwise -1.  Open borders and non-manifold edges therefore never join charts.
+ * lnerf_atlas_round: charts are the connected components of  f ~ g  iff f and g are linked and bucket[f] == bucket[g];
+ *   label[f] converges to the smallest face index of f's component.  One round: hook (m = min of label[f] and the
+ *   labels of f's linked same-bucket neighbours; if m < label[f]: atomicMin(label[label[f]], m), atomicMin(label[f], m),
+ *   *changed_dev = 1), then LNERF_ATLAS_JUMP_HOPS steps of label[f] = label[label[f]].  changed_dev int32[1] is cleared
+ *   first.  A round that leaves it 0 changed nothing and the labels are final; the host stops at
+ *   LNERF_ATLAS_MAX_ROUNDS and raises.  No kernel loops on the labels beyond those fixed hops.
+ * lnerf_atlas_compact: charts numbered 0 .. C-1 in ascending label order: face_chart [n_faces] (-1 for a refused face),
+ *   chart_axis [capacity n_faces, C written] = the bucket, counts_dev int64[1] = C.
+ * lnerf_atlas_boxes: chart_box [n_charts,4] f32 = (p_lo, p_hi, q_lo, q_hi), min / max over the corners of the chart's
+ *   faces, by integer atomics on the order-preserving encoding  e = bits ^ (bits < 0 ? 0xFFFFFFFF : 0x80000000)  (so
+ *   -0 < +0).  A chart without faces gets (NaN, NaN, NaN, NaN) patterns and must not be used.
+ * Scale and packing (host): g = pad; ext_p = p_hi - p_lo, ext_q = q_hi - q_lo in f64; s_0 = (R - 2g - 2) / the largest
+ *   extent (1 when all are 0), s_k = f32(s_0 * 0.95^k); rectangle w = 2g + 2 + floor(ext_p * s), h = 2g + 2 +
+ *   floor(ext_q * s) with the ROUNDED s; charts sorted by (h desc, w desc, id asc) go on shelves left to right: a new
+ *   shelf (y += shelf height, x = 0) when x + w > R, failure when w > R or y + h > R, shelf height = the largest h placed
+ *   on it.  The first k that packs is taken; past k = 200 the host raises.
+ * lnerf_atlas_uv: a corner at plane position (p, q) of a face in chart c with origin (ox, oy) = chart_org[c]:
+ *     X = ((float)(ox + g) + 0.5f) + (p - p_lo) * s,   Y = ((float)(oy + g) + 0.5f) + (q_hi - q) * s,
+ *     u = X / R,   v = 1.0f - Y / R        (the texel convention of lnerf_uv_raster)
+ *   written to vt[ft[f][k]]; ft [n_faces,3] int32 is the caller's: one row of vt per distinct (chart, vertex) pair in
+ *   ascending (chart, vertex) order.  Faces that share a row write the same bits.
+ * lnerf_atlas_fold: a same-bucket component can still wind over itself (a helicoid).  On the packed UVs, with the
+ *   pixel-space corners, candidate boxes and E_ab of lnerf_uv_raster, a texel centre is STRICTLY inside a face iff
+ *   E_12, E_20 and E_01 each have the sign of the area and none is 0.  Pass A: texel_owner [R*R] int32 = the largest
+ *   face index strictly covering the texel (-1 = none).  Pass B: evicted[f] = 1 for every face that strictly covers a
+ *   texel it does not own, else 0.  The host makes each evicted face a chart of its own, numbered after the others
+ *   in face order, and continues the shelves with their rectangles; the other faces keep their vt bits.
+ *   `stages`: LNERF_UV_ITEMS (candidate counts and prefix -> counts_dev int64[1]), then LNERF_UV_COVER with n_items =
+ *   that count or an upper bound.  A face with an ft index outside [0, n_vt) has no candidates.
+ * Scratch sizes: the *_scratch_bytes calls (0 = arguments out of range); scratch is 16-byte aligned. */
+#define LNERF_ATLAS_MAX_ROUNDS 256
+#define LNERF_ATLAS_JUMP_HOPS 4
+#define LNERF_ATLAS_MAX_FACES (1 << 28)
+int lnerf_atlas_buckets(const float *verts, int n_verts, const int32_t *faces, int n_faces, int32_t *bucket,
+                        int32_t *label, int64_t *counts_dev, lnerf_stream_t stream);
+int lnerf_atlas_round(const int32_t *bucket, const int32_t *twin, int n_faces, int32_t *label, int32_t *changed_dev,
+                      lnerf_stream_t stream);
+size_t lnerf_atlas_compact_scratch_bytes(int n_faces);
+int lnerf_atlas_compact(const int32_t *bucket, const int32_t *label, int n_faces, void *scratch, size_t scratch_bytes,
+                        int32_t *face_chart, int32_t *chart_axis, int64_t *counts_dev, lnerf_stream_t stream);
+size_t lnerf_atlas_boxes_scratch_bytes(int n_charts);
+int lnerf_atlas_boxes(const float *verts, int n_verts, const int32_t *faces, const int32_t *bucket,
+                      const int32_t *face_chart, int n_faces, int n_charts, void *scratch, size_t scratch_bytes,
+                      float *chart_box, lnerf_stream_t stream);
+int lnerf_atlas_uv(const float *verts, int n_verts, const int32_t *faces, const int32_t *ft, int n_faces,
+                   const int32_t *face_chart, const int32_t *chart_axis, const int32_t *chart_org, const float *chart_box,
+                   int n_charts, int pad, float scale, int R, float *vt, int n_vt, lnerf_stream_t stream);
+size_t lnerf_atlas_fold_scratch_bytes(int n_faces, int R);
+int lnerf_atlas_fold(const float *vt, int n_vt, const int32_t *ft, int n_faces, int R, int stages, int64_t n_items,
+                     void *scratch, size_t scratch_bytes, int32_t *texel_owner, int32_t *evicted, int64_t *counts_dev,
+                     lnerf_stream_t stream);
+
 /* ---- shaded renders (shading = "lambertian" / "textureless"): the kernels around the field (csrc/shade.hip).  Additive
  * to ABI 7.  The normal is the upstream renderer's training normal, a central finite difference of sigma at six offset
  * points; its gradient is the field's ordinary backward at 7 m points.  All arithmetic is f32 + - * / sqrt in the order

@@ -1,4 +1,4 @@
-// Prefix sums shared by the mesh-export kernels (isosurface.hip, uvbake.hip, decimate.hip): a compaction there is
+// Prefix sums shared by the mesh-export kernels (isosurface.hip, uvbake.hip, decimate.hip, atlas.hip): a compaction there is
 //   per block   block_exclusive_scan inside the kernel that counts, its block total -> blk[block]
 //   k_scan_top  ONE workgroup: exclusive prefix of the block totals (in place) and the grand total
 //   per block   block prefix + position in the block

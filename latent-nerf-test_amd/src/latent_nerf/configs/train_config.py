@@ -82,6 +82,8 @@ class OptimConfig:
     # geometry.  A shaded step evaluates the field at 7 points per sample.  None: every step renders the plain albedo
     start_shading_iter: Optional[int] = None
 
+MESH_ATLASES = ("triangle", "charts")   # log.mesh_atlas (src/uv_atlas.py ATLAS_CHOICES)
+
 
 @dataclass
 class LogConfig:
@@ -100,6 +102,9 @@ class LogConfig:
     # with save_mesh: the exported normals (and, textured, an object-space normal map normal_object.png) come from the
     # field's density gradient at the final vertices instead of the lattice / the decimated faces
     mesh_field_normals: bool = False
+    # with save_mesh and mesh_texture_resolution: the UV atlas the texture lives in, "triangle" (every face a chart of its
+    # own) or "charts" (connected patches projected along the axis nearest their normals, raymarching.chart_atlas)
+    mesh_atlas: str = "triangle"
     # evaluation also writes a normal-shaded render (*_normals.png / *_normals video) beside every *_rgb one
     eval_normals: bool = False
     max_keep_ckpts: int = 2
@@ -139,6 +144,8 @@ class TrainConfig:
         if self._auto_layout:
             self.render.gridtype = "blocked" if self.render.table_dtype == "bf16" else "hash"
         self.render.layout()  # validates
+        if self.log.mesh_atlas not in MESH_ATLASES:
+            raise ValueError("log.mesh_atlas must be one of %s, not %r" % (" | ".join(MESH_ATLASES), self.log.mesh_atlas))
 
     def note_explicit(self, key, value):
         """config_cli.apply_overrides tells us which fields the user set."""

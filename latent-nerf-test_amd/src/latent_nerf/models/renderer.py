@@ -558,7 +558,7 @@ class NeRFRenderer(nn.Module):
 
     @torch.no_grad()
     def export_mesh(self, path, resolution=None, S=128, thresh=None, texture_resolution=0, gutter=4, target_faces=0,
-                    field_normals=False):
+                    field_normals=False, atlas="triangle"):
         """Triangle mesh of the density field -> `path`/mesh.obj (the upstream renderer's export_mesh(path, resolution,
         S)): the density on a `resolution`^3 lattice over [-bound, bound]^3 (density_lattice), marching cubes on the GPU
         at iso `thresh` (default min(mean density, density_thresh), as upstream) with the box capped, vertex colours
@@ -574,9 +574,14 @@ class NeRFRenderer(nn.Module):
         gradient of the density, after the decimation when there is one) instead of the lattice's central differences
         or the decimated mesh's face sums; a textured export also bakes an object-space normal map, stored as
         (n + 1) / 2 -- `normal_map` [3,R,R] in the result and normal_object.png beside albedo.png (mesh.mtl unchanged).
+        atlas: "triangle" (the per-triangle atlas) or "charts" (raymarching.chart_atlas at texture_resolution, of the
+        decimated mesh when there is a decimation: connected patches share their texture vertices, and the result also
+        carries face_chart, chart_rect and atlas_scale).
         Returns dict(verts [V,3], faces [F,3] int32, normals [V,3], colors [V,3], iso, path, faces_before (the
         marching-cubes face count)) with device tensors, plus vt, ft, texture, mask, rgb when textured."""
+        from ...uv_atlas import check_atlas_choice
         from .mesh_io import write_obj
+        check_atlas_choice(atlas, "export_mesh: atlas")
         vol = self.density_lattice(resolution, S)
         if thresh is None:
             iso = float(torch.clamp(self.mean_density_dev.reshape(-1)[0], max=float(self.density_thresh)))
@@ -602,12 +607,12 @@ class NeRFRenderer(nn.Module):
                   "faces_before": faces_before}
         if int(texture_resolution) > 0:
             result.update(self._export_textured(str(path), verts, faces, normals, int(texture_resolution), gutter, S,
-                                                bool(field_normals)))
+                                                bool(field_normals), atlas))
         else:
             write_obj(out, verts.cpu().numpy(), faces.cpu().numpy(), normals.cpu().numpy(), colors.cpu().numpy())
         return result
 
-    def _export_textured(self, path, verts, faces, normals, R, gutter, S, normal_map=False):
+    def _export_textured(self, path, verts, faces, normals, R, gutter, S, normal_map=False, atlas="triangle"):
         """The textured half of export_mesh: atlas, bake, mesh.obj + mesh.mtl + albedo.png (+ latent_texture.pt;
         normal_map: + normal_object.png, the field's normals over the same atlas)."""
         import warnings
@@ -618,13 +623,18 @@ class NeRFRenderer(nn.Module):
         from ...uv_atlas import MIN_TEXELS_PER_CELL, atlas_cells, atlas_min_resolution, per_triangle_atlas
         from .mesh_io import write_textured_obj
         F = faces.shape[0]
-        need = atlas_min_resolution(F)
-        if F > 0 and R < need:
-            warnings.warn("export_mesh: texture_resolution %d gives the per-triangle atlas of %d faces %.1f texels per "
-                          "chart cell (fewer than %d): use texture_resolution >= %d, or target_faces <= %d"
-                          % (R, F, R / atlas_cells(F), MIN_TEXELS_PER_CELL, need, 2 * (R // MIN_TEXELS_PER_CELL) ** 2),
-                          stacklevel=3)
-        vt, ft = per_triangle_atlas(F, verts.device)
+        extra = {}
+        if atlas == "charts":
+            vt, ft, info = rm.chart_atlas(verts, faces, R)
+            extra = {"face_chart": info["face_chart"], "chart_rect": info["chart_rect"], "atlas_scale": info["scale"]}
+        else:
+            need = atlas_min_resolution(F)
+            if F > 0 and R < need:
+                warnings.warn("export_mesh: texture_resolution %d gives the per-triangle atlas of %d faces %.1f texels per "
+                              "chart cell (fewer than %d): use texture_resolution >= %d, or target_faces <= %d"
+                              % (R, F, R / atlas_cells(F), MIN_TEXELS_PER_CELL, need, 2 * (R // MIN_TEXELS_PER_CELL) ** 2),
+                              stacklevel=3)
+            vt, ft = per_triangle_atlas(F, verts.device)
         baked = self.bake_texture(verts, faces, vt, ft, resolution=R, gutter=gutter, S=S)
         os.makedirs(path, exist_ok=True)
         out = os.path.join(path, "mesh.obj")
@@ -640,7 +650,7 @@ class NeRFRenderer(nn.Module):
             img = (nmap.clamp(0, 1).permute(1, 2, 0).cpu().numpy() * 255).round().astype(np.uint8)
             Image.fromarray(img).save(os.path.join(path, "normal_object.png"))
             baked = dict(baked, normal_map=nmap)
-        return dict(baked, vt=vt, ft=ft)
+        return dict(baked, vt=vt, ft=ft, **extra)
 
     def shadow_extra_state(self):
         """Context manager: inside it the occupancy state (density grid, bitfield, mean) is a SHADOW copy, so

@@ -27,6 +27,8 @@ MC_CLOSE_BOUNDARY, MC_COUNT_ONLY, MC_REUSE_COUNT = 1, 2, 4   # LNERF_MC_* flags 
 UV_ITEMS, UV_COVER, UV_EMIT = 1, 2, 4                         # LNERF_UV_* stages of lnerf_uv_raster
 UV_MAX_RES = 8192                                             # LNERF_UV_MAX_RES
 DECIMATE_DEFAULT_ROUNDS = 128                                 # LNERF_DECIMATE_DEFAULT_ROUNDS
+ATLAS_MAX_ROUNDS = 256                                        # LNERF_ATLAS_MAX_ROUNDS
+ATLAS_MAX_FACES = 1 << 28                                     # LNERF_ATLAS_MAX_FACES
 
 
 class LnerfLibraryError(RuntimeError):
@@ -126,6 +128,15 @@ _SIGNATURES = {
     "lnerf_uv_dilate": [_P, _P, _I, _I, _I, _P, _P, _P],
     "lnerf_decimate_scratch_bytes": [_I, _I],
     "lnerf_decimate": [_P, _I, _P, _I, _I, _F, _I, _P, _Z, _P, _P, _P, _P, _P],
+    "lnerf_atlas_buckets": [_P, _I, _P, _I, _P, _P, _P, _P],
+    "lnerf_atlas_round": [_P, _P, _I, _P, _P, _P],
+    "lnerf_atlas_compact_scratch_bytes": [_I],
+    "lnerf_atlas_compact": [_P, _P, _I, _P, _Z, _P, _P, _P, _P],
+    "lnerf_atlas_boxes_scratch_bytes": [_I],
+    "lnerf_atlas_boxes": [_P, _I, _P, _P, _P, _I, _I, _P, _Z, _P, _P],
+    "lnerf_atlas_uv": [_P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _I, _F, _I, _P, _I, _P],
+    "lnerf_atlas_fold_scratch_bytes": [_I, _I],
+    "lnerf_atlas_fold": [_P, _I, _P, _I, _I, _I, _L, _P, _Z, _P, _P, _P, _P],
     "lnerf_fd_points": [_P, _F, _F, _L, _P, _P, _P, _P],
     "lnerf_shade_fd_forward": [_P, _P, _I, _P, _L, _I, _P, _I, _F, _P, _P, _P],
     "lnerf_shade_fd_backward": [_P, _P, _I, _P, _L, _I, _P, _I, _F, _P, _P, _P, _P, _P],
@@ -143,6 +154,9 @@ _RESTYPES = {
     "lnerf_marching_cubes_scratch_bytes": _Z,
     "lnerf_uv_raster_scratch_bytes": _Z,
     "lnerf_decimate_scratch_bytes": _Z,
+    "lnerf_atlas_compact_scratch_bytes": _Z,
+    "lnerf_atlas_boxes_scratch_bytes": _Z,
+    "lnerf_atlas_fold_scratch_bytes": _Z,
 }
 
 _lib = None

@@ -537,6 +537,142 @@ def decimate_mesh(verts, faces, target_faces, max_error=float("inf"), max_rounds
     return out_v[:Vo], out_f[:Fo], out_n[:Vo]
 
 
+# ------------------------------------------------------------------------------ chart atlas
+def _half_edge_twins(faces, V):
+    """twin [3F] int32 of the half-edges 3 f + k = faces[f][k] -> faces[f][(k+1)%3]: the one half-edge the other way round
+    when the undirected edge occurs in exactly two half-edges, one each way, and its ends differ; else -1."""
+    F = faces.shape[0]
+    a = faces.reshape(-1).long()
+    b = faces[:, [1, 2, 0]].reshape(-1).long()
+    key = torch.minimum(a, b) * max(V, 1) + torch.maximum(a, b)
+    key, order = torch.sort(key, stable=True)
+    _, counts = torch.unique_consecutive(key, return_counts=True)
+    start = torch.cumsum(counts, 0) - counts
+    first = start[counts == 2]
+    e0, e1 = order[first], order[first + 1]
+    ok = ((a[e0] < b[e0]) != (a[e1] < b[e1])) & (a[e0] != b[e0])
+    e0, e1 = e0[ok], e1[ok]
+    twin = torch.full((3 * F,), -1, device=faces.device, dtype=torch.int32)
+    twin[e0] = e1.int()
+    twin[e1] = e0.int()
+    return twin
+
+
+def chart_atlas(verts, faces, resolution, pad=2, stats=None):
+    """Chart UV atlas of a mesh on the GPU (lnerf_atlas_*, include/lnerf_hip.h "chart atlas"): faces bucketed by the axis
+    nearest their normal, connected same-bucket patches projected along it, their boxes shelf-packed into the square at
+    one scale, and faces that fold over their own chart evicted into charts of their own.
+    verts [V,3] f32, faces [F,3] (into verts), on the GPU -> vt [n_vt,2] f32 (one row per (chart, vertex) pair), ft [F,3]
+    long, and a dict: face_chart [F] int32, chart_rect [C,4] int32 (ox, oy, w, h in texels), chart_axis [C] int32, scale,
+    k, evicted (count), evicted_faces [E] long, rounds.  `stats` (a dict) receives the scalars.  Deterministic bit
+    for bit.  Synchronous: one host read per label round and a few around the packing, which is host code."""
+    import numpy as np
+    from ...uv_atlas import ATLAS_MAX_SHRINKS, atlas_pack_error, chart_rect_sizes, pack_charts, shelf_pack
+    R, pad = int(resolution), int(pad)
+    if not 1 <= R <= _b.UV_MAX_RES:
+        raise ValueError("chart_atlas: resolution %d outside [1, %d]" % (R, _b.UV_MAX_RES))
+    if pad < 0 or 2 * pad + 2 > R:
+        raise ValueError("chart_atlas: pad %d needs 2 pad + 2 <= resolution (%d)" % (pad, R))
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError("chart_atlas: verts must be [V,3]")
+    verts = verts.contiguous()
+    _chk(verts, "verts")
+    dev = verts.device
+    faces = _face_index(faces, "chart_atlas", "faces", dev)
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    if F > _b.ATLAS_MAX_FACES or V >= 2 ** 31:
+        raise ValueError("chart_atlas: %d faces / %d vertices out of range" % (F, V))
+    lib = _b.get_lib()
+    i32 = dict(device=dev, dtype=torch.int32)
+    counts = torch.zeros(1, device=dev, dtype=torch.int64)
+    bucket, label = torch.empty(F, **i32), torch.empty(F, **i32)
+    _b.call("lnerf_atlas_buckets", _p(verts), V, _p(faces), F, _p(bucket), _p(label), _p(counts), _stream())
+    bad = int(counts[0])
+    if bad:
+        raise ValueError("chart_atlas: %d faces index outside verts (%d)" % (bad, V))
+    # charts: rounds of hook + pointer jumping until a round changes nothing
+    twin = _half_edge_twins(faces, V)
+    changed = torch.zeros(1, **i32)
+    rounds = 0
+    while True:
+        if rounds >= _b.ATLAS_MAX_ROUNDS:
+            raise RuntimeError("chart_atlas: the labels have not settled after %d rounds" % rounds)
+        _b.call("lnerf_atlas_round", _p(bucket), _p(twin), F, _p(label), _p(changed), _stream())
+        rounds += 1
+        if int(changed[0]) == 0:
+            break
+    nbytes = lib.lnerf_atlas_compact_scratch_bytes(F)
+    scratch = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    face_chart, chart_axis = torch.empty(F, **i32), torch.empty(F, **i32)
+    _b.call("lnerf_atlas_compact", _p(bucket), _p(label), F, _p(scratch), nbytes, _p(face_chart), _p(chart_axis),
+            _p(counts), _stream())
+    C = int(counts[0])
+    chart_axis = chart_axis[:C].clone()
+
+    def boxes(fc, n, sub=None):
+        f, b = (faces, bucket) if sub is None else (faces[sub].contiguous(), bucket[sub].contiguous())
+        nb = lib.lnerf_atlas_boxes_scratch_bytes(n)
+        sc = torch.empty(max(nb, 16), device=dev, dtype=torch.uint8)
+        out = torch.empty(n, 4, device=dev, dtype=torch.float32)
+        _b.call("lnerf_atlas_boxes", _p(verts), V, _p(f), _p(b), _p(fc), int(f.shape[0]), n, _p(sc), nb, _p(out), _stream())
+        return out
+
+    def emit(fc, axis, rect, box, s):
+        """vt, ft (int32) of the layout: texture vertices = the distinct (chart, vertex) pairs, ascending."""
+        key = (fc.long()[:, None] * max(V, 1) + faces.long()).reshape(-1)
+        uniq, inv = torch.unique(key, sorted=True, return_inverse=True)
+        ft = inv.reshape(F, 3).int().contiguous()
+        vt = torch.zeros(int(uniq.shape[0]), 2, device=dev, dtype=torch.float32)
+        org = torch.as_tensor(rect[:, :2].astype("int32"), device=dev).contiguous()
+        _b.call("lnerf_atlas_uv", _p(verts), V, _p(faces), _p(ft), F, _p(fc), _p(axis), _p(org), _p(box), int(axis.shape[0]),
+                pad, s, R, _p(vt), int(vt.shape[0]), _stream())
+        return vt, ft
+
+    def folded(vt, ft):
+        """evicted [F] bool: faces that strictly cover a texel centre a face with a larger index covers too."""
+        nb = lib.lnerf_atlas_fold_scratch_bytes(F, R)
+        sc = torch.empty(max(nb, 16), device=dev, dtype=torch.uint8)
+        owner = torch.empty(R * R, **i32)
+        ev = torch.zeros(F, **i32)
+        args = (_p(vt), int(vt.shape[0]), _p(ft), F, R)
+        _b.call("lnerf_atlas_fold", *args, _b.UV_ITEMS, 0, _p(sc), nb, None, None, _p(counts), _stream())
+        _b.call("lnerf_atlas_fold", *args, _b.UV_COVER, int(counts[0]), _p(sc), nb, _p(owner), _p(ev), _p(counts), _stream())
+        return ev != 0
+
+    box = boxes(face_chart, C)
+    box_np = box.cpu().numpy()
+    k = 0
+    while True:
+        k, s, rect, state = pack_charts(box_np, R, pad, k)
+        vt, ft = emit(face_chart, chart_axis, rect, box, s)
+        ev = folded(vt, ft) if F > 0 else torch.zeros(0, device=dev, dtype=torch.bool)
+        ev_faces = torch.nonzero(ev).reshape(-1)
+        E = int(ev_faces.shape[0])
+        fc, axis = face_chart, chart_axis
+        if E > 0:
+            # every evicted face becomes a chart of its own, numbered after the others in face order
+            ev_box = boxes(torch.arange(E, **i32), E, ev_faces)
+            eb = ev_box.cpu().numpy().astype("float64")
+            w, h = chart_rect_sizes(eb[:, 1] - eb[:, 0], eb[:, 3] - eb[:, 2], s, pad)
+            placed = shelf_pack(w, h, R, state)
+            if placed is None:
+                k += 1
+                if k > ATLAS_MAX_SHRINKS:
+                    raise atlas_pack_error(R, C + E, pad)
+                continue
+            rect = np.concatenate([rect, np.stack([placed[0], placed[1], w, h], 1)], 0)
+            fc = face_chart.clone()
+            fc[ev_faces] = torch.arange(C, C + E, **i32)
+            axis = torch.cat([chart_axis, bucket[ev_faces]])
+            vt, ft = emit(fc, axis, rect, torch.cat([box, ev_box]).contiguous(), s)
+        break
+    info = dict(face_chart=fc, chart_rect=torch.as_tensor(rect.astype("int32"), device=dev).reshape(-1, 4), chart_axis=axis,
+                scale=s, k=k, evicted=E, evicted_faces=ev_faces, rounds=rounds)
+    if stats is not None:
+        stats.update(scale=s, k=k, evicted=E, rounds=rounds, charts=int(axis.shape[0]))
+    return vt, ft.long(), info
+
+
 # ------------------------------------------------------------------------------ texture baking
 def uv_raster(verts, faces, vt, ft, R):
     """Which texel of an R x R texture each face of a UV-mapped mesh covers (lnerf_uv_raster, include/lnerf_hip.h).

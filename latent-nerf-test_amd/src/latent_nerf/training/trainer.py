@@ -539,7 +539,8 @@ class Trainer:
             tex = int(getattr(self.cfg.log, "mesh_texture_resolution", 0))
             target = int(getattr(self.cfg.log, "mesh_target_faces", 0))
             mesh = self.nerf.export_mesh(self.exp_path / "mesh", texture_resolution=tex, target_faces=target,
-                                         field_normals=bool(getattr(self.cfg.log, "mesh_field_normals", False)))
+                                         field_normals=bool(getattr(self.cfg.log, "mesh_field_normals", False)),
+                                         atlas=getattr(self.cfg.log, "mesh_atlas", "triangle"))
             self.log("exported %s (%d vertices, %d triangles; %d before decimation; iso %.4g)"
                      % (mesh["path"], mesh["verts"].shape[0], mesh["faces"].shape[0], mesh["faces_before"], mesh["iso"]))
         return frames

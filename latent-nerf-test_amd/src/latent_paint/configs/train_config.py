@@ -12,6 +12,7 @@ from typing import Optional, Tuple
 from ... import config_cli as _cli
 
 INTERPOLATION_MODES = ("nearest", "bilinear", "bicubic")
+UV_ATLASES = ("triangle", "charts")
 
 RenderConfig = _cli.make_section("RenderConfig", (
     ("train_grid_size", int, 64, "side of the square training render, in latent pixels"),
@@ -35,6 +36,7 @@ GuideConfig = _cli.make_section("GuideConfig", (
     ("texture_interpolation_mode", str, "nearest", " | ".join(INTERPOLATION_MODES)),
     ("init_texture", Optional[str], None, "latent texture [4,R,R] or [1,4,R,R] (torch.save) to start from, e.g. the "
                                           "latent_texture.pt of the NeRF's textured mesh export; R = texture_resolution"),
+    ("uv_atlas", str, "triangle", "atlas built for a mesh without UVs when xatlas is missing: " + " | ".join(UV_ATLASES)),
     ("guidance", str, "synthetic", "'synthetic' (seeded offline stand-in) or 'stable-diffusion' (diffusers adapter)"),
 ), doc="guidance")
 
@@ -78,6 +80,8 @@ class TrainConfig:
             raise ValueError("required config fields not set: %s" % ", ".join(unset))
         if self.guide.texture_interpolation_mode not in INTERPOLATION_MODES:
             raise ValueError("guide.texture_interpolation_mode must be one of %s" % ", ".join(INTERPOLATION_MODES))
+        if self.guide.uv_atlas not in UV_ATLASES:
+            raise ValueError("guide.uv_atlas must be one of %s, not %r" % (" | ".join(UV_ATLASES), self.guide.uv_atlas))
         if self.render.batch_size < 1:
             raise ValueError("render.batch_size must be >= 1 (got %s)" % self.render.batch_size)
         return self

@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ...uv_atlas import per_triangle_atlas
+from ...uv_atlas import chart_atlas, check_atlas_choice, per_triangle_atlas
 from .mesh import Mesh
 from .render import Renderer
 
@@ -94,7 +94,8 @@ class TexturedMeshModel(nn.Module):
     def init_texture_map(self):
         """UV map, in the reference's order of preference (:81-109): the mesh's own UVs when every face corner
         has one; else `vt.pth` / `ft.pth` cached in the experiment directory; else a fresh atlas (xatlas when
-        importable, as the reference; otherwise the built-in per-triangle atlas), which is then cached."""
+        importable, as the reference; otherwise the built-in atlas `guide.uv_atlas` names: the per-triangle one or
+        the chart atlas at the texture's resolution), which is then cached."""
         mesh = self.mesh
         if mesh.vt is not None and mesh.ft is not None and mesh.vt.shape[0] > 0 and int(mesh.ft.min()) > -1:
             return mesh.vt.to(self.device), mesh.ft.to(self.device)
@@ -106,7 +107,12 @@ class TexturedMeshModel(nn.Module):
         try:
             import xatlas
         except ImportError:
-            vt, ft = per_triangle_atlas(mesh.faces.shape[0], self.device)
+            kind = check_atlas_choice(getattr(self.opt.guide, "uv_atlas", "triangle"), "guide.uv_atlas")
+            if kind == "charts":
+                vt, ft = chart_atlas(mesh.vertices.to(self.device).float(), mesh.faces.to(self.device),
+                                     self.texture_resolution)
+            else:
+                vt, ft = per_triangle_atlas(mesh.faces.shape[0], self.device)
         else:
             atlas = xatlas.Atlas()
             atlas.add_mesh(mesh.vertices.cpu().numpy(), mesh.faces.int().cpu().numpy())

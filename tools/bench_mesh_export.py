@@ -12,7 +12,11 @@ triangle); mc_GBps = mc_bytes / mc time.
 --target-faces N[,N...]: also time the decimation of each marching-cubes mesh to N faces (raymarching.decimate_mesh: one
 host read per round, so the time includes those synchronisations) with its round and collapse counts, and, on the
 largest lattice, Latent-Paint's rasteriser (lnerf_raster_prepare + lnerf_rasterize at 512 x 512, one view) on the
-undecimated and on each decimated mesh."""
+undecimated and on each decimated mesh.
+--atlas charts [--atlas-resolution 1024]: also time raymarching.chart_atlas on each marching-cubes mesh and on each
+decimated one (the whole call: label rounds with one host read each, the host-side packing, the fold check), with
+its chart, round, shrink (k) and eviction counts and the share of the texture's texels that a face covers.  Only
+sizes >= 256 are run, to keep the leg short."""
 import argparse
 import json
 import os
@@ -67,8 +71,10 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sizes", default="128,256,512")
     ap.add_argument("--target-faces", default="", help="comma-separated face targets of a decimation leg (empty: none)")
+    ap.add_argument("--atlas", default="", choices=["", "charts"], help="charts: also time the chart atlas of every mesh")
+    ap.add_argument("--atlas-resolution", type=int, default=1024)
     args = ap.parse_args()
-    from src.latent_nerf.raymarching import decimate_mesh, marching_cubes
+    from src.latent_nerf.raymarching import chart_atlas, decimate_mesh, marching_cubes, uv_raster
     assert torch.cuda.is_available(), "bench_mesh_export needs the GPU"
     dev = torch.device("cuda:0")
     net, cfg = field(dev, args.precision)
@@ -97,6 +103,15 @@ def main():
                                                    "V_out": int(dv.shape[0]), "rounds": st["rounds"],
                                                    "collapses": st["collapses"]})
             meshes.append((N, dv, df))
+        if args.atlas == "charts" and R >= 256:
+            for label, mv, mf in meshes:
+                st = {}
+                t_a, (vt, ft, _) = timed(lambda: chart_atlas(mv, mf, args.atlas_resolution, stats=st), args.reps)
+                covered = int(uv_raster(mv, mf, vt, ft, args.atlas_resolution)[1].shape[0])
+                row.setdefault("atlas", []).append(
+                    {"F": int(mf.shape[0]), "resolution": args.atlas_resolution, "ms": round(t_a, 3), "charts": st["charts"],
+                     "rounds": st["rounds"], "k": st["k"], "evicted": st["evicted"], "n_vt": int(vt.shape[0]),
+                     "scale": round(st["scale"], 3), "covered": round(covered / args.atlas_resolution ** 2, 4)})
         if targets and R == sizes[-1]:
             row["raster_512_ms"] = {str(int(m[2].shape[0])): round(raster_ms(dev, m[1], m[2], args.reps), 3)
                                     for m in meshes}

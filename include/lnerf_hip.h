@@ -743,6 +743,72 @@ int lnerf_atlas_fold(const float *vt, int n_vt, const int32_t *ft, int n_faces, 
                      void *scratch, size_t scratch_bytes, int32_t *texel_owner, int32_t *evicted, int64_t *counts_dev,
                      lnerf_stream_t stream);
 
+/* ---- mesh cleaning: connected components, a stable filter and Taubin smoothing, what NeRFRenderer.export_mesh runs
+ * between marching cubes and the decimation (csrc/meshclean.hip; raymarching.mesh_components / clean_mesh / smooth_mesh).
+ * Additive to ABI 7.  Device arithmetic is f32 / f64 + - * / sqrt in the order written, no fused multiply-adds; integer
+ * atomics only, so every result is independent of the order in which they land and bit-reproducible (numpy restatement:
+ * tests/meshclean_reference.py).  No kernel loops on anything but a bound fixed at its launch.
+ *   verts [n_verts,3] f32, faces [n_faces,3] int32, n_faces <= LNERF_MESH_MAX_FACES, n_verts <= 3 LNERF_MESH_MAX_FACES.
+ * Connectivity: two vertices are connected iff some face holds both (a face that repeats an index still links its
+ *   distinct vertices).  A face with an index outside [0, n_verts) is skipped by every kernel of the three component
+ *   calls and of the filter, which read nothing through the index (the host side refuses the mesh).
+ * lnerf_mesh_components_begin: label[v] = v; counts_dev int64[1] = the number of faces with an index out of range.
+ * lnerf_mesh_components_round: label[v] converges to the smallest vertex index of v's component.  One round: hook (one
+ *   lane per face: m = the smallest label of its three vertices; for each corner v with m < label[v]:
+ *   atomicMin(label[label[v]], m), atomicMin(label[v], m), *changed_dev = 1), then LNERF_MESH_JUMP_HOPS steps of
+ *   label[v] = label[label[v]] per vertex, applied with atomicMin.  changed_dev int32[1] is cleared first.  A round that
+ *   leaves it 0 changed nothing and the labels are final; the host stops at LNERF_MESH_MAX_ROUNDS and raises.
+ * lnerf_mesh_components_finish: components = the roots (label[v] == v) among the REFERENCED vertices (those in at least
+ *   one face), numbered 0 .. C-1 in ascending root order.  vert_comp [n_verts] (-1 for an unreferenced vertex),
+ *   face_comp [n_faces] = vert_comp[faces[f][0]] (-1 for a skipped face), comp_faces [C] int32 = faces per component,
+ *   comp_box [C,6] f32 = (x_lo, y_lo, z_lo, x_hi, y_hi, z_hi) over the component's vertices, by integer min / max atomics
+ *   on the order-preserving encoding of lnerf_atlas_boxes (so -0 < +0).  comp_faces and comp_box have capacity
+ *   min(n_verts, n_faces) rows (a component owns at least one face and one vertex), C of them written.
+ *   counts_dev int64[2] = {C, referenced vertices}.
+ * lnerf_mesh_filter: face_keep uint8 [n_faces], any per-face flag (a kept face with an index out of range counts as
+ *   dropped).  Kept faces in their old order -> faces_out [capacity n_faces, 3], re-indexed; the vertices they reference
+ *   in their old order: vert_src [capacity n_verts], vert_src[new] = old.  counts_dev int64[2] = {V_out, F_out}.
+ * Keep rule of raymarching.clean_mesh (host, f64, from the f32 comp_box / comp_faces): d_a = hi_a - lo_a,
+ *   diag2_c = (dx dx + dy dy) + dz dz; diag2_mesh the same from the min / max over all component boxes; a component
+ *   passes iff comp_faces >= min_faces and diag2_c >= (min_diameter min_diameter) diag2_mesh; with keep_largest = k > 0
+ *   only the k passing components with the most faces stay (ties to the smaller id).
+ * lnerf_mesh_smooth: Taubin smoothing.  0 <= iterations <= LNERF_SMOOTH_MAX_ITER, 0 < lambda <= 1, -1.5 <= mu <= 0,
+ *   anything else LNERF_ERR_INVALID_ARG.  A face with an index out of range fails the call before any kernel reads
+ *   through it (one host read: the call is synchronous up to there); a face that repeats an index contributes to nothing.
+ *   Incidence list of vertex v: the pairs (f, k) with faces[f][k] == v, ascending in 3 f + k (built on the device: count,
+ *   scan, fill, sort).  A step with weight w reads the positions from before the step; for a vertex with n > 0
+ *   incidences, per coordinate in f64: S = 0; for each incidence ascending S += p[faces[f][(k+1)%3]], then
+ *   S += p[faces[f][(k+2)%3]]; mean = S / (double)(2 n); p' = (float)((double)p + (double)w * (mean - (double)p)).  A
+ *   vertex without incidences keeps its position; a step with w == 0 is skipped.  One iteration = step(lambda) then
+ *   step(mu) (host defaults LNERF_SMOOTH_LAMBDA, LNERF_SMOOTH_MU).  On a closed manifold mesh this is the uniform
+ *   umbrella operator (every neighbour counted twice).
+ *   normals_out (may be NULL), from the final positions, lnerf_decimate's definition: the f32 sum over the vertex's
+ *   incident faces in ascending face order of (p1 - p0) x (p2 - p0), times 1.0f / sqrtf(l2) (0 for l2 = 0).
+ *   iterations = 0 copies the vertices and still gives the normals.  verts_out [n_verts,3] must not be verts.
+ * Scratch sizes: the *_scratch_bytes calls (0 = arguments out of range); scratch is 16-byte aligned. */
+#define LNERF_MESH_MAX_ROUNDS 256
+#define LNERF_MESH_JUMP_HOPS 4
+#define LNERF_MESH_MAX_FACES (1 << 28)
+#define LNERF_SMOOTH_MAX_ITER 1000
+#define LNERF_SMOOTH_LAMBDA 0.5f
+#define LNERF_SMOOTH_MU (-0.53f)
+int lnerf_mesh_components_begin(const int32_t *faces, int n_verts, int n_faces, int32_t *label, int64_t *counts_dev,
+                                lnerf_stream_t stream);
+int lnerf_mesh_components_round(const int32_t *faces, int n_verts, int n_faces, int32_t *label, int32_t *changed_dev,
+                                lnerf_stream_t stream);
+size_t lnerf_mesh_components_scratch_bytes(int n_verts, int n_faces);
+int lnerf_mesh_components_finish(const float *verts, int n_verts, const int32_t *faces, int n_faces, const int32_t *label,
+                                 void *scratch, size_t scratch_bytes, int32_t *vert_comp, int32_t *face_comp,
+                                 int32_t *comp_faces, float *comp_box, int64_t *counts_dev, lnerf_stream_t stream);
+size_t lnerf_mesh_filter_scratch_bytes(int n_verts, int n_faces);
+int lnerf_mesh_filter(const int32_t *faces, int n_verts, int n_faces, const uint8_t *face_keep, void *scratch,
+                      size_t scratch_bytes, int32_t *faces_out, int32_t *vert_src, int64_t *counts_dev,
+                      lnerf_stream_t stream);
+size_t lnerf_mesh_smooth_scratch_bytes(int n_verts, int n_faces);
+int lnerf_mesh_smooth(const float *verts, int n_verts, const int32_t *faces, int n_faces, int iterations, float lambda,
+                      float mu, void *scratch, size_t scratch_bytes, float *verts_out, float *normals_out,
+                      lnerf_stream_t stream);
+
 /* ---- shaded renders (shading = "lambertian" / "textureless"): the kernels around the field (csrc/shade.hip).  Additive
  * to ABI 7.  The normal is the upstream renderer's training normal, a central finite difference of sigma at six offset
  * points; its gradient is the field's ordinary backward at 7 m points.  All arithmetic is f32 + - * / sqrt in the order

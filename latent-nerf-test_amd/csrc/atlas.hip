@@ -19,6 +19,7 @@
 //                                         index over STRICT coverage; <true>, pass B: a face strictly covering a texel
 //                                         it did not win is marked evicted (every writer stores the same 1)
 #include "common.h"
+#include "mesh_shared.h"
 #include "scan.h"
 #include "uv_shared.h"
 
@@ -38,15 +39,6 @@ __device__ __forceinline__ void atlas_plane(int b, float x, float y, float z, fl
         case 4: p = x; q = y; break;
         default: p = y; q = x; break;
     }
-}
-
-// f32 -> u32 with the same order (negative values reversed below the positive ones)
-__device__ __forceinline__ uint32_t atlas_encode(float v) {
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float atlas_decode(uint32_t e) {
-    return __uint_as_float((e & 0x80000000u) ? (e & 0x7FFFFFFFu) : ~e);
 }
 
 __device__ __forceinline__ bool atlas_face_ok(const int32_t *__restrict__ faces, int n_verts, int f, int v[3]) {
@@ -179,7 +171,7 @@ k_atlas_box(const float *__restrict__ verts, int n_verts, const int32_t *__restr
     for (int k = 0; k < 3; ++k) {
         float p, q;
         atlas_plane(b, verts[(int64_t)v[k] * 3], verts[(int64_t)v[k] * 3 + 1], verts[(int64_t)v[k] * 3 + 2], p, q);
-        const uint32_t ep = atlas_encode(p), eq = atlas_encode(q);
+        const uint32_t ep = ordered_encode(p), eq = ordered_encode(q);
         plo = min(plo, ep); phi = max(phi, ep);
         qlo = min(qlo, eq); qhi = max(qhi, eq);
     }
@@ -194,7 +186,7 @@ k_atlas_unbox(const uint32_t *__restrict__ enc, int n_charts, float *__restrict_
     const int c = blockIdx.x * ATLAS_THREADS + threadIdx.x;
     if (c >= n_charts) return;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) chart_box[(int64_t)c * 4 + k] = atlas_decode(enc[(int64_t)k * n_charts + c]);
+    for (int k = 0; k < 4; ++k) chart_box[(int64_t)c * 4 + k] = ordered_decode(enc[(int64_t)k * n_charts + c]);
 }
 
 struct AtlasUv {

@@ -105,6 +105,15 @@ class LogConfig:
     # with save_mesh and mesh_texture_resolution: the UV atlas the texture lives in, "triangle" (every face a chart of its
     # own) or "charts" (connected patches projected along the axis nearest their normals, raymarching.chart_atlas)
     mesh_atlas: str = "triangle"
+    # with save_mesh: the marching-cubes mesh is cleaned before anything else (raymarching.clean_mesh): connected components
+    # with fewer faces than mesh_min_component_faces, or a bounding-box diagonal below mesh_min_component_diameter (a
+    # fraction in [0, 1]) of the whole mesh's, are dropped; mesh_keep_largest = k > 0 keeps the k largest of the rest.
+    # The upstream exporter cleans with 8 faces and 0.05 of the diagonal.  0: off
+    mesh_min_component_faces: int = 0
+    mesh_min_component_diameter: float = 0.0
+    mesh_keep_largest: int = 0
+    # with save_mesh: > 0 runs this many Taubin smoothing iterations (raymarching.smooth_mesh) before the decimation
+    mesh_smooth_iterations: int = 0
     # evaluation also writes a normal-shaded render (*_normals.png / *_normals video) beside every *_rgb one
     eval_normals: bool = False
     max_keep_ckpts: int = 2
@@ -146,6 +155,12 @@ class TrainConfig:
         self.render.layout()  # validates
         if self.log.mesh_atlas not in MESH_ATLASES:
             raise ValueError("log.mesh_atlas must be one of %s, not %r" % (" | ".join(MESH_ATLASES), self.log.mesh_atlas))
+        for n in ("mesh_min_component_faces", "mesh_min_component_diameter", "mesh_keep_largest", "mesh_smooth_iterations"):
+            if not getattr(self.log, n) >= 0:
+                raise ValueError("log.%s must be >= 0, not %r" % (n, getattr(self.log, n)))
+        if self.log.mesh_min_component_diameter > 1:
+            raise ValueError("log.mesh_min_component_diameter is a fraction of the mesh's diagonal in [0, 1], not %r"
+                             % self.log.mesh_min_component_diameter)
 
     def note_explicit(self, key, value):
         """config_cli.apply_overrides tells us which fields the user set."""

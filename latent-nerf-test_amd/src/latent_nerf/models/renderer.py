@@ -558,7 +558,8 @@ class NeRFRenderer(nn.Module):
 
     @torch.no_grad()
     def export_mesh(self, path, resolution=None, S=128, thresh=None, texture_resolution=0, gutter=4, target_faces=0,
-                    field_normals=False, atlas="triangle"):
+                    field_normals=False, atlas="triangle", min_component_faces=0, min_component_diameter=0.0,
+                    keep_largest=0, smooth_iterations=0):
         """Triangle mesh of the density field -> `path`/mesh.obj (the upstream renderer's export_mesh(path, resolution,
         S)): the density on a `resolution`^3 lattice over [-bound, bound]^3 (density_lattice), marching cubes on the GPU
         at iso `thresh` (default min(mean density, density_thresh), as upstream) with the box capped, vertex colours
@@ -577,11 +578,28 @@ class NeRFRenderer(nn.Module):
         atlas: "triangle" (the per-triangle atlas) or "charts" (raymarching.chart_atlas at texture_resolution, of the
         decimated mesh when there is a decimation: connected patches share their texture vertices, and the result also
         carries face_chart, chart_rect and atlas_scale).
+        min_component_faces / min_component_diameter / keep_largest (any > 0): the marching-cubes mesh is cleaned first
+        (raymarching.clean_mesh): connected components with fewer faces, or a bounding-box diagonal below that fraction
+        of the whole mesh's, go -- the floaters of a field trained by score distillation -- and keep_largest = k keeps
+        the k largest of the rest.  The lattice normals follow the vertices that stay.
+        smooth_iterations > 0: that many Taubin iterations (raymarching.smooth_mesh) take the lattice's stair steps
+        out of the surface; without a decimation the normals are then the smoothed mesh's face sums.
+        Order: marching cubes, clean, smooth, decimate, then colours / field normals / atlas / bake on the final mesh.
         Returns dict(verts [V,3], faces [F,3] int32, normals [V,3], colors [V,3], iso, path, faces_before (the
-        marching-cubes face count)) with device tensors, plus vt, ft, texture, mask, rgb when textured."""
+        marching-cubes face count), components and components_kept (None without a cleaning), faces_cleaned (the face
+        count after the cleaning)) with device tensors, plus vt, ft, texture, mask, rgb when textured."""
         from ...uv_atlas import check_atlas_choice
         from .mesh_io import write_obj
         check_atlas_choice(atlas, "export_mesh: atlas")
+        min_component_faces, min_component_diameter = int(min_component_faces), float(min_component_diameter)
+        keep_largest, smooth_iterations = int(keep_largest), int(smooth_iterations)
+        if min_component_faces < 0 or keep_largest < 0:
+            raise ValueError("export_mesh: min_component_faces (%d) and keep_largest (%d) must be >= 0"
+                             % (min_component_faces, keep_largest))
+        if not 0.0 <= min_component_diameter <= 1.0:
+            raise ValueError("export_mesh: min_component_diameter %r outside [0, 1]" % min_component_diameter)
+        if not 0 <= smooth_iterations <= _b.SMOOTH_MAX_ITER:
+            raise ValueError("export_mesh: smooth_iterations %d outside [0, %d]" % (smooth_iterations, _b.SMOOTH_MAX_ITER))
         vol = self.density_lattice(resolution, S)
         if thresh is None:
             iso = float(torch.clamp(self.mean_density_dev.reshape(-1)[0], max=float(self.density_thresh)))
@@ -590,8 +608,18 @@ class NeRFRenderer(nn.Module):
         b = self.bound
         verts, faces, normals = rm.marching_cubes(vol, iso, (-b, -b, -b), (b, b, b), close_boundary=True)
         faces_before = int(faces.shape[0])
+        del vol
+        components = components_kept = None
+        if min_component_faces > 0 or min_component_diameter > 0.0 or keep_largest > 0:
+            st = {}
+            verts, faces, vert_src = rm.clean_mesh(verts, faces, min_component_faces, min_component_diameter, keep_largest,
+                                                   stats=st)
+            normals = normals[vert_src]
+            components, components_kept = st["components"], st["kept"]
+        faces_cleaned = int(faces.shape[0])
+        if smooth_iterations > 0:
+            verts, normals = rm.smooth_mesh(verts, faces, smooth_iterations)
         if int(target_faces) > 0:
-            del vol
             verts, faces, normals = rm.decimate_mesh(verts, faces, int(target_faces))
         colors = torch.empty(verts.shape[0], 3, device=verts.device)
         chunk = S ** 3
@@ -604,7 +632,8 @@ class NeRFRenderer(nn.Module):
                        if verts.shape[0] > 0 else torch.zeros(0, 3, device=verts.device))
         out = os.path.join(str(path), "mesh.obj")
         result = {"verts": verts, "faces": faces, "normals": normals, "colors": colors, "iso": iso, "path": out,
-                  "faces_before": faces_before}
+                  "faces_before": faces_before, "components": components, "components_kept": components_kept,
+                  "faces_cleaned": faces_cleaned}
         if int(texture_resolution) > 0:
             result.update(self._export_textured(str(path), verts, faces, normals, int(texture_resolution), gutter, S,
                                                 bool(field_normals), atlas))

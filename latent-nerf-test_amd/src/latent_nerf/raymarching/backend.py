@@ -29,6 +29,10 @@ UV_MAX_RES = 8192                                             # LNERF_UV_MAX_RES
 DECIMATE_DEFAULT_ROUNDS = 128                                 # LNERF_DECIMATE_DEFAULT_ROUNDS
 ATLAS_MAX_ROUNDS = 256                                        # LNERF_ATLAS_MAX_ROUNDS
 ATLAS_MAX_FACES = 1 << 28                                     # LNERF_ATLAS_MAX_FACES
+MESH_MAX_ROUNDS = 256                                         # LNERF_MESH_MAX_ROUNDS
+MESH_MAX_FACES = 1 << 28                                      # LNERF_MESH_MAX_FACES
+SMOOTH_MAX_ITER = 1000                                        # LNERF_SMOOTH_MAX_ITER
+SMOOTH_LAMBDA, SMOOTH_MU = 0.5, -0.53                         # LNERF_SMOOTH_LAMBDA, LNERF_SMOOTH_MU
 
 
 class LnerfLibraryError(RuntimeError):
@@ -137,6 +141,14 @@ _SIGNATURES = {
     "lnerf_atlas_uv": [_P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _I, _F, _I, _P, _I, _P],
     "lnerf_atlas_fold_scratch_bytes": [_I, _I],
     "lnerf_atlas_fold": [_P, _I, _P, _I, _I, _I, _L, _P, _Z, _P, _P, _P, _P],
+    "lnerf_mesh_components_begin": [_P, _I, _I, _P, _P, _P],
+    "lnerf_mesh_components_round": [_P, _I, _I, _P, _P, _P],
+    "lnerf_mesh_components_scratch_bytes": [_I, _I],
+    "lnerf_mesh_components_finish": [_P, _I, _P, _I, _P, _P, _Z, _P, _P, _P, _P, _P, _P],
+    "lnerf_mesh_filter_scratch_bytes": [_I, _I],
+    "lnerf_mesh_filter": [_P, _I, _I, _P, _P, _Z, _P, _P, _P, _P],
+    "lnerf_mesh_smooth_scratch_bytes": [_I, _I],
+    "lnerf_mesh_smooth": [_P, _I, _P, _I, _I, _F, _F, _P, _Z, _P, _P, _P],
     "lnerf_fd_points": [_P, _F, _F, _L, _P, _P, _P, _P],
     "lnerf_shade_fd_forward": [_P, _P, _I, _P, _L, _I, _P, _I, _F, _P, _P, _P],
     "lnerf_shade_fd_backward": [_P, _P, _I, _P, _L, _I, _P, _I, _F, _P, _P, _P, _P, _P],
@@ -157,6 +169,9 @@ _RESTYPES = {
     "lnerf_atlas_compact_scratch_bytes": _Z,
     "lnerf_atlas_boxes_scratch_bytes": _Z,
     "lnerf_atlas_fold_scratch_bytes": _Z,
+    "lnerf_mesh_components_scratch_bytes": _Z,
+    "lnerf_mesh_filter_scratch_bytes": _Z,
+    "lnerf_mesh_smooth_scratch_bytes": _Z,
 }
 
 _lib = None

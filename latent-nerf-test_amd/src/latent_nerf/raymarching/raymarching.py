@@ -537,6 +537,160 @@ def decimate_mesh(verts, faces, target_faces, max_error=float("inf"), max_rounds
     return out_v[:Vo], out_f[:Fo], out_n[:Vo]
 
 
+# ------------------------------------------------------------------------------ mesh cleaning
+def _mesh_inputs(verts, faces, op):
+    """(verts contiguous f32 on the GPU, faces int32 [F,3] beside it, V, F) for the mesh-cleaning ops."""
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError("%s: verts must be [V,3]" % op)
+    verts = verts.contiguous()
+    _chk(verts, "verts")
+    faces = _face_index(faces, op, "faces", verts.device)
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    if F > _b.MESH_MAX_FACES or V > 3 * _b.MESH_MAX_FACES:
+        raise ValueError("%s: %d vertices / %d faces out of range" % (op, V, F))
+    return verts, faces, V, F
+
+
+def mesh_components(verts, faces, stats=None):
+    """Connected components of a mesh on the GPU (lnerf_mesh_components_*, include/lnerf_hip.h "mesh cleaning"): two
+    vertices are connected iff a face holds both.  verts [V,3] f32, faces [F,3] (into verts), on the GPU ->
+    dict(vert_comp [V] int32 (-1: in no face), face_comp [F] int32, comp_faces [C] int32, comp_box [C,6] f32 (x_lo, y_lo,
+    z_lo, x_hi, y_hi, z_hi), components = C, referenced (vertices in a face), rounds); components are numbered by their
+    smallest vertex.  A face indexing outside verts or a non-finite coordinate raises ValueError.  `stats` (a dict)
+    receives the scalars.  Deterministic bit for bit.  Synchronous: one host read per label round."""
+    verts, faces, V, F = _mesh_inputs(verts, faces, "mesh_components")
+    if V > 0 and not bool(torch.isfinite(verts).all()):
+        raise ValueError("mesh_components: verts holds non-finite coordinates")
+    dev = verts.device
+    i32 = dict(device=dev, dtype=torch.int32)
+    counts = torch.zeros(2, device=dev, dtype=torch.int64)
+    label = torch.empty(V, **i32)
+    _b.call("lnerf_mesh_components_begin", _p(faces), V, F, _p(label), _p(counts), _stream())
+    bad = int(counts[0])
+    if bad:
+        raise ValueError("mesh_components: %d faces index outside verts (%d)" % (bad, V))
+    changed = torch.zeros(1, **i32)
+    rounds = 0
+    while True:
+        if rounds >= _b.MESH_MAX_ROUNDS:
+            raise RuntimeError("mesh_components: the labels have not settled after %d rounds" % rounds)
+        _b.call("lnerf_mesh_components_round", _p(faces), V, F, _p(label), _p(changed), _stream())
+        rounds += 1
+        if int(changed[0]) == 0:
+            break
+    nbytes = _b.get_lib().lnerf_mesh_components_scratch_bytes(V, F)
+    scratch = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    cap = min(V, F)
+    vert_comp, face_comp, comp_faces = torch.empty(V, **i32), torch.empty(F, **i32), torch.empty(cap, **i32)
+    comp_box = torch.empty(cap, 6, device=dev, dtype=torch.float32)
+    _b.call("lnerf_mesh_components_finish", _p(verts), V, _p(faces), F, _p(label), _p(scratch), nbytes, _p(vert_comp),
+            _p(face_comp), _p(comp_faces), _p(comp_box), _p(counts), _stream())
+    C, referenced = (int(c) for c in counts.tolist())
+    if stats is not None:
+        stats.update(components=C, referenced=referenced, rounds=rounds)
+    return dict(vert_comp=vert_comp, face_comp=face_comp, comp_faces=comp_faces[:C], comp_box=comp_box[:C], components=C,
+                referenced=referenced, rounds=rounds)
+
+
+def mesh_filter(verts, faces, face_keep):
+    """The faces with a non-zero flag and the vertices they reference, both in their old order (lnerf_mesh_filter).
+    verts [V,3] f32, faces [F,3], face_keep [F] (bool / uint8), on the GPU -> verts [V',3], faces [F',3] int32
+    (re-indexed), vert_src [V'] long with verts_out = verts[vert_src]: gather any per-vertex attribute through it."""
+    verts, faces, V, F = _mesh_inputs(verts, faces, "mesh_filter")
+    if not isinstance(face_keep, torch.Tensor) or face_keep.shape != (F,) or face_keep.dtype not in (torch.bool, torch.uint8):
+        raise ValueError("mesh_filter: face_keep must be a bool / uint8 tensor [%d]" % F)
+    dev = verts.device
+    keep = face_keep.to(device=dev, dtype=torch.uint8).contiguous()
+    nbytes = _b.get_lib().lnerf_mesh_filter_scratch_bytes(V, F)
+    scratch = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    counts = torch.zeros(2, device=dev, dtype=torch.int64)
+    faces_out = torch.empty(F, 3, device=dev, dtype=torch.int32)
+    vert_src = torch.empty(V, device=dev, dtype=torch.int32)
+    _b.call("lnerf_mesh_filter", _p(faces), V, F, _p(keep), _p(scratch), nbytes, _p(faces_out), _p(vert_src), _p(counts),
+            _stream())
+    Vo, Fo = (int(c) for c in counts.tolist())
+    vert_src = vert_src[:Vo].long()
+    return verts[vert_src], faces_out[:Fo], vert_src
+
+
+def component_keep(comp_faces, comp_box, min_faces=0, min_diameter=0.0, keep_largest=0):
+    """clean_mesh's keep rule (include/lnerf_hip.h "mesh cleaning"), on the host in f64: comp_faces [C], comp_box [C,6]
+    numpy -> bool [C]."""
+    import numpy as np
+    n = np.asarray(comp_faces, np.int64)
+    box = np.asarray(comp_box, np.float64).reshape(-1, 6)
+    C = len(n)
+    if C == 0:
+        return np.zeros(0, bool)
+    d = box[:, 3:] - box[:, :3]
+    diag2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+    D = box[:, 3:].max(0) - box[:, :3].min(0)
+    diag2_mesh = (D[0] * D[0] + D[1] * D[1]) + D[2] * D[2]
+    md = float(min_diameter)
+    ok = (n >= int(min_faces)) & (diag2 >= (md * md) * diag2_mesh)
+    k = int(keep_largest)
+    if k > 0:
+        order = sorted(np.nonzero(ok)[0].tolist(), key=lambda c: (-int(n[c]), c))[:k]
+        ok = np.zeros(C, bool)
+        ok[order] = True
+    return ok
+
+
+def clean_mesh(verts, faces, min_faces=0, min_diameter=0.0, keep_largest=0, stats=None):
+    """Drop the small connected components of a mesh on the GPU: a component stays iff it has at least `min_faces` faces
+    and its bounding-box diagonal is at least `min_diameter` (a fraction in [0, 1]) of the whole mesh's; keep_largest =
+    k > 0 then keeps only the k such components with the most faces.  The rule itself runs on the host from the
+    components' boxes and counts (mesh_components); the compaction is lnerf_mesh_filter.
+    -> verts [V',3] f32, faces [F',3] int32, vert_src [V'] long (verts' = verts[vert_src]); faces and vertices keep their
+    order.  With everything at 0 only the vertices in no face go.  `stats` (a dict) receives components, kept, rounds,
+    faces_before, faces_after."""
+    min_faces, keep_largest, min_diameter = int(min_faces), int(keep_largest), float(min_diameter)
+    if min_faces < 0 or keep_largest < 0:
+        raise ValueError("clean_mesh: min_faces (%d) and keep_largest (%d) must be >= 0" % (min_faces, keep_largest))
+    if not 0.0 <= min_diameter <= 1.0:
+        raise ValueError("clean_mesh: min_diameter %r outside [0, 1]" % min_diameter)
+    verts, faces, V, F = _mesh_inputs(verts, faces, "clean_mesh")
+    comp = mesh_components(verts, faces)
+    ok = component_keep(comp["comp_faces"].cpu().numpy(), comp["comp_box"].cpu().numpy(), min_faces, min_diameter,
+                        keep_largest)
+    ok_dev = torch.as_tensor(ok, device=verts.device)
+    keep = ok_dev[comp["face_comp"].long()] if F > 0 else torch.zeros(0, device=verts.device, dtype=torch.bool)
+    out_v, out_f, vert_src = mesh_filter(verts, faces, keep)
+    if stats is not None:
+        stats.update(components=comp["components"], kept=int(ok.sum()), rounds=comp["rounds"], faces_before=F,
+                     faces_after=int(out_f.shape[0]))
+    return out_v, out_f, vert_src
+
+
+def smooth_mesh(verts, faces, iterations=10, lam=_b.SMOOTH_LAMBDA, mu=_b.SMOOTH_MU):
+    """Taubin smoothing on the GPU (lnerf_mesh_smooth): `iterations` times a step of weight `lam` towards the mean of the
+    incident faces' other corners, then a step of weight `mu` (negative: it undoes the shrinkage; mu = 0 is plain
+    Laplacian smoothing).  verts [V,3] f32, faces [F,3] (into verts), on the GPU -> verts [V,3] f32, normals [V,3] f32
+    (area-weighted face sums of the result, as decimate_mesh's).  The connectivity does not change.  iterations = 0
+    gives the vertices back with their normals.  Deterministic bit for bit."""
+    iterations, lam, mu = int(iterations), float(lam), float(mu)
+    if not 0 <= iterations <= _b.SMOOTH_MAX_ITER:
+        raise ValueError("smooth_mesh: %d iterations outside [0, %d]" % (iterations, _b.SMOOTH_MAX_ITER))
+    if not 0.0 < lam <= 1.0:
+        raise ValueError("smooth_mesh: lam %r outside (0, 1]" % lam)
+    if not -1.5 <= mu <= 0.0:
+        raise ValueError("smooth_mesh: mu %r outside [-1.5, 0]" % mu)
+    verts, faces, V, F = _mesh_inputs(verts, faces, "smooth_mesh")
+    dev = verts.device
+    nbytes = _b.get_lib().lnerf_mesh_smooth_scratch_bytes(V, F)
+    scratch = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    out_v = torch.empty(V, 3, device=dev, dtype=torch.float32)
+    out_n = torch.empty(V, 3, device=dev, dtype=torch.float32)
+    try:
+        _b.call("lnerf_mesh_smooth", _p(verts), V, _p(faces), F, iterations, lam, mu, _p(scratch), nbytes, _p(out_v),
+                _p(out_n), _stream())
+    except _b.LnerfError as e:
+        if "index outside" in str(e):
+            raise ValueError("smooth_mesh: %s" % e) from e
+        raise
+    return out_v, out_n
+
+
 # ------------------------------------------------------------------------------ chart atlas
 def _half_edge_twins(faces, V):
     """twin [3F] int32 of the half-edges 3 f + k = faces[f][k] -> faces[f][(k+1)%3]: the one half-edge the other way round

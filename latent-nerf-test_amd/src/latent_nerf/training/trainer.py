@@ -540,9 +540,16 @@ class Trainer:
             target = int(getattr(self.cfg.log, "mesh_target_faces", 0))
             mesh = self.nerf.export_mesh(self.exp_path / "mesh", texture_resolution=tex, target_faces=target,
                                          field_normals=bool(getattr(self.cfg.log, "mesh_field_normals", False)),
-                                         atlas=getattr(self.cfg.log, "mesh_atlas", "triangle"))
+                                         atlas=getattr(self.cfg.log, "mesh_atlas", "triangle"),
+                                         min_component_faces=int(getattr(self.cfg.log, "mesh_min_component_faces", 0)),
+                                         min_component_diameter=float(getattr(self.cfg.log, "mesh_min_component_diameter", 0.0)),
+                                         keep_largest=int(getattr(self.cfg.log, "mesh_keep_largest", 0)),
+                                         smooth_iterations=int(getattr(self.cfg.log, "mesh_smooth_iterations", 0)))
             self.log("exported %s (%d vertices, %d triangles; %d before decimation; iso %.4g)"
                      % (mesh["path"], mesh["verts"].shape[0], mesh["faces"].shape[0], mesh["faces_before"], mesh["iso"]))
+            if mesh["components"] is not None:
+                self.log("mesh cleaning kept %d of %d components (%d of %d triangles)"
+                         % (mesh["components_kept"], mesh["components"], mesh["faces_cleaned"], mesh["faces_before"]))
         return frames
 
     def preview_rgb(self, latents):

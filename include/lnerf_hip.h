@@ -844,6 +844,44 @@ int lnerf_shade_fd_backward(const float *sigmas7, const float *rgbs7, int C, con
                             int rays_per_view, const float *shade, int B, float inv_2eps, const float *dsigma_c,
                             const float *dcolours, float *dsigmas7, float *drgbs7, lnerf_stream_t stream);
 
+/* ---- orientation regulariser of the shaded renders (Ref-NeRF's R_o, the upstream trainers' lambda_orient), fused into the
+ * shade kernels (csrc/shade.hip).  Additive to ABI 7.  Per ray:  orient = sum_i w_i max(0, n_i . v)^2  -- the compositing
+ * weight times the squared share of the normal that faces AWAY from the camera.  All arithmetic is f32 + - * / sqrt in the
+ * order written here, no fused multiply-adds, except the weight w (expf, a 64-lane scan: tolerance-checked).  numpy
+ * restatement: tests/orient_reference.py.
+ *
+ * lnerf_shade_fd_orient_forward: lnerf_shade_fd_forward's arguments and outputs (sigma_c and colours bit for bit), plus
+ *   deltas f32 [cap, 2] = (dt, t) of the march (8-byte aligned), rays_d f32 [n_ids, 3], density_scale >= 0, T_thresh and the
+ *   output orient f32 [n_ids].  For ray r with (id, off, cnt) = rays[r]:
+ *     d = rays_d[id],   s_v = (d_x d_x + d_y d_y) + d_z d_z,   r_v = 1 / sqrt(fmax(s_v, 1e-20)),   v_a = d_a * r_v;
+ *   per sample i < cnt, s = off + i, with n of lnerf_shade_fd_forward:
+ *     c = (n_x v_x + n_y v_y) + n_z v_z,   q = c > 0 ? c : 0;
+ *   w_i is the compositing weight as lnerf_composite_rays_train_forward defines it, on sigma' = density_scale * sg[0]:
+ *     tau = sigma' * dt (dt = deltas[s][0]), 64-lane inclusive scan of tau with a scalar carry between the chunks of 64,
+ *     excl = (the previous lane's inclusive sum; lane 0: 0) + carry -- never inc - tau --, T = expf(-excl),
+ *     alpha = 1 - expf(-tau),   w = T >= T_thresh ? alpha * T : 0.
+ *   Unlike the compositing there is no early stop: behind T < T_thresh every sample still gets its sigma_c and colours
+ *   (and, in the backward, its gradient rows); only w is 0.
+ *     orient[id] = sum_i w_i * (q_i * q_i)   (lane partials over i = lane, lane + 64, ..; then the wave's sum; one writer).
+ *   A ray with cnt = 0 writes orient[id] = 0 (and nothing else).
+ *
+ * lnerf_shade_fd_orient_backward: lnerf_shade_fd_backward's arguments, plus deltas, rays_d, density_scale, T_thresh as above
+ *   and d_orient f32 [n_ids], the gradient w.r.t. orient.  w is DETACHED: it is recomputed as in the forward and no gradient
+ *   reaches sg[0] or deltas through it.  Per sample, with go = d_orient[id]:
+ *     e = go * w_i,   dn_a = (dn_a of lnerf_shade_fd_backward) + (e * (2 q)) * v_a,
+ *   and the rest is lnerf_shade_fd_backward from its q = n . dn on: the projection, the seven dsigmas7 rows, the drgbs7
+ *   rows.  One writer per element, no atomics, no memset, the same bits on every run.  d_orient == NULL: no gradient for
+ *   the term -- the call IS lnerf_shade_fd_backward (the same kernel; deltas and rays_d are then not read). */
+int lnerf_shade_fd_orient_forward(const float *sigmas7, const float *rgbs7, int C, const int32_t *rays, int64_t N,
+                                  int rays_per_view, const float *shade, int B, float inv_2eps, const float *deltas,
+                                  const float *rays_d, float density_scale, float T_thresh, float *sigma_c, float *colours,
+                                  float *orient, lnerf_stream_t stream);
+int lnerf_shade_fd_orient_backward(const float *sigmas7, const float *rgbs7, int C, const int32_t *rays, int64_t N,
+                                   int rays_per_view, const float *shade, int B, float inv_2eps, const float *dsigma_c,
+                                   const float *dcolours, const float *deltas, const float *rays_d, float density_scale,
+                                   float T_thresh, const float *d_orient, float *dsigmas7, float *drgbs7,
+                                   lnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

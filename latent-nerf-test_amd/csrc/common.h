@@ -120,6 +120,15 @@ __device__ __forceinline__ float wave_sum(float v) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
+// Optical depth in front of this lane's sample, from the chunk's inclusive scan `inc` and the depth `carry` of the chunks
+// before it: the NEIGHBOURING lane's inclusive sum (lane 0: nothing), never `inc - tau`.  The lane's own tau can be
+// arbitrarily large (sigma = exp(h) is unclamped, a surface sample has sigma dt ~ 1e4 and more); subtracting it back out
+// of a sum that contains it rounds the small prefix in front of it away (error 2^-24 tau in excl, i.e. in T and the
+// weight; inf - inf = NaN at sigma = +inf).  The compositing forward and backward both call this (the backward's `keep`
+// has to reproduce the forward's decisions bit for bit), and so does the orientation term of the shaded renders
+// (shade.hip), whose weights are the compositing's.
+__device__ __forceinline__ float exclusive_depth(float inc, float carry) { return lane_prev_f(inc, 0.f) + carry; }
+
 __device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float(((uint32_t)h) << 16); }
 // round-to-nearest-even f32 -> bf16 (NaN preserved as quiet NaN)
 __device__ __forceinline__ uint16_t f32_to_bf16(float f) {

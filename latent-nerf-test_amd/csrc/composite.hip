@@ -37,14 +37,8 @@ __device__ __forceinline__ Chunk<C> load_chunk(const float *__restrict__ sigmas,
     return k;
 }
 
-// Optical depth in front of this lane's sample, from the chunk's inclusive scan `inc` and the depth `carry` of the chunks
-// before it: the NEIGHBOURING lane's inclusive sum (lane 0: nothing), never `inc - tau`.  The lane's own tau can be
-// arbitrarily large (sigma = exp(h) is unclamped, a surface sample has sigma dt ~ 1e4 and more); subtracting it back out
-// of a sum that contains it rounds the small prefix in front of it away (error 2^-24 tau in excl, i.e. in T and the
-// weight; inf - inf = NaN at sigma = +inf).  Forward and backward both call this: the backward's `keep` has to
-// reproduce the forward's decisions bit for bit.
-__device__ __forceinline__ float exclusive_depth(float inc, float carry) { return lane_prev_f(inc, 0.f) + carry; }
-
+// (exclusive_depth, the optical depth in front of a lane's sample, lives in common.h: the shaded renders' orientation
+// term takes its weights from the same function)
 // One ray's forward loop over its span: each lane's share of weights_sum, depth and the C colour sums (no background);
 // the caller adds them across the wave.
 template <int C>

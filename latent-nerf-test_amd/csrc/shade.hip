@@ -4,6 +4,8 @@
 //   k_fd_points   sample -> itself + its six +-eps neighbours (clamped to the box), rows 7 i .. 7 i + 6, and m7 = 7 m
 //   k_shade_fwd   the seven densities of a sample -> finite-difference normal -> Lambert term -> colour
 //   k_shade_bwd   recomputes the normal and the Lambert term, writes the gradient of all seven rows (one writer each)
+//   k_shade_orient_fwd / _bwd   the same with the orientation term fused in: orient[ray] = sum_i w_i max(0, n_i . v)^2, w
+//                  the compositing weight (scanned here, detached), its gradient added to dn before the projection
 //
 // All arithmetic is f32 + - * / sqrt in the stated order: the library is built with -ffp-contract=off and nothing here
 // is an explicit fmaf, so the numpy restatement matches bit for bit.
@@ -116,6 +118,22 @@ __device__ __forceinline__ Lambert lambert_of(const float (&sg)[FD_ROWS], float 
     return o;
 }
 
+// the forward's two rows of sample s: its own density and its shaded colour
+template <int C>
+__device__ __forceinline__ void store_shaded(const Sample7<C> &k, const Lambert &o, const Light &L, int64_t s,
+                                             float *__restrict__ sigma_c, float *__restrict__ colours) {
+    sigma_c[s] = k.sg[0];
+    float col[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) col[c] = L.textureless ? o.lam : k.alb[c] * o.lam;
+    if (C == 4) {
+        reinterpret_cast<float4 *>(colours)[s] = make_float4(col[0], col[1], col[2], col[C - 1]);
+    } else {
+#pragma unroll
+        for (int c = 0; c < C; ++c) colours[s * C + c] = col[c];
+    }
+}
+
 // One wavefront per ray, lanes striding over the ray's samples; the next 64 samples' loads are requested before this
 // chunk's arithmetic (the kernel is a few memory round trips long, nothing else).
 template <int C>
@@ -139,16 +157,7 @@ k_shade_fwd(const float *__restrict__ sigmas7, const float *__restrict__ rgbs7, 
         if (i < cnt) {
             const int64_t s = off + i;
             const Lambert o = lambert_of(cur.sg, inv_2eps, L);
-            sigma_c[s] = cur.sg[0];
-            float col[C];
-#pragma unroll
-            for (int c = 0; c < C; ++c) col[c] = L.textureless ? o.lam : cur.alb[c] * o.lam;
-            if (C == 4) {
-                reinterpret_cast<float4 *>(colours)[s] = make_float4(col[0], col[1], col[2], col[C - 1]);
-            } else {
-#pragma unroll
-                for (int c = 0; c < C; ++c) colours[s * C + c] = col[c];
-            }
+            store_shaded<C>(cur, o, L, s, sigma_c, colours);
         }
         cur = nxt;
     }
@@ -180,6 +189,64 @@ __device__ __forceinline__ Grad7<C> load_grad7(const float *__restrict__ dsigma_
     return k;
 }
 
+// The backward's first half: gradient of the colours w.r.t. the normal (dn, before the projection onto its tangent plane)
+// and the albedo.
+template <int C>
+__device__ __forceinline__ void lambert_grad(const Sample7<C> &cur, const Grad7<C> &gcur, const Lambert &o, const Light &L,
+                                             float (&dn)[3], float (&dalb)[C]) {
+    float dlam;
+    if (L.textureless) {
+        dlam = gcur.dcol[0];
+#pragma unroll
+        for (int c = 1; c < C; ++c) dlam = dlam + gcur.dcol[c];
+#pragma unroll
+        for (int c = 0; c < C; ++c) dalb[c] = 0.f;
+    } else {
+        dlam = gcur.dcol[0] * cur.alb[0];
+#pragma unroll
+        for (int c = 1; c < C; ++c) dlam = dlam + gcur.dcol[c] * cur.alb[c];
+#pragma unroll
+        for (int c = 0; c < C; ++c) dalb[c] = gcur.dcol[c] * o.lam;
+    }
+    const float k = L.diffuse * dlam;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) dn[a] = o.d > 0.f ? k * L.l[a] : 0.f;
+}
+
+// The backward's second half: dn -> the gradient of the six offset densities (through n = -g / |g|), and the seven rows of
+// both outputs of the sample whose first row is s7.
+template <int C>
+__device__ __forceinline__ void project_and_store(const Lambert &o, const float (&dn)[3], float dsig, const float (&dalb)[C],
+                                                  float inv_2eps, int64_t s7, float *__restrict__ dsigmas7,
+                                                  float *__restrict__ drgbs7) {
+    const float ndn = (o.n[0] * dn[0] + o.n[1] * dn[1]) + o.n[2] * dn[2];
+    const bool project = o.s > 1e-20f;
+    float ds[FD_ROWS];
+    ds[0] = dsig;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float t = project ? dn[a] - o.n[a] * ndn : dn[a];
+        const float dg = -(o.r * t);
+        const float v = dg * inv_2eps;
+        ds[1 + 2 * a] = v;
+        ds[2 + 2 * a] = -v;
+    }
+#pragma unroll
+    for (int j = 0; j < FD_ROWS; ++j) dsigmas7[s7 + j] = ds[j];
+    if (C == 4) {
+        float4 *row = reinterpret_cast<float4 *>(drgbs7) + s7;
+        row[0] = make_float4(dalb[0], dalb[1], dalb[2], dalb[C - 1]);
+#pragma unroll
+        for (int j = 1; j < FD_ROWS; ++j) row[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+        float *row = drgbs7 + s7 * C;
+#pragma unroll
+        for (int c = 0; c < C; ++c) row[c] = dalb[c];
+#pragma unroll
+        for (int j = C; j < FD_ROWS * C; ++j) row[j] = 0.f;
+    }
+}
+
 // Same launch shape as the forward.  Every element of rows 7 (off + i) .. 7 (off + i) + 6 of dsigmas7 and drgbs7 is
 // written by the lane that owns sample i: no atomics.
 template <int C>
@@ -208,53 +275,140 @@ k_shade_bwd(const float *__restrict__ sigmas7, const float *__restrict__ rgbs7, 
         if (i < cnt) {
             const int64_t s7 = (off + i) * FD_ROWS;
             const Lambert o = lambert_of(cur.sg, inv_2eps, L);
-            float dlam, dalb[C];
-            if (L.textureless) {
-                dlam = gcur.dcol[0];
-#pragma unroll
-                for (int c = 1; c < C; ++c) dlam = dlam + gcur.dcol[c];
-#pragma unroll
-                for (int c = 0; c < C; ++c) dalb[c] = 0.f;
-            } else {
-                dlam = gcur.dcol[0] * cur.alb[0];
-#pragma unroll
-                for (int c = 1; c < C; ++c) dlam = dlam + gcur.dcol[c] * cur.alb[c];
-#pragma unroll
-                for (int c = 0; c < C; ++c) dalb[c] = gcur.dcol[c] * o.lam;
-            }
-            const float k = L.diffuse * dlam;
-            float dn[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) dn[a] = o.d > 0.f ? k * L.l[a] : 0.f;
-            const float ndn = (o.n[0] * dn[0] + o.n[1] * dn[1]) + o.n[2] * dn[2];
-            const bool project = o.s > 1e-20f;
-            float ds[FD_ROWS];
-            ds[0] = gcur.dsig;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const float t = project ? dn[a] - o.n[a] * ndn : dn[a];
-                const float dg = -(o.r * t);
-                const float v = dg * inv_2eps;
-                ds[1 + 2 * a] = v;
-                ds[2 + 2 * a] = -v;
-            }
-#pragma unroll
-            for (int j = 0; j < FD_ROWS; ++j) dsigmas7[s7 + j] = ds[j];
-            if (C == 4) {
-                float4 *row = reinterpret_cast<float4 *>(drgbs7) + s7;
-                row[0] = make_float4(dalb[0], dalb[1], dalb[2], dalb[C - 1]);
-#pragma unroll
-                for (int j = 1; j < FD_ROWS; ++j) row[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-            } else {
-                float *row = drgbs7 + s7 * C;
-#pragma unroll
-                for (int c = 0; c < C; ++c) row[c] = dalb[c];
-#pragma unroll
-                for (int j = C; j < FD_ROWS * C; ++j) row[j] = 0.f;
-            }
+            float dn[3], dalb[C];
+            lambert_grad<C>(cur, gcur, o, L, dn, dalb);
+            project_and_store<C>(o, dn, gcur.dsig, dalb, inv_2eps, s7, dsigmas7, drgbs7);
         }
         cur = nxt;
         gcur = gnxt;
+    }
+}
+
+// ---- the orientation term (contract: include/lnerf_hip.h, "orientation regulariser"; numpy: tests/orient_reference.py)
+
+// unit view direction of ray `id`
+__device__ __forceinline__ void view_dir(const float *__restrict__ rays_d, int64_t id, float (&v)[3]) {
+    const float d[3] = {rays_d[id * 3], rays_d[id * 3 + 1], rays_d[id * 3 + 2]};
+    const float s = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
+    const float r = 1.0f / sqrtf(fmaxf(s, 1e-20f));
+#pragma unroll
+    for (int a = 0; a < 3; ++a) v[a] = d[a] * r;
+}
+
+// dt of sample i of the span (0 past its end): the .x of the march's 8-byte (dt, t) pair
+__device__ __forceinline__ float load_dt(const float *__restrict__ deltas, int64_t off, int cnt, int i) {
+    return i < cnt ? reinterpret_cast<const float2 *>(deltas)[off + i].x : 0.f;
+}
+
+// Compositing weight of this lane's sample, as composite_ray_fwd defines it, on `sigma` (scaled already) -- called by
+// ALL 64 lanes (lanes past the span pass zeros).  There is no early stop here: behind T < T_thresh the weights are 0 and
+// the chunks go on, every sample of the span still gets its rows.
+__device__ __forceinline__ float composite_weight(float sigma, float dt, bool valid, float T_thresh, float &carry) {
+    const float tau = sigma * dt;
+    const float inc = wave_inclusive_sum(tau);
+    const float excl = exclusive_depth(inc, carry);
+    const float T = expf(-excl);
+    const float alpha = 1.0f - expf(-tau);
+    carry += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(inc), 63));
+    return (valid && T >= T_thresh) ? alpha * T : 0.f;
+}
+
+// max(0, n . v)
+__device__ __forceinline__ float facing_away(const Lambert &o, const float (&v)[3]) {
+    const float c = (o.n[0] * v[0] + o.n[1] * v[1]) + o.n[2] * v[2];
+    return c > 0.f ? c : 0.f;
+}
+
+// k_shade_fwd plus orient[id] = sum_i w_i q_i^2 (a ray without samples writes 0: the buffer is uninitialised).
+template <int C>
+__global__ void __launch_bounds__(256)
+k_shade_orient_fwd(const float *__restrict__ sigmas7, const float *__restrict__ rgbs7, const int32_t *__restrict__ rays,
+                   int64_t N, int rays_per_view, const float *__restrict__ shade, int B, float inv_2eps,
+                   const float *__restrict__ deltas, const float *__restrict__ rays_d, float density_scale, float T_thresh,
+                   float *__restrict__ sigma_c, float *__restrict__ colours, float *__restrict__ orient) {
+    const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (r >= N) return;
+    const int lane = lane_id();
+    const int64_t id = rays[r * 3];
+    const int64_t off = rays[r * 3 + 1];
+    const int cnt = rays[r * 3 + 2];
+    const Light L = load_light(shade, id, rays_per_view, B);
+    float v[3];
+    view_dir(rays_d, id, v);
+    float acc = 0.f, carry = 0.f;
+    Sample7<C> cur = load_sample7<C>(sigmas7, rgbs7, off, cnt, lane);
+    float dt = load_dt(deltas, off, cnt, lane);
+    for (int base = 0; base < cnt; base += 64) {      // (wave-uniform: the scan below runs with all lanes)
+        Sample7<C> nxt = cur;
+        float dt_nxt = dt;
+        if (base + 64 < cnt) {
+            nxt = load_sample7<C>(sigmas7, rgbs7, off, cnt, base + 64 + lane);
+            dt_nxt = load_dt(deltas, off, cnt, base + 64 + lane);
+        }
+        const int i = base + lane;
+        const bool valid = i < cnt;
+        const Lambert o = lambert_of(cur.sg, inv_2eps, L);
+        if (valid) store_shaded<C>(cur, o, L, off + i, sigma_c, colours);
+        const float w = composite_weight(density_scale * cur.sg[0], dt, valid, T_thresh, carry);
+        const float q = facing_away(o, v);
+        acc += w * (q * q);
+        cur = nxt;
+        dt = dt_nxt;
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) orient[id] = acc;
+}
+
+// k_shade_bwd with the term's gradient in dn:  dn_a += (go w (2 q)) v_a, go = d_orient[id], w recomputed and DETACHED (no
+// gradient reaches sg[0] or deltas through it).
+template <int C>
+__global__ void __launch_bounds__(256)
+k_shade_orient_bwd(const float *__restrict__ sigmas7, const float *__restrict__ rgbs7, const int32_t *__restrict__ rays,
+                   int64_t N, int rays_per_view, const float *__restrict__ shade, int B, float inv_2eps,
+                   const float *__restrict__ dsigma_c, const float *__restrict__ dcolours, const float *__restrict__ deltas,
+                   const float *__restrict__ rays_d, float density_scale, float T_thresh, const float *__restrict__ d_orient,
+                   float *__restrict__ dsigmas7, float *__restrict__ drgbs7) {
+    const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (r >= N) return;
+    const int lane = lane_id();
+    const int64_t id = rays[r * 3];
+    const int64_t off = rays[r * 3 + 1];
+    const int cnt = rays[r * 3 + 2];
+    if (cnt <= 0) return;
+    const Light L = load_light(shade, id, rays_per_view, B);
+    float v[3];
+    view_dir(rays_d, id, v);
+    const float go = d_orient[id];
+    float carry = 0.f;
+    Sample7<C> cur = load_sample7<C>(sigmas7, rgbs7, off, cnt, lane);
+    Grad7<C> gcur = load_grad7<C>(dsigma_c, dcolours, off, cnt, lane);
+    float dt = load_dt(deltas, off, cnt, lane);
+    for (int base = 0; base < cnt; base += 64) {      // (wave-uniform)
+        Sample7<C> nxt = cur;
+        Grad7<C> gnxt = gcur;
+        float dt_nxt = dt;
+        if (base + 64 < cnt) {
+            nxt = load_sample7<C>(sigmas7, rgbs7, off, cnt, base + 64 + lane);
+            gnxt = load_grad7<C>(dsigma_c, dcolours, off, cnt, base + 64 + lane);
+            dt_nxt = load_dt(deltas, off, cnt, base + 64 + lane);
+        }
+        const int i = base + lane;
+        const bool valid = i < cnt;
+        const Lambert o = lambert_of(cur.sg, inv_2eps, L);
+        const float w = composite_weight(density_scale * cur.sg[0], dt, valid, T_thresh, carry);
+        if (valid) {
+            float dn[3], dalb[C];
+            lambert_grad<C>(cur, gcur, o, L, dn, dalb);
+            const float q = facing_away(o, v);
+            const float e = go * w;
+            const float k = e * (2.0f * q);
+#pragma unroll
+            for (int a = 0; a < 3; ++a) dn[a] = dn[a] + k * v[a];
+            project_and_store<C>(o, dn, gcur.dsig, dalb, inv_2eps, (off + i) * FD_ROWS, dsigmas7, drgbs7);
+        }
+        cur = nxt;
+        gcur = gnxt;
+        dt = dt_nxt;
     }
 }
 
@@ -332,5 +486,76 @@ int lnerf_shade_fd_backward(const float *sigmas7, const float *rgbs7, int C, con
     LNERF_CHECK_LAUNCH("shade_fd_backward");
     return LNERF_OK;
 }
+
+// the arguments the orient entry points add to the plain ones
+#define LNERF_REQUIRE_ORIENT(name)                                                                                     \
+    LNERF_REQUIRE(deltas && rays_d, name ": null pointer (deltas / rays_d)");                                          \
+    LNERF_REQUIRE(((uintptr_t)deltas & 7) == 0, name ": deltas must be 8-byte aligned");                               \
+    LNERF_REQUIRE(density_scale >= 0.f, name ": density_scale must be >= 0")
+
+int lnerf_shade_fd_orient_forward(const float *sigmas7, const float *rgbs7, int C, const int32_t *rays, int64_t N,
+                                  int rays_per_view, const float *shade, int B, float inv_2eps, const float *deltas,
+                                  const float *rays_d, float density_scale, float T_thresh, float *sigma_c, float *colours,
+                                  float *orient, lnerf_stream_t stream) {
+    LNERF_REQUIRE(N >= 0, "shade_fd_orient_forward: negative N");
+    LNERF_REQUIRE(C >= 1 && C <= 4, "shade_fd_orient_forward: C must be 1..4 (got %d)", C);
+    LNERF_REQUIRE(rays_per_view > 0, "shade_fd_orient_forward: rays_per_view must be > 0");
+    if (N == 0) return LNERF_OK;
+    LNERF_REQUIRE(B > 0, "shade_fd_orient_forward: B must be > 0");
+    LNERF_REQUIRE(sigmas7 && rgbs7 && rays && shade && sigma_c && colours && orient,
+                  "shade_fd_orient_forward: null pointer");
+    LNERF_REQUIRE(C != 4 || (((uintptr_t)rgbs7 | (uintptr_t)colours) & 15) == 0,
+                  "shade_fd_orient_forward: (C = 4) rgbs7 / colours must be 16-byte aligned");
+    LNERF_REQUIRE_ORIENT("shade_fd_orient_forward");
+    const dim3 grid((unsigned)div_up(N, 4)), block(256);
+#define LNERF_SHADE_FWD(CC)                                                                                            \
+    hipLaunchKernelGGL(k_shade_orient_fwd<CC>, grid, block, 0, as_stream(stream), sigmas7, rgbs7, rays, N, rays_per_view, \
+                       shade, B, inv_2eps, deltas, rays_d, density_scale, T_thresh, sigma_c, colours, orient)
+    switch (C) {
+        case 1: LNERF_SHADE_FWD(1); break;
+        case 2: LNERF_SHADE_FWD(2); break;
+        case 3: LNERF_SHADE_FWD(3); break;
+        default: LNERF_SHADE_FWD(4); break;
+    }
+#undef LNERF_SHADE_FWD
+    LNERF_CHECK_LAUNCH("shade_fd_orient_forward");
+    return LNERF_OK;
+}
+
+int lnerf_shade_fd_orient_backward(const float *sigmas7, const float *rgbs7, int C, const int32_t *rays, int64_t N,
+                                   int rays_per_view, const float *shade, int B, float inv_2eps, const float *dsigma_c,
+                                   const float *dcolours, const float *deltas, const float *rays_d, float density_scale,
+                                   float T_thresh, const float *d_orient, float *dsigmas7, float *drgbs7,
+                                   lnerf_stream_t stream) {
+    // no gradient for the term: the plain backward, the same kernel and hence the same bits
+    if (!d_orient)
+        return lnerf_shade_fd_backward(sigmas7, rgbs7, C, rays, N, rays_per_view, shade, B, inv_2eps, dsigma_c, dcolours,
+                                       dsigmas7, drgbs7, stream);
+    LNERF_REQUIRE(N >= 0, "shade_fd_orient_backward: negative N");
+    LNERF_REQUIRE(C >= 1 && C <= 4, "shade_fd_orient_backward: C must be 1..4 (got %d)", C);
+    LNERF_REQUIRE(rays_per_view > 0, "shade_fd_orient_backward: rays_per_view must be > 0");
+    if (N == 0) return LNERF_OK;
+    LNERF_REQUIRE(B > 0, "shade_fd_orient_backward: B must be > 0");
+    LNERF_REQUIRE(sigmas7 && rgbs7 && rays && shade && dsigma_c && dcolours && dsigmas7 && drgbs7,
+                  "shade_fd_orient_backward: null pointer");
+    LNERF_REQUIRE(C != 4 || (((uintptr_t)rgbs7 | (uintptr_t)dcolours | (uintptr_t)drgbs7) & 15) == 0,
+                  "shade_fd_orient_backward: (C = 4) rgbs7 / dcolours / drgbs7 must be 16-byte aligned");
+    LNERF_REQUIRE_ORIENT("shade_fd_orient_backward");
+    const dim3 grid((unsigned)div_up(N, 4)), block(256);
+#define LNERF_SHADE_BWD(CC)                                                                                            \
+    hipLaunchKernelGGL(k_shade_orient_bwd<CC>, grid, block, 0, as_stream(stream), sigmas7, rgbs7, rays, N, rays_per_view, \
+                       shade, B, inv_2eps, dsigma_c, dcolours, deltas, rays_d, density_scale, T_thresh, d_orient, dsigmas7, \
+                       drgbs7)
+    switch (C) {
+        case 1: LNERF_SHADE_BWD(1); break;
+        case 2: LNERF_SHADE_BWD(2); break;
+        case 3: LNERF_SHADE_BWD(3); break;
+        default: LNERF_SHADE_BWD(4); break;
+    }
+#undef LNERF_SHADE_BWD
+    LNERF_CHECK_LAUNCH("shade_fd_orient_backward");
+    return LNERF_OK;
+}
+#undef LNERF_REQUIRE_ORIENT
 
 }  // extern "C"

@@ -81,6 +81,11 @@ class OptimConfig:
     # 20 % plain albedo, under a random light near the camera (ambient 0.1) -- the defence against flat, "painted-on"
     # geometry.  A shaded step evaluates the field at 7 points per sample.  None: every step renders the plain albedo
     start_shading_iter: Optional[int] = None
+    # weight of the orientation regulariser on SHADED steps (needs start_shading_iter; the plain albedo steps of a shaded
+    # schedule do not have the term, as upstream): mean over the rays of sum_i w_i max(0, n_i . v)^2, the compositing
+    # weight times the squared share of the finite-difference normal that faces away from the camera -- against
+    # inside-out shells and foggy fronts.  Fused into the shade kernels.  The upstream trainers use about 1e-2.  0: off
+    lambda_orient: float = 0.0
 
 MESH_ATLASES = ("triangle", "charts")   # log.mesh_atlas (src/uv_atlas.py ATLAS_CHOICES)
 
@@ -153,6 +158,11 @@ class TrainConfig:
         if self._auto_layout:
             self.render.gridtype = "blocked" if self.render.table_dtype == "bf16" else "hash"
         self.render.layout()  # validates
+        if not self.optim.lambda_orient >= 0:
+            raise ValueError("optim.lambda_orient must be >= 0, not %r" % (self.optim.lambda_orient,))
+        if self.optim.lambda_orient > 0 and self.optim.start_shading_iter is None:
+            raise ValueError("optim.lambda_orient = %r needs optim.start_shading_iter: the orientation term exists only on "
+                             "shaded steps (it reads their finite-difference normal)" % (self.optim.lambda_orient,))
         if self.log.mesh_atlas not in MESH_ATLASES:
             raise ValueError("log.mesh_atlas must be one of %s, not %r" % (" | ".join(MESH_ATLASES), self.log.mesh_atlas))
         for n in ("mesh_min_component_faces", "mesh_min_component_diameter", "mesh_keep_largest", "mesh_smooth_iterations"):

@@ -39,11 +39,12 @@ def _sample_pdf(bins, weights, n_samples, stratified):
 
 class PreparedRays:
     """Output of NeRFRenderer.prepare_rays(): the marched samples of one view (a MarchResult in one of the renderer's
-    two sample-buffer sets), its background colours and the ray-batch shape."""
-    __slots__ = ("march", "bg", "prefix", "N", "cap")
+    two sample-buffer sets), its background colours, the ray-batch shape and the ray directions [N,3] the march read (in
+    the camera form: the buffer it generated them into), which the orientation term of a shaded render reads."""
+    __slots__ = ("march", "bg", "prefix", "N", "cap", "rays_d")
 
-    def __init__(self, march, bg, prefix, N, cap):
-        self.march, self.bg, self.prefix, self.N, self.cap = march, bg, prefix, N, cap
+    def __init__(self, march, bg, prefix, N, cap, rays_d=None):
+        self.march, self.bg, self.prefix, self.N, self.cap, self.rays_d = march, bg, prefix, N, cap, rays_d
 
 
 class _ShadowExtraState:
@@ -131,8 +132,13 @@ class NeRFRenderer(nn.Module):
 
     SHADED = ("lambertian", "textureless")
 
-    def _check_shading(self, shading, light_d=None, sampler="run_cuda"):
-        """Validates `shading` before any tensor is touched.  -> (normal render?, shaded render?)."""
+    def _check_shading(self, shading, light_d=None, sampler="run_cuda", orient=False):
+        """Validates `shading` (and `orient`) before any tensor is touched.  -> (normal render?, shaded render?)."""
+        if orient and (shading not in self.SHADED or not self.training or sampler != "run_cuda"):
+            # the term reads the finite-difference normal of a shaded TRAINING render and the march's spans
+            raise ValueError("orient=True needs shading='lambertian' / 'textureless' in training mode on the "
+                             "occupancy-marched renderer (got shading=%r, %s mode, %s)"
+                             % (shading, "training" if self.training else "evaluation", sampler))
         if shading in self.SHADED:
             if light_d is None:
                 # there is no random light inside the renderer: a render is a function of its arguments
@@ -295,11 +301,11 @@ class NeRFRenderer(nn.Module):
         self._march_slots[slot] = march
         self._march = march
         self._march_key = (N, int(max_steps))
-        return PreparedRays(march, bg, prefix, N, cap)
+        return PreparedRays(march, bg, prefix, N, cap, rays_d)
 
     def run_cuda(self, rays_o, rays_d, dt_gamma=0.0, bg_color=None, perturb=False, force_all_rays=False,
                  max_steps=1024, T_thresh=1e-4, prepared=None, shading="albedo", light_d=None, ambient_ratio=0.1,
-                 normal_eps=1e-2, **kwargs):
+                 normal_eps=1e-2, orient=False, **kwargs):
         """rays_o, rays_d [B,N,3] -> dict(image [B,N,C], depth [B,N], weights_sum [B,N]).
         Training mode: march -> hash gather -> MLP -> composite, all on device, no host sync (latent_tune: the fused
         composite + decode, image in RGB);
@@ -313,8 +319,12 @@ class NeRFRenderer(nn.Module):
         density at distance normal_eps (the upstream renderer's training normal: six more field queries per sample, whose
         gradient is the field's ordinary backward at 7 M points).  light_d: [3] or [B,3], the direction toward the light
         of each of the B views (normalised here) -- or a ready device record [B,5] = (unit l, ambient, textureless 0 / 1)
-        (raymarching.shade_record), taken as it is: the kind and the ambient share are then the record's."""
-        shade_normal, shaded = self._check_shading(shading, light_d)
+        (raymarching.shade_record), taken as it is: the kind and the ambient share are then the record's.
+        orient=True (shaded training renders only): additionally 'loss_orient' [B,N], per ray sum_i w_i max(0, n_i . v)^2
+        with the compositing weights w (detached) and the unit ray direction v -- the orientation regulariser, computed and
+        differentiated inside the shade kernels (raymarching.shade_fd(orient=...)); image, depth and weights_sum keep
+        their bits."""
+        shade_normal, shaded = self._check_shading(shading, light_d, orient=orient)
         C = 3 if shade_normal else self.img_dims
         decode = self.tuned and not shade_normal   # composite 4 latent channels, decode per ray (bg_color is RGB)
         results = {}
@@ -340,7 +350,15 @@ class NeRFRenderer(nn.Module):
                 shade = rm.shade_record(light_d, ambient_ratio, shading == "textureless", n_views, march.xyzs.device)
                 pts7, m7_dev = rm.fd_points(march.xyzs, self.bound, normal_eps, cap, m_dev)
                 sigmas7, rgbs7 = self.field(pts7, 7 * cap, m7_dev, 7 * cap)
-                sigmas, rgbs = rm.shade_fd(sigmas7, rgbs7, march.rays, shade, max(N // n_views, 1), normal_eps)
+                if orient:
+                    if prepared.rays_d is None:
+                        raise ValueError("orient=True needs a PreparedRays of prepare_rays() (it carries the ray directions)")
+                    sigmas, rgbs, loss_orient = rm.shade_fd(
+                        sigmas7, rgbs7, march.rays, shade, max(N // n_views, 1), normal_eps,
+                        orient=(march.deltas, prepared.rays_d, self.density_scale, T_thresh, N))
+                    results["loss_orient"] = loss_orient.view(*prefix)
+                else:
+                    sigmas, rgbs = rm.shade_fd(sigmas7, rgbs7, march.rays, shade, max(N // n_views, 1), normal_eps)
             else:
                 sigmas, rgbs = self.field(march.xyzs, cap, m_dev, cap)
             sigmas = self.density_scale * sigmas if self.density_scale != 1.0 else sigmas
@@ -424,7 +442,8 @@ class NeRFRenderer(nn.Module):
         kernels and composited with the same HIP kernels (every ray owns a fixed span of samples).
         shading="normal" (evaluation only): as in run_cuda; the shaded renders ('lambertian' / 'textureless') are
         run_cuda's alone."""
-        shade_normal, _ = self._check_shading(shading, kwargs.get("light_d"), sampler="run")
+        shade_normal, _ = self._check_shading(shading, kwargs.get("light_d"), sampler="run",
+                                              orient=kwargs.get("orient", False))
         prefix = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3).float()
         rays_d = rays_d.contiguous().view(-1, 3).float()

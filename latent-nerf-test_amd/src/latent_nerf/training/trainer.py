@@ -110,6 +110,11 @@ class Trainer:
             self.grad_sync.attach_sink(self.nerf.encoder, pipeline_groups=max(1, cfg.optim.exchange_groups))
         self.dataloaders = self.init_dataloaders()
         self.shape_loss = self.init_shape_guidance()
+        # optim.lambda_orient: the term's gradient w.r.t. the per-ray loss_orient of a shaded render is a CONSTANT,
+        # lambda / (rays of the render) -- allocated here, before any capture, one tensor per render shape
+        self._orient_const = {}
+        if self._lambda_orient() > 0:
+            self._orient_grad((n_views, cfg.render.train_h * cfg.render.train_w))
         self.past_checkpoints = []
         if cfg.optim.ckpt is not None:
             self.load_checkpoint(cfg.optim.ckpt, model_only=True)
@@ -185,11 +190,28 @@ class Trainer:
             return step(self.text_z[int(dirs[0])], pred)
         return torch.cat([step(self.text_z[int(d)], pred[i:i + 1]) for i, d in enumerate(dirs)])
 
+    def _lambda_orient(self):
+        return float(getattr(self.cfg.optim, "lambda_orient", 0.0))
+
+    def _orient_grad(self, shape):
+        """d(lambda_orient * mean(loss_orient)) / d(loss_orient): lambda / (number of rays of the render) on every ray, the
+        normalisation of the sparsity term (sparsity_loss_grad).  One cached tensor per shape, read-only."""
+        key = tuple(int(v) for v in shape)
+        g = self._orient_const.get(key)
+        if g is None:
+            g = torch.full(key, self._lambda_orient() / max(math.prod(key), 1), device=self.device, dtype=torch.float32)
+            self._orient_const[key] = g
+        return g
+
     def _backward(self, out, pred, grad, grad_ws=None):
         """SDS: d(loss)/d(pred) = grad (src/latent_paint_mesh/training/trainer.py:657-658).  The sparsity term's gradient
         w.r.t. weights_sum comes from one HIP launch (`grad_ws` when the caller already has it) and enters the
-        compositing backward beside it; the shape term (a function of the samples) goes through autograd."""
+        compositing backward beside it; the orientation term of a shaded step enters the shade backward as a constant
+        per-ray gradient; the shape term (a function of the samples) goes through autograd."""
         tensors, grads = [pred], [grad]
+        if "loss_orient" in out:
+            tensors.append(out["loss_orient"])
+            grads.append(self._orient_grad(out["loss_orient"].shape))
         if self.cfg.optim.lambda_sparsity > 0:
             tensors.append(out["weights_sum"])
             grads.append(grad_ws if grad_ws is not None
@@ -205,6 +227,8 @@ class Trainer:
         loss = torch.zeros((), device=self.device)
         if self.cfg.optim.lambda_sparsity > 0:
             loss = loss + self.cfg.optim.lambda_sparsity * sparsity_loss(out["weights_sum"].detach())
+        if "loss_orient" in out:
+            loss = loss + self._lambda_orient() * out["loss_orient"].detach().mean()
         return loss
 
     def train_render(self, data):
@@ -244,7 +268,10 @@ class Trainer:
         the static buffers, so the kind inside the shaded form is DATA -- one captured graph serves both kinds."""
         if not self._shaded:
             return {}
-        return {"shading": "lambertian", "light_d": self._static_buffers()["shade"]}
+        args = {"shading": "lambertian", "light_d": self._static_buffers()["shade"]}
+        if self._lambda_orient() > 0:
+            args["orient"] = True       # (loss_orient in the render's dict: _backward picks it up)
+        return args
 
     # ---- one step on this rank's views: camera upload -> batched render -> guidance -> backward -> exchange -> optimiser
     def _graph_ready(self):

@@ -268,6 +268,41 @@ int lnerf_grid_encode_backward_input(const float *xyzs, float bound, const void 
                                      const int32_t *res_host, int64_t m_host, const int32_t *m_dev, int64_t level_stride,
                                      const float *dfeat, float *dxyz, int variant, lnerf_stream_t stream);
 
+/* ---- `gridencoder.grad_total_variation` (the upstream trainers' `lambda_tv`): total-variation regulariser of the hash
+ * table itself.  Definition (ours; float64 restatement in tests/tv_reference.py): level l has the vertex lattice
+ * [0, res_l]^3; for every SAMPLED vertex p and channel c
+ *   dtable[offsets[l] + row_l(p), c] += w_l * sum over q in N(p) of (e_c(p) - e_c(q)),   e(p) = table[offsets[l] + row_l(p)],
+ * N(p) = the up to six axis neighbours of p inside the lattice, row_l the level's index function (dense / hash / blocked /
+ * tiled).  Only p's own row is written.  With every vertex of the level sampled and w_l = lambda / N_l this is the exact
+ * gradient (hash collisions included) of lambda / (2 N_l) * sum over lattice edges |e(p) - e(q)|^2; with n_l vertices sampled
+ * and w_l = lambda / n_l its unbiased estimate.
+ * The unit of sampling is a LINE: all res_l + 1 vertices that share one (y, z), consecutive lanes = consecutive x.
+ *
+ * lnerf_grid_tv_plan (HOST ONLY, no device work): line_offsets_host[L + 1], level l takes
+ *   n_l = min((res_l + 1)^2, max(1, tv_vertices / (res_l + 1))) lines; tv_vertices in [1, 2^30].
+ * lnerf_grid_tv_lines: lines int32 [line_offsets_host[L], 2] = (y, z) of every line.  A level whose plan takes all
+ *   (res_l + 1)^2 lines is swept in plane order (line j = plane index j); otherwise line j is drawn from stratum j of the
+ *   S = (res_l + 1)^2 plane indices: lo_j = floor(j S / n_l), idx = lo_j + h mod (lo_{j+1} - lo_j) (64-bit integers),
+ *   y = idx mod (res_l + 1), z = idx / (res_l + 1), h = the counter-based hash of lnerf_synthetic_guidance / lnerf_occ_sample
+ *   keyed by (j, seed, step, l) -- the lines of a level are distinct by construction.  `step_dev` (optional, device int32):
+ *   when given, *step_dev replaces `step` (the optimiser's device counter: a replayed hipGraph draws fresh lines).
+ * lnerf_grid_tv_grad: `table` is the f32 MASTER table [rows, 2]; `layout_flags` is 0, LNERF_GRID_BLOCKED or LNERF_GRID_TILED;
+ *   `lines` as written by lnerf_grid_tv_lines, or NULL: the kernel then draws the very same lines itself from
+ *   (seed, step, step_dev) -- one launch.  Given lines outside the lattice are ignored.  weights_host[L]: w_l, finite; a
+ *   weight of exactly 0 skips the level.  dtable (f32 [rows, 2]) is ACCUMULATED into; rows of unsampled vertices keep
+ *   their bits.
+ *   Reproducibility: on a DENSE level the sampled rows are distinct (distinct lines, bijective index; lines passed in must
+ *   be distinct there) and are updated by a plain read-modify-write: bitwise reproducible.  On a HASHED level every
+ *   contribution is one float atomic add per channel: a row that collects more than one contribution is summed in arrival
+ *   order, its last bits may differ from run to run. */
+int lnerf_grid_tv_plan(int num_levels, const int32_t *res_host, int64_t tv_vertices, int32_t *line_offsets_host);
+int lnerf_grid_tv_lines(int num_levels, const int32_t *res_host, const int32_t *line_offsets_host, uint32_t seed,
+                        uint32_t step, const int32_t *step_dev, int32_t *lines, lnerf_stream_t stream);
+int lnerf_grid_tv_grad(const float *table, int num_levels, int level_dim, const int32_t *offsets_host,
+                       const int32_t *res_host, int layout_flags, const int32_t *line_offsets_host, const int32_t *lines,
+                       uint32_t seed, uint32_t step, const int32_t *step_dev, const float *weights_host, float *dtable,
+                       lnerf_stream_t stream);
+
 /* ---- H7 helper: inverse of the bf16 weight-fragment layout at the head of the MLP workspace: map_wK[2 i], map_wK[2 i + 1] = the two
  * bf16 elements of that image which hold weight i of wK (forward / transposed fragments).  map_w1 int32[64*32*2],
  * map_w2 int32[64*64*2], map_w3 int32[out_dim*64*2].  For lnerf_adam_step_multi_shadow. */

@@ -86,6 +86,14 @@ class OptimConfig:
     # weight times the squared share of the finite-difference normal that faces away from the camera -- against
     # inside-out shells and foggy fronts.  Fused into the shade kernels.  The upstream trainers use about 1e-2.  0: off
     lambda_orient: float = 0.0
+    # weight of the total-variation regulariser of the hash table (the upstream trainers' lambda_tv): per level, 1 / (2 N)
+    # times the sum over the lattice edges of the squared feature difference, estimated per step on whole x-lines of
+    # the vertex lattice (GridEncoder.grad_total_variation) -- the training-time answer to noisy coarse geometry and
+    # floaters.  Single process only; > 0 takes the table's Adam step out of the scatter (the term needs the dense f32
+    # gradient), as optim.fuse_table_update = false does.  0: off, nothing changes
+    lambda_tv: float = 0.0
+    # lattice vertices the term samples per level and step (levels with fewer vertices are swept whole)
+    tv_vertices: int = 65536
 
 MESH_ATLASES = ("triangle", "charts")   # log.mesh_atlas (src/uv_atlas.py ATLAS_CHOICES)
 
@@ -163,6 +171,10 @@ class TrainConfig:
         if self.optim.lambda_orient > 0 and self.optim.start_shading_iter is None:
             raise ValueError("optim.lambda_orient = %r needs optim.start_shading_iter: the orientation term exists only on "
                              "shaded steps (it reads their finite-difference normal)" % (self.optim.lambda_orient,))
+        if not self.optim.lambda_tv >= 0:
+            raise ValueError("optim.lambda_tv must be >= 0, not %r" % (self.optim.lambda_tv,))
+        if not self.optim.tv_vertices >= 1:
+            raise ValueError("optim.tv_vertices must be >= 1, not %r" % (self.optim.tv_vertices,))
         if self.log.mesh_atlas not in MESH_ATLASES:
             raise ValueError("log.mesh_atlas must be one of %s, not %r" % (" | ".join(MESH_ATLASES), self.log.mesh_atlas))
         for n in ("mesh_min_component_faces", "mesh_min_component_diameter", "mesh_keep_largest", "mesh_smooth_iterations"):

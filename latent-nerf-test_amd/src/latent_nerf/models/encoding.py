@@ -177,6 +177,51 @@ def grid_encode_backward(xyzs, bound, dfeat, levels: GridLevels, m_host, m_dev, 
     return dtable
 
 
+def grid_tv_plan(levels: GridLevels, tv_vertices=65536):
+    """Line plan of the total-variation term (lnerf_grid_tv_plan, host only): [L + 1] line offsets, level l takes
+    min((res_l + 1)^2, max(1, tv_vertices // (res_l + 1))) whole x-lines of its vertex lattice per step."""
+    out = (ctypes.c_int32 * (levels.num_levels + 1))()
+    _b.call("lnerf_grid_tv_plan", levels.num_levels, levels.c_res, int(tv_vertices), out)
+    return list(out)
+
+
+def grid_tv_lines(levels: GridLevels, plan, seed=0, step=0, step_dev=None, device=None, out=None):
+    """The (y, z) of every line of `plan` (grid_tv_plan) at (seed, step) -- `step_dev` (device int32) replaces `step`
+    when given -- as int32 [plan[-1], 2] (lnerf_grid_tv_lines)."""
+    if out is None:
+        if device is None:
+            raise ValueError("grid_tv_lines: give `device` or `out`")
+        if torch.device(device).type != "cuda":
+            raise ValueError("grid_tv_lines: lines must live on the GPU (got %s); there is no CPU path" % (device,))
+        out = torch.empty(plan[-1], 2, device=device, dtype=torch.int32)
+    if tuple(out.shape) != (plan[-1], 2):
+        raise ValueError("grid_tv_lines: lines must be [%d, 2]" % plan[-1])
+    c_plan = (ctypes.c_int32 * len(plan))(*plan)
+    _b.call("lnerf_grid_tv_lines", levels.num_levels, levels.c_res, c_plan, int(seed) & 0xFFFFFFFF,
+            int(step) & 0xFFFFFFFF, _chk(step_dev, "step_dev", torch.int32, allow_none=True),
+            _chk(out, "lines", torch.int32), _stream())
+    return out
+
+
+def grid_tv_grad(table, levels: GridLevels, plan, weights, dtable, lines=None, seed=0, step=0, step_dev=None):
+    """dtable (f32 [rows, 2]) += the total-variation term of `table` (the f32 master) on the lines of `plan`
+    (lnerf_grid_tv_grad; see include/lnerf_hip.h): weights[l] per sampled vertex of level l, 0 skips the level; `lines`
+    int32 [plan[-1], 2] or None = drawn inside the launch from (seed, step | *step_dev)."""
+    if len(weights) != levels.num_levels or len(plan) != levels.num_levels + 1:
+        raise ValueError("grid_tv_grad: need one weight per level and L + 1 line offsets")
+    if tuple(table.shape) != (levels.n_rows, 2) or tuple(dtable.shape) != (levels.n_rows, 2):
+        raise ValueError("grid_tv_grad: table and dtable must be [%d, 2]" % levels.n_rows)
+    if lines is not None and tuple(lines.shape) != (plan[-1], 2):
+        raise ValueError("grid_tv_grad: lines must be [%d, 2]" % plan[-1])
+    c_plan = (ctypes.c_int32 * len(plan))(*plan)
+    c_w = (ctypes.c_float * levels.num_levels)(*[float(w) for w in weights])
+    _b.call("lnerf_grid_tv_grad", _chk(table, "table"), levels.num_levels, levels.level_dim, levels.c_offsets, levels.c_res,
+            levels.flag, c_plan, _chk(lines, "lines", torch.int32, allow_none=True), int(seed) & 0xFFFFFFFF,
+            int(step) & 0xFFFFFFFF, _chk(step_dev, "step_dev", torch.int32, allow_none=True), c_w, _chk(dtable, "dtable"),
+            _stream())
+    return dtable
+
+
 class FusedTableUpdate:
     """Set on a GridEncoder (`encoder.fused_update`) by FusedAdam(fuse_table_update=True).  When ARMED
     (FusedAdam.arm(), once per step, right before the step's single backward) the scatter of that backward applies
@@ -438,6 +483,7 @@ class GridEncoder(nn.Module):
         self._shadow_version = -1
         self.fused_update = None  # FusedTableUpdate, installed by FusedAdam(fuse_table_update=True)
         self.grad_sink = None     # GradSink, installed by GradSync.attach_sink() (data parallel, bf16 on the wire)
+        self._tv_plans = {}       # tv_vertices -> (line offsets, sampled vertices per level) of grad_total_variation
 
     def reset_parameters(self):
         self.embeddings.data.uniform_(-1e-4, 1e-4)
@@ -458,6 +504,30 @@ class GridEncoder(nn.Module):
     def mark_shadow_fresh(self):
         """Called by the fused optimiser step, which rewrites the shadow in the same pass."""
         self._shadow_version = self.embeddings._version
+
+    def grad_total_variation(self, weight, tv_vertices=65536, seed=0, step=None, step_dev=None, grad=None, lines=None):
+        """Adds the gradient of the table's total-variation regulariser (the upstream encoder's `grad_total_variation`,
+        the trainers' `lambda_tv`) into `grad` (default: `embeddings.grad`, which must exist): per level, `weight` / n_l
+        times the sum of the differences to the axis neighbours on n_l sampled lattice vertices -- whole x-lines, drawn
+        from (seed, step), or from (seed, *step_dev) when the optimiser's device counter is given; coarse levels are swept
+        whole.  One launch (lnerf_grid_tv_grad); reads the f32 master, leaves table and shadow alone.  `lines`: explicit
+        int32 [grid_tv_plan(...)[-1], 2] lines instead of drawn ones."""
+        if grad is None:
+            grad = self.embeddings.grad
+            if grad is None:
+                raise RuntimeError("grad_total_variation: embeddings.grad does not exist (call it after backward(), or "
+                                   "pass `grad`)")
+        key = int(tv_vertices)
+        plan = self._tv_plans.get(key)
+        if plan is None:
+            plan = grid_tv_plan(self.levels, key)
+            res = self.levels.resolutions
+            self._tv_plans[key] = plan = (plan, [(plan[l + 1] - plan[l]) * (res[l] + 1) for l in range(len(res))])
+        plan, n_vertices = plan
+        weights = [float(weight) / n for n in n_vertices]
+        if step is None:
+            step = 0
+        return grid_tv_grad(self.embeddings.data, self.levels, plan, weights, grad, lines, seed, step, step_dev)
 
     def encode(self, xyzs, bound, m_host, m_dev=None, level_stride=None, feat_dtype=torch.float32):
         """Level-major features [L, level_stride, 2] (differentiable w.r.t. embeddings, and w.r.t. xyzs when it

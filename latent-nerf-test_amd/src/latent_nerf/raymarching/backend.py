@@ -83,6 +83,9 @@ _SIGNATURES = {
     "lnerf_grid_encode_backward_adam": [_P, _F, _P, _I, _I, _I, _P, _P, _P, _L, _P, _L, _P, _I, _P, _Z, _P, _P, _P, _P, _F,
                                         _F, _F, _F, _I, _P, _F, _P],
     "lnerf_grid_encode_backward_input": [_P, _F, _P, _I, _I, _I, _P, _P, _P, _L, _P, _L, _P, _P, _I, _P],
+    "lnerf_grid_tv_plan": [_I, _P, _L, _P],
+    "lnerf_grid_tv_lines": [_I, _P, _P, _U, _U, _P, _P, _P],
+    "lnerf_grid_tv_grad": [_P, _I, _I, _P, _P, _I, _P, _P, _U, _U, _P, _P, _P, _P],
     "lnerf_density_normals": [_P, _P, _P, _F, _F, _L, _P, _P, _P, _P],
     "lnerf_mlp_forward": [_P, _I, _L, _P, _P, _P, _P, _P, _P, _P, _I, _F, _F, _L, _P, _P, _P, _I, _P, _Z, _P],
     "lnerf_mlp_backward_workspace_bytes": [_I],

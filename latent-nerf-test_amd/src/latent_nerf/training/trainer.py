@@ -40,6 +40,10 @@ class Trainer:
         self.cfg = cfg
         self.train_step = 0
         self.rank, self.world = D.world_info()
+        self.lambda_tv = float(getattr(cfg.optim, "lambda_tv", 0.0))
+        if self.lambda_tv > 0 and D.exchange_active():
+            raise ValueError("optim.lambda_tv > 0 is single-process only: the float atomics of the term on the hashed "
+                             "levels would let the replicas of a data-parallel run drift apart bit by bit")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
         seed_everything(cfg.optim.seed)   # model initialisation: the same stream on every rank
         self.exp_path = make_path(cfg.log.exp_dir)
@@ -69,6 +73,13 @@ class Trainer:
         n_views = len(self.views)
         self.exchange = D.exchange_active()     # more than one rank, or LNERF_FORCE_DIST on one
         fuse = bool(cfg.optim.fuse_table_update) and not self.exchange
+        # optim.lambda_tv: the total-variation term of the table is added to its dense f32 gradient right before the
+        # optimiser step, so the table's Adam step cannot run inside the scatter
+        if self.lambda_tv > 0:
+            if fuse:
+                self.log("optim.lambda_tv = %g: the table's Adam step runs outside the scatter (plain route, dense f32 "
+                         "gradient), as with optim.fuse_table_update = false" % self.lambda_tv)
+            fuse = False
         # capturable: the step counter lives on the device, so that the captured step (optim.graph_step) and the eager
         # step run the very same kernels with the very same bias corrections
         self.optimizer = FusedAdam(self.nerf.get_params(cfg.optim.lr), betas=(0.9, 0.99), eps=1e-15,
@@ -254,6 +265,12 @@ class Trainer:
             ex.finish_gathers()     # (sharded optimiser: the new shadow rows of every owner; no-op otherwise)
         else:
             self.grad_sync.allreduce()
+            if self.lambda_tv > 0:
+                # the optimiser multiplies the whole gradient by `scale`: the term's weight is lambda_tv for any number
+                # of views.  Lines: (seed, the optimiser's device step counter) -- fresh ones on every replay
+                o = self.cfg.optim
+                self.nerf.encoder.grad_total_variation(self.lambda_tv / scale, o.tv_vertices, seed=o.seed,
+                                                       step=self.optimizer.step_no + 1, step_dev=self.optimizer.step_dev)
             self.optimizer.step(grad_scale=scale)
 
     # ---- shading schedule (optim.start_shading_iter)

@@ -466,7 +466,11 @@ int lnerf_bg_backward(const float *dirs, int64_t N, const float *w1, const float
 
 /* ---- sketch-shape guidance (the reference names igl's winding number, README.md:119-122).
  * triangles [F, 3, 3] f32 (vertex positions), points [n,3].  Brute force with LDS-tiled triangles; meant for a
- * one-off evaluation on a dense grid. */
+ * one-off evaluation on a dense grid.
+ * Zero-area triangles (marching-cubes output has them where a lattice value equals the iso level):
+ * lnerf_mesh_distance counts one as its segments, a == b == c as the point a; lnerf_mesh_winding_number gives it the
+ * solid angle 0 at every point off that segment (its triple product vanishes).  lnerf_mesh_winding_number accepts n_faces == 0 (out = 0);
+ * lnerf_mesh_distance needs n_faces >= 1.  n == 0 writes nothing; out [n] is written and nothing behind it. */
 int lnerf_mesh_winding_number(const float *points, int64_t n, const float *triangles, int n_faces, float *out,
                               lnerf_stream_t stream);
 int lnerf_mesh_distance(const float *points, int64_t n, const float *triangles, int n_faces, float *out,

@@ -25,7 +25,11 @@ __device__ __forceinline__ float solid_angle(P3 a, P3 b, P3 c) {
     return 2.0f * atan2f(det, den);
 }
 
-// closest-point distance^2 from p to triangle (a, b, c)  (Ericson, Real-Time Collision Detection 5.1.5)
+// closest-point distance^2 from p to triangle (a, b, c)  (Ericson, Real-Time Collision Detection 5.1.5).
+// A zero-area triangle counts as its segments (a zero-length one as a point): an edge region is entered only when its
+// quotient has a positive denominator (the edge has a length), so a == b falls through to the regions of c and of edge
+// AC instead of dividing 0 by 0, whose NaN fminf would drop.  A triangle with an area never has a zero denominator in
+// the region it reaches, and its result is bit for bit what it was without the guards.
 __device__ __forceinline__ float tri_dist2(P3 p, P3 a, P3 b, P3 c) {
     const P3 ab = sub3(b, a), ac = sub3(c, a), ap = sub3(p, a);
     const float d1 = dot3(ab, ap), d2 = dot3(ac, ap);
@@ -34,7 +38,7 @@ __device__ __forceinline__ float tri_dist2(P3 p, P3 a, P3 b, P3 c) {
     const float d3 = dot3(ab, bp), d4 = dot3(ac, bp);
     if (d3 >= 0.f && d4 <= d3) return dot3(bp, bp);
     const float vc = d1 * d4 - d3 * d2;
-    if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) {
+    if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f && (d1 - d3) > 0.f) {
         const float v = d1 / (d1 - d3);
         const P3 q = {ap.x - v * ab.x, ap.y - v * ab.y, ap.z - v * ab.z};
         return dot3(q, q);
@@ -43,18 +47,20 @@ __device__ __forceinline__ float tri_dist2(P3 p, P3 a, P3 b, P3 c) {
     const float d5 = dot3(ab, cp), d6 = dot3(ac, cp);
     if (d6 >= 0.f && d5 <= d6) return dot3(cp, cp);
     const float vb = d5 * d2 - d1 * d6;
-    if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) {
+    if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f && (d2 - d6) > 0.f) {
         const float w = d2 / (d2 - d6);
         const P3 q = {ap.x - w * ac.x, ap.y - w * ac.y, ap.z - w * ac.z};
         return dot3(q, q);
     }
     const float va = d3 * d6 - d5 * d4;
-    if (va <= 0.f && (d4 - d3) >= 0.f && (d5 - d6) >= 0.f) {
+    if (va <= 0.f && (d4 - d3) >= 0.f && (d5 - d6) >= 0.f && ((d4 - d3) + (d5 - d6)) > 0.f) {
         const float w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
         const P3 q = {bp.x - w * (c.x - b.x), bp.y - w * (c.y - b.y), bp.z - w * (c.z - b.z)};
         return dot3(q, q);
     }
-    const float denom = 1.0f / (va + vb + vc);
+    const float area2 = va + vb + vc;
+    if (!(area2 > 0.f)) return fminf(dot3(ap, ap), fminf(dot3(bp, bp), dot3(cp, cp)));  // no interior: nearest vertex
+    const float denom = 1.0f / area2;
     const float v = vb * denom, w = vc * denom;
     const P3 q = {ap.x - ab.x * v - ac.x * w, ap.y - ab.y * v - ac.y * w, ap.z - ab.z * v - ac.z * w};
     return dot3(q, q);

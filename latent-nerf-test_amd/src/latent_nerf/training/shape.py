@@ -160,5 +160,6 @@ class ShapeLoss:
         ce = -(nerf_occ * torch.log(inside.clamp(0.01, 0.99)) + (1.0 - nerf_occ) * torch.log((1.0 - inside).clamp(0.01, 0.99)))
         if self.proximal_surface > 0:
             d = self.occ.distance_at(x)
-            ce = ce * (1.0 - torch.exp(-(d * d) / (2.0 * self.proximal_surface ** 2)))
+            # -expm1, not 1 - exp: near the surface the weight is ~d^2 and 1 - exp leaves it an absolute error of 2^-24
+            ce = ce * -torch.expm1(-(d * d) / (2.0 * self.proximal_surface ** 2))
         return torch.where(valid, ce, torch.zeros_like(ce)).sum()

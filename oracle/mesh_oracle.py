@@ -27,19 +27,21 @@ def _closest_on_segment(p, a, b):
 
 def distance(points: np.ndarray, tris: np.ndarray) -> np.ndarray:
     """Unsigned distance of points [n,3] to the triangle soup [F,3,3] (projection onto the plane if the foot
-    is inside the triangle, else the nearest of the three edges)."""
+    is inside the triangle, else the nearest of the three edges).  A triangle of zero area (its float64 normal is
+    exactly 0) has no plane: it counts as its three segments, a zero-length segment as a point."""
     p = points.astype(np.float64)[:, None, :]
     a, b, c = (tris[None, :, k, :].astype(np.float64) for k in range(3))
     nrm = np.cross(b - a, c - a)
-    nn = np.maximum(np.linalg.norm(nrm, axis=-1, keepdims=True), 1e-30)
-    nrm = nrm / nn
+    nn = np.linalg.norm(nrm, axis=-1, keepdims=True)
+    flat = nn[..., 0] == 0.0
+    nrm = nrm / np.maximum(nn, 1e-30)
     dist_plane = np.einsum("nfi,nfi->nf", p - a, nrm)
     foot = p - dist_plane[..., None] * nrm
 
     def same_side(u, v, w):  # foot on the inner side of edge u->v (w is the opposite vertex)
         return np.einsum("nfi,nfi->nf", np.cross(v - u, foot - u), np.cross(v - u, w - u)) >= 0
 
-    inside = same_side(a, b, c) & same_side(b, c, a) & same_side(c, a, b)
+    inside = same_side(a, b, c) & same_side(b, c, a) & same_side(c, a, b) & ~flat
     d_edges = np.minimum.reduce([np.linalg.norm(p - _closest_on_segment(p, u, v), axis=-1)
                                  for u, v in ((a, b), (b, c), (c, a))])
     d = np.where(inside, np.abs(dist_plane), d_edges)

@@ -26,13 +26,7 @@ __device__ __forceinline__ Chunk<C> load_chunk(const float *__restrict__ sigmas,
         const float2 d = reinterpret_cast<const float2 *>(deltas)[s];
         k.dt = d.x; k.t = d.y;
         k.sigma = sigmas[s];
-        if (C == 4) {
-            const float4 v = reinterpret_cast<const float4 *>(rgbs)[s];
-            k.rgb[0] = v.x; k.rgb[1] = v.y; k.rgb[2] = v.z; k.rgb[C - 1] = v.w;
-        } else {
-#pragma unroll
-            for (int c = 0; c < C; ++c) k.rgb[c] = rgbs[s * C + c];
-        }
+        load_row<C>(rgbs, s, k.rgb);
     }
     return k;
 }
@@ -84,9 +78,7 @@ k_composite_train_fwd(const float *__restrict__ sigmas, const float *__restrict_
     const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (r >= N) return;
     const int lane = lane_id();
-    const int64_t id = rays[r * 3];
-    const int64_t off = rays[r * 3 + 1];
-    const int cnt = rays[r * 3 + 2];
+    const auto [id, off, cnt] = load_span(rays, r);
     float a_ws, a_d, a_c[C];
     composite_ray_fwd<C>(sigmas, rgbs, deltas, off, cnt, T_thresh, lane, a_ws, a_d, a_c);
     a_ws = wave_sum(a_ws);
@@ -130,9 +122,7 @@ k_composite_train_decode_fwd(const float *__restrict__ sigmas, const float *__re
     const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (r >= N) return;
     const int lane = lane_id();
-    const int64_t id = rays[r * 3];
-    const int64_t off = rays[r * 3 + 1];
-    const int cnt = rays[r * 3 + 2];
+    const auto [id, off, cnt] = load_span(rays, r);
     float a_ws, a_d, a_c[4];
     composite_ray_fwd<4>(sigmas, latents, deltas, off, cnt, T_thresh, lane, a_ws, a_d, a_c);
     a_ws = wave_sum(a_ws);
@@ -158,9 +148,11 @@ k_decode_image(const float *__restrict__ latent_image, const float *__restrict__
     decode_pixel(decoder, L, weights_sum[i], bg ? bg + i * 3 : nullptr, image + i * 3);
 }
 
-// d_rgbs[s][c] = di[c] * w (di == nullptr: zeros), one 16-byte store for the four latent channels
+// d_rgbs[s][c] = di[c] * w (di == nullptr: zeros), one 16-byte store for the four latent channels.  (Written out, not
+// through store_row: with the products in a row of their own, k_composite_train_bwd<3> orders its address arithmetic
+// differently, and the compositing kernels' code is held fixed.)
 template <int C>
-__device__ __forceinline__ void store_row(float *__restrict__ d_rgbs, int64_t s, const float *di, float w) {
+__device__ __forceinline__ void store_grad_row(float *__restrict__ d_rgbs, int64_t s, const float *di, float w) {
     if (C == 4) {
         reinterpret_cast<float4 *>(d_rgbs)[s] = di ? make_float4(di[0] * w, di[1] * w, di[2] * w, di[C - 1] * w)
                                                      : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -200,7 +192,7 @@ __device__ __forceinline__ void composite_ray_bwd(const float *__restrict__ sigm
         if (stopped) {  // zero-fill the tail of the span
             if (valid) {
                 d_sigmas[s] = 0.f;
-                store_row<C>(d_rgbs, s, nullptr, 0.f);
+                store_grad_row<C>(d_rgbs, s, nullptr, 0.f);
             }
             continue;
         }
@@ -224,7 +216,7 @@ __device__ __forceinline__ void composite_ray_bwd(const float *__restrict__ sigm
             // dL/dtau_i = g_i T_{i+1} - sum_{k>i} g_k w_k
             const float dtau = keep ? fmaf(g, T * e, -(total - pinc)) : 0.f;
             d_sigmas[s] = dt * dtau;
-            store_row<C>(d_rgbs, s, di, w);
+            store_grad_row<C>(d_rgbs, s, di, w);
         }
         carry_tau += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(inc), 63));
         carry_p = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pinc), 63));
@@ -244,9 +236,7 @@ k_composite_train_bwd(const float *__restrict__ g_ws, const float *__restrict__ 
     const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (r >= N) return;
     const int lane = lane_id();
-    const int64_t id = rays[r * 3];
-    const int64_t off = rays[r * 3 + 1];
-    const int cnt = rays[r * 3 + 2];
+    const auto [id, off, cnt] = load_span(rays, r);
     const float ws = weights_sum[id];
     const float dws = g_ws ? g_ws[id] : 0.f;
     const float ddp = g_depth ? g_depth[id] : 0.f;
@@ -278,9 +268,7 @@ k_composite_train_decode_bwd(const float *__restrict__ g_ws, const float *__rest
     const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (r >= N) return;
     const int lane = lane_id();
-    const int64_t id = rays[r * 3];
-    const int64_t off = rays[r * 3 + 1];
-    const int cnt = rays[r * 3 + 2];
+    const auto [id, off, cnt] = load_span(rays, r);
     const float ws = weights_sum[id];
     float dws = g_ws ? g_ws[id] : 0.f;
     const float ddp = g_depth ? g_depth[id] : 0.f;

@@ -2,10 +2,11 @@
 // Contract: include/lnerf_hip.h, "shaded renders"; numpy restatement: tests/shading_reference.py.
 //
 //   k_fd_points   sample -> itself + its six +-eps neighbours (clamped to the box), rows 7 i .. 7 i + 6, and m7 = 7 m
-//   k_shade_fwd   the seven densities of a sample -> finite-difference normal -> Lambert term -> colour
-//   k_shade_bwd   recomputes the normal and the Lambert term, writes the gradient of all seven rows (one writer each)
-//   k_shade_orient_fwd / _bwd   the same with the orientation term fused in: orient[ray] = sum_i w_i max(0, n_i . v)^2, w
-//                  the compositing weight (scanned here, detached), its gradient added to dn before the projection
+//   k_shade_fwd<C, ORIENT>   the seven densities of a sample -> finite-difference normal -> Lambert term -> colour
+//   k_shade_bwd<C, ORIENT>   recomputes the normal and the Lambert term, writes the gradient of all seven rows (one writer
+//                  each)
+//   ORIENT = true  the same with the orientation term fused in: orient[ray] = sum_i w_i max(0, n_i . v)^2, w the
+//                  compositing weight (scanned here, detached), its gradient added to dn before the projection
 //
 // All arithmetic is f32 + - * / sqrt in the stated order: the library is built with -ffp-contract=off and nothing here
 // is an explicit fmaf, so the numpy restatement matches bit for bit.
@@ -86,13 +87,7 @@ __device__ __forceinline__ Sample7<C> load_sample7(const float *__restrict__ sig
         const int64_t s7 = (off + i) * FD_ROWS;
 #pragma unroll
         for (int j = 0; j < FD_ROWS; ++j) k.sg[j] = sigmas7[s7 + j];
-        if (C == 4) {
-            const float4 v = reinterpret_cast<const float4 *>(rgbs7)[s7];
-            k.alb[0] = v.x; k.alb[1] = v.y; k.alb[2] = v.z; k.alb[C - 1] = v.w;
-        } else {
-#pragma unroll
-            for (int c = 0; c < C; ++c) k.alb[c] = rgbs7[s7 * C + c];
-        }
+        load_row<C>(rgbs7, s7, k.alb);
     }
     return k;
 }
@@ -126,40 +121,99 @@ __device__ __forceinline__ void store_shaded(const Sample7<C> &k, const Lambert 
     float col[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) col[c] = L.textureless ? o.lam : k.alb[c] * o.lam;
-    if (C == 4) {
-        reinterpret_cast<float4 *>(colours)[s] = make_float4(col[0], col[1], col[2], col[C - 1]);
-    } else {
-#pragma unroll
-        for (int c = 0; c < C; ++c) colours[s * C + c] = col[c];
-    }
+    store_row<C>(colours, s, col);
 }
+
+// ---- the orientation term (contract: include/lnerf_hip.h, "orientation regulariser"; numpy: tests/orient_reference.py)
+
+// unit view direction of ray `id`
+__device__ __forceinline__ void view_dir(const float *__restrict__ rays_d, int64_t id, float (&v)[3]) {
+    const float d[3] = {rays_d[id * 3], rays_d[id * 3 + 1], rays_d[id * 3 + 2]};
+    const float s = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
+    const float r = 1.0f / sqrtf(fmaxf(s, 1e-20f));
+#pragma unroll
+    for (int a = 0; a < 3; ++a) v[a] = d[a] * r;
+}
+
+// dt of sample i of the span (0 past its end): the .x of the march's 8-byte (dt, t) pair
+__device__ __forceinline__ float load_dt(const float *__restrict__ deltas, int64_t off, int cnt, int i) {
+    return i < cnt ? reinterpret_cast<const float2 *>(deltas)[off + i].x : 0.f;
+}
+
+// Compositing weight of this lane's sample, as composite_ray_fwd defines it, on `sigma` (scaled already) -- called by
+// ALL 64 lanes (lanes past the span pass zeros).  There is no early stop here: behind T < T_thresh the weights are 0 and
+// the chunks go on, every sample of the span still gets its rows.
+__device__ __forceinline__ float composite_weight(float sigma, float dt, bool valid, float T_thresh, float &carry) {
+    const float tau = sigma * dt;
+    const float inc = wave_inclusive_sum(tau);
+    const float excl = exclusive_depth(inc, carry);
+    const float T = expf(-excl);
+    const float alpha = 1.0f - expf(-tau);
+    carry += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(inc), 63));
+    return (valid && T >= T_thresh) ? alpha * T : 0.f;
+}
+
+// max(0, n . v)
+__device__ __forceinline__ float facing_away(const Lambert &o, const float (&v)[3]) {
+    const float c = (o.n[0] * v[0] + o.n[1] * v[1]) + o.n[2] * v[2];
+    return c > 0.f ? c : 0.f;
+}
+
+// What the orientation term adds to a kernel's arguments, as ONE trailing parameter: the plain instantiations' block is
+// empty and their other arguments lie where they always did.
+template <bool ORIENT>
+struct OrientArgs {};
+template <>
+struct OrientArgs<true> {
+    const float *deltas, *rays_d;
+    float density_scale, T_thresh;
+    float *orient;             // forward: the output, one element per ray id
+    const float *d_orient;     // backward: its upstream gradient
+};
 
 // One wavefront per ray, lanes striding over the ray's samples; the next 64 samples' loads are requested before this
 // chunk's arithmetic (the kernel is a few memory round trips long, nothing else).
-template <int C>
+// ORIENT: plus orient[id] = sum_i w_i q_i^2.  A ray without samples writes 0 (the buffer is uninitialised), so there is no
+// early return, and the chunk's arithmetic runs on ALL 64 lanes: composite_weight is a wave scan.
+template <int C, bool ORIENT>
 __global__ void __launch_bounds__(256)
 k_shade_fwd(const float *__restrict__ sigmas7, const float *__restrict__ rgbs7, const int32_t *__restrict__ rays, int64_t N,
             int rays_per_view, const float *__restrict__ shade, int B, float inv_2eps, float *__restrict__ sigma_c,
-            float *__restrict__ colours) {
+            float *__restrict__ colours, OrientArgs<ORIENT> oa) {
     const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (r >= N) return;
     const int lane = lane_id();
-    const int64_t id = rays[r * 3];
-    const int64_t off = rays[r * 3 + 1];
-    const int cnt = rays[r * 3 + 2];
-    if (cnt <= 0) return;
+    const auto [id, off, cnt] = load_span(rays, r);
+    if (!ORIENT && cnt <= 0) return;
     const Light L = load_light(shade, id, rays_per_view, B);
+    float v[3], acc = 0.f, carry = 0.f, dt = 0.f;
+    if constexpr (ORIENT) view_dir(oa.rays_d, id, v);
     Sample7<C> cur = load_sample7<C>(sigmas7, rgbs7, off, cnt, lane);
-    for (int base = 0; base < cnt; base += 64) {
+    if constexpr (ORIENT) dt = load_dt(oa.deltas, off, cnt, lane);
+    for (int base = 0; base < cnt; base += 64) {      // (wave-uniform)
         Sample7<C> nxt = cur;
-        if (base + 64 < cnt) nxt = load_sample7<C>(sigmas7, rgbs7, off, cnt, base + 64 + lane);
+        float dt_nxt = dt;
+        if (base + 64 < cnt) {
+            nxt = load_sample7<C>(sigmas7, rgbs7, off, cnt, base + 64 + lane);
+            if constexpr (ORIENT) dt_nxt = load_dt(oa.deltas, off, cnt, base + 64 + lane);
+        }
         const int i = base + lane;
-        if (i < cnt) {
-            const int64_t s = off + i;
+        const bool valid = i < cnt;
+        if (ORIENT || valid) {
             const Lambert o = lambert_of(cur.sg, inv_2eps, L);
-            store_shaded<C>(cur, o, L, s, sigma_c, colours);
+            if (valid) store_shaded<C>(cur, o, L, off + i, sigma_c, colours);
+            if constexpr (ORIENT) {
+                const float w = composite_weight(oa.density_scale * cur.sg[0], dt, valid, oa.T_thresh, carry);
+                const float q = facing_away(o, v);
+                acc += w * (q * q);
+            }
         }
         cur = nxt;
+        dt = dt_nxt;
+    }
+    if constexpr (ORIENT) {
+        acc = wave_sum(acc);
+        if (lane == 0) oa.orient[id] = acc;
     }
 }
 
@@ -178,6 +232,8 @@ __device__ __forceinline__ Grad7<C> load_grad7(const float *__restrict__ dsigma_
     if (i < cnt) {
         const int64_t s = off + i;
         k.dsig = dsigma_c[s];
+        // (written out, not load_row: at C = 1 both loads index with s, and through the helper k_shade_bwd<1> forms the
+        // two addresses in the other order -- the plain kernels' code is held fixed)
         if (C == 4) {
             const float4 v = reinterpret_cast<const float4 *>(dcolours)[s];
             k.dcol[0] = v.x; k.dcol[1] = v.y; k.dcol[2] = v.z; k.dcol[C - 1] = v.w;
@@ -233,15 +289,13 @@ __device__ __forceinline__ void project_and_store(const Lambert &o, const float 
     }
 #pragma unroll
     for (int j = 0; j < FD_ROWS; ++j) dsigmas7[s7 + j] = ds[j];
+    store_row<C>(drgbs7, s7, dalb);
     if (C == 4) {
         float4 *row = reinterpret_cast<float4 *>(drgbs7) + s7;
-        row[0] = make_float4(dalb[0], dalb[1], dalb[2], dalb[C - 1]);
 #pragma unroll
         for (int j = 1; j < FD_ROWS; ++j) row[j] = make_float4(0.f, 0.f, 0.f, 0.f);
     } else {
         float *row = drgbs7 + s7 * C;
-#pragma unroll
-        for (int c = 0; c < C; ++c) row[c] = dalb[c];
 #pragma unroll
         for (int j = C; j < FD_ROWS * C; ++j) row[j] = 0.f;
     }
@@ -249,140 +303,28 @@ __device__ __forceinline__ void project_and_store(const Lambert &o, const float 
 
 // Same launch shape as the forward.  Every element of rows 7 (off + i) .. 7 (off + i) + 6 of dsigmas7 and drgbs7 is
 // written by the lane that owns sample i: no atomics.
-template <int C>
+// ORIENT: with the term's gradient in dn:  dn_a += (go w (2 q)) v_a, go = d_orient[id], w recomputed (on all 64 lanes) and
+// DETACHED (no gradient reaches sg[0] or deltas through it).
+template <int C, bool ORIENT>
 __global__ void __launch_bounds__(256)
 k_shade_bwd(const float *__restrict__ sigmas7, const float *__restrict__ rgbs7, const int32_t *__restrict__ rays, int64_t N,
             int rays_per_view, const float *__restrict__ shade, int B, float inv_2eps, const float *__restrict__ dsigma_c,
-            const float *__restrict__ dcolours, float *__restrict__ dsigmas7, float *__restrict__ drgbs7) {
+            const float *__restrict__ dcolours, float *__restrict__ dsigmas7, float *__restrict__ drgbs7,
+            OrientArgs<ORIENT> oa) {
     const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (r >= N) return;
     const int lane = lane_id();
-    const int64_t id = rays[r * 3];
-    const int64_t off = rays[r * 3 + 1];
-    const int cnt = rays[r * 3 + 2];
+    const auto [id, off, cnt] = load_span(rays, r);
     if (cnt <= 0) return;
     const Light L = load_light(shade, id, rays_per_view, B);
+    float v[3], go = 0.f, carry = 0.f, dt = 0.f;
+    if constexpr (ORIENT) {
+        view_dir(oa.rays_d, id, v);
+        go = oa.d_orient[id];
+    }
     Sample7<C> cur = load_sample7<C>(sigmas7, rgbs7, off, cnt, lane);
     Grad7<C> gcur = load_grad7<C>(dsigma_c, dcolours, off, cnt, lane);
-    for (int base = 0; base < cnt; base += 64) {
-        Sample7<C> nxt = cur;
-        Grad7<C> gnxt = gcur;
-        if (base + 64 < cnt) {
-            nxt = load_sample7<C>(sigmas7, rgbs7, off, cnt, base + 64 + lane);
-            gnxt = load_grad7<C>(dsigma_c, dcolours, off, cnt, base + 64 + lane);
-        }
-        const int i = base + lane;
-        if (i < cnt) {
-            const int64_t s7 = (off + i) * FD_ROWS;
-            const Lambert o = lambert_of(cur.sg, inv_2eps, L);
-            float dn[3], dalb[C];
-            lambert_grad<C>(cur, gcur, o, L, dn, dalb);
-            project_and_store<C>(o, dn, gcur.dsig, dalb, inv_2eps, s7, dsigmas7, drgbs7);
-        }
-        cur = nxt;
-        gcur = gnxt;
-    }
-}
-
-// ---- the orientation term (contract: include/lnerf_hip.h, "orientation regulariser"; numpy: tests/orient_reference.py)
-
-// unit view direction of ray `id`
-__device__ __forceinline__ void view_dir(const float *__restrict__ rays_d, int64_t id, float (&v)[3]) {
-    const float d[3] = {rays_d[id * 3], rays_d[id * 3 + 1], rays_d[id * 3 + 2]};
-    const float s = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
-    const float r = 1.0f / sqrtf(fmaxf(s, 1e-20f));
-#pragma unroll
-    for (int a = 0; a < 3; ++a) v[a] = d[a] * r;
-}
-
-// dt of sample i of the span (0 past its end): the .x of the march's 8-byte (dt, t) pair
-__device__ __forceinline__ float load_dt(const float *__restrict__ deltas, int64_t off, int cnt, int i) {
-    return i < cnt ? reinterpret_cast<const float2 *>(deltas)[off + i].x : 0.f;
-}
-
-// Compositing weight of this lane's sample, as composite_ray_fwd defines it, on `sigma` (scaled already) -- called by
-// ALL 64 lanes (lanes past the span pass zeros).  There is no early stop here: behind T < T_thresh the weights are 0 and
-// the chunks go on, every sample of the span still gets its rows.
-__device__ __forceinline__ float composite_weight(float sigma, float dt, bool valid, float T_thresh, float &carry) {
-    const float tau = sigma * dt;
-    const float inc = wave_inclusive_sum(tau);
-    const float excl = exclusive_depth(inc, carry);
-    const float T = expf(-excl);
-    const float alpha = 1.0f - expf(-tau);
-    carry += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(inc), 63));
-    return (valid && T >= T_thresh) ? alpha * T : 0.f;
-}
-
-// max(0, n . v)
-__device__ __forceinline__ float facing_away(const Lambert &o, const float (&v)[3]) {
-    const float c = (o.n[0] * v[0] + o.n[1] * v[1]) + o.n[2] * v[2];
-    return c > 0.f ? c : 0.f;
-}
-
-// k_shade_fwd plus orient[id] = sum_i w_i q_i^2 (a ray without samples writes 0: the buffer is uninitialised).
-template <int C>
-__global__ void __launch_bounds__(256)
-k_shade_orient_fwd(const float *__restrict__ sigmas7, const float *__restrict__ rgbs7, const int32_t *__restrict__ rays,
-                   int64_t N, int rays_per_view, const float *__restrict__ shade, int B, float inv_2eps,
-                   const float *__restrict__ deltas, const float *__restrict__ rays_d, float density_scale, float T_thresh,
-                   float *__restrict__ sigma_c, float *__restrict__ colours, float *__restrict__ orient) {
-    const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    if (r >= N) return;
-    const int lane = lane_id();
-    const int64_t id = rays[r * 3];
-    const int64_t off = rays[r * 3 + 1];
-    const int cnt = rays[r * 3 + 2];
-    const Light L = load_light(shade, id, rays_per_view, B);
-    float v[3];
-    view_dir(rays_d, id, v);
-    float acc = 0.f, carry = 0.f;
-    Sample7<C> cur = load_sample7<C>(sigmas7, rgbs7, off, cnt, lane);
-    float dt = load_dt(deltas, off, cnt, lane);
-    for (int base = 0; base < cnt; base += 64) {      // (wave-uniform: the scan below runs with all lanes)
-        Sample7<C> nxt = cur;
-        float dt_nxt = dt;
-        if (base + 64 < cnt) {
-            nxt = load_sample7<C>(sigmas7, rgbs7, off, cnt, base + 64 + lane);
-            dt_nxt = load_dt(deltas, off, cnt, base + 64 + lane);
-        }
-        const int i = base + lane;
-        const bool valid = i < cnt;
-        const Lambert o = lambert_of(cur.sg, inv_2eps, L);
-        if (valid) store_shaded<C>(cur, o, L, off + i, sigma_c, colours);
-        const float w = composite_weight(density_scale * cur.sg[0], dt, valid, T_thresh, carry);
-        const float q = facing_away(o, v);
-        acc += w * (q * q);
-        cur = nxt;
-        dt = dt_nxt;
-    }
-    acc = wave_sum(acc);
-    if (lane == 0) orient[id] = acc;
-}
-
-// k_shade_bwd with the term's gradient in dn:  dn_a += (go w (2 q)) v_a, go = d_orient[id], w recomputed and DETACHED (no
-// gradient reaches sg[0] or deltas through it).
-template <int C>
-__global__ void __launch_bounds__(256)
-k_shade_orient_bwd(const float *__restrict__ sigmas7, const float *__restrict__ rgbs7, const int32_t *__restrict__ rays,
-                   int64_t N, int rays_per_view, const float *__restrict__ shade, int B, float inv_2eps,
-                   const float *__restrict__ dsigma_c, const float *__restrict__ dcolours, const float *__restrict__ deltas,
-                   const float *__restrict__ rays_d, float density_scale, float T_thresh, const float *__restrict__ d_orient,
-                   float *__restrict__ dsigmas7, float *__restrict__ drgbs7) {
-    const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    if (r >= N) return;
-    const int lane = lane_id();
-    const int64_t id = rays[r * 3];
-    const int64_t off = rays[r * 3 + 1];
-    const int cnt = rays[r * 3 + 2];
-    if (cnt <= 0) return;
-    const Light L = load_light(shade, id, rays_per_view, B);
-    float v[3];
-    view_dir(rays_d, id, v);
-    const float go = d_orient[id];
-    float carry = 0.f;
-    Sample7<C> cur = load_sample7<C>(sigmas7, rgbs7, off, cnt, lane);
-    Grad7<C> gcur = load_grad7<C>(dsigma_c, dcolours, off, cnt, lane);
-    float dt = load_dt(deltas, off, cnt, lane);
+    if constexpr (ORIENT) dt = load_dt(oa.deltas, off, cnt, lane);
     for (int base = 0; base < cnt; base += 64) {      // (wave-uniform)
         Sample7<C> nxt = cur;
         Grad7<C> gnxt = gcur;
@@ -390,21 +332,26 @@ k_shade_orient_bwd(const float *__restrict__ sigmas7, const float *__restrict__ 
         if (base + 64 < cnt) {
             nxt = load_sample7<C>(sigmas7, rgbs7, off, cnt, base + 64 + lane);
             gnxt = load_grad7<C>(dsigma_c, dcolours, off, cnt, base + 64 + lane);
-            dt_nxt = load_dt(deltas, off, cnt, base + 64 + lane);
+            if constexpr (ORIENT) dt_nxt = load_dt(oa.deltas, off, cnt, base + 64 + lane);
         }
         const int i = base + lane;
         const bool valid = i < cnt;
-        const Lambert o = lambert_of(cur.sg, inv_2eps, L);
-        const float w = composite_weight(density_scale * cur.sg[0], dt, valid, T_thresh, carry);
-        if (valid) {
-            float dn[3], dalb[C];
-            lambert_grad<C>(cur, gcur, o, L, dn, dalb);
-            const float q = facing_away(o, v);
-            const float e = go * w;
-            const float k = e * (2.0f * q);
+        if (ORIENT || valid) {
+            const Lambert o = lambert_of(cur.sg, inv_2eps, L);
+            float w = 0.f;
+            if constexpr (ORIENT) w = composite_weight(oa.density_scale * cur.sg[0], dt, valid, oa.T_thresh, carry);
+            if (valid) {
+                float dn[3], dalb[C];
+                lambert_grad<C>(cur, gcur, o, L, dn, dalb);
+                if constexpr (ORIENT) {
+                    const float q = facing_away(o, v);
+                    const float e = go * w;
+                    const float k = e * (2.0f * q);
 #pragma unroll
-            for (int a = 0; a < 3; ++a) dn[a] = dn[a] + k * v[a];
-            project_and_store<C>(o, dn, gcur.dsig, dalb, inv_2eps, (off + i) * FD_ROWS, dsigmas7, drgbs7);
+                    for (int a = 0; a < 3; ++a) dn[a] = dn[a] + k * v[a];
+                }
+                project_and_store<C>(o, dn, gcur.dsig, dalb, inv_2eps, (off + i) * FD_ROWS, dsigmas7, drgbs7);
+            }
         }
         cur = nxt;
         gcur = gnxt;
@@ -415,6 +362,78 @@ k_shade_orient_bwd(const float *__restrict__ sigmas7, const float *__restrict__ 
 }  // namespace lnerf
 
 using namespace lnerf;
+
+// ---- the four shading entry points: one validate-and-launch path per direction.  `name` is the entry point's, for the
+// messages; `oa` is the orient calls' argument block (plain calls: nullptr).
+static int check_orient(const char *name, const OrientArgs<true> &oa) {
+    LNERF_REQUIRE(oa.deltas && oa.rays_d, "%s: null pointer (deltas / rays_d)", name);
+    LNERF_REQUIRE(((uintptr_t)oa.deltas & 7) == 0, "%s: deltas must be 8-byte aligned", name);
+    LNERF_REQUIRE(oa.density_scale >= 0.f, "%s: density_scale must be >= 0", name);
+    return LNERF_OK;
+}
+
+static int shade_forward(const char *name, const float *sigmas7, const float *rgbs7, int C, const int32_t *rays, int64_t N,
+                         int rays_per_view, const float *shade, int B, float inv_2eps, float *sigma_c, float *colours,
+                         const OrientArgs<true> *oa, lnerf_stream_t stream) {
+    LNERF_REQUIRE(N >= 0, "%s: negative N", name);
+    LNERF_REQUIRE(C >= 1 && C <= 4, "%s: C must be 1..4 (got %d)", name, C);
+    LNERF_REQUIRE(rays_per_view > 0, "%s: rays_per_view must be > 0", name);
+    if (N == 0) return LNERF_OK;
+    LNERF_REQUIRE(B > 0, "%s: B must be > 0", name);
+    LNERF_REQUIRE(sigmas7 && rgbs7 && rays && shade && sigma_c && colours && (!oa || oa->orient), "%s: null pointer", name);
+    LNERF_REQUIRE(C != 4 || (((uintptr_t)rgbs7 | (uintptr_t)colours) & 15) == 0,
+                  "%s: (C = 4) rgbs7 / colours must be 16-byte aligned", name);
+    if (oa && check_orient(name, *oa) != LNERF_OK) return LNERF_ERR_INVALID_ARG;
+    const dim3 grid((unsigned)div_up(N, 4)), block(256);
+    const auto launch = [&](auto kernel, auto orient_args) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, as_stream(stream), sigmas7, rgbs7, rays, N, rays_per_view, shade, B,
+                           inv_2eps, sigma_c, colours, orient_args);
+    };
+#define LNERF_SHADE_FWD(CC)                                                                                            \
+    if (oa) launch(k_shade_fwd<CC, true>, *oa);                                                                        \
+    else launch(k_shade_fwd<CC, false>, OrientArgs<false>{})
+    switch (C) {
+        case 1: LNERF_SHADE_FWD(1); break;
+        case 2: LNERF_SHADE_FWD(2); break;
+        case 3: LNERF_SHADE_FWD(3); break;
+        default: LNERF_SHADE_FWD(4); break;
+    }
+#undef LNERF_SHADE_FWD
+    LNERF_CHECK_LAUNCH(name);
+    return LNERF_OK;
+}
+
+static int shade_backward(const char *name, const float *sigmas7, const float *rgbs7, int C, const int32_t *rays, int64_t N,
+                          int rays_per_view, const float *shade, int B, float inv_2eps, const float *dsigma_c,
+                          const float *dcolours, float *dsigmas7, float *drgbs7, const OrientArgs<true> *oa,
+                          lnerf_stream_t stream) {
+    LNERF_REQUIRE(N >= 0, "%s: negative N", name);
+    LNERF_REQUIRE(C >= 1 && C <= 4, "%s: C must be 1..4 (got %d)", name, C);
+    LNERF_REQUIRE(rays_per_view > 0, "%s: rays_per_view must be > 0", name);
+    if (N == 0) return LNERF_OK;
+    LNERF_REQUIRE(B > 0, "%s: B must be > 0", name);
+    LNERF_REQUIRE(sigmas7 && rgbs7 && rays && shade && dsigma_c && dcolours && dsigmas7 && drgbs7, "%s: null pointer", name);
+    LNERF_REQUIRE(C != 4 || (((uintptr_t)rgbs7 | (uintptr_t)dcolours | (uintptr_t)drgbs7) & 15) == 0,
+                  "%s: (C = 4) rgbs7 / dcolours / drgbs7 must be 16-byte aligned", name);
+    if (oa && check_orient(name, *oa) != LNERF_OK) return LNERF_ERR_INVALID_ARG;
+    const dim3 grid((unsigned)div_up(N, 4)), block(256);
+    const auto launch = [&](auto kernel, auto orient_args) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, as_stream(stream), sigmas7, rgbs7, rays, N, rays_per_view, shade, B,
+                           inv_2eps, dsigma_c, dcolours, dsigmas7, drgbs7, orient_args);
+    };
+#define LNERF_SHADE_BWD(CC)                                                                                            \
+    if (oa) launch(k_shade_bwd<CC, true>, *oa);                                                                        \
+    else launch(k_shade_bwd<CC, false>, OrientArgs<false>{})
+    switch (C) {
+        case 1: LNERF_SHADE_BWD(1); break;
+        case 2: LNERF_SHADE_BWD(2); break;
+        case 3: LNERF_SHADE_BWD(3); break;
+        default: LNERF_SHADE_BWD(4); break;
+    }
+#undef LNERF_SHADE_BWD
+    LNERF_CHECK_LAUNCH(name);
+    return LNERF_OK;
+}
 
 extern "C" {
 
@@ -437,89 +456,24 @@ int lnerf_fd_points(const float *xyzs, float bound, float eps, int64_t m_host, c
 int lnerf_shade_fd_forward(const float *sigmas7, const float *rgbs7, int C, const int32_t *rays, int64_t N,
                            int rays_per_view, const float *shade, int B, float inv_2eps, float *sigma_c, float *colours,
                            lnerf_stream_t stream) {
-    LNERF_REQUIRE(N >= 0, "shade_fd_forward: negative N");
-    LNERF_REQUIRE(C >= 1 && C <= 4, "shade_fd_forward: C must be 1..4 (got %d)", C);
-    LNERF_REQUIRE(rays_per_view > 0, "shade_fd_forward: rays_per_view must be > 0");
-    if (N == 0) return LNERF_OK;
-    LNERF_REQUIRE(B > 0, "shade_fd_forward: B must be > 0");
-    LNERF_REQUIRE(sigmas7 && rgbs7 && rays && shade && sigma_c && colours, "shade_fd_forward: null pointer");
-    LNERF_REQUIRE(C != 4 || (((uintptr_t)rgbs7 | (uintptr_t)colours) & 15) == 0,
-                  "shade_fd_forward: (C = 4) rgbs7 / colours must be 16-byte aligned");
-    const dim3 grid((unsigned)div_up(N, 4)), block(256);
-#define LNERF_SHADE_FWD(CC)                                                                                            \
-    hipLaunchKernelGGL(k_shade_fwd<CC>, grid, block, 0, as_stream(stream), sigmas7, rgbs7, rays, N, rays_per_view, shade, \
-                       B, inv_2eps, sigma_c, colours)
-    switch (C) {
-        case 1: LNERF_SHADE_FWD(1); break;
-        case 2: LNERF_SHADE_FWD(2); break;
-        case 3: LNERF_SHADE_FWD(3); break;
-        default: LNERF_SHADE_FWD(4); break;
-    }
-#undef LNERF_SHADE_FWD
-    LNERF_CHECK_LAUNCH("shade_fd_forward");
-    return LNERF_OK;
+    return shade_forward("shade_fd_forward", sigmas7, rgbs7, C, rays, N, rays_per_view, shade, B, inv_2eps, sigma_c, colours,
+                         nullptr, stream);
 }
 
 int lnerf_shade_fd_backward(const float *sigmas7, const float *rgbs7, int C, const int32_t *rays, int64_t N,
                             int rays_per_view, const float *shade, int B, float inv_2eps, const float *dsigma_c,
                             const float *dcolours, float *dsigmas7, float *drgbs7, lnerf_stream_t stream) {
-    LNERF_REQUIRE(N >= 0, "shade_fd_backward: negative N");
-    LNERF_REQUIRE(C >= 1 && C <= 4, "shade_fd_backward: C must be 1..4 (got %d)", C);
-    LNERF_REQUIRE(rays_per_view > 0, "shade_fd_backward: rays_per_view must be > 0");
-    if (N == 0) return LNERF_OK;
-    LNERF_REQUIRE(B > 0, "shade_fd_backward: B must be > 0");
-    LNERF_REQUIRE(sigmas7 && rgbs7 && rays && shade && dsigma_c && dcolours && dsigmas7 && drgbs7,
-                  "shade_fd_backward: null pointer");
-    LNERF_REQUIRE(C != 4 || (((uintptr_t)rgbs7 | (uintptr_t)dcolours | (uintptr_t)drgbs7) & 15) == 0,
-                  "shade_fd_backward: (C = 4) rgbs7 / dcolours / drgbs7 must be 16-byte aligned");
-    const dim3 grid((unsigned)div_up(N, 4)), block(256);
-#define LNERF_SHADE_BWD(CC)                                                                                            \
-    hipLaunchKernelGGL(k_shade_bwd<CC>, grid, block, 0, as_stream(stream), sigmas7, rgbs7, rays, N, rays_per_view, shade, \
-                       B, inv_2eps, dsigma_c, dcolours, dsigmas7, drgbs7)
-    switch (C) {
-        case 1: LNERF_SHADE_BWD(1); break;
-        case 2: LNERF_SHADE_BWD(2); break;
-        case 3: LNERF_SHADE_BWD(3); break;
-        default: LNERF_SHADE_BWD(4); break;
-    }
-#undef LNERF_SHADE_BWD
-    LNERF_CHECK_LAUNCH("shade_fd_backward");
-    return LNERF_OK;
+    return shade_backward("shade_fd_backward", sigmas7, rgbs7, C, rays, N, rays_per_view, shade, B, inv_2eps, dsigma_c,
+                          dcolours, dsigmas7, drgbs7, nullptr, stream);
 }
-
-// the arguments the orient entry points add to the plain ones
-#define LNERF_REQUIRE_ORIENT(name)                                                                                     \
-    LNERF_REQUIRE(deltas && rays_d, name ": null pointer (deltas / rays_d)");                                          \
-    LNERF_REQUIRE(((uintptr_t)deltas & 7) == 0, name ": deltas must be 8-byte aligned");                               \
-    LNERF_REQUIRE(density_scale >= 0.f, name ": density_scale must be >= 0")
 
 int lnerf_shade_fd_orient_forward(const float *sigmas7, const float *rgbs7, int C, const int32_t *rays, int64_t N,
                                   int rays_per_view, const float *shade, int B, float inv_2eps, const float *deltas,
                                   const float *rays_d, float density_scale, float T_thresh, float *sigma_c, float *colours,
                                   float *orient, lnerf_stream_t stream) {
-    LNERF_REQUIRE(N >= 0, "shade_fd_orient_forward: negative N");
-    LNERF_REQUIRE(C >= 1 && C <= 4, "shade_fd_orient_forward: C must be 1..4 (got %d)", C);
-    LNERF_REQUIRE(rays_per_view > 0, "shade_fd_orient_forward: rays_per_view must be > 0");
-    if (N == 0) return LNERF_OK;
-    LNERF_REQUIRE(B > 0, "shade_fd_orient_forward: B must be > 0");
-    LNERF_REQUIRE(sigmas7 && rgbs7 && rays && shade && sigma_c && colours && orient,
-                  "shade_fd_orient_forward: null pointer");
-    LNERF_REQUIRE(C != 4 || (((uintptr_t)rgbs7 | (uintptr_t)colours) & 15) == 0,
-                  "shade_fd_orient_forward: (C = 4) rgbs7 / colours must be 16-byte aligned");
-    LNERF_REQUIRE_ORIENT("shade_fd_orient_forward");
-    const dim3 grid((unsigned)div_up(N, 4)), block(256);
-#define LNERF_SHADE_FWD(CC)                                                                                            \
-    hipLaunchKernelGGL(k_shade_orient_fwd<CC>, grid, block, 0, as_stream(stream), sigmas7, rgbs7, rays, N, rays_per_view, \
-                       shade, B, inv_2eps, deltas, rays_d, density_scale, T_thresh, sigma_c, colours, orient)
-    switch (C) {
-        case 1: LNERF_SHADE_FWD(1); break;
-        case 2: LNERF_SHADE_FWD(2); break;
-        case 3: LNERF_SHADE_FWD(3); break;
-        default: LNERF_SHADE_FWD(4); break;
-    }
-#undef LNERF_SHADE_FWD
-    LNERF_CHECK_LAUNCH("shade_fd_orient_forward");
-    return LNERF_OK;
+    const OrientArgs<true> oa = {deltas, rays_d, density_scale, T_thresh, orient, nullptr};
+    return shade_forward("shade_fd_orient_forward", sigmas7, rgbs7, C, rays, N, rays_per_view, shade, B, inv_2eps, sigma_c,
+                         colours, &oa, stream);
 }
 
 int lnerf_shade_fd_orient_backward(const float *sigmas7, const float *rgbs7, int C, const int32_t *rays, int64_t N,
@@ -531,31 +485,9 @@ int lnerf_shade_fd_orient_backward(const float *sigmas7, const float *rgbs7, int
     if (!d_orient)
         return lnerf_shade_fd_backward(sigmas7, rgbs7, C, rays, N, rays_per_view, shade, B, inv_2eps, dsigma_c, dcolours,
                                        dsigmas7, drgbs7, stream);
-    LNERF_REQUIRE(N >= 0, "shade_fd_orient_backward: negative N");
-    LNERF_REQUIRE(C >= 1 && C <= 4, "shade_fd_orient_backward: C must be 1..4 (got %d)", C);
-    LNERF_REQUIRE(rays_per_view > 0, "shade_fd_orient_backward: rays_per_view must be > 0");
-    if (N == 0) return LNERF_OK;
-    LNERF_REQUIRE(B > 0, "shade_fd_orient_backward: B must be > 0");
-    LNERF_REQUIRE(sigmas7 && rgbs7 && rays && shade && dsigma_c && dcolours && dsigmas7 && drgbs7,
-                  "shade_fd_orient_backward: null pointer");
-    LNERF_REQUIRE(C != 4 || (((uintptr_t)rgbs7 | (uintptr_t)dcolours | (uintptr_t)drgbs7) & 15) == 0,
-                  "shade_fd_orient_backward: (C = 4) rgbs7 / dcolours / drgbs7 must be 16-byte aligned");
-    LNERF_REQUIRE_ORIENT("shade_fd_orient_backward");
-    const dim3 grid((unsigned)div_up(N, 4)), block(256);
-#define LNERF_SHADE_BWD(CC)                                                                                            \
-    hipLaunchKernelGGL(k_shade_orient_bwd<CC>, grid, block, 0, as_stream(stream), sigmas7, rgbs7, rays, N, rays_per_view, \
-                       shade, B, inv_2eps, dsigma_c, dcolours, deltas, rays_d, density_scale, T_thresh, d_orient, dsigmas7, \
-                       drgbs7)
-    switch (C) {
-        case 1: LNERF_SHADE_BWD(1); break;
-        case 2: LNERF_SHADE_BWD(2); break;
-        case 3: LNERF_SHADE_BWD(3); break;
-        default: LNERF_SHADE_BWD(4); break;
-    }
-#undef LNERF_SHADE_BWD
-    LNERF_CHECK_LAUNCH("shade_fd_orient_backward");
-    return LNERF_OK;
+    const OrientArgs<true> oa = {deltas, rays_d, density_scale, T_thresh, nullptr, d_orient};
+    return shade_backward("shade_fd_orient_backward", sigmas7, rgbs7, C, rays, N, rays_per_view, shade, B, inv_2eps,
+                          dsigma_c, dcolours, dsigmas7, drgbs7, &oa, stream);
 }
-#undef LNERF_REQUIRE_ORIENT
 
 }  // extern "C"

@@ -407,8 +407,11 @@ def shade_record(light_d, ambient_ratio, textureless, n_views, device):
 
 
 class _ShadeFD(torch.autograd.Function):
+    """lnerf_shade_fd_forward / _backward; with `orient` (shade_fd's tuple, or None) lnerf_shade_fd_orient_*, which return
+    the term as a third output: one forward launch, one backward launch either way."""
+
     @staticmethod
-    def forward(ctx, sigmas7, rgbs7, rays, shade, rays_per_view, eps):
+    def forward(ctx, sigmas7, rgbs7, rays, shade, rays_per_view, eps, orient):
         sigmas7 = sigmas7.contiguous()
         rgbs7 = rgbs7.contiguous()
         shade = shade.contiguous()
@@ -417,83 +420,56 @@ class _ShadeFD(torch.autograd.Function):
         if shade.dim() != 2 or shade.shape[1] != 5:
             raise ValueError("shade_fd: shade must be [B,5] = (l_x, l_y, l_z, ambient, textureless)")
         cap, C, N, B = sigmas7.shape[0] // 7, rgbs7.shape[1], rays.shape[0], shade.shape[0]
+        if orient is not None:
+            deltas, rays_d, density_scale, T_thresh, n_ids = orient
+            n_ids = int(n_ids)
+            if deltas.dim() != 2 or deltas.shape[1] != 2 or deltas.shape[0] < cap:
+                raise ValueError("shade_fd: orient needs the march's deltas [>= cap, 2] (got %s for cap %d)"
+                                 % (tuple(deltas.shape), cap))
+            if rays_d.dim() != 2 or rays_d.shape[1] != 3 or rays_d.shape[0] != n_ids or N > n_ids:
+                raise ValueError("shade_fd: orient needs rays_d [n_ids, 3] with n_ids = %d >= the %d rays (got %s)"
+                                 % (n_ids, N, tuple(rays_d.shape)))
         dev = sigmas7.device
         inv_2eps = 1.0 / (2.0 * float(eps))
         # (rows outside every ray's span are not written, as with the field's own outputs: no fill launch in the step)
         sigma_c = torch.empty(cap, device=dev, dtype=torch.float32)
         colours = torch.empty(cap, C, device=dev, dtype=torch.float32)
-        _b.call("lnerf_shade_fd_forward", _chk(sigmas7, "sigmas7"), _chk(rgbs7, "rgbs7"), C,
-                _chk(rays, "rays", torch.int32), N, int(rays_per_view), _chk(shade, "shade"), B, inv_2eps, _p(sigma_c),
-                _p(colours), _stream())
-        ctx.save_for_backward(sigmas7, rgbs7, rays, shade)
+        args = (_chk(sigmas7, "sigmas7"), _chk(rgbs7, "rgbs7"), C, _chk(rays, "rays", torch.int32), N, int(rays_per_view),
+                _chk(shade, "shade"), B, inv_2eps)
         ctx.set_materialize_grads(False)
-        ctx.meta = (int(rays_per_view), inv_2eps)
-        return sigma_c, colours
+        if orient is None:
+            _b.call("lnerf_shade_fd_forward", *args, _p(sigma_c), _p(colours), _stream())
+            ctx.save_for_backward(sigmas7, rgbs7, rays, shade)
+            ctx.meta = (int(rays_per_view), inv_2eps)
+            return sigma_c, colours
+        # every ray of the table writes its own element (0 for an empty span); with fewer rays than ids the rest is 0
+        orient_ray = (torch.empty if N == n_ids else torch.zeros)(n_ids, device=dev, dtype=torch.float32)
+        _b.call("lnerf_shade_fd_orient_forward", *args, _chk(deltas, "deltas"), _chk(rays_d, "rays_d"),
+                float(density_scale), float(T_thresh), _p(sigma_c), _p(colours), _p(orient_ray), _stream())
+        ctx.save_for_backward(sigmas7, rgbs7, rays, shade, deltas, rays_d)
+        ctx.meta = (int(rays_per_view), inv_2eps, float(density_scale), float(T_thresh))
+        return sigma_c, colours, orient_ray
 
     @staticmethod
-    def backward(ctx, dsigma_c, dcolours):
-        sigmas7, rgbs7, rays, shade = ctx.saved_tensors
-        rays_per_view, inv_2eps = ctx.meta
+    def backward(ctx, dsigma_c, dcolours, d_orient=None):
+        sigmas7, rgbs7, rays, shade, *orient = ctx.saved_tensors
+        rays_per_view, inv_2eps, *orient_meta = ctx.meta
         cap, C, N, B = sigmas7.shape[0] // 7, rgbs7.shape[1], rays.shape[0], shade.shape[0]
         dsigma_c = torch.zeros(cap, device=sigmas7.device) if dsigma_c is None else dsigma_c.contiguous()
         dcolours = torch.zeros(cap, C, device=sigmas7.device) if dcolours is None else dcolours.contiguous()
         # every row below 7 m lies in a ray's span and is written by the kernel; the rows above are read by nobody
         dsigmas7 = torch.empty_like(sigmas7)
         drgbs7 = torch.empty_like(rgbs7)
-        _b.call("lnerf_shade_fd_backward", _p(sigmas7), _p(rgbs7), C, _p(rays), N, rays_per_view, _p(shade), B, inv_2eps,
-                _chk(dsigma_c, "dsigma_c"), _chk(dcolours, "dcolours"), _p(dsigmas7), _p(drgbs7), _stream())
-        return dsigmas7, drgbs7, None, None, None, None
-
-
-class _ShadeFDOrient(torch.autograd.Function):
-    """_ShadeFD with the orientation term: one forward launch, one backward launch (lnerf_shade_fd_orient_*)."""
-
-    @staticmethod
-    def forward(ctx, sigmas7, rgbs7, rays, shade, rays_per_view, eps, deltas, rays_d, density_scale, T_thresh, n_ids):
-        sigmas7 = sigmas7.contiguous()
-        rgbs7 = rgbs7.contiguous()
-        shade = shade.contiguous()
-        if sigmas7.shape[0] % 7 != 0 or rgbs7.shape[0] != sigmas7.shape[0]:
-            raise ValueError("shade_fd: sigmas7 [7 cap] and rgbs7 [7 cap, C] must hold seven rows per sample")
-        if shade.dim() != 2 or shade.shape[1] != 5:
-            raise ValueError("shade_fd: shade must be [B,5] = (l_x, l_y, l_z, ambient, textureless)")
-        cap, C, N, B = sigmas7.shape[0] // 7, rgbs7.shape[1], rays.shape[0], shade.shape[0]
-        n_ids = int(n_ids)
-        if deltas.dim() != 2 or deltas.shape[1] != 2 or deltas.shape[0] < cap:
-            raise ValueError("shade_fd: orient needs the march's deltas [>= cap, 2] (got %s for cap %d)"
-                             % (tuple(deltas.shape), cap))
-        if rays_d.dim() != 2 or rays_d.shape[1] != 3 or rays_d.shape[0] != n_ids or N > n_ids:
-            raise ValueError("shade_fd: orient needs rays_d [n_ids, 3] with n_ids = %d >= the %d rays (got %s)"
-                             % (n_ids, N, tuple(rays_d.shape)))
-        dev = sigmas7.device
-        inv_2eps = 1.0 / (2.0 * float(eps))
-        sigma_c = torch.empty(cap, device=dev, dtype=torch.float32)
-        colours = torch.empty(cap, C, device=dev, dtype=torch.float32)
-        # every ray of the table writes its own element (0 for an empty span); with fewer rays than ids the rest is 0
-        orient = (torch.empty if N == n_ids else torch.zeros)(n_ids, device=dev, dtype=torch.float32)
-        _b.call("lnerf_shade_fd_orient_forward", _chk(sigmas7, "sigmas7"), _chk(rgbs7, "rgbs7"), C,
-                _chk(rays, "rays", torch.int32), N, int(rays_per_view), _chk(shade, "shade"), B, inv_2eps,
-                _chk(deltas, "deltas"), _chk(rays_d, "rays_d"), float(density_scale), float(T_thresh), _p(sigma_c),
-                _p(colours), _p(orient), _stream())
-        ctx.save_for_backward(sigmas7, rgbs7, rays, shade, deltas, rays_d)
-        ctx.set_materialize_grads(False)
-        ctx.meta = (int(rays_per_view), inv_2eps, float(density_scale), float(T_thresh))
-        return sigma_c, colours, orient
-
-    @staticmethod
-    def backward(ctx, dsigma_c, dcolours, d_orient):
-        sigmas7, rgbs7, rays, shade, deltas, rays_d = ctx.saved_tensors
-        rays_per_view, inv_2eps, density_scale, T_thresh = ctx.meta
-        cap, C, N, B = sigmas7.shape[0] // 7, rgbs7.shape[1], rays.shape[0], shade.shape[0]
-        dsigma_c = torch.zeros(cap, device=sigmas7.device) if dsigma_c is None else dsigma_c.contiguous()
-        dcolours = torch.zeros(cap, C, device=sigmas7.device) if dcolours is None else dcolours.contiguous()
-        d_orient = None if d_orient is None else d_orient.contiguous()
-        dsigmas7 = torch.empty_like(sigmas7)
-        drgbs7 = torch.empty_like(rgbs7)
-        _b.call("lnerf_shade_fd_orient_backward", _p(sigmas7), _p(rgbs7), C, _p(rays), N, rays_per_view, _p(shade), B,
-                inv_2eps, _chk(dsigma_c, "dsigma_c"), _chk(dcolours, "dcolours"), _p(deltas), _p(rays_d), density_scale,
-                T_thresh, _chk(d_orient, "d_orient", allow_none=True), _p(dsigmas7), _p(drgbs7), _stream())
-        return (dsigmas7, drgbs7) + (None,) * 9
+        args = (_p(sigmas7), _p(rgbs7), C, _p(rays), N, rays_per_view, _p(shade), B, inv_2eps,
+                _chk(dsigma_c, "dsigma_c"), _chk(dcolours, "dcolours"))
+        if orient:
+            deltas, rays_d = orient
+            d_orient = None if d_orient is None else d_orient.contiguous()   # (None: the library runs the plain backward)
+            _b.call("lnerf_shade_fd_orient_backward", *args, _p(deltas), _p(rays_d), *orient_meta,
+                    _chk(d_orient, "d_orient", allow_none=True), _p(dsigmas7), _p(drgbs7), _stream())
+        else:
+            _b.call("lnerf_shade_fd_backward", *args, _p(dsigmas7), _p(drgbs7), _stream())
+        return (dsigmas7, drgbs7) + (None,) * 5
 
 
 def shade_fd(sigmas7, rgbs7, rays, shade, rays_per_view, eps, orient=None):
@@ -506,11 +482,7 @@ def shade_fd(sigmas7, rgbs7, rays, shade, rays_per_view, eps, orient=None):
     (lnerf_shade_fd_orient_forward / _backward, ONE node, one launch each way) -> (sigma_c, colours, orient_ray [n_ids]),
     orient_ray[id] = sum_i w_i max(0, n_i . v)^2 with the compositing weights w (detached: its gradient reaches sigmas7
     through the normal alone) and v the unit direction of ray id; sigma_c and colours are the plain call's bits."""
-    if orient is None:
-        return _ShadeFD.apply(sigmas7, rgbs7, rays, shade, rays_per_view, eps)
-    deltas, rays_d, density_scale, T_thresh, n_ids = orient
-    return _ShadeFDOrient.apply(sigmas7, rgbs7, rays, shade, rays_per_view, eps, deltas, rays_d, density_scale, T_thresh,
-                                n_ids)
+    return _ShadeFD.apply(sigmas7, rgbs7, rays, shade, rays_per_view, eps, orient)
 
 
 # ------------------------------------------------------------------------------ mesh export

@@ -1,4 +1,4 @@
-"""References of the orientation regulariser of the shaded renders (csrc/shade.hip, k_shade_orient_fwd / _bwd; contract in
+"""References of the orientation regulariser of the shaded renders (csrc/shade.hip, ORIENT = true; contract in
 include/lnerf_hip.h, "orientation regulariser"):  orient[ray] = sum_i w_i max(0, n_i . v)^2.
 
 Built on tests/shading_reference.py (imported unchanged).  The per-sample terms -- the normal n, q = max(0, n . v) and the

@@ -1,7 +1,7 @@
-"""The orientation regulariser on the MI355X (csrc/shade.hip k_shade_orient_fwd / _bwd, raymarching.shade_fd(orient=...),
-render(orient=True), optim.lambda_orient).  References: tests/orient_reference.py (float64; its op-level case and the
-preconditions asserted on it before anything is compared: sigma' dt <= 1.5, every reference T at least 1e-3 (relative)
-away from T_thresh, every lit / away-facing normal more than 0.1 rad from l / v).
+"""The orientation regulariser on the MI355X (csrc/shade.hip k_shade_fwd / k_shade_bwd with ORIENT = true,
+raymarching.shade_fd(orient=...), render(orient=True), optim.lambda_orient).  References: tests/orient_reference.py
+(float64; its op-level case and the preconditions asserted on it before anything is compared: sigma' dt <= 1.5, every
+reference T at least 1e-3 (relative) away from T_thresh, every lit / away-facing normal more than 0.1 rad from l / v).
 
 1. Forward: sigma_c and colours are lnerf_shade_fd_forward's bits; per ray with k samples |orient - ref| <= 2 COMPOSITE_TOL(k)
    (the compositing bound 32 2^-24 (k + 1) in its (1 + max |c|) form with q^2 <= 1); the empty ray and the back-facing ray
@@ -115,9 +115,10 @@ class _Op:
 
 
 CASES = [(4, 1.0), (3, 0.5), (4, 0.5), (3, 1.0)]
+CASES_EVERY_C = CASES + [(2, 1.0), (1, 0.5)]      # the entry points dispatch on C = 1..4
 
 
-@pytest.mark.parametrize("C,density_scale", CASES)
+@pytest.mark.parametrize("C,density_scale", CASES_EVERY_C)
 def test_forward(dev, C, density_scale):
     op = _Op(dev, C, density_scale)
     k, M = op.k, op.k["M"]
@@ -145,7 +146,7 @@ def test_forward(dev, C, density_scale):
     assert _same_bits(again[2], torch.from_numpy(got).float())
 
 
-@pytest.mark.parametrize("C,density_scale", CASES)
+@pytest.mark.parametrize("C,density_scale", CASES_EVERY_C)
 def test_backward_without_a_gradient_for_the_term_is_the_plain_backward(dev, C, density_scale):
     op = _Op(dev, C, density_scale)
     k, M = op.k, op.k["M"]

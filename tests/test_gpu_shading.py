@@ -123,7 +123,7 @@ def _shade_case(C, seed=2):
     return rays, M, cap, sig, alb, shade, dsig, dcol
 
 
-@pytest.mark.parametrize("C", [4, 3])
+@pytest.mark.parametrize("C", [4, 3, 2, 1])
 def test_shade_forward_and_backward_bit_equal_to_numpy(dev, C):
     from src.latent_nerf.raymarching import backend as B
     from src.latent_nerf.raymarching.raymarching import _p, _stream

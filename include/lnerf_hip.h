@@ -921,6 +921,50 @@ int lnerf_shade_fd_orient_backward(const float *sigmas7, const float *rgbs7, int
                                    float T_thresh, const float *d_orient, float *dsigmas7, float *drgbs7,
                                    lnerf_stream_t stream);
 
+/* ---- distortion loss of the training renders (mip-NeRF 360's L_dist on the march's samples; optim.lambda_distortion),
+ * csrc/distortion.hip.  Additive to ABI 7.  Per ray, with the compositing weights w and the samples' mid-points m:
+ *   loss = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 dt_i
+ * in world units of t (no normalisation to [0, 1]) -- it pulls a ray's weight into one compact interval.  All arithmetic
+ * is f32 + - * in the order written here, no fused multiply-adds, except expf and the 64-lane scans (tolerance-checked).
+ * numpy restatement: tests/distortion_reference.py.
+ *
+ * lnerf_distortion_forward: one wavefront per ray, rays[r] = (id, off, cnt) as in the compositing; sigmas f32 [cap] are
+ *   the densities handed to the compositing (multiplied by density_scale already), deltas f32 [cap, 2] = (dt, t) of the
+ *   march (8-byte aligned; t increases along a span, sample s covers [t, t + dt]), 0 <= T_thresh < 1.  For sample
+ *   s = off + i, i < cnt, front to back, with t_0 = deltas[off][1]:
+ *     tau = sigma * dt, 64-lane inclusive scan of tau with a scalar carry between the chunks of 64,
+ *     excl = (the previous lane's inclusive sum; lane 0: 0) + carry -- never inc - tau --, T = expf(-excl),
+ *     e = expf(-tau),   alpha = 1 - e,   live = T >= T_thresh,   w = live ? alpha * T : 0
+ *   (lnerf_shade_fd_orient_forward's weight; no early stop: behind the cut only w is 0),
+ *     m = (t - t_0) + 0.5 * dt,
+ *     A = sum_{j<i} w_j,   B = sum_{j<i} (w_j * m_j):  64-lane inclusive scans of w and of w * m, each taken from the
+ *       previous lane (lane 0: 0) plus its scalar carry, the carries growing by lane 63's inclusive sum per chunk,
+ *     u = m * A - B,
+ *     loss[id] = sum_i w_i * (2 * u_i + (1.0f / 3.0f) * (w_i * dt_i))
+ *   (lane partials over i = lane, lane + 64, ..; then the wave's sum; one writer), and
+ *     ray_sums[id] = (A_tot, B_tot), f32 [n_ids, 2]: the two carries after the last chunk.
+ *   A ray with cnt = 0 writes loss[id] = 0 and ray_sums[id] = (0, 0).  Elements of ids no ray carries are not touched.
+ *
+ * lnerf_distortion_backward: the same launch shape, ONE forward sweep per ray; the weights are NOT detached.  d_loss
+ *   f32 [n_ids] is the gradient w.r.t. loss; loss and ray_sums are the forward's outputs.  With go = d_loss[id],
+ *   G_tot = loss[id] + loss[id]  (sum_i g_i w_i = 2 L: the loss is homogeneous of degree 2 in w), and w, m, u, e, T, live
+ *   recomputed as above, per sample
+ *     g = 2 * ((u + u) + (B_tot - m * A_tot)) + (2.0f / 3.0f) * (w * dt)          (= dL/dw_i, from
+ *         sum_{j>i} w_j = A_tot - A_i - w_i and likewise for B),
+ *     P = inclusive 64-lane scan of g * w plus its scalar carry (the carry IS lane 63's P),
+ *     dtau = live ? g * (T * e) - (G_tot - P) : 0                                 (= g_i T_{i+1} - sum_{j>i} g_j w_j),
+ *     dsigmas[s] = (go * dt) * dtau.
+ *   Every row of every span is written (zeros behind the cut); rows outside every span are not touched; a ray with
+ *   cnt = 0 writes nothing.  One writer per element, no atomics, no memset, the same bits on every run.  No gradient goes
+ *   to deltas.
+ * Both calls refuse, before any launch: N < 0, T_thresh outside [0, 1), and for N > 0 null pointers and deltas that are
+ * not 8-byte aligned. */
+int lnerf_distortion_forward(const float *sigmas, const float *deltas, const int32_t *rays, int64_t N, float T_thresh,
+                             float *loss, float *ray_sums, lnerf_stream_t stream);
+int lnerf_distortion_backward(const float *sigmas, const float *deltas, const int32_t *rays, int64_t N, float T_thresh,
+                              const float *d_loss, const float *loss, const float *ray_sums, float *dsigmas,
+                              lnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -94,6 +94,13 @@ class OptimConfig:
     lambda_tv: float = 0.0
     # lattice vertices the term samples per level and step (levels with fewer vertices are swept whole)
     tv_vertices: int = 65536
+    # weight of the distortion loss of mip-NeRF 360 on every training render (albedo and shaded, latent and latent_tune):
+    # mean over the rays of sum_ij w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 dt_i, the compositing weights w at the samples'
+    # mid-points m, in world units of the ray parameter -- it pulls a ray's weight into one compact interval, the
+    # training-time answer to semi-transparent fog in front of the object and floaters between camera and surface.  The
+    # gradient reaches the densities through the weights.  Any number of views and ranks (the term is local to a ray).
+    # mip-NeRF 360 uses 1e-2.  0: off, nothing changes
+    lambda_distortion: float = 0.0
 
 MESH_ATLASES = ("triangle", "charts")   # log.mesh_atlas (src/uv_atlas.py ATLAS_CHOICES)
 
@@ -173,6 +180,8 @@ class TrainConfig:
                              "shaded steps (it reads their finite-difference normal)" % (self.optim.lambda_orient,))
         if not self.optim.lambda_tv >= 0:
             raise ValueError("optim.lambda_tv must be >= 0, not %r" % (self.optim.lambda_tv,))
+        if not self.optim.lambda_distortion >= 0:
+            raise ValueError("optim.lambda_distortion must be >= 0, not %r" % (self.optim.lambda_distortion,))
         if not self.optim.tv_vertices >= 1:
             raise ValueError("optim.tv_vertices must be >= 1, not %r" % (self.optim.tv_vertices,))
         if self.log.mesh_atlas not in MESH_ATLASES:

@@ -162,6 +162,13 @@ class NeRFRenderer(nn.Module):
                              "differentiable here)")
         return shading == "normal", False
 
+    def _check_distortion(self, distortion, sampler="run_cuda"):
+        """Validates `distortion` before any tensor is touched."""
+        if distortion and (not self.training or sampler != "run_cuda"):
+            # the term is a training loss on the march's spans (deltas = (dt, t) with the occupancy skips)
+            raise ValueError("distortion=True needs training mode on the occupancy-marched renderer (got %s mode, %s)"
+                             % ("training" if self.training else "evaluation", sampler))
+
     def _check_fd_stride(self, cap):
         """The shaded render evaluates the field at 7 points per sample in ONE node: its level stride is 7 * cap."""
         if getattr(self, "precision", "f32") == "bf16" and 7 * int(cap) > (1 << 24):
@@ -305,7 +312,7 @@ class NeRFRenderer(nn.Module):
 
     def run_cuda(self, rays_o, rays_d, dt_gamma=0.0, bg_color=None, perturb=False, force_all_rays=False,
                  max_steps=1024, T_thresh=1e-4, prepared=None, shading="albedo", light_d=None, ambient_ratio=0.1,
-                 normal_eps=1e-2, orient=False, **kwargs):
+                 normal_eps=1e-2, orient=False, distortion=False, **kwargs):
         """rays_o, rays_d [B,N,3] -> dict(image [B,N,C], depth [B,N], weights_sum [B,N]).
         Training mode: march -> hash gather -> MLP -> composite, all on device, no host sync (latent_tune: the fused
         composite + decode, image in RGB);
@@ -323,7 +330,12 @@ class NeRFRenderer(nn.Module):
         orient=True (shaded training renders only): additionally 'loss_orient' [B,N], per ray sum_i w_i max(0, n_i . v)^2
         with the compositing weights w (detached) and the unit ray direction v -- the orientation regulariser, computed and
         differentiated inside the shade kernels (raymarching.shade_fd(orient=...)); image, depth and weights_sum keep
-        their bits."""
+        their bits.
+        distortion=True (training renders of every kind): additionally 'loss_distortion' [B,N], per ray the distortion
+        loss of mip-NeRF 360, sum_ij w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 dt_i on the march's samples, with the
+        compositing weights w NOT detached (raymarching.distortion_loss on the very sigmas the compositing gets); image,
+        depth and weights_sum keep their bits."""
+        self._check_distortion(distortion)
         shade_normal, shaded = self._check_shading(shading, light_d, orient=orient)
         C = 3 if shade_normal else self.img_dims
         decode = self.tuned and not shade_normal   # composite 4 latent channels, decode per ray (bg_color is RGB)
@@ -362,6 +374,8 @@ class NeRFRenderer(nn.Module):
             else:
                 sigmas, rgbs = self.field(march.xyzs, cap, m_dev, cap)
             sigmas = self.density_scale * sigmas if self.density_scale != 1.0 else sigmas
+            if distortion:
+                results["loss_distortion"] = rm.distortion_loss(sigmas, march.deltas, march.rays, T_thresh, N).view(*prefix)
             if decode:
                 weights_sum, depth, image, _ = rm.composite_rays_train_decode(sigmas, rgbs, march.deltas, march.rays,
                                                                              self.decoder, T_thresh, bg)
@@ -442,6 +456,7 @@ class NeRFRenderer(nn.Module):
         kernels and composited with the same HIP kernels (every ray owns a fixed span of samples).
         shading="normal" (evaluation only): as in run_cuda; the shaded renders ('lambertian' / 'textureless') are
         run_cuda's alone."""
+        self._check_distortion(kwargs.get("distortion", False), sampler="run")
         shade_normal, _ = self._check_shading(shading, kwargs.get("light_d"), sampler="run",
                                               orient=kwargs.get("orient", False))
         prefix = rays_o.shape[:-1]

@@ -485,6 +485,51 @@ def shade_fd(sigmas7, rgbs7, rays, shade, rays_per_view, eps, orient=None):
     return _ShadeFD.apply(sigmas7, rgbs7, rays, shade, rays_per_view, eps, orient)
 
 
+# ------------------------------------------------------------------------------ distortion loss
+class _DistortionLoss(torch.autograd.Function):
+    """lnerf_distortion_forward / _backward: one launch each way."""
+
+    @staticmethod
+    def forward(ctx, sigmas, deltas, rays, T_thresh, n_ids):
+        sigmas = sigmas.contiguous()
+        N, dev = rays.shape[0], sigmas.device
+        if deltas.dim() != 2 or deltas.shape[1] != 2 or deltas.shape[0] < sigmas.shape[0]:
+            raise ValueError("distortion_loss: deltas must be the march's [>= %d, 2] (got %s)"
+                             % (sigmas.shape[0], tuple(deltas.shape)))
+        if N > n_ids:
+            raise ValueError("distortion_loss: n_ids = %d is less than the %d rays" % (n_ids, N))
+        # every ray of the table writes its own element (0 for an empty span); with fewer rays than ids the rest is 0
+        loss = (torch.empty if N == n_ids else torch.zeros)(n_ids, device=dev, dtype=torch.float32)
+        ray_sums = torch.empty(n_ids, 2, device=dev, dtype=torch.float32)     # (read back by the rays that wrote them)
+        _b.call("lnerf_distortion_forward", _chk(sigmas, "sigmas"), _chk(deltas, "deltas"),
+                _chk(rays, "rays", torch.int32), N, float(T_thresh), _p(loss), _p(ray_sums), _stream())
+        ctx.save_for_backward(sigmas, deltas, rays, loss, ray_sums)
+        ctx.set_materialize_grads(False)
+        ctx.T_thresh = float(T_thresh)
+        return loss
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        if d_loss is None:
+            return None, None, None, None, None
+        sigmas, deltas, rays, loss, ray_sums = ctx.saved_tensors
+        d_loss = d_loss.contiguous()
+        # every row below the march's counter lies in a ray's span and is written; the rows above are read by nobody
+        dsigmas = torch.empty_like(sigmas)
+        _b.call("lnerf_distortion_backward", _p(sigmas), _p(deltas), _p(rays), rays.shape[0], ctx.T_thresh,
+                _chk(d_loss, "d_loss"), _p(loss), _p(ray_sums), _p(dsigmas), _stream())
+        return dsigmas, None, None, None, None
+
+
+def distortion_loss(sigmas, deltas, rays, T_thresh=1e-4, n_ids=None):
+    """The distortion loss of mip-NeRF 360 per ray (lnerf_distortion_forward / _backward, contract in include/lnerf_hip.h):
+    sigmas [cap] (the densities the compositing gets, scaled already), deltas [cap,2] = (dt, t), rays int32 [N,3] =
+    (id, offset, count) -> loss [n_ids] (n_ids defaults to N; ids of no ray hold 0),
+    loss[id] = sum_ij w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 dt_i with the compositing weights w (NOT detached: sigmas
+    receives the gradient) and the mid-points m = t + dt / 2, in world units of t.  One autograd node; there is no CPU path."""
+    return _DistortionLoss.apply(sigmas, deltas, rays, T_thresh, rays.shape[0] if n_ids is None else int(n_ids))
+
+
 # ------------------------------------------------------------------------------ mesh export
 def marching_cubes(volume, iso, lo, hi, close_boundary=True):
     """Iso-surface of a dense f32 volume [nx, ny, nz] (z fastest) on the GPU (lnerf_marching_cubes, include/lnerf_hip.h).

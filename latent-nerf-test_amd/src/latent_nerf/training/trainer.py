@@ -126,6 +126,10 @@ class Trainer:
         self._orient_const = {}
         if self._lambda_orient() > 0:
             self._orient_grad((n_views, cfg.render.train_h * cfg.render.train_w))
+        # optim.lambda_distortion: the same pattern for the per-ray loss_distortion of every training render
+        self._distortion_const = {}
+        if self._lambda_distortion() > 0:
+            self._distortion_grad((n_views, cfg.render.train_h * cfg.render.train_w))
         self.past_checkpoints = []
         if cfg.optim.ckpt is not None:
             self.load_checkpoint(cfg.optim.ckpt, model_only=True)
@@ -214,15 +218,33 @@ class Trainer:
             self._orient_const[key] = g
         return g
 
+    def _lambda_distortion(self):
+        return float(getattr(self.cfg.optim, "lambda_distortion", 0.0))
+
+    def _distortion_grad(self, shape):
+        """d(lambda_distortion * mean(loss_distortion)) / d(loss_distortion): lambda / (number of rays of the render) on
+        every ray, as _orient_grad.  One cached tensor per shape, read-only."""
+        key = tuple(int(v) for v in shape)
+        g = self._distortion_const.get(key)
+        if g is None:
+            g = torch.full(key, self._lambda_distortion() / max(math.prod(key), 1), device=self.device,
+                           dtype=torch.float32)
+            self._distortion_const[key] = g
+        return g
+
     def _backward(self, out, pred, grad, grad_ws=None):
         """SDS: d(loss)/d(pred) = grad (src/latent_paint_mesh/training/trainer.py:657-658).  The sparsity term's gradient
         w.r.t. weights_sum comes from one HIP launch (`grad_ws` when the caller already has it) and enters the
         compositing backward beside it; the orientation term of a shaded step enters the shade backward as a constant
-        per-ray gradient; the shape term (a function of the samples) goes through autograd."""
+        per-ray gradient, and so does the distortion term into its own node (its gradient joins the compositing's on the
+        densities); the shape term (a function of the samples) goes through autograd."""
         tensors, grads = [pred], [grad]
         if "loss_orient" in out:
             tensors.append(out["loss_orient"])
             grads.append(self._orient_grad(out["loss_orient"].shape))
+        if "loss_distortion" in out:
+            tensors.append(out["loss_distortion"])
+            grads.append(self._distortion_grad(out["loss_distortion"].shape))
         if self.cfg.optim.lambda_sparsity > 0:
             tensors.append(out["weights_sum"])
             grads.append(grad_ws if grad_ws is not None
@@ -240,6 +262,8 @@ class Trainer:
             loss = loss + self.cfg.optim.lambda_sparsity * sparsity_loss(out["weights_sum"].detach())
         if "loss_orient" in out:
             loss = loss + self._lambda_orient() * out["loss_orient"].detach().mean()
+        if "loss_distortion" in out:
+            loss = loss + self._lambda_distortion() * out["loss_distortion"].detach().mean()
         return loss
 
     def train_render(self, data):
@@ -249,7 +273,7 @@ class Trainer:
         else:
             H, W = data["H"], data["W"]
             out = self.nerf.render(data["rays_o"], data["rays_d"], staged=False, perturb=True, bg_color=None,
-                                   force_all_rays=True)
+                                   force_all_rays=True, **self._distortion_args())
             pred = out["image"].reshape(1, H, W, -1).permute(0, 3, 1, 2).contiguous()
         grad = self._guidance_grad(pred, [int(d) for d in data["dir"]])
         self._backward(out, pred, grad)
@@ -284,11 +308,16 @@ class Trainer:
         """Keywords of the step's render: a shaded step reads its per-view record (light, ambient, textureless flag) from
         the static buffers, so the kind inside the shaded form is DATA -- one captured graph serves both kinds."""
         if not self._shaded:
-            return {}
-        args = {"shading": "lambertian", "light_d": self._static_buffers()["shade"]}
+            return self._distortion_args()
+        args = {"shading": "lambertian", "light_d": self._static_buffers()["shade"], **self._distortion_args()}
         if self._lambda_orient() > 0:
             args["orient"] = True       # (loss_orient in the render's dict: _backward picks it up)
         return args
+
+    def _distortion_args(self):
+        """Keyword of EVERY training render, plain or shaded, when optim.lambda_distortion > 0 (loss_distortion in the
+        render's dict: _backward picks it up); nothing otherwise."""
+        return {"distortion": True} if self._lambda_distortion() > 0 else {}
 
     # ---- one step on this rank's views: camera upload -> batched render -> guidance -> backward -> exchange -> optimiser
     def _graph_ready(self):

@@ -965,6 +965,64 @@ int lnerf_distortion_backward(const float *sigmas, const float *deltas, const in
                               const float *d_loss, const float *loss, const float *ray_sums, float *dsigmas,
                               lnerf_stream_t stream);
 
+/* ---- composited normal image of the shaded training renders and the 2D normal-smoothness stencil (the upstream
+ * DreamFusion-style trainers' lambda_2d_normal_smooth; optim.lambda_normal_smooth), csrc/normal_image.hip.  Additive to
+ * ABI 7.  Per ray:  normal_image = sum_i w_i n_i  -- the finite-difference normals of the samples under the compositing
+ * weights; per pixel of an image: the squared differences to the right and the lower neighbour.  All arithmetic is f32
+ * + - * / sqrt in the order written here, no fused multiply-adds, except expf and the 64-lane scans (tolerance-checked).
+ * numpy restatement: tests/normal_image_reference.py.
+ *
+ * lnerf_normal_image_forward: one wavefront per ray, rays[r] = (id, off, cnt) as in the compositing; sigmas7 f32 [7 cap]
+ *   are the UNSCALED densities at lnerf_fd_points' rows, deltas f32 [cap, 2] = (dt, t) of the march (8-byte aligned),
+ *   density_scale >= 0, 0 <= T_thresh < 1, normal_image f32 [n_ids, 3].  For sample s = off + i, i < cnt, with
+ *   sg = sigmas7[7 s .. 7 s + 6]:
+ *     n of lnerf_shade_fd_forward:  g_a = (sg[1 + 2 a] - sg[2 + 2 a]) * inv_2eps,   s2 = (g_x g_x + g_y g_y) + g_z g_z,
+ *       r = 1 / sqrt(fmax(s2, 1e-20)),   n_a = -(g_a r), a NaN component becomes 0;
+ *     w of lnerf_shade_fd_orient_forward on sigma' = density_scale * sg[0]:  tau = sigma' * dt (dt = deltas[s][0]), 64-lane
+ *       inclusive scan of tau with a scalar carry between the chunks of 64, excl = (the previous lane's inclusive sum;
+ *       lane 0: 0) + carry -- never inc - tau --, T = expf(-excl), e = expf(-tau), alpha = 1 - e, live = T >= T_thresh,
+ *       w = live ? alpha * T : 0  (no early stop: behind the cut only w is 0);
+ *     normal_image[id][a] = sum_i w_i * n_{i,a}   (lane partials over i = lane, lane + 64, ..; then the wave's sum; one
+ *       writer).
+ *   A ray with cnt = 0 writes (0, 0, 0).  Elements of ids no ray carries are not touched.
+ *
+ * lnerf_normal_image_backward: the same launch shape, ONE forward sweep per ray; the weights are NOT detached (upstream
+ *   composites the normals with live weights).  d_normal_image f32 [n_ids, 3] is the gradient w.r.t. normal_image,
+ *   normal_image the forward's output, dsigmas7 f32 [7 cap].  With dN = d_normal_image[id], N = normal_image[id], and n, s2,
+ *   r, w, T, e, live recomputed as above, per sample
+ *     g = (n_x dN_x + n_y dN_y) + n_z dN_z                                         (= dL/dw_i),
+ *     G_tot = (N_x dN_x + N_y dN_y) + N_z dN_z                                     (= sum_i g_i w_i: N is linear in w),
+ *     P = inclusive 64-lane scan of g * w plus its scalar carry (the carry IS lane 63's P),
+ *     dtau = live ? g * (T * e) - (G_tot - P) : 0                                  (= g_i T_{i+1} - sum_{j>i} g_j w_j),
+ *     dsigmas7[7 s] = (density_scale * dt) * dtau,
+ *     dn_a = w * dN_a,   q = (n_x dn_x + n_y dn_y) + n_z dn_z,   dg_a = -(r * (s2 > 1e-20 ? dn_a - n_a q : dn_a)),
+ *     dsigmas7[7 s + 1 + 2 a] = dg_a * inv_2eps,   dsigmas7[7 s + 2 + 2 a] = -(dg_a * inv_2eps)
+ *   (the normalisation backward of lnerf_shade_fd_backward).  All seven rows of every span are written (behind the cut:
+ *   zeros); rows outside every span are not touched; a ray with cnt = 0 writes nothing.  One writer per element, no
+ *   atomics, no memset, the same bits on every run.  No gradient goes to deltas.
+ *
+ * lnerf_image_smooth_forward: img f32 [B, H, W, C], 1 <= C <= 4, one lane per pixel p = (b, y, x) -> loss f32 [B, H, W, 2]:
+ *     loss[p][0] = x + 1 < W ? sum_c (img[b, y, x + 1, c] - img[p][c])^2 : 0,
+ *     loss[p][1] = y + 1 < H ? sum_c (img[b, y + 1, x, c] - img[p][c])^2 : 0     (sums from c = 0 upward).
+ * lnerf_image_smooth_backward: gather form, d_loss f32 [B, H, W, 2] -> d_img f32 [B, H, W, C]; per pixel and channel, from
+ *   acc = 0 and in this order:
+ *     x + 1 < W:  acc = acc - (2 * d_loss[p][0]) * (img[b, y, x + 1, c] - img[p][c])            (own-h)
+ *     y + 1 < H:  acc = acc - (2 * d_loss[p][1]) * (img[b, y + 1, x, c] - img[p][c])            (own-v)
+ *     x > 0:      acc = acc + (2 * d_loss[b, y, x - 1][0]) * (img[p][c] - img[b, y, x - 1, c])  (left)
+ *     y > 0:      acc = acc + (2 * d_loss[b, y - 1, x][1]) * (img[p][c] - img[b, y - 1, x, c])  (up)
+ *     d_img[p][c] = acc.
+ *   Every element of loss / d_img is written; B, H or W = 0 launches nothing.
+ * All four calls refuse, before any launch: negative sizes, T_thresh outside [0, 1), density_scale < 0, C outside 1..4, and
+ * for a non-empty call null pointers and deltas that are not 8-byte aligned. */
+int lnerf_normal_image_forward(const float *sigmas7, const float *deltas, const int32_t *rays, int64_t N, float inv_2eps,
+                               float density_scale, float T_thresh, float *normal_image, lnerf_stream_t stream);
+int lnerf_normal_image_backward(const float *sigmas7, const float *deltas, const int32_t *rays, int64_t N, float inv_2eps,
+                                float density_scale, float T_thresh, const float *d_normal_image, const float *normal_image,
+                                float *dsigmas7, lnerf_stream_t stream);
+int lnerf_image_smooth_forward(const float *img, int B, int H, int W, int C, float *loss, lnerf_stream_t stream);
+int lnerf_image_smooth_backward(const float *img, int B, int H, int W, int C, const float *d_loss, float *d_img,
+                                lnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

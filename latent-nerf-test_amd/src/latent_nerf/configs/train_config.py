@@ -101,6 +101,16 @@ class OptimConfig:
     # gradient reaches the densities through the weights.  Any number of views and ranks (the term is local to a ray).
     # mip-NeRF 360 uses 1e-2.  0: off, nothing changes
     lambda_distortion: float = 0.0
+    # weight of the 2D normal-smoothness term on the shaded steps of optim.start_shading_iter (the upstream DreamFusion-style
+    # trainers' lambda_2d_normal_smooth): the finite-difference normals of a shaded render are composited into a per-pixel
+    # normal image [B,H,W,3] (compositing weights NOT detached) and the squared differences between neighbouring pixels
+    # are penalised,
+    #   lambda * ( sum_h / (B * H * (W - 1) * 3) + sum_v / (B * (H - 1) * W * 3) ),
+    # sum_h / sum_v over the horizontal / vertical pixel pairs and the three components -- against the high-frequency
+    # bumps ("orange peel") that textureless shading brings out.  The plain-albedo steps of a shaded schedule do not have
+    # it (they compute no normal).  Any number of views and ranks (the term is local to a view's image).  Upstream's
+    # weight was not available to copy: no value is recommended here.  0: off, nothing changes
+    lambda_normal_smooth: float = 0.0
 
 MESH_ATLASES = ("triangle", "charts")   # log.mesh_atlas (src/uv_atlas.py ATLAS_CHOICES)
 
@@ -178,6 +188,12 @@ class TrainConfig:
         if self.optim.lambda_orient > 0 and self.optim.start_shading_iter is None:
             raise ValueError("optim.lambda_orient = %r needs optim.start_shading_iter: the orientation term exists only on "
                              "shaded steps (it reads their finite-difference normal)" % (self.optim.lambda_orient,))
+        if not self.optim.lambda_normal_smooth >= 0:
+            raise ValueError("optim.lambda_normal_smooth must be >= 0, not %r" % (self.optim.lambda_normal_smooth,))
+        if self.optim.lambda_normal_smooth > 0 and self.optim.start_shading_iter is None:
+            raise ValueError("optim.lambda_normal_smooth = %r needs optim.start_shading_iter: the term acts on the "
+                             "shaded steps (it composites their finite-difference normal)"
+                             % (self.optim.lambda_normal_smooth,))
         if not self.optim.lambda_tv >= 0:
             raise ValueError("optim.lambda_tv must be >= 0, not %r" % (self.optim.lambda_tv,))
         if not self.optim.lambda_distortion >= 0:

@@ -132,8 +132,15 @@ class NeRFRenderer(nn.Module):
 
     SHADED = ("lambertian", "textureless")
 
-    def _check_shading(self, shading, light_d=None, sampler="run_cuda", orient=False):
-        """Validates `shading` (and `orient`) before any tensor is touched.  -> (normal render?, shaded render?)."""
+    def _check_shading(self, shading, light_d=None, sampler="run_cuda", orient=False, normal_image=False):
+        """Validates `shading` (and `orient`, `normal_image`) before any tensor is touched.  -> (normal render?, shaded
+        render?)."""
+        if normal_image and (shading not in self.SHADED or not self.training or sampler != "run_cuda" or self.tuned):
+            # the image composites the finite-difference normal of a shaded TRAINING render on the march's spans
+            raise ValueError("normal_image=True needs shading='lambertian' / 'textureless' in training mode on the "
+                             "occupancy-marched renderer, not latent_tune (got shading=%r, %s mode, %s%s)"
+                             % (shading, "training" if self.training else "evaluation", sampler,
+                                ", latent_tune" if self.tuned else ""))
         if orient and (shading not in self.SHADED or not self.training or sampler != "run_cuda"):
             # the term reads the finite-difference normal of a shaded TRAINING render and the march's spans
             raise ValueError("orient=True needs shading='lambertian' / 'textureless' in training mode on the "
@@ -312,7 +319,7 @@ class NeRFRenderer(nn.Module):
 
     def run_cuda(self, rays_o, rays_d, dt_gamma=0.0, bg_color=None, perturb=False, force_all_rays=False,
                  max_steps=1024, T_thresh=1e-4, prepared=None, shading="albedo", light_d=None, ambient_ratio=0.1,
-                 normal_eps=1e-2, orient=False, distortion=False, **kwargs):
+                 normal_eps=1e-2, orient=False, distortion=False, normal_image=False, **kwargs):
         """rays_o, rays_d [B,N,3] -> dict(image [B,N,C], depth [B,N], weights_sum [B,N]).
         Training mode: march -> hash gather -> MLP -> composite, all on device, no host sync (latent_tune: the fused
         composite + decode, image in RGB);
@@ -334,9 +341,13 @@ class NeRFRenderer(nn.Module):
         distortion=True (training renders of every kind): additionally 'loss_distortion' [B,N], per ray the distortion
         loss of mip-NeRF 360, sum_ij w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 dt_i on the march's samples, with the
         compositing weights w NOT detached (raymarching.distortion_loss on the very sigmas the compositing gets); image,
-        depth and weights_sum keep their bits."""
+        depth and weights_sum keep their bits.
+        normal_image=True (shaded training renders only): additionally 'normal_image' [B,N,3], per ray sum_i w_i n_i, the
+        finite-difference normals of the samples under the compositing weights (NOT detached) -- raymarching.normal_image
+        on the very sigmas7 the shade node gets; differentiable, the input of the 2D normal-smoothness term
+        (raymarching.image_smooth).  image, depth, weights_sum, loss_orient and loss_distortion keep their bits."""
         self._check_distortion(distortion)
-        shade_normal, shaded = self._check_shading(shading, light_d, orient=orient)
+        shade_normal, shaded = self._check_shading(shading, light_d, orient=orient, normal_image=normal_image)
         C = 3 if shade_normal else self.img_dims
         decode = self.tuned and not shade_normal   # composite 4 latent channels, decode per ray (bg_color is RGB)
         results = {}
@@ -371,6 +382,9 @@ class NeRFRenderer(nn.Module):
                     results["loss_orient"] = loss_orient.view(*prefix)
                 else:
                     sigmas, rgbs = rm.shade_fd(sigmas7, rgbs7, march.rays, shade, max(N // n_views, 1), normal_eps)
+                if normal_image:
+                    results["normal_image"] = rm.normal_image(sigmas7, march.deltas, march.rays, N, normal_eps,
+                                                              self.density_scale, T_thresh).view(*prefix, 3)
             else:
                 sigmas, rgbs = self.field(march.xyzs, cap, m_dev, cap)
             sigmas = self.density_scale * sigmas if self.density_scale != 1.0 else sigmas
@@ -458,7 +472,8 @@ class NeRFRenderer(nn.Module):
         run_cuda's alone."""
         self._check_distortion(kwargs.get("distortion", False), sampler="run")
         shade_normal, _ = self._check_shading(shading, kwargs.get("light_d"), sampler="run",
-                                              orient=kwargs.get("orient", False))
+                                              orient=kwargs.get("orient", False),
+                                              normal_image=kwargs.get("normal_image", False))
         prefix = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3).float()
         rays_d = rays_d.contiguous().view(-1, 3).float()

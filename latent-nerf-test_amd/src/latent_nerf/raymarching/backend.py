@@ -159,6 +159,10 @@ _SIGNATURES = {
     "lnerf_shade_fd_orient_backward": [_P, _P, _I, _P, _L, _I, _P, _I, _F, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P],
     "lnerf_distortion_forward": [_P, _P, _P, _L, _F, _P, _P, _P],
     "lnerf_distortion_backward": [_P, _P, _P, _L, _F, _P, _P, _P, _P, _P],
+    "lnerf_normal_image_forward": [_P, _P, _P, _L, _F, _F, _F, _P, _P],
+    "lnerf_normal_image_backward": [_P, _P, _P, _L, _F, _F, _F, _P, _P, _P, _P],
+    "lnerf_image_smooth_forward": [_P, _I, _I, _I, _I, _P, _P],
+    "lnerf_image_smooth_backward": [_P, _I, _I, _I, _I, _P, _P, _P],
     "lnerf_step_tail": [_I, _I, _P, _P, _P, _L, _I, _P, _Z, _P, _P, _P, _P, _P, _F, _P, _Z, _I, _I, _P, _P, _P, _F, _P,
                         _F, _F, _F, _I, _P, _F, _I, _P],
 }

@@ -530,6 +530,91 @@ def distortion_loss(sigmas, deltas, rays, T_thresh=1e-4, n_ids=None):
     return _DistortionLoss.apply(sigmas, deltas, rays, T_thresh, rays.shape[0] if n_ids is None else int(n_ids))
 
 
+# ------------------------------------------------------------------------------ composited normal image, 2D smoothness
+class _NormalImage(torch.autograd.Function):
+    """lnerf_normal_image_forward / _backward: one launch each way."""
+
+    @staticmethod
+    def forward(ctx, sigmas7, deltas, rays, n_ids, normal_eps, density_scale, T_thresh):
+        sigmas7 = sigmas7.contiguous()
+        N, dev = rays.shape[0], sigmas7.device
+        if sigmas7.dim() != 1 or sigmas7.shape[0] % 7 != 0:
+            raise ValueError("normal_image: sigmas7 [7 cap] must hold seven rows per sample (got %s)"
+                             % (tuple(sigmas7.shape),))
+        cap = sigmas7.shape[0] // 7
+        if deltas.dim() != 2 or deltas.shape[1] != 2 or deltas.shape[0] < cap:
+            raise ValueError("normal_image: deltas must be the march's [>= %d, 2] (got %s)" % (cap, tuple(deltas.shape)))
+        if N > n_ids:
+            raise ValueError("normal_image: n_ids = %d is less than the %d rays" % (n_ids, N))
+        inv_2eps = 1.0 / (2.0 * float(normal_eps))
+        # every ray of the table writes its own row (zeros for an empty span); with fewer rays than ids the rest is 0
+        image = (torch.empty if N == n_ids else torch.zeros)(n_ids, 3, device=dev, dtype=torch.float32)
+        _b.call("lnerf_normal_image_forward", _chk(sigmas7, "sigmas7"), _chk(deltas, "deltas"),
+                _chk(rays, "rays", torch.int32), N, inv_2eps, float(density_scale), float(T_thresh), _p(image), _stream())
+        ctx.save_for_backward(sigmas7, deltas, rays, image)
+        ctx.set_materialize_grads(False)
+        ctx.meta = (inv_2eps, float(density_scale), float(T_thresh))
+        return image
+
+    @staticmethod
+    def backward(ctx, d_image):
+        if d_image is None:
+            return (None,) * 7
+        sigmas7, deltas, rays, image = ctx.saved_tensors
+        d_image = d_image.contiguous()
+        # the kernel writes the seven rows of every span; the rows outside every span are zeros
+        dsigmas7 = torch.zeros_like(sigmas7)
+        _b.call("lnerf_normal_image_backward", _p(sigmas7), _p(deltas), _p(rays), rays.shape[0], *ctx.meta,
+                _chk(d_image, "d_normal_image"), _p(image), _p(dsigmas7), _stream())
+        return (dsigmas7,) + (None,) * 6
+
+
+def normal_image(sigmas7, deltas, rays, n_ids=None, normal_eps=1e-2, density_scale=1.0, T_thresh=1e-4):
+    """The composited normal of every ray (lnerf_normal_image_forward / _backward, contract in include/lnerf_hip.h):
+    sigmas7 [7 cap] (the unscaled densities of the field at fd_points' rows: what shade_fd gets), deltas [cap,2] = (dt, t),
+    rays int32 [N,3] = (id, offset, count) -> normal_image [n_ids, 3] (n_ids defaults to N; ids of no ray hold 0),
+    normal_image[id] = sum_i w_i n_i with shade_fd's finite-difference normals n (distance normal_eps) and the compositing
+    weights w on density_scale * sigma (NOT detached: sigmas7 receives the gradient through the weights and through the
+    normals; rows outside every span get 0).  One autograd node; there is no CPU path."""
+    return _NormalImage.apply(sigmas7, deltas, rays, rays.shape[0] if n_ids is None else int(n_ids), normal_eps,
+                              density_scale, T_thresh)
+
+
+class _ImageSmooth(torch.autograd.Function):
+    """lnerf_image_smooth_forward / _backward: one launch each way."""
+
+    @staticmethod
+    def forward(ctx, img):
+        if img.dim() != 4 or not 1 <= img.shape[3] <= 4:
+            raise ValueError("image_smooth: img must be [B,H,W,C] with 1 <= C <= 4 (got %s)" % (tuple(img.shape),))
+        img = img.contiguous()
+        B, H, W, C = img.shape
+        loss = torch.empty(B, H, W, 2, device=img.device, dtype=torch.float32)
+        _b.call("lnerf_image_smooth_forward", _chk(img, "img"), B, H, W, C, _p(loss), _stream())
+        ctx.save_for_backward(img)
+        ctx.set_materialize_grads(False)
+        return loss
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        if d_loss is None:
+            return None
+        img, = ctx.saved_tensors
+        B, H, W, C = img.shape
+        d_loss = d_loss.contiguous()
+        d_img = torch.empty_like(img)          # (every element is written)
+        _b.call("lnerf_image_smooth_backward", _p(img), B, H, W, C, _chk(d_loss, "d_loss"), _p(d_img), _stream())
+        return d_img
+
+
+def image_smooth(img):
+    """Squared differences between neighbouring pixels (lnerf_image_smooth_forward / _backward, contract in
+    include/lnerf_hip.h): img f32 [B,H,W,C], 1 <= C <= 4 -> loss [B,H,W,2], loss[b,y,x,0] = sum_c (img[b,y,x+1,c] -
+    img[b,y,x,c])^2 (0 in the last column), loss[b,y,x,1] the same toward y + 1 (0 in the last row).  One autograd node;
+    there is no CPU path."""
+    return _ImageSmooth.apply(img)
+
+
 # ------------------------------------------------------------------------------ mesh export
 def marching_cubes(volume, iso, lo, hi, close_boundary=True):
     """Iso-surface of a dense f32 volume [nx, ny, nz] (z fastest) on the GPU (lnerf_marching_cubes, include/lnerf_hip.h).

@@ -130,6 +130,11 @@ class Trainer:
         self._distortion_const = {}
         if self._lambda_distortion() > 0:
             self._distortion_grad((n_views, cfg.render.train_h * cfg.render.train_w))
+        # optim.lambda_normal_smooth: the gradient w.r.t. image_smooth's [B,H,W,2] pair sums of a shaded render's normal
+        # image is a constant too, one value per channel
+        self._normal_smooth_const = {}
+        if self._lambda_normal_smooth() > 0:
+            self._normal_smooth_grad((n_views, cfg.render.train_h, cfg.render.train_w, 2))
         self.past_checkpoints = []
         if cfg.optim.ckpt is not None:
             self.load_checkpoint(cfg.optim.ckpt, model_only=True)
@@ -232,12 +237,43 @@ class Trainer:
             self._distortion_const[key] = g
         return g
 
+    def _lambda_normal_smooth(self):
+        return float(getattr(self.cfg.optim, "lambda_normal_smooth", 0.0))
+
+    def _normal_smooth_grad(self, shape):
+        """d(lambda_normal_smooth * (sum_h / (B H (W - 1) 3) + sum_v / (B (H - 1) W 3))) / d(the [B,H,W,2] pair sums of
+        image_smooth): lambda / (B H (W - 1) 3) on channel 0, lambda / (B (H - 1) W 3) on channel 1, 0 where an image has
+        no such pair (W = 1 / H = 1).  One cached tensor per shape, read-only."""
+        key = tuple(int(v) for v in shape)
+        g = self._normal_smooth_const.get(key)
+        if g is None:
+            B, H, W, _ = key
+            lam, n_h, n_v = self._lambda_normal_smooth(), B * H * (W - 1) * 3, B * (H - 1) * W * 3
+            g = torch.empty(key, device=self.device, dtype=torch.float32)
+            g[..., 0] = lam / n_h if n_h > 0 else 0.0
+            g[..., 1] = lam / n_v if n_v > 0 else 0.0
+            self._normal_smooth_const[key] = g
+        return g
+
+    def _normal_smooth(self, out):
+        """The [B,H,W,2] pair sums of a shaded render's normal image (raymarching.image_smooth), built once per render's
+        dict; None for a render without 'normal_image'."""
+        if "normal_image" not in out:
+            return None
+        if "loss_normal_smooth" not in out:
+            from ..raymarching import image_smooth
+            r = self.cfg.render
+            out["loss_normal_smooth"] = image_smooth(out["normal_image"].reshape(-1, r.train_h, r.train_w, 3))
+        return out["loss_normal_smooth"]
+
     def _backward(self, out, pred, grad, grad_ws=None):
         """SDS: d(loss)/d(pred) = grad (src/latent_paint_mesh/training/trainer.py:657-658).  The sparsity term's gradient
         w.r.t. weights_sum comes from one HIP launch (`grad_ws` when the caller already has it) and enters the
         compositing backward beside it; the orientation term of a shaded step enters the shade backward as a constant
         per-ray gradient, and so does the distortion term into its own node (its gradient joins the compositing's on the
-        densities); the shape term (a function of the samples) goes through autograd."""
+        densities); the 2D normal-smoothness term of a shaded step enters image_smooth's node with its constant gradient
+        and reaches the densities through the normal image; the shape term (a function of the samples) goes through
+        autograd."""
         tensors, grads = [pred], [grad]
         if "loss_orient" in out:
             tensors.append(out["loss_orient"])
@@ -245,6 +281,10 @@ class Trainer:
         if "loss_distortion" in out:
             tensors.append(out["loss_distortion"])
             grads.append(self._distortion_grad(out["loss_distortion"].shape))
+        pairs = self._normal_smooth(out)
+        if pairs is not None:
+            tensors.append(pairs)
+            grads.append(self._normal_smooth_grad(pairs.shape))
         if self.cfg.optim.lambda_sparsity > 0:
             tensors.append(out["weights_sum"])
             grads.append(grad_ws if grad_ws is not None
@@ -264,6 +304,9 @@ class Trainer:
             loss = loss + self._lambda_orient() * out["loss_orient"].detach().mean()
         if "loss_distortion" in out:
             loss = loss + self._lambda_distortion() * out["loss_distortion"].detach().mean()
+        pairs = self._normal_smooth(out)
+        if pairs is not None:
+            loss = loss + (pairs.detach() * self._normal_smooth_grad(pairs.shape)).sum()
         return loss
 
     def train_render(self, data):
@@ -312,6 +355,8 @@ class Trainer:
         args = {"shading": "lambertian", "light_d": self._static_buffers()["shade"], **self._distortion_args()}
         if self._lambda_orient() > 0:
             args["orient"] = True       # (loss_orient in the render's dict: _backward picks it up)
+        if self._lambda_normal_smooth() > 0:
+            args["normal_image"] = True     # (normal_image in the render's dict: _backward builds the term on it)
         return args
 
     def _distortion_args(self):

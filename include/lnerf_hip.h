@@ -524,6 +524,58 @@ int lnerf_texture_map_forward(const float *uv, const int32_t *face_idx, const fl
 int lnerf_texture_map_backward(const float *uv, const int32_t *face_idx, const float *dout, int n_pixels, int C, int R,
                                int mode, float *dtexture, lnerf_stream_t stream);
 
+/* ---- Mip-mapped texture lookup (`guide.texture_interpolation_mode mipmap`; csrc/texmip.hip).  Additive to ABI 7; the
+ * three point lookups above are unchanged.  The reference has no counterpart (kaolin's texture_mapping is a point
+ * lookup): this is the trilinear filter of rasteriser-based texture optimisers, isotropic, the longer of the two
+ * screen-space UV derivatives choosing the level.  f32, every operation rounded on its own (no fused multiply-add).
+ *
+ * lnerf_uv_footprint: rho [B*H*W] = the length, in UV units, of the longer of the two screen-space UV derivative
+ *   vectors per one-pixel step; 0 where face_idx < 0.  face_idx [B*H*W], face_xy [B,F,3,2] and face_z [B,F,3] are what
+ *   lnerf_raster_prepare_batch / lnerf_rasterize_batch wrote; face_uv [F,3,2] = the per-face-vertex UVs (u_k, v_k).
+ *   The definition is analytic on the winning face, not a difference of neighbouring pixels (those break at face
+ *   borders and silhouettes).  With the pixel centre (px, py), area, e0, e1 of lnerf_rasterize:
+ *     inv = 1 / area;  w0 = e0 * inv;  w1 = e1 * inv;  w2 = 1 - w0 - w1;
+ *     q_k = w_k / z_k;  qs = q0 + q1 + q2;  z = 1 / qs;  bw_k = q_k * z            (the rasteriser's barycentrics)
+ *     dw0/dpx = (y1 - y2) * inv   dw0/dpy = (x2 - x1) * inv
+ *     dw1/dpx = (y2 - y0) * inv   dw1/dpy = (x0 - x2) * inv      dw2 = -dw0 - dw1
+ *     a_k = dw_k / z_k;  s = a0 + a1 + a2;  dbw_k = (a_k - bw_k * s) * z           (per axis)
+ *     du = u0 * dbw0 + u1 * dbw1 + u2 * dbw2,  dv likewise                          (per axis)
+ *     rho = max(sqrt(du/dpx^2 + dv/dpx^2) * (2 / W), sqrt(du/dpy^2 + dv/dpy^2) * (2 / H))
+ *   (one pixel step is 2/W in px and 2/H in py).  rho does not depend on the texture's side: one call serves textures
+ *   of any resolution.  1 <= H, W <= 32767, B >= 1, B * H * W < 2^31.
+ *
+ * The pyramid of a square texture [C,R,R] with L levels, R divisible by 2^L: level l (1..L) has side R >> l and is the
+ *   2 x 2 box average of level l - 1, ((t00 + t01) + (t10 + t11)) * 0.25 -- with texel centres (align_corners=False) a
+ *   coarse texel covers exactly four fine ones.  Level 0 is the texture itself and is not copied.  Levels 1..L are
+ *   packed [C, S], S = sum_l (R >> l)^2, level l of channel c starting at c * S + sum_{m<l} (R >> m)^2.  C * R * R <= 2^38.
+ * lnerf_mip_build: texture -> pyramid, one launch per level.  L = 0 launches nothing (pyramid may be NULL).
+ * lnerf_mip_build_backward: the exact transpose in gather form (no atomics, deterministic), from the coarsest level
+ *   down: d[l-1][c,i,j] += 0.25 * d[l][c,i/2,j/2] INSIDE dpyramid (which it therefore changes), ending with
+ *   dtexture[c,i,j] += 0.25 * d[1][c,i/2,j/2].  dtexture is ACCUMULATED into.
+ *
+ * lnerf_texture_mip_forward: out [n_pixels, C]; uv [n_pixels,2], rho [n_pixels] (lnerf_uv_footprint), face_idx may be
+ *   NULL (every pixel is foreground); pixels with face_idx < 0 give 0.
+ *     s = rho * R;  lambda = s > 0 ? clamp(log2f(s) + bias, 0, L) : 0;  l0 = min(floor(lambda), L);  t = lambda - l0
+ *     out = t == 0 ? bil(l0) : (1 - t) * bil(l0) + t * bil(l0 + 1)
+ *   bil(l) = lnerf_texture_map_forward's mode 1 (bilinear) on level l: the same texel coordinates for side R >> l,
+ *   the same four taps and weights, the same sum.  When t == 0 only level l0 is read, so wherever the footprint is at
+ *   most one texel (and bias <= 0) the result is mode 1's bit for bit.  bias must be finite.
+ * lnerf_texture_mip_backward: float atomics of w * ((1 - t) * g) into level l0 and w * (t * g) into level l0 + 1
+ *   (w * g when t == 0), level 0 being dtexture and the others dpyramid (same packing); both are ACCUMULATED into.
+ *   lnerf_mip_build_backward then folds dpyramid into dtexture.  uv and rho carry no gradient.
+ * All five: no allocation, no synchronisation, no host read-back; capturable.  Every argument is checked before the
+ * first launch. */
+int lnerf_uv_footprint(const int32_t *face_idx, const float *face_xy, const float *face_z, const float *face_uv, int B,
+                       int H, int W, int n_faces, float *rho, lnerf_stream_t stream);
+int lnerf_mip_build(const float *texture, int C, int R, int L, float *pyramid, lnerf_stream_t stream);
+int lnerf_mip_build_backward(float *dpyramid, int C, int R, int L, float *dtexture, lnerf_stream_t stream);
+int lnerf_texture_mip_forward(const float *uv, const float *rho, const int32_t *face_idx, const float *texture,
+                              const float *pyramid, int n_pixels, int C, int R, int L, float bias, float *out,
+                              lnerf_stream_t stream);
+int lnerf_texture_mip_backward(const float *uv, const float *rho, const int32_t *face_idx, const float *dout,
+                               int n_pixels, int C, int R, int L, float bias, float *dtexture, float *dpyramid,
+                               lnerf_stream_t stream);
+
 /* ---- optimiser step used by the bench/trainer (Adam, src/latent_paint/training/trainer.py:93-95:
  * betas (0.9, 0.99), eps 1e-15).  g is multiplied by grad_scale (1/world_size) first; if
  * zero_grad != 0 the gradient is cleared in the same pass; if shadow_bf16 != NULL the bf16

@@ -6,6 +6,7 @@
 // per-face-vertex attributes, face_idx = -1 on background, texture lookup = grid_sample(align_corners=False,
 // padding 'border') on (u, 1 - v).
 #include "common.h"
+#include "tex_shared.h"
 
 namespace lnerf {
 
@@ -294,20 +295,8 @@ k_interp_attr_bwd(const int32_t *__restrict__ face_idx, const float *__restrict_
     atomicAdd(&a[2 * D + d], bary[p * 3 + 2] * g);
 }
 
-// texture lookup: tex [C,R,R]; uv [P,2]; mode 0 nearest, 1 bilinear, 2 bicubic; grid_sample(align_corners=False, border)
-// on (u, 1 - v) after clamping uv to [0, 1] (the semantics of kal.render.mesh.texture_mapping, the op the reference
-// calls at src/latent_paint/models/render.py:64 with mode = guide.texture_interpolation_mode)
-__device__ __forceinline__ void tex_coords(float u, float v, int R, bool clip, float &x, float &y) {
-    u = clampf(u, 0.f, 1.f);
-    v = clampf(v, 0.f, 1.f);
-    const float gx = u * 2.0f - 1.0f, gy = -(v * 2.0f - 1.0f);
-    x = ((gx + 1.0f) * (float)R - 1.0f) * 0.5f;
-    y = ((gy + 1.0f) * (float)R - 1.0f) * 0.5f;
-    if (clip) {  // padding_mode = 'border' (nearest / bilinear clip the position, bicubic clips every tap instead)
-        x = clampf(x, 0.f, (float)(R - 1));
-        y = clampf(y, 0.f, (float)(R - 1));
-    }
-}
+// texture lookup: tex [C,R,R]; uv [P,2]; mode 0 nearest, 1 bilinear, 2 bicubic, at the texel coordinates of tex_coords
+// (tex_shared.h)
 // cubic convolution weights of the 4 taps around a position with fractional part t (A = -0.75, as grid_sample)
 __device__ __forceinline__ void cubic_weights(float t, float w[4]) {
     const float A = -0.75f;

@@ -5,13 +5,14 @@ reference, all deliberate: `guide.texture_resolution` is a real (typed) field an
 (in the reference it is a bare class attribute, :41); `guide.text` / `guide.shape_path` /
 `log.exp_name` default to "" so that the tree can be built without pyrallis and are checked by `validate()`;
 `guide.guidance` selects the offline stand-in for the diffusion model."""
+import math
 from dataclasses import dataclass, field
 from pathlib import Path
 from typing import Optional, Tuple
 
 from ... import config_cli as _cli
 
-INTERPOLATION_MODES = ("nearest", "bilinear", "bicubic")
+INTERPOLATION_MODES = ("nearest", "bilinear", "bicubic", "mipmap")
 UV_ATLASES = ("triangle", "charts")
 
 RenderConfig = _cli.make_section("RenderConfig", (
@@ -33,7 +34,10 @@ GuideConfig = _cli.make_section("GuideConfig", (
     ("shape_scale", float, 0.6, "size of the mesh inside the unit cube"),
     ("dy", float, 0.25, "lift of the mesh along +y"),
     ("texture_resolution", int, 128, "side of the square latent texture"),
-    ("texture_interpolation_mode", str, "nearest", " | ".join(INTERPOLATION_MODES)),
+    ("texture_interpolation_mode", str, "nearest", " | ".join(INTERPOLATION_MODES) + " (mipmap: trilinear over a mip "
+                                                   "pyramid, the level from each pixel's footprint in the texture)"),
+    ("texture_max_mip_level", int, -1, "mipmap: coarsest level used; -1 = every level the texture's side allows"),
+    ("texture_lod_bias", float, 0.0, "mipmap: added to the level log2(pixel footprint in texels); > 0 blurs"),
     ("init_texture", Optional[str], None, "latent texture [4,R,R] or [1,4,R,R] (torch.save) to start from, e.g. the "
                                           "latent_texture.pt of the NeRF's textured mesh export; R = texture_resolution"),
     ("uv_atlas", str, "triangle", "atlas built for a mesh without UVs when xatlas is missing: " + " | ".join(UV_ATLASES)),
@@ -80,6 +84,11 @@ class TrainConfig:
             raise ValueError("required config fields not set: %s" % ", ".join(unset))
         if self.guide.texture_interpolation_mode not in INTERPOLATION_MODES:
             raise ValueError("guide.texture_interpolation_mode must be one of %s" % ", ".join(INTERPOLATION_MODES))
+        if self.guide.texture_max_mip_level < -1:
+            raise ValueError("guide.texture_max_mip_level must be -1 (every level) or >= 0 (got %s)"
+                             % self.guide.texture_max_mip_level)
+        if not math.isfinite(self.guide.texture_lod_bias):
+            raise ValueError("guide.texture_lod_bias must be finite (got %s)" % self.guide.texture_lod_bias)
         if self.guide.uv_atlas not in UV_ATLASES:
             raise ValueError("guide.uv_atlas must be one of %s, not %r" % (" | ".join(UV_ATLASES), self.guide.uv_atlas))
         if self.render.batch_size < 1:

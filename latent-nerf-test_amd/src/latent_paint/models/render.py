@@ -1,7 +1,9 @@
 """HIP-backed counterpart of src/latent_paint/models/render.py (Renderer :5-69): same constructor, camera
 convention (:19-31) and the two render entry points (:34-47, :50-69), with the kaolin calls replaced by the
 C-ABI raster kernels (csrc/raster.hip).  `render_views` / `render_views_texture` take B views per call (the fork's
-`render.batch_size`); the single-view methods are their B = 1 case, on the one tile-culled rasteriser."""
+`render.batch_size`); the single-view methods are their B = 1 case, on the one tile-culled rasteriser.
+`interpolation_mode="mipmap"` is this project's own: the trilinear mip-mapped lookup of csrc/texmip.hip, for renders much
+smaller than their texture."""
 import math
 
 import torch
@@ -9,7 +11,7 @@ import torch
 from ...latent_nerf.raymarching import backend as _b
 from ...latent_nerf.raymarching.raymarching import _chk, _p, _stream
 
-_MODES = {"nearest": 0, "bilinear": 1, "bicubic": 2}
+_MODES = {"nearest": 0, "bilinear": 1, "bicubic": 2}   # lnerf_texture_map_*'s point lookups ("mipmap": _TextureMip)
 
 
 class _InterpAttr(torch.autograd.Function):
@@ -58,11 +60,93 @@ class _TextureMap(torch.autograd.Function):
         return dtex, None, None, None
 
 
+def mip_levels(R, max_mip_level=-1):
+    """Levels 1..L of an R x R texture: L_full = the trailing zero bits of R (a level's side may be odd only at the last
+    level), capped by `max_mip_level` when that is >= 0.  R = 1 or odd R gives 0: plain bilinear."""
+    R = int(R)
+    full = (R & -R).bit_length() - 1 if R > 0 else 0
+    return full if max_mip_level < 0 else min(int(max_mip_level), full)
+
+
+def mip_texels(R, L):
+    """Texels per channel of the packed levels 1..L."""
+    return sum((R >> l) ** 2 for l in range(1, L + 1))
+
+
+def uv_footprint(face_idx, face_xy, face_z, face_uv, B, H, W):
+    """rho [B*H*W]: the longer screen-space UV derivative per one-pixel step, in UV units (lnerf_uv_footprint)."""
+    F = face_uv.shape[0]
+    rho = torch.empty(B * H * W, device=face_idx.device)
+    _b.call("lnerf_uv_footprint", _chk(face_idx, "face_idx", torch.int32), _chk(face_xy, "face_xy"), _chk(face_z, "face_z"),
+            _chk(face_uv, "face_uv"), B, H, W, F, _p(rho), _stream())
+    return rho
+
+
+def mip_build(tex, L):
+    """tex [C,R,R] -> levels 1..L packed [C,S] (None when L = 0)."""
+    C, R = tex.shape[0], tex.shape[1]
+    if L == 0:
+        return None
+    pyr = torch.empty(C, mip_texels(R, L), device=tex.device)
+    _b.call("lnerf_mip_build", _chk(tex, "texture"), C, R, L, _p(pyr), _stream())
+    return pyr
+
+
+def mip_lookup(tex, pyr, uv, rho, face_idx, L, bias):
+    """The trilinear lookup (lnerf_texture_mip_forward) -> [P,C]."""
+    C, R, P = tex.shape[0], tex.shape[1], uv.shape[0]
+    out = torch.empty(P, C, device=tex.device)
+    _b.call("lnerf_texture_mip_forward", _chk(uv, "uv"), _chk(rho, "rho"), _p(face_idx), _chk(tex, "texture"), _p(pyr), P,
+            C, R, L, float(bias), _p(out), _stream())
+    return out
+
+
+def mip_lookup_backward(dout, shape, uv, rho, face_idx, L, bias):
+    """dout [P,C] -> the gradient of the [C,R,R] texture: the atomics of lnerf_texture_mip_backward into level 0 and a
+    packed gradient pyramid, which lnerf_mip_build_backward then folds into level 0."""
+    C, R = shape
+    dtex = torch.zeros(C, R, R, device=dout.device)
+    dpyr = torch.zeros(C, mip_texels(R, L), device=dout.device) if L > 0 else None
+    _b.call("lnerf_texture_mip_backward", _p(uv), _p(rho), _p(face_idx), _chk(dout, "dout"), uv.shape[0], C, R, L,
+            float(bias), _p(dtex), _p(dpyr), _stream())
+    _b.call("lnerf_mip_build_backward", _p(dpyr), C, R, L, _p(dtex), _stream())
+    return dtex
+
+
+class _TextureMip(torch.autograd.Function):
+    """Footprint, pyramid and trilinear lookup of one render call; the backward returns the texture's gradient."""
+
+    @staticmethod
+    def forward(ctx, tex, uv, face_idx, face_xy, face_z, face_uv, dims, max_mip_level, lod_bias):
+        if tex.dim() != 4 or tex.shape[0] != 1 or tex.shape[2] != tex.shape[3]:
+            raise ValueError("texture_map: texture must be [1,C,R,R] (got %s)" % (tuple(tex.shape),))
+        B, H, W = dims
+        t = tex[0].contiguous()
+        L = mip_levels(t.shape[1], max_mip_level)     # per call: render_test passes the decoded, larger texture
+        rho = uv_footprint(face_idx, face_xy, face_z, face_uv, B, H, W)
+        out = mip_lookup(t, mip_build(t, L), uv, rho, face_idx, L, lod_bias)
+        ctx.save_for_backward(uv, rho, face_idx)
+        ctx.meta = (t.shape[0], t.shape[1], L, lod_bias)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        uv, rho, face_idx = ctx.saved_tensors
+        C, R, L, bias = ctx.meta
+        dtex = mip_lookup_backward(dout.contiguous(), (C, R), uv, rho, face_idx, L, bias)
+        return (dtex[None],) + (None,) * 8
+
+
 class Renderer:
-    def __init__(self, device, dim=(224, 224), interpolation_mode="nearest"):
-        assert interpolation_mode in ["nearest", "bilinear", "bicubic"], "no interpolation mode %s" % interpolation_mode
+    def __init__(self, device, dim=(224, 224), interpolation_mode="nearest", max_mip_level=-1, lod_bias=0.0):
+        assert interpolation_mode in ["nearest", "bilinear", "bicubic", "mipmap"], \
+            "no interpolation mode %s" % interpolation_mode
+        if not math.isfinite(lod_bias):
+            raise ValueError("Renderer: lod_bias must be finite (got %r)" % (lod_bias,))
         self.device = device
         self.interpolation_mode = interpolation_mode
+        self.max_mip_level = int(max_mip_level)        # "mipmap" only: < 0 = every level the texture's side allows
+        self.lod_bias = float(lod_bias)                # "mipmap" only: added to the level log2(footprint in texels)
         self.fov = math.pi / 3                         # kal.render.camera.generate_perspective_projection(np.pi / 3)
         self.dim = dim
         self.background = torch.ones(dim).to(device).float()
@@ -92,6 +176,10 @@ class Renderer:
 
     def _rasterize_views(self, verts, faces, elev, azim, radius, look_at_height, dims):
         """B views of one mesh through the tile-culled rasteriser -> (face_idx [B*H*W], bary [B*H*W,3], B, H, W)."""
+        return self._rasterize_views_faces(verts, faces, elev, azim, radius, look_at_height, dims)[:5]
+
+    def _rasterize_views_faces(self, verts, faces, elev, azim, radius, look_at_height, dims):
+        """_rasterize_views' result followed by the projected faces it was made from: face_xy [B,F,3,2], face_z [B,F,3]."""
         elev, azim, radius = list(elev), list(azim), list(radius)
         B = len(elev)
         if B < 1 or len(azim) != B or len(radius) != B:
@@ -111,7 +199,7 @@ class Renderer:
         bary = torch.empty(B * H * W, 3, device=self.device)
         _b.call("lnerf_rasterize_batch", B, H, W, _p(face_z), _p(face_xy), _p(face_box), F, _p(face_idx), _p(bary),
                 _stream())
-        return face_idx, bary, B, H, W
+        return face_idx, bary, B, H, W, face_xy, face_z
 
     def _rasterize(self, verts, faces, elev, azim, radius, look_at_height, dims):
         face_idx, bary, _, H, W = self._rasterize_views(verts, faces, [elev], [azim], [radius], look_at_height, dims)
@@ -131,10 +219,16 @@ class Renderer:
         """B views of the textured mesh in one call -> (image [B,C,H,W], mask [B,1,H,W]).  The batch is B*H*W flat
         pixels through the single-view kernels; the texture is shared, so its gradient sums over the views."""
         dims = self.dim if dims is None else dims
-        face_idx, bary, B, H, W = self._rasterize_views(verts, faces, elev, azim, radius, look_at_height, dims)
+        face_idx, bary, B, H, W, face_xy, face_z = self._rasterize_views_faces(verts, faces, elev, azim, radius,
+                                                                               look_at_height, dims)
+        face_uv = uv_face_attr[0].detach().contiguous()
         with torch.no_grad():                          # uv_features.detach() in the reference (:61)
-            uv = _InterpAttr.apply(uv_face_attr[0].detach(), face_idx, bary).contiguous()
-        image = _TextureMap.apply(texture_map, uv, face_idx, _MODES[self.interpolation_mode])
+            uv = _InterpAttr.apply(face_uv, face_idx, bary).contiguous()
+        if self.interpolation_mode == "mipmap":
+            image = _TextureMip.apply(texture_map, uv, face_idx, face_xy, face_z, face_uv, (B, H, W), self.max_mip_level,
+                                      self.lod_bias)
+        else:
+            image = _TextureMap.apply(texture_map, uv, face_idx, _MODES[self.interpolation_mode])
         mask = (face_idx > -1).float().reshape(B, H, W, 1)
         image = image.reshape(B, H, W, -1) * mask
         if white_background:

@@ -9,6 +9,7 @@ the checkpoint keys (`background_sphere_colors`, `texture_img`, `texture_img_rgb
 computes: a learnable 4-channel latent texture [1,4,R,R] looked up through the mesh's UV map, over a learnable
 background = per-face-vertex colours [1,F_env,3,4] of a large sphere around the scene."""
 import os
+import warnings
 from pathlib import Path
 
 import numpy as np
@@ -23,6 +24,10 @@ from .render import Renderer
 # latent -> RGB linear estimate (rows = latent channels), the table of textured_mesh.py:34-40
 LATENT_RGB_ROWS = ((0.298, 0.207, 0.208), (0.187, 0.286, 0.173), (-0.158, 0.189, 0.264), (-0.184, -0.271, -0.473))
 LATENT_SIDE = 64   # side of the latent image the diffusion model consumes (src/stable_diffusion.py:259)
+PER_TRIANGLE_MIPMAP_WARNING = (
+    "guide.texture_interpolation_mode mipmap on the per-triangle atlas: faces that are neighbours on the mesh are not "
+    "neighbours in this atlas, so the coarse mip levels average unrelated faces, and no filter in texture space can "
+    "help that.  Use --guide.uv_atlas charts, a mesh with its own UVs, or a small --guide.texture_max_mip_level.")
 
 
 def load_init_texture(path, R):
@@ -52,7 +57,9 @@ class TexturedMeshModel(nn.Module):
         self.texture_resolution = int(texture_resolution)
         self.linear_rgb_estimator = torch.tensor(LATENT_RGB_ROWS, device=self.device)
         self.renderer = Renderer(device=self.device, dim=(render_grid_size, render_grid_size),
-                                 interpolation_mode=opt.guide.texture_interpolation_mode)
+                                 interpolation_mode=opt.guide.texture_interpolation_mode,
+                                 max_mip_level=getattr(opt.guide, "texture_max_mip_level", -1),
+                                 lod_bias=getattr(opt.guide, "texture_lod_bias", 0.0))
         self.env_sphere, self.mesh = self.init_meshes()
         self.background_sphere_colors, self.texture_img, self.texture_img_rgb_finetune = self.init_paint()
         self.vt, self.ft = self.init_texture_map()
@@ -113,6 +120,8 @@ class TexturedMeshModel(nn.Module):
                                      self.texture_resolution)
             else:
                 vt, ft = per_triangle_atlas(mesh.faces.shape[0], self.device)
+                if getattr(self.opt.guide, "texture_interpolation_mode", None) == "mipmap":
+                    warnings.warn(PER_TRIANGLE_MIPMAP_WARNING, stacklevel=2)
         else:
             atlas = xatlas.Atlas()
             atlas.add_mesh(mesh.vertices.cpu().numpy(), mesh.faces.int().cpu().numpy())

@@ -63,8 +63,10 @@ const char *lnerf_build_info(void);
  *   "scatter_bin_wgs":         persistent workgroups of the binning pass (default 0 = 256 x scatter_bin_per_cu).
  *   "scatter_skip_zero":       1 (default) = contributions that are exactly zero are not binned.
  *   "scatter_reduce_threads":  threads per workgroup of the reduce pass, 512 or 1024 (default 1024).
- *   "gather_pair_loads":       0 = one load per vertex; 1 = x-adjacent vertices of dense levels with one load;
- *                              2 (default) = additionally one aligned 16-byte load per 4-row group of a bf16 table.
+ *   "gather_pair_loads":       0 = one load per vertex; 1 = x-adjacent vertices with one load where they are adjacent rows
+ *                              (dense levels, inside a block of the blocked layout, aligned pairs of the vertex hash);
+ *                              2 (default) = additionally one aligned 16-byte load per 4-row group of a bf16 table
+ *                              (vertex hash).
  *   "gather_dedup_max_res":    levels with resolution <= value fetch a cell's 8 vertices once per run of
  *                              lanes (consecutive samples of a ray) in that cell (default 512; 0 = off).
  *   "gather_lds_pad":          experiment knob: bytes of unused dynamic LDS per gather workgroup, 0 .. 65536 (default 0).
@@ -167,7 +169,9 @@ int lnerf_compact_rays(const int32_t *alive_in, int64_t n, int32_t *alive_out, i
  * Level metadata is passed from the host (num_levels <= LNERF_MAX_LEVELS):
  *   offsets_host [L+1] row offsets, scales_host [L] per-level scale, res_host [L] resolution.
  * xyzs are world positions; the kernels normalise x01 = (x + bound) / (2*bound).
- * `variant` must be 0 (level on blockIdx.y), optionally with the layout flags LNERF_GRID_BLOCKED / LNERF_GRID_TILED. */
+ * `variant` must be 0 (level on blockIdx.y), optionally with the layout flags LNERF_GRID_BLOCKED / LNERF_GRID_TILED.
+ * The forward kernel keeps sample indices and byte offsets into a level in 32 bits: m_host < 2^31, and a level has at
+ * most 2^30 rows with a bf16 table, 2^29 with an f32 table (4 GiB); anything larger is refused. */
 int lnerf_grid_encode_forward(const float *xyzs, float bound, const void *table, int table_dtype, int num_levels,
                               int level_dim, const int32_t *offsets_host, const float *scales_host,
                               const int32_t *res_host, int64_t m_host, const int32_t *m_dev, int64_t level_stride,

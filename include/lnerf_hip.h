@@ -392,7 +392,19 @@ int lnerf_synthetic_guidance(const float *image, const float *targets, const int
 
 /* ---- H8/H9: `raymarching.composite_rays_train_forward/backward`.  One wavefront per ray,
  * log-space prefix scan of sigma*dt across lanes.  C = colour channels (3 or 4).
- * bg_color [N,C] or NULL: image += (1 - weights_sum) * bg. */
+ * bg_color [N,C] or NULL: image += (1 - weights_sum) * bg.
+ *
+ * THE COMPOSITING WEIGHT (csrc/span_walk.h, span_weight: one definition, which every op below that weights samples
+ * "as the compositing does" calls).  For ray r with (id, off, cnt) = rays[r], sample s = off + i, i < cnt, front to back,
+ * on a density sigma (an op that takes density_scale says so: sigma = density_scale * its density):
+ *     tau = sigma * dt (dt = deltas[s][0]), 64-lane inclusive scan of tau with a scalar carry between the chunks of 64,
+ *     excl = (the previous lane's inclusive sum; lane 0: 0) + carry -- never inc - tau --, T = expf(-excl),
+ *     e = expf(-tau),   alpha = 1 - e,   live = T >= T_thresh,   w = live ? alpha * T : 0,   T e = T_{i+1}.
+ *   Nothing is clamped: a NaN T is not live, behind the first T < T_thresh every w is 0 (T falls along the ray).  The
+ *   weight itself has no early stop.  The compositing stops reading a ray there (weights_sum, depth, image are sums of the
+ *   live samples; the backward writes zeros behind it); the regularisers walk on, because every sample still gets its rows.
+ *   expf and the scan are tolerance-checked, not restated bit for bit.
+ *   weights_sum = sum_i w_i,  depth = sum_i w_i t_i,  image_c = sum_i w_i rgb_ic. */
 int lnerf_composite_rays_train_forward(const float *sigmas, const float *rgbs, const float *deltas,
                                        const int32_t *rays, int64_t N, int C, float T_thresh, const float *bg_color,
                                        float *weights_sum, float *depth, float *image, lnerf_stream_t stream);
@@ -951,10 +963,7 @@ int lnerf_shade_fd_backward(const float *sigmas7, const float *rgbs7, int C, con
  *     d = rays_d[id],   s_v = (d_x d_x + d_y d_y) + d_z d_z,   r_v = 1 / sqrt(fmax(s_v, 1e-20)),   v_a = d_a * r_v;
  *   per sample i < cnt, s = off + i, with n of lnerf_shade_fd_forward:
  *     c = (n_x v_x + n_y v_y) + n_z v_z,   q = c > 0 ? c : 0;
- *   w_i is the compositing weight as lnerf_composite_rays_train_forward defines it, on sigma' = density_scale * sg[0]:
- *     tau = sigma' * dt (dt = deltas[s][0]), 64-lane inclusive scan of tau with a scalar carry between the chunks of 64,
- *     excl = (the previous lane's inclusive sum; lane 0: 0) + carry -- never inc - tau --, T = expf(-excl),
- *     alpha = 1 - expf(-tau),   w = T >= T_thresh ? alpha * T : 0.
+ *   w_i is THE COMPOSITING WEIGHT (lnerf_composite_rays_train_forward, above) on sigma = density_scale * sg[0].
  *   Unlike the compositing there is no early stop: behind T < T_thresh every sample still gets its sigma_c and colours
  *   (and, in the backward, its gradient rows); only w is 0.
  *     orient[id] = sum_i w_i * (q_i * q_i)   (lane partials over i = lane, lane + 64, ..; then the wave's sum; one writer).
@@ -988,10 +997,8 @@ int lnerf_shade_fd_orient_backward(const float *sigmas7, const float *rgbs7, int
  *   the densities handed to the compositing (multiplied by density_scale already), deltas f32 [cap, 2] = (dt, t) of the
  *   march (8-byte aligned; t increases along a span, sample s covers [t, t + dt]), 0 <= T_thresh < 1.  For sample
  *   s = off + i, i < cnt, front to back, with t_0 = deltas[off][1]:
- *     tau = sigma * dt, 64-lane inclusive scan of tau with a scalar carry between the chunks of 64,
- *     excl = (the previous lane's inclusive sum; lane 0: 0) + carry -- never inc - tau --, T = expf(-excl),
- *     e = expf(-tau),   alpha = 1 - e,   live = T >= T_thresh,   w = live ? alpha * T : 0
- *   (lnerf_shade_fd_orient_forward's weight; no early stop: behind the cut only w is 0),
+ *     w, T, e, live: THE COMPOSITING WEIGHT (lnerf_composite_rays_train_forward, above) on sigma; no early stop: behind
+ *       the cut only w is 0,
  *     m = (t - t_0) + 0.5 * dt,
  *     A = sum_{j<i} w_j,   B = sum_{j<i} (w_j * m_j):  64-lane inclusive scans of w and of w * m, each taken from the
  *       previous lane (lane 0: 0) plus its scalar carry, the carries growing by lane 63's inclusive sum per chunk,
@@ -1034,10 +1041,8 @@ int lnerf_distortion_backward(const float *sigmas, const float *deltas, const in
  *   sg = sigmas7[7 s .. 7 s + 6]:
  *     n of lnerf_shade_fd_forward:  g_a = (sg[1 + 2 a] - sg[2 + 2 a]) * inv_2eps,   s2 = (g_x g_x + g_y g_y) + g_z g_z,
  *       r = 1 / sqrt(fmax(s2, 1e-20)),   n_a = -(g_a r), a NaN component becomes 0;
- *     w of lnerf_shade_fd_orient_forward on sigma' = density_scale * sg[0]:  tau = sigma' * dt (dt = deltas[s][0]), 64-lane
- *       inclusive scan of tau with a scalar carry between the chunks of 64, excl = (the previous lane's inclusive sum;
- *       lane 0: 0) + carry -- never inc - tau --, T = expf(-excl), e = expf(-tau), alpha = 1 - e, live = T >= T_thresh,
- *       w = live ? alpha * T : 0  (no early stop: behind the cut only w is 0);
+ *     w, T, e, live: THE COMPOSITING WEIGHT (lnerf_composite_rays_train_forward, above) on sigma = density_scale * sg[0]
+ *       (no early stop: behind the cut only w is 0);
  *     normal_image[id][a] = sum_i w_i * n_{i,a}   (lane partials over i = lane, lane + 64, ..; then the wave's sum; one
  *       writer).
  *   A ray with cnt = 0 writes (0, 0, 0).  Elements of ids no ray carries are not touched.

@@ -120,45 +120,6 @@ __device__ __forceinline__ float wave_sum(float v) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
-// Optical depth in front of this lane's sample, from the chunk's inclusive scan `inc` and the depth `carry` of the chunks
-// before it: the NEIGHBOURING lane's inclusive sum (lane 0: nothing), never `inc - tau`.  The lane's own tau can be
-// arbitrarily large (sigma = exp(h) is unclamped, a surface sample has sigma dt ~ 1e4 and more); subtracting it back out
-// of a sum that contains it rounds the small prefix in front of it away (error 2^-24 tau in excl, i.e. in T and the
-// weight; inf - inf = NaN at sigma = +inf).  The compositing forward and backward both call this (the backward's `keep`
-// has to reproduce the forward's decisions bit for bit), and so does the orientation term of the shaded renders
-// (shade.hip), whose weights are the compositing's.
-__device__ __forceinline__ float exclusive_depth(float inc, float carry) { return lane_prev_f(inc, 0.f) + carry; }
-
-// ---- the span vocabulary of the one-wavefront-per-ray kernels (composite.hip, shade.hip)
-// row r of the march's ray table: the ray's id and the span [off, off + cnt) of its samples
-struct RaySpan {
-    int64_t id, off;
-    int cnt;
-};
-__device__ __forceinline__ RaySpan load_span(const int32_t *__restrict__ rays, int64_t r) {
-    return {rays[r * 3], rays[r * 3 + 1], rays[r * 3 + 2]};
-}
-// row `row` of a [rows, C] f32 array: one 16-byte access for the four latent channels (the callers check the alignment)
-template <int C>
-__device__ __forceinline__ void load_row(const float *p, int64_t row, float (&v)[C]) {
-    if (C == 4) {
-        const float4 q = reinterpret_cast<const float4 *>(p)[row];
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[C - 1] = q.w;
-    } else {
-#pragma unroll
-        for (int c = 0; c < C; ++c) v[c] = p[row * C + c];
-    }
-}
-template <int C>
-__device__ __forceinline__ void store_row(float *p, int64_t row, const float (&v)[C]) {
-    if (C == 4) {
-        reinterpret_cast<float4 *>(p)[row] = make_float4(v[0], v[1], v[2], v[C - 1]);
-    } else {
-#pragma unroll
-        for (int c = 0; c < C; ++c) p[row * C + c] = v[c];
-    }
-}
-
 __device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float(((uint32_t)h) << 16); }
 // round-to-nearest-even f32 -> bf16 (NaN preserved as quiet NaN)
 __device__ __forceinline__ uint16_t f32_to_bf16(float f) {

@@ -4,7 +4,9 @@
 // transmittance comes from a log-space prefix scan of tau = sigma*dt across the 64 lanes with
 // a scalar carry between 64-sample chunks, and the per-ray sums are wave reductions.
 // The early stop "T < T_thresh" is wave-uniform because T is monotone along the ray.
-#include "common.h"
+// The weight itself (span_weight) and the span vocabulary live in span_walk.h, shared with the regularisers that weight
+// samples the way this image does.
+#include "span_walk.h"
 
 namespace lnerf {
 
@@ -23,16 +25,14 @@ __device__ __forceinline__ Chunk<C> load_chunk(const float *__restrict__ sigmas,
     const int i = base + lane;
     if (i < cnt) {
         const int64_t s = off + i;
-        const float2 d = reinterpret_cast<const float2 *>(deltas)[s];
-        k.dt = d.x; k.t = d.y;
+        const Step d = load_step(deltas, s);
+        k.dt = d.dt; k.t = d.t;
         k.sigma = sigmas[s];
         load_row<C>(rgbs, s, k.rgb);
     }
     return k;
 }
 
-// (exclusive_depth, the optical depth in front of a lane's sample, lives in common.h: the shaded renders' orientation
-// term takes its weights from the same function)
 // One ray's forward loop over its span: each lane's share of weights_sum, depth and the C colour sums (no background);
 // the caller adds them across the wave.
 template <int C>
@@ -50,21 +50,14 @@ __device__ __forceinline__ void composite_ray_fwd(const float *__restrict__ sigm
     for (int base = 0; base < cnt; base += 64) {
         Chunk<C> nxt = cur;
         if (base + 64 < cnt) nxt = load_chunk<C>(sigmas, rgbs, deltas, off, cnt, base + 64, lane);
-        const bool valid = base + lane < cnt;
-        const float dt = cur.dt, t = cur.t;
-        const float tau = cur.sigma * dt;     // (invalid lanes carry zeros)
-        const float inc = wave_inclusive_sum(tau);
-        const float excl = exclusive_depth(inc, carry);
-        const float T = expf(-excl);
-        const float alpha = 1.0f - expf(-tau);
-        const float w = (valid && T >= T_thresh) ? alpha * T : 0.f;
+        const float tau = cur.sigma * cur.dt;     // (invalid lanes carry zeros)
+        const float w = span_weight(tau, base + lane < cnt, T_thresh, carry).w;
         a_ws += w;
-        a_d = fmaf(w, t, a_d);
+        a_d = fmaf(w, cur.t, a_d);
         if (w != 0.f) {
 #pragma unroll
             for (int c = 0; c < C; ++c) a_c[c] = fmaf(w, cur.rgb[c], a_c[c]);
         }
-        carry += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(inc), 63));
         if (expf(-carry) < T_thresh) break;  // every later sample starts below the threshold
         cur = nxt;
     }
@@ -148,20 +141,6 @@ k_decode_image(const float *__restrict__ latent_image, const float *__restrict__
     decode_pixel(decoder, L, weights_sum[i], bg ? bg + i * 3 : nullptr, image + i * 3);
 }
 
-// d_rgbs[s][c] = di[c] * w (di == nullptr: zeros), one 16-byte store for the four latent channels.  (Written out, not
-// through store_row: with the products in a row of their own, k_composite_train_bwd<3> orders its address arithmetic
-// differently, and the compositing kernels' code is held fixed.)
-template <int C>
-__device__ __forceinline__ void store_grad_row(float *__restrict__ d_rgbs, int64_t s, const float *di, float w) {
-    if (C == 4) {
-        reinterpret_cast<float4 *>(d_rgbs)[s] = di ? make_float4(di[0] * w, di[1] * w, di[2] * w, di[C - 1] * w)
-                                                     : make_float4(0.f, 0.f, 0.f, 0.f);
-    } else {
-#pragma unroll
-        for (int c = 0; c < C; ++c) d_rgbs[s * C + c] = di ? di[c] * w : 0.f;
-    }
-}
-
 // total = sum_k g_k w_k of one ray, from the forward outputs (g_k = dws + ddp t_k + sum_c di_c (rgb_kc - bg_c))
 template <int C>
 __device__ __forceinline__ float ray_total(float dws, float ddp, float ws, float depth, const float (&di)[C],
@@ -192,34 +171,30 @@ __device__ __forceinline__ void composite_ray_bwd(const float *__restrict__ sigm
         if (stopped) {  // zero-fill the tail of the span
             if (valid) {
                 d_sigmas[s] = 0.f;
-                store_grad_row<C>(d_rgbs, s, nullptr, 0.f);
+                const float zero[C] = {};
+                store_row<C>(d_rgbs, s, zero);
             }
             continue;
         }
         Chunk<C> nxt = cur;   // the next chunk's inputs, requested before this chunk's arithmetic (see the forward)
         if (base + 64 < cnt) nxt = load_chunk<C>(sigmas, rgbs, deltas, off, cnt, base + 64, lane);
-        const float dt = cur.dt, t = cur.t;
-        const float tau = cur.sigma * dt;
-        const float inc = wave_inclusive_sum(tau);
-        const float excl = exclusive_depth(inc, carry_tau);
-        const float T = expf(-excl);
-        const float e = expf(-tau);
-        const float alpha = 1.0f - e;
-        const bool keep = valid && T >= T_thresh;
-        const float w = keep ? alpha * T : 0.f;
-        float g = fmaf(ddp, t, dws);
+        const float dt = cur.dt;
+        const SpanWeight k = span_weight(cur.sigma * dt, valid, T_thresh, carry_tau);
+        float g = fmaf(ddp, cur.t, dws);
 #pragma unroll
         for (int c = 0; c < C; ++c) g = fmaf(di[c], cur.rgb[c] - bgc[c], g);
-        const float gw = g * w;
+        const float gw = g * k.w;
         const float pinc = wave_inclusive_sum(gw) + carry_p;  // inclusive prefix of g_k w_k
         if (valid) {
             // dL/dtau_i = g_i T_{i+1} - sum_{k>i} g_k w_k
-            const float dtau = keep ? fmaf(g, T * e, -(total - pinc)) : 0.f;
+            const float dtau = k.live ? fmaf(g, k.Te, -(total - pinc)) : 0.f;
             d_sigmas[s] = dt * dtau;
-            store_grad_row<C>(d_rgbs, s, di, w);
+            float drgb[C];    // d_rgbs[s][c] = di[c] * w
+#pragma unroll
+            for (int c = 0; c < C; ++c) drgb[c] = di[c] * k.w;
+            store_row<C>(d_rgbs, s, drgb);
         }
-        carry_tau += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(inc), 63));
-        carry_p = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pinc), 63));
+        carry_p = lane63(pinc);
         if (expf(-carry_tau) < T_thresh) stopped = true;
         cur = nxt;
     }

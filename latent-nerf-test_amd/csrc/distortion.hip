@@ -2,10 +2,10 @@
 // Contract and order of operations: include/lnerf_hip.h, "distortion loss"; numpy restatement: tests/distortion_reference.py.
 //
 // One wavefront per ray, lanes on consecutive samples of the ray's span, chunks of 64 chained through scalar carries --
-// the shape of the training compositing (composite.hip).  The weights are the compositing's (exclusive_depth, T_thresh),
+// the shape of the training compositing (composite.hip).  The weights are the compositing's (span_walk.h, span_weight),
 // and here they are NOT detached: the backward is the compositing backward's identity with g_i = dL/dw_i of this term.
 // No LDS, no atomics: every output element has one writer.
-#include "common.h"
+#include "span_walk.h"
 
 namespace lnerf {
 
@@ -17,8 +17,8 @@ __device__ __forceinline__ DistChunk load_dist_chunk(const float *__restrict__ s
                                                      int64_t off, int cnt, int i) {
     DistChunk k = {0.f, 0.f, 0.f};
     if (i < cnt) {
-        const float2 d = reinterpret_cast<const float2 *>(deltas)[off + i];
-        k.dt = d.x; k.t = d.y;
+        const Step d = load_step(deltas, off + i);
+        k.dt = d.dt; k.t = d.t;
         k.sigma = sigmas[off + i];
     }
     return k;
@@ -26,27 +26,14 @@ __device__ __forceinline__ DistChunk load_dist_chunk(const float *__restrict__ s
 
 // What one chunk of a ray knows about this lane's sample, and the three carries it moves forward.  Called by ALL 64 lanes
 // (wave scans); lanes past the span carry w = 0.
-struct DistTerms {
-    float w, m, dt, Te, u;   // weight, shifted mid-point, dt, T_{i+1} = T e, u = m A - B
-    bool live;               // valid && T >= T_thresh
+struct DistTerms : SpanWeight {   // the compositing weight: w, Te = T_{i+1}, live
+    float m, dt, u;               // shifted mid-point, dt, u = m A - B
 };
 struct DistCarry {
     float tau, A, B;         // optical depth, sum of w, sum of w m of the chunks before this one
 };
-__device__ __forceinline__ float lane63(float v) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
 __device__ __forceinline__ DistTerms dist_terms(const DistChunk &k, bool valid, float t0, float T_thresh, DistCarry &c) {
-    DistTerms o;
-    const float tau = k.sigma * k.dt;
-    const float inc = wave_inclusive_sum(tau);
-    const float excl = exclusive_depth(inc, c.tau);
-    const float T = expf(-excl);
-    const float e = expf(-tau);
-    const float alpha = 1.0f - e;
-    o.live = valid && T >= T_thresh;
-    o.w = o.live ? alpha * T : 0.f;
-    o.Te = T * e;
+    DistTerms o = {span_weight(k.sigma * k.dt, valid, T_thresh, c.tau)};
     o.dt = k.dt;
     o.m = (k.t - t0) + 0.5f * k.dt;
     const float wm = o.w * o.m;
@@ -55,7 +42,6 @@ __device__ __forceinline__ DistTerms dist_terms(const DistChunk &k, bool valid, 
     const float A = lane_prev_f(incA, 0.f) + c.A;     // exclusive: the neighbouring lane's inclusive sum
     const float B = lane_prev_f(incB, 0.f) + c.B;
     o.u = o.m * A - B;
-    c.tau += lane63(inc);
     c.A += lane63(incA);
     c.B += lane63(incB);
     return o;

@@ -2,78 +2,34 @@
 // Contract and order of operations: include/lnerf_hip.h, "composited normal image"; numpy restatement:
 // tests/normal_image_reference.py.
 //
-//   k_normal_image_fwd   normal_image[ray] = sum_i w_i n_i: the finite-difference normal of shade.hip, the compositing weight
-//                        of the orientation term -- one wavefront per ray, chunks of 64 chained through a scalar carry
+//   k_normal_image_fwd   normal_image[ray] = sum_i w_i n_i: the finite-difference normal and the compositing weight of
+//                        span_walk.h -- one wavefront per ray, chunks of 64 chained through a scalar carry
 //   k_normal_image_bwd   ONE forward sweep per ray: the weights are NOT detached (sum_i g_i w_i = N . dN comes from the
-//                        forward's output), and the normal's gradient goes through shade.hip's projection
+//                        forward's output), and the normal's gradient goes through span_walk.h's projection
 //   k_image_smooth_fwd   squared differences to the right and the lower neighbour, one lane per pixel
 //   k_image_smooth_bwd   its gradient in gather form (own-h, own-v, left, up)
 //
 // All arithmetic is f32 + - * / sqrt in the stated order (-ffp-contract=off, no explicit fmaf) except expf and the 64-lane
 // scans.  No LDS, no atomics: every output element has one writer.
-#include "common.h"
+#include "span_walk.h"
 
 namespace lnerf {
 
-constexpr int NI_ROWS = 7;       // the sample and its six neighbours (shade.hip's FD_ROWS)
-
 // one lane's sample of a 64-sample chunk (zeros past the end of the span)
 struct NormalChunk {
-    float sg[NI_ROWS], dt;
+    float sg[FD_ROWS], dt;
 };
 __device__ __forceinline__ NormalChunk load_normal_chunk(const float *__restrict__ sigmas7, const float *__restrict__ deltas,
                                                          int64_t off, int cnt, int i) {
     NormalChunk k;
 #pragma unroll
-    for (int j = 0; j < NI_ROWS; ++j) k.sg[j] = 0.f;
+    for (int j = 0; j < FD_ROWS; ++j) k.sg[j] = 0.f;
     k.dt = 0.f;
     if (i < cnt) {
-        const int64_t s7 = (off + i) * NI_ROWS;
-#pragma unroll
-        for (int j = 0; j < NI_ROWS; ++j) k.sg[j] = sigmas7[s7 + j];
-        k.dt = reinterpret_cast<const float2 *>(deltas)[off + i].x;
+        load_fd_rows(sigmas7, (off + i) * FD_ROWS, k.sg);
+        k.dt = load_step(deltas, off + i).dt;
     }
     return k;
-}
-
-// finite-difference normal of one sample, as lnerf_shade_fd_forward defines it
-struct FdNormal {
-    float n[3], s, r;
-};
-__device__ __forceinline__ FdNormal fd_normal(const float (&sg)[NI_ROWS], float inv_2eps) {
-    FdNormal o;
-    float g[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) g[a] = (sg[1 + 2 * a] - sg[2 + 2 * a]) * inv_2eps;
-    o.s = (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
-    o.r = 1.0f / sqrtf(fmaxf(o.s, 1e-20f));          // (fmaxf: a NaN s gives the floor)
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float v = -(g[a] * o.r);
-        o.n[a] = v != v ? 0.f : v;
-    }
-    return o;
-}
-
-// Compositing weight of this lane's sample, as lnerf_shade_fd_orient_forward defines it, with what the backward needs of
-// it.  Called by ALL 64 lanes (a wave scan); lanes past the span carry w = 0.  No early stop.
-struct NormalWeight {
-    float w, Te;     // weight, T_{i+1} = T e
-    bool live;       // valid && T >= T_thresh
-};
-__device__ __forceinline__ NormalWeight normal_weight(float sigma, float dt, bool valid, float T_thresh, float &carry) {
-    NormalWeight o;
-    const float tau = sigma * dt;
-    const float inc = wave_inclusive_sum(tau);
-    const float excl = exclusive_depth(inc, carry);
-    const float T = expf(-excl);
-    const float e = expf(-tau);
-    const float alpha = 1.0f - e;
-    o.live = valid && T >= T_thresh;
-    o.w = o.live ? alpha * T : 0.f;
-    o.Te = T * e;
-    carry += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(inc), 63));
-    return o;
 }
 
 // normal_image[id] = sum_i w_i n_i.  A ray without samples writes zeros (the buffer is uninitialised): no early return
@@ -91,7 +47,7 @@ k_normal_image_fwd(const float *__restrict__ sigmas7, const float *__restrict__ 
         NormalChunk nxt = cur;    // the next chunk's inputs, requested before this chunk's scan
         if (base + 64 < cnt) nxt = load_normal_chunk(sigmas7, deltas, off, cnt, base + 64 + lane);
         const FdNormal o = fd_normal(cur.sg, inv_2eps);
-        const NormalWeight k = normal_weight(density_scale * cur.sg[0], cur.dt, base + lane < cnt, T_thresh, carry);
+        const SpanWeight k = span_weight((density_scale * cur.sg[0]) * cur.dt, base + lane < cnt, T_thresh, carry);
 #pragma unroll
         for (int a = 0; a < 3; ++a) acc[a] += k.w * o.n[a];
         cur = nxt;
@@ -130,31 +86,19 @@ k_normal_image_bwd(const float *__restrict__ sigmas7, const float *__restrict__ 
         const int i = base + lane;
         const bool valid = i < cnt;
         const FdNormal o = fd_normal(cur.sg, inv_2eps);
-        const NormalWeight k = normal_weight(density_scale * cur.sg[0], cur.dt, valid, T_thresh, carry);
+        const SpanWeight k = span_weight((density_scale * cur.sg[0]) * cur.dt, valid, T_thresh, carry);
         const float g = (o.n[0] * dN[0] + o.n[1] * dN[1]) + o.n[2] * dN[2];
         const float pinc = wave_inclusive_sum(g * k.w) + carry_g;
         if (valid) {
             // dL/dtau_i = g_i T_{i+1} - sum_{j>i} g_j w_j
             const float dtau = k.live ? g * k.Te - (total - pinc) : 0.f;
-            float dn[3], ds[NI_ROWS];
+            float dn[3];
 #pragma unroll
             for (int a = 0; a < 3; ++a) dn[a] = k.w * dN[a];
-            const float q = (o.n[0] * dn[0] + o.n[1] * dn[1]) + o.n[2] * dn[2];
-            const bool project = o.s > 1e-20f;
-            ds[0] = (density_scale * cur.dt) * dtau;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const float t = project ? dn[a] - o.n[a] * q : dn[a];
-                const float dg = -(o.r * t);
-                const float v = dg * inv_2eps;
-                ds[1 + 2 * a] = v;
-                ds[2 + 2 * a] = -v;
-            }
-            const int64_t s7 = (off + i) * NI_ROWS;
-#pragma unroll
-            for (int j = 0; j < NI_ROWS; ++j) dsigmas7[s7 + j] = ds[j];
+            store_fd_rows(dsigmas7, (off + i) * FD_ROWS, (density_scale * cur.dt) * dtau,
+                          fd_normal_backward(o, dn, inv_2eps));
         }
-        carry_g = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pinc), 63));
+        carry_g = lane63(pinc);
         cur = nxt;
     }
 }

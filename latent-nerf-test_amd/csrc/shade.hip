@@ -6,17 +6,17 @@
 //   k_shade_bwd<C, ORIENT>   recomputes the normal and the Lambert term, writes the gradient of all seven rows (one writer
 //                  each)
 //   ORIENT = true  the same with the orientation term fused in: orient[ray] = sum_i w_i max(0, n_i . v)^2, w the
-//                  compositing weight (scanned here, detached), its gradient added to dn before the projection
+//                  compositing weight (span_walk.h's, scanned here, detached), its gradient added to dn before the projection
+// The finite-difference normal and its backward projection are span_walk.h's, shared with normal_image.hip.
 //
 // All arithmetic is f32 + - * / sqrt in the stated order: the library is built with -ffp-contract=off and nothing here
 // is an explicit fmaf, so the numpy restatement matches bit for bit.
-#include "common.h"
+#include "span_walk.h"
 
 namespace lnerf {
 
-constexpr int FD_ROWS = 7;                   // the sample and its six neighbours
 constexpr int FD_BLOCK = 256;
-constexpr int FD_FLOATS = FD_ROWS * 3;       // floats of pts7 per sample
+constexpr int FD_FLOATS = FD_ROWS * 3;       // floats of pts7 per sample (FD_ROWS: the sample and its six neighbours)
 
 // One lane per sample.  The 21 floats of a sample are contiguous in pts7, so the 64 samples of a wave own one
 // contiguous span of 64 * 84 bytes: it is staged in LDS and stored with consecutive lanes on consecutive floats.
@@ -85,29 +85,18 @@ __device__ __forceinline__ Sample7<C> load_sample7(const float *__restrict__ sig
     for (int c = 0; c < C; ++c) k.alb[c] = 0.f;
     if (i < cnt) {
         const int64_t s7 = (off + i) * FD_ROWS;
-#pragma unroll
-        for (int j = 0; j < FD_ROWS; ++j) k.sg[j] = sigmas7[s7 + j];
+        load_fd_rows(sigmas7, s7, k.sg);
         load_row<C>(rgbs7, s7, k.alb);
     }
     return k;
 }
 
 // finite-difference normal of one sample and its Lambert term
-struct Lambert {
-    float n[3], s, r, d, lam;
+struct Lambert : FdNormal {
+    float d, lam;
 };
 __device__ __forceinline__ Lambert lambert_of(const float (&sg)[FD_ROWS], float inv_2eps, const Light &L) {
-    Lambert o;
-    float g[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) g[a] = (sg[1 + 2 * a] - sg[2 + 2 * a]) * inv_2eps;
-    o.s = (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
-    o.r = 1.0f / sqrtf(fmaxf(o.s, 1e-20f));          // (fmaxf: a NaN s gives the floor)
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float v = -(g[a] * o.r);
-        o.n[a] = v != v ? 0.f : v;
-    }
+    Lambert o = {fd_normal(sg, inv_2eps)};
     o.d = (o.n[0] * L.l[0] + o.n[1] * L.l[1]) + o.n[2] * L.l[2];
     o.lam = L.ambient + L.diffuse * (o.d > 0.f ? o.d : 0.f);
     return o;
@@ -135,26 +124,13 @@ __device__ __forceinline__ void view_dir(const float *__restrict__ rays_d, int64
     for (int a = 0; a < 3; ++a) v[a] = d[a] * r;
 }
 
-// dt of sample i of the span (0 past its end): the .x of the march's 8-byte (dt, t) pair
+// dt of sample i of the span (0 past its end)
 __device__ __forceinline__ float load_dt(const float *__restrict__ deltas, int64_t off, int cnt, int i) {
-    return i < cnt ? reinterpret_cast<const float2 *>(deltas)[off + i].x : 0.f;
-}
-
-// Compositing weight of this lane's sample, as composite_ray_fwd defines it, on `sigma` (scaled already) -- called by
-// ALL 64 lanes (lanes past the span pass zeros).  There is no early stop here: behind T < T_thresh the weights are 0 and
-// the chunks go on, every sample of the span still gets its rows.
-__device__ __forceinline__ float composite_weight(float sigma, float dt, bool valid, float T_thresh, float &carry) {
-    const float tau = sigma * dt;
-    const float inc = wave_inclusive_sum(tau);
-    const float excl = exclusive_depth(inc, carry);
-    const float T = expf(-excl);
-    const float alpha = 1.0f - expf(-tau);
-    carry += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(inc), 63));
-    return (valid && T >= T_thresh) ? alpha * T : 0.f;
+    return i < cnt ? load_step(deltas, off + i).dt : 0.f;
 }
 
 // max(0, n . v)
-__device__ __forceinline__ float facing_away(const Lambert &o, const float (&v)[3]) {
+__device__ __forceinline__ float facing_away(const FdNormal &o, const float (&v)[3]) {
     const float c = (o.n[0] * v[0] + o.n[1] * v[1]) + o.n[2] * v[2];
     return c > 0.f ? c : 0.f;
 }
@@ -174,7 +150,7 @@ struct OrientArgs<true> {
 // One wavefront per ray, lanes striding over the ray's samples; the next 64 samples' loads are requested before this
 // chunk's arithmetic (the kernel is a few memory round trips long, nothing else).
 // ORIENT: plus orient[id] = sum_i w_i q_i^2.  A ray without samples writes 0 (the buffer is uninitialised), so there is no
-// early return, and the chunk's arithmetic runs on ALL 64 lanes: composite_weight is a wave scan.
+// early return, and the chunk's arithmetic runs on ALL 64 lanes: span_weight is a wave scan.
 template <int C, bool ORIENT>
 __global__ void __launch_bounds__(256)
 k_shade_fwd(const float *__restrict__ sigmas7, const float *__restrict__ rgbs7, const int32_t *__restrict__ rays, int64_t N,
@@ -203,7 +179,7 @@ k_shade_fwd(const float *__restrict__ sigmas7, const float *__restrict__ rgbs7, 
             const Lambert o = lambert_of(cur.sg, inv_2eps, L);
             if (valid) store_shaded<C>(cur, o, L, off + i, sigma_c, colours);
             if constexpr (ORIENT) {
-                const float w = composite_weight(oa.density_scale * cur.sg[0], dt, valid, oa.T_thresh, carry);
+                const float w = span_weight((oa.density_scale * cur.sg[0]) * dt, valid, oa.T_thresh, carry).w;
                 const float q = facing_away(o, v);
                 acc += w * (q * q);
             }
@@ -232,15 +208,7 @@ __device__ __forceinline__ Grad7<C> load_grad7(const float *__restrict__ dsigma_
     if (i < cnt) {
         const int64_t s = off + i;
         k.dsig = dsigma_c[s];
-        // (written out, not load_row: at C = 1 both loads index with s, and through the helper k_shade_bwd<1> forms the
-        // two addresses in the other order -- the plain kernels' code is held fixed)
-        if (C == 4) {
-            const float4 v = reinterpret_cast<const float4 *>(dcolours)[s];
-            k.dcol[0] = v.x; k.dcol[1] = v.y; k.dcol[2] = v.z; k.dcol[C - 1] = v.w;
-        } else {
-#pragma unroll
-            for (int c = 0; c < C; ++c) k.dcol[c] = dcolours[s * C + c];
-        }
+        load_row<C>(dcolours, s, k.dcol);
     }
     return k;
 }
@@ -269,26 +237,13 @@ __device__ __forceinline__ void lambert_grad(const Sample7<C> &cur, const Grad7<
     for (int a = 0; a < 3; ++a) dn[a] = o.d > 0.f ? k * L.l[a] : 0.f;
 }
 
-// The backward's second half: dn -> the gradient of the six offset densities (through n = -g / |g|), and the seven rows of
-// both outputs of the sample whose first row is s7.
+// The backward's second half: the seven rows of both outputs of the sample whose first row is s7 (dn -> the six offset
+// densities' gradient is fd_normal_backward).
 template <int C>
 __device__ __forceinline__ void project_and_store(const Lambert &o, const float (&dn)[3], float dsig, const float (&dalb)[C],
                                                   float inv_2eps, int64_t s7, float *__restrict__ dsigmas7,
                                                   float *__restrict__ drgbs7) {
-    const float ndn = (o.n[0] * dn[0] + o.n[1] * dn[1]) + o.n[2] * dn[2];
-    const bool project = o.s > 1e-20f;
-    float ds[FD_ROWS];
-    ds[0] = dsig;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float t = project ? dn[a] - o.n[a] * ndn : dn[a];
-        const float dg = -(o.r * t);
-        const float v = dg * inv_2eps;
-        ds[1 + 2 * a] = v;
-        ds[2 + 2 * a] = -v;
-    }
-#pragma unroll
-    for (int j = 0; j < FD_ROWS; ++j) dsigmas7[s7 + j] = ds[j];
+    store_fd_rows(dsigmas7, s7, dsig, fd_normal_backward(o, dn, inv_2eps));
     store_row<C>(drgbs7, s7, dalb);
     if (C == 4) {
         float4 *row = reinterpret_cast<float4 *>(drgbs7) + s7;
@@ -339,7 +294,7 @@ k_shade_bwd(const float *__restrict__ sigmas7, const float *__restrict__ rgbs7, 
         if (ORIENT || valid) {
             const Lambert o = lambert_of(cur.sg, inv_2eps, L);
             float w = 0.f;
-            if constexpr (ORIENT) w = composite_weight(oa.density_scale * cur.sg[0], dt, valid, oa.T_thresh, carry);
+            if constexpr (ORIENT) w = span_weight((oa.density_scale * cur.sg[0]) * dt, valid, oa.T_thresh, carry).w;
             if (valid) {
                 float dn[3], dalb[C];
                 lambert_grad<C>(cur, gcur, o, L, dn, dalb);

@@ -1,7 +1,8 @@
 """References of the distortion loss of the training renders (csrc/distortion.hip; contract in include/lnerf_hip.h,
 "distortion loss"):  loss[ray] = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 dt_i.
 
-  weights()             w, T, tau per span row (float64), the kernel's kill rule T >= T_thresh
+  weights()             w, T, tau per span row (float64), the kernel's kill rule T >= T_thresh (tests/span_reference.py,
+                        which also holds span_rows(), per_ray_max() and the chunk's exclusive sum)
   double_sum()          the DEFINITION in float64: the O(k^2) double sum over the unshifted mid-points m = t + dt / 2 --
                         no prefix sums, no shift by t_0, nothing of the kernels' algebra
   double_sum_torch()    the same double sum in torch (float64 in the tests), weights NOT detached: its autograd gives the
@@ -15,36 +16,16 @@
 import numpy as np
 import torch
 
+from tests import span_reference as S
+from tests.span_reference import CHUNK, per_ray_max, span_rows    # (the tests reach them through this module)
+
 T_THRESH = 1e-4
-CHUNK = 64
-
-
-def span_rows(rays):
-    """rays [N,3] -> (rows int64 [m], ids int64 [m]) of every span row, ray after ray."""
-    rows, ids = [], []
-    for rid, off, cnt in np.asarray(rays).tolist():
-        rows.append(np.arange(off, off + cnt, dtype=np.int64))
-        ids.append(np.full(cnt, rid, dtype=np.int64))
-    if not rows:
-        return np.zeros(0, np.int64), np.zeros(0, np.int64)
-    return np.concatenate(rows), np.concatenate(ids)
 
 
 def weights(sigmas, deltas, rays, T_thresh=T_THRESH):
-    """float64 compositing weights of every span row (ray order): tau = sigma dt, T = exp(-sum of the taus in front),
-    w = T >= T_thresh ? (1 - exp(-tau)) T : 0.  -> (w, T, tau)."""
-    sig = np.asarray(sigmas, dtype=np.float32).astype(np.float64)
-    dt = np.asarray(deltas, dtype=np.float32).astype(np.float64)[:, 0]
-    w, T, tau = [], [], []
-    for _, off, cnt in np.asarray(rays).tolist():
-        t = sig[off:off + cnt] * dt[off:off + cnt]
-        excl = np.concatenate([[0.0], np.cumsum(t)[:-1]]) if cnt else np.zeros(0)
-        Tr = np.exp(-excl)
-        w.append(np.where(Tr >= float(T_thresh), (1.0 - np.exp(-t)) * Tr, 0.0))
-        T.append(Tr)
-        tau.append(t)
-    cat = lambda v: np.concatenate(v) if v else np.zeros(0)
-    return cat(w), cat(T), cat(tau)
+    """float64 compositing weights of every span row (ray order) -> (w, T, tau): span_reference.weights."""
+    return S.weights(sigmas, deltas, rays, T_thresh)
+
 
 
 def double_sum(sigmas, deltas, rays, n_ids, T_thresh=T_THRESH):
@@ -82,13 +63,6 @@ def double_sum_torch(sigma_rows, deltas, rays, n_ids, T_thresh=T_THRESH):
     return loss
 
 
-def _excl(x, carry, dtype):
-    """One chunk: the inclusive sum, the exclusive one (previous lane's inclusive, lane 0: 0, plus the carry), the carry after."""
-    inc = np.cumsum(x, dtype=dtype)
-    prev = np.concatenate([np.zeros(1, dtype), inc[:-1]]).astype(dtype)
-    return inc, (prev + carry).astype(dtype), dtype(carry + inc[-1])
-
-
 def restate(sigmas, deltas, rays, n_ids, T_thresh=T_THRESH, d_loss=None, dtype=np.float32):
     """The header's order of operations in `dtype` -> dict(loss [n_ids], sums [n_ids,2], w [m], live [m], m [m] in ray
     order, and with d_loss [n_ids]: dsigmas [m], the gradient rows of every span)."""
@@ -109,15 +83,15 @@ def restate(sigmas, deltas, rays, n_ids, T_thresh=T_THRESH, d_loss=None, dtype=n
                 s = slice(off + base, off + min(base + CHUNK, cnt))
                 dt, t = d[s, 0], d[s, 1]
                 tau = sig[s] * dt
-                _, excl, c_tau = _excl(tau, c_tau, dtype)
+                _, excl, c_tau = S.chunk_excl(tau, c_tau, dtype)
                 T = np.exp(-excl).astype(dtype)
                 e = np.exp(-tau).astype(dtype)
                 alpha = dtype(1) - e
                 live = T >= thr
                 w = np.where(live, alpha * T, dtype(0)).astype(dtype)
                 m = (t - t0) + dtype(0.5) * dt
-                _, A, c_A = _excl(w, c_A, dtype)
-                _, B, c_B = _excl(w * m, c_B, dtype)
+                _, A, c_A = S.chunk_excl(w, c_A, dtype)
+                _, B, c_B = S.chunk_excl(w * m, c_B, dtype)
                 u = m * A - B
                 acc = dtype(acc + (w * (dtype(2) * u + third * (w * dt))).sum(dtype=dtype))
                 rec.append((dt, w, m, u, T * e, live))
@@ -148,16 +122,6 @@ def reference_gradient(sigmas, deltas, rays, n_ids, d_loss, T_thresh=T_THRESH):
     (loss * torch.from_numpy(np.asarray(d_loss, dtype=np.float32)).double()).sum().backward()
     grad = sg.grad if sg.grad is not None else torch.zeros_like(sg)
     return loss.detach().numpy(), grad.numpy()
-
-
-def per_ray_max(values, rays, n_ids):
-    """values [m] in span-row order -> per ray id the largest |value| of its span (0 for an empty span / an absent id)."""
-    out, at = np.zeros(int(n_ids)), 0
-    for rid, _, cnt in np.asarray(rays).tolist():
-        if cnt:
-            out[rid] = float(np.abs(values[at:at + cnt]).max())
-        at += cnt
-    return out
 
 
 def f32_errors(sigmas, deltas, rays, n_ids, d_loss, T_thresh=T_THRESH):

@@ -2,7 +2,8 @@
 include/lnerf_hip.h, "composited normal image"):  normal_image[ray] = sum_i w_i n_i,  loss[p] = (sum_c (right - own)^2,
 sum_c (below - own)^2).
 
-  fd_normal()           the finite-difference normal of lnerf_shade_fd_forward for any dtype (a NaN component becomes 0)
+  fd_normal()           the finite-difference normal of lnerf_shade_fd_forward for any dtype (tests/span_reference.py, which
+                        also holds its backward, span_rows(), per_ray_max() and the chunk's exclusive sum)
   truth()               float64, no chunks, nothing of the kernels' algebra: the weights by a plain cumulative sum, the
                         forward as a plain sum, the backward with the suffix sums sum_{j>i} g_j w_j written out -- NOT the
                         identity sum_i g_i w_i = N . dN the kernel's one sweep rests on
@@ -18,57 +19,10 @@ sum_c (below - own)^2).
   op_case() / check_case()   the op-level input of tests/test_gpu_normal_image.py and its preconditions"""
 import numpy as np
 
+from tests import span_reference as S
+from tests.span_reference import CHUNK, FLOOR, fd_normal, per_ray_max, span_rows    # (the tests reach them through this module)
+
 T_THRESH = 1e-4
-CHUNK = 64
-FLOOR = np.float32(1e-20)
-
-
-def span_rows(rays):
-    """rays [N,3] -> (rows int64 [m], ids int64 [m]) of every span row, ray after ray."""
-    rows, ids = [], []
-    for rid, off, cnt in np.asarray(rays).tolist():
-        rows.append(np.arange(off, off + cnt, dtype=np.int64))
-        ids.append(np.full(cnt, rid, dtype=np.int64))
-    if not rows:
-        return np.zeros(0, np.int64), np.zeros(0, np.int64)
-    return np.concatenate(rows), np.concatenate(ids)
-
-
-def per_ray_max(values, rays, n_ids):
-    """values [m] or [m, k] in span-row order -> per ray id the largest |value| of its span (0 for an empty span / absent id)."""
-    out, at = np.zeros(int(n_ids)), 0
-    for rid, _, cnt in np.asarray(rays).tolist():
-        if cnt:
-            out[rid] = float(np.abs(values[at:at + cnt]).max())
-        at += cnt
-    return out
-
-
-def fd_normal(sg, inv_2eps, dtype):
-    """sg [m,7] -> (n [m,3], s2 [m], r [m]) in `dtype`, the order of lnerf_shade_fd_forward."""
-    sg = np.asarray(sg, dtype=np.float32).astype(dtype)
-    k = dtype(np.float32(inv_2eps))
-    with np.errstate(all="ignore"):
-        g = [((sg[:, 1 + 2 * a] - sg[:, 2 + 2 * a]) * k).astype(dtype) for a in range(3)]
-        s2 = ((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]).astype(dtype)
-        r = (dtype(1) / np.sqrt(np.fmax(s2, dtype(FLOOR)))).astype(dtype)      # (fmax: a NaN s2 gives the floor)
-        n = np.stack([-(g[a] * r) for a in range(3)], -1).astype(dtype)
-        n = np.where(np.isnan(n), dtype(0), n).astype(dtype)
-    return n, s2, r
-
-
-def _normal_backward(n, s2, r, dn, inv_2eps, dtype):
-    """dn [m,3] -> the six stencil rows [m,6] (+x, -x, +y, -y, +z, -z), the order of lnerf_shade_fd_backward."""
-    k = dtype(np.float32(inv_2eps))
-    with np.errstate(all="ignore"):
-        q = ((n[:, 0] * dn[:, 0] + n[:, 1] * dn[:, 1]) + n[:, 2] * dn[:, 2]).astype(dtype)
-        project = s2 > dtype(FLOOR)                                            # (False for a NaN s2)
-        out = np.zeros((n.shape[0], 6), dtype)
-        for a in range(3):
-            t = np.where(project, dn[:, a] - n[:, a] * q, dn[:, a]).astype(dtype)
-            v = ((-(r * t)) * k).astype(dtype)
-            out[:, 2 * a], out[:, 2 * a + 1] = v, -v
-    return out
 
 
 def _inputs(sigmas7, deltas, dtype):
@@ -103,20 +57,13 @@ def truth(sigmas7, deltas, rays, n_ids, inv_2eps, density_scale, T_thresh=T_THRE
             dtau = np.where(live, g * T * e - after, 0.0)
             rows = np.zeros((cnt, 7))
             rows[:, 0] = ds * dt * dtau
-            rows[:, 1:] = _normal_backward(n, s2, r, w[:, None] * go[None, :], inv_2eps, np.float64)
+            rows[:, 1:] = S.normal_backward(n, s2, r, w[:, None] * go[None, :], inv_2eps, np.float64)
             grads.append(rows)
     cat = lambda v, shape: np.concatenate(v) if v else np.zeros(shape)
     out = dict(image=image, w=cat(ws, 0), T=cat(Ts, 0), live=cat(lives, 0).astype(bool), n=cat(ns, (0, 3)), r=cat(rs, 0))
     if dN is not None:
         out["grad"] = cat(grads, (0, 7))
     return out
-
-
-def _excl(x, carry, dtype):
-    """One chunk: the exclusive sum (previous lane's inclusive, lane 0: 0, plus the carry) and the carry after."""
-    inc = np.cumsum(x, dtype=dtype)
-    prev = np.concatenate([np.zeros(1, dtype), inc[:-1]]).astype(dtype)
-    return (prev + carry).astype(dtype), dtype(carry + inc[-1])
 
 
 def restate(sigmas7, deltas, rays, n_ids, inv_2eps, density_scale, T_thresh=T_THRESH, dN=None, dtype=np.float32):
@@ -134,7 +81,7 @@ def restate(sigmas7, deltas, rays, n_ids, inv_2eps, density_scale, T_thresh=T_TH
                 n, s2, r = fd_normal(sg[s], inv_2eps, dtype)
                 dt = d[s, 0]
                 tau = ((ds * sg[s, 0]).astype(dtype) * dt).astype(dtype)
-                excl, carry = _excl(tau, carry, dtype)
+                _, excl, carry = S.chunk_excl(tau, carry, dtype)
                 T = np.exp(-excl).astype(dtype)
                 e = np.exp(-tau).astype(dtype)
                 alpha = dtype(1) - e
@@ -156,7 +103,7 @@ def restate(sigmas7, deltas, rays, n_ids, inv_2eps, density_scale, T_thresh=T_TH
                     dtau = np.where(live, g * Te - (total - P), dtype(0)).astype(dtype)
                     rows = np.zeros((len(w), 7), dtype)
                     rows[:, 0] = (ds * dt).astype(dtype) * dtau
-                    rows[:, 1:] = _normal_backward(n, s2, r, (w[:, None] * go[None, :]).astype(dtype), inv_2eps, dtype)
+                    rows[:, 1:] = S.normal_backward(n, s2, r, (w[:, None] * go[None, :]).astype(dtype), inv_2eps, dtype)
                     grads.append(rows)
     cat = lambda v, t, shape: np.concatenate(v).astype(t) if v else np.zeros(shape, t)
     out = dict(image=image, w=cat(ws, dtype, 0), live=cat(lives, bool, 0))

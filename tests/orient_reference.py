@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from tests import shading_reference as R
+from tests import span_reference as S
 
 FLOOR = 1e-20
 
@@ -44,12 +45,8 @@ def sample_terms(sigmas7, rays, shade, rays_per_view, inv_2eps, rays_d, dtype=np
     light, ambient, tl = rec[:, :3], rec[:, 3], rec[:, 4] != 0
     sg = np.asarray(sigmas7, dtype=np.float32).reshape(-1, 7)[rows].astype(dtype)
     inv = dtype(np.float32(inv_2eps))
+    n, s, r = S.fd_normal(sg, inv_2eps, dtype)
     with np.errstate(all="ignore"):
-        g = np.stack([(sg[:, 1 + 2 * a] - sg[:, 2 + 2 * a]) * inv for a in range(3)], -1)
-        s = (g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]) + g[:, 2] * g[:, 2]
-        r = dtype(1.0) / np.sqrt(np.fmax(s, dtype(FLOOR)))
-        n = -(g * r[:, None])
-        n = np.where(n != n, dtype(0.0), n).astype(dtype)
         d = _dot3(n, light)
         lam = ambient + (dtype(1.0) - ambient) * np.where(d > 0, d, dtype(0.0))
         v = view_dirs(rays_d, dtype)[ids]
@@ -60,21 +57,9 @@ def sample_terms(sigmas7, rays, shade, rays_per_view, inv_2eps, rays_d, dtype=np
 
 
 def weights(sigma_c, deltas, rays, density_scale, T_thresh):
-    """float64 compositing weights of every span row (ray order) on sigma' = density_scale * sigma_c:
-    tau = sigma' dt, T = exp(-sum of the taus in front), w = T >= T_thresh ? (1 - exp(-tau)) T : 0.  -> (w, T, tau)."""
-    rows, _ = R._span_rows(rays)
-    sig = np.asarray(sigma_c, dtype=np.float32).astype(np.float64)
-    dt = np.asarray(deltas, dtype=np.float32).astype(np.float64)[:, 0]
-    w, T, tau = (np.zeros(len(rows)) for _ in range(3))
-    at = 0
-    for _, off, cnt in np.asarray(rays).tolist():
-        t = (float(density_scale) * sig[off:off + cnt]) * dt[off:off + cnt]
-        excl = np.concatenate([[0.0], np.cumsum(t)[:-1]]) if cnt else np.zeros(0)
-        Tr = np.exp(-excl)
-        w[at:at + cnt] = np.where(Tr >= float(T_thresh), (1.0 - np.exp(-t)) * Tr, 0.0)
-        T[at:at + cnt], tau[at:at + cnt] = Tr, t
-        at += cnt
-    return w, T, tau
+    """float64 compositing weights of every span row (ray order) on sigma' = density_scale * sigma_c -> (w, T, tau):
+    span_reference.weights."""
+    return S.weights(sigma_c, deltas, rays, T_thresh, density_scale)
 
 
 def orient_forward(sigmas7, rays, shade, rays_per_view, inv_2eps, deltas, rays_d, density_scale, T_thresh, n_ids):
@@ -88,16 +73,8 @@ def orient_forward(sigmas7, rays, shade, rays_per_view, inv_2eps, deltas, rays_d
 
 def _project(t, dn, dtype):
     """dn [m,3] -> the six offset rows of dsigmas7 (columns 1..6 of [m,7]; column 0 is left 0), the kernel's op order."""
-    n, s, r, inv = t["n"], t["s"], t["r"], t["inv"]
-    with np.errstate(all="ignore"):
-        qq = _dot3(n, dn)
-        tt = np.where((s > dtype(FLOOR))[:, None], dn - n * qq[:, None], dn)
-        dg = -(r[:, None] * tt)
-        vv = dg * inv
-    ds = np.zeros((len(s), 7), dtype=dtype)
-    for a in range(3):
-        ds[:, 1 + 2 * a] = vv[:, a]
-        ds[:, 2 + 2 * a] = -vv[:, a]
+    ds = np.zeros((len(t["s"]), 7), dtype=dtype)
+    ds[:, 1:] = S.normal_backward(t["n"], t["s"], t["r"], dn.astype(dtype), t["inv"], dtype)
     return ds
 
 

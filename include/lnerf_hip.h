@@ -109,6 +109,10 @@ int lnerf_packbits(const float *grid, int64_t n_cells, float thresh, const float
  *                        zeroed it (zero it when the buffer is allocated): the peak a training loop sizes its sample
  *                        buffers from, kept without a launch of its own,
  *                        [4 ...) scratch of the call (two-launch form: per-ray counts, per-workgroup sums)
+ *   the step, ONE rule for the training march and lnerf_march_rays: dt(t) = fminf(fmaxf(t * dt_gamma, dt_min), dt_max)
+ *     with dt_min = 2 sqrt(3) / max_steps and dt_max = 2 sqrt(3) 2^(cascade-1) / grid_size, also at dt_gamma = 0
+ *     (the closed-form lattice t_k = t0 + k dt(0), dt(0) computed once on the host).  Where dt_min > dt_max, that is
+ *     max_steps < grid_size / 2^(cascade-1), the rule yields dt_max everywhere.
  *   jitter of the march start t0 = near + dt(near) * u_n, one of
  *     noises [N] in [0,1)          the upstream form (`noises = torch.rand(N)`);
  *     noise_counter (device int32) counter-based generator: u_n = hash(n, noise_seed, *noise_counter) in [0,1)

@@ -120,6 +120,7 @@ struct MarchParams {
     float dt_gamma;
     float dt_min;
     float dt_max;
+    float dt_uniform;   // the step at dt_gamma = 0: clampf(0, dt_min, dt_max), which is dt_max where dt_min > dt_max
 };
 
 // x already clamped to [-bound, bound].  Op order mirrors oracle/nerf_oracle.py::march_cell_index.
@@ -389,7 +390,7 @@ k_march_train(MarchRays R, int64_t N, const uint8_t *__restrict__ bitfield, Marc
                 // -- the pass is a chain of dependent L2 round trips (one per chunk, ~16 per ray), this makes it ~16 / MARCH_CHUNKS.  Chunks
                 // past the ray's end read a clamped (valid) cell and are ignored; the decisions and their order are those
                 // of the one-chunk loop below.
-                const float dt = P.dt_min;
+                const float dt = P.dt_uniform;   // the one step rule at t * dt_gamma = 0
                 bool done = false;
                 for (int base = 0; base < (1 << 22) && !done; base += 64 * MARCH_CHUNKS) {  // bound: a non-finite `far` must not spin
                     float tj[MARCH_CHUNKS], xj[MARCH_CHUNKS], yj[MARCH_CHUNKS], zj[MARCH_CHUNKS];
@@ -823,6 +824,7 @@ static MarchParams make_params(float bound, int cascade, int G, int max_steps, f
     P.dt_gamma = dt_gamma;
     P.dt_min = (float)(2.0 * 1.7320508075688772 / (double)max_steps);
     P.dt_max = (float)(2.0 * 1.7320508075688772 * (double)(1 << (cascade - 1)) / (double)G);
+    P.dt_uniform = fminf(fmaxf(0.0f, P.dt_min), P.dt_max);   // clampf's order of min and max
     return P;
 }
 

@@ -255,7 +255,9 @@ def march_rays_train(rays_o, rays_d, nears, fars, bitfield, bound: float, cascad
     t_{k+1} = t_k + clamp(t_k*dt_gamma, dt_min, dt_max) while t_k < far, and emit a sample
     at every lattice point whose occupancy bit is set, up to `max_steps` samples per ray.
     (Skipping empty voxels, as marching implementations do, never leaves this lattice, so
-    the emitted set is the same.)  With dt_gamma == 0 the lattice is t_k = t_0 + k*dt_min.
+    the emitted set is the same.)  With dt_gamma == 0 the lattice is t_k = t_0 + k*dt with the same
+    rule's dt = clamp(0, dt_min, dt_max): dt_min, or dt_max where dt_min > dt_max (max_steps <
+    G / 2^(cascade-1)), as the recurrence and the inference march step there.
 
     Returns xyzs [M,3], dirs [M,3], deltas [M,2] = (dt_k, t_k), rays int32 [N,3] =
     (ray id, offset, count) in ray order, and M."""
@@ -285,11 +287,12 @@ def march_rays_train(rays_o, rays_d, nears, fars, bitfield, bound: float, cascad
     if dt_gamma == 0.0:
         # number of lattice points any ray can have before reaching far
         span = (far - t0).clamp_min(0)
-        K = int(torch.ceil(span.max() / dt_min).item()) + 2 if N > 0 else 0
+        dtu = torch.clamp(torch.zeros((), dtype=f32), dt_min, dt_max)  # the one step rule; dt_max where dt_min > dt_max
+        K = int(torch.ceil(span.max() / dtu).item()) + 2 if N > 0 else 0
         k = torch.arange(K, dtype=f32)
-        t = k[None, :] * dt_min
+        t = k[None, :] * dtu
         t = t + t0[:, None]  # [N,K]
-        dt = dt_min.expand(N, K)
+        dt = dtu.expand(N, K)
     else:
         ts, dts = [], []
         tcur = t0.clone()

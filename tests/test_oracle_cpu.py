@@ -272,20 +272,49 @@ def _march_in_chunks(n_step, ro, rd, nears, fars, bits, bound, cascade, G, max_s
     return per_ray
 
 
-@pytest.mark.parametrize("bound,cascade,dt_gamma", [(1.0, 1, 1.0 / 64), (2.0, 2, 1.0 / 128)])
-def test_infer_march_in_chunks_equals_training_march(bound, cascade, dt_gamma):
+def _assert_same_ray_samples(got, want, dt_gamma):
+    """Rows (xyz, dir, dt, t) of one ray from the inference march in chunks against the training march's.  With
+    dt_gamma > 0 both walk the recurrence: bit for bit.  At dt_gamma = 0 the training march takes lattice point k in
+    closed form, fl(fl(k dt) + t0), and the inference march by k additions, so t is the same number only up to their
+    roundings: the step and the direction are bit for bit, t within (k / 2 + 1) 2^-24 t (half an ulp per addition
+    against two roundings), x within that times |d| plus the two roundings of o + t d on either side."""
+    if dt_gamma > 0:
+        assert torch.equal(got, want)
+        return
+    assert torch.equal(got[:, 3:7], want[:, 3:7])
+    g, w = got.double(), want.double()
+    k = torch.round(w[:, 7] / w[:, 6])           # at most t / dt lattice points lie before a sample (near >= 0)
+    tol_t = (k / 2 + 1) * 2.0 ** -24 * w[:, 7].clamp_min(1.0)
+    assert bool(((g[:, 7] - w[:, 7]).abs() <= tol_t).all()), float(((g[:, 7] - w[:, 7]).abs() / tol_t).max())
+    tol_x = w[:, 3:6].abs() * tol_t[:, None] + 2.0 ** -23 * (w[:, :3].abs() + (w[:, 7:8] * w[:, 3:6]).abs())
+    assert bool(((g[:, :3] - w[:, :3]).abs() <= tol_x).all())
+
+
+@pytest.mark.parametrize("bound,cascade,dt_gamma,G,max_steps", [
+    pytest.param(1.0, 1, 1.0 / 64, 16, 96, id="1.0-1-0.015625"),
+    pytest.param(2.0, 2, 1.0 / 128, 16, 96, id="2.0-2-0.0078125"),
+    # dt_min > dt_max (max_steps < G / 2^(cascade-1)): one step rule, dt_max, in both marches -- at dt_gamma = 0 too
+    pytest.param(1.0, 1, 0.0, 64, 16, id="inverted-64-16"),
+    pytest.param(1.0, 1, 0.0, 128, 64, id="inverted-128-64"),
+    pytest.param(1.0, 1, 1.0 / 64, 64, 16, id="inverted-64-16-gamma"),
+])
+def test_infer_march_in_chunks_equals_training_march(bound, cascade, dt_gamma, G, max_steps):
     """With dt_gamma > 0 both marches walk t = t + clamp(t*dt_gamma, dt_min, dt_max) from near: the inference march,
-    restarted from the handed-over rays_t every n_step samples, emits exactly the training march's samples."""
-    G, max_steps = 16, 96
+    restarted from the handed-over rays_t every n_step samples, emits exactly the training march's samples.  At
+    dt_gamma = 0 they emit the same samples with the same step, t to the rounding of the two lattice forms
+    (_assert_same_ray_samples)."""
     g = torch.Generator().manual_seed(11)
     bits = O.packbits((torch.rand(cascade * G ** 3, generator=g) < 0.8).float(), 0.5)
     ro, rd = _infer_scene(N=120, bound=bound)
     nears, fars = O.near_far_from_aabb(ro, rd, [-bound] * 3 + [bound] * 3, 0.1)
     xyzs, dirs, deltas, rays, M = O.march_rays_train(ro, rd, nears, fars, bits, bound, cascade, G, max_steps,
                                                      dt_gamma, None)
-    # rays span several calls of every n_step, and with bound 2 the per-ray cap binds
-    assert int(rays[:, 2].max()) == max_steps if bound > 1 else int(rays[:, 2].max()) > 3 * 8
+    # rays span several calls of every n_step, and with bound 2 (or a small max_steps) the per-ray cap binds
+    assert int(rays[:, 2].max()) == max_steps if (bound > 1 or max_steps < 96) else int(rays[:, 2].max()) > 3 * 8
     assert int((rays[:, 2] == 0).sum()) >= 120 // 5  # and the misses have no samples
+    if max_steps < G:   # the inverted regime: every step is dt_max
+        dt_max = torch.tensor(2.0 * O.SQRT3 * (2 ** (cascade - 1)) / G, dtype=torch.float32)
+        assert 2.0 * O.SQRT3 / max_steps > float(dt_max) and bool((deltas[:, 0] == dt_max).all())
     want = torch.cat([xyzs, dirs, deltas], -1)
     for n_step in (1, 3, 8):
         per_ray = _march_in_chunks(n_step, ro, rd, nears, fars, bits, bound, cascade, G, max_steps, dt_gamma)
@@ -293,7 +322,7 @@ def test_infer_march_in_chunks_equals_training_march(bound, cascade, dt_gamma):
             o, c = int(rays[n, 1]), int(rays[n, 2])
             assert len(per_ray[n]) == c, (n_step, n, len(per_ray[n]), c)
             if c:
-                assert torch.equal(torch.stack(per_ray[n]), want[o:o + c]), (n_step, n)
+                _assert_same_ray_samples(torch.stack(per_ray[n]), want[o:o + c], dt_gamma)
 
 
 def test_infer_march_padding_and_dead_entries():

@@ -74,6 +74,10 @@ const char *lnerf_build_info(void);
  *   "mlp_fwd_blocks":          persistent workgroups of the bf16 MLP forward (default 768).
  *   "mlp_fwd_wps":             wavefronts per SIMD the bf16 forward is compiled for, 3 (default) or 2.
  *   "mlp_bwd_blocks":          persistent workgroups of the MLP backward (default and maximum 512 = slab count).
+ * and one switch between two forms of the same result (any value is taken as on / off):
+ *   "adam_skip":               1 (default) = the fused table update leaves 16-row groups with all-zero moments and zero
+ *                              gradient alone where a moment map is bound (lnerf_moment_map_bind); 0 = the map is still
+ *                              maintained, every group takes the step.  Bit-identical either way.
  */
 int lnerf_set_tuning(const char *key, int value);
 
@@ -665,6 +669,23 @@ int lnerf_grid_encode_backward_adam_tail(const float *xyzs, float bound, const v
                                          float *const *exp_avg_sq_host, float mlp_lr, const int32_t *const *maps_host,
                                          float beta1, float beta2, float eps, int step, int32_t *step_dev, float grad_scale,
                                          int flags, lnerf_stream_t stream);
+/* ---- moment map of the fused table update (additive to ABI 7).  With g = +-0, m = v = +0 the Adam step returns m, v and
+ * p as they were, bit for bit (finite lr, eps > 0), so a 16-row group of the table whose moments are all-zero bits and
+ * which gets no gradient needs no load and no store: the part of the table no sample has ever reached.  The map holds one
+ * byte per (bucket, 16-row group) of the scatter's bucket plan -- level l, bucket b (4096 rows from the level's first
+ * row), group g = row in bucket >> 4 at byte ((buckets of the levels below l) + b) * 256 + g -- and after every fused
+ * step  byte != 0  <=>  some exp_avg / exp_avg_sq word of the group has a non-zero bit pattern (-0.0 counts).
+ *   lnerf_moment_map_bytes  size of the map of a level table (0: not plannable).
+ *   lnerf_moment_map_build  one streaming launch that computes every byte from the moments.
+ *   lnerf_moment_map_bind   binds `map` to the optimiser state whose first moment is `exp_avg` (process-wide registry
+ *     under a mutex; a null map unbinds).  lnerf_grid_encode_backward_adam / _adam_tail look their exp_avg up: with a
+ *     binding pass 2 skips clean groups without gradient and keeps the map current; without one they behave as before.
+ * The owner keeps the map valid: whatever else writes the moments (lnerf_adam_step, a copy) makes it stale -- rebuild
+ * it on the same stream before the next fused call, or unbind.  Unbind before the map or the moments are freed. */
+size_t lnerf_moment_map_bytes(int num_levels, const int32_t *offsets_host);
+int lnerf_moment_map_build(const float *exp_avg, const float *exp_avg_sq, int num_levels, int level_dim,
+                           const int32_t *offsets_host, void *map, size_t map_bytes, lnerf_stream_t stream);
+int lnerf_moment_map_bind(const float *exp_avg, void *map, size_t map_bytes);
 int lnerf_cast_f32_to_bf16(const float *src, void *dst, int64_t n, lnerf_stream_t stream);
 
 /* ---- iso-surface extraction (marching cubes): NeRFRenderer.export_mesh's kernel (the upstream renderer runs

@@ -3,6 +3,10 @@
 // the passes share: grid_shared.h.
 #include "grid_shared.h"
 
+#include <math.h>
+#include <mutex>
+#include <unordered_map>
+
 namespace lnerf {
 
 // Pass 2.  LDS float atomics run at ~0.5 lane/clk on gfx950 while integer LDS atomics run at the
@@ -25,7 +29,22 @@ struct FusedUpdate {
     AdamArgs a;
     uint16_t *grad_out;  // when set: no Adam step -- every row's finished sum is WRITTEN as bf16 here instead (the wire
                          // format of the data-parallel all-reduce: no zero fill, no read-modify-write, no cast)
+    uint8_t *live;       // optional MOMENT MAP (null: every row takes the step, nothing is kept): one byte per 16-row group
+                         // of a bucket, at (global bucket) * LIVE_GROUPS + (row in bucket >> 4); after every fused step
+                         // byte != 0 <=> some m or v word of the group has a non-zero BIT pattern
+    int skip;            // with a map: a group whose byte is 0 and whose 16 gradients are all zero is left alone (0: every
+                         // group takes the step, the map is only maintained)
 };
+// A group with m = v = +0 (all-zero bits) and g = +-0 comes out of adam_one as it went in: m' = fma(b1, +0, +-0) = +0,
+// v' = +0, p' = p - (lr * 0) * rcp(0 + eps) = p bit for bit (finite lr, eps > 0: the host side checks both), and the bf16
+// shadow, which equals bf16(p) already, stays valid.  Such a group needs no load and no store.  -0.0 in a moment counts
+// as non-zero: the un-skipped arithmetic would turn it into +0.0.  Nothing crosses workgroups: a bucket's bytes are read
+// for use, and written, only by the workgroup that finishes the bucket in that launch.
+constexpr int LIVE_SHIFT = 4, LIVE_GROUPS = BK_ROWS >> LIVE_SHIFT;   // 16 rows = 128 B each of p, m, v; 256 bytes per bucket
+static_assert(LIVE_GROUPS == 256, "the moment map's layout is part of the C ABI (lnerf_moment_map_bytes)");
+__device__ __forceinline__ uint32_t f4_bits(const float4 &x) {
+    return __float_as_uint(x.x) | __float_as_uint(x.y) | __float_as_uint(x.z) | __float_as_uint(x.w);
+}
 
 // power-of-two scale of a level's fixed-point sums: |value| < 2^(e-126) (e = biased exponent of the level's bound
 // found by pass 1) is scaled by 2^(BITS+126-e), which puts every addend below 2^BITS; split so that both factors are
@@ -203,6 +222,7 @@ __shared__ long long s_acc[BK_ROWS * 2];                   // [feature][row]: a 
 template <int NW> __shared__ int s_red[NW];                 // the slice decision's record count; merge_slices' arrival value
 template <int NW> __shared__ uint32_t s_bmp[NW][128];      // per wave: segment-start bitmap of a sub-batch (4096 records)
 template <int NW> __shared__ uint32_t s_soff[NW][64];      // per wave: (chunk slot - flat start) of its non-empty segments
+__shared__ uint32_t s_live[BK_ROWS >> 6];                  // the bucket's bytes of the moment map as they were before this step
 // The workspace as both passes and the step's tail see it (by value; built once per call on the host: scatter_ws)
 struct ScatterWs {
     unsigned int *gmax;                // level maxima, CUR_STRIDE words apart (raised by pass 1)
@@ -438,20 +458,54 @@ template <int RT> __device__ __forceinline__ void finish_wire(const UnFix &t, ui
         go[r] = bf16_pair(g.x, g.y);
     }
 }
-// the Adam step row by row (a partial bucket, an odd first row, the last arriver of a sliced bucket)
+// The moment map's rule, the ONE definition both Adam finishers use.  PER consecutive lanes of a wave hold a group (8: a
+// row pair each, 16: a row each); call both parts with the whole wave.
+template <int PER> __device__ __forceinline__ uint32_t group_slice(unsigned long long ballot, int lane) {
+    return (uint32_t)(ballot >> (lane & (64 - PER))) & ((1u << PER) - 1u);
+}
+// a group's byte as it was before this step (s_live: filled by reduce_bucket in front of a barrier; zeros without a map)
+__device__ __forceinline__ uint32_t old_byte(int group) { return reinterpret_cast<const uint8_t *>(s_live)[group]; }
+struct GroupStep { bool step, first; };   // the group takes the step / as a FIRST TOUCH: m = v = +0 are known, p is not loaded yet
+template <int PER>
+__device__ __forceinline__ GroupStep group_step(const FusedUpdate &fu, uint32_t old_byte, bool g_nonzero, int lane) {
+    const bool live = !fu.live || !fu.skip || old_byte != 0u;
+    const bool nz = group_slice<PER>(__ballot(g_nonzero), lane) != 0u;
+    return {live || nz, !live};
+}
+// the group's new byte = "any non-zero bit in its new m | v" (it falls back to 0 when the moments have decayed to +0); one
+// lane per group writes it, and only when it changes
+template <int PER>
+__device__ __forceinline__ void group_mark(uint8_t *byte_at, uint32_t old_byte, bool stepped, uint32_t mv_bits, int lane) {
+    const uint32_t now = group_slice<PER>(__ballot(stepped && mv_bits != 0u), lane) != 0u ? 1u : 0u;
+    if (byte_at && stepped && (lane & (PER - 1)) == 0 && now != (old_byte != 0u ? 1u : 0u)) *byte_at = (uint8_t)now;
+}
+// the Adam step row by row (a partial bucket, an odd first row, the last arriver of a sliced bucket); live_at: the
+// bucket's first byte of the moment map
 template <int RT>
 __device__ __forceinline__ void finish_adam(const UnFix &t, const FusedUpdate &fu, const AdamArgs &a, int64_t R0, int rows,
-                                            int tid) {
+                                            int tid, int64_t live_at) {
     float2 *p2 = reinterpret_cast<float2 *>(fu.p) + R0, *m2 = reinterpret_cast<float2 *>(fu.m) + R0;
     float2 *v2 = reinterpret_cast<float2 *>(fu.v) + R0;
     uint32_t *sh = fu.shadow ? reinterpret_cast<uint32_t *>(fu.shadow) + R0 : nullptr;
-    for (int r = tid; r < rows; r += RT) {
-        float2 Pr = p2[r], Mr = m2[r], Vr = v2[r];
-        float2 g = unfix(t, r);
-        adam_one(Pr.x, g.x, Mr.x, Vr.x, a);
-        adam_one(Pr.y, g.y, Mr.y, Vr.y, a);
-        p2[r] = Pr; m2[r] = Mr; v2[r] = Vr;
-        if (sh) sh[r] = bf16_pair(Pr.x, Pr.y);
+    uint8_t *lv = fu.live ? fu.live + live_at : nullptr;
+    for (int r0 = 0; r0 < rows; r0 += RT) {   // (uniform trip count: the group rule votes across the wave)
+        const int r = r0 + tid;
+        const bool in = r < rows;
+        const uint32_t old = in ? old_byte(r >> LIVE_SHIFT) : 0u;
+        const float2 g0 = in ? unfix(t, r) : make_float2(0.f, 0.f);
+        const GroupStep gs = group_step<16>(fu, old, g0.x != 0.f || g0.y != 0.f, tid & 63);
+        const bool step = in && gs.step;
+        uint32_t mv = 0u;
+        if (step) {
+            float2 Pr = p2[r], Mr = make_float2(0.f, 0.f), Vr = make_float2(0.f, 0.f), g = g0;
+            if (!gs.first) { Mr = m2[r]; Vr = v2[r]; }
+            adam_one(Pr.x, g.x, Mr.x, Vr.x, a);
+            adam_one(Pr.y, g.y, Mr.y, Vr.y, a);
+            p2[r] = Pr; m2[r] = Mr; v2[r] = Vr;
+            if (sh) sh[r] = bf16_pair(Pr.x, Pr.y);
+            mv = __float_as_uint(Mr.x) | __float_as_uint(Mr.y) | __float_as_uint(Vr.x) | __float_as_uint(Vr.y);
+        }
+        group_mark<16>(lv ? lv + (r >> LIVE_SHIFT) : nullptr, old, step, mv, tid & 63);
     }
 }
 // FIN_ADAM_FAST: the lane's row pairs q = tid + j RT, their parameters and moments in registers between prefetch() and
@@ -466,25 +520,57 @@ template <int RT> struct RowState {
         : p4(reinterpret_cast<float4 *>(reinterpret_cast<float2 *>(fu.p) + R0)),
           m4(reinterpret_cast<float4 *>(reinterpret_cast<float2 *>(fu.m) + R0)),
           v4(reinterpret_cast<float4 *>(reinterpret_cast<float2 *>(fu.v) + R0)) {}
-    __device__ __forceinline__ void prefetch(int tid) {
+    __device__ __forceinline__ void prefetch(const FusedUpdate &fu, int tid) {
+        const bool all = !fu.live || !fu.skip;   // uniform
 #pragma unroll
         for (int j = 0; j < NQ; ++j) {  // all of the lane's loads: six 16-byte loads in flight behind the barrier
             const int q = tid + j * RT;
-            P[j] = ld_f4(p4 + q); Mv[j] = ld_f4(m4 + q); V[j] = ld_f4(v4 + q);
+            if (all || old_byte(q >> (LIVE_SHIFT - 1)) != 0u) {   // (a clean group: no load; a first touch loads p in finish())
+                P[j] = ld_f4(p4 + q); Mv[j] = ld_f4(m4 + q); V[j] = ld_f4(v4 + q);
+            }
         }
     }
-    __device__ __forceinline__ void finish(const UnFix &t, const FusedUpdate &fu, const AdamArgs &a, int64_t R0, int tid) {
+    __device__ __forceinline__ void finish(const UnFix &t, const FusedUpdate &fu, const AdamArgs &a, int64_t R0, int tid,
+                                           int64_t live_at) {
         uint2 *sh2 = fu.shadow ? reinterpret_cast<uint2 *>(reinterpret_cast<uint32_t *>(fu.shadow) + R0) : nullptr;
+        uint8_t *lv = fu.live ? fu.live + live_at : nullptr;
+        const int lane = tid & 63;
+        // every row pair's arithmetic first, every store behind it: with the stores of one pair in front of the next
+        // pair's group vote, the vote's branch made the compiler wait for those stores (s_waitcnt vmcnt(0): +10 us)
+        bool step[NQ];
+        uint32_t mv[NQ];
 #pragma unroll
         for (int j = 0; j < NQ; ++j) {
             const int q = tid + j * RT;
             float2 g0 = unfix(t, 2 * q), g1 = unfix(t, 2 * q + 1);
-            adam_one(P[j].x, g0.x, Mv[j].x, V[j].x, a);
-            adam_one(P[j].y, g0.y, Mv[j].y, V[j].y, a);
-            adam_one(P[j].z, g1.x, Mv[j].z, V[j].z, a);
-            adam_one(P[j].w, g1.y, Mv[j].w, V[j].w, a);
-            st_f4(p4 + q, P[j]); st_f4(m4 + q, Mv[j]); st_f4(v4 + q, V[j]);
-            if (sh2) sh2[q] = make_uint2(bf16_pair(P[j].x, P[j].y), bf16_pair(P[j].z, P[j].w));
+            const GroupStep gs = group_step<8>(fu, old_byte(q >> (LIVE_SHIFT - 1)),
+                                               g0.x != 0.f || g0.y != 0.f || g1.x != 0.f || g1.y != 0.f, lane);
+            step[j] = gs.step;
+            mv[j] = 0u;
+            if (gs.step) {
+                if (gs.first) {   // (about once per group in a whole training run: a late dependent load is acceptable)
+                    P[j] = ld_f4(p4 + q);
+                    Mv[j] = make_float4(0.f, 0.f, 0.f, 0.f); V[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+                adam_one(P[j].x, g0.x, Mv[j].x, V[j].x, a);
+                adam_one(P[j].y, g0.y, Mv[j].y, V[j].y, a);
+                adam_one(P[j].z, g1.x, Mv[j].z, V[j].z, a);
+                adam_one(P[j].w, g1.y, Mv[j].w, V[j].w, a);
+                mv[j] = f4_bits(Mv[j]) | f4_bits(V[j]);
+            }
+        }
+        // (every load above has been consumed: free at run time.  Said through the builtin, so that the compiler's own
+        // bookkeeping starts clean here -- it otherwise guards each store below against the loads of the branches above
+        // with a vmcnt(2), which at run time waits for the stores in front of it)
+        __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) {
+            const int q = tid + j * RT;
+            if (step[j]) {
+                st_f4(p4 + q, P[j]); st_f4(m4 + q, Mv[j]); st_f4(v4 + q, V[j]);
+                if (sh2) sh2[q] = make_uint2(bf16_pair(P[j].x, P[j].y), bf16_pair(P[j].z, P[j].w));
+            }
+            group_mark<8>(lv ? lv + (q >> 3) : nullptr, old_byte(q >> (LIVE_SHIFT - 1)), step[j], mv[j], lane);
         }
     }
 };
@@ -524,6 +610,13 @@ __device__ __forceinline__ void reduce_bucket(const ReduceUnit &u, const GridMet
     // bucket without records the Adam step (g = 0) and a wire bucket its zeros.
     const bool have = i1 > i0 || !direct;
     if (!have && !FUSE) return;
+    // the bucket's 256 bytes of the moment map, word i on lane i (every wave of a bucket without records, else the first):
+    // requested here, put into s_live in front of the workgroup's next barrier -- no register is held across the record loop
+    const int64_t live_at = (int64_t)(bm.bstart[l] + u.b) * LIVE_GROUPS;
+    uint32_t live_words = 0u;
+    if (FUSE && out.fu.live && (wave == 0 || !have)) live_words = reinterpret_cast<const uint32_t *>(out.fu.live + live_at)[lane];
+    // a bucket without records whose groups are all clean has no work (every wave sees all 256 bytes: uniform)
+    if (FUSE && !have && out.fu.live && out.fu.skip && __ballot(live_words != 0u) == 0ull) return;
     // from the bound of |value| of the LEVEL (found by pass 1).  One device-scope atomic load: the last workgroup of a
     // closing launch to arrive ZEROES the maxima (tail_arrive) -- ordered behind this read by the arrival, but a plain
     // load the compiler might re-issue later would be a data race on paper
@@ -545,17 +638,20 @@ __device__ __forceinline__ void reduce_bucket(const ReduceUnit &u, const GridMet
         uint32_t e_first = 0u;
         if (lane < nmy) e_first = tab[(int64_t)(first + NW * lane) * nb];
         for (int i = tid; i < BK_ROWS * 2; i += RT) s_acc[i] = 0ll;
+        if (FUSE && wave == 0) s_live[lane] = live_words;
         __syncthreads();
         step_now = __builtin_amdgcn_readfirstlane(step_now);   // (returned by now: into a scalar register for the loop)
         RED_STAMP(10);
         accumulate<RT, REC>(tab, nb, first, nmy, e_first, static_cast<const REC *>(ws.recs) + (int64_t)l * bm.n_items * ITEM_RECS,
                             t.fs, lane, wave);
         RED_STAMP(11);
-        if (fin == FIN_ADAM_FAST) rs.prefetch(tid);
+        if (fin == FIN_ADAM_FAST) rs.prefetch(out.fu, tid);
         __syncthreads();
         RED_STAMP(12);
-    } else if (fin == FIN_ADAM_FAST) {
-        rs.prefetch(tid);
+    } else {   // (FUSE: no records, but live groups whose moments decay)
+        if (wave == 0) s_live[lane] = live_words;
+        __syncthreads();
+        if (fin == FIN_ADAM_FAST) rs.prefetch(out.fu, tid);
     }
     if (!direct && !merge_slices<RT>(u, S, bm, ws, tid)) return;
     AdamArgs a = out.fu.a;   // (once, in front of the choice; have_step: the closing launch, see the kernel)
@@ -565,8 +661,8 @@ __device__ __forceinline__ void reduce_bucket(const ReduceUnit &u, const GridMet
     switch (fin) {
     case FIN_ADD: finish_add<RT>(t, out.dtable, R0, rows, tid); break;
     case FIN_WIRE: finish_wire<RT>(t, out.fu.grad_out, R0, rows, tid); break;
-    case FIN_ADAM: finish_adam<RT>(t, out.fu, a, R0, rows, tid); break;
-    case FIN_ADAM_FAST: rs.finish(t, out.fu, a, R0, tid); RED_STAMP(13); RED_STAMP_FLUSH(); break;
+    case FIN_ADAM: finish_adam<RT>(t, out.fu, a, R0, rows, tid, live_at); break;
+    case FIN_ADAM_FAST: rs.finish(t, out.fu, a, R0, tid, live_at); RED_STAMP(13); RED_STAMP_FLUSH(); break;
     }
 }
 
@@ -629,6 +725,39 @@ k_step_tail(unsigned int *__restrict__ gmax, AdamArgs a, SlabAdam sa, int32_t *_
         __syncthreads();
         if (threadIdx.x == 0) tail_arrive(arrive, (int)gridDim.x, (int)blockIdx.x, tick, step_now, gmax, do_tick, clear_gmax);
     }
+}
+
+// The moment map from the moments themselves (lnerf_moment_map_build): one lane per row of every bucket, 16 lanes per
+// byte, every byte of the map written (rows past a level's end count as zero).
+struct MapLevels { int num_levels, offsets[LNERF_MAX_LEVELS + 1], bstart[LNERF_MAX_LEVELS + 1]; };
+__global__ void __launch_bounds__(256)
+k_moment_map(const float2 *__restrict__ m, const float2 *__restrict__ v, MapLevels lv, uint8_t *__restrict__ map) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;   // (buckets x BK_ROWS threads: whole blocks)
+    const int gb = (int)(t >> BK_SHIFT), rb = (int)(t & (BK_ROWS - 1));
+    int l = 0;
+    while (l + 1 < lv.num_levels && gb >= lv.bstart[l + 1]) ++l;
+    const int64_t row = (int64_t)lv.offsets[l] + ((int64_t)(gb - lv.bstart[l]) << BK_SHIFT) + rb;
+    uint32_t bits = 0u;
+    if (row < (int64_t)lv.offsets[l + 1]) {
+        const float2 a = m[row], b = v[row];
+        bits = __float_as_uint(a.x) | __float_as_uint(a.y) | __float_as_uint(b.x) | __float_as_uint(b.y);
+    }
+    const uint32_t any = group_slice<16>(__ballot(bits != 0u), (int)threadIdx.x & 63);
+    if ((threadIdx.x & 15) == 0) map[t >> LIVE_SHIFT] = any ? (uint8_t)1 : (uint8_t)0;
+}
+
+// Moment maps bound to a table's optimiser state (lnerf_moment_map_bind), by the exp_avg pointer: the fused entry points
+// look theirs up when they fill FusedUpdate.  No binding: no map, every group takes the step.
+struct BoundMap { uint8_t *map; size_t bytes; };
+static std::mutex g_maps_mutex;
+static std::unordered_map<const void *, BoundMap> g_maps;
+// with a bound map: leave groups with zero moments and zero gradient alone (0: the map is maintained, every group steps)
+int g_adam_skip = 1;
+// "adam_skip" switches between two forms of the SAME result; it is not one of the path-selecting keys below
+static bool set_form_switch(const char *key, int value) {
+    if (strcmp(key, "adam_skip") != 0) return false;
+    g_adam_skip = value ? 1 : 0;
+    return true;
 }
 
 extern int g_mlp_fwd_blocks, g_mlp_fwd_wps, g_mlp_bwd_blocks;  // mlp.hip
@@ -738,6 +867,7 @@ extern "C" {
 
 int lnerf_set_tuning(const char *key, int value) {
     LNERF_REQUIRE(key, "set_tuning: null key");
+    if (set_form_switch(key, value)) return LNERF_OK;
     if (strcmp(key, "scatter_compact_max_res") == 0) {
         LNERF_REQUIRE(value >= 0, "set_tuning: scatter_compact_max_res must be >= 0");
         g_compact_max_res = value;
@@ -994,9 +1124,9 @@ int lnerf_grid_scatter_reduce_bf16(float bound, int num_levels, int level_dim, c
 }
 
 // what the Adam-mode entry points check alike (behind their own checks of the step), and the kernel-side descriptor
-static int fill_fused_adam(const char *who, FusedUpdate &fu, float *table, float *exp_avg, float *exp_avg_sq,
-                           const float *dtable_zero, void *shadow_bf16, float lr, float beta1, float beta2, float eps,
-                           int step, const int32_t *step_dev, float grad_scale) {
+static int fill_fused_adam(const char *who, FusedUpdate &fu, int num_levels, const int32_t *offsets_host, float *table,
+                           float *exp_avg, float *exp_avg_sq, const float *dtable_zero, void *shadow_bf16, float lr, float beta1,
+                           float beta2, float eps, int step, const int32_t *step_dev, float grad_scale) {
     LNERF_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "%s: betas must be in [0,1)", who);
     LNERF_REQUIRE((((uintptr_t)table | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)dtable_zero) & 15) == 0,
                   "%s: buffers must be 16-byte aligned", who);
@@ -1004,6 +1134,60 @@ static int fill_fused_adam(const char *who, FusedUpdate &fu, float *table, float
     memset(&fu, 0, sizeof(fu));
     fu.p = table; fu.m = exp_avg; fu.v = exp_avg_sq; fu.shadow = (uint16_t *)shadow_bf16;
     adam_host_args(fu.a, lr, beta1, beta2, eps, step, step_dev, grad_scale, 0);
+    {   // the moment map bound to this optimiser state, if any
+        std::lock_guard<std::mutex> lock(g_maps_mutex);
+        const auto it = g_maps.find(exp_avg);
+        if (it != g_maps.end()) {
+            const size_t need = lnerf_moment_map_bytes(num_levels, offsets_host);
+            LNERF_REQUIRE(need > 0 && it->second.bytes >= need, "%s: the bound moment map is too small (%zu < %zu)", who,
+                          it->second.bytes, need);
+            fu.live = it->second.map;
+        }
+    }
+    // (a skipped group equals a stepped one only where 0 * rcp(eps) and lr * 0 are zero: see FusedUpdate)
+    fu.skip = g_adam_skip && eps > 0.f && isfinite(lr) && isfinite(grad_scale) ? 1 : 0;
+    return LNERF_OK;
+}
+
+size_t lnerf_moment_map_bytes(int num_levels, const int32_t *offsets_host) {
+    ScatterPlan plan;
+    if (!plan_from_offsets(num_levels, offsets_host, 1, plan)) return 0;
+    return (size_t)plan.buckets * LIVE_GROUPS;
+}
+
+int lnerf_moment_map_build(const float *exp_avg, const float *exp_avg_sq, int num_levels, int level_dim,
+                           const int32_t *offsets_host, void *map, size_t map_bytes, lnerf_stream_t stream) {
+    LNERF_REQUIRE(exp_avg && exp_avg_sq && map, "moment_map_build: null pointer");
+    LNERF_REQUIRE(level_dim == 2, "moment_map_build: level_dim must be 2");
+    const size_t need = lnerf_moment_map_bytes(num_levels, offsets_host);
+    LNERF_REQUIRE(need > 0, "moment_map_build: bad level table");
+    LNERF_REQUIRE(map_bytes >= need, "moment_map_build: map too small (%zu < %zu)", map_bytes, need);
+    LNERF_REQUIRE((((uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 7) == 0 && ((uintptr_t)map & 15) == 0,
+                  "moment_map_build: moments must be 8-byte, the map 16-byte aligned");
+    MapLevels lv = {};
+    lv.num_levels = num_levels;
+    int buckets = 0;
+    for (int l = 0; l < num_levels; ++l) {
+        lv.offsets[l] = offsets_host[l];
+        lv.bstart[l] = buckets;
+        buckets += (int)div_up((int64_t)offsets_host[l + 1] - offsets_host[l], BK_ROWS);
+    }
+    lv.offsets[num_levels] = offsets_host[num_levels];
+    lv.bstart[num_levels] = buckets;
+    LNERF_REQUIRE((size_t)buckets * LIVE_GROUPS == need, "moment_map_build: bucket plan mismatch");
+    hipLaunchKernelGGL(k_moment_map, dim3((unsigned)(buckets * (BK_ROWS / 256))), dim3(256), 0, as_stream(stream),
+                       reinterpret_cast<const float2 *>(exp_avg), reinterpret_cast<const float2 *>(exp_avg_sq), lv, (uint8_t *)map);
+    LNERF_CHECK_LAUNCH("moment_map_build");
+    return LNERF_OK;
+}
+
+int lnerf_moment_map_bind(const float *exp_avg, void *map, size_t map_bytes) {
+    LNERF_REQUIRE(exp_avg, "moment_map_bind: null exp_avg");
+    LNERF_REQUIRE(!map || (map_bytes > 0 && map_bytes % LIVE_GROUPS == 0 && ((uintptr_t)map & 15) == 0),
+                  "moment_map_bind: the map must be 16-byte aligned and whole buckets of %d bytes", LIVE_GROUPS);
+    std::lock_guard<std::mutex> lock(g_maps_mutex);
+    if (map) g_maps[exp_avg] = {(uint8_t *)map, map_bytes};
+    else g_maps.erase(exp_avg);
     return LNERF_OK;
 }
 
@@ -1016,7 +1200,7 @@ int lnerf_grid_encode_backward_adam(const float *xyzs, float bound, const void *
     LNERF_REQUIRE(table && exp_avg && exp_avg_sq, "grid_encode_backward_adam: null optimiser state");
     LNERF_REQUIRE(step_dev || step >= 1, "grid_encode_backward_adam: step must be >= 1 (got %d)", step);
     FusedUpdate fu;
-    if (int rc = fill_fused_adam("grid_encode_backward_adam", fu, table, exp_avg, exp_avg_sq, dtable_zero, shadow_bf16, lr, beta1,
+    if (int rc = fill_fused_adam("grid_encode_backward_adam", fu, num_levels, offsets_host, table, exp_avg, exp_avg_sq, dtable_zero, shadow_bf16, lr, beta1,
                                  beta2, eps, step, step_dev, grad_scale)) return rc;
     return scatter_backward({xyzs, bound, dfeat, dfeat_dtype, num_levels, level_dim, offsets_host, scales_host, res_host,
                              m_host, m_dev, level_stride, dtable_zero, variant, workspace, workspace_bytes, stream, &fu});
@@ -1065,7 +1249,7 @@ int lnerf_grid_encode_backward_adam_tail(const float *xyzs, float bound, const v
     LNERF_REQUIRE(step_dev, "grid_encode_backward_adam_tail: needs the device counter pair (int32[2])");
     LNERF_REQUIRE(m_host > 0, "grid_encode_backward_adam_tail: needs m_host > 0 (use lnerf_step_tail for an empty frame)");
     FusedUpdate fu;
-    if (int rc = fill_fused_adam("grid_encode_backward_adam_tail", fu, table, exp_avg, exp_avg_sq, dtable_zero, shadow_bf16, lr,
+    if (int rc = fill_fused_adam("grid_encode_backward_adam_tail", fu, num_levels, offsets_host, table, exp_avg, exp_avg_sq, dtable_zero, shadow_bf16, lr,
                                  beta1, beta2, eps, step, step_dev, grad_scale)) return rc;
     TailJob tj = {};
     if (mlp_workspace) {

@@ -3,6 +3,7 @@ extension of the absent src/latent_nerf/models/encoders (SURVEY.md Appendix A); 
 table follows the align_corners=False convention recorded there."""
 import ctypes
 import math
+import weakref
 from typing import NamedTuple, Optional
 
 import numpy as np
@@ -228,8 +229,22 @@ class FusedTableUpdate:
     the table's Adam step itself (lnerf_grid_encode_backward_adam) and the table gets no `.grad`; any other
     backward through the encoder (unarmed) produces the ordinary gradient.  Single GPU only."""
 
-    def __init__(self, exp_avg, exp_avg_sq, lr, betas, eps, optimizer):
+    def __init__(self, exp_avg, exp_avg_sq, lr, betas, eps, optimizer, levels=None):
         self.exp_avg, self.exp_avg_sq = exp_avg, exp_avg_sq
+        # the MOMENT MAP (include/lnerf_hip.h, lnerf_moment_map_*): one byte per 16-row group, non-zero where a moment has
+        # a non-zero bit; the fused step leaves clean groups without gradient alone and keeps the map current.  Owned
+        # here, bound to exp_avg in the library for as long as this object lives, never part of a state_dict.  Whatever
+        # else writes the moments calls rebuild_map() on the same stream (FusedAdam does).
+        self.levels, self.map = levels, None
+        if levels is not None and exp_avg.is_cuda:
+            n = int(_b.get_lib().lnerf_moment_map_bytes(levels.num_levels, levels.c_offsets))
+            if n == 0:
+                raise _b.LnerfError("lnerf_moment_map_bytes: this level table has no bucket plan")
+            self.map = torch.empty(n, device=exp_avg.device, dtype=torch.uint8)
+            self.rebuild_map()
+            _b.call("lnerf_moment_map_bind", _p(exp_avg), _p(self.map), n)
+            # (by pointer value: the finalizer must not keep the tensors alive; they outlive it through self)
+            weakref.finalize(self, _unbind_moment_map, exp_avg.data_ptr()).atexit = False
         self.lr, self.betas, self.eps = float(lr), betas, float(eps)
         self.optimizer = optimizer          # step number / device step counter live there
         self.zero = torch.zeros_like(exp_avg)  # dtable scratch argument of the fused entry points (never written)
@@ -244,6 +259,21 @@ class FusedTableUpdate:
         # tick of the step counter all ran inside the scatter's pass 2
         self.closed = False
         self.inline_tail = False            # set by FusedAdam: the tail may run inside the scatter (no other small parameter)
+
+    def rebuild_map(self):
+        """The moment map from the moments as they are (one streaming launch on the current stream): call behind anything
+        but the fused step that wrote exp_avg / exp_avg_sq, before the next armed backward."""
+        if self.map is not None:
+            lv = self.levels
+            _b.call("lnerf_moment_map_build", _p(self.exp_avg), _p(self.exp_avg_sq), lv.num_levels, lv.level_dim,
+                    lv.c_offsets, _p(self.map), self.map.numel(), _stream())
+
+
+def _unbind_moment_map(exp_avg_ptr):
+    try:
+        _b.get_lib().lnerf_moment_map_bind(ctypes.c_void_p(exp_avg_ptr), None, 0)
+    except Exception:   # (interpreter shutdown: the library may be gone)
+        pass
 
 
 def grid_encode_backward_adam(xyzs, bound, dfeat, encoder, m_host, m_dev, level_stride, variant):

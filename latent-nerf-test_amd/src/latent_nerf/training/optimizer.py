@@ -85,7 +85,7 @@ class FusedAdam:
                 raise ValueError("fuse_table_update needs the encoder")
             for p, m, v, lr in self.big:
                 if p is encoder.embeddings:
-                    self.fused = E.FusedTableUpdate(m, v, lr, betas, eps, self)
+                    self.fused = E.FusedTableUpdate(m, v, lr, betas, eps, self, levels=encoder.levels)
                     encoder.fused_update = self.fused
             if self.fused is None:
                 raise ValueError("fuse_table_update: encoder.embeddings is not among the parameters")
@@ -192,6 +192,10 @@ class FusedAdam:
                         self.step_no, _p(self.step_dev), float(grad_scale), 0, _stream())
                 if rest and rest[0] is not None:
                     rest[0]()
+            if self.fused is not None and p is enc.embeddings:
+                # (this step wrote the table's moments behind the fused path's back: an un-armed step, the lambda_tv
+                # route, several ranks -- its moment map is stale until rebuilt, on the same stream)
+                self.fused.rebuild_map()
         pend = self.fused.pending_tail if self.fused is not None else None
         if self.fused is not None and self.fused.closed:
             self.fused.closed = False      # the armed backward closed the step: nothing left to launch
@@ -264,5 +268,7 @@ class FusedAdam:
         for (p, m, v, lr), sm, sv in zip(entries, state["exp_avg"], state["exp_avg_sq"]):
             m.copy_(sm)
             v.copy_(sv)
+        if self.fused is not None:
+            self.fused.rebuild_map()       # (the copies above made the table's moment map stale)
         if self.step_dev is not None:
             self.step_dev[0:1].fill_(self.step_no + 1)

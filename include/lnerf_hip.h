@@ -196,7 +196,18 @@ int lnerf_grid_encode_forward(const float *xyzs, float bound, const void *table,
  *              every call leaves zero again; the rest may hold anything).
  * variant 3  : variant 2 with packed 8-byte records (12-bit row inside the bucket + two values rounded
  *              to 26-bit floats, 17 mantissa bits): a third less record traffic, relative rounding
- *              2^-18 per addend; same workspace. */
+ *              2^-18 per addend; same workspace.
+ * Variants 2 / 3, numeric contract (DESIGN.md "Numeric contract of the bucketed scatter"; tested in
+ * tests/test_gpu_scatter_numerics.py): every row is within a derived bound of the exact sum of its f32 addends; the
+ * result scales bit for bit with a power-of-two scaling of dfeat; a level's rows depend on that level's gradients
+ * only, and on nothing a previous call left in the workspace.
+ * NON-FINITE dfeat (NaN, +-inf): the call returns normally, the result is reproducible, and every OTHER level is bit
+ * for bit what it is without the value.  What the rows of the level that holds the value contain is UNSPECIFIED INSIDE
+ * THAT LEVEL: pass 1 raises the level's bound to 3e38, so the level's finite addends are quantised to 2^-44 (2^-30) of
+ * 2^128 and come out as zero, and the non-finite addend goes through a float -> integer conversion that is not defined
+ * for it.  Observed on an MI355X: a NaN converts to 0, so the whole level reads zero; +-inf leaves +-inf in the 8 rows of
+ * its sample with 8-byte records and -+2^116 there with 12-byte records, the rest of the level zero.  This is tolerable
+ * because the MLP's own gradients are non-finite in the same step: the failure is loud anyway. */
 #define LNERF_SCATTER_ZERO_HEAD_BYTES (64 * 1024)
 size_t lnerf_grid_encode_backward_workspace_bytes(int num_levels, const int32_t *offsets_host, int64_t m_host);
 /* The first lnerf_grid_scatter_clear_bytes() bytes of that workspace (bucket cursors, level maxima) are cleared by every

@@ -5,13 +5,14 @@
 //   lnerf_atlas_buckets  k_atlas_bucket   one lane per face: index check, axis bucket of the face normal, label = f
 //   lnerf_atlas_round    k_atlas_hook     one lane per face: the smallest label among the face and its linked
 //                                         same-bucket neighbours -> atomicMin onto the face's label and its label's label
-//                        k_atlas_jump     one lane per face: ATLAS_JUMP_HOPS steps of label = label[label]
+//                        k_label_jump     (mesh_shared.h) one lane per face: pointer jumping
 //   lnerf_atlas_compact  k_atlas_roots    roots (label[f] == f) ranked inside each block (scan.h), block totals
-//                        k_scan_top       (scan.h) prefix of the block totals -> counts[0] = charts
-//                        k_atlas_assign   face_chart = rank of the face's root; chart_axis from the root
+//                        scan_top         (scan.h) prefix of the block totals -> counts[0] = charts
+//                        k_atlas_assign   face_chart = root_number (mesh_shared.h) of the face's root; chart_axis from
+//                                         the root
 //   lnerf_atlas_boxes    k_atlas_box      one lane per face: atomicMin / atomicMax of the order-preserving encoding of
 //                                         its corners' plane coordinates into its chart's box
-//                        k_atlas_unbox    one lane per chart: back to f32
+//                        k_box_decode     (mesh_shared.h) one lane per chart: back to f32
 //   lnerf_atlas_uv       k_atlas_uv       one lane per face: its three texture vertices (a vertex shared inside a chart
 //                                         is written by several faces, each with the same bits)
 //   lnerf_atlas_fold     k_fold_setup     the item list of uvbake.hip (uv_shared.h) over the packed UVs
@@ -25,10 +26,6 @@
 
 namespace lnerf {
 
-constexpr int ATLAS_THREADS = 256;
-constexpr int ATLAS_LOG2 = 8;
-constexpr int ATLAS_JUMP_HOPS = 4;
-
 // plane coordinates (p, q) of a point in bucket b: p x q = the bucket's axis
 __device__ __forceinline__ void atlas_plane(int b, float x, float y, float z, float &p, float &q) {
     switch (b) {
@@ -41,25 +38,15 @@ __device__ __forceinline__ void atlas_plane(int b, float x, float y, float z, fl
     }
 }
 
-__device__ __forceinline__ bool atlas_face_ok(const int32_t *__restrict__ faces, int n_verts, int f, int v[3]) {
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        v[k] = faces[(int64_t)f * 3 + k];
-        ok = ok && v[k] >= 0 && v[k] < n_verts;
-    }
-    return ok;
-}
-
-__global__ void __launch_bounds__(ATLAS_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_atlas_bucket(const float *__restrict__ verts, int n_verts, const int32_t *__restrict__ faces, int n_faces,
                int32_t *__restrict__ bucket, int32_t *__restrict__ label, unsigned long long *__restrict__ n_bad) {
-    const int f = blockIdx.x * ATLAS_THREADS + threadIdx.x;
+    const int f = mesh_gid();
     bool bad = false;
     if (f < n_faces) {
         int v[3];
         int b = -1;
-        if (atlas_face_ok(faces, n_verts, f, v)) {
+        if (face_ok(faces, n_verts, f, v)) {
             float P[3][3];
 #pragma unroll
             for (int k = 0; k < 3; ++k)
@@ -83,17 +70,16 @@ k_atlas_bucket(const float *__restrict__ verts, int n_verts, const int32_t *__re
         bucket[f] = b;
         label[f] = f;
     }
-    const unsigned long long mask = __ballot(bad);
-    if (lane_id() == 0 && mask != 0) atomicAdd(n_bad, (unsigned long long)__popcll(mask));
+    count_bad(bad, n_bad);
 }
 
 // Labels only ever decrease and always name a face of the same component, so a plain read that misses another
 // workgroup's atomicMin of the same launch sees an older valid label: it costs at most a round, never the result.  A
 // launch in which no lane raises `changed` wrote nothing, so all it read was the settled state.
-__global__ void __launch_bounds__(ATLAS_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_atlas_hook(const int32_t *__restrict__ bucket, const int32_t *__restrict__ twin, int n_faces, int32_t *label,
              int32_t *__restrict__ changed) {
-    const int f = blockIdx.x * ATLAS_THREADS + threadIdx.x;
+    const int f = mesh_gid();
     if (f >= n_faces) return;
     const int b = bucket[f];
     const int lf = label[f];
@@ -115,57 +101,42 @@ k_atlas_hook(const int32_t *__restrict__ bucket, const int32_t *__restrict__ twi
     }
 }
 
-__global__ void __launch_bounds__(ATLAS_THREADS)
-k_atlas_jump(int n_faces, int32_t *label) {
-    const int f = blockIdx.x * ATLAS_THREADS + threadIdx.x;
-    if (f >= n_faces) return;
-    const int l0 = label[f];
-    int l = l0;
-#pragma unroll
-    for (int h = 0; h < ATLAS_JUMP_HOPS; ++h) {
-        if (l < 0 || l >= n_faces) return;
-        const int ll = label[l];
-        if (ll < l) l = ll;
-    }
-    if (l >= 0 && l < l0) atomicMin(&label[f], l);
-}
-
-__global__ void __launch_bounds__(ATLAS_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_atlas_roots(const int32_t *__restrict__ bucket, const int32_t *__restrict__ label, int n_faces,
               int32_t *__restrict__ root_rank, int64_t *__restrict__ blk_roots) {
-    const int f = blockIdx.x * ATLAS_THREADS + threadIdx.x;
+    const int f = mesh_gid();
     const int n[1] = {(f < n_faces && bucket[f] >= 0 && label[f] == f) ? 1 : 0};
     int excl[1], total[1];
-    block_exclusive_scan<ATLAS_THREADS>(n, excl, total);
+    block_exclusive_scan<MESH_THREADS>(n, excl, total);
     if (f < n_faces) root_rank[f] = excl[0];
     if (threadIdx.x == 0) blk_roots[blockIdx.x] = total[0];
 }
 
-__global__ void __launch_bounds__(ATLAS_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_atlas_assign(const int32_t *__restrict__ bucket, const int32_t *__restrict__ label, int n_faces,
                const int32_t *__restrict__ root_rank, const int64_t *__restrict__ blk_roots,
                int32_t *__restrict__ face_chart, int32_t *__restrict__ chart_axis) {
-    const int f = blockIdx.x * ATLAS_THREADS + threadIdx.x;
+    const int f = mesh_gid();
     if (f >= n_faces) return;
     const int b = bucket[f], l = label[f];
     int c = -1;
     if (b >= 0 && l >= 0 && l < n_faces) {
-        c = (int)blk_roots[l >> ATLAS_LOG2] + root_rank[l];
+        c = root_number(blk_roots, root_rank, l);
         if (l == f) chart_axis[c] = b;
     }
     face_chart[f] = c;
 }
 
 // enc: [4][n_charts] u32 = p_lo, p_hi, q_lo, q_hi (lo cleared to ~0, hi to 0)
-__global__ void __launch_bounds__(ATLAS_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_atlas_box(const float *__restrict__ verts, int n_verts, const int32_t *__restrict__ faces,
             const int32_t *__restrict__ bucket, const int32_t *__restrict__ face_chart, int n_faces, int n_charts,
             uint32_t *enc) {
-    const int f = blockIdx.x * ATLAS_THREADS + threadIdx.x;
+    const int f = mesh_gid();
     if (f >= n_faces) return;
     const int b = bucket[f], c = face_chart[f];
     int v[3];
-    if (b < 0 || b > 5 || c < 0 || c >= n_charts || !atlas_face_ok(faces, n_verts, f, v)) return;
+    if (b < 0 || b > 5 || c < 0 || c >= n_charts || !face_ok(faces, n_verts, f, v)) return;
     uint32_t plo = 0xFFFFFFFFu, phi = 0u, qlo = 0xFFFFFFFFu, qhi = 0u;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -181,14 +152,6 @@ k_atlas_box(const float *__restrict__ verts, int n_verts, const int32_t *__restr
     atomicMax(&enc[(int64_t)3 * n_charts + c], qhi);
 }
 
-__global__ void __launch_bounds__(ATLAS_THREADS)
-k_atlas_unbox(const uint32_t *__restrict__ enc, int n_charts, float *__restrict__ chart_box) {
-    const int c = blockIdx.x * ATLAS_THREADS + threadIdx.x;
-    if (c >= n_charts) return;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) chart_box[(int64_t)c * 4 + k] = ordered_decode(enc[(int64_t)k * n_charts + c]);
-}
-
 struct AtlasUv {
     const float *verts;
     const int32_t *faces, *ft, *face_chart, *chart_axis, *chart_org;
@@ -197,13 +160,13 @@ struct AtlasUv {
     float scale, Rf;
 };
 
-__global__ void __launch_bounds__(ATLAS_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_atlas_uv(AtlasUv a, float *__restrict__ vt) {
-    const int f = blockIdx.x * ATLAS_THREADS + threadIdx.x;
+    const int f = mesh_gid();
     if (f >= a.n_faces) return;
     const int c = a.face_chart[f];
     int v[3];
-    if (c < 0 || c >= a.n_charts || !atlas_face_ok(a.faces, a.n_verts, f, v)) return;
+    if (c < 0 || c >= a.n_charts || !face_ok(a.faces, a.n_verts, f, v)) return;
     const int b = a.chart_axis[c];
     if (b < 0 || b > 5) return;
     const float p_lo = a.chart_box[(int64_t)c * 4], q_hi = a.chart_box[(int64_t)c * 4 + 3];
@@ -269,32 +232,37 @@ k_fold_pass(UvMesh m, const int64_t *__restrict__ face_off, const int64_t *__res
 
 struct FoldLayout {
     int64_t nbF;
-    size_t off_bytes, bytes;
+    size_t face_off, blk_items, bytes;
 };
 
 static FoldLayout fold_layout(int n_faces) {
     FoldLayout L;
+    Carve c;
     L.nbF = div_up(n_faces, UV_THREADS);
-    L.off_bytes = align256((size_t)n_faces * 8);
-    L.bytes = L.off_bytes + align256((size_t)L.nbF * 8);
+    L.face_off = c.take((size_t)n_faces * 8);
+    L.blk_items = c.take((size_t)L.nbF * 8);
+    L.bytes = c.o;
     return L;
 }
 
-static size_t compact_bytes(int n_faces) {
-    return align256((size_t)n_faces * 4) + align256((size_t)div_up(n_faces, ATLAS_THREADS) * 8);
-}
+struct CompactLayout {
+    int64_t nb;
+    size_t root_rank, blk_roots, bytes;
+};
 
-static bool hip_ok(hipError_t e, const char *what) {
-    if (e == hipSuccess) return true;
-    set_error("%s failed: %s", what, hipGetErrorString(e));
-    return false;
+static CompactLayout compact_layout(int n_faces) {
+    CompactLayout L;
+    Carve c;
+    L.nb = div_up(n_faces, MESH_THREADS);
+    L.root_rank = c.take((size_t)n_faces * 4);
+    L.blk_roots = c.take((size_t)L.nb * 8);
+    L.bytes = c.o;
+    return L;
 }
 
 }  // namespace lnerf
 
 using namespace lnerf;
-
-#define ATLAS_GRID(n) dim3((unsigned)div_up((n), ATLAS_THREADS)), dim3(ATLAS_THREADS), 0, s
 
 extern "C" {
 
@@ -307,8 +275,8 @@ int lnerf_atlas_buckets(const float *verts, int n_verts, const int32_t *faces, i
     hipStream_t s = as_stream(stream);
     if (!hip_ok(hipMemsetAsync(counts_dev, 0, 8, s), "atlas_buckets: clearing the count")) return LNERF_ERR_HIP;
     if (n_faces > 0) {
-        hipLaunchKernelGGL(k_atlas_bucket, ATLAS_GRID(n_faces), verts, n_verts, faces, n_faces, bucket, label,
-                           reinterpret_cast<unsigned long long *>(counts_dev));
+        MESH_LAUNCH(k_atlas_bucket, n_faces, verts, n_verts, faces, n_faces, bucket, label,
+                    reinterpret_cast<unsigned long long *>(counts_dev));
         LNERF_CHECK_LAUNCH("atlas_buckets");
     }
     return LNERF_OK;
@@ -323,9 +291,9 @@ int lnerf_atlas_round(const int32_t *bucket, const int32_t *twin, int n_faces, i
     hipStream_t s = as_stream(stream);
     if (!hip_ok(hipMemsetAsync(changed_dev, 0, 4, s), "atlas_round: clearing the flag")) return LNERF_ERR_HIP;
     if (n_faces > 0) {
-        hipLaunchKernelGGL(k_atlas_hook, ATLAS_GRID(n_faces), bucket, twin, n_faces, label, changed_dev);
+        MESH_LAUNCH(k_atlas_hook, n_faces, bucket, twin, n_faces, label, changed_dev);
         LNERF_CHECK_LAUNCH("atlas_round(hook)");
-        hipLaunchKernelGGL(k_atlas_jump, ATLAS_GRID(n_faces), n_faces, label);
+        MESH_LAUNCH(k_label_jump, n_faces, n_faces, label);
         LNERF_CHECK_LAUNCH("atlas_round(jump)");
     }
     return LNERF_OK;
@@ -333,7 +301,7 @@ int lnerf_atlas_round(const int32_t *bucket, const int32_t *twin, int n_faces, i
 
 size_t lnerf_atlas_compact_scratch_bytes(int n_faces) {
     if (n_faces < 0 || n_faces > LNERF_ATLAS_MAX_FACES) return 0;
-    return compact_bytes(n_faces);
+    return compact_layout(n_faces).bytes;
 }
 
 int lnerf_atlas_compact(const int32_t *bucket, const int32_t *label, int n_faces, void *scratch, size_t scratch_bytes,
@@ -342,23 +310,20 @@ int lnerf_atlas_compact(const int32_t *bucket, const int32_t *label, int n_faces
                   LNERF_ATLAS_MAX_FACES);
     LNERF_REQUIRE(scratch && counts_dev, "atlas_compact: null pointer");
     LNERF_REQUIRE(n_faces == 0 || (bucket && label && face_chart && chart_axis), "atlas_compact: null pointer");
-    const size_t need = compact_bytes(n_faces);
-    LNERF_REQUIRE(scratch_bytes >= need, "atlas_compact: scratch of %zu bytes, need %zu", scratch_bytes, need);
+    const CompactLayout L = compact_layout(n_faces);
+    LNERF_REQUIRE(scratch_bytes >= L.bytes, "atlas_compact: scratch of %zu bytes, need %zu", scratch_bytes, L.bytes);
     LNERF_REQUIRE(((uintptr_t)scratch & 15) == 0, "atlas_compact: scratch must be 16-byte aligned");
-    int32_t *root_rank = reinterpret_cast<int32_t *>(scratch);
-    int64_t *blk_roots = reinterpret_cast<int64_t *>(reinterpret_cast<char *>(scratch) + align256((size_t)n_faces * 4));
-    const int64_t nb = div_up(n_faces, ATLAS_THREADS);
+    int32_t *root_rank = at<int32_t>(scratch, L.root_rank);
+    int64_t *blk_roots = at<int64_t>(scratch, L.blk_roots);
     hipStream_t s = as_stream(stream);
     if (n_faces > 0) {
-        hipLaunchKernelGGL(k_atlas_roots, ATLAS_GRID(n_faces), bucket, label, n_faces, root_rank, blk_roots);
+        MESH_LAUNCH(k_atlas_roots, n_faces, bucket, label, n_faces, root_rank, blk_roots);
         LNERF_CHECK_LAUNCH("atlas_compact(roots)");
     }
-    hipLaunchKernelGGL(k_scan_top<int64_t>, dim3(1), dim3(SCAN_TOP_THREADS), 0, s, blk_roots, (int64_t *)nullptr, nb,
-                       counts_dev, (int64_t *)nullptr);
+    scan_top(blk_roots, nullptr, L.nb, counts_dev, nullptr, s);
     LNERF_CHECK_LAUNCH("atlas_compact(scan)");
     if (n_faces > 0) {
-        hipLaunchKernelGGL(k_atlas_assign, ATLAS_GRID(n_faces), bucket, label, n_faces, root_rank, blk_roots, face_chart,
-                           chart_axis);
+        MESH_LAUNCH(k_atlas_assign, n_faces, bucket, label, n_faces, root_rank, blk_roots, face_chart, chart_axis);
         LNERF_CHECK_LAUNCH("atlas_compact(assign)");
     }
     return LNERF_OK;
@@ -383,17 +348,15 @@ int lnerf_atlas_boxes(const float *verts, int n_verts, const int32_t *faces, con
     if (n_charts == 0) return LNERF_OK;
     hipStream_t s = as_stream(stream);
     uint32_t *enc = reinterpret_cast<uint32_t *>(scratch);
-    const size_t row = (size_t)n_charts * 4;
-    for (int k = 0; k < 4; ++k)
-        if (!hip_ok(hipMemsetAsync(reinterpret_cast<char *>(enc) + k * row, (k & 1) ? 0 : 0xff, row, s),
-                    "atlas_boxes: clearing the boxes"))
+    for (int k = 0; k < 4; k += 2)      // p_lo, p_hi, then q_lo, q_hi
+        if (!box_clear(enc + (size_t)k * n_charts, enc + (size_t)(k + 1) * n_charts, n_charts, s,
+                       "atlas_boxes: clearing the boxes"))
             return LNERF_ERR_HIP;
     if (n_faces > 0) {
-        hipLaunchKernelGGL(k_atlas_box, ATLAS_GRID(n_faces), verts, n_verts, faces, bucket, face_chart, n_faces, n_charts,
-                           enc);
+        MESH_LAUNCH(k_atlas_box, n_faces, verts, n_verts, faces, bucket, face_chart, n_faces, n_charts, enc);
         LNERF_CHECK_LAUNCH("atlas_boxes(box)");
     }
-    hipLaunchKernelGGL(k_atlas_unbox, ATLAS_GRID(n_charts), enc, n_charts, chart_box);
+    MESH_LAUNCH(k_box_decode<4>, n_charts, enc, n_charts, (const int64_t *)nullptr, chart_box);
     LNERF_CHECK_LAUNCH("atlas_boxes(unbox)");
     return LNERF_OK;
 }
@@ -416,7 +379,7 @@ int lnerf_atlas_uv(const float *verts, int n_verts, const int32_t *faces, const 
     a.n_verts = n_verts; a.n_faces = n_faces; a.n_charts = n_charts; a.n_vt = n_vt; a.pad = pad;
     a.scale = scale; a.Rf = (float)R;
     hipStream_t s = as_stream(stream);
-    hipLaunchKernelGGL(k_atlas_uv, ATLAS_GRID(n_faces), a, vt);
+    MESH_LAUNCH(k_atlas_uv, n_faces, a, vt);
     LNERF_CHECK_LAUNCH("atlas_uv");
     return LNERF_OK;
 }
@@ -445,16 +408,14 @@ int lnerf_atlas_fold(const float *vt, int n_vt, const int32_t *ft, int n_faces, 
     m.verts = nullptr; m.faces = nullptr; m.vt = vt; m.ft = ft;
     m.n_verts = 0; m.n_vt = n_vt; m.n_faces = n_faces; m.R = R;
     m.Rf = (float)R;
-    int64_t *face_off = reinterpret_cast<int64_t *>(scratch);
-    int64_t *blk_items = reinterpret_cast<int64_t *>(reinterpret_cast<char *>(scratch) + L.off_bytes);
+    int64_t *face_off = at<int64_t>(scratch, L.face_off), *blk_items = at<int64_t>(scratch, L.blk_items);
     hipStream_t s = as_stream(stream);
     if (stages & LNERF_UV_ITEMS) {
         if (n_faces > 0) {
-            hipLaunchKernelGGL(k_fold_setup, dim3((unsigned)L.nbF), dim3(UV_THREADS), 0, s, m, face_off, blk_items);
+            LNERF_LAUNCH(k_fold_setup, n_faces, UV_THREADS, s, m, face_off, blk_items);
             LNERF_CHECK_LAUNCH("atlas_fold(setup)");
         }
-        hipLaunchKernelGGL(k_scan_top<int64_t>, dim3(1), dim3(SCAN_TOP_THREADS), 0, s, blk_items, (int64_t *)nullptr,
-                           L.nbF, counts_dev, (int64_t *)nullptr);
+        scan_top(blk_items, nullptr, L.nbF, counts_dev, nullptr, s);
         LNERF_CHECK_LAUNCH("atlas_fold(scan)");
     }
     if (stages & LNERF_UV_COVER) {
@@ -464,13 +425,8 @@ int lnerf_atlas_fold(const float *vt, int n_vt, const int32_t *ft, int n_faces, 
         for (int pass = 0; pass < 2; ++pass)
             for (int64_t base = 0; base < n_items; base += UV_ITEMS_PER_LAUNCH) {
                 const int64_t n = min(n_items - base, UV_ITEMS_PER_LAUNCH);
-                const dim3 grid((unsigned)div_up(n, UV_THREADS));
-                if (pass == 0)
-                    hipLaunchKernelGGL(k_fold_pass<false>, grid, dim3(UV_THREADS), 0, s, m, face_off, blk_items, L.nbF,
-                                       counts_dev, base, n, texel_owner, evicted);
-                else
-                    hipLaunchKernelGGL(k_fold_pass<true>, grid, dim3(UV_THREADS), 0, s, m, face_off, blk_items, L.nbF,
-                                       counts_dev, base, n, texel_owner, evicted);
+                LNERF_LAUNCH(pass == 0 ? k_fold_pass<false> : k_fold_pass<true>, n, UV_THREADS, s, m, face_off, blk_items,
+                             L.nbF, counts_dev, base, n, texel_owner, evicted);
                 LNERF_CHECK_LAUNCH("atlas_fold(pass)");
             }
     }

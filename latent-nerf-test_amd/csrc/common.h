@@ -35,7 +35,26 @@ inline hipStream_t as_stream(lnerf_stream_t s) { return reinterpret_cast<hipStre
         }                                                                                \
     } while (0)
 
+// false, with the error set, unless `e` is hipSuccess
+static inline bool hip_ok(hipError_t e, const char *what) {
+    if (e == hipSuccess) return true;
+    set_error("%s failed: %s", what, hipGetErrorString(e));
+    return false;
+}
+
+// *dst = the word at src on the device once everything queued on s before it is done
+template <typename T>
+static inline bool read_back(const T *src, T *dst, hipStream_t s, const char *what) {
+    return hip_ok(hipMemcpyAsync(dst, src, sizeof(T), hipMemcpyDeviceToHost, s), what) &&
+           hip_ok(hipStreamSynchronize(s), what);
+}
+
 static inline int64_t div_up(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// one lane per item: n items (a launch needs a workgroup even for none) in workgroups of `threads` on stream s
+static inline unsigned grid_of(int64_t n, int threads) { return (unsigned)(n > threads ? div_up(n, threads) : 1); }
+#define LNERF_LAUNCH(kernel, n, threads, s, ...) \
+    hipLaunchKernelGGL(kernel, dim3(::lnerf::grid_of(n, threads)), dim3(threads), 0, s, __VA_ARGS__)
 
 // ---------------------------------------------------------------- device helpers
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }

@@ -4,7 +4,7 @@
 // Launches (one lane per face, half-edge or vertex; the only atomics are order-independent: counts and a 64-bit min):
 //   setup      k_dc_check    index range and repeated indices of the input faces -> keep flags, bad-face count
 //              (scan)        compaction of the kept faces (k_dc_compact_faces)
-//   lists      k_dc_count, (scan), k_dc_fill, k_dc_sort   vertex -> face lists, each sorted ascending
+//   lists      vertex_face_lists (mesh_shared.h)   vertex -> face lists, each sorted ascending
 //   quadrics   k_dc_quadric  per vertex, its faces' plane quadrics in ascending face order (f64)
 //   round      k_dc_status   locked flag, K1 = none, remap = identity
 //              k_dc_eval     per half-edge: validity, v*, cost, key; atomic min of the key into K1 of both ends
@@ -12,100 +12,43 @@
 //              -- host read of the selected count --
 //              k_dc_rank     (only in the round that would pass the target) keep the m smallest keys
 //              k_dc_apply, k_dc_remap, (scan), k_dc_compact_faces, lists of the new faces
-//   output     k_dc_count, k_dc_used, (scan), k_dc_out_verts, k_dc_out_faces, lists, k_dc_normals, k_dc_counts
-// scan = k_dc_scan_blocks, k_scan_top (scan.h, one workgroup), k_dc_scan_add: exclusive int32 prefix with the total at [n].
+//   output     k_vf_count, k_dc_used, (scan), k_dc_out_verts, k_dc_out_faces, lists, k_vertex_normals (mesh_shared.h),
+//              k_dc_counts
+// scan = scan_flat (scan.h): exclusive int32 prefix with the total at [n].
 #include <algorithm>
 #include <utility>
 
 #include "common.h"
+#include "mesh_shared.h"
 #include "scan.h"
 
 namespace lnerf {
 
-constexpr int DC_THREADS = 256;
-constexpr int DC_PPT = 16;
-constexpr int DC_BLOCK = DC_THREADS * DC_PPT;
 constexpr unsigned long long DC_NONE = ~0ull;
 
-__device__ __forceinline__ int dc_gid() { return blockIdx.x * DC_THREADS + threadIdx.x; }
-
-// ---------------------------------------------------------------- exclusive scan, int32, total at out[n]
-__global__ void __launch_bounds__(DC_THREADS)
-k_dc_scan_blocks(const int32_t *__restrict__ in, int n, int32_t *__restrict__ out, int32_t *__restrict__ blk) {
-    const int base = blockIdx.x * DC_BLOCK + threadIdx.x * DC_PPT;
-    int sum[1] = {0}, run[1], tot[1];
-    for (int q = 0; q < DC_PPT; ++q)
-        if (base + q < n) sum[0] += in[base + q];
-    block_exclusive_scan<DC_THREADS>(sum, run, tot);
-    for (int q = 0; q < DC_PPT; ++q)
-        if (base + q < n) {
-            const int x = in[base + q];
-            out[base + q] = run[0];
-            run[0] += x;
-        }
-    if (threadIdx.x == 0) blk[blockIdx.x] = tot[0];
+// ---------------------------------------------------------------- faces
+__global__ void __launch_bounds__(MESH_THREADS)
+k_dc_check(const int32_t *__restrict__ faces, int F, int V, int32_t *__restrict__ keep,
+           unsigned long long *__restrict__ n_bad) {
+    const int f = mesh_gid();
+    bool bad = false;
+    if (f < F) {
+        int v[3];
+        bad = !face_ok(faces, V, f, v);
+        keep[f] = !bad && !face_repeats(v[0], v[1], v[2]) ? 1 : 0;
+    }
+    count_bad(bad, n_bad);
 }
 
-__global__ void __launch_bounds__(DC_THREADS)
-k_dc_scan_add(int32_t *__restrict__ out, int n, const int32_t *__restrict__ blk, int nb) {
-    const int i = dc_gid();
-    if (i < n) out[i] += blk[i / DC_BLOCK];
-    if (i == 0) out[n] = blk[nb];
-}
-
-// ---------------------------------------------------------------- faces and vertex -> face lists
-__device__ __forceinline__ bool dc_degenerate(int a, int b, int c) { return a == b || b == c || c == a; }
-
-__global__ void __launch_bounds__(DC_THREADS)
-k_dc_check(const int32_t *__restrict__ faces, int F, int V, int32_t *__restrict__ keep, int32_t *__restrict__ bad) {
-    const int f = dc_gid();
-    if (f >= F) return;
-    const int a = faces[(int64_t)f * 3], b = faces[(int64_t)f * 3 + 1], c = faces[(int64_t)f * 3 + 2];
-    const bool in = a >= 0 && a < V && b >= 0 && b < V && c >= 0 && c < V;
-    if (!in) atomicAdd(bad, 1);
-    keep[f] = in && !dc_degenerate(a, b, c) ? 1 : 0;
-}
-
-__global__ void __launch_bounds__(DC_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_dc_compact_faces(const int32_t *__restrict__ src, int F, const int32_t *__restrict__ keep,
                    const int32_t *__restrict__ at, int32_t *__restrict__ dst) {
-    const int f = dc_gid();
+    const int f = mesh_gid();
     if (f >= F || !keep[f]) return;
     const int64_t o = (int64_t)at[f] * 3;
     dst[o] = src[(int64_t)f * 3];
     dst[o + 1] = src[(int64_t)f * 3 + 1];
     dst[o + 2] = src[(int64_t)f * 3 + 2];
-}
-
-__global__ void __launch_bounds__(DC_THREADS)
-k_dc_count(const int32_t *__restrict__ faces, int F, int32_t *__restrict__ cnt) {
-    const int i = dc_gid();
-    if (i < 3 * F) atomicAdd(&cnt[faces[i]], 1);
-}
-
-__global__ void __launch_bounds__(DC_THREADS)
-k_dc_fill(const int32_t *__restrict__ faces, int F, const int32_t *__restrict__ off, int32_t *__restrict__ cur,
-          int32_t *__restrict__ list) {
-    const int i = dc_gid();
-    if (i >= 3 * F) return;
-    const int w = faces[i];
-    list[off[w] + atomicAdd(&cur[w], 1)] = i / 3;
-}
-
-__global__ void __launch_bounds__(DC_THREADS)
-k_dc_sort(const int32_t *__restrict__ off, int V, int32_t *__restrict__ list) {
-    const int w = dc_gid();
-    if (w >= V) return;
-    const int b = off[w], e = off[w + 1];
-    for (int i = b + 1; i < e; ++i) {          // insertion sort: the lists are short
-        const int x = list[i];
-        int j = i - 1;
-        while (j >= b && list[j] > x) {
-            list[j + 1] = list[j];
-            --j;
-        }
-        list[j + 1] = x;
-    }
 }
 
 // ---------------------------------------------------------------- quadrics: a00 a01 a02 a11 a12 a22 b0 b1 b2 c
@@ -135,10 +78,10 @@ __device__ __forceinline__ void dc_face_quadric(const float *__restrict__ pos, c
     q[6] = w * (n0 * d); q[7] = w * (n1 * d); q[8] = w * (n2 * d); q[9] = w * (d * d);
 }
 
-__global__ void __launch_bounds__(DC_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_dc_quadric(const float *__restrict__ pos, const int32_t *__restrict__ faces, const int32_t *__restrict__ off,
              const int32_t *__restrict__ list, int V, double *__restrict__ Q) {
-    const int w = dc_gid();
+    const int w = mesh_gid();
     if (w >= V) return;
     double acc[10];
 #pragma unroll
@@ -154,18 +97,10 @@ k_dc_quadric(const float *__restrict__ pos, const int32_t *__restrict__ faces, c
 }
 
 // ---------------------------------------------------------------- a round
-// the vertices after / before w in face f (w must be a corner of f)
-__device__ __forceinline__ void dc_corner(const int32_t *__restrict__ faces, int f, int w, int &nxt, int &prv) {
-    const int a = faces[(int64_t)f * 3], b = faces[(int64_t)f * 3 + 1], c = faces[(int64_t)f * 3 + 2];
-    if (a == w) { nxt = b; prv = c; }
-    else if (b == w) { nxt = c; prv = a; }
-    else { nxt = a; prv = b; }
-}
-
-__global__ void __launch_bounds__(DC_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_dc_status(const int32_t *__restrict__ faces, const int32_t *__restrict__ off, const int32_t *__restrict__ list, int V,
             int32_t *__restrict__ locked, unsigned long long *__restrict__ K1, int32_t *__restrict__ remap) {
-    const int w = dc_gid();
+    const int w = mesh_gid();
     if (w >= V) return;
     K1[w] = DC_NONE;
     remap[w] = w;
@@ -174,11 +109,11 @@ k_dc_status(const int32_t *__restrict__ faces, const int32_t *__restrict__ off, 
     // every neighbour must follow w in exactly one face and precede it in exactly one
     for (int k = 0; k < deg && !lock; ++k) {
         int nk, pk;
-        dc_corner(faces, list[b + k], w, nk, pk);
+        face_corner(faces, list[b + k], w, nk, pk);
         int nn = 0, pn = 0, np = 0, pp = 0;
         for (int j = 0; j < deg; ++j) {
             int nj, pj;
-            dc_corner(faces, list[b + j], w, nj, pj);
+            face_corner(faces, list[b + j], w, nj, pj);
             nn += nj == nk; pn += pj == nk; np += nj == pk; pp += pj == pk;
         }
         lock = nn != 1 || pn != 1 || np != 1 || pp != 1;
@@ -187,11 +122,11 @@ k_dc_status(const int32_t *__restrict__ faces, const int32_t *__restrict__ off, 
         int cur = 0, len = 0;
         for (int s = 1; s <= deg; ++s) {
             int nc, pc;
-            dc_corner(faces, list[b + cur], w, nc, pc);
+            face_corner(faces, list[b + cur], w, nc, pc);
             int j = 0;
             for (; j < deg - 1; ++j) {   // (there is one: every nxt is exactly one face's prv)
                 int nj, pj;
-                dc_corner(faces, list[b + j], w, nj, pj);
+                face_corner(faces, list[b + j], w, nj, pj);
                 if (pj == nc) break;
             }
             cur = j;
@@ -251,12 +186,12 @@ __device__ __forceinline__ bool dc_face_blocks(const float *__restrict__ pos, co
     return !(m[0][0] * m[1][0] + m[0][1] * m[1][1] + m[0][2] * m[1][2] > 0.0);
 }
 
-__global__ void __launch_bounds__(DC_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_dc_eval(const float *__restrict__ pos, const int32_t *__restrict__ faces, int F, const double *__restrict__ Q,
           const int32_t *__restrict__ off, const int32_t *__restrict__ list, const int32_t *__restrict__ locked,
           float max_error, unsigned long long *__restrict__ keys, float *__restrict__ vstar,
           unsigned long long *__restrict__ K1) {
-    const int e = dc_gid();
+    const int e = mesh_gid();
     if (e >= 3 * F) return;
     const int f = e / 3, k = e - 3 * f;
     const int u = faces[e], v = faces[(int64_t)f * 3 + (k == 2 ? 0 : k + 1)];
@@ -268,10 +203,10 @@ k_dc_eval(const float *__restrict__ pos, const int32_t *__restrict__ faces, int 
     int common = 0;
     for (int i = 0; i < du; ++i) {
         int ni, pi;
-        dc_corner(faces, list[bu + i], u, ni, pi);
+        face_corner(faces, list[bu + i], u, ni, pi);
         for (int j = 0; j < dv; ++j) {
             int nj, pj;
-            dc_corner(faces, list[bv + j], v, nj, pj);
+            face_corner(faces, list[bv + j], v, nj, pj);
             common += nj == ni;
         }
     }
@@ -326,30 +261,30 @@ k_dc_eval(const float *__restrict__ pos, const int32_t *__restrict__ faces, int 
     atomicMin(&K1[v], key);
 }
 
-__global__ void __launch_bounds__(DC_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_dc_face_key(const int32_t *__restrict__ faces, int F, const unsigned long long *__restrict__ K1,
               unsigned long long *__restrict__ FK) {
-    const int f = dc_gid();
+    const int f = mesh_gid();
     if (f >= F) return;
     const unsigned long long a = K1[faces[(int64_t)f * 3]], b = K1[faces[(int64_t)f * 3 + 1]],
                              c = K1[faces[(int64_t)f * 3 + 2]];
     FK[f] = min(a, min(b, c));
 }
 
-__global__ void __launch_bounds__(DC_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_dc_k2(const int32_t *__restrict__ off, const int32_t *__restrict__ list, int V,
         const unsigned long long *__restrict__ FK, unsigned long long *__restrict__ K2) {
-    const int w = dc_gid();
+    const int w = mesh_gid();
     if (w >= V) return;
     unsigned long long m = DC_NONE;
     for (int s = off[w]; s < off[w + 1]; ++s) m = min(m, FK[list[s]]);
     K2[w] = m;
 }
 
-__global__ void __launch_bounds__(DC_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_dc_select(const int32_t *__restrict__ faces, int F, const unsigned long long *__restrict__ keys,
             const unsigned long long *__restrict__ K2, int32_t *__restrict__ flag) {
-    const int e = dc_gid();
+    const int e = mesh_gid();
     if (e >= 3 * F) return;
     const unsigned long long key = keys[e];
     bool s = false;
@@ -361,36 +296,36 @@ k_dc_select(const int32_t *__restrict__ faces, int F, const unsigned long long *
     flag[e] = s ? 1 : 0;
 }
 
-__global__ void __launch_bounds__(DC_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_dc_gather(const int32_t *__restrict__ flag, const int32_t *__restrict__ at, int n, int cap,
             int32_t *__restrict__ sel) {
-    const int e = dc_gid();
+    const int e = mesh_gid();
     if (e < n && flag[e] && at[e] < cap) sel[at[e]] = e;
 }
 
 // keep[i] = 1 iff the key of selected edge i is among the m smallest (keys are distinct)
-__global__ void __launch_bounds__(DC_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_dc_rank(const int32_t *__restrict__ sel, int S, int m, const unsigned long long *__restrict__ keys,
           int32_t *__restrict__ keep) {
-    __shared__ unsigned long long s_k[DC_THREADS];
-    const int i = dc_gid();
+    __shared__ unsigned long long s_k[MESH_THREADS];
+    const int i = mesh_gid();
     const unsigned long long mine = i < S ? keys[sel[i]] : DC_NONE;
     int rank = 0;
-    for (int t = 0; t < S; t += DC_THREADS) {
+    for (int t = 0; t < S; t += MESH_THREADS) {
         __syncthreads();
         s_k[threadIdx.x] = t + (int)threadIdx.x < S ? keys[sel[t + threadIdx.x]] : DC_NONE;
         __syncthreads();
-        const int n = min(DC_THREADS, S - t);
+        const int n = min(MESH_THREADS, S - t);
         for (int j = 0; j < n; ++j) rank += s_k[j] < mine;
     }
     if (i < S) keep[i] = rank < m ? 1 : 0;
 }
 
-__global__ void __launch_bounds__(DC_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_dc_apply(const int32_t *__restrict__ faces, const int32_t *__restrict__ sel, int S, const int32_t *__restrict__ keep,
            const float *__restrict__ vstar, float *__restrict__ pos, double *__restrict__ Q,
            int32_t *__restrict__ remap) {
-    const int i = dc_gid();
+    const int i = mesh_gid();
     if (i >= S || (keep && !keep[i])) return;
     const int e = sel[i];
     const int f = e / 3, k = e - 3 * f;
@@ -402,28 +337,28 @@ k_dc_apply(const int32_t *__restrict__ faces, const int32_t *__restrict__ sel, i
     remap[v] = u;
 }
 
-__global__ void __launch_bounds__(DC_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_dc_remap(int32_t *__restrict__ faces, int F, const int32_t *__restrict__ remap, int32_t *__restrict__ keep) {
-    const int f = dc_gid();
+    const int f = mesh_gid();
     if (f >= F) return;
     const int a = remap[faces[(int64_t)f * 3]], b = remap[faces[(int64_t)f * 3 + 1]], c = remap[faces[(int64_t)f * 3 + 2]];
     faces[(int64_t)f * 3] = a;
     faces[(int64_t)f * 3 + 1] = b;
     faces[(int64_t)f * 3 + 2] = c;
-    keep[f] = dc_degenerate(a, b, c) ? 0 : 1;
+    keep[f] = face_repeats(a, b, c) ? 0 : 1;
 }
 
 // ---------------------------------------------------------------- output
-__global__ void __launch_bounds__(DC_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_dc_used(const int32_t *__restrict__ cnt, int V, int32_t *__restrict__ used) {
-    const int w = dc_gid();
+    const int w = mesh_gid();
     if (w < V) used[w] = cnt[w] > 0 ? 1 : 0;
 }
 
-__global__ void __launch_bounds__(DC_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_dc_out_verts(const float *__restrict__ pos, const int32_t *__restrict__ used, const int32_t *__restrict__ at, int V,
                float *__restrict__ out) {
-    const int w = dc_gid();
+    const int w = mesh_gid();
     if (w >= V || !used[w]) return;
     const int64_t o = (int64_t)at[w] * 3;
     out[o] = pos[(int64_t)w * 3];
@@ -431,34 +366,10 @@ k_dc_out_verts(const float *__restrict__ pos, const int32_t *__restrict__ used, 
     out[o + 2] = pos[(int64_t)w * 3 + 2];
 }
 
-__global__ void __launch_bounds__(DC_THREADS)
+__global__ void __launch_bounds__(MESH_THREADS)
 k_dc_out_faces(const int32_t *__restrict__ faces, int F, const int32_t *__restrict__ at, int32_t *__restrict__ out) {
-    const int i = dc_gid();
+    const int i = mesh_gid();
     if (i < 3 * F) out[i] = at[faces[i]];
-}
-
-__global__ void __launch_bounds__(DC_THREADS)
-k_dc_normals(const float *__restrict__ verts, const int32_t *__restrict__ faces, const int32_t *__restrict__ off,
-             const int32_t *__restrict__ list, int V, float *__restrict__ normals) {
-    const int w = dc_gid();
-    if (w >= V) return;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    for (int s = off[w]; s < off[w + 1]; ++s) {
-        const int64_t f = list[s];
-        const int64_t a = faces[f * 3], b = faces[f * 3 + 1], c = faces[f * 3 + 2];
-        const float e1x = verts[b * 3] - verts[a * 3], e1y = verts[b * 3 + 1] - verts[a * 3 + 1],
-                    e1z = verts[b * 3 + 2] - verts[a * 3 + 2];
-        const float e2x = verts[c * 3] - verts[a * 3], e2y = verts[c * 3 + 1] - verts[a * 3 + 1],
-                    e2z = verts[c * 3 + 2] - verts[a * 3 + 2];
-        s0 = s0 + (e1y * e2z - e1z * e2y);
-        s1 = s1 + (e1z * e2x - e1x * e2z);
-        s2 = s2 + (e1x * e2y - e1y * e2x);
-    }
-    const float l2 = s0 * s0 + s1 * s1 + s2 * s2;
-    const float inv = l2 > 0.f ? 1.0f / sqrtf(l2) : 0.f;
-    normals[(int64_t)w * 3] = s0 * inv;
-    normals[(int64_t)w * 3 + 1] = s1 * inv;
-    normals[(int64_t)w * 3 + 2] = s2 * inv;
 }
 
 __global__ void k_dc_counts(const int32_t *__restrict__ vtot, int F, int rounds, int64_t collapses,
@@ -473,96 +384,42 @@ __global__ void k_dc_counts(const int32_t *__restrict__ vtot, int F, int rounds,
 
 // ---------------------------------------------------------------- host side
 struct DcLayout {
-    size_t pos, Q, fa, fb, cnt, off, list, locked, remap, K1, K2, FK, keys, vstar, flag, at, sel, keep, blk, dev, bytes;
+    size_t pos, Q, fa, fb, cnt, off, list, locked, remap, K1, K2, FK, keys, vstar, flag, pfx, sel, keep, blk, dev, bytes;
 };
 
 static DcLayout dc_layout(int V, int F) {
     const int64_t n = std::max(3 * (int64_t)F, (int64_t)V) + 1;     // longest scan input, plus its total
-    const int64_t nb = div_up(n, DC_BLOCK) + 1;
     DcLayout L;
-    size_t o = 0;
-    auto take = [&o](size_t bytes) { const size_t at = o; o += align256(bytes); return at; };
-    L.pos = take((size_t)V * 12);
-    L.Q = take((size_t)V * 80);
-    L.fa = take((size_t)F * 12);
-    L.fb = take((size_t)F * 12);
-    L.cnt = take((size_t)V * 4);
-    L.off = take(((size_t)V + 1) * 4);
-    L.list = take((size_t)F * 12);
-    L.locked = take((size_t)V * 4);
-    L.remap = take((size_t)V * 4);
-    L.K1 = take((size_t)V * 8);
-    L.K2 = take((size_t)V * 8);
-    L.FK = take((size_t)F * 8);
-    L.keys = take((size_t)F * 24);
-    L.vstar = take((size_t)F * 36);
-    L.flag = take((size_t)n * 4);
-    L.at = take((size_t)n * 4);
-    L.sel = take(((size_t)F + 1) * 4);
-    L.keep = take(((size_t)F + 1) * 4);
-    L.blk = take((size_t)nb * 4);
-    L.dev = take(64);
-    L.bytes = o;
+    Carve c;
+    L.pos = c.take((size_t)V * 12);
+    L.Q = c.take((size_t)V * 80);
+    L.fa = c.take((size_t)F * 12);
+    L.fb = c.take((size_t)F * 12);
+    L.cnt = c.take((size_t)V * 4);
+    L.off = c.take(((size_t)V + 1) * 4);
+    L.list = c.take((size_t)F * 12);
+    L.locked = c.take((size_t)V * 4);
+    L.remap = c.take((size_t)V * 4);
+    L.K1 = c.take((size_t)V * 8);
+    L.K2 = c.take((size_t)V * 8);
+    L.FK = c.take((size_t)F * 8);
+    L.keys = c.take((size_t)F * 24);
+    L.vstar = c.take((size_t)F * 36);
+    L.flag = c.take((size_t)n * 4);
+    L.pfx = c.take((size_t)n * 4);
+    L.sel = c.take(((size_t)F + 1) * 4);
+    L.keep = c.take(((size_t)F + 1) * 4);
+    L.blk = c.take(scan_flat_blk_bytes(n));
+    L.dev = c.take(64);
+    L.bytes = c.o;
     return L;
 }
-
-struct DcRun {
-    char *base;
-    DcLayout L;
-    hipStream_t s;
-    template <class T> T *at(size_t o) const { return reinterpret_cast<T *>(base + o); }
-};
-
-static unsigned dc_grid(int64_t n) { return (unsigned)std::max<int64_t>(1, div_up(n, DC_THREADS)); }
 
 #define DC_TRY(x)                          \
     do {                                   \
         const int rc__ = (x);              \
         if (rc__ != LNERF_OK) return rc__; \
     } while (0)
-
-#define DC_HIP(x, what)                                                               \
-    do {                                                                              \
-        const hipError_t e__ = (x);                                                   \
-        if (e__ != hipSuccess) {                                                      \
-            ::lnerf::set_error("decimate(%s): %s", what, hipGetErrorString(e__));     \
-            return LNERF_ERR_HIP;                                                     \
-        }                                                                             \
-    } while (0)
-
-// exclusive prefix of in[0, n) into out[0, n], out[n] = total
-static int dc_scan(const DcRun &r, const int32_t *in, int n, int32_t *out) {
-    const int nb = (int)div_up(std::max(n, 1), DC_BLOCK);
-    int32_t *blk = r.at<int32_t>(r.L.blk);
-    hipLaunchKernelGGL(k_dc_scan_blocks, dim3(nb), dim3(DC_THREADS), 0, r.s, in, n, out, blk);
-    // (int32: more than 1024 blocks, where a thread of k_scan_top owns several entries, takes over 1.4 M faces, too many
-    // for a test through the Python restatement; the int64 instantiation of the same template is tested on that side)
-    hipLaunchKernelGGL(k_scan_top<int32_t>, dim3(1), dim3(SCAN_TOP_THREADS), 0, r.s, blk, (int32_t *)nullptr, (int64_t)nb,
-                       blk + nb, (int32_t *)nullptr);
-    hipLaunchKernelGGL(k_dc_scan_add, dim3(dc_grid(std::max(n, 1))), dim3(DC_THREADS), 0, r.s, out, n, blk, nb);
-    LNERF_CHECK_LAUNCH("decimate(scan)");
-    return LNERF_OK;
-}
-
-// vertex -> face lists of faces [F] over V vertices: off [V+1], list [3F], ascending per vertex
-static int dc_lists(const DcRun &r, const int32_t *faces, int F, int V) {
-    int32_t *cnt = r.at<int32_t>(r.L.cnt), *off = r.at<int32_t>(r.L.off), *list = r.at<int32_t>(r.L.list);
-    DC_HIP(hipMemsetAsync(cnt, 0, (size_t)V * 4, r.s), "memset");
-    hipLaunchKernelGGL(k_dc_count, dim3(dc_grid(3 * (int64_t)F)), dim3(DC_THREADS), 0, r.s, faces, F, cnt);
-    LNERF_CHECK_LAUNCH("decimate(count)");
-    DC_TRY(dc_scan(r, cnt, V, off));
-    DC_HIP(hipMemsetAsync(cnt, 0, (size_t)V * 4, r.s), "memset");
-    hipLaunchKernelGGL(k_dc_fill, dim3(dc_grid(3 * (int64_t)F)), dim3(DC_THREADS), 0, r.s, faces, F, off, cnt, list);
-    hipLaunchKernelGGL(k_dc_sort, dim3(dc_grid(V)), dim3(DC_THREADS), 0, r.s, off, V, list);
-    LNERF_CHECK_LAUNCH("decimate(lists)");
-    return LNERF_OK;
-}
-
-static int dc_read(const DcRun &r, const int32_t *src, int32_t *dst) {
-    DC_HIP(hipMemcpyAsync(dst, src, 4, hipMemcpyDeviceToHost, r.s), "read-back");
-    DC_HIP(hipStreamSynchronize(r.s), "read-back");
-    return LNERF_OK;
-}
 
 }  // namespace lnerf
 
@@ -571,18 +428,14 @@ using namespace lnerf;
 extern "C" {
 
 size_t lnerf_decimate_scratch_bytes(int n_verts, int n_faces) {
-    if (n_verts < 0 || n_faces < 0 || n_faces > LNERF_DECIMATE_MAX_FACES || n_verts > 3 * LNERF_DECIMATE_MAX_FACES)
-        return 0;
+    if (!mesh_sizes_ok(n_verts, n_faces, LNERF_DECIMATE_MAX_FACES)) return 0;
     return dc_layout(n_verts, n_faces).bytes;
 }
 
 int lnerf_decimate(const float *verts, int n_verts, const int32_t *faces, int n_faces, int target_faces, float max_error,
                    int max_rounds, void *scratch, size_t scratch_bytes, float *verts_out, int32_t *faces_out,
                    float *normals_out, int64_t *counts_dev, lnerf_stream_t stream) {
-    LNERF_REQUIRE(n_verts >= 0 && n_faces >= 0 && n_faces <= LNERF_DECIMATE_MAX_FACES &&
-                  n_verts <= 3 * LNERF_DECIMATE_MAX_FACES,
-                  "decimate: %d vertices / %d faces out of range (faces <= %d)", n_verts, n_faces,
-                  LNERF_DECIMATE_MAX_FACES);
+    MESH_REQUIRE_SIZES("decimate", n_verts, n_faces, LNERF_DECIMATE_MAX_FACES);
     LNERF_REQUIRE(target_faces >= 0 && max_rounds >= 0, "decimate: target_faces %d and max_rounds %d must be >= 0",
                   target_faces, max_rounds);
     LNERF_REQUIRE(max_error >= 0.f, "decimate: max_error must be >= 0 (+inf: none)");
@@ -591,37 +444,47 @@ int lnerf_decimate(const float *verts, int n_verts, const int32_t *faces, int n_
     const DcLayout L = dc_layout(n_verts, n_faces);
     LNERF_REQUIRE(scratch_bytes >= L.bytes, "decimate: scratch of %zu bytes, need %zu", scratch_bytes, L.bytes);
     LNERF_REQUIRE(((uintptr_t)scratch & 15) == 0, "decimate: scratch must be 16-byte aligned");
-    const DcRun r{reinterpret_cast<char *>(scratch), L, as_stream(stream)};
-    hipStream_t s = r.s;
+    hipStream_t s = as_stream(stream);
     const int V = n_verts;
-    float *pos = r.at<float>(L.pos), *vstar = r.at<float>(L.vstar);
-    double *Q = r.at<double>(L.Q);
-    int32_t *fa = r.at<int32_t>(L.fa), *fb = r.at<int32_t>(L.fb);
-    int32_t *off = r.at<int32_t>(L.off), *list = r.at<int32_t>(L.list), *cnt = r.at<int32_t>(L.cnt);
-    int32_t *locked = r.at<int32_t>(L.locked), *remap = r.at<int32_t>(L.remap);
-    int32_t *flag = r.at<int32_t>(L.flag), *at = r.at<int32_t>(L.at), *sel = r.at<int32_t>(L.sel);
-    int32_t *keep = r.at<int32_t>(L.keep), *dev = r.at<int32_t>(L.dev);
-    unsigned long long *K1 = r.at<unsigned long long>(L.K1), *K2 = r.at<unsigned long long>(L.K2);
-    unsigned long long *FK = r.at<unsigned long long>(L.FK), *keys = r.at<unsigned long long>(L.keys);
+    float *pos = at<float>(scratch, L.pos), *vstar = at<float>(scratch, L.vstar);
+    double *Q = at<double>(scratch, L.Q);
+    int32_t *fa = at<int32_t>(scratch, L.fa), *fb = at<int32_t>(scratch, L.fb);
+    int32_t *off = at<int32_t>(scratch, L.off), *list = at<int32_t>(scratch, L.list), *cnt = at<int32_t>(scratch, L.cnt);
+    int32_t *locked = at<int32_t>(scratch, L.locked), *remap = at<int32_t>(scratch, L.remap);
+    int32_t *flag = at<int32_t>(scratch, L.flag), *pfx = at<int32_t>(scratch, L.pfx), *sel = at<int32_t>(scratch, L.sel);
+    int32_t *keep = at<int32_t>(scratch, L.keep), *blk = at<int32_t>(scratch, L.blk);
+    unsigned long long *K1 = at<unsigned long long>(scratch, L.K1), *K2 = at<unsigned long long>(scratch, L.K2);
+    unsigned long long *FK = at<unsigned long long>(scratch, L.FK), *keys = at<unsigned long long>(scratch, L.keys);
+    unsigned long long *n_bad = at<unsigned long long>(scratch, L.dev);
+    const int32_t *zero = at<int32_t>(scratch, L.dev) + 2;      // (a word that stays cleared)
+    // exclusive prefix of in[0, n) into pfx[0, n], pfx[n] = total
+    auto scan = [&](const int32_t *in, int n) { return scan_flat(in, n, pfx, blk, s, "decimate(scan)"); };
+    // vertex -> face lists of f [nf] over nv vertices: off [nv+1], list [3 nf], ascending per vertex
+    auto lists = [&](const int32_t *f, int nf, int nv) {
+        return vertex_face_lists(f, nf, nv, cnt, off, list, blk, s, "decimate(lists)");
+    };
+    auto read = [&](const int32_t *src, int32_t *dst) {
+        return read_back(src, dst, s, "decimate(read-back)") ? LNERF_OK : LNERF_ERR_HIP;
+    };
 
     // ---- input: index range first (no kernel reads through a face before this), repeated indices, compaction
-    DC_HIP(hipMemsetAsync(dev, 0, 64, s), "memset");
+    if (!hip_ok(hipMemsetAsync(n_bad, 0, 64, s), "decimate(memset)")) return LNERF_ERR_HIP;
     int F = 0;
     if (n_faces > 0) {
-        hipLaunchKernelGGL(k_dc_check, dim3(dc_grid(n_faces)), dim3(DC_THREADS), 0, s, faces, n_faces, V, flag, dev);
+        MESH_LAUNCH(k_dc_check, n_faces, faces, n_faces, V, flag, n_bad);
         LNERF_CHECK_LAUNCH("decimate(check)");
-        int bad = 0;
-        DC_TRY(dc_read(r, dev, &bad));
-        LNERF_REQUIRE(bad == 0, "decimate: %d faces index outside [0, %d)", bad, V);
-        DC_TRY(dc_scan(r, flag, n_faces, at));
-        hipLaunchKernelGGL(k_dc_compact_faces, dim3(dc_grid(n_faces)), dim3(DC_THREADS), 0, s, faces, n_faces, flag, at,
-                           fa);
+        unsigned long long bad = 0;
+        if (!read_back(n_bad, &bad, s, "decimate(read-back)")) return LNERF_ERR_HIP;
+        LNERF_REQUIRE(bad == 0, "decimate: %d faces index outside [0, %d)", (int)bad, V);
+        DC_TRY(scan(flag, n_faces));
+        MESH_LAUNCH(k_dc_compact_faces, n_faces, faces, n_faces, flag, pfx, fa);
         LNERF_CHECK_LAUNCH("decimate(compact)");
-        DC_TRY(dc_read(r, at + n_faces, &F));
+        DC_TRY(read(pfx + n_faces, &F));
     }
-    if (V > 0) DC_HIP(hipMemcpyAsync(pos, verts, (size_t)V * 12, hipMemcpyDeviceToDevice, s), "copy");
-    DC_TRY(dc_lists(r, fa, F, V));
-    hipLaunchKernelGGL(k_dc_quadric, dim3(dc_grid(V)), dim3(DC_THREADS), 0, s, pos, fa, off, list, V, Q);
+    if (V > 0 && !hip_ok(hipMemcpyAsync(pos, verts, (size_t)V * 12, hipMemcpyDeviceToDevice, s), "decimate(copy)"))
+        return LNERF_ERR_HIP;
+    DC_TRY(lists(fa, F, V));
+    MESH_LAUNCH(k_dc_quadric, V, pos, fa, off, list, V, Q);
     LNERF_CHECK_LAUNCH("decimate(quadric)");
 
     // ---- rounds
@@ -629,61 +492,60 @@ int lnerf_decimate(const float *verts, int n_verts, const int32_t *faces, int n_
     int64_t collapses = 0;
     while (rounds < max_rounds && F > target_faces) {
         const int E = 3 * F;
-        hipLaunchKernelGGL(k_dc_status, dim3(dc_grid(V)), dim3(DC_THREADS), 0, s, fa, off, list, V, locked, K1, remap);
-        hipLaunchKernelGGL(k_dc_eval, dim3(dc_grid(E)), dim3(DC_THREADS), 0, s, pos, fa, F, Q, off, list, locked,
+        MESH_LAUNCH(k_dc_status, V, fa, off, list, V, locked, K1, remap);
+        MESH_LAUNCH(k_dc_eval, E, pos, fa, F, Q, off, list, locked,
                            max_error, keys, vstar, K1);
-        hipLaunchKernelGGL(k_dc_face_key, dim3(dc_grid(F)), dim3(DC_THREADS), 0, s, fa, F, K1, FK);
-        hipLaunchKernelGGL(k_dc_k2, dim3(dc_grid(V)), dim3(DC_THREADS), 0, s, off, list, V, FK, K2);
-        hipLaunchKernelGGL(k_dc_select, dim3(dc_grid(E)), dim3(DC_THREADS), 0, s, fa, F, keys, K2, flag);
+        MESH_LAUNCH(k_dc_face_key, F, fa, F, K1, FK);
+        MESH_LAUNCH(k_dc_k2, V, off, list, V, FK, K2);
+        MESH_LAUNCH(k_dc_select, E, fa, F, keys, K2, flag);
         LNERF_CHECK_LAUNCH("decimate(select)");
-        DC_TRY(dc_scan(r, flag, E, at));
-        hipLaunchKernelGGL(k_dc_gather, dim3(dc_grid(E)), dim3(DC_THREADS), 0, s, flag, at, E, F + 1, sel);
+        DC_TRY(scan(flag, E));
+        MESH_LAUNCH(k_dc_gather, E, flag, pfx, E, F + 1, sel);
         LNERF_CHECK_LAUNCH("decimate(gather)");
         int S = 0;
-        DC_TRY(dc_read(r, at + E, &S));
+        DC_TRY(read(pfx + E, &S));
         if (S == 0) break;
         // independent collapses own disjoint face pairs, so S <= F / 2 (the gather wrote at most F + 1 entries)
         LNERF_REQUIRE(2 * (int64_t)S <= F, "decimate: internal: %d independent collapses among %d faces", S, F);
         int m = S;
         if (F - 2 * S < target_faces) {
             m = (F - target_faces + 1) / 2;
-            hipLaunchKernelGGL(k_dc_rank, dim3(dc_grid(S)), dim3(DC_THREADS), 0, s, sel, S, m, keys, keep);
+            MESH_LAUNCH(k_dc_rank, S, sel, S, m, keys, keep);
         }
-        hipLaunchKernelGGL(k_dc_apply, dim3(dc_grid(S)), dim3(DC_THREADS), 0, s, fa, sel, S, m < S ? keep : nullptr,
+        MESH_LAUNCH(k_dc_apply, S, fa, sel, S, m < S ? keep : nullptr,
                            vstar, pos, Q, remap);
-        hipLaunchKernelGGL(k_dc_remap, dim3(dc_grid(F)), dim3(DC_THREADS), 0, s, fa, F, remap, flag);
+        MESH_LAUNCH(k_dc_remap, F, fa, F, remap, flag);
         LNERF_CHECK_LAUNCH("decimate(apply)");
-        DC_TRY(dc_scan(r, flag, F, at));
-        hipLaunchKernelGGL(k_dc_compact_faces, dim3(dc_grid(F)), dim3(DC_THREADS), 0, s, fa, F, flag, at, fb);
+        DC_TRY(scan(flag, F));
+        MESH_LAUNCH(k_dc_compact_faces, F, fa, F, flag, pfx, fb);
         LNERF_CHECK_LAUNCH("decimate(compact)");
         std::swap(fa, fb);
         F -= 2 * m;          // each collapse removes exactly its edge's two faces (link condition)
         ++rounds;
         collapses += m;
-        DC_TRY(dc_lists(r, fa, F, V));
+        DC_TRY(lists(fa, F, V));
     }
 
     // ---- output: referenced vertices in order, faces renumbered, normals
-    const int32_t *vtot = dev;      // (0: no vertices)
+    const int32_t *vtot = zero;      // (no vertices)
     if (V > 0) {
-        DC_HIP(hipMemsetAsync(cnt, 0, (size_t)V * 4, s), "memset");
-        hipLaunchKernelGGL(k_dc_count, dim3(dc_grid(3 * (int64_t)F)), dim3(DC_THREADS), 0, s, fa, F, cnt);
-        hipLaunchKernelGGL(k_dc_used, dim3(dc_grid(V)), dim3(DC_THREADS), 0, s, cnt, V, flag);
+        if (!hip_ok(hipMemsetAsync(cnt, 0, (size_t)V * 4, s), "decimate(memset)")) return LNERF_ERR_HIP;
+        MESH_LAUNCH(k_vf_count, F, fa, F, cnt);
+        MESH_LAUNCH(k_dc_used, V, cnt, V, flag);
         LNERF_CHECK_LAUNCH("decimate(used)");
-        DC_TRY(dc_scan(r, flag, V, at));
-        hipLaunchKernelGGL(k_dc_out_verts, dim3(dc_grid(V)), dim3(DC_THREADS), 0, s, pos, flag, at, V, verts_out);
-        hipLaunchKernelGGL(k_dc_out_faces, dim3(dc_grid(3 * (int64_t)F)), dim3(DC_THREADS), 0, s, fa, F, at, faces_out);
+        DC_TRY(scan(flag, V));
+        MESH_LAUNCH(k_dc_out_verts, V, pos, flag, pfx, V, verts_out);
+        MESH_LAUNCH(k_dc_out_faces, 3 * (int64_t)F, fa, F, pfx, faces_out);
         LNERF_CHECK_LAUNCH("decimate(output)");
-        vtot = at + V;
+        vtot = pfx + V;
     }
-    hipLaunchKernelGGL(k_dc_counts, dim3(1), dim3(64), 0, s, vtot, F, rounds, collapses, counts_dev);
+    LNERF_LAUNCH(k_dc_counts, 1, 64, s, vtot, F, rounds, collapses, counts_dev);
     LNERF_CHECK_LAUNCH("decimate(counts)");
     if (normals_out && V > 0) {
         int Vout = 0;
-        DC_TRY(dc_read(r, vtot, &Vout));
-        DC_TRY(dc_lists(r, faces_out, F, Vout));   // lists of the output faces over the output vertices
-        hipLaunchKernelGGL(k_dc_normals, dim3(dc_grid(Vout)), dim3(DC_THREADS), 0, s, verts_out, faces_out, off, list,
-                           Vout, normals_out);
+        DC_TRY(read(vtot, &Vout));
+        DC_TRY(lists(faces_out, F, Vout));   // lists of the output faces over the output vertices
+        MESH_LAUNCH(k_vertex_normals, Vout, verts_out, faces_out, off, list, Vout, normals_out);
         LNERF_CHECK_LAUNCH("decimate(normals)");
     }
     return LNERF_OK;

@@ -4,13 +4,13 @@
 // lnerf_uv_raster, stage by stage (every pass linear in its work, no cross-workgroup waiting):
 //   ITEMS  k_uv_setup  one lane per face: pixel-space corners, area, candidate box; items = box area; an in-block
 //                      exclusive prefix of the items (int64) and per-block item / bad-index totals
-//          k_scan_top  (scan.h) ONE workgroup: exclusive prefix of the block totals (in place) -> counts[0] items,
+//          scan_top    (scan.h) ONE workgroup: exclusive prefix of the block totals (in place) -> counts[0] items,
 //                      [1] bad faces
 //   COVER  k_uv_cover  one lane per (face, box texel) item, so one big UV triangle does not serialise on one lane:
 //                      the item's face by binary search over the item prefix, the edge test, atomicMax of the face
 //                      index into texel_face (the largest covering index wins, whatever the order)
 //          k_uv_count  one lane per texel: covered texels per block of UV_THREADS texels
-//          k_scan_top  exclusive prefix of those -> counts[2] = P
+//          scan_top    exclusive prefix of those -> counts[2] = P
 //   EMIT   k_uv_emit   one lane per texel: rank among the block's covered texels (ballot / mbcnt + wave totals in LDS),
 //                      texel_idx and the surface point at block prefix + rank (ascending linear order)
 // lnerf_uv_dilate: one launch per gutter round (k_uv_dilate), ping-ponging between the caller's two buffers.
@@ -158,16 +158,19 @@ k_uv_dilate(const float *__restrict__ src, const uint8_t *__restrict__ msrc, flo
 
 struct UvLayout {
     int64_t nbF, nbT;
-    size_t off_bytes, blk_bytes, bytes;
+    size_t face_off, blk_items, blk_bad, blk_texels, bytes;
 };
 
 static UvLayout uv_layout(int n_faces, int R) {
     UvLayout L;
+    Carve c;
     L.nbF = div_up(n_faces, UV_THREADS);
     L.nbT = div_up((int64_t)R * R, UV_THREADS);
-    L.off_bytes = align256((size_t)n_faces * 8);
-    L.blk_bytes = align256((size_t)L.nbF * 8);
-    L.bytes = L.off_bytes + 2 * L.blk_bytes + (size_t)L.nbT * 8;
+    L.face_off = c.take((size_t)n_faces * 8);
+    L.blk_items = c.take((size_t)L.nbF * 8);
+    L.blk_bad = c.take((size_t)L.nbF * 8);
+    L.blk_texels = c.take((size_t)L.nbT * 8);
+    L.bytes = c.o;
     return L;
 }
 
@@ -203,41 +206,33 @@ int lnerf_uv_raster(const float *verts, int n_verts, const int32_t *faces, const
     m.verts = verts; m.faces = faces; m.vt = vt; m.ft = ft;
     m.n_verts = n_verts; m.n_vt = n_vt; m.n_faces = n_faces; m.R = R;
     m.Rf = (float)R;
-    int64_t *face_off = reinterpret_cast<int64_t *>(scratch);
-    int64_t *blk_items = reinterpret_cast<int64_t *>(reinterpret_cast<char *>(scratch) + L.off_bytes);
-    int64_t *blk_bad = reinterpret_cast<int64_t *>(reinterpret_cast<char *>(blk_items) + L.blk_bytes);
-    int64_t *blk_texels = reinterpret_cast<int64_t *>(reinterpret_cast<char *>(blk_bad) + L.blk_bytes);
+    int64_t *face_off = at<int64_t>(scratch, L.face_off), *blk_items = at<int64_t>(scratch, L.blk_items);
+    int64_t *blk_bad = at<int64_t>(scratch, L.blk_bad), *blk_texels = at<int64_t>(scratch, L.blk_texels);
     const int64_t n_texels = (int64_t)R * R;
     hipStream_t s = as_stream(stream);
     if (stages & LNERF_UV_ITEMS) {
         if (n_faces > 0) {
-            hipLaunchKernelGGL(k_uv_setup, dim3((unsigned)L.nbF), dim3(UV_THREADS), 0, s, m, face_off, blk_items, blk_bad);
+            LNERF_LAUNCH(k_uv_setup, n_faces, UV_THREADS, s, m, face_off, blk_items, blk_bad);
             LNERF_CHECK_LAUNCH("uv_raster(setup)");
         }
-        hipLaunchKernelGGL(k_scan_top<int64_t>, dim3(1), dim3(SCAN_TOP_THREADS), 0, s, blk_items, blk_bad, L.nbF,
-                           counts_dev, counts_dev + 1);
+        scan_top(blk_items, blk_bad, L.nbF, counts_dev, counts_dev + 1, s);
         LNERF_CHECK_LAUNCH("uv_raster(scan items)");
     }
     if (stages & LNERF_UV_COVER) {
-        if (hipMemsetAsync(texel_face, 0xff, (size_t)n_texels * 4, s) != hipSuccess) {
-            set_error("uv_raster: clearing texel_face failed");
+        if (!hip_ok(hipMemsetAsync(texel_face, 0xff, (size_t)n_texels * 4, s), "uv_raster: clearing texel_face"))
             return LNERF_ERR_HIP;
-        }
         for (int64_t base = 0; base < n_items; base += UV_ITEMS_PER_LAUNCH) {
             const int64_t n = min(n_items - base, UV_ITEMS_PER_LAUNCH);
-            hipLaunchKernelGGL(k_uv_cover, dim3((unsigned)div_up(n, UV_THREADS)), dim3(UV_THREADS), 0, s, m, face_off,
-                               blk_items, L.nbF, counts_dev, base, n, texel_face);
+            LNERF_LAUNCH(k_uv_cover, n, UV_THREADS, s, m, face_off, blk_items, L.nbF, counts_dev, base, n, texel_face);
             LNERF_CHECK_LAUNCH("uv_raster(cover)");
         }
-        hipLaunchKernelGGL(k_uv_count, dim3((unsigned)L.nbT), dim3(UV_THREADS), 0, s, texel_face, n_texels, blk_texels);
+        LNERF_LAUNCH(k_uv_count, n_texels, UV_THREADS, s, texel_face, n_texels, blk_texels);
         LNERF_CHECK_LAUNCH("uv_raster(count)");
-        hipLaunchKernelGGL(k_scan_top<int64_t>, dim3(1), dim3(SCAN_TOP_THREADS), 0, s, blk_texels, (int64_t *)nullptr,
-                           L.nbT, counts_dev + 2, (int64_t *)nullptr);
+        scan_top(blk_texels, nullptr, L.nbT, counts_dev + 2, nullptr, s);
         LNERF_CHECK_LAUNCH("uv_raster(scan texels)");
     }
     if ((stages & LNERF_UV_EMIT) && max_texels > 0) {
-        hipLaunchKernelGGL(k_uv_emit, dim3((unsigned)L.nbT), dim3(UV_THREADS), 0, s, m, texel_face, blk_texels,
-                           texel_idx, pos, max_texels);
+        LNERF_LAUNCH(k_uv_emit, n_texels, UV_THREADS, s, m, texel_face, blk_texels, texel_idx, pos, max_texels);
         LNERF_CHECK_LAUNCH("uv_raster(emit)");
     }
     return LNERF_OK;
@@ -253,17 +248,15 @@ int lnerf_uv_dilate(float *texture, uint8_t *mask, int C, int R, int passes, flo
     float *a = texture, *b = tmp_texture;
     uint8_t *ma = mask, *mb = tmp_mask;
     for (int r = 0; r < passes; ++r) {
-        hipLaunchKernelGGL(k_uv_dilate, dim3((unsigned)div_up(n, UV_THREADS)), dim3(UV_THREADS), 0, s, a, ma, b, mb, C, R);
+        LNERF_LAUNCH(k_uv_dilate, n, UV_THREADS, s, a, ma, b, mb, C, R);
         LNERF_CHECK_LAUNCH("uv_dilate");
         float *t = a; a = b; b = t;
         uint8_t *mt = ma; ma = mb; mb = mt;
     }
     if (a != texture) {
-        if (hipMemcpyAsync(texture, a, (size_t)n * C * 4, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-            hipMemcpyAsync(mask, ma, (size_t)n, hipMemcpyDeviceToDevice, s) != hipSuccess) {
-            set_error("uv_dilate: copy-back failed");
+        if (!hip_ok(hipMemcpyAsync(texture, a, (size_t)n * C * 4, hipMemcpyDeviceToDevice, s), "uv_dilate: copy-back") ||
+            !hip_ok(hipMemcpyAsync(mask, ma, (size_t)n, hipMemcpyDeviceToDevice, s), "uv_dilate: copy-back"))
             return LNERF_ERR_HIP;
-        }
     }
     return LNERF_OK;
 }

@@ -27,6 +27,7 @@ MC_CLOSE_BOUNDARY, MC_COUNT_ONLY, MC_REUSE_COUNT = 1, 2, 4   # LNERF_MC_* flags 
 UV_ITEMS, UV_COVER, UV_EMIT = 1, 2, 4                         # LNERF_UV_* stages of lnerf_uv_raster
 UV_MAX_RES = 8192                                             # LNERF_UV_MAX_RES
 DECIMATE_DEFAULT_ROUNDS = 128                                 # LNERF_DECIMATE_DEFAULT_ROUNDS
+DECIMATE_MAX_FACES = 1 << 28                                  # LNERF_DECIMATE_MAX_FACES
 ATLAS_MAX_ROUNDS = 256                                        # LNERF_ATLAS_MAX_ROUNDS
 ATLAS_MAX_FACES = 1 << 28                                     # LNERF_ATLAS_MAX_FACES
 MESH_MAX_ROUNDS = 256                                         # LNERF_MESH_MAX_ROUNDS

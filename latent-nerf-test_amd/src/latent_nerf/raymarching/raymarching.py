@@ -663,6 +663,37 @@ def _face_index(t, op, name, dev):
     return t.to(device=dev, dtype=torch.int32).contiguous()
 
 
+def _mesh_inputs(verts, faces, op, max_faces, max_verts=None, order="%(V)d vertices / %(F)d faces"):
+    """(verts contiguous f32 on the GPU, faces int32 [F,3] beside it, V, F) for the mesh ops; F <= max_faces and
+    V <= max_verts (3 max_faces unless given), or ValueError with the counts in the op's `order`."""
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError("%s: verts must be [V,3]" % op)
+    faces = _face_index(faces, op, "faces", verts.device)
+    verts = verts.contiguous()
+    _chk(verts, "verts")
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    if F > max_faces or V > (3 * max_faces if max_verts is None else max_verts):
+        raise ValueError("%s: %s out of range" % (op, order % dict(V=V, F=F)))
+    return verts, faces, V, F
+
+
+def _scratch(nbytes, dev):
+    """`nbytes` of device scratch (never an empty tensor: its pointer would be NULL)."""
+    return torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+
+
+def _settle_labels(entry, args, changed, max_rounds, op):
+    """Label rounds (`entry`(*args, changed, stream)) until one changes nothing -> the number of rounds run."""
+    rounds = 0
+    while True:
+        if rounds >= max_rounds:
+            raise RuntimeError("%s: the labels have not settled after %d rounds" % (op, rounds))
+        _b.call(entry, *args, _p(changed), _stream())
+        rounds += 1
+        if int(changed[0]) == 0:
+            return rounds
+
+
 def decimate_mesh(verts, faces, target_faces, max_error=float("inf"), max_rounds=_b.DECIMATE_DEFAULT_ROUNDS, stats=None):
     """Quadric-error decimation on the GPU (lnerf_decimate, include/lnerf_hip.h): rounds of independent edge collapses until
     at most `target_faces` faces are left -- target_faces or one fewer, unless a round finds no valid collapse, max_rounds
@@ -670,22 +701,15 @@ def decimate_mesh(verts, faces, target_faces, max_error=float("inf"), max_rounds
     verts [V,3] f32, faces [F,3] (into verts), on the GPU -> verts [V',3] f32, faces [F',3] int32, normals [V',3] f32 on
     the device; the vertices still referenced and the faces left keep their order.  `stats` (a dict) receives rounds
     and collapses.  Synchronous: one host read of the counts per round."""
-    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3:
-        raise ValueError("decimate_mesh: verts must be [V,3]")
-    faces = _face_index(faces, "decimate_mesh", "faces", verts.device)
     target_faces, max_rounds, max_error = int(target_faces), int(max_rounds), float(max_error)
     if target_faces < 0 or max_rounds < 0:
         raise ValueError("decimate_mesh: target_faces (%d) and max_rounds (%d) must be >= 0" % (target_faces, max_rounds))
     if not max_error >= 0:
         raise ValueError("decimate_mesh: max_error must be >= 0 (inf: no ceiling)")
-    verts = verts.contiguous()
-    _chk(verts, "verts")
+    verts, faces, V, F = _mesh_inputs(verts, faces, "decimate_mesh", _b.DECIMATE_MAX_FACES)
     dev = verts.device
-    V, F = int(verts.shape[0]), int(faces.shape[0])
     nbytes = _b.get_lib().lnerf_decimate_scratch_bytes(V, F)
-    if nbytes == 0:
-        raise ValueError("decimate_mesh: %d vertices / %d faces out of range" % (V, F))
-    scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    scratch = _scratch(nbytes, dev)
     counts = torch.zeros(4, device=dev, dtype=torch.int64)
     out_v = torch.empty(V, 3, device=dev, dtype=torch.float32)
     out_f = torch.empty(F, 3, device=dev, dtype=torch.int32)
@@ -699,19 +723,6 @@ def decimate_mesh(verts, faces, target_faces, max_error=float("inf"), max_rounds
 
 
 # ------------------------------------------------------------------------------ mesh cleaning
-def _mesh_inputs(verts, faces, op):
-    """(verts contiguous f32 on the GPU, faces int32 [F,3] beside it, V, F) for the mesh-cleaning ops."""
-    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3:
-        raise ValueError("%s: verts must be [V,3]" % op)
-    verts = verts.contiguous()
-    _chk(verts, "verts")
-    faces = _face_index(faces, op, "faces", verts.device)
-    V, F = int(verts.shape[0]), int(faces.shape[0])
-    if F > _b.MESH_MAX_FACES or V > 3 * _b.MESH_MAX_FACES:
-        raise ValueError("%s: %d vertices / %d faces out of range" % (op, V, F))
-    return verts, faces, V, F
-
-
 def mesh_components(verts, faces, stats=None):
     """Connected components of a mesh on the GPU (lnerf_mesh_components_*, include/lnerf_hip.h "mesh cleaning"): two
     vertices are connected iff a face holds both.  verts [V,3] f32, faces [F,3] (into verts), on the GPU ->
@@ -719,7 +730,7 @@ def mesh_components(verts, faces, stats=None):
     z_lo, x_hi, y_hi, z_hi), components = C, referenced (vertices in a face), rounds); components are numbered by their
     smallest vertex.  A face indexing outside verts or a non-finite coordinate raises ValueError.  `stats` (a dict)
     receives the scalars.  Deterministic bit for bit.  Synchronous: one host read per label round."""
-    verts, faces, V, F = _mesh_inputs(verts, faces, "mesh_components")
+    verts, faces, V, F = _mesh_inputs(verts, faces, "mesh_components", _b.MESH_MAX_FACES)
     if V > 0 and not bool(torch.isfinite(verts).all()):
         raise ValueError("mesh_components: verts holds non-finite coordinates")
     dev = verts.device
@@ -730,17 +741,10 @@ def mesh_components(verts, faces, stats=None):
     bad = int(counts[0])
     if bad:
         raise ValueError("mesh_components: %d faces index outside verts (%d)" % (bad, V))
-    changed = torch.zeros(1, **i32)
-    rounds = 0
-    while True:
-        if rounds >= _b.MESH_MAX_ROUNDS:
-            raise RuntimeError("mesh_components: the labels have not settled after %d rounds" % rounds)
-        _b.call("lnerf_mesh_components_round", _p(faces), V, F, _p(label), _p(changed), _stream())
-        rounds += 1
-        if int(changed[0]) == 0:
-            break
+    rounds = _settle_labels("lnerf_mesh_components_round", (_p(faces), V, F, _p(label)), torch.zeros(1, **i32),
+                            _b.MESH_MAX_ROUNDS, "mesh_components")
     nbytes = _b.get_lib().lnerf_mesh_components_scratch_bytes(V, F)
-    scratch = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    scratch = _scratch(nbytes, dev)
     cap = min(V, F)
     vert_comp, face_comp, comp_faces = torch.empty(V, **i32), torch.empty(F, **i32), torch.empty(cap, **i32)
     comp_box = torch.empty(cap, 6, device=dev, dtype=torch.float32)
@@ -757,13 +761,13 @@ def mesh_filter(verts, faces, face_keep):
     """The faces with a non-zero flag and the vertices they reference, both in their old order (lnerf_mesh_filter).
     verts [V,3] f32, faces [F,3], face_keep [F] (bool / uint8), on the GPU -> verts [V',3], faces [F',3] int32
     (re-indexed), vert_src [V'] long with verts_out = verts[vert_src]: gather any per-vertex attribute through it."""
-    verts, faces, V, F = _mesh_inputs(verts, faces, "mesh_filter")
+    verts, faces, V, F = _mesh_inputs(verts, faces, "mesh_filter", _b.MESH_MAX_FACES)
     if not isinstance(face_keep, torch.Tensor) or face_keep.shape != (F,) or face_keep.dtype not in (torch.bool, torch.uint8):
         raise ValueError("mesh_filter: face_keep must be a bool / uint8 tensor [%d]" % F)
     dev = verts.device
     keep = face_keep.to(device=dev, dtype=torch.uint8).contiguous()
     nbytes = _b.get_lib().lnerf_mesh_filter_scratch_bytes(V, F)
-    scratch = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    scratch = _scratch(nbytes, dev)
     counts = torch.zeros(2, device=dev, dtype=torch.int64)
     faces_out = torch.empty(F, 3, device=dev, dtype=torch.int32)
     vert_src = torch.empty(V, device=dev, dtype=torch.int32)
@@ -810,7 +814,7 @@ def clean_mesh(verts, faces, min_faces=0, min_diameter=0.0, keep_largest=0, stat
         raise ValueError("clean_mesh: min_faces (%d) and keep_largest (%d) must be >= 0" % (min_faces, keep_largest))
     if not 0.0 <= min_diameter <= 1.0:
         raise ValueError("clean_mesh: min_diameter %r outside [0, 1]" % min_diameter)
-    verts, faces, V, F = _mesh_inputs(verts, faces, "clean_mesh")
+    verts, faces, V, F = _mesh_inputs(verts, faces, "clean_mesh", _b.MESH_MAX_FACES)
     comp = mesh_components(verts, faces)
     ok = component_keep(comp["comp_faces"].cpu().numpy(), comp["comp_box"].cpu().numpy(), min_faces, min_diameter,
                         keep_largest)
@@ -836,10 +840,10 @@ def smooth_mesh(verts, faces, iterations=10, lam=_b.SMOOTH_LAMBDA, mu=_b.SMOOTH_
         raise ValueError("smooth_mesh: lam %r outside (0, 1]" % lam)
     if not -1.5 <= mu <= 0.0:
         raise ValueError("smooth_mesh: mu %r outside [-1.5, 0]" % mu)
-    verts, faces, V, F = _mesh_inputs(verts, faces, "smooth_mesh")
+    verts, faces, V, F = _mesh_inputs(verts, faces, "smooth_mesh", _b.MESH_MAX_FACES)
     dev = verts.device
     nbytes = _b.get_lib().lnerf_mesh_smooth_scratch_bytes(V, F)
-    scratch = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    scratch = _scratch(nbytes, dev)
     out_v = torch.empty(V, 3, device=dev, dtype=torch.float32)
     out_n = torch.empty(V, 3, device=dev, dtype=torch.float32)
     try:
@@ -888,15 +892,9 @@ def chart_atlas(verts, faces, resolution, pad=2, stats=None):
         raise ValueError("chart_atlas: resolution %d outside [1, %d]" % (R, _b.UV_MAX_RES))
     if pad < 0 or 2 * pad + 2 > R:
         raise ValueError("chart_atlas: pad %d needs 2 pad + 2 <= resolution (%d)" % (pad, R))
-    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3:
-        raise ValueError("chart_atlas: verts must be [V,3]")
-    verts = verts.contiguous()
-    _chk(verts, "verts")
+    verts, faces, V, F = _mesh_inputs(verts, faces, "chart_atlas", _b.ATLAS_MAX_FACES, max_verts=2 ** 31 - 1,
+                                      order="%(F)d faces / %(V)d vertices")
     dev = verts.device
-    faces = _face_index(faces, "chart_atlas", "faces", dev)
-    V, F = int(verts.shape[0]), int(faces.shape[0])
-    if F > _b.ATLAS_MAX_FACES or V >= 2 ** 31:
-        raise ValueError("chart_atlas: %d faces / %d vertices out of range" % (F, V))
     lib = _b.get_lib()
     i32 = dict(device=dev, dtype=torch.int32)
     counts = torch.zeros(1, device=dev, dtype=torch.int64)
@@ -907,17 +905,10 @@ def chart_atlas(verts, faces, resolution, pad=2, stats=None):
         raise ValueError("chart_atlas: %d faces index outside verts (%d)" % (bad, V))
     # charts: rounds of hook + pointer jumping until a round changes nothing
     twin = _half_edge_twins(faces, V)
-    changed = torch.zeros(1, **i32)
-    rounds = 0
-    while True:
-        if rounds >= _b.ATLAS_MAX_ROUNDS:
-            raise RuntimeError("chart_atlas: the labels have not settled after %d rounds" % rounds)
-        _b.call("lnerf_atlas_round", _p(bucket), _p(twin), F, _p(label), _p(changed), _stream())
-        rounds += 1
-        if int(changed[0]) == 0:
-            break
+    rounds = _settle_labels("lnerf_atlas_round", (_p(bucket), _p(twin), F, _p(label)), torch.zeros(1, **i32),
+                            _b.ATLAS_MAX_ROUNDS, "chart_atlas")
     nbytes = lib.lnerf_atlas_compact_scratch_bytes(F)
-    scratch = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    scratch = _scratch(nbytes, dev)
     face_chart, chart_axis = torch.empty(F, **i32), torch.empty(F, **i32)
     _b.call("lnerf_atlas_compact", _p(bucket), _p(label), F, _p(scratch), nbytes, _p(face_chart), _p(chart_axis),
             _p(counts), _stream())
@@ -927,7 +918,7 @@ def chart_atlas(verts, faces, resolution, pad=2, stats=None):
     def boxes(fc, n, sub=None):
         f, b = (faces, bucket) if sub is None else (faces[sub].contiguous(), bucket[sub].contiguous())
         nb = lib.lnerf_atlas_boxes_scratch_bytes(n)
-        sc = torch.empty(max(nb, 16), device=dev, dtype=torch.uint8)
+        sc = _scratch(nb, dev)
         out = torch.empty(n, 4, device=dev, dtype=torch.float32)
         _b.call("lnerf_atlas_boxes", _p(verts), V, _p(f), _p(b), _p(fc), int(f.shape[0]), n, _p(sc), nb, _p(out), _stream())
         return out
@@ -946,7 +937,7 @@ def chart_atlas(verts, faces, resolution, pad=2, stats=None):
     def folded(vt, ft):
         """evicted [F] bool: faces that strictly cover a texel centre a face with a larger index covers too."""
         nb = lib.lnerf_atlas_fold_scratch_bytes(F, R)
-        sc = torch.empty(max(nb, 16), device=dev, dtype=torch.uint8)
+        sc = _scratch(nb, dev)
         owner = torch.empty(R * R, **i32)
         ev = torch.zeros(F, **i32)
         args = (_p(vt), int(vt.shape[0]), _p(ft), F, R)

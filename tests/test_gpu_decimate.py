@@ -141,6 +141,11 @@ def test_out_of_range_indices_are_refused_without_a_fault(dev):
         assert rc == -1 and b"1 faces index outside" in lib.lnerf_last_error()
         with pytest.raises(B.LnerfError, match="outside"):
             decimate_mesh(tv, tf, 0)
+    # bad faces in two different waves (faces 3 and 129 of 130) are counted together
+    f130 = np.resize(f, (130, 3)).copy()
+    f130[3, 1], f130[129, 0] = V, -1
+    with pytest.raises(B.LnerfError, match="decimate: 2 faces index outside"):
+        decimate_mesh(tv, torch.from_numpy(f130).to(dev), 0)
     with pytest.raises(ValueError):
         decimate_mesh(tv, torch.from_numpy(f).to(dev), -1)
     with pytest.raises(ValueError, match="no CPU path"):

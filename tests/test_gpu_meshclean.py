@@ -175,7 +175,11 @@ def test_clean_mesh_matches_restatement(dev, case, args):
         assert len(gf) == 3596
 
 
-@pytest.mark.parametrize("case", ["floaters", "odd", "empty", "257x256", "1025x255", "255x1025", "1024x1024"])
+# V x F around the 4096-entry block of the flat scan (scan.h) that the incidence lists of lnerf_mesh_smooth go through
+FLAT_SCAN_EDGES = ["4095x4097", "4096x4096", "4097x4095"]
+
+
+@pytest.mark.parametrize("case", ["floaters", "odd", "empty", "257x256", "1025x255", "255x1025", "1024x1024"] + FLAT_SCAN_EDGES)
 def test_filter_matches_restatement_on_any_flag(dev, case):
     from src.latent_nerf.raymarching import mesh_filter
     v, f = _mesh(case)
@@ -205,6 +209,7 @@ def _smooth(dev, v, f, *args):
 
 SMOOTH_CASES = [("staircase", 1), ("staircase", 3), ("staircase", 0), ("staircase", 3, 0.5, 0.0), ("staircase", 2, 1.0, -1.5),
                 ("open", 2), ("noise", 2), ("odd", 3), ("empty", 2), ("257x256", 2), ("1025x255", 1)]
+SMOOTH_CASES += [(name, 2) for name in FLAT_SCAN_EDGES]
 
 
 @pytest.mark.parametrize("case", SMOOTH_CASES, ids=lambda c: "-".join(str(x) for x in c))
@@ -218,6 +223,25 @@ def test_smooth_mesh_matches_restatement_bit_for_bit(dev, case):
         assert np.array_equal(_bits(gv), _bits(v))
     elif case[0] != "empty":
         assert not np.array_equal(_bits(gv), _bits(v))
+
+
+def test_smooth_and_decimate_share_their_normals(dev):
+    """smooth_mesh documents its normals "as decimate_mesh's": with nothing to smooth and nothing to collapse the two
+    entry points return the same bits, the restatement's."""
+    from src.latent_nerf.raymarching import decimate_mesh
+    v, f = _mesh("floaters")
+    # every vertex referenced and no face repeating an index: decimate_mesh then returns the mesh as it is
+    assert np.array_equal(np.unique(f), np.arange(len(v)))
+    assert not ((f[:, 0] == f[:, 1]) | (f[:, 1] == f[:, 2]) | (f[:, 2] == f[:, 0])).any()
+    sv, sn = _smooth(dev, v, f, 0)
+    st = {}
+    dv, df, dn = decimate_mesh(*_t(dev, v, f), target_faces=len(f), stats=st)
+    torch.cuda.synchronize()
+    assert st["rounds"] == 0 and np.array_equal(df.cpu().numpy(), f)
+    assert np.array_equal(_bits(dv.cpu().numpy()), _bits(v)) and np.array_equal(_bits(sv), _bits(v))
+    rn = M.smooth(v, f, 0)[1]
+    assert np.array_equal(_bits(sn), _bits(rn)) and np.array_equal(_bits(dn.cpu().numpy()), _bits(rn))
+    assert np.array_equal(_bits(sn), _bits(dn.cpu().numpy()))
 
 
 def test_taubin_smooths_the_staircase_without_shrinking_it(dev):

@@ -16,7 +16,9 @@ undecimated and on each decimated mesh.
 --atlas charts [--atlas-resolution 1024]: also time raymarching.chart_atlas on each marching-cubes mesh and on each
 decimated one (the whole call: label rounds with one host read each, the host-side packing, the fold check), with
 its chart, round, shrink (k) and eviction counts and the share of the texture's texels that a face covers.  Only
-sizes >= 256 are run, to keep the leg short."""
+sizes >= 256 are run, to keep the leg short.
+--clean: also time raymarching.clean_mesh (the upstream exporter's 8 faces / 0.05 of the diagonal: label rounds with one
+host read each, the host-side keep rule, the filter) and smooth_mesh(iterations=10) on each marching-cubes mesh."""
 import argparse
 import json
 import os
@@ -73,8 +75,9 @@ def main():
     ap.add_argument("--target-faces", default="", help="comma-separated face targets of a decimation leg (empty: none)")
     ap.add_argument("--atlas", default="", choices=["", "charts"], help="charts: also time the chart atlas of every mesh")
     ap.add_argument("--atlas-resolution", type=int, default=1024)
+    ap.add_argument("--clean", action="store_true", help="also time clean_mesh and 10 smoothing iterations of every mesh")
     args = ap.parse_args()
-    from src.latent_nerf.raymarching import chart_atlas, decimate_mesh, marching_cubes, uv_raster
+    from src.latent_nerf.raymarching import chart_atlas, clean_mesh, decimate_mesh, marching_cubes, smooth_mesh, uv_raster
     assert torch.cuda.is_available(), "bench_mesh_export needs the GPU"
     dev = torch.device("cuda:0")
     net, cfg = field(dev, args.precision)
@@ -93,6 +96,13 @@ def main():
                "mc_bytes": mc_bytes, "mc_GBps": round(mc_bytes / (t_mc * 1e-3) / 1e9, 1),
                "query_Mpts_per_s": round(R ** 3 / (t_q * 1e-3) / 1e6, 1)}
         del vol
+        if args.clean:
+            st = {}
+            t_c, (_, cf, _) = timed(lambda: clean_mesh(v, f, 8, 0.05, stats=st), args.reps)
+            t_s, _ = timed(lambda: smooth_mesh(v, f, 10), args.reps)
+            row["clean"] = {"ms": round(t_c, 3), "components": st["components"], "kept": st["kept"],
+                            "rounds": st["rounds"], "F_out": int(cf.shape[0])}
+            row["smooth"] = {"iterations": 10, "ms": round(t_s, 3)}
         meshes = [(F, v, f)]
         for N in targets:
             if N >= F:

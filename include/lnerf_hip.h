@@ -773,6 +773,35 @@ int lnerf_uv_raster(const float *verts, int n_verts, const int32_t *faces, const
 int lnerf_uv_dilate(float *texture, uint8_t *mask, int C, int R, int passes, float *tmp_texture, uint8_t *tmp_mask,
                     lnerf_stream_t stream);
 
+/* ---- multi-view projection: colours surface points from K images of the surface, with a visibility test and an angle
+ * weight (csrc/uvproject.hip; NeRFRenderer.bake_views, Latent-Paint's view bake).  Additive to ABI 7.
+ *   pos, nrm [P,3] f32: a surface point x and its unit outward normal n (any points: the kernel knows no atlas);
+ *   cams_dev: device [K,14], the record of lnerf_raster_prepare_batch (rotation rows 9, eye 3, fx, fy; camera z is
+ *     negative in front);  zbuf [K,H,W]: camera z of the visible surface at each pixel centre (negative); a value >= 0
+ *     marks a pixel that must not be used (background, or eroded by the host);  images [K,C,H,W], 1 <= C <= 4.
+ *   1 <= K <= 65535, 2 <= H, W <= 32767, 0 < cos_min <= 1, power >= 0, slack >= 0, 0 <= P < 2^31.
+ * Per point and view k, all in f32, the views in ascending k and accumulated in that order (deterministic, no atomics):
+ *   1. d = eye - x, c = (n . d) / |d| (products summed left to right); rejected unless c >= cos_min.
+ *   2. p = rot (x - eye), each row as fmaf(r0, x, fmaf(r1, y, r2 * z)) like lnerf_raster_prepare_batch; rejected unless
+ *      p.z < 0.  X = p.x * fx / (-p.z), Y = p.y * fy / (-p.z).
+ *   3. u = ((X + 1) W - 1) / 2, v = ((1 - Y) H - 1) / 2: pixel centres at integers (column u, row v), the rasteriser's
+ *      convention.  j0 = floor(u), i0 = floor(v), tu = u - j0, tv = v - i0; rejected unless 0 <= j0, j0 + 1 <= W - 1,
+ *      0 <= i0, i0 + 1 <= H - 1.
+ *   4. rejected unless zbuf < 0 at all four taps (i0 | i0 + 1, j0 | j0 + 1): silhouette pixels mix in background.
+ *   5. depth test against the NEAREST tap (tu >= 0.5 -> j0 + 1, tv >= 0.5 -> i0 + 1): accepted iff
+ *      p.z >= zbuf[nearest] - bias,
+ *      bias = slack * (-p.z) * 2 / min(fx W, fy H) * sqrt(max(1 - c^2, 0)) / c + 1e-4 * (-p.z)    (left to right):
+ *      the depth change across `slack` pixel footprints of a surface tilted by acos c, plus a floor for head-on views.
+ *   6. w = powf(c, power); colour, per channel, the bilinear sample a + tv (b - a) with a = I[i0,j0] + tu (I[i0,j0+1] -
+ *      I[i0,j0]) and b the same on row i0 + 1; weight += w, count += 1, acc += w * (colour - first), `first` being the
+ *      colour of the point's first accepted view.
+ * Outputs: out [P,C] = first + acc / weight where weight > 0, else 0 -- the weighted mean sum(w colour) / sum(w),
+ *   evaluated around the first accepted colour: differences of equal taps and of equal views are exact zeros, so a
+ *   colour that all accepted views agree on comes back bit for bit; weight [P]; count [P] int32, the views accepted. */
+int lnerf_uv_project_views(const float *pos, const float *nrm, int64_t P, const float *cams_dev, int K, int H, int W,
+                           const float *zbuf, const float *images, int C, float cos_min, float power, float slack,
+                           float *out, float *weight, int32_t *count, lnerf_stream_t stream);
+
 /* ---- mesh decimation: rounds of independent quadric-error (Garland-Heckbert) edge collapses, NeRFRenderer.export_mesh's
  * `target_faces` (csrc/decimate.hip).  Additive to ABI 7.  Fully deterministic; the C call is synchronous (one host
  * read of the counts before round 1, one per round).

@@ -1,0 +1,137 @@
+// Multi-view projection of images onto surface points: the kernel behind NeRFRenderer.bake_views and Latent-Paint's
+// view bake (src/view_bake.py).  Contract and the rule per (point, view): include/lnerf_hip.h, lnerf_uv_project_views;
+// float64 restatement: tests/test_gpu_view_bake.py.
+//
+// k_uv_project: one lane per point, 256 per workgroup.  The camera records are staged into LDS once per workgroup
+// (PROJ_CAM_TILE at a time, so any K fits), and every lane of a wave reads the same record: a broadcast.  A lane walks
+// the views in ascending k and keeps its sums in registers, so the result does not depend on the launch shape and
+// needs no atomics.  The z-buffer and image taps are gathers; neighbouring texels of a chart are neighbouring surface
+// points, so a wave's taps of one view fall into a few cache lines of that view's planes.
+#include "common.h"
+
+namespace lnerf {
+
+constexpr int PROJ_THREADS = 256;
+constexpr int PROJ_CAM_TILE = 64;   // camera records per LDS tile (64 * 14 floats = 3.5 KiB)
+constexpr int PROJ_MAX_C = 4;
+
+struct ProjArgs {
+    const float *pos, *nrm, *cams, *zbuf, *images;
+    int64_t P;
+    int K, H, W, C;
+    float cos_min, power, slack;
+    float *out, *weight;
+    int32_t *count;
+};
+
+__global__ void __launch_bounds__(PROJ_THREADS) k_uv_project(ProjArgs a) {
+    __shared__ float s_cam[PROJ_CAM_TILE * 14];
+    const int64_t p = (int64_t)blockIdx.x * PROJ_THREADS + threadIdx.x;
+    const bool live = p < a.P;
+    float x[3] = {0.f, 0.f, 0.f}, n[3] = {0.f, 0.f, 0.f};
+    if (live) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            x[d] = a.pos[p * 3 + d];
+            n[d] = a.nrm[p * 3 + d];
+        }
+    }
+    const float Wf = (float)a.W, Hf = (float)a.H;
+    const int64_t plane = (int64_t)a.H * a.W;
+    float acc[PROJ_MAX_C] = {0.f, 0.f, 0.f, 0.f}, first[PROJ_MAX_C] = {0.f, 0.f, 0.f, 0.f};
+    float wsum = 0.f;
+    int cnt = 0;
+    for (int k0 = 0; k0 < a.K; k0 += PROJ_CAM_TILE) {
+        const int nk = min(PROJ_CAM_TILE, a.K - k0);
+        __syncthreads();
+        for (int t = threadIdx.x; t < nk * 14; t += PROJ_THREADS) s_cam[t] = a.cams[(int64_t)k0 * 14 + t];
+        __syncthreads();
+        if (!live) continue;
+        for (int kk = 0; kk < nk; ++kk) {
+            const float *cam = s_cam + kk * 14;
+            // 1. the angle between the normal and the direction to the eye
+            const float dx = cam[9] - x[0], dy = cam[10] - x[1], dz = cam[11] - x[2];
+            const float len = sqrtf(dx * dx + dy * dy + dz * dz);
+            const float c = (n[0] * dx + n[1] * dy + n[2] * dz) / len;
+            if (!(c >= a.cos_min)) continue;
+            // 2. camera space, with the rasteriser's own arithmetic (raster.hip prepare_corner)
+            const float rx = x[0] - cam[9], ry = x[1] - cam[10], rz = x[2] - cam[11];
+            const float px = fmaf(cam[0], rx, fmaf(cam[1], ry, cam[2] * rz));
+            const float py = fmaf(cam[3], rx, fmaf(cam[4], ry, cam[5] * rz));
+            const float pz = fmaf(cam[6], rx, fmaf(cam[7], ry, cam[8] * rz));
+            if (!(pz < 0.f)) continue;
+            const float fx = cam[12], fy = cam[13];
+            const float X = px * fx / (-pz), Y = py * fy / (-pz);
+            // 3. pixel coordinates, pixel centres at integers; all four taps inside the image
+            const float u = ((X + 1.0f) * Wf - 1.0f) * 0.5f, v = ((1.0f - Y) * Hf - 1.0f) * 0.5f;
+            if (!(u >= 0.f && u < Wf - 1.0f && v >= 0.f && v < Hf - 1.0f)) continue;
+            const float uf = floorf(u), vf = floorf(v);
+            const int j0 = (int)uf, i0 = (int)vf;
+            const float tu = u - uf, tv = v - vf;
+            // 4. no tap on the background or on an eroded pixel
+            const int k = k0 + kk;
+            const float *zb = a.zbuf + (int64_t)k * plane + (int64_t)i0 * a.W + j0;
+            const float z00 = zb[0], z01 = zb[1], z10 = zb[a.W], z11 = zb[a.W + 1];
+            if (!(z00 < 0.f && z01 < 0.f && z10 < 0.f && z11 < 0.f)) continue;
+            // 5. depth test against the nearest pixel centre
+            const float zt = tv >= 0.5f ? (tu >= 0.5f ? z11 : z10) : (tu >= 0.5f ? z01 : z00);
+            const float depth = -pz;
+            const float bias = a.slack * depth * 2.0f / fminf(fx * Wf, fy * Hf) * sqrtf(fmaxf(1.0f - c * c, 0.f)) / c +
+                               1e-4f * depth;
+            if (!(pz >= zt - bias)) continue;
+            // 6. accumulate the weighted mean around the first accepted colour: the differences are exact zeros where
+            // the taps or the views agree, so a colour all views share comes back as it is
+            const float w = powf(c, a.power);
+            const float *im = a.images + (int64_t)k * a.C * plane + (int64_t)i0 * a.W + j0;
+#pragma unroll
+            for (int ch = 0; ch < PROJ_MAX_C; ++ch) {
+                if (ch < a.C) {
+                    const float *t = im + ch * plane;
+                    const float top = t[0] + tu * (t[1] - t[0]), bot = t[a.W] + tu * (t[a.W + 1] - t[a.W]);
+                    const float col = top + tv * (bot - top);
+                    if (cnt == 0) first[ch] = col;
+                    acc[ch] += w * (col - first[ch]);
+                }
+            }
+            wsum += w;
+            ++cnt;
+        }
+    }
+    if (!live) return;
+#pragma unroll
+    for (int ch = 0; ch < PROJ_MAX_C; ++ch)
+        if (ch < a.C) a.out[p * a.C + ch] = wsum > 0.f ? first[ch] + acc[ch] / wsum : 0.f;
+    a.weight[p] = wsum;
+    a.count[p] = cnt;
+}
+
+}  // namespace lnerf
+
+using namespace lnerf;
+
+extern "C" {
+
+int lnerf_uv_project_views(const float *pos, const float *nrm, int64_t P, const float *cams_dev, int K, int H, int W,
+                           const float *zbuf, const float *images, int C, float cos_min, float power, float slack,
+                           float *out, float *weight, int32_t *count, lnerf_stream_t stream) {
+    LNERF_REQUIRE(P >= 0 && P < ((int64_t)1 << 31), "uv_project_views: P = %lld outside [0, 2^31)", (long long)P);
+    LNERF_REQUIRE(K >= 1 && K <= 65535, "uv_project_views: K must be in [1, 65535]");
+    LNERF_REQUIRE(H >= 2 && W >= 2 && H <= 32767 && W <= 32767, "uv_project_views: H and W must be in [2, 32767]");
+    LNERF_REQUIRE(C >= 1 && C <= PROJ_MAX_C, "uv_project_views: C must be in [1, %d]", PROJ_MAX_C);
+    LNERF_REQUIRE(cos_min > 0.f && cos_min <= 1.f, "uv_project_views: cos_min must be in (0, 1]");
+    LNERF_REQUIRE(power >= 0.f && power < 3.0e38f && slack >= 0.f && slack < 3.0e38f,
+                  "uv_project_views: power and slack must be finite and >= 0");
+    LNERF_REQUIRE(cams_dev && zbuf && images, "uv_project_views: null pointer");
+    if (P == 0) return LNERF_OK;
+    LNERF_REQUIRE(pos && nrm && out && weight && count, "uv_project_views: null pointer");
+    ProjArgs a;
+    a.pos = pos; a.nrm = nrm; a.cams = cams_dev; a.zbuf = zbuf; a.images = images;
+    a.P = P; a.K = K; a.H = H; a.W = W; a.C = C;
+    a.cos_min = cos_min; a.power = power; a.slack = slack;
+    a.out = out; a.weight = weight; a.count = count;
+    LNERF_LAUNCH(k_uv_project, P, PROJ_THREADS, as_stream(stream), a);
+    LNERF_CHECK_LAUNCH("uv_project_views");
+    return LNERF_OK;
+}
+
+}  // extern "C"

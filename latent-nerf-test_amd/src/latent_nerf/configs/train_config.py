@@ -144,6 +144,12 @@ class LogConfig:
     mesh_keep_largest: int = 0
     # with save_mesh: > 0 runs this many Taubin smoothing iterations (raymarching.smooth_mesh) before the decimation
     mesh_smooth_iterations: int = 0
+    # with save_mesh and mesh_texture_resolution: > 0 bakes albedo.png from this many RENDERED views (a Fibonacci lattice
+    # of directions at the evaluation camera), decoded as images -- through the guidance model's decoder with
+    # log.decode_eval -- and projected into the atlas with a visibility test and an angle weight; the per-point preview
+    # is kept as albedo_preview.png.  mesh_bake_view_size: side of those renders (0 = render.eval_h x render.eval_w)
+    mesh_bake_views: int = 0
+    mesh_bake_view_size: int = 0
     # evaluation also writes a normal-shaded render (*_normals.png / *_normals video) beside every *_rgb one
     eval_normals: bool = False
     max_keep_ckpts: int = 2
@@ -205,6 +211,12 @@ class TrainConfig:
         for n in ("mesh_min_component_faces", "mesh_min_component_diameter", "mesh_keep_largest", "mesh_smooth_iterations"):
             if not getattr(self.log, n) >= 0:
                 raise ValueError("log.%s must be >= 0, not %r" % (n, getattr(self.log, n)))
+        for n in ("mesh_bake_views", "mesh_bake_view_size"):
+            if not getattr(self.log, n) >= 0:
+                raise ValueError("log.%s must be >= 0, not %r" % (n, getattr(self.log, n)))
+        if self.log.mesh_bake_views > 0 and not self.log.mesh_texture_resolution > 0:
+            raise ValueError("log.mesh_bake_views = %r needs log.mesh_texture_resolution > 0: the views are baked into "
+                             "the exported texture" % (self.log.mesh_bake_views,))
         if self.log.mesh_min_component_diameter > 1:
             raise ValueError("log.mesh_min_component_diameter is a fraction of the mesh's diagonal in [0, 1], not %r"
                              % self.log.mesh_min_component_diameter)

@@ -606,9 +606,53 @@ class NeRFRenderer(nn.Module):
         return {"texture": texture, "mask": mask, "rgb": rgb}
 
     @torch.no_grad()
+    def bake_views(self, verts, faces, vt, ft, images, cams, resolution, gutter=4, fallback=None, erode=0, cos_min=0.2,
+                   power=4.0, slack=2.0):
+        """Project K images of the mesh (images [K,C,H,W] seen by the camera records cams [K,14]) into its UV atlas:
+        texels from lnerf_uv_raster, texel normal = the winding normal of the covering face (marching cubes winds
+        outwards), visibility from view_zbuffer at the images' size, colours from project_views, `fallback` [C,R,R]
+        where no view sees a texel, `gutter` dilation rounds (view_bake.bake_views, shared with Latent-Paint).
+        -> dict(rgb [C,R,R], view_weight [R,R], view_count [R,R] int32, mask [R,R] uint8)."""
+        from ... import view_bake
+        return view_bake.bake_views(verts, faces, vt, ft, images, cams, resolution, gutter=gutter, fallback=fallback,
+                                    erode=erode, cos_min=cos_min, power=power, slack=slack)
+
+    @torch.no_grad()
+    def render_bake_views(self, K, view_size=None):
+        """K evaluation renders for a view bake: the directions of raymarching.bake_view_poses at the evaluation
+        camera (radius_range[1] * 1.2, the mean fovy), rendered as Trainer.eval_render does (evaluation mode,
+        unperturbed, the evaluation background) at `view_size` (an int or (h, w); default eval_h x eval_w).
+        -> (images [K,C,h,w], cams [K,14] rasteriser records of the same cameras)."""
+        from ...view_bake import view_cameras
+        cfg = self.cfg
+        if view_size is None or view_size == 0:
+            h, w = int(cfg.eval_h), int(cfg.eval_w)
+        elif isinstance(view_size, (tuple, list)):
+            h, w = int(view_size[0]), int(view_size[1])
+        else:
+            h = w = int(view_size)
+        if h < 2 or w < 2:
+            raise ValueError("render_bake_views: view_size %r is smaller than 2 x 2" % (view_size,))
+        dev = self.density_grid.device
+        fovy = 0.5 * (cfg.fovy_range[0] + cfg.fovy_range[1])
+        cams, c2w, intr = view_cameras(rm.bake_view_poses(K), cfg.radius_range[1] * 1.2, fovy, h, w, dev)
+        was_training = self.training
+        self.eval()
+        try:
+            views = []
+            for pose in c2w:
+                rays_o, rays_d = rm.get_rays(pose[None].to(dev), intr, h, w)
+                out = self.render(rays_o, rays_d, staged=True, perturb=False, bg_color=None)
+                views.append(out["image"].reshape(h, w, -1).permute(2, 0, 1).float())
+        finally:
+            self.train(was_training)
+        return torch.stack(views).contiguous(), cams
+
+    @torch.no_grad()
     def export_mesh(self, path, resolution=None, S=128, thresh=None, texture_resolution=0, gutter=4, target_faces=0,
                     field_normals=False, atlas="triangle", min_component_faces=0, min_component_diameter=0.0,
-                    keep_largest=0, smooth_iterations=0):
+                    keep_largest=0, smooth_iterations=0, bake_views=0, view_size=None, view_decoder=None,
+                    view_erode=None):
         """Triangle mesh of the density field -> `path`/mesh.obj (the upstream renderer's export_mesh(path, resolution,
         S)): the density on a `resolution`^3 lattice over [-bound, bound]^3 (density_lattice), marching cubes on the GPU
         at iso `thresh` (default min(mean density, density_thresh), as upstream) with the box capped, vertex colours
@@ -634,6 +678,14 @@ class NeRFRenderer(nn.Module):
         smooth_iterations > 0: that many Taubin iterations (raymarching.smooth_mesh) take the lattice's stair steps
         out of the surface; without a decimation the normals are then the smoothed mesh's face sums.
         Order: marching cubes, clean, smooth, decimate, then colours / field normals / atlas / bake on the final mesh.
+        bake_views = K > 0 (needs texture_resolution > 0): albedo.png is baked from K RENDERED views instead of per-point
+        previews -- render_bake_views at `view_size`, `view_decoder` ([K,C,h,w] renders -> [K,3,H',W'] RGB in [0, 1] at
+        any up-scaling that keeps the aspect ratio, e.g. the diffusion model's VAE decoder; None: the linear preview
+        for latents, the identity for RGB renders), then bake_views with the point bake as the fallback for texels no
+        view sees.  `view_erode` pixels are taken off every silhouette (default: 0 at the render size, else the
+        up-scaling factor, about what a decoder smears the background over).  The point bake's image is kept as
+        albedo_preview.png; the result gains view_rgb [3,R,R], view_weight and view_count [R,R]; rgb, texture and
+        latent_texture.pt are what they are without the option.
         Returns dict(verts [V,3], faces [F,3] int32, normals [V,3], colors [V,3], iso, path, faces_before (the
         marching-cubes face count), components and components_kept (None without a cleaning), faces_cleaned (the face
         count after the cleaning)) with device tensors, plus vt, ft, texture, mask, rgb when textured."""
@@ -642,6 +694,12 @@ class NeRFRenderer(nn.Module):
         check_atlas_choice(atlas, "export_mesh: atlas")
         min_component_faces, min_component_diameter = int(min_component_faces), float(min_component_diameter)
         keep_largest, smooth_iterations = int(keep_largest), int(smooth_iterations)
+        bake_views = int(bake_views)
+        if bake_views < 0:
+            raise ValueError("export_mesh: bake_views must be >= 0 (got %d)" % bake_views)
+        if bake_views > 0 and int(texture_resolution) <= 0:
+            raise ValueError("export_mesh: bake_views = %d needs texture_resolution > 0 (the views are baked into the "
+                             "texture)" % bake_views)
         if min_component_faces < 0 or keep_largest < 0:
             raise ValueError("export_mesh: min_component_faces (%d) and keep_largest (%d) must be >= 0"
                              % (min_component_faces, keep_largest))
@@ -685,14 +743,17 @@ class NeRFRenderer(nn.Module):
                   "faces_cleaned": faces_cleaned}
         if int(texture_resolution) > 0:
             result.update(self._export_textured(str(path), verts, faces, normals, int(texture_resolution), gutter, S,
-                                                bool(field_normals), atlas))
+                                                bool(field_normals), atlas,
+                                                views=(bake_views, view_size, view_decoder, view_erode)))
         else:
             write_obj(out, verts.cpu().numpy(), faces.cpu().numpy(), normals.cpu().numpy(), colors.cpu().numpy())
         return result
 
-    def _export_textured(self, path, verts, faces, normals, R, gutter, S, normal_map=False, atlas="triangle"):
+    def _export_textured(self, path, verts, faces, normals, R, gutter, S, normal_map=False, atlas="triangle",
+                         views=(0, None, None, None)):
         """The textured half of export_mesh: atlas, bake, mesh.obj + mesh.mtl + albedo.png (+ latent_texture.pt;
-        normal_map: + normal_object.png, the field's normals over the same atlas)."""
+        normal_map: + normal_object.png, the field's normals over the same atlas; views = (K, size, decoder, erode)
+        with K > 0: albedo.png from K rendered views, the point bake's image as albedo_preview.png)."""
         import warnings
 
         import numpy as np
@@ -719,6 +780,12 @@ class NeRFRenderer(nn.Module):
         write_textured_obj(out, verts.cpu().numpy(), faces.cpu().numpy(), vt.cpu().numpy(), ft.cpu().numpy(),
                            normals.cpu().numpy(), material="mesh.mtl", texture="albedo.png")
         albedo = (baked["rgb"].permute(1, 2, 0).cpu().numpy() * 255).round().astype(np.uint8)
+        if views[0] > 0:
+            from ...view_bake import to_uint8
+            Image.fromarray(albedo).save(os.path.join(path, "albedo_preview.png"))
+            seen = self._bake_rendered_views(verts, faces, vt, ft, R, gutter, baked["rgb"], *views)
+            baked = dict(baked, view_rgb=seen["rgb"], view_weight=seen["view_weight"], view_count=seen["view_count"])
+            albedo = to_uint8(seen["rgb"])
         Image.fromarray(albedo).save(os.path.join(path, "albedo.png"))
         if (self.latent_mode or self.tuned) and baked["texture"].shape[0] == 4:
             torch.save(baked["texture"].cpu(), os.path.join(path, "latent_texture.pt"))
@@ -729,6 +796,26 @@ class NeRFRenderer(nn.Module):
             Image.fromarray(img).save(os.path.join(path, "normal_object.png"))
             baked = dict(baked, normal_map=nmap)
         return dict(baked, vt=vt, ft=ft, **extra)
+
+    def _bake_rendered_views(self, verts, faces, vt, ft, R, gutter, fallback, K, view_size, view_decoder, view_erode):
+        """export_mesh's view bake: K renders, decoded as images, projected into the atlas over `fallback`."""
+        renders, cams = self.render_bake_views(K, view_size)
+        h, w = renders.shape[-2:]
+        if view_decoder is None:
+            C = renders.shape[1]
+            images = self._latent_preview(renders.permute(0, 2, 3, 1).reshape(-1, C)).reshape(K, h, w, 3).permute(0, 3, 1, 2)
+        else:
+            images = view_decoder(renders)
+        if images.dim() != 4 or images.shape[0] != K or images.shape[1] != 3:
+            raise ValueError("export_mesh: view_decoder must return [K,3,H,W] = [%d,3,...], not %s"
+                             % (K, tuple(images.shape)))
+        H, W = (int(v) for v in images.shape[-2:])
+        if H * w != W * h:
+            raise ValueError("export_mesh: view_decoder changed the aspect ratio (%d x %d -> %d x %d)" % (h, w, H, W))
+        if view_erode is None:
+            view_erode = 0 if (H, W) == (h, w) else max(1, -(-H // h))
+        return self.bake_views(verts, faces, vt, ft, images.float().clamp(0, 1), cams, R, gutter=gutter, fallback=fallback,
+                               erode=int(view_erode))
 
     def shadow_extra_state(self):
         """Context manager: inside it the occupancy state (density grid, bitfield, mean) is a SHADOW copy, so

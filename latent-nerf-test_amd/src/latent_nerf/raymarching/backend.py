@@ -142,6 +142,7 @@ _SIGNATURES = {
     "lnerf_uv_raster_scratch_bytes": [_I, _I],
     "lnerf_uv_raster": [_P, _I, _P, _P, _I, _P, _I, _I, _I, _L, _P, _Z, _P, _P, _P, _L, _P, _P],
     "lnerf_uv_dilate": [_P, _P, _I, _I, _I, _P, _P, _P],
+    "lnerf_uv_project_views": [_P, _P, _L, _P, _I, _I, _I, _P, _P, _I, _F, _F, _F, _P, _P, _P, _P],
     "lnerf_decimate_scratch_bytes": [_I, _I],
     "lnerf_decimate": [_P, _I, _P, _I, _I, _F, _I, _P, _Z, _P, _P, _P, _P, _P],
     "lnerf_atlas_buckets": [_P, _I, _P, _I, _P, _P, _P, _P],

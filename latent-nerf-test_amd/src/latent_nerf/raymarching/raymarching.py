@@ -12,6 +12,7 @@ Conventions that differ from a CUDA port, by design for MI355X:
   * `deltas[:, 1]` is the absolute ray parameter t (depth = sum w_i t_i).
 """
 import ctypes
+import math
 
 import torch
 
@@ -1043,3 +1044,113 @@ def uv_dilate(texture, mask, passes):
         tmp, tmp_mask = torch.empty_like(texture), torch.empty_like(mask)
         _b.call("lnerf_uv_dilate", _p(texture), _p(mask), C, R, passes, _p(tmp), _p(tmp_mask), _stream())
     return texture, mask
+
+
+# ------------------------------------------------------------------------------ view projection
+GOLDEN_ANGLE = math.pi * (3.0 - math.sqrt(5.0))
+
+
+def bake_view_poses(K, theta_range=(math.radians(15.0), math.radians(150.0))):
+    """K view directions for a view bake: a spherical Fibonacci lattice restricted to the polar band `theta_range`
+    (radians from +y, the convention of pose_from_angles and Latent-Paint's Renderer).  The polar cosine is stratified
+    over the band -- view k sits at the mid-point of the k-th of K equal strata, so the views share the band's area
+    evenly -- and the azimuth is k x the golden angle.  -> [(theta, phi)] * K, host floats; deterministic."""
+    K = int(K)
+    t0, t1 = float(theta_range[0]), float(theta_range[1])
+    if K < 1:
+        raise ValueError("bake_view_poses: K must be >= 1 (got %d)" % K)
+    if not 0.0 <= t0 <= t1 <= math.pi:
+        raise ValueError("bake_view_poses: theta_range %r is not an interval of [0, pi]" % (theta_range,))
+    c0, c1 = math.cos(t0), math.cos(t1)
+    poses = []
+    for k in range(K):
+        c = c0 + (k + 0.5) / K * (c1 - c0)
+        poses.append((math.acos(max(-1.0, min(1.0, c))), (k * GOLDEN_ANGLE) % (2.0 * math.pi)))
+    return poses
+
+
+def nerf_camera_record(c2w, fx, fy, cx, cy, H, W):
+    """The NeRF camera (camera-to-world `c2w` [4,4] with the columns right, down, forward, eye of lnerf_get_rays, and
+    pixel intrinsics) as the rasteriser's 14-float record (rotation rows, eye, fx, fy; camera z negative in front): the
+    rows are right, -down, -forward and the focal lengths 2 fx / W, 2 fy / H, so the centre of pixel (row i, column j)
+    of get_rays lands on the rasteriser's pixel (i, j).  The record has no principal point: cx = W / 2 and cy = H / 2
+    (what intrinsics_from_fov gives) or ValueError.  -> list of 14 floats."""
+    m = c2w.detach().cpu().double().tolist() if isinstance(c2w, torch.Tensor) else [[float(v) for v in r] for r in c2w]
+    if len(m) < 3 or any(len(r) != 4 for r in m[:3]):
+        raise ValueError("nerf_camera_record: c2w must be [4,4] (or [3,4])")
+    H, W = int(H), int(W)
+    if abs(float(cx) - W / 2.0) > 1e-6 * W or abs(float(cy) - H / 2.0) > 1e-6 * H:
+        raise ValueError("nerf_camera_record: the rasteriser's camera has its principal point at the image centre "
+                         "(%g, %g), not (%g, %g)" % (W / 2.0, H / 2.0, cx, cy))
+    right, down, fwd, eye = ([m[r][c] for r in range(3)] for c in range(4))
+    return right + [-v for v in down] + [-v for v in fwd] + eye + [2.0 * float(fx) / W, 2.0 * float(fy) / H]
+
+
+def _cams(cams, op, dev):
+    if not isinstance(cams, torch.Tensor) or cams.dim() != 2 or cams.shape[1] != 14 or cams.shape[0] < 1:
+        raise ValueError("%s: cams must be [K,14] with K >= 1" % op)
+    cams = cams.to(device=dev, dtype=torch.float32).contiguous()
+    _chk(cams, "cams")
+    return cams
+
+
+def view_zbuffer(verts, faces, cams, H, W, erode=0):
+    """Camera z of the visible surface of a mesh at every pixel centre of K views -> zbuf [K,H,W] f32: the batched
+    rasteriser (lnerf_raster_prepare_batch, lnerf_rasterize_batch) and, per view, its perspective-correct barycentrics
+    over the corners' camera z (lnerf_interpolate_attributes).  Foreground is negative; background pixels hold +1, and
+    with `erode` > 0 so does every pixel within `erode` pixels (Chebyshev distance) of a background pixel: a decoder
+    that up-scales smears the background over about its factor.  cams: [K,14] records."""
+    H, W, erode = int(H), int(W), int(erode)
+    if erode < 0:
+        raise ValueError("view_zbuffer: erode must be >= 0")
+    verts, faces, V, F = _mesh_inputs(verts, faces, "view_zbuffer", 2 ** 31 - 1)
+    dev = verts.device
+    cams = _cams(cams, "view_zbuffer", dev)
+    K = cams.shape[0]
+    face_z = torch.empty(K, F, 3, device=dev)
+    face_xy = torch.empty(K, F, 3, 2, device=dev)
+    face_box = torch.empty(K, F, 4, device=dev, dtype=torch.int16)
+    _b.call("lnerf_raster_prepare_batch", _p(verts), V, _p(faces), F, _p(cams), K, H, W, _p(face_z), _p(face_xy),
+            _p(face_box), _stream())
+    face_idx = torch.empty(K, H * W, device=dev, dtype=torch.int32)
+    bary = torch.empty(K, H * W, 3, device=dev)
+    _b.call("lnerf_rasterize_batch", K, H, W, _p(face_z), _p(face_xy), _p(face_box), F, _p(face_idx), _p(bary), _stream())
+    zbuf = torch.empty(K, H * W, device=dev)
+    for k in range(K):   # face indices are per view: one D = 1 interpolation over each view's own corner depths
+        _b.call("lnerf_interpolate_attributes", _p(face_idx[k]), _p(bary[k]), _p(face_z[k]), H * W, 1, _p(zbuf[k]),
+                _stream())
+    bg = (face_idx < 0).view(K, 1, H, W)
+    if erode > 0:
+        bg = torch.nn.functional.max_pool2d(bg.float(), 2 * erode + 1, stride=1, padding=erode) > 0
+    return torch.where(bg.view(K, H, W), torch.ones((), device=dev), zbuf.view(K, H, W)).contiguous()
+
+
+def project_views(pos, nrm, cams, zbuf, images, cos_min=0.2, power=4.0, slack=2.0):
+    """Colour surface points from K images of the surface (lnerf_uv_project_views, include/lnerf_hip.h: the rule).
+    pos, nrm [P,3] (point, unit outward normal), cams [K,14], zbuf [K,H,W] (view_zbuffer), images [K,C,H,W], 1 <= C <= 4.
+    A view counts for a point where the point faces it (cosine >= cos_min), projects with all four bilinear taps on
+    foreground pixels and passes the depth test (`slack` pixel footprints of bias); its colour is weighted by
+    cosine^power.  -> out [P,C] (the weighted mean, 0 where no view counted), weight [P], count [P] int32."""
+    for t, name in ((pos, "pos"), (nrm, "nrm")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError("project_views: %s must be [P,3]" % name)
+    if pos.shape != nrm.shape:
+        raise ValueError("project_views: pos %s and nrm %s differ" % (tuple(pos.shape), tuple(nrm.shape)))
+    dev = pos.device
+    pos, nrm = pos.float().contiguous(), nrm.to(dev).float().contiguous()
+    cams = _cams(cams, "project_views", dev)
+    K = cams.shape[0]
+    if not isinstance(images, torch.Tensor) or images.dim() != 4 or images.shape[0] != K or not 1 <= images.shape[1] <= 4:
+        raise ValueError("project_views: images must be [K,C,H,W] with K = %d and 1 <= C <= 4" % K)
+    C, H, W = (int(v) for v in images.shape[1:])
+    if not isinstance(zbuf, torch.Tensor) or tuple(zbuf.shape) != (K, H, W):
+        raise ValueError("project_views: zbuf must be [K,H,W] = [%d,%d,%d]" % (K, H, W))
+    images, zbuf = images.to(dev).float().contiguous(), zbuf.to(dev).float().contiguous()
+    P = pos.shape[0]
+    out = torch.zeros(P, C, device=dev)
+    weight = torch.zeros(P, device=dev)
+    count = torch.zeros(P, device=dev, dtype=torch.int32)
+    _b.call("lnerf_uv_project_views", _chk(pos, "pos") if P else None, _chk(nrm, "nrm") if P else None, P, _p(cams), K, H,
+            W, _chk(zbuf, "zbuf"), _chk(images, "images"), C, float(cos_min), float(power), float(slack),
+            _p(out) if P else None, _p(weight) if P else None, _p(count) if P else None, _stream())
+    return out, weight, count

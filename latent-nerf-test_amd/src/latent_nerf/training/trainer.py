@@ -656,7 +656,12 @@ class Trainer:
             # the density field as a triangle mesh (NeRFRenderer.export_mesh) -> <exp_dir>/mesh/mesh.obj
             tex = int(getattr(self.cfg.log, "mesh_texture_resolution", 0))
             target = int(getattr(self.cfg.log, "mesh_target_faces", 0))
+            # the view bake decodes its renders the way the evaluation renders are decoded (preview_rgb)
+            decoded = getattr(self.cfg.log, "decode_eval", False) and self.nerf.latent_mode
             mesh = self.nerf.export_mesh(self.exp_path / "mesh", texture_resolution=tex, target_faces=target,
+                                         bake_views=int(getattr(self.cfg.log, "mesh_bake_views", 0)),
+                                         view_size=int(getattr(self.cfg.log, "mesh_bake_view_size", 0)) or None,
+                                         view_decoder=(lambda z: decode_with(self.diffusion, z.float())) if decoded else None,
                                          field_normals=bool(getattr(self.cfg.log, "mesh_field_normals", False)),
                                          atlas=getattr(self.cfg.log, "mesh_atlas", "triangle"),
                                          min_component_faces=int(getattr(self.cfg.log, "mesh_min_component_faces", 0)),

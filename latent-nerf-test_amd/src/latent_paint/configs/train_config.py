@@ -60,6 +60,8 @@ LogConfig = _cli.make_section("LogConfig", (
     ("eval_size", int, 10, "evaluation views during training"),
     ("full_eval_size", int, 100, "evaluation views of the final pass"),
     ("save_mesh", bool, True, "export the textured mesh with the final evaluation"),
+    ("mesh_bake_views", int, 0, "with save_mesh: > 0 projects albedo.png from this many evaluation renders of the decoded "
+                                "mesh instead of decoding the atlas as one picture (kept as albedo_preview.png)"),
     ("max_keep_ckpts", int, 2, "older checkpoints are deleted beyond this count"),
 ), namespace={"exp_dir": property(lambda self: Path(self.exp_root) / self.exp_name)}, doc="logging and saving")
 
@@ -91,6 +93,11 @@ class TrainConfig:
             raise ValueError("guide.texture_lod_bias must be finite (got %s)" % self.guide.texture_lod_bias)
         if self.guide.uv_atlas not in UV_ATLASES:
             raise ValueError("guide.uv_atlas must be one of %s, not %r" % (" | ".join(UV_ATLASES), self.guide.uv_atlas))
+        if self.log.mesh_bake_views < 0:
+            raise ValueError("log.mesh_bake_views must be >= 0 (got %s)" % self.log.mesh_bake_views)
+        if self.log.mesh_bake_views > 0 and self.guide.texture_resolution < 1:
+            raise ValueError("log.mesh_bake_views = %s needs guide.texture_resolution > 0: the views are baked into the "
+                             "exported texture" % self.log.mesh_bake_views)
         if self.render.batch_size < 1:
             raise ValueError("render.batch_size must be >= 1 (got %s)" % self.render.batch_size)
         return self

@@ -17,6 +17,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ... import view_bake
+from ...latent_nerf.raymarching.raymarching import bake_view_poses
 from ...uv_atlas import chart_atlas, check_atlas_choice, per_triangle_atlas
 from .mesh import Mesh
 from .render import Renderer
@@ -199,9 +201,17 @@ class TexturedMeshModel(nn.Module):
 
     # ------------------------------------------------------------------ export
     @torch.no_grad()
-    def export_mesh(self, path, guidance=None):
-        """Writes `albedo.png` (the decoded texture), `mesh.obj` (v / vt / f v/vt) and `mesh.mtl` into `path`."""
+    def export_mesh(self, path, guidance=None, bake_views=0, view_size=None):
+        """Writes `albedo.png` (the decoded texture), `mesh.obj` (v / vt / f v/vt) and `mesh.mtl` into `path`.
+        bake_views = K > 0: the decoder sees the whole atlas as one picture, so chart borders and unrelated neighbouring
+        charts are decoded together; instead `albedo.png` is projected from K evaluation renders of the decoded mesh
+        (render_test at `view_size`, default render.eval_grid_size; the directions of raymarching.bake_view_poses at the
+        evaluation radius) with view_bake.bake_views, the decoded atlas filling the texels no view sees and kept as
+        `albedo_preview.png`.  -> dict(rgb [3,R,R]; K > 0: + view_rgb, view_weight, view_count, mask)."""
         from PIL import Image
+        bake_views = int(bake_views)
+        if bake_views < 0:
+            raise ValueError("export_mesh: bake_views must be >= 0 (got %d)" % bake_views)
         path = Path(path)
         path.mkdir(parents=True, exist_ok=True)
         if self.latent_mode:
@@ -212,7 +222,32 @@ class TexturedMeshModel(nn.Module):
         else:
             rgb = self.texture_img_rgb_finetune
         albedo = (rgb[0].permute(1, 2, 0).clamp(0, 1).cpu().numpy() * 255).astype(np.uint8)
+        result = {"rgb": rgb[0]}
+        if bake_views > 0:
+            Image.fromarray(albedo).save(path / "albedo_preview.png")
+            result.update(self._bake_rendered_views(rgb, bake_views, view_size))
+            # (the projected image is rounded to 8 bits, as the NeRF exporter's; the preview above keeps the upstream
+            # exporter's truncation, so that it and the K = 0 file stay byte for byte what they were)
+            albedo = view_bake.to_uint8(result["view_rgb"])
         Image.fromarray(albedo).save(path / "albedo.png")
+        self._write_obj(path)
+        return result
+
+    def _bake_rendered_views(self, rgb, K, view_size):
+        """export_mesh's view bake over the decoded atlas `rgb` [1,3,R,R]: K renders of it on the mesh, projected back."""
+        side = int(view_size or self.opt.render.eval_grid_size)
+        poses = bake_view_poses(K)
+        view = self._view([t for t, _ in poses], [p for _, p in poses], [self.opt.render.radius_range[1] * 1.2] * K)
+        cams = self.renderer._cameras(view["elev"], view["azim"], view["radius"], view["look_at_height"])
+        # (the atlas is decoded already: render_test's decoder hands it back; the RGB backbone renders its own texture)
+        images = self.render_test(view["elev"], view["azim"], view["radius"], decode_func=lambda _t: rgb,
+                                  dims=(side, side))["image"]
+        baked = view_bake.bake_views(self.mesh.vertices, self.mesh.faces, self.vt, self.ft, images.clamp(0, 1), cams,
+                                     rgb.shape[-1], fallback=rgb[0].float().clamp(0, 1))
+        return {"view_rgb": baked["rgb"], "view_weight": baked["view_weight"], "view_count": baked["view_count"],
+                "mask": baked["mask"]}
+
+    def _write_obj(self, path):
         v = self.mesh.vertices.cpu().numpy()
         f = self.mesh.faces.cpu().numpy() + 1
         vt = self.vt.cpu().numpy()

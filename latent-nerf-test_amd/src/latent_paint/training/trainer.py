@@ -181,7 +181,8 @@ class Trainer:
         self.evaluate(self.dataloaders["val_large"], self.final_renders_path, save_as_video=True)
         if self.cfg.log.save_mesh:
             target = make_path(self.exp_path / "mesh")
-            self.mesh_model.export_mesh(target, guidance=self.diffusion)
+            self.mesh_model.export_mesh(target, guidance=self.diffusion,
+                                        bake_views=int(getattr(self.cfg.log, "mesh_bake_views", 0)))
             self.log("saved mesh to %s" % target)
 
     @torch.no_grad()

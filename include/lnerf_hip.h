@@ -611,6 +611,77 @@ int lnerf_texture_mip_backward(const float *uv, const float *rho, const int32_t 
                                int n_pixels, int C, int R, int L, float bias, float *dtexture, float *dpyramid,
                                lnerf_stream_t stream);
 
+/* ---- Coverage-weighted texture pyramids (`guide.texture_mip_coverage`, the pull-push fill of the exports;
+ * csrc/texcov.hip).  Additive to ABI 7; the plain pyramid above is unchanged.  A pyramid whose level l is the
+ * coverage-weighted mean of level l - 1, the weights carried along, read normalised (the lookup) or pushed back down into
+ * the texels no surface point owns (the fill).  f32, every operation rounded on its own.  Shapes and packing are the
+ * plain pyramid's: texture [C,R,R], R divisible by 2^L, values of levels 1..L packed [C,S], their weights [S].
+ *
+ * Weights.  w0 [R,R] in [0,1] (the callers pass 0 or 1).  With a, b, c, d the four children of a level-l texel (i, j) in
+ *   the order (2i, 2j), (2i, 2j+1), (2i+1, 2j), (2i+1, 2j+1) of level l - 1:
+ *     s   = (wa + wb) + (wc + wd)
+ *     w_l = s * 0.25
+ *   For 0/1 weights at level 0 every w_l is a multiple of 4^-l not above 1: exact in f32 (up to L = 11).
+ * lnerf_mipcov_weights: w0 -> wpyr, one launch per level.  L = 0 launches nothing (wpyr may be NULL, here and below).
+ *
+ * lnerf_mipcov_pull: texture, w0, wpyr -> pyramid, one launch per level, t the values of level l - 1:
+ *     v_l = s > 0 ? ((wa * ta + wb * tb) + (wc * tc + wd * td)) / s : 0
+ *   With every weight 1 this is lnerf_mip_build bit for bit (s = 4, and / 4 is * 0.25).
+ * lnerf_mipcov_pull_backward: the exact transpose in gather form (no atomics, deterministic), from the coarsest level
+ *   down, INSIDE dpyramid (which it therefore changes), ending in dtexture, which is ACCUMULATED into:
+ *     d[l-1][child] += (w_child / s) * d[l][parent]      s recomputed from the parent's four children
+ *   Nothing is added where s == 0 (s > 0 is false).
+ *
+ * lnerf_mipcov_push: the pull-push fill.  `pyramid` holds lnerf_mipcov_pull's values on entry and the filled levels on
+ *   exit; level 0 is `texture`, filled in place.  With L >= 1:
+ *     F_L = v_L
+ *     for l = L - 1 ... 0:
+ *       k   = l >= 1 ? min(s_l, 1) : w0      s_l as above: a coarse texel with one whole covered child counts as known
+ *       F_l = k == 1 ? v_l : k == 0 ? up(F_{l+1}) : k * v_l + (1 - k) * up(F_{l+1})
+ *   (k == 0 is the general rule without reading v_l: an uncovered texel of the texture may hold anything.)
+ *   A texel of any level is REACHED when its ancestor on level L has w_L > 0.  Texels that are not reached are left
+ *   alone on every level, so texels under a coarsest-level texel of weight 0 stay as they were.
+ *   up = the 2 x bilinear upsample with texel centres (align_corners=False), edges clamped.  For the texel (i, j) of
+ *   level l, on level l + 1 (side Rc):
+ *     pi = i / 2;  ni = i odd ? min(pi + 1, Rc - 1) : max(pi - 1, 0);   pj, nj likewise
+ *     taps in the order (pi, pj), (pi, nj), (ni, pj), (ni, nj) with b = 9/16, 3/16, 3/16, 1/16
+ *     up = (b0 * F0 + b1 * F1) + (b2 * F2 + b3 * F3)
+ *   (pi, pj) is the texel's parent and is reached when the texel is.  A tap that is not reached holds no value: its
+ *   term is 0 in the sum, and up is then divided by (b0 + b1') + (b2' + b3'), b' = b on reached taps and 0 elsewhere
+ *   (at least 9/16).  With all four reached there is no division.
+ *   filled [R,R] uint8 (may be NULL): 1 where w0 != 1 and the texel is reached, i.e. where level 0 was written; else 0.
+ *   Texels with w0 == 1 are not written at all.  With L = 0 nothing is pushed (filled = 0 everywhere).
+ *
+ * lnerf_texture_mipcov_forward / _backward: lnerf_texture_mip_* with the weights.  lambda, l0, t and the taps
+ *   (i_k, b_k), k = 00, 01, 10, 11, are exactly those of lnerf_texture_mip_forward; V = `pyramid` from lnerf_mipcov_pull
+ *   (level 0 = texture), W = w0 / wpyr.  Per level read, in the order of the plain mode's sum:
+ *     n(l) = (b00 * W00) * V00 + (b01 * W01) * V01 + (b10 * W10) * V10 + (b11 * W11) * V11
+ *     d(l) = (b00 * W00) + (b01 * W01) + (b10 * W10) + (b11 * W11)
+ *     N = t == 0 ? n(l0) : (1 - t) * n(l0) + t * n(l0 + 1);   D likewise from d
+ *   Three cases, decided from these f32 values only:
+ *     (a) every W read is exactly 1:  out = N.  No division: the plain mode's result bit for bit.
+ *     (b) D == 0 (a sliver face that covers no texel centre): the plain mode's result, every W taken as 1.
+ *     (c) otherwise:  out = N / D.
+ *   Backward: float atomics of (b_k * W_k) * (m * g / D) into tap k of level l, m * g = (1 - t) * g on l0 and t * g on
+ *   l0 + 1 (g when t == 0); in cases (a) and (b) the plain mode's addends b_k * (m * g).  Level 0 is dtexture, the
+ *   others dpyramid; both are ACCUMULATED into.  lnerf_mipcov_pull_backward then folds dpyramid into dtexture.  The
+ *   weights, uv and rho carry no gradient.
+ * All six: no allocation, no synchronisation, no host read-back; capturable.  Every argument is checked before the
+ * first launch. */
+int lnerf_mipcov_weights(const float *w0, int R, int L, float *wpyr, lnerf_stream_t stream);
+int lnerf_mipcov_pull(const float *texture, const float *w0, const float *wpyr, int C, int R, int L, float *pyramid,
+                      lnerf_stream_t stream);
+int lnerf_mipcov_pull_backward(float *dpyramid, const float *w0, const float *wpyr, int C, int R, int L,
+                               float *dtexture, lnerf_stream_t stream);
+int lnerf_mipcov_push(float *texture, const float *w0, const float *wpyr, float *pyramid, int C, int R, int L,
+                      uint8_t *filled, lnerf_stream_t stream);
+int lnerf_texture_mipcov_forward(const float *uv, const float *rho, const int32_t *face_idx, const float *texture,
+                                 const float *pyramid, const float *w0, const float *wpyr, int n_pixels, int C, int R,
+                                 int L, float bias, float *out, lnerf_stream_t stream);
+int lnerf_texture_mipcov_backward(const float *uv, const float *rho, const int32_t *face_idx, const float *dout,
+                                  const float *w0, const float *wpyr, int n_pixels, int C, int R, int L, float bias,
+                                  float *dtexture, float *dpyramid, lnerf_stream_t stream);
+
 /* ---- optimiser step used by the bench/trainer (Adam, src/latent_paint/training/trainer.py:93-95:
  * betas (0.9, 0.99), eps 1e-15).  g is multiplied by grad_scale (1/world_size) first; if
  * zero_grad != 0 the gradient is cleared in the same pass; if shadow_bf16 != NULL the bf16

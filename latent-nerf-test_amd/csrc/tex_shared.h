@@ -1,4 +1,5 @@
-// Texel coordinates of a texture lookup, shared by the point lookups (raster.hip) and the mip-mapped one (texmip.hip).
+// Texel coordinates of a texture lookup, shared by the point lookups (raster.hip) and the mip-mapped ones (texmip.hip,
+// texcov.hip), and what the two pyramids have in common.
 #pragma once
 #include "common.h"
 
@@ -17,6 +18,49 @@ __device__ __forceinline__ void tex_coords(float u, float v, int R, bool clip, f
         x = clampf(x, 0.f, (float)(R - 1));
         y = clampf(y, 0.f, (float)(R - 1));
     }
+}
+
+// ---- the mip pyramid's packing, taps and shape check, shared by texmip.hip and texcov.hip
+// texels of levels 1 .. l - 1 of one channel in the packed buffer: sum_m (R >> m)^2 = (R^2 - (R >> (l-1))^2) / 3, exact
+// because R is divisible by 2^L
+__host__ __device__ __forceinline__ int64_t mip_offset(int R, int l) {
+    const int64_t r0 = R, r1 = R >> (l - 1);
+    return (r0 * r0 - r1 * r1) / 3;
+}
+static int64_t mip_texels(int R, int L) { return L > 0 ? mip_offset(R, L + 1) : 0; }
+
+// k_texture_map's bilinear lookup (raster.hip, mode 1) on one level: the same coordinates, taps and weights
+struct BilTaps {
+    int64_t i00, i01, i10, i11;
+    float w00, w01, w10, w11;
+};
+__device__ __forceinline__ BilTaps bil_taps(float u, float v, int R) {
+    float x, y;
+    tex_coords(u, v, R, true, x, y);
+    const float xf = floorf(x), yf = floorf(y);
+    const int x0 = (int)xf, y0 = (int)yf, x1 = min(x0 + 1, R - 1), y1 = min(y0 + 1, R - 1);
+    const float ax = x - xf, ay = y - yf;
+    BilTaps b;
+    b.w00 = (1.f - ax) * (1.f - ay); b.w01 = ax * (1.f - ay); b.w10 = (1.f - ax) * ay; b.w11 = ax * ay;
+    b.i00 = (int64_t)y0 * R + x0; b.i01 = (int64_t)y0 * R + x1; b.i10 = (int64_t)y1 * R + x0; b.i11 = (int64_t)y1 * R + x1;
+    return b;
+}
+__device__ __forceinline__ float bil_read(const float *tc, const BilTaps &b) {
+    return b.w00 * tc[b.i00] + b.w01 * tc[b.i01] + b.w10 * tc[b.i10] + b.w11 * tc[b.i11];
+}
+__device__ __forceinline__ void bil_add(float *tc, const BilTaps &b, float g) {
+    atomicAdd(&tc[b.i00], b.w00 * g); atomicAdd(&tc[b.i01], b.w01 * g);
+    atomicAdd(&tc[b.i10], b.w10 * g); atomicAdd(&tc[b.i11], b.w11 * g);
+}
+
+// the shape of a texture and its pyramid, checked before any launch
+static int check_mip_shape(const char *who, int C, int R, int L) {
+    LNERF_REQUIRE(C >= 1, "%s: C must be >= 1 (got %d)", who, C);
+    LNERF_REQUIRE(R >= 1, "%s: R must be >= 1 (got %d)", who, R);
+    LNERF_REQUIRE(L >= 0, "%s: L must be >= 0 (got %d)", who, L);
+    LNERF_REQUIRE(L <= 30 && (R & ((1 << L) - 1)) == 0, "%s: R must be divisible by 2^L (got R = %d, L = %d)", who, R, L);
+    LNERF_REQUIRE((int64_t)C * R * R <= ((int64_t)1 << 38), "%s: C * R * R must be <= 2^38 (got C = %d, R = %d)", who, C, R);
+    return LNERF_OK;
 }
 
 }  // namespace lnerf

@@ -94,38 +94,6 @@ k_mip_up(const float *__restrict__ dcoarse, int64_t cstride, float *__restrict__
     dfine[c * fstride + r] += 0.25f * dcoarse[c * cstride + (int64_t)(i / 2) * Rc + j / 2];
 }
 
-// texels of levels 1 .. l - 1 of one channel in the packed buffer: sum_m (R >> m)^2 = (R^2 - (R >> (l-1))^2) / 3, exact
-// because R is divisible by 2^L
-__host__ __device__ __forceinline__ int64_t mip_offset(int R, int l) {
-    const int64_t r0 = R, r1 = R >> (l - 1);
-    return (r0 * r0 - r1 * r1) / 3;
-}
-static int64_t mip_texels(int R, int L) { return L > 0 ? mip_offset(R, L + 1) : 0; }
-
-// k_texture_map's bilinear lookup (raster.hip, mode 1) on one level: the same coordinates, taps and weights
-struct BilTaps {
-    int64_t i00, i01, i10, i11;
-    float w00, w01, w10, w11;
-};
-__device__ __forceinline__ BilTaps bil_taps(float u, float v, int R) {
-    float x, y;
-    tex_coords(u, v, R, true, x, y);
-    const float xf = floorf(x), yf = floorf(y);
-    const int x0 = (int)xf, y0 = (int)yf, x1 = min(x0 + 1, R - 1), y1 = min(y0 + 1, R - 1);
-    const float ax = x - xf, ay = y - yf;
-    BilTaps b;
-    b.w00 = (1.f - ax) * (1.f - ay); b.w01 = ax * (1.f - ay); b.w10 = (1.f - ax) * ay; b.w11 = ax * ay;
-    b.i00 = (int64_t)y0 * R + x0; b.i01 = (int64_t)y0 * R + x1; b.i10 = (int64_t)y1 * R + x0; b.i11 = (int64_t)y1 * R + x1;
-    return b;
-}
-__device__ __forceinline__ float bil_read(const float *tc, const BilTaps &b) {
-    return b.w00 * tc[b.i00] + b.w01 * tc[b.i01] + b.w10 * tc[b.i10] + b.w11 * tc[b.i11];
-}
-__device__ __forceinline__ void bil_add(float *tc, const BilTaps &b, float g) {
-    atomicAdd(&tc[b.i00], b.w00 * g); atomicAdd(&tc[b.i01], b.w01 * g);
-    atomicAdd(&tc[b.i10], b.w10 * g); atomicAdd(&tc[b.i11], b.w11 * g);
-}
-
 // One thread per (pixel, channel), as k_texture_map.  tex = level 0 [C,R,R], pyr = levels 1..L packed [C,S]; in the
 // backward both are the gradients the atomics add to.
 template <bool BWD>
@@ -162,16 +130,6 @@ k_texture_mip(const float *__restrict__ uv, const float *__restrict__ rho, const
     } else {
         out_or_dout[t] = (1.f - mix) * bil_read(t0, b0) + mix * bil_read(t1, b1);
     }
-}
-
-// the shape of a texture and its pyramid, checked before any launch
-static int check_mip_shape(const char *who, int C, int R, int L) {
-    LNERF_REQUIRE(C >= 1, "%s: C must be >= 1 (got %d)", who, C);
-    LNERF_REQUIRE(R >= 1, "%s: R must be >= 1 (got %d)", who, R);
-    LNERF_REQUIRE(L >= 0, "%s: L must be >= 0 (got %d)", who, L);
-    LNERF_REQUIRE(L <= 30 && (R & ((1 << L) - 1)) == 0, "%s: R must be divisible by 2^L (got R = %d, L = %d)", who, R, L);
-    LNERF_REQUIRE((int64_t)C * R * R <= ((int64_t)1 << 38), "%s: C * R * R must be <= 2^38 (got C = %d, R = %d)", who, C, R);
-    return LNERF_OK;
 }
 
 }  // namespace lnerf

@@ -113,6 +113,8 @@ class OptimConfig:
     lambda_normal_smooth: float = 0.0
 
 MESH_ATLASES = ("triangle", "charts")   # log.mesh_atlas (src/uv_atlas.py ATLAS_CHOICES)
+TEXTURE_FILLS = ("dilate", "pullpush")   # log.mesh_texture_fill (src/view_bake.py TEXTURE_FILLS)
+BAKE_UNSEEN = ("fallback", "inpaint")    # log.mesh_bake_unseen (src/view_bake.py BAKE_UNSEEN)
 
 
 @dataclass
@@ -150,6 +152,13 @@ class LogConfig:
     # is kept as albedo_preview.png.  mesh_bake_view_size: side of those renders (0 = render.eval_h x render.eval_w)
     mesh_bake_views: int = 0
     mesh_bake_view_size: int = 0
+    # with mesh_texture_resolution: what the exported images hold outside the charts.  "dilate": the gutter rounds only;
+    # "pullpush": the whole atlas is filled from the charts (raymarching.pull_push_fill), so that the mip levels a viewer
+    # builds from albedo.png / normal_object.png / latent_texture.pt do not average the empty colour in at chart borders
+    mesh_texture_fill: str = "dilate"
+    # with mesh_bake_views: covered texels no view sees take the point bake's colour ("fallback") or are filled from the
+    # seen texels ("inpaint")
+    mesh_bake_unseen: str = "fallback"
     # evaluation also writes a normal-shaded render (*_normals.png / *_normals video) beside every *_rgb one
     eval_normals: bool = False
     max_keep_ckpts: int = 2
@@ -208,6 +217,12 @@ class TrainConfig:
             raise ValueError("optim.tv_vertices must be >= 1, not %r" % (self.optim.tv_vertices,))
         if self.log.mesh_atlas not in MESH_ATLASES:
             raise ValueError("log.mesh_atlas must be one of %s, not %r" % (" | ".join(MESH_ATLASES), self.log.mesh_atlas))
+        if self.log.mesh_texture_fill not in TEXTURE_FILLS:
+            raise ValueError("log.mesh_texture_fill must be one of %s, not %r"
+                             % (" | ".join(TEXTURE_FILLS), self.log.mesh_texture_fill))
+        if self.log.mesh_bake_unseen not in BAKE_UNSEEN:
+            raise ValueError("log.mesh_bake_unseen must be one of %s, not %r"
+                             % (" | ".join(BAKE_UNSEEN), self.log.mesh_bake_unseen))
         for n in ("mesh_min_component_faces", "mesh_min_component_diameter", "mesh_keep_largest", "mesh_smooth_iterations"):
             if not getattr(self.log, n) >= 0:
                 raise ValueError("log.%s must be >= 0, not %r" % (n, getattr(self.log, n)))

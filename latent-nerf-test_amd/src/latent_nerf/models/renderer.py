@@ -578,13 +578,17 @@ class NeRFRenderer(nn.Module):
         return rgb.clamp(0, 1)
 
     @torch.no_grad()
-    def bake_texture(self, verts, faces, vt, ft, resolution=1024, gutter=4, S=128, fn=None):
+    def bake_texture(self, verts, faces, vt, ft, resolution=1024, gutter=4, S=128, fn=None, fill="dilate"):
         """Sample the field over a mesh's UV atlas.  Every texel whose centre a face covers (lnerf_uv_raster: the
         face with the largest index where charts overlap) gets fn(surface point), fn(pts [P,3]) -> [P,C] queried in
         S^3-point chunks (default: the field's features, 4-channel latents -- latent_tune included -- or RGB); then `gutter` dilation rounds
         (lnerf_uv_dilate) spread the chart borders outwards so that bilinear lookups there do not blend in zeros.
         Texel (i, j) sits at u = (j + 0.5) / R, v = 1 - (i + 0.5) / R, the convention Latent-Paint's texture lookup uses.
-        -> dict(texture [C,R,R] f32, mask [R,R] uint8 (2 covered, 1 gutter, 0 empty), rgb [3,R,R] in [0, 1])."""
+        fill="pullpush": the texels the gutter leaves empty are then filled from the rest (view_bake.fill_atlas: a
+        coverage-weighted pull-push over the whole atlas; mask code 3), so that mip levels built from the image do not seam.
+        -> dict(texture [C,R,R] f32, mask [R,R] uint8 (2 covered, 1 gutter, 3 filled, 0 empty), rgb [3,R,R] in [0, 1])."""
+        from ... import view_bake
+        view_bake.check_choice(fill, view_bake.TEXTURE_FILLS, "bake_texture: fill")
         if fn is None:
             def fn(pts):
                 return self.field(pts, pts.shape[0])[1]
@@ -602,20 +606,22 @@ class NeRFRenderer(nn.Module):
         mask = (texel_face.reshape(-1) >= 0).to(torch.uint8) * 2
         texture, mask = texture.view(C, R, R), mask.view(R, R)
         rm.uv_dilate(texture, mask, gutter)
+        texture, mask = view_bake.fill_atlas(texture, mask, fill)
         rgb = self._latent_preview(texture.reshape(C, -1).T).T.reshape(3, R, R).contiguous()
         return {"texture": texture, "mask": mask, "rgb": rgb}
 
     @torch.no_grad()
     def bake_views(self, verts, faces, vt, ft, images, cams, resolution, gutter=4, fallback=None, erode=0, cos_min=0.2,
-                   power=4.0, slack=2.0):
+                   power=4.0, slack=2.0, fill="dilate", unseen="fallback"):
         """Project K images of the mesh (images [K,C,H,W] seen by the camera records cams [K,14]) into its UV atlas:
         texels from lnerf_uv_raster, texel normal = the winding normal of the covering face (marching cubes winds
         outwards), visibility from view_zbuffer at the images' size, colours from project_views, `fallback` [C,R,R]
-        where no view sees a texel, `gutter` dilation rounds (view_bake.bake_views, shared with Latent-Paint).
+        where no view sees a texel (unseen="inpaint": filled from the seen texels instead), `gutter` dilation rounds and
+        `fill` as bake_texture (view_bake.bake_views, shared with Latent-Paint).
         -> dict(rgb [C,R,R], view_weight [R,R], view_count [R,R] int32, mask [R,R] uint8)."""
         from ... import view_bake
         return view_bake.bake_views(verts, faces, vt, ft, images, cams, resolution, gutter=gutter, fallback=fallback,
-                                    erode=erode, cos_min=cos_min, power=power, slack=slack)
+                                    erode=erode, cos_min=cos_min, power=power, slack=slack, fill=fill, unseen=unseen)
 
     @torch.no_grad()
     def render_bake_views(self, K, view_size=None):
@@ -652,7 +658,7 @@ class NeRFRenderer(nn.Module):
     def export_mesh(self, path, resolution=None, S=128, thresh=None, texture_resolution=0, gutter=4, target_faces=0,
                     field_normals=False, atlas="triangle", min_component_faces=0, min_component_diameter=0.0,
                     keep_largest=0, smooth_iterations=0, bake_views=0, view_size=None, view_decoder=None,
-                    view_erode=None):
+                    view_erode=None, fill="dilate", unseen="fallback"):
         """Triangle mesh of the density field -> `path`/mesh.obj (the upstream renderer's export_mesh(path, resolution,
         S)): the density on a `resolution`^3 lattice over [-bound, bound]^3 (density_lattice), marching cubes on the GPU
         at iso `thresh` (default min(mean density, density_thresh), as upstream) with the box capped, vertex colours
@@ -686,12 +692,19 @@ class NeRFRenderer(nn.Module):
         up-scaling factor, about what a decoder smears the background over).  The point bake's image is kept as
         albedo_preview.png; the result gains view_rgb [3,R,R], view_weight and view_count [R,R]; rgb, texture and
         latent_texture.pt are what they are without the option.
+        fill = "pullpush" (textured): every baked image -- albedo.png, albedo_preview.png, normal_object.png,
+        latent_texture.pt -- is filled beyond the gutter over the whole atlas (bake_texture); "dilate" leaves the files
+        byte for byte what they were.  unseen = "inpaint" (with bake_views): covered texels no view sees are filled from
+        the seen ones instead of taking the point bake's colour.
         Returns dict(verts [V,3], faces [F,3] int32, normals [V,3], colors [V,3], iso, path, faces_before (the
         marching-cubes face count), components and components_kept (None without a cleaning), faces_cleaned (the face
         count after the cleaning)) with device tensors, plus vt, ft, texture, mask, rgb when textured."""
         from ...uv_atlas import check_atlas_choice
         from .mesh_io import write_obj
+        from ...view_bake import BAKE_UNSEEN, TEXTURE_FILLS, check_choice
         check_atlas_choice(atlas, "export_mesh: atlas")
+        check_choice(fill, TEXTURE_FILLS, "export_mesh: fill")
+        check_choice(unseen, BAKE_UNSEEN, "export_mesh: unseen")
         min_component_faces, min_component_diameter = int(min_component_faces), float(min_component_diameter)
         keep_largest, smooth_iterations = int(keep_largest), int(smooth_iterations)
         bake_views = int(bake_views)
@@ -744,16 +757,18 @@ class NeRFRenderer(nn.Module):
         if int(texture_resolution) > 0:
             result.update(self._export_textured(str(path), verts, faces, normals, int(texture_resolution), gutter, S,
                                                 bool(field_normals), atlas,
-                                                views=(bake_views, view_size, view_decoder, view_erode)))
+                                                views=(bake_views, view_size, view_decoder, view_erode), fill=fill,
+                                                unseen=unseen))
         else:
             write_obj(out, verts.cpu().numpy(), faces.cpu().numpy(), normals.cpu().numpy(), colors.cpu().numpy())
         return result
 
     def _export_textured(self, path, verts, faces, normals, R, gutter, S, normal_map=False, atlas="triangle",
-                         views=(0, None, None, None)):
+                         views=(0, None, None, None), fill="dilate", unseen="fallback"):
         """The textured half of export_mesh: atlas, bake, mesh.obj + mesh.mtl + albedo.png (+ latent_texture.pt;
         normal_map: + normal_object.png, the field's normals over the same atlas; views = (K, size, decoder, erode)
-        with K > 0: albedo.png from K rendered views, the point bake's image as albedo_preview.png)."""
+        with K > 0: albedo.png from K rendered views, the point bake's image as albedo_preview.png; `fill` and `unseen`
+        as export_mesh)."""
         import warnings
 
         import numpy as np
@@ -774,7 +789,7 @@ class NeRFRenderer(nn.Module):
                               % (R, F, R / atlas_cells(F), MIN_TEXELS_PER_CELL, need, 2 * (R // MIN_TEXELS_PER_CELL) ** 2),
                               stacklevel=3)
             vt, ft = per_triangle_atlas(F, verts.device)
-        baked = self.bake_texture(verts, faces, vt, ft, resolution=R, gutter=gutter, S=S)
+        baked = self.bake_texture(verts, faces, vt, ft, resolution=R, gutter=gutter, S=S, fill=fill)
         os.makedirs(path, exist_ok=True)
         out = os.path.join(path, "mesh.obj")
         write_textured_obj(out, verts.cpu().numpy(), faces.cpu().numpy(), vt.cpu().numpy(), ft.cpu().numpy(),
@@ -783,7 +798,8 @@ class NeRFRenderer(nn.Module):
         if views[0] > 0:
             from ...view_bake import to_uint8
             Image.fromarray(albedo).save(os.path.join(path, "albedo_preview.png"))
-            seen = self._bake_rendered_views(verts, faces, vt, ft, R, gutter, baked["rgb"], *views)
+            seen = self._bake_rendered_views(verts, faces, vt, ft, R, gutter, baked["rgb"], *views, fill=fill,
+                                             unseen=unseen)
             baked = dict(baked, view_rgb=seen["rgb"], view_weight=seen["view_weight"], view_count=seen["view_count"])
             albedo = to_uint8(seen["rgb"])
         Image.fromarray(albedo).save(os.path.join(path, "albedo.png"))
@@ -791,13 +807,14 @@ class NeRFRenderer(nn.Module):
             torch.save(baked["texture"].cpu(), os.path.join(path, "latent_texture.pt"))
         if normal_map:
             nmap = self.bake_texture(verts, faces, vt, ft, resolution=R, gutter=gutter, S=S,
-                                     fn=lambda pts: (self.normal(pts) + 1.0) / 2.0)["texture"]
+                                     fn=lambda pts: (self.normal(pts) + 1.0) / 2.0, fill=fill)["texture"]
             img = (nmap.clamp(0, 1).permute(1, 2, 0).cpu().numpy() * 255).round().astype(np.uint8)
             Image.fromarray(img).save(os.path.join(path, "normal_object.png"))
             baked = dict(baked, normal_map=nmap)
         return dict(baked, vt=vt, ft=ft, **extra)
 
-    def _bake_rendered_views(self, verts, faces, vt, ft, R, gutter, fallback, K, view_size, view_decoder, view_erode):
+    def _bake_rendered_views(self, verts, faces, vt, ft, R, gutter, fallback, K, view_size, view_decoder, view_erode,
+                             fill="dilate", unseen="fallback"):
         """export_mesh's view bake: K renders, decoded as images, projected into the atlas over `fallback`."""
         renders, cams = self.render_bake_views(K, view_size)
         h, w = renders.shape[-2:]
@@ -815,7 +832,7 @@ class NeRFRenderer(nn.Module):
         if view_erode is None:
             view_erode = 0 if (H, W) == (h, w) else max(1, -(-H // h))
         return self.bake_views(verts, faces, vt, ft, images.float().clamp(0, 1), cams, R, gutter=gutter, fallback=fallback,
-                               erode=int(view_erode))
+                               erode=int(view_erode), fill=fill, unseen=unseen)
 
     def shadow_extra_state(self):
         """Context manager: inside it the occupancy state (density grid, bitfield, mean) is a SHADOW copy, so

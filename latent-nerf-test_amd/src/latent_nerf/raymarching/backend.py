@@ -128,6 +128,12 @@ _SIGNATURES = {
     "lnerf_mip_build_backward": [_P, _I, _I, _I, _P, _P],
     "lnerf_texture_mip_forward": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P],
     "lnerf_texture_mip_backward": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P],
+    "lnerf_mipcov_weights": [_P, _I, _I, _P, _P],
+    "lnerf_mipcov_pull": [_P, _P, _P, _I, _I, _I, _P, _P],
+    "lnerf_mipcov_pull_backward": [_P, _P, _P, _I, _I, _I, _P, _P],
+    "lnerf_mipcov_push": [_P, _P, _P, _P, _I, _I, _I, _P, _P],
+    "lnerf_texture_mipcov_forward": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P],
+    "lnerf_texture_mipcov_backward": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P],
     "lnerf_adam_step": [_P, _P, _I, _P, _P, _P, _L, _F, _F, _F, _F, _I, _P, _F, _I, _P],
     "lnerf_adam_tick": [_P, _P],
     "lnerf_adam_step_multi": [_I, _P, _P, _P, _P, _P, _P, _F, _F, _F, _I, _P, _F, _I, _P],

@@ -1046,6 +1046,92 @@ def uv_dilate(texture, mask, passes):
     return texture, mask
 
 
+# ------------------------------------------------------------------------------ coverage-weighted pyramids
+def _mip_full_levels(R):
+    """The trailing zero bits of R: every level a square texture of side R can have."""
+    return (R & -R).bit_length() - 1 if R > 0 else 0
+
+
+def _mip_texels(R, L):
+    return sum((R >> l) ** 2 for l in range(1, L + 1))
+
+
+def _mipcov_shape(op, texture, weight, L):
+    if not isinstance(weight, torch.Tensor) or weight.dim() != 2 or weight.shape[0] != weight.shape[1]:
+        raise ValueError("%s: weight must be [R,R]" % op)
+    R = int(weight.shape[0])
+    if texture is not None and (not isinstance(texture, torch.Tensor) or texture.dim() != 3
+                                or tuple(texture.shape[1:]) != (R, R)):
+        raise ValueError("%s: texture must be [C,R,R] with the weight's R = %d" % (op, R))
+    L = _mip_full_levels(R) if L is None else int(L)
+    if L < 0 or L > _mip_full_levels(R):
+        raise ValueError("%s: L = %d outside [0, %d], the levels a side of %d allows" % (op, L, _mip_full_levels(R), R))
+    return R, L
+
+
+def mipcov_weights(weight, L=None):
+    """weight [R,R] f32 in [0,1] -> the weights of levels 1..L packed [S] (lnerf_mipcov_weights; None when L = 0).
+    L = None: every level the side allows."""
+    R, L = _mipcov_shape("mipcov_weights", None, weight, L)
+    if L == 0:
+        return None
+    wpyr = torch.empty(_mip_texels(R, L), device=weight.device)
+    _b.call("lnerf_mipcov_weights", _chk(weight, "weight"), R, L, _p(wpyr), _stream())
+    return wpyr
+
+
+def mipcov_pull(texture, weight, wpyr, L=None):
+    """texture [C,R,R] -> the coverage-weighted means of levels 1..L packed [C,S] (lnerf_mipcov_pull; None when L = 0)."""
+    R, L = _mipcov_shape("mipcov_pull", texture, weight, L)
+    if L == 0:
+        return None
+    C = int(texture.shape[0])
+    pyr = torch.empty(C, _mip_texels(R, L), device=texture.device)
+    _b.call("lnerf_mipcov_pull", _chk(texture, "texture"), _chk(weight, "weight"), _chk(wpyr, "wpyr"), C, R, L, _p(pyr),
+            _stream())
+    return pyr
+
+
+def mipcov_pull_backward(dpyr, weight, wpyr, dtexture, L=None):
+    """Folds the gradient pyramid dpyr [C,S] (which it changes) into dtexture [C,R,R], which it adds to
+    (lnerf_mipcov_pull_backward).  Returns dtexture."""
+    R, L = _mipcov_shape("mipcov_pull_backward", dtexture, weight, L)
+    _b.call("lnerf_mipcov_pull_backward", _chk(dpyr, "dpyr", allow_none=L == 0), _chk(weight, "weight"),
+            _chk(wpyr, "wpyr", allow_none=L == 0), int(dtexture.shape[0]), R, L, _chk(dtexture, "dtexture"), _stream())
+    return dtexture
+
+
+def mipcov_push(texture, weight, wpyr, pyr, L=None):
+    """The push of the pull-push fill, in place over texture [C,R,R] and the pulled pyr [C,S] (lnerf_mipcov_push).
+    -> (texture, filled [R,R] uint8: 1 where a texel with weight != 1 was given a value)."""
+    R, L = _mipcov_shape("mipcov_push", texture, weight, L)
+    filled = torch.empty(R, R, device=texture.device, dtype=torch.uint8)
+    _b.call("lnerf_mipcov_push", _chk(texture, "texture"), _chk(weight, "weight"), _chk(wpyr, "wpyr", allow_none=L == 0),
+            _chk(pyr, "pyr", allow_none=L == 0), int(texture.shape[0]), R, L, _p(filled), _stream())
+    return texture, filled
+
+
+def pull_push_fill(texture, weight):
+    """Fill the texels of texture [C,R,R] that `weight` [R,R] (f32 in [0,1]; 1 = known) does not cover from the ones it
+    does: the coverage-weighted pyramid pulled up to a single texel and pushed back down (include/lnerf_hip.h), so that
+    one known texel anywhere fills the whole texture.  A side that is not a power of two is padded to the next one with
+    weight 0 for the fill and cropped again: the padding adds no value, it only lets the pyramid reach one texel.
+    Texels of weight 1 keep their bits.  -> (a new filled texture, filled [R,R] uint8)."""
+    R, _ = _mipcov_shape("pull_push_fill", texture, weight, None)
+    side = 1 << max(R - 1, 0).bit_length()
+    weight = weight.to(torch.float32)
+    out = texture.to(torch.float32)
+    if side != R:
+        weight = torch.nn.functional.pad(weight, (0, side - R, 0, side - R))
+        out = torch.nn.functional.pad(out, (0, side - R, 0, side - R))
+    weight, out = weight.contiguous(), out.clone().contiguous()
+    wpyr = mipcov_weights(weight)
+    out, filled = mipcov_push(out, weight, wpyr, mipcov_pull(out, weight, wpyr))
+    if side != R:
+        out, filled = out[:, :R, :R].contiguous(), filled[:R, :R].contiguous()
+    return out, filled
+
+
 # ------------------------------------------------------------------------------ view projection
 GOLDEN_ANGLE = math.pi * (3.0 - math.sqrt(5.0))
 

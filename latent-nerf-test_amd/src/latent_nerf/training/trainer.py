@@ -667,7 +667,9 @@ class Trainer:
                                          min_component_faces=int(getattr(self.cfg.log, "mesh_min_component_faces", 0)),
                                          min_component_diameter=float(getattr(self.cfg.log, "mesh_min_component_diameter", 0.0)),
                                          keep_largest=int(getattr(self.cfg.log, "mesh_keep_largest", 0)),
-                                         smooth_iterations=int(getattr(self.cfg.log, "mesh_smooth_iterations", 0)))
+                                         smooth_iterations=int(getattr(self.cfg.log, "mesh_smooth_iterations", 0)),
+                                         fill=getattr(self.cfg.log, "mesh_texture_fill", "dilate"),
+                                         unseen=getattr(self.cfg.log, "mesh_bake_unseen", "fallback"))
             self.log("exported %s (%d vertices, %d triangles; %d before decimation; iso %.4g)"
                      % (mesh["path"], mesh["verts"].shape[0], mesh["faces"].shape[0], mesh["faces_before"], mesh["iso"]))
             if mesh["components"] is not None:

@@ -14,6 +14,8 @@ from ... import config_cli as _cli
 
 INTERPOLATION_MODES = ("nearest", "bilinear", "bicubic", "mipmap")
 UV_ATLASES = ("triangle", "charts")
+TEXTURE_FILLS = ("dilate", "pullpush")   # log.mesh_texture_fill (src/view_bake.py TEXTURE_FILLS)
+BAKE_UNSEEN = ("fallback", "inpaint")    # log.mesh_bake_unseen (src/view_bake.py BAKE_UNSEEN)
 
 RenderConfig = _cli.make_section("RenderConfig", (
     ("train_grid_size", int, 64, "side of the square training render, in latent pixels"),
@@ -38,6 +40,10 @@ GuideConfig = _cli.make_section("GuideConfig", (
                                                    "pyramid, the level from each pixel's footprint in the texture)"),
     ("texture_max_mip_level", int, -1, "mipmap: coarsest level used; -1 = every level the texture's side allows"),
     ("texture_lod_bias", float, 0.0, "mipmap: added to the level log2(pixel footprint in texels); > 0 blurs"),
+    ("texture_mip_coverage", bool, False, "mipmap: coverage-weighted pyramid -- the texels no face covers stay out of "
+                                          "every level and receive no gradient"),
+    ("texture_coverage_ring", int, 1, "texture_mip_coverage: rounds the covered texels are grown by (a bilinear tap "
+                                      "reads one texel beyond a chart's edge)"),
     ("init_texture", Optional[str], None, "latent texture [4,R,R] or [1,4,R,R] (torch.save) to start from, e.g. the "
                                           "latent_texture.pt of the NeRF's textured mesh export; R = texture_resolution"),
     ("uv_atlas", str, "triangle", "atlas built for a mesh without UVs when xatlas is missing: " + " | ".join(UV_ATLASES)),
@@ -62,6 +68,11 @@ LogConfig = _cli.make_section("LogConfig", (
     ("save_mesh", bool, True, "export the textured mesh with the final evaluation"),
     ("mesh_bake_views", int, 0, "with save_mesh: > 0 projects albedo.png from this many evaluation renders of the decoded "
                                 "mesh instead of decoding the atlas as one picture (kept as albedo_preview.png)"),
+    ("mesh_texture_fill", str, "dilate", "texels of the exported texture outside the charts: " + " | ".join(TEXTURE_FILLS)
+                                         + " (dilate: the gutter only; pullpush: the whole atlas, so that mip levels "
+                                         "built from it do not seam)"),
+    ("mesh_bake_unseen", str, "fallback", "with mesh_bake_views: covered texels no view sees: " + " | ".join(BAKE_UNSEEN)
+                                          + " (fallback: the decoded atlas; inpaint: filled from the seen texels)"),
     ("max_keep_ckpts", int, 2, "older checkpoints are deleted beyond this count"),
 ), namespace={"exp_dir": property(lambda self: Path(self.exp_root) / self.exp_name)}, doc="logging and saving")
 
@@ -91,6 +102,17 @@ class TrainConfig:
                              % self.guide.texture_max_mip_level)
         if not math.isfinite(self.guide.texture_lod_bias):
             raise ValueError("guide.texture_lod_bias must be finite (got %s)" % self.guide.texture_lod_bias)
+        if self.guide.texture_mip_coverage and self.guide.texture_interpolation_mode != "mipmap":
+            raise ValueError("guide.texture_mip_coverage needs guide.texture_interpolation_mode mipmap (got %s)"
+                             % self.guide.texture_interpolation_mode)
+        if self.guide.texture_coverage_ring < 0:
+            raise ValueError("guide.texture_coverage_ring must be >= 0 (got %s)" % self.guide.texture_coverage_ring)
+        if self.log.mesh_texture_fill not in TEXTURE_FILLS:
+            raise ValueError("log.mesh_texture_fill must be one of %s, not %r"
+                             % (" | ".join(TEXTURE_FILLS), self.log.mesh_texture_fill))
+        if self.log.mesh_bake_unseen not in BAKE_UNSEEN:
+            raise ValueError("log.mesh_bake_unseen must be one of %s, not %r"
+                             % (" | ".join(BAKE_UNSEEN), self.log.mesh_bake_unseen))
         if self.guide.uv_atlas not in UV_ATLASES:
             raise ValueError("guide.uv_atlas must be one of %s, not %r" % (" | ".join(UV_ATLASES), self.guide.uv_atlas))
         if self.log.mesh_bake_views < 0:

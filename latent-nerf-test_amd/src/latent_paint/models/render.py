@@ -3,13 +3,15 @@ convention (:19-31) and the two render entry points (:34-47, :50-69), with the k
 C-ABI raster kernels (csrc/raster.hip).  `render_views` / `render_views_texture` take B views per call (the fork's
 `render.batch_size`); the single-view methods are their B = 1 case, on the one tile-culled rasteriser.
 `interpolation_mode="mipmap"` is this project's own: the trilinear mip-mapped lookup of csrc/texmip.hip, for renders much
-smaller than their texture."""
+smaller than their texture; with `mip_coverage` its pyramid is the coverage-weighted one of csrc/texcov.hip, which keeps the
+texels no face covers out of every level."""
 import math
 
 import torch
 
 from ...latent_nerf.raymarching import backend as _b
-from ...latent_nerf.raymarching.raymarching import _chk, _p, _stream
+from ...latent_nerf.raymarching.raymarching import (_chk, _p, _stream, mipcov_pull, mipcov_pull_backward, mipcov_weights,
+                                                    uv_dilate, uv_raster)
 
 _MODES = {"nearest": 0, "bilinear": 1, "bicubic": 2}   # lnerf_texture_map_*'s point lookups ("mipmap": _TextureMip)
 
@@ -113,6 +115,43 @@ def mip_lookup_backward(dout, shape, uv, rho, face_idx, L, bias):
     return dtex
 
 
+def mipcov_lookup(tex, pyr, w0, wpyr, uv, rho, face_idx, L, bias):
+    """The normalised trilinear lookup (lnerf_texture_mipcov_forward) -> [P,C]; pyr = mipcov_pull's levels, w0 [R,R] and
+    wpyr [S] the weights of the same levels."""
+    C, R, P = tex.shape[0], tex.shape[1], uv.shape[0]
+    out = torch.empty(P, C, device=tex.device)
+    _b.call("lnerf_texture_mipcov_forward", _chk(uv, "uv"), _chk(rho, "rho"), _p(face_idx), _chk(tex, "texture"), _p(pyr),
+            _chk(w0, "w0"), _p(wpyr), P, C, R, L, float(bias), _p(out), _stream())
+    return out
+
+
+def mipcov_lookup_backward(dout, shape, w0, wpyr, uv, rho, face_idx, L, bias):
+    """dout [P,C] -> the gradient of the [C,R,R] texture: the atomics of lnerf_texture_mipcov_backward into level 0 and a
+    packed gradient pyramid, which lnerf_mipcov_pull_backward then folds into level 0."""
+    C, R = shape
+    dtex = torch.zeros(C, R, R, device=dout.device)
+    dpyr = torch.zeros(C, mip_texels(R, L), device=dout.device) if L > 0 else None
+    _b.call("lnerf_texture_mipcov_backward", _p(uv), _p(rho), _p(face_idx), _chk(dout, "dout"), _chk(w0, "w0"), _p(wpyr),
+            uv.shape[0], C, R, L, float(bias), _p(dtex), _p(dpyr), _stream())
+    return mipcov_pull_backward(dpyr, w0, wpyr, dtex, L)
+
+
+def texture_coverage(verts, faces, face_uv, R, ring=1):
+    """The texels of an R x R texture that belong to the surface -> bool [R,R]: the texels whose centre a face covers
+    (uv_raster's texel_face >= 0), grown by `ring` rounds of uv_dilate's mask.  A bilinear tap reads one texel beyond a
+    chart's edge, so with ring >= 1 those texels count as parameters too.  face_uv [F,3,2]: per-face-vertex UVs."""
+    R = int(R)
+    if R > _b.UV_MAX_RES:
+        raise ValueError("texture_mip_coverage: a texture side of %d is above LNERF_UV_MAX_RES = %d, the largest atlas "
+                         "uv_raster covers" % (R, _b.UV_MAX_RES))
+    F = face_uv.shape[0]
+    ft = torch.arange(3 * F, device=face_uv.device, dtype=torch.int32).reshape(F, 3)
+    texel_face, _, _ = uv_raster(verts.float().contiguous(), faces, face_uv.reshape(-1, 2).float().contiguous(), ft, R)
+    mask = (texel_face >= 0).to(torch.uint8) * 2
+    uv_dilate(torch.zeros(1, R, R, device=mask.device), mask, int(ring))
+    return mask > 0
+
+
 class _TextureMip(torch.autograd.Function):
     """Footprint, pyramid and trilinear lookup of one render call; the backward returns the texture's gradient."""
 
@@ -137,16 +176,47 @@ class _TextureMip(torch.autograd.Function):
         return (dtex[None],) + (None,) * 8
 
 
+class _TextureMipCoverage(torch.autograd.Function):
+    """_TextureMip on the coverage-weighted pyramid: w0 [R,R] f32 and wpyr [S] are the weights of the texture's side."""
+
+    @staticmethod
+    def forward(ctx, tex, uv, face_idx, face_xy, face_z, face_uv, dims, L, lod_bias, w0, wpyr):
+        if tex.dim() != 4 or tex.shape[0] != 1 or tex.shape[2] != tex.shape[3]:
+            raise ValueError("texture_map: texture must be [1,C,R,R] (got %s)" % (tuple(tex.shape),))
+        B, H, W = dims
+        t = tex[0].contiguous()
+        rho = uv_footprint(face_idx, face_xy, face_z, face_uv, B, H, W)
+        out = mipcov_lookup(t, mipcov_pull(t, w0, wpyr, L), w0, wpyr, uv, rho, face_idx, L, lod_bias)
+        ctx.save_for_backward(uv, rho, face_idx, w0, wpyr)
+        ctx.meta = (t.shape[0], t.shape[1], L, lod_bias)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        uv, rho, face_idx, w0, wpyr = ctx.saved_tensors
+        C, R, L, bias = ctx.meta
+        dtex = mipcov_lookup_backward(dout.contiguous(), (C, R), w0, wpyr, uv, rho, face_idx, L, bias)
+        return (dtex[None],) + (None,) * 10
+
+
 class Renderer:
-    def __init__(self, device, dim=(224, 224), interpolation_mode="nearest", max_mip_level=-1, lod_bias=0.0):
+    def __init__(self, device, dim=(224, 224), interpolation_mode="nearest", max_mip_level=-1, lod_bias=0.0,
+                 mip_coverage=False, coverage_ring=1):
         assert interpolation_mode in ["nearest", "bilinear", "bicubic", "mipmap"], \
             "no interpolation mode %s" % interpolation_mode
         if not math.isfinite(lod_bias):
             raise ValueError("Renderer: lod_bias must be finite (got %r)" % (lod_bias,))
+        if mip_coverage and interpolation_mode != "mipmap":
+            raise ValueError("Renderer: mip_coverage needs interpolation_mode mipmap (got %s)" % interpolation_mode)
+        if int(coverage_ring) < 0:
+            raise ValueError("Renderer: coverage_ring must be >= 0 (got %r)" % (coverage_ring,))
         self.device = device
         self.interpolation_mode = interpolation_mode
         self.max_mip_level = int(max_mip_level)        # "mipmap" only: < 0 = every level the texture's side allows
         self.lod_bias = float(lod_bias)                # "mipmap" only: added to the level log2(footprint in texels)
+        self.mip_coverage = bool(mip_coverage)         # "mipmap" only: the coverage-weighted pyramid (csrc/texcov.hip)
+        self.coverage_ring = int(coverage_ring)        # ... rounds the covered texels are grown by (the bilinear taps' reach)
+        self._coverage = {}                            # (side, levels, UV layout) -> (w0 [R,R] f32, wpyr [S])
         self.fov = math.pi / 3                         # kal.render.camera.generate_perspective_projection(np.pi / 3)
         self.dim = dim
         self.background = torch.ones(dim).to(device).float()
@@ -201,6 +271,15 @@ class Renderer:
                 _stream())
         return face_idx, bary, B, H, W, face_xy, face_z
 
+    def coverage_weights(self, verts, faces, face_uv, R, L):
+        """(w0 [R,R] f32 of 0 / 1, wpyr [S]) of one UV layout at one texture side, computed once: render_test passes the
+        decoded texture, whose side is not the trained one."""
+        key = (int(R), int(L), face_uv.data_ptr(), tuple(face_uv.shape))
+        if key not in self._coverage:
+            w0 = texture_coverage(verts.to(self.device), faces.to(self.device), face_uv, R, self.coverage_ring).float()
+            self._coverage[key] = (w0.contiguous(), mipcov_weights(w0, L))
+        return self._coverage[key]
+
     def _rasterize(self, verts, faces, elev, azim, radius, look_at_height, dims):
         face_idx, bary, _, H, W = self._rasterize_views(verts, faces, [elev], [azim], [radius], look_at_height, dims)
         return face_idx, bary, H, W
@@ -224,7 +303,13 @@ class Renderer:
         face_uv = uv_face_attr[0].detach().contiguous()
         with torch.no_grad():                          # uv_features.detach() in the reference (:61)
             uv = _InterpAttr.apply(face_uv, face_idx, bary).contiguous()
-        if self.interpolation_mode == "mipmap":
+        if self.interpolation_mode == "mipmap" and self.mip_coverage:
+            R = texture_map.shape[-1]
+            L = mip_levels(R, self.max_mip_level)      # per call, as _TextureMip
+            w0, wpyr = self.coverage_weights(verts, faces, face_uv, R, L)
+            image = _TextureMipCoverage.apply(texture_map, uv, face_idx, face_xy, face_z, face_uv, (B, H, W), L,
+                                              self.lod_bias, w0, wpyr)
+        elif self.interpolation_mode == "mipmap":
             image = _TextureMip.apply(texture_map, uv, face_idx, face_xy, face_z, face_uv, (B, H, W), self.max_mip_level,
                                       self.lod_bias)
         else:

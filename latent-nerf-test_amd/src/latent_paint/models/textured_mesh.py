@@ -18,10 +18,10 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ... import view_bake
-from ...latent_nerf.raymarching.raymarching import bake_view_poses
+from ...latent_nerf.raymarching.raymarching import bake_view_poses, pull_push_fill
 from ...uv_atlas import chart_atlas, check_atlas_choice, per_triangle_atlas
 from .mesh import Mesh
-from .render import Renderer
+from .render import Renderer, texture_coverage
 
 # latent -> RGB linear estimate (rows = latent channels), the table of textured_mesh.py:34-40
 LATENT_RGB_ROWS = ((0.298, 0.207, 0.208), (0.187, 0.286, 0.173), (-0.158, 0.189, 0.264), (-0.184, -0.271, -0.473))
@@ -61,7 +61,9 @@ class TexturedMeshModel(nn.Module):
         self.renderer = Renderer(device=self.device, dim=(render_grid_size, render_grid_size),
                                  interpolation_mode=opt.guide.texture_interpolation_mode,
                                  max_mip_level=getattr(opt.guide, "texture_max_mip_level", -1),
-                                 lod_bias=getattr(opt.guide, "texture_lod_bias", 0.0))
+                                 lod_bias=getattr(opt.guide, "texture_lod_bias", 0.0),
+                                 mip_coverage=getattr(opt.guide, "texture_mip_coverage", False),
+                                 coverage_ring=getattr(opt.guide, "texture_coverage_ring", 1))
         self.env_sphere, self.mesh = self.init_meshes()
         self.background_sphere_colors, self.texture_img, self.texture_img_rgb_finetune = self.init_paint()
         self.vt, self.ft = self.init_texture_map()
@@ -201,17 +203,25 @@ class TexturedMeshModel(nn.Module):
 
     # ------------------------------------------------------------------ export
     @torch.no_grad()
-    def export_mesh(self, path, guidance=None, bake_views=0, view_size=None):
+    def export_mesh(self, path, guidance=None, bake_views=0, view_size=None, fill="dilate", unseen="fallback"):
         """Writes `albedo.png` (the decoded texture), `mesh.obj` (v / vt / f v/vt) and `mesh.mtl` into `path`.
         bake_views = K > 0: the decoder sees the whole atlas as one picture, so chart borders and unrelated neighbouring
         charts are decoded together; instead `albedo.png` is projected from K evaluation renders of the decoded mesh
         (render_test at `view_size`, default render.eval_grid_size; the directions of raymarching.bake_view_poses at the
         evaluation radius) with view_bake.bake_views, the decoded atlas filling the texels no view sees and kept as
-        `albedo_preview.png`.  -> dict(rgb [3,R,R]; K > 0: + view_rgb, view_weight, view_count, mask)."""
+        `albedo_preview.png`.
+        fill = "pullpush": the texels of the decoded atlas that no face covers (raymarching.uv_raster at the decoded
+        side) are filled from the covered ones over the whole atlas (raymarching.pull_push_fill; the covered texels keep
+        their bits), and so is the view bake's image beyond its gutter -- mip levels built from the files then do not
+        seam at chart borders.  "dilate" leaves every file byte for byte what it was.  unseen = "inpaint" (K > 0):
+        covered texels no view sees are filled from the seen ones instead of taking the decoded atlas' colour.
+        -> dict(rgb [3,R,R]; K > 0: + view_rgb, view_weight, view_count, mask)."""
         from PIL import Image
         bake_views = int(bake_views)
         if bake_views < 0:
             raise ValueError("export_mesh: bake_views must be >= 0 (got %d)" % bake_views)
+        view_bake.check_choice(fill, view_bake.TEXTURE_FILLS, "export_mesh: fill")
+        view_bake.check_choice(unseen, view_bake.BAKE_UNSEEN, "export_mesh: unseen")
         path = Path(path)
         path.mkdir(parents=True, exist_ok=True)
         if self.latent_mode:
@@ -221,11 +231,14 @@ class TexturedMeshModel(nn.Module):
             rgb = decode_with(guidance, self.texture_img)
         else:
             rgb = self.texture_img_rgb_finetune
+        if fill == "pullpush":
+            covered = texture_coverage(self.mesh.vertices, self.mesh.faces, self.face_attributes[0], rgb.shape[-1], ring=0)
+            rgb = pull_push_fill(rgb[0].float(), covered.float())[0][None]
         albedo = (rgb[0].permute(1, 2, 0).clamp(0, 1).cpu().numpy() * 255).astype(np.uint8)
         result = {"rgb": rgb[0]}
         if bake_views > 0:
             Image.fromarray(albedo).save(path / "albedo_preview.png")
-            result.update(self._bake_rendered_views(rgb, bake_views, view_size))
+            result.update(self._bake_rendered_views(rgb, bake_views, view_size, fill, unseen))
             # (the projected image is rounded to 8 bits, as the NeRF exporter's; the preview above keeps the upstream
             # exporter's truncation, so that it and the K = 0 file stay byte for byte what they were)
             albedo = view_bake.to_uint8(result["view_rgb"])
@@ -233,7 +246,7 @@ class TexturedMeshModel(nn.Module):
         self._write_obj(path)
         return result
 
-    def _bake_rendered_views(self, rgb, K, view_size):
+    def _bake_rendered_views(self, rgb, K, view_size, fill="dilate", unseen="fallback"):
         """export_mesh's view bake over the decoded atlas `rgb` [1,3,R,R]: K renders of it on the mesh, projected back."""
         side = int(view_size or self.opt.render.eval_grid_size)
         poses = bake_view_poses(K)
@@ -243,7 +256,7 @@ class TexturedMeshModel(nn.Module):
         images = self.render_test(view["elev"], view["azim"], view["radius"], decode_func=lambda _t: rgb,
                                   dims=(side, side))["image"]
         baked = view_bake.bake_views(self.mesh.vertices, self.mesh.faces, self.vt, self.ft, images.clamp(0, 1), cams,
-                                     rgb.shape[-1], fallback=rgb[0].float().clamp(0, 1))
+                                     rgb.shape[-1], fallback=rgb[0].float().clamp(0, 1), fill=fill, unseen=unseen)
         return {"view_rgb": baked["rgb"], "view_weight": baked["view_weight"], "view_count": baked["view_count"],
                 "mask": baked["mask"]}
 

@@ -182,7 +182,9 @@ class Trainer:
         if self.cfg.log.save_mesh:
             target = make_path(self.exp_path / "mesh")
             self.mesh_model.export_mesh(target, guidance=self.diffusion,
-                                        bake_views=int(getattr(self.cfg.log, "mesh_bake_views", 0)))
+                                        bake_views=int(getattr(self.cfg.log, "mesh_bake_views", 0)),
+                                        fill=getattr(self.cfg.log, "mesh_texture_fill", "dilate"),
+                                        unseen=getattr(self.cfg.log, "mesh_bake_unseen", "fallback"))
             self.log("saved mesh to %s" % target)
 
     @torch.no_grad()

@@ -612,17 +612,19 @@ int lnerf_texture_mip_backward(const float *uv, const float *rho, const int32_t 
                                lnerf_stream_t stream);
 
 /* ---- Coverage-weighted texture pyramids (`guide.texture_mip_coverage`, the pull-push fill of the exports;
- * csrc/texcov.hip).  Additive to ABI 7; the plain pyramid above is unchanged.  A pyramid whose level l is the
- * coverage-weighted mean of level l - 1, the weights carried along, read normalised (the lookup) or pushed back down into
- * the texels no surface point owns (the fill).  f32, every operation rounded on its own.  Shapes and packing are the
- * plain pyramid's: texture [C,R,R], R divisible by 2^L, values of levels 1..L packed [C,S], their weights [S].
+ * csrc/texmip.hip: the plain pyramid's kernels, instantiated with weights).  Additive to ABI 7; the plain pyramid above
+ * is unchanged.  A pyramid whose level l is the coverage-weighted mean of level l - 1, the weights carried along, read
+ * normalised (the lookup) or pushed back down into the texels no surface point owns (the fill).  f32, every operation
+ * rounded on its own.  Shapes, packing, argument rules, lambda, l0, t and the taps are the plain pyramid's: texture
+ * [C,R,R], R divisible by 2^L, values of levels 1..L packed [C,S], their weights [S].
  *
  * Weights.  w0 [R,R] in [0,1] (the callers pass 0 or 1).  With a, b, c, d the four children of a level-l texel (i, j) in
  *   the order (2i, 2j), (2i, 2j+1), (2i+1, 2j), (2i+1, 2j+1) of level l - 1:
  *     s   = (wa + wb) + (wc + wd)
  *     w_l = s * 0.25
  *   For 0/1 weights at level 0 every w_l is a multiple of 4^-l not above 1: exact in f32 (up to L = 11).
- * lnerf_mipcov_weights: w0 -> wpyr, one launch per level.  L = 0 launches nothing (wpyr may be NULL, here and below).
+ * lnerf_mipcov_weights: w0 -> wpyr = lnerf_mip_build of the one-channel texture w0, bit for bit.  L = 0 launches nothing
+ *   (wpyr may be NULL, here and below).
  *
  * lnerf_mipcov_pull: texture, w0, wpyr -> pyramid, one launch per level, t the values of level l - 1:
  *     v_l = s > 0 ? ((wa * ta + wb * tb) + (wc * tc + wd * td)) / s : 0
@@ -652,9 +654,9 @@ int lnerf_texture_mip_backward(const float *uv, const float *rho, const int32_t 
  *   filled [R,R] uint8 (may be NULL): 1 where w0 != 1 and the texel is reached, i.e. where level 0 was written; else 0.
  *   Texels with w0 == 1 are not written at all.  With L = 0 nothing is pushed (filled = 0 everywhere).
  *
- * lnerf_texture_mipcov_forward / _backward: lnerf_texture_mip_* with the weights.  lambda, l0, t and the taps
- *   (i_k, b_k), k = 00, 01, 10, 11, are exactly those of lnerf_texture_mip_forward; V = `pyramid` from lnerf_mipcov_pull
- *   (level 0 = texture), W = w0 / wpyr.  Per level read, in the order of the plain mode's sum:
+ * lnerf_texture_mipcov_forward / _backward: lnerf_texture_mip_* with the weights, (i_k, b_k), k = 00, 01, 10, 11, its
+ *   taps; V = `pyramid` from lnerf_mipcov_pull (level 0 = texture), W = w0 / wpyr.  Per level read, in the order of the
+ *   plain mode's sum:
  *     n(l) = (b00 * W00) * V00 + (b01 * W01) * V01 + (b10 * W10) * V10 + (b11 * W11) * V11
  *     d(l) = (b00 * W00) + (b01 * W01) + (b10 * W10) + (b11 * W11)
  *     N = t == 0 ? n(l0) : (1 - t) * n(l0) + t * n(l0 + 1);   D likewise from d

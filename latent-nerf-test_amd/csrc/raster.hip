@@ -326,17 +326,9 @@ k_texture_map(const float *__restrict__ uv, const int32_t *__restrict__ face_idx
         if (BWD) atomicAdd(&tc[yi * R + xi], out_or_dout[t]);
         else out_or_dout[t] = tc[yi * R + xi];
     } else if (mode == 1) {
-        const float xf = floorf(x), yf = floorf(y);
-        const int x0 = (int)xf, y0 = (int)yf, x1 = min(x0 + 1, R - 1), y1 = min(y0 + 1, R - 1);
-        const float ax = x - xf, ay = y - yf;
-        const float w00 = (1.f - ax) * (1.f - ay), w01 = ax * (1.f - ay), w10 = (1.f - ax) * ay, w11 = ax * ay;
-        if (BWD) {
-            const float g = out_or_dout[t];
-            atomicAdd(&tc[y0 * R + x0], w00 * g); atomicAdd(&tc[y0 * R + x1], w01 * g);
-            atomicAdd(&tc[y1 * R + x0], w10 * g); atomicAdd(&tc[y1 * R + x1], w11 * g);
-        } else {
-            out_or_dout[t] = w00 * tc[y0 * R + x0] + w01 * tc[y0 * R + x1] + w10 * tc[y1 * R + x0] + w11 * tc[y1 * R + x1];
-        }
+        const BilTaps b = bil_taps(uv[p * 2], uv[p * 2 + 1], R);   // the taps the mip-mapped lookup reads per level
+        if (BWD) bil_add(tc, b, out_or_dout[t]);
+        else out_or_dout[t] = bil_read(tc, b);
     } else {
         const float xf = floorf(x), yf = floorf(y);
         const int xb = (int)xf - 1, yb = (int)yf - 1;

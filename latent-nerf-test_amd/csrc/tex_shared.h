@@ -1,5 +1,5 @@
-// Texel coordinates of a texture lookup, shared by the point lookups (raster.hip) and the mip-mapped ones (texmip.hip,
-// texcov.hip), and what the two pyramids have in common.
+// Texel coordinates and bilinear taps of a texture lookup, shared by the point lookups (raster.hip) and the mip-mapped
+// ones (texmip.hip), and the pyramid's packing and shape check.
 #pragma once
 #include "common.h"
 
@@ -20,7 +20,7 @@ __device__ __forceinline__ void tex_coords(float u, float v, int R, bool clip, f
     }
 }
 
-// ---- the mip pyramid's packing, taps and shape check, shared by texmip.hip and texcov.hip
+// ---- the mip pyramid's packing, taps and shape check
 // texels of levels 1 .. l - 1 of one channel in the packed buffer: sum_m (R >> m)^2 = (R^2 - (R >> (l-1))^2) / 3, exact
 // because R is divisible by 2^L
 __host__ __device__ __forceinline__ int64_t mip_offset(int R, int l) {
@@ -29,7 +29,7 @@ __host__ __device__ __forceinline__ int64_t mip_offset(int R, int l) {
 }
 static int64_t mip_texels(int R, int L) { return L > 0 ? mip_offset(R, L + 1) : 0; }
 
-// k_texture_map's bilinear lookup (raster.hip, mode 1) on one level: the same coordinates, taps and weights
+// the bilinear lookup on one level of side R: k_texture_map's mode 1 (raster.hip) and every level k_texture_mip reads
 struct BilTaps {
     int64_t i00, i01, i10, i11;
     float w00, w01, w10, w11;

@@ -1046,65 +1046,96 @@ def uv_dilate(texture, mask, passes):
     return texture, mask
 
 
-# ------------------------------------------------------------------------------ coverage-weighted pyramids
-def _mip_full_levels(R):
-    """The trailing zero bits of R: every level a square texture of side R can have."""
-    return (R & -R).bit_length() - 1 if R > 0 else 0
+# ------------------------------------------------------------------------------ texture pyramids, plain and weighted
+def mip_levels(R, max_mip_level=-1):
+    """Levels 1..L of an R x R texture: L_full = the trailing zero bits of R (a level's side may be odd only at the last
+    level), capped by `max_mip_level` when that is >= 0.  R = 1 or odd R gives 0: plain bilinear."""
+    R = int(R)
+    full = (R & -R).bit_length() - 1 if R > 0 else 0
+    return full if max_mip_level < 0 else min(int(max_mip_level), full)
 
 
-def _mip_texels(R, L):
+def mip_texels(R, L):
+    """Texels per channel of the packed levels 1..L."""
     return sum((R >> l) ** 2 for l in range(1, L + 1))
 
 
-def _mipcov_shape(op, texture, weight, L):
-    if not isinstance(weight, torch.Tensor) or weight.dim() != 2 or weight.shape[0] != weight.shape[1]:
+def _pyramid_shape(op, texture, weight, L):
+    """(R, L) of a call on texture [C,R,R] (None: the weights alone) and weight [R,R] (None: the plain pyramid)."""
+    square = lambda t, dim: isinstance(t, torch.Tensor) and t.dim() == dim and t.shape[-2] == t.shape[-1]
+    if weight is not None and not square(weight, 2):
         raise ValueError("%s: weight must be [R,R]" % op)
-    R = int(weight.shape[0])
-    if texture is not None and (not isinstance(texture, torch.Tensor) or texture.dim() != 3
-                                or tuple(texture.shape[1:]) != (R, R)):
-        raise ValueError("%s: texture must be [C,R,R] with the weight's R = %d" % (op, R))
-    L = _mip_full_levels(R) if L is None else int(L)
-    if L < 0 or L > _mip_full_levels(R):
-        raise ValueError("%s: L = %d outside [0, %d], the levels a side of %d allows" % (op, L, _mip_full_levels(R), R))
+    if texture is not None and not (square(texture, 3) and (weight is None or texture.shape[-1] == weight.shape[-1])):
+        raise ValueError("%s: texture must be [C,R,R]" % op
+                         + ("" if weight is None else " with the weight's R = %d" % weight.shape[-1]))
+    R = int((texture if weight is None else weight).shape[-1])
+    L = mip_levels(R) if L is None else int(L)
+    if L < 0 or L > mip_levels(R):
+        raise ValueError("%s: L = %d outside [0, %d], the levels a side of %d allows" % (op, L, mip_levels(R), R))
     return R, L
+
+
+def pyramid_build(texture, L=None, weight=None, wpyr=None):
+    """texture [C,R,R] -> levels 1..L packed [C,S] (None when L = 0; L = None: every level the side allows): the 2 x 2
+    box averages (lnerf_mip_build) or, given weight [R,R] and its levels wpyr [S], the coverage-weighted means
+    (lnerf_mipcov_pull)."""
+    R, L = _pyramid_shape("mip_build" if weight is None else "mipcov_pull", texture, weight, L)
+    if L == 0:
+        return None
+    C = int(texture.shape[0])
+    pyr = torch.empty(C, mip_texels(R, L), device=texture.device)
+    if weight is None:
+        _b.call("lnerf_mip_build", _chk(texture, "texture"), C, R, L, _p(pyr), _stream())
+    else:
+        _b.call("lnerf_mipcov_pull", _chk(texture, "texture"), _chk(weight, "weight"), _chk(wpyr, "wpyr"), C, R, L,
+                _p(pyr), _stream())
+    return pyr
+
+
+def pyramid_fold(dpyr, dtexture, L=None, weight=None, wpyr=None):
+    """The transpose of pyramid_build: folds the gradient pyramid dpyr [C,S] (which it changes) into dtexture [C,R,R],
+    which it adds to (lnerf_mip_build_backward, or lnerf_mipcov_pull_backward given the weights).  Returns dtexture."""
+    R, L = _pyramid_shape("mip_build_backward" if weight is None else "mipcov_pull_backward", dtexture, weight, L)
+    C = int(dtexture.shape[0])
+    if weight is None:
+        _b.call("lnerf_mip_build_backward", _chk(dpyr, "dpyr", allow_none=L == 0), C, R, L, _chk(dtexture, "dtexture"),
+                _stream())
+    else:
+        _b.call("lnerf_mipcov_pull_backward", _chk(dpyr, "dpyr", allow_none=L == 0), _chk(weight, "weight"),
+                _chk(wpyr, "wpyr", allow_none=L == 0), C, R, L, _chk(dtexture, "dtexture"), _stream())
+    return dtexture
+
+
+def mip_build(tex, L):
+    """tex [C,R,R] -> levels 1..L packed [C,S] (None when L = 0)."""
+    return pyramid_build(tex, L)
 
 
 def mipcov_weights(weight, L=None):
     """weight [R,R] f32 in [0,1] -> the weights of levels 1..L packed [S] (lnerf_mipcov_weights; None when L = 0).
     L = None: every level the side allows."""
-    R, L = _mipcov_shape("mipcov_weights", None, weight, L)
+    R, L = _pyramid_shape("mipcov_weights", None, weight, L)
     if L == 0:
         return None
-    wpyr = torch.empty(_mip_texels(R, L), device=weight.device)
+    wpyr = torch.empty(mip_texels(R, L), device=weight.device)
     _b.call("lnerf_mipcov_weights", _chk(weight, "weight"), R, L, _p(wpyr), _stream())
     return wpyr
 
 
 def mipcov_pull(texture, weight, wpyr, L=None):
-    """texture [C,R,R] -> the coverage-weighted means of levels 1..L packed [C,S] (lnerf_mipcov_pull; None when L = 0)."""
-    R, L = _mipcov_shape("mipcov_pull", texture, weight, L)
-    if L == 0:
-        return None
-    C = int(texture.shape[0])
-    pyr = torch.empty(C, _mip_texels(R, L), device=texture.device)
-    _b.call("lnerf_mipcov_pull", _chk(texture, "texture"), _chk(weight, "weight"), _chk(wpyr, "wpyr"), C, R, L, _p(pyr),
-            _stream())
-    return pyr
+    """texture [C,R,R] -> the coverage-weighted means of levels 1..L packed [C,S] (None when L = 0)."""
+    return pyramid_build(texture, L, weight, wpyr)
 
 
 def mipcov_pull_backward(dpyr, weight, wpyr, dtexture, L=None):
-    """Folds the gradient pyramid dpyr [C,S] (which it changes) into dtexture [C,R,R], which it adds to
-    (lnerf_mipcov_pull_backward).  Returns dtexture."""
-    R, L = _mipcov_shape("mipcov_pull_backward", dtexture, weight, L)
-    _b.call("lnerf_mipcov_pull_backward", _chk(dpyr, "dpyr", allow_none=L == 0), _chk(weight, "weight"),
-            _chk(wpyr, "wpyr", allow_none=L == 0), int(dtexture.shape[0]), R, L, _chk(dtexture, "dtexture"), _stream())
-    return dtexture
+    """Folds dpyr [C,S] (which it changes) into dtexture [C,R,R], which it adds to and returns."""
+    return pyramid_fold(dpyr, dtexture, L, weight, wpyr)
 
 
 def mipcov_push(texture, weight, wpyr, pyr, L=None):
     """The push of the pull-push fill, in place over texture [C,R,R] and the pulled pyr [C,S] (lnerf_mipcov_push).
     -> (texture, filled [R,R] uint8: 1 where a texel with weight != 1 was given a value)."""
-    R, L = _mipcov_shape("mipcov_push", texture, weight, L)
+    R, L = _pyramid_shape("mipcov_push", texture, weight, L)
     filled = torch.empty(R, R, device=texture.device, dtype=torch.uint8)
     _b.call("lnerf_mipcov_push", _chk(texture, "texture"), _chk(weight, "weight"), _chk(wpyr, "wpyr", allow_none=L == 0),
             _chk(pyr, "pyr", allow_none=L == 0), int(texture.shape[0]), R, L, _p(filled), _stream())
@@ -1117,7 +1148,7 @@ def pull_push_fill(texture, weight):
     one known texel anywhere fills the whole texture.  A side that is not a power of two is padded to the next one with
     weight 0 for the fill and cropped again: the padding adds no value, it only lets the pyramid reach one texel.
     Texels of weight 1 keep their bits.  -> (a new filled texture, filled [R,R] uint8)."""
-    R, _ = _mipcov_shape("pull_push_fill", texture, weight, None)
+    R, _ = _pyramid_shape("pull_push_fill", texture, weight, None)
     side = 1 << max(R - 1, 0).bit_length()
     weight = weight.to(torch.float32)
     out = texture.to(torch.float32)

@@ -3,17 +3,24 @@ convention (:19-31) and the two render entry points (:34-47, :50-69), with the k
 C-ABI raster kernels (csrc/raster.hip).  `render_views` / `render_views_texture` take B views per call (the fork's
 `render.batch_size`); the single-view methods are their B = 1 case, on the one tile-culled rasteriser.
 `interpolation_mode="mipmap"` is this project's own: the trilinear mip-mapped lookup of csrc/texmip.hip, for renders much
-smaller than their texture; with `mip_coverage` its pyramid is the coverage-weighted one of csrc/texcov.hip, which keeps the
+smaller than their texture; with `mip_coverage` its pyramid is the coverage-weighted one of the same file, which keeps the
 texels no face covers out of every level."""
 import math
 
 import torch
 
 from ...latent_nerf.raymarching import backend as _b
-from ...latent_nerf.raymarching.raymarching import (_chk, _p, _stream, mipcov_pull, mipcov_pull_backward, mipcov_weights,
-                                                    uv_dilate, uv_raster)
+from ...latent_nerf.raymarching.raymarching import (_chk, _p, _stream, mip_build, mip_levels, mip_texels,  # noqa: F401
+                                                    mipcov_weights, pyramid_build, pyramid_fold, uv_dilate, uv_raster)
 
 _MODES = {"nearest": 0, "bilinear": 1, "bicubic": 2}   # lnerf_texture_map_*'s point lookups ("mipmap": _TextureMip)
+
+
+def _texture_shape(tex):
+    """(C, R) of the one square [1,C,R,R] texture the lookup kernels read."""
+    if tex.dim() != 4 or tex.shape[0] != 1 or tex.shape[2] != tex.shape[3]:
+        raise ValueError("texture_map: texture must be [1,C,R,R] (got %s)" % (tuple(tex.shape),))
+    return tex.shape[1], tex.shape[2]
 
 
 class _InterpAttr(torch.autograd.Function):
@@ -39,10 +46,7 @@ class _InterpAttr(torch.autograd.Function):
 class _TextureMap(torch.autograd.Function):
     @staticmethod
     def forward(ctx, tex, uv, face_idx, mode):
-        if tex.dim() != 4 or tex.shape[0] != 1 or tex.shape[2] != tex.shape[3]:
-            # the kernels read one square [C,R,R] texture
-            raise ValueError("texture_map: texture must be [1,C,R,R] (got %s)" % (tuple(tex.shape),))
-        C, R = tex.shape[1], tex.shape[2]
+        C, R = _texture_shape(tex)
         P = uv.shape[0]
         tex = tex.contiguous()
         out = torch.empty(P, C, device=tex.device)
@@ -62,19 +66,6 @@ class _TextureMap(torch.autograd.Function):
         return dtex, None, None, None
 
 
-def mip_levels(R, max_mip_level=-1):
-    """Levels 1..L of an R x R texture: L_full = the trailing zero bits of R (a level's side may be odd only at the last
-    level), capped by `max_mip_level` when that is >= 0.  R = 1 or odd R gives 0: plain bilinear."""
-    R = int(R)
-    full = (R & -R).bit_length() - 1 if R > 0 else 0
-    return full if max_mip_level < 0 else min(int(max_mip_level), full)
-
-
-def mip_texels(R, L):
-    """Texels per channel of the packed levels 1..L."""
-    return sum((R >> l) ** 2 for l in range(1, L + 1))
-
-
 def uv_footprint(face_idx, face_xy, face_z, face_uv, B, H, W):
     """rho [B*H*W]: the longer screen-space UV derivative per one-pixel step, in UV units (lnerf_uv_footprint)."""
     F = face_uv.shape[0]
@@ -84,56 +75,33 @@ def uv_footprint(face_idx, face_xy, face_z, face_uv, B, H, W):
     return rho
 
 
-def mip_build(tex, L):
-    """tex [C,R,R] -> levels 1..L packed [C,S] (None when L = 0)."""
-    C, R = tex.shape[0], tex.shape[1]
-    if L == 0:
-        return None
-    pyr = torch.empty(C, mip_texels(R, L), device=tex.device)
-    _b.call("lnerf_mip_build", _chk(tex, "texture"), C, R, L, _p(pyr), _stream())
-    return pyr
-
-
-def mip_lookup(tex, pyr, uv, rho, face_idx, L, bias):
-    """The trilinear lookup (lnerf_texture_mip_forward) -> [P,C]."""
+def mip_lookup(tex, pyr, uv, rho, face_idx, L, bias, w0=None, wpyr=None):
+    """The trilinear lookup -> [P,C]: lnerf_texture_mip_forward on mip_build's levels, or, given the weights w0 [R,R]
+    and wpyr [S], the normalised lnerf_texture_mipcov_forward on mipcov_pull's."""
     C, R, P = tex.shape[0], tex.shape[1], uv.shape[0]
     out = torch.empty(P, C, device=tex.device)
-    _b.call("lnerf_texture_mip_forward", _chk(uv, "uv"), _chk(rho, "rho"), _p(face_idx), _chk(tex, "texture"), _p(pyr), P,
-            C, R, L, float(bias), _p(out), _stream())
+    head = (_chk(uv, "uv"), _chk(rho, "rho"), _p(face_idx), _chk(tex, "texture"), _p(pyr))
+    tail = (P, C, R, L, float(bias), _p(out), _stream())
+    if w0 is None:
+        _b.call("lnerf_texture_mip_forward", *head, *tail)
+    else:
+        _b.call("lnerf_texture_mipcov_forward", *head, _chk(w0, "w0"), _p(wpyr), *tail)
     return out
 
 
-def mip_lookup_backward(dout, shape, uv, rho, face_idx, L, bias):
-    """dout [P,C] -> the gradient of the [C,R,R] texture: the atomics of lnerf_texture_mip_backward into level 0 and a
-    packed gradient pyramid, which lnerf_mip_build_backward then folds into level 0."""
+def mip_lookup_backward(dout, shape, uv, rho, face_idx, L, bias, w0=None, wpyr=None):
+    """dout [P,C] -> the gradient of the [C,R,R] texture: the atomics of lnerf_texture_mip_backward (given the weights,
+    lnerf_texture_mipcov_backward) into level 0 and a packed gradient pyramid, which pyramid_fold then folds into level 0."""
     C, R = shape
     dtex = torch.zeros(C, R, R, device=dout.device)
     dpyr = torch.zeros(C, mip_texels(R, L), device=dout.device) if L > 0 else None
-    _b.call("lnerf_texture_mip_backward", _p(uv), _p(rho), _p(face_idx), _chk(dout, "dout"), uv.shape[0], C, R, L,
-            float(bias), _p(dtex), _p(dpyr), _stream())
-    _b.call("lnerf_mip_build_backward", _p(dpyr), C, R, L, _p(dtex), _stream())
-    return dtex
-
-
-def mipcov_lookup(tex, pyr, w0, wpyr, uv, rho, face_idx, L, bias):
-    """The normalised trilinear lookup (lnerf_texture_mipcov_forward) -> [P,C]; pyr = mipcov_pull's levels, w0 [R,R] and
-    wpyr [S] the weights of the same levels."""
-    C, R, P = tex.shape[0], tex.shape[1], uv.shape[0]
-    out = torch.empty(P, C, device=tex.device)
-    _b.call("lnerf_texture_mipcov_forward", _chk(uv, "uv"), _chk(rho, "rho"), _p(face_idx), _chk(tex, "texture"), _p(pyr),
-            _chk(w0, "w0"), _p(wpyr), P, C, R, L, float(bias), _p(out), _stream())
-    return out
-
-
-def mipcov_lookup_backward(dout, shape, w0, wpyr, uv, rho, face_idx, L, bias):
-    """dout [P,C] -> the gradient of the [C,R,R] texture: the atomics of lnerf_texture_mipcov_backward into level 0 and a
-    packed gradient pyramid, which lnerf_mipcov_pull_backward then folds into level 0."""
-    C, R = shape
-    dtex = torch.zeros(C, R, R, device=dout.device)
-    dpyr = torch.zeros(C, mip_texels(R, L), device=dout.device) if L > 0 else None
-    _b.call("lnerf_texture_mipcov_backward", _p(uv), _p(rho), _p(face_idx), _chk(dout, "dout"), _chk(w0, "w0"), _p(wpyr),
-            uv.shape[0], C, R, L, float(bias), _p(dtex), _p(dpyr), _stream())
-    return mipcov_pull_backward(dpyr, w0, wpyr, dtex, L)
+    head = (_p(uv), _p(rho), _p(face_idx), _chk(dout, "dout"))
+    tail = (uv.shape[0], C, R, L, float(bias), _p(dtex), _p(dpyr), _stream())
+    if w0 is None:
+        _b.call("lnerf_texture_mip_backward", *head, *tail)
+    else:
+        _b.call("lnerf_texture_mipcov_backward", *head, _chk(w0, "w0"), _p(wpyr), *tail)
+    return pyramid_fold(dpyr, dtex, L, w0, wpyr)
 
 
 def texture_coverage(verts, faces, face_uv, R, ring=1):
@@ -153,49 +121,25 @@ def texture_coverage(verts, faces, face_uv, R, ring=1):
 
 
 class _TextureMip(torch.autograd.Function):
-    """Footprint, pyramid and trilinear lookup of one render call; the backward returns the texture's gradient."""
+    """Footprint, pyramid and trilinear lookup of one render call; the backward returns the texture's gradient.  With
+    w0 [R,R] f32 and wpyr [S], the weights of the texture's side, the pyramid is the coverage-weighted one."""
 
     @staticmethod
-    def forward(ctx, tex, uv, face_idx, face_xy, face_z, face_uv, dims, max_mip_level, lod_bias):
-        if tex.dim() != 4 or tex.shape[0] != 1 or tex.shape[2] != tex.shape[3]:
-            raise ValueError("texture_map: texture must be [1,C,R,R] (got %s)" % (tuple(tex.shape),))
-        B, H, W = dims
-        t = tex[0].contiguous()
-        L = mip_levels(t.shape[1], max_mip_level)     # per call: render_test passes the decoded, larger texture
-        rho = uv_footprint(face_idx, face_xy, face_z, face_uv, B, H, W)
-        out = mip_lookup(t, mip_build(t, L), uv, rho, face_idx, L, lod_bias)
-        ctx.save_for_backward(uv, rho, face_idx)
-        ctx.meta = (t.shape[0], t.shape[1], L, lod_bias)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        uv, rho, face_idx = ctx.saved_tensors
-        C, R, L, bias = ctx.meta
-        dtex = mip_lookup_backward(dout.contiguous(), (C, R), uv, rho, face_idx, L, bias)
-        return (dtex[None],) + (None,) * 8
-
-
-class _TextureMipCoverage(torch.autograd.Function):
-    """_TextureMip on the coverage-weighted pyramid: w0 [R,R] f32 and wpyr [S] are the weights of the texture's side."""
-
-    @staticmethod
-    def forward(ctx, tex, uv, face_idx, face_xy, face_z, face_uv, dims, L, lod_bias, w0, wpyr):
-        if tex.dim() != 4 or tex.shape[0] != 1 or tex.shape[2] != tex.shape[3]:
-            raise ValueError("texture_map: texture must be [1,C,R,R] (got %s)" % (tuple(tex.shape),))
+    def forward(ctx, tex, uv, face_idx, face_xy, face_z, face_uv, dims, L, lod_bias, w0=None, wpyr=None):
+        C, R = _texture_shape(tex)
         B, H, W = dims
         t = tex[0].contiguous()
         rho = uv_footprint(face_idx, face_xy, face_z, face_uv, B, H, W)
-        out = mipcov_lookup(t, mipcov_pull(t, w0, wpyr, L), w0, wpyr, uv, rho, face_idx, L, lod_bias)
+        out = mip_lookup(t, pyramid_build(t, L, w0, wpyr), uv, rho, face_idx, L, lod_bias, w0, wpyr)
         ctx.save_for_backward(uv, rho, face_idx, w0, wpyr)
-        ctx.meta = (t.shape[0], t.shape[1], L, lod_bias)
+        ctx.meta = (C, R, L, lod_bias)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         uv, rho, face_idx, w0, wpyr = ctx.saved_tensors
         C, R, L, bias = ctx.meta
-        dtex = mipcov_lookup_backward(dout.contiguous(), (C, R), w0, wpyr, uv, rho, face_idx, L, bias)
+        dtex = mip_lookup_backward(dout.contiguous(), (C, R), uv, rho, face_idx, L, bias, w0, wpyr)
         return (dtex[None],) + (None,) * 10
 
 
@@ -214,7 +158,7 @@ class Renderer:
         self.interpolation_mode = interpolation_mode
         self.max_mip_level = int(max_mip_level)        # "mipmap" only: < 0 = every level the texture's side allows
         self.lod_bias = float(lod_bias)                # "mipmap" only: added to the level log2(footprint in texels)
-        self.mip_coverage = bool(mip_coverage)         # "mipmap" only: the coverage-weighted pyramid (csrc/texcov.hip)
+        self.mip_coverage = bool(mip_coverage)         # "mipmap" only: the coverage-weighted pyramid (csrc/texmip.hip)
         self.coverage_ring = int(coverage_ring)        # ... rounds the covered texels are grown by (the bilinear taps' reach)
         self._coverage = {}                            # (side, levels, UV layout) -> (w0 [R,R] f32, wpyr [S])
         self.fov = math.pi / 3                         # kal.render.camera.generate_perspective_projection(np.pi / 3)
@@ -303,15 +247,12 @@ class Renderer:
         face_uv = uv_face_attr[0].detach().contiguous()
         with torch.no_grad():                          # uv_features.detach() in the reference (:61)
             uv = _InterpAttr.apply(face_uv, face_idx, bary).contiguous()
-        if self.interpolation_mode == "mipmap" and self.mip_coverage:
+        if self.interpolation_mode == "mipmap":
             R = texture_map.shape[-1]
-            L = mip_levels(R, self.max_mip_level)      # per call, as _TextureMip
-            w0, wpyr = self.coverage_weights(verts, faces, face_uv, R, L)
-            image = _TextureMipCoverage.apply(texture_map, uv, face_idx, face_xy, face_z, face_uv, (B, H, W), L,
-                                              self.lod_bias, w0, wpyr)
-        elif self.interpolation_mode == "mipmap":
-            image = _TextureMip.apply(texture_map, uv, face_idx, face_xy, face_z, face_uv, (B, H, W), self.max_mip_level,
-                                      self.lod_bias)
+            L = mip_levels(R, self.max_mip_level)      # per call: render_test passes the decoded, larger texture
+            weights = self.coverage_weights(verts, faces, face_uv, R, L) if self.mip_coverage else ()
+            image = _TextureMip.apply(texture_map, uv, face_idx, face_xy, face_z, face_uv, (B, H, W), L, self.lod_bias,
+                                      *weights)
         else:
             image = _TextureMap.apply(texture_map, uv, face_idx, _MODES[self.interpolation_mode])
         mask = (face_idx > -1).float().reshape(B, H, W, 1)

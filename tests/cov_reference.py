@@ -1,4 +1,4 @@
-"""float64 references of the coverage-weighted pyramids (csrc/texcov.hip; the contracts are in include/lnerf_hip.h):
+"""float64 references of the coverage-weighted pyramids (csrc/texmip.hip; the contracts are in include/lnerf_hip.h):
 the weights, the pull and its transpose, the push, and the normalised trilinear lookup.  Taps, lambda, the packing and
 the ULP come from tests/mip_reference.py.
 

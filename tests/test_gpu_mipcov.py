@@ -1,4 +1,4 @@
-"""The coverage-weighted pyramids (csrc/texcov.hip) on the GPU against the float64 references of tests/cov_reference.py.
+"""The coverage-weighted pyramids (csrc/texmip.hip) on the GPU against the float64 references of tests/cov_reference.py.
 
 ULP = 2^-24, the relative error of one f32 operation.  Every bound below is a count of the kernel's roundings times
 ULP times the magnitude the reference propagates (the same rule as the value on absolute values).  The branch decisions
@@ -108,6 +108,22 @@ def test_weights_are_exact(dev, R):
                     assert float(got.max()) <= 1.0
             for got, ref in zip(wl, V.weight_levels_f32(w0, L)):
                 assert torch.equal(got, ref), (name, L)
+
+
+@pytest.mark.parametrize("R", [2, 12, 64])
+def test_weights_are_the_plain_build_of_one_channel(dev, R):
+    """lnerf_mipcov_weights runs lnerf_mip_build's kernel on a [1,R,R] texture: the two entry points agree bit for bit."""
+    from src.latent_nerf.raymarching import mipcov_weights
+    from src.latent_paint.models.render import mip_build
+    g = torch.Generator().manual_seed(R + 3)
+    for L in _levels_for(R):
+        for name, w0 in patterns(R, g).items():
+            w0_d = w0.to(dev).contiguous()
+            got, want = mipcov_weights(w0_d, L), mip_build(w0_d[None], L)
+            if L == 0:
+                assert got is None and want is None
+            else:
+                assert torch.equal(got, want[0]), (name, L)
 
 
 @pytest.mark.parametrize("R", SIDES)
@@ -251,7 +267,7 @@ def _between(got, ends):
 @pytest.mark.parametrize("R", SIDES)
 def test_lookup_forward_backward(dev, R, bias):
     from src.latent_nerf.raymarching import mipcov_pull
-    from src.latent_paint.models.render import mip_lookup, mipcov_lookup, mipcov_lookup_backward
+    from src.latent_paint.models.render import mip_lookup, mip_lookup_backward
     g = torch.Generator().manual_seed(R * 13 + int(bias * 4))
     worst_b, seen_b, seen_c = 0.0, 0, 0
     for C, with_idx in ((1, True), (3, False), (3, True), (4, False)):
@@ -270,7 +286,7 @@ def test_lookup_forward_backward(dev, R, bias):
                 wl, w0_d, wpyr = _weights(dev, w0, R, L)
                 tex_d, uv_d, rho_d = tex.to(dev), uv.to(dev), rho.to(dev)
                 pyr = mipcov_pull(tex_d, w0_d, wpyr, L)
-                got_d = mipcov_lookup(tex_d, pyr, w0_d, wpyr, uv_d, rho_d, face_idx, L, bias)
+                got_d = mip_lookup(tex_d, pyr, uv_d, rho_d, face_idx, L, bias, w0_d, wpyr)
                 got = got_d.cpu().double()
                 levels = [tex] + (M.unpack(pyr.cpu(), R, L) if L else [])
                 look = V.Lookup(levels, wl, uv)
@@ -298,7 +314,7 @@ def test_lookup_forward_backward(dev, R, bias):
                 assert torch.equal(got_d.cpu()[sure_b], want_plain.cpu()[sure_b]), (C, L, name)
                 # ---- backward: level 0 after the fold, per texel
                 dout = torch.randn(P, C, generator=g)
-                gotb = mipcov_lookup_backward(dout.to(dev), (C, R), w0_d, wpyr, uv_d, rho_d, face_idx, L, bias).cpu().double()
+                gotb = mip_lookup_backward(dout.to(dev), (C, R), uv_d, rho_d, face_idx, L, bias, w0_d, wpyr).cpu().double()
                 gT = torch.where(fg[None], dout.double().T, torch.zeros(()).double())             # [C,P]
                 d, s, n, slack = [], [], [], []
                 reach_b = torch.zeros(R * R, dtype=torch.bool)      # level-0 texels a case (b) pixel may add to

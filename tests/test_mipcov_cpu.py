@@ -1,6 +1,6 @@
 """The coverage-weighted pyramids without a GPU: the float64 references of tests/cov_reference.py against independent
 statements of what they compute, the config surface (`guide.texture_mip_coverage`, `log.mesh_texture_fill`,
-`log.mesh_bake_unseen`), and the C ABI of csrc/texcov.hip (exports, ctypes table, every argument check -- made-up
+`log.mesh_bake_unseen`), and the C ABI of csrc/texmip.hip (exports, ctypes table, every argument check -- made-up
 pointers, nothing is launched)."""
 import ctypes
 import re

@@ -195,8 +195,9 @@ def normals(pos, faces):
     return (acc * inv[:, None]).astype(np.float32)
 
 
-def decimate(verts, faces, target_faces, max_error=np.inf, max_rounds=DEFAULT_MAX_ROUNDS):
-    """-> (verts [V',3] f32, faces [F',3] int32, normals [V',3] f32, info dict(rounds, collapses))."""
+def decimate(verts, faces, target_faces, max_error=np.inf, max_rounds=DEFAULT_MAX_ROUNDS, trace=None):
+    """-> (verts [V',3] f32, faces [F',3] int32, normals [V',3] f32, info dict(rounds, collapses)).  `trace` (a list)
+    receives (F, S, m) of every round begun: the faces it started from, the edges selected, the collapses applied."""
     pos = np.array(verts, dtype=np.float32).reshape(-1, 3)
     faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
     V = len(pos)
@@ -221,10 +222,14 @@ def decimate(verts, faces, target_faces, max_error=np.inf, max_rounds=DEFAULT_MA
         sel = np.nonzero(valid & (K2[u] == keys) & (K2[v] == keys))[0]
         S = len(sel)
         if S == 0:
+            if trace is not None:
+                trace.append((F, 0, 0))
             break
         if F - 2 * S < target_faces:
             m = (F - target_faces + 1) // 2
             sel = np.sort(sel[np.argsort(keys[sel])[:m]])
+        if trace is not None:
+            trace.append((F, S, len(sel)))
         su, sv = u[sel], v[sel]
         pos[su] = vstar[sel]
         Q[su] = Q[su] + Q[sv]

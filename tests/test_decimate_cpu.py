@@ -6,6 +6,7 @@ import pytest
 
 from tests import decimate_reference as D
 from tests import mc_reference as R
+from tests.decimate_cases import component_euler as _component_euler
 
 
 def _lattice(n):
@@ -41,26 +42,6 @@ def _boundary_vertices(f):
     key = d[:, 0] * (1 << 32) + d[:, 1]
     rkey = d[:, 1] * (1 << 32) + d[:, 0]
     return np.unique(d[~np.isin(rkey, key)])
-
-
-def _component_euler(v, f):
-    """Euler characteristic of every connected component, sorted."""
-    f = np.asarray(f, np.int64)
-    lab = np.arange(len(v))
-    while True:
-        m = lab[f].min(1)
-        new = lab.copy()
-        for j in range(3):
-            np.minimum.at(new, f[:, j], m)
-        new = new[new]
-        if np.array_equal(new, lab):
-            break
-        lab = new
-    chis = []
-    for c in np.unique(lab[f[:, 0]]):
-        fc = f[lab[f[:, 0]] == c]
-        chis.append(R.euler_characteristic(v, fc))
-    return sorted(chis)
 
 
 @pytest.mark.parametrize("name", sorted(SHAPES))

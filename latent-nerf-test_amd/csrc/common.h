@@ -55,6 +55,24 @@ static inline int64_t div_up(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline unsigned grid_of(int64_t n, int threads) { return (unsigned)(n > threads ? div_up(n, threads) : 1); }
 #define LNERF_LAUNCH(kernel, n, threads, s, ...) \
     hipLaunchKernelGGL(kernel, dim3(::lnerf::grid_of(n, threads)), dim3(threads), 0, s, __VA_ARGS__)
+// grid-stride kernels: the same, capped (a lane takes several items)
+static inline int grid_for(int64_t n, int block = 256, int cap = 4096) {
+    const int64_t g = div_up(n, block);
+    return (int)(g < 1 ? 1 : g > cap ? cap : g);
+}
+
+// The counter-based generator of the march's jitter (k = 0), the occupancy draw, the TV lines and the synthetic
+// guidance: a 32-bit hash of (element, seed, step, stream k), and its top 24 bits as a float in [0, 1).  Restated in
+// oracle/nerf_oracle.py occ_hash / march_noise.
+__host__ __device__ __forceinline__ uint32_t counter_hash(uint32_t i, uint32_t seed, uint32_t step, uint32_t k) {
+    uint32_t x = i * 0x9E3779B1u + seed;
+    x ^= step * 0x85EBCA77u + k * 0xC2B2AE3Du;
+    x ^= x >> 16; x *= 0x7FEB352Du;
+    x ^= x >> 15; x *= 0x846CA68Bu;
+    x ^= x >> 16;
+    return x;
+}
+__host__ __device__ __forceinline__ float hash_unit(uint32_t x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }
 
 // ---------------------------------------------------------------- device helpers
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }

@@ -18,7 +18,7 @@
 // Sampling, per step and level: n_lines = min((res + 1)^2, max(1, tv_vertices / (res + 1))) (lnerf_grid_tv_plan).  All
 // lines taken: the level is swept whole, line j is plane index j.  Otherwise line j is drawn from stratum j of the
 // (res + 1)^2 plane indices, lo_j = floor(j S / n), idx = lo_j + h mod (lo_{j+1} - lo_j) in 64-bit integers, y = idx mod
-// (res + 1), z = idx / (res + 1), h = the guid_hash / occ_hash mixing of (j, seed, step, level): distinct lines by
+// (res + 1), z = idx / (res + 1), h = counter_hash(j, seed, step, level) of common.h: distinct lines by
 // construction.  `step` is read from the optimiser's device counter when one is given -- a replayed graph draws fresh
 // lines every step.
 //
@@ -31,15 +31,6 @@
 
 namespace lnerf {
 
-__host__ __device__ __forceinline__ uint32_t tv_hash(uint32_t i, uint32_t seed, uint32_t step, uint32_t k) {
-    uint32_t x = i * 0x9E3779B1u + seed;
-    x ^= step * 0x85EBCA77u + k * 0xC2B2AE3Du;
-    x ^= x >> 16; x *= 0x7FEB352Du;
-    x ^= x >> 15; x *= 0x846CA68Bu;
-    x ^= x >> 16;
-    return x;
-}
-
 // line j of n of a level with `stride` = res + 1 vertices per axis -> (y, z)
 __host__ __device__ __forceinline__ void tv_line(uint32_t j, uint32_t n, uint32_t stride, uint32_t seed, uint32_t step,
                                                  uint32_t level, uint32_t &y, uint32_t &z) {
@@ -47,7 +38,7 @@ __host__ __device__ __forceinline__ void tv_line(uint32_t j, uint32_t n, uint32_
     unsigned long long idx = j;
     if ((unsigned long long)n != S) {   // (uniform per level.  j S < n S < 2^62: checked on the host)
         const unsigned long long lo = (unsigned long long)j * S / n, hi = ((unsigned long long)j + 1ull) * S / n;
-        idx = lo + (unsigned long long)tv_hash(j, seed, step, level) % (hi - lo);   // n <= S: no stratum is empty
+        idx = lo + (unsigned long long)counter_hash(j, seed, step, level) % (hi - lo);   // n <= S: no stratum is empty
     }
     y = (uint32_t)(idx % stride);
     z = (uint32_t)(idx / stride);

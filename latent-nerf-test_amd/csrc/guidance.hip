@@ -11,15 +11,6 @@
 
 namespace lnerf {
 
-__host__ __device__ __forceinline__ uint32_t guid_hash(uint32_t i, uint32_t seed, uint32_t step, uint32_t k) {
-    uint32_t x = i * 0x9E3779B1u + seed;
-    x ^= step * 0x85EBCA77u + k * 0xC2B2AE3Du;
-    x ^= x >> 16; x *= 0x7FEB352Du;
-    x ^= x >> 15; x *= 0x846CA68Bu;
-    x ^= x >> 16;
-    return x;
-}
-
 // one thread per ray: image row [C], target row of the view's direction bucket, C normal deviates (Box-Muller on two
 // 24-bit uniforms per pair of channels), optionally the entropy gradient of the ray's opacity
 template <int C>
@@ -30,7 +21,7 @@ k_synthetic_guidance(const float *__restrict__ image, const float *__restrict__ 
                      const float *__restrict__ ws, float ent_scale, float ent_eps, float *__restrict__ grad_ws) {
     const uint32_t step = (uint32_t)*step_dev;
     // one timestep per step (the torch form draws torch.randint(.., [1]))
-    const int t = t_lo + (int)(((unsigned long long)guid_hash(0xFFFFFFFFu, seed, step, 7u) * (unsigned long long)n_t) >> 32);
+    const int t = t_lo + (int)(((unsigned long long)counter_hash(0xFFFFFFFFu, seed, step, 7u) * (unsigned long long)n_t) >> 32);
     const float w = weights[t];
     const float ek = ent_scale / (float)n_rays;
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rays; r += (int64_t)gridDim.x * blockDim.x) {
@@ -42,8 +33,8 @@ k_synthetic_guidance(const float *__restrict__ image, const float *__restrict__ 
 #pragma unroll
         for (int c = 0; c < 4; c += 2) {
             // u1 in (0, 1], u2 in [0, 1): z = sqrt(-2 ln u1) (cos, sin)(2 pi u2)
-            const float u1 = (float)((guid_hash((uint32_t)r, seed, step, (uint32_t)c) >> 8) + 1u) * (1.0f / 16777216.0f);
-            const float u2 = (float)(guid_hash((uint32_t)r, seed, step, (uint32_t)c + 1u) >> 8) * (1.0f / 16777216.0f);
+            const float u1 = (float)((counter_hash((uint32_t)r, seed, step, (uint32_t)c) >> 8) + 1u) * (1.0f / 16777216.0f);
+            const float u2 = hash_unit(counter_hash((uint32_t)r, seed, step, (uint32_t)c + 1u));
             const float rad = sqrtf(-2.0f * logf(u1));
             float sn, cs;
             sincosf(6.28318530717958647692f * u2, &sn, &cs);

@@ -1,7 +1,7 @@
 // H1 ray generation, H2 AABB slab test, H3 Morton/bitfield, H4 occupancy-pruned march
 // (training: count -> scan -> write; inference: march_rays / compact_rays).
-// gfx950 only: wave64 ballot / mbcnt compaction, one wavefront per ray.
-#include "common.h"
+// gfx950 only: wave64 ballot / mbcnt compaction, one wavefront per ray.  (The occupancy refresh, H10: occupancy.hip.)
+#include "scan.h"
 
 #include <math.h>
 #include <string.h>
@@ -161,18 +161,10 @@ struct MarchNoise {
     uint32_t seed;
     int bias;                // the write pass runs after the scan pass has advanced the counter: bias 1
 };
-__host__ __device__ __forceinline__ float march_hash_uniform(uint32_t ray, uint32_t seed, uint32_t step) {
-    uint32_t x = ray * 0x9E3779B1u + seed;
-    x ^= step * 0x85EBCA77u;
-    x ^= x >> 16; x *= 0x7FEB352Du;
-    x ^= x >> 15; x *= 0x846CA68Bu;
-    x ^= x >> 16;
-    return (float)(x >> 8) * (1.0f / 16777216.0f);
-}
 __device__ __forceinline__ float march_noise(const MarchNoise &nz, int64_t n) {
     if (nz.values) return nz.values[n];
     if (!nz.counter) return 0.0f;
-    return march_hash_uniform((uint32_t)n, nz.seed, (uint32_t)(*nz.counter - nz.bias));
+    return hash_unit(counter_hash((uint32_t)n, nz.seed, (uint32_t)(*nz.counter - nz.bias), 0u));
 }
 
 // ---- the training march in its parts.  k_march_train reads top to bottom: load the ray (march_ray), find its span
@@ -226,12 +218,7 @@ __device__ __forceinline__ void march_totals(const MarchOut &out, int64_t N) {
     for (int64_t base = 0; base < N; base += 64) {
         const int64_t i = base + lane;
         const int c = i < N ? out.cnt[i] : 0;   // (one round trip per 64 rays: this is the rare overflow path)
-        long long inc = c;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const long long u = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += u;
-        }
+        const long long inc = wave_inclusive_sum_ll(c);
         const long long off = carry + inc - c;
         const bool dropped = march_dropped(c, off, out.capacity);
         if (c > 0 && !dropped) { ++live; best = off + c > best ? off + c : best; }
@@ -458,55 +445,34 @@ k_march_train(MarchRays R, int64_t N, const uint8_t *__restrict__ bitfield, Marc
 // per chunk; the kernel is latency from end to end).
 __global__ void __launch_bounds__(1024) k_march_scan(MarchOut out, int64_t N) {
     int32_t *__restrict__ rays = out.rays;
-    __shared__ long long wave_tot[16];
-    __shared__ int wave_live[16], wave_drop[16];
     __shared__ long long wave_best[16];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int tid = threadIdx.x;
     const int64_t K = (N + 1023) / 1024;
     const int64_t n0 = (int64_t)tid * K, n1 = (n0 + K < N) ? n0 + K : N;
-    long long mine = 0;
-    for (int64_t n = n0; n < n1; ++n) mine += rays[n * 3 + 2];
-    // inclusive scan of `mine` over the workgroup
-    long long inc = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const long long u = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += u;
-    }
-    if (lane == 63) wave_tot[wid] = inc;
-    __syncthreads();
-    long long off = inc - mine;
-    for (int w = 0; w < wid; ++w) off += wave_tot[w];
-    int live = 0, drop = 0;
-    long long best = 0;
+    long long mine[1] = {0}, before[1], total[1];
+    for (int64_t n = n0; n < n1; ++n) mine[0] += rays[n * 3 + 2];
+    block_exclusive_scan<1024>(mine, before, total);
+    long long off = before[0], best = 0;
+    int kept[2] = {0, 0}, unused[2], sum[2];   // live rays, dropped rays
     for (int64_t n = n0; n < n1; ++n) {
         const int c = rays[n * 3 + 2];
         const bool dropped = march_dropped(c, off, out.capacity);
         rays[n * 3 + 1] = (int32_t)(dropped ? 0 : off);
         if (dropped) rays[n * 3 + 2] = 0;
-        if (c > 0 && !dropped) { ++live; best = off + c; }   // (empty rays carry a meaningless offset)
-        drop += dropped ? 1 : 0;
+        if (c > 0 && !dropped) { ++kept[0]; best = off + c; }   // (empty rays carry a meaningless offset)
+        kept[1] += dropped ? 1 : 0;
         off += c;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-        live += __shfl_xor(live, o, 64);
-        drop += __shfl_xor(drop, o, 64);
         const long long u = __shfl_xor(best, o, 64);
         best = u > best ? u : best;
     }
-    if (lane == 0) { wave_live[wid] = live; wave_drop[wid] = drop; wave_best[wid] = best; }
-    __syncthreads();
+    if (lane_id() == 0) wave_best[tid >> 6] = best;
+    block_exclusive_scan<1024>(kept, unused, sum);   // (int counters: other slots than the scan above; its barrier publishes wave_best)
     if (tid == 0) {
-        long long total = 0, bmax = 0;
-        int lv = 0, dr = 0;
-        for (int w = 0; w < 16; ++w) {
-            total += wave_tot[w];
-            lv += wave_live[w];
-            dr += wave_drop[w];
-            bmax = wave_best[w] > bmax ? wave_best[w] : bmax;
-        }
-        march_write_totals(out, total, bmax, lv, dr);
+        for (int w = 0; w < 16; ++w) best = wave_best[w] > best ? wave_best[w] : best;
+        march_write_totals(out, total[0], best, sum[0], sum[1]);
     }
 }
 
@@ -588,231 +554,29 @@ k_composite_rays(int64_t n_alive, int n_step, int32_t *__restrict__ rays_alive, 
     if (!alive) rays_alive[i] = -1;
 }
 
-// Live-ray compaction: keep entries >= 0, preserve order.  Single workgroup, wave ballot +
-// mbcnt prefix, LDS carry across waves.
+// Live-ray compaction: keep entries >= 0, preserve order.  Single workgroup; round k of a pass is its k-th 1024
+// consecutive entries, and the COMPACT_ROUNDS rounds of a pass share one block scan: two barriers per 4096 entries.
+constexpr int COMPACT_ROUNDS = 4;   // (8: the scan's 8 x 16 wave sums per thread spill)
 __global__ void __launch_bounds__(1024) k_compact_rays(const int32_t *__restrict__ in, int64_t n,
                                                        int32_t *__restrict__ out, int32_t *__restrict__ n_out) {
-    __shared__ int wave_cnt[16];
-    __shared__ int carry_s;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    if (tid == 0) carry_s = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < n; base += 1024) {
-        const int64_t i = base + tid;
-        const int32_t v = (i < n) ? in[i] : -1;
-        const bool keep = v >= 0;
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0) wave_cnt[wid] = __popcll(m);
-        __syncthreads();
-        int off = carry_s;
-        for (int w = 0; w < wid; ++w) off += wave_cnt[w];
-        if (keep) out[off + mbcnt(m)] = v;
-        __syncthreads();
-        if (tid == 0) {
-            int tot = 0;
-            for (int w = 0; w < 16; ++w) tot += wave_cnt[w];
-            carry_s += tot;
+    int carry = 0;
+    for (int64_t base = threadIdx.x; base < n + threadIdx.x; base += 1024 * COMPACT_ROUNDS) {   // (workgroup-uniform trip count)
+        int32_t v[COMPACT_ROUNDS];
+        int keep[COMPACT_ROUNDS], rank[COMPACT_ROUNDS], total[COMPACT_ROUNDS];
+#pragma unroll
+        for (int k = 0; k < COMPACT_ROUNDS; ++k) {
+            v[k] = base + k * 1024 < n ? in[base + k * 1024] : -1;
+            keep[k] = v[k] >= 0 ? 1 : 0;
         }
-        __syncthreads();
-    }
-    if (tid == 0) *n_out = carry_s;
-}
-
-// ------------------------------------------------------------------ H10 helpers
-__global__ void __launch_bounds__(256)
-k_occ_cell_points(const uint32_t *__restrict__ indices, int64_t n, float mip_bound, int G,
-                  const float *__restrict__ noise, float *__restrict__ xyzs) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint32_t idx = indices ? indices[i] : (uint32_t)i;
-        const float cx = (float)compact_bits(idx), cy = (float)compact_bits(idx >> 1), cz = (float)compact_bits(idx >> 2);
-        const float nx = noise ? noise[i * 3] : 0.5f, ny = noise ? noise[i * 3 + 1] : 0.5f,
-                    nz = noise ? noise[i * 3 + 2] : 0.5f;
-        const float s = 2.0f / (float)G;
-        float ux = cx + nx, uy = cy + ny, uz = cz + nz;
-        ux = ux * s; uy = uy * s; uz = uz * s;
-        ux = ux - 1.0f; uy = uy - 1.0f; uz = uz - 1.0f;
-        xyzs[i * 3] = ux * mip_bound;
-        xyzs[i * 3 + 1] = uy * mip_bound;
-        xyzs[i * 3 + 2] = uz * mip_bound;
-    }
-}
-
-// ---- steady-state sampling of the refresh, on the device (lnerf_occ_sample): n_rand uniformly random cells + n_rand
-// cells drawn uniformly from the OCCUPIED ones, jittered points inside them.  The upstream form (torch.nonzero of the
-// grid, two randint, an index, a cat, a rand) is six launches and a host synchronisation on the size of the occupied
-// list; here the list is compacted in ascending cell order by two launches (deterministic: replicas of a data-parallel
-// run draw the same cells), its length stays on the device, and one launch draws cells and points from a counter-based
-// generator u = hash(i, seed, step, k) -- restated in oracle/nerf_oracle.py occ_sample.
-constexpr int OCC_BLOCK_CELLS = 4096;   // cells per workgroup of the compaction (256 threads x 16)
-__host__ __device__ __forceinline__ uint32_t occ_hash(uint32_t i, uint32_t seed, uint32_t step, uint32_t k) {
-    uint32_t x = i * 0x9E3779B1u + seed;
-    x ^= step * 0x85EBCA77u + k * 0xC2B2AE3Du;
-    x ^= x >> 16; x *= 0x7FEB352Du;
-    x ^= x >> 15; x *= 0x846CA68Bu;
-    x ^= x >> 16;
-    return x;
-}
-__global__ void __launch_bounds__(256) k_occ_count(const float *__restrict__ grid, int64_t n_cells, int32_t *__restrict__ counts) {
-    __shared__ int wsum[4];
-    const int64_t base = (int64_t)blockIdx.x * OCC_BLOCK_CELLS;
-    int c = 0;
-#pragma unroll 4
-    for (int k = 0; k < 16; ++k) {
-        const int64_t i = base + k * 256 + threadIdx.x;
-        c += (i < n_cells && grid[i] > 0.f) ? 1 : 0;
-    }
-    c = wave_inclusive_sum_i(c);
-    if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
-}
-__global__ void __launch_bounds__(256) k_occ_fill(const float *__restrict__ grid, int64_t n_cells,
-                                                  const int32_t *__restrict__ counts, int n_blocks,
-                                                  int32_t *__restrict__ list, int32_t *__restrict__ total_dev) {
-    __shared__ int s_part[4], s_wave[4];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    // cells in earlier workgroups (and, by workgroup 0, the total)
-    int part = 0;
-    for (int b = tid; b < (int)blockIdx.x; b += 256) part += counts[b];
-    part = wave_inclusive_sum_i(part);
-    if (lane == 63) s_part[w] = part;
-    __syncthreads();
-    int offset = ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
-    if (blockIdx.x == 0) {
-        int all = 0;
-        for (int b = tid; b < n_blocks; b += 256) all += counts[b];
-        all = wave_inclusive_sum_i(all);
-        __syncthreads();
-        if (lane == 63) s_wave[w] = all;
-        __syncthreads();
-        if (tid == 0) *total_dev = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
-        __syncthreads();
-    }
-    const int64_t base = (int64_t)blockIdx.x * OCC_BLOCK_CELLS;
-    for (int k = 0; k < 16; ++k) {   // ascending cell order: 256 consecutive cells per round
-        const int64_t i = base + k * 256 + tid;
-        const bool occ = i < n_cells && grid[i] > 0.f;
-        const unsigned long long m = __ballot(occ);
-        if (lane == 0) s_wave[w] = __popcll(m);
-        __syncthreads();
-        int before = 0;
-        for (int ww = 0; ww < w; ++ww) before += s_wave[ww];
-        const int round_total = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
-        if (occ) list[offset + before + mbcnt(m)] = (int32_t)i;
-        offset += round_total;
-        __syncthreads();
-    }
-}
-__global__ void __launch_bounds__(256)
-k_occ_draw(const int32_t *__restrict__ list, const int32_t *__restrict__ total_dev, int64_t n_cells, int64_t n_rand,
-           uint32_t seed, uint32_t step, float mip_bound, int G, uint32_t *__restrict__ indices, float *__restrict__ xyzs) {
-    const int total = *total_dev;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < 2 * n_rand; i += (int64_t)gridDim.x * blockDim.x) {
-        // STRATIFIED draws, ascending by construction: draw j of a half takes one element, uniformly, from the j-th of
-        // n_rand equal strata of its population -- the cells in (Morton) order for the first half, the ascending list of
-        // occupied cells for the second (a stratum of less than one element repeats its element: with fewer occupied cells
-        // than draws every occupied cell is drawn total / n_rand times in a row, each time with its own jitter).  Every
-        // cell keeps the marginal probability of the independent draws the upstream refresh makes (n_rand / n_cells;
-        // n_rand / total), no stratum is left out by chance, and consecutive lanes evaluate NEIGHBOURING cells: the density
-        // query on the candidates runs at the rate of ray samples instead of that of unrelated points (gather + MLP
-        // 285 -> 195 us per refresh, the per-cell maximum 75 -> 60: measured by sorting the independent draws).
-        const uint32_t h = occ_hash((uint32_t)i, seed, step, 0u);
-        const unsigned long long j = (unsigned long long)(i < n_rand ? i : i - n_rand);
-        const unsigned long long pop = (i >= n_rand && total > 0) ? (unsigned long long)total : (unsigned long long)n_cells;
-        const unsigned long long lo = j * pop / (unsigned long long)n_rand, hi = (j + 1ull) * pop / (unsigned long long)n_rand;
-        unsigned long long pick = lo + (((unsigned long long)h * (hi - lo)) >> 32);   // (hi == lo: the stratum's one element)
-        pick = pick < pop ? pick : pop - 1ull;
-        const uint32_t idx = (i >= n_rand && total > 0) ? (uint32_t)list[(int)pick] : (uint32_t)pick;
-        indices[i] = idx;
-        const float nx = (float)(occ_hash((uint32_t)i, seed, step, 1u) >> 8) * (1.0f / 16777216.0f);
-        const float ny = (float)(occ_hash((uint32_t)i, seed, step, 2u) >> 8) * (1.0f / 16777216.0f);
-        const float nz = (float)(occ_hash((uint32_t)i, seed, step, 3u) >> 8) * (1.0f / 16777216.0f);
-        const float cx = (float)compact_bits(idx), cy = (float)compact_bits(idx >> 1), cz = (float)compact_bits(idx >> 2);
-        const float s = 2.0f / (float)G;
-        float ux = cx + nx, uy = cy + ny, uz = cz + nz;
-        ux = ux * s; uy = uy * s; uz = uz * s;
-        ux = ux - 1.0f; uy = uy - 1.0f; uz = uz - 1.0f;
-        xyzs[i * 3] = ux * mip_bound;
-        xyzs[i * 3 + 1] = uy * mip_bound;
-        xyzs[i * 3 + 2] = uz * mip_bound;
-    }
-}
-
-// Occupancy refresh, order-independent form (replicas of a data-parallel run must stay bit-identical, and the sampled
-// index list may name a cell more than once): pass 1 takes the MAXIMUM of the new densities per cell into a scratch
-// grid (non-negative floats order as unsigned integers: atomicMax on the bits), pass 2 applies
-// grid = max(grid * decay, scratch) to the touched cells.  scratch: one uint32 per cell, all zero between calls.
-__global__ void __launch_bounds__(256) k_occ_update_max(unsigned int *__restrict__ scratch,
-                                                        const uint32_t *__restrict__ indices, int64_t n,
-                                                        const float *__restrict__ sig) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint32_t idx = indices ? indices[i] : (uint32_t)i;
-        const float s = sig[i];
-        // bit 31 marks "touched" (a density of exactly 0 must still decay the cell); densities < 0 never update
-        if (s >= 0.f) atomicMax(&scratch[idx], __float_as_uint(s) | 0x80000000u);
-    }
-}
-__global__ void __launch_bounds__(256) k_occ_update_apply(float *__restrict__ grid, unsigned int *__restrict__ scratch,
-                                                          const uint32_t *__restrict__ indices, int64_t n, float decay) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint32_t idx = indices ? indices[i] : (uint32_t)i;
-        // the first entry of a cell takes its maximum (and leaves the scratch word zero for the next call); further
-        // entries of the same cell find zero: exactly one thread updates the cell, whatever the order
-        const unsigned int m = atomicExch(&scratch[idx], 0u);
-        if (!(m & 0x80000000u)) continue;
-        const float old = grid[idx];
-        if (old >= 0.f) grid[idx] = fmaxf(old * decay, __uint_as_float(m & 0x7FFFFFFFu));
-    }
-}
-
-// mean of max(grid, 0) over all cells, in a FIXED summation order (a float atomicAdd over the partial sums would make
-// the mean -- and with it the occupancy threshold min(mean, thresh) and the bitfield -- depend on arrival order):
-// OCC_MEAN_BLOCKS workgroups each sum a fixed strided slice (wave sums, then the 4 waves in order) into partial[block];
-// one workgroup adds the partials in index order.
-constexpr int OCC_MEAN_BLOCKS = 256;
-__global__ void __launch_bounds__(256) k_occ_mean_partial(const float *__restrict__ grid, int64_t n,
-                                                          float *__restrict__ partial) {
-    __shared__ float s_w[4];
-    float s = 0.f;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        s += fmaxf(grid[i], 0.f);
-    s = wave_sum(s);
-    if (lane_id() == 0) s_w[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
-}
-// apply + mean in ONE pass over the CELLS (not the candidates): a cell whose scratch word is marked takes
-// grid = max(grid * decay, maximum) and the word goes back to zero; every thread adds max(grid, 0) of its cells in the
-// slice order of k_occ_mean_partial, so the mean is the one the two separate launches give, bit for bit.  Streaming
-// (16 B per cell) instead of one atomicExch per candidate: 58 + 9 us -> 8 us for 2 M cells / 1 M candidates.
-__global__ void __launch_bounds__(256) k_occ_apply_mean(float *__restrict__ grid, unsigned int *__restrict__ scratch,
-                                                        int64_t n, float decay, float *__restrict__ partial) {
-    __shared__ float s_w[4];
-    float s = 0.f;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float g = grid[i];
-        const unsigned int m = scratch[i];
-        if (m & 0x80000000u) {
-            scratch[i] = 0u;
-            if (g >= 0.f) {
-                g = fmaxf(g * decay, __uint_as_float(m & 0x7FFFFFFFu));
-                grid[i] = g;
-            }
+        block_exclusive_scan<1024>(keep, rank, total);
+#pragma unroll
+        for (int k = 0; k < COMPACT_ROUNDS; ++k) {
+            if (keep[k]) out[carry + rank[k]] = v[k];
+            carry += total[k];
         }
-        s += fmaxf(g, 0.f);
+        __syncthreads();   // the next pass reuses the scan's slots
     }
-    s = wave_sum(s);
-    if (lane_id() == 0) s_w[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
-}
-__global__ void __launch_bounds__(64) k_occ_mean_final(const float *__restrict__ partial, int blocks, float n,
-                                                       float *__restrict__ mean) {
-    if (threadIdx.x == 0) {
-        float s = 0.f;
-        for (int b = 0; b < blocks; ++b) s += partial[b];
-        *mean = s / n;
-    }
+    if (threadIdx.x == 0) *n_out = carry;
 }
 
 static MarchParams make_params(float bound, int cascade, int G, int max_steps, float dt_gamma) {
@@ -826,13 +590,6 @@ static MarchParams make_params(float bound, int cascade, int G, int max_steps, f
     P.dt_max = (float)(2.0 * 1.7320508075688772 * (double)(1 << (cascade - 1)) / (double)G);
     P.dt_uniform = fminf(fmaxf(0.0f, P.dt_min), P.dt_max);   // clampf's order of min and max
     return P;
-}
-
-static int grid_for(int64_t n, int block = 256, int cap = 4096) {
-    int64_t g = div_up(n, block);
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (int)g;
 }
 
 }  // namespace lnerf
@@ -1061,88 +818,6 @@ int lnerf_compact_rays(const int32_t *alive_in, int64_t n, int32_t *alive_out, i
     LNERF_REQUIRE(alive_in != alive_out || n == 0, "compact_rays: in-place compaction is not supported");
     hipLaunchKernelGGL(k_compact_rays, dim3(1), dim3(1024), 0, as_stream(stream), alive_in, n, alive_out, n_alive_dev);
     LNERF_CHECK_LAUNCH("compact_rays");
-    return LNERF_OK;
-}
-
-int lnerf_occ_cell_points(const uint32_t *indices, int64_t n, int cascade_level, int grid_size, float bound,
-                          const float *noise, float *xyzs, lnerf_stream_t stream) {
-    LNERF_REQUIRE(n >= 0 && cascade_level >= 0 && cascade_level < 8 && grid_size > 0 && bound > 0.f,
-                  "occ_cell_points: bad arguments");
-    if (n == 0) return LNERF_OK;
-    LNERF_REQUIRE(xyzs, "occ_cell_points: null xyzs");
-    const float mip_bound = fminf((float)(1 << cascade_level), bound);
-    hipLaunchKernelGGL(k_occ_cell_points, dim3(grid_for(n)), dim3(256), 0, as_stream(stream), indices, n, mip_bound,
-                       grid_size, noise, xyzs);
-    LNERF_CHECK_LAUNCH("occ_cell_points");
-    return LNERF_OK;
-}
-
-int lnerf_occ_sample(const float *grid_level, int64_t n_cells, int cascade_level, int grid_size, float bound,
-                     int64_t n_rand, uint32_t seed, uint32_t step, int32_t *scratch, uint32_t *indices, float *xyzs,
-                     lnerf_stream_t stream) {
-    LNERF_REQUIRE(n_cells > 0 && n_cells <= ((int64_t)1 << 31) && n_rand >= 0 && 2 * n_rand < ((int64_t)1 << 31),
-                  "occ_sample: sizes out of range");
-    LNERF_REQUIRE(cascade_level >= 0 && cascade_level < 8 && grid_size > 0 && bound > 0.f, "occ_sample: bad arguments");
-    if (n_rand == 0) return LNERF_OK;
-    LNERF_REQUIRE(grid_level && scratch && indices && xyzs, "occ_sample: null pointer");
-    const int n_blocks = (int)div_up(n_cells, (int64_t)OCC_BLOCK_CELLS);
-    int32_t *counts = scratch, *total = scratch + n_blocks, *list = scratch + n_blocks + 1;   // [n_blocks | 1 | n_cells]
-    hipStream_t s = as_stream(stream);
-    hipLaunchKernelGGL(k_occ_count, dim3((unsigned)n_blocks), dim3(256), 0, s, grid_level, n_cells, counts);
-    LNERF_CHECK_LAUNCH("occ_sample(count)");
-    hipLaunchKernelGGL(k_occ_fill, dim3((unsigned)n_blocks), dim3(256), 0, s, grid_level, n_cells, counts, n_blocks, list, total);
-    LNERF_CHECK_LAUNCH("occ_sample(fill)");
-    const float mip_bound = fminf((float)(1 << cascade_level), bound);
-    hipLaunchKernelGGL(k_occ_draw, dim3(grid_for(2 * n_rand)), dim3(256), 0, s, list, total, n_cells, n_rand, seed, step,
-                       mip_bound, grid_size, indices, xyzs);
-    LNERF_CHECK_LAUNCH("occ_sample(draw)");
-    return LNERF_OK;
-}
-
-size_t lnerf_occ_sample_scratch_bytes(int64_t n_cells) {
-    if (n_cells <= 0) return 0;
-    return (size_t)(div_up(n_cells, (int64_t)OCC_BLOCK_CELLS) + 1 + n_cells) * sizeof(int32_t);
-}
-
-int lnerf_occ_update(float *grid_level, const uint32_t *indices, int64_t n, const float *new_sigmas, float decay,
-                     uint32_t *scratch_cells, lnerf_stream_t stream) {
-    LNERF_REQUIRE(n >= 0, "occ_update: negative n");
-    if (n == 0) return LNERF_OK;
-    LNERF_REQUIRE(grid_level && new_sigmas && scratch_cells, "occ_update: null pointer");
-    hipStream_t s = as_stream(stream);
-    hipLaunchKernelGGL(k_occ_update_max, dim3(grid_for(n)), dim3(256), 0, s, scratch_cells, indices, n, new_sigmas);
-    LNERF_CHECK_LAUNCH("occ_update(max)");
-    hipLaunchKernelGGL(k_occ_update_apply, dim3(grid_for(n)), dim3(256), 0, s, grid_level, scratch_cells, indices, n, decay);
-    LNERF_CHECK_LAUNCH("occ_update(apply)");
-    return LNERF_OK;
-}
-
-int lnerf_occ_update_mean(float *grid_level, int64_t n_cells, const uint32_t *indices, int64_t n, const float *new_sigmas,
-                          float decay, uint32_t *scratch_cells, float *mean_dev, float *scratch256,
-                          lnerf_stream_t stream) {
-    LNERF_REQUIRE(n >= 0 && n_cells > 0, "occ_update_mean: bad sizes");
-    LNERF_REQUIRE(grid_level && scratch_cells && mean_dev && scratch256 && (n == 0 || new_sigmas),
-                  "occ_update_mean: null pointer");
-    hipStream_t s = as_stream(stream);
-    if (n > 0) {
-        hipLaunchKernelGGL(k_occ_update_max, dim3(grid_for(n)), dim3(256), 0, s, scratch_cells, indices, n, new_sigmas);
-        LNERF_CHECK_LAUNCH("occ_update_mean(max)");
-    }
-    hipLaunchKernelGGL(k_occ_apply_mean, dim3(OCC_MEAN_BLOCKS), dim3(256), 0, s, grid_level, scratch_cells, n_cells, decay,
-                       scratch256);
-    LNERF_CHECK_LAUNCH("occ_update_mean(apply)");
-    hipLaunchKernelGGL(k_occ_mean_final, dim3(1), dim3(64), 0, s, scratch256, OCC_MEAN_BLOCKS, (float)n_cells, mean_dev);
-    LNERF_CHECK_LAUNCH("occ_update_mean(final)");
-    return LNERF_OK;
-}
-
-int lnerf_occ_mean(const float *grid, int64_t n, float *mean_dev, float *scratch256, lnerf_stream_t stream) {
-    LNERF_REQUIRE(n > 0 && grid && mean_dev && scratch256, "occ_mean: bad arguments");
-    hipLaunchKernelGGL(k_occ_mean_partial, dim3(OCC_MEAN_BLOCKS), dim3(256), 0, as_stream(stream), grid, n, scratch256);
-    LNERF_CHECK_LAUNCH("occ_mean(partial)");
-    hipLaunchKernelGGL(k_occ_mean_final, dim3(1), dim3(64), 0, as_stream(stream), scratch256, OCC_MEAN_BLOCKS, (float)n,
-                       mean_dev);
-    LNERF_CHECK_LAUNCH("occ_mean(final)");
     return LNERF_OK;
 }
 

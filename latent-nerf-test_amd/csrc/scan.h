@@ -1,5 +1,8 @@
-// Prefix sums and scratch layout shared by the mesh-export kernels (isosurface.hip, uvbake.hip, decimate.hip, atlas.hip,
-// meshclean.hip, mesh_shared.h).  A compaction there is
+// Integer prefix sums of the library, and the scratch layout of the mesh-export kernels.  block_exclusive_scan and the
+// 64-bit wave scan serve every workgroup scan outside the scatter (grid.hip and grid_bin.hip keep their tuned ones): the
+// march's scan kernel and overflow totals and the live-ray compaction (rays.hip), the occupied-cell list of the refresh
+// (occupancy.hip), and the mesh-export kernels (isosurface.hip, uvbake.hip, decimate.hip, atlas.hip, meshclean.hip,
+// mesh_shared.h).  A compaction of the mesh export is
 //   per block   block_exclusive_scan inside the kernel that counts, its block total -> blk[block]
 //   scan_top    k_scan_top, ONE workgroup: exclusive prefix of the block totals (in place) and the grand total
 //   per block   block prefix + position in the block

@@ -236,7 +236,7 @@ def march_cell_index(x: torch.Tensor, dt: torch.Tensor, bound: float, cascade: i
 
 def march_noise(N: int, seed: int, step: int) -> torch.Tensor:
     """Counter-based jitter u_n = hash(n, seed, step) in [0,1) of lnerf_march_rays_train's `noise_counter` form
-    (csrc/rays.hip march_hash_uniform; our own definition -- the upstream draws torch.rand(N)): a 32-bit integer
+    (csrc/common.h counter_hash with k = 0 and hash_unit; our own definition -- the upstream draws torch.rand(N)): a 32-bit integer
     finaliser, the top 24 bits scaled by 2^-24."""
     import numpy as np
     M32 = np.uint64(0xFFFFFFFF)
@@ -730,7 +730,8 @@ def occupancy_cell_points(indices: torch.Tensor, cascade_level: int, G: int, bou
 
 
 def occ_hash(i, seed: int, step: int, k: int):
-    """32-bit hash of lnerf_occ_sample (csrc/rays.hip occ_hash; our own definition): numpy uint64 arithmetic masked to
+    """32-bit hash of lnerf_occ_sample (csrc/common.h counter_hash, shared with the march, the TV lines and the
+    synthetic guidance; our own definition): numpy uint64 arithmetic masked to
     32 bits."""
     import numpy as np
     M32 = np.uint64(0xFFFFFFFF)

@@ -8,7 +8,7 @@ import math
 import numpy as np
 import torch
 
-MEAN_BLOCKS = 256              # workgroups of the mean pass (csrc/rays.hip OCC_MEAN_BLOCKS), 256 threads each
+MEAN_BLOCKS = 256              # workgroups of the mean pass (csrc/occupancy.hip OCC_MEAN_BLOCKS), 256 threads each
 MEAN_STRIDE = MEAN_BLOCKS * 256
 U = 2.0 ** -24                 # unit roundoff of float32
 DECAY = 0.95

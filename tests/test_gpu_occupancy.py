@@ -1,4 +1,4 @@
-"""The occupancy refresh (update_extra_state() and the kernels under "H10 helpers" in csrc/rays.hip) at production
+"""The occupancy refresh (update_extra_state() and the kernels of csrc/occupancy.hip) at production
 sizes and in its steady state, against oracle/nerf_oracle.py and tests/occupancy_reference.py.  Every comparison is on
 bits (tensor.view(torch.int32)) but two: the device mean of a grid that is not integer-valued is held to the rounding
 bound derived from its size (occupancy_reference.mean_rel_bound), and the one cell of the special-value table whose
@@ -54,7 +54,7 @@ from tests import occupancy_reference as R
 
 pytestmark = pytest.mark.gpu
 
-BLOCK = 4096                      # cells per workgroup of the compaction (csrc/rays.hip OCC_BLOCK_CELLS)
+BLOCK = 4096                      # cells per workgroup of the compaction (csrc/occupancy.hip OCC_BLOCK_CELLS)
 RAGGED = 257 * BLOCK + 37         # 258 workgroups, the last one of 37 cells
 
 

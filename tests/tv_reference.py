@@ -39,7 +39,7 @@ def full_plan(resolutions):
 def draw_lines(resolutions, offs, seed, step):
     """int64 [offs[-1], 2] = (y, z) of every line, exact integers: a level whose plan takes every line is swept in plane
     order; otherwise line j comes from stratum j: lo_j = j S // n, idx = lo_j + h mod (lo_{j+1} - lo_j), h = the
-    occ_hash / guid_hash mixing of (j, seed, step, level)."""
+    counter_hash (csrc/common.h; O.occ_hash) of (j, seed, step, level)."""
     out = np.zeros((offs[-1], 2), dtype=np.int64)
     for l, res in enumerate(resolutions):
         s, n = res + 1, offs[l + 1] - offs[l]

@@ -875,6 +875,49 @@ int lnerf_uv_project_views(const float *pos, const float *nrm, int64_t P, const 
                            const float *zbuf, const float *images, int C, float cos_min, float power, float slack,
                            float *out, float *weight, int32_t *count, lnerf_stream_t stream);
 
+/* ---- exposure matching and two-band blending of a view bake (csrc/viewblend.hip; view_bake.bake_views with
+ * exposure = True / blend = "bands").  Additive to ABI 7.  pos, nrm, cams_dev, zbuf, images, cos_min, power, slack as
+ * lnerf_uv_project_views, and a point ACCEPTS a view by that call's steps 1-5, one device function for all
+ * (csrc/view_shared.h).  No call allocates or reads back; all are capturable; every argument is checked before the first
+ * launch; two calls give the same bits (numpy restatement: tests/view_blend_reference.py).
+ * lnerf_view_lowpass: a masked, normalised, separable Gaussian low-pass of each view.  images, low [K,C,H,W] f32,
+ *   1 <= K <= 65535, 1 <= C <= 4, 1 <= H, W <= 32767, K C H W < 2^31; a pixel is USABLE iff zbuf < 0.  taps_host: 2r + 1
+ *   host floats in [0, 1], 0 <= r <= LNERF_LOWPASS_MAX_R (the host side: exp(-t^2 / (2 sigma^2)) in f64, normalised to
+ *   sum 1, r = ceil(3 sigma), rounded to f32); they are copied into the launch.  All sums in f32, t ascending from -r,
+ *   each term a product then an add:
+ *     rows:    num(i,j) = sum_t g[t] I(i, j+t), den(i,j) = sum_t g[t]   over the taps inside the image AND usable;
+ *     columns: num'(i,j) = sum_t g[t] num(i+t, j), den'(i,j) = sum_t g[t] den(i+t, j)   over the taps inside the image;
+ *     low = den' > 0 ? num' / den' : 0, written at every pixel, usable or not.
+ *   An unusable pixel is skipped by selection, never multiplied by 0: a NaN or inf there reaches no output.
+ *   Scratch: lnerf_view_lowpass_scratch_bytes() (0 = arguments out of range; 16-byte aligned).
+ * lnerf_view_overlap_stats: for every ordered pair of views, how many points both accept and what the first shows
+ *   there.  low [K,C,H,W]; 1 <= K <= LNERF_STATS_MAX_K.  N [K,K] int64 and S [K,K,C] int64 must be zero on entry and are
+ *   accumulated into: for every point and every ordered pair i != j of its accepted views
+ *     N[i,j] += 1,   S[i,j,c] += llrintf(L_i[c] * 16777216.0f),
+ *   L_i the bilinear sample of low_i at the point with step 6's nested lerps.  64-bit integer atomics only, so the
+ *   sums do not depend on the order in which they land.  Domain: finite low with |value| <= 64: a term is then at most
+ *   2^30 and P < 2^31 of them stay below 2^62.
+ * lnerf_uv_project_views_bands: the two-band projection.  low [K,C,H,W]; gains: device [K,C] or NULL (no gain and NO
+ *   multiplication: the samples keep their bits).  Any K up to 65535, the views in ascending k, no atomics.  Per
+ *   accepted view: w = powf(c, power), I_k = g_k * bil(images_k), L_k = g_k * bil(low_k) per channel; weight += w,
+ *   count += 1, acc += w * (L_k - Lfirst); the BEST view is the one with the largest w (strict >, so the lowest k wins
+ *   an exact tie).  lowmean = Lfirst + acc / weight;  out [P,C] = I_best + (lowmean - L_best), evaluated in that order,
+ *   where weight > 0, else 0: the low band is the weighted mean of the views' low bands, everything above it comes
+ *   from the best view alone.  weight [P] and count [P] are exactly those of lnerf_uv_project_views; best [P] int32 is
+ *   -1 where no view is accepted. */
+#define LNERF_LOWPASS_MAX_R 64
+#define LNERF_STATS_MAX_K 64
+size_t lnerf_view_lowpass_scratch_bytes(int K, int C, int H, int W);
+int lnerf_view_lowpass(const float *images, const float *zbuf, int K, int C, int H, int W, const float *taps_host, int r,
+                       void *scratch, size_t scratch_bytes, float *low, lnerf_stream_t stream);
+int lnerf_view_overlap_stats(const float *pos, const float *nrm, int64_t P, const float *cams_dev, int K, int H, int W,
+                             const float *zbuf, const float *low, int C, float cos_min, float slack, int64_t *N, int64_t *S,
+                             lnerf_stream_t stream);
+int lnerf_uv_project_views_bands(const float *pos, const float *nrm, int64_t P, const float *cams_dev, int K, int H, int W,
+                                 const float *zbuf, const float *images, const float *low, const float *gains, int C,
+                                 float cos_min, float power, float slack, float *out, float *weight, int32_t *count,
+                                 int32_t *best, lnerf_stream_t stream);
+
 /* ---- mesh decimation: rounds of independent quadric-error (Garland-Heckbert) edge collapses, NeRFRenderer.export_mesh's
  * `target_faces` (csrc/decimate.hip).  Additive to ABI 7.  Fully deterministic; the C call is synchronous (one host
  * read of the counts before round 1, one per round).

@@ -7,13 +7,9 @@
 // the views in ascending k and keeps its sums in registers, so the result does not depend on the launch shape and
 // needs no atomics.  The z-buffer and image taps are gathers; neighbouring texels of a chart are neighbouring surface
 // points, so a wave's taps of one view fall into a few cache lines of that view's planes.
-#include "common.h"
+#include "view_shared.h"
 
 namespace lnerf {
-
-constexpr int PROJ_THREADS = 256;
-constexpr int PROJ_CAM_TILE = 64;   // camera records per LDS tile (64 * 14 floats = 3.5 KiB)
-constexpr int PROJ_MAX_C = 4;
 
 struct ProjArgs {
     const float *pos, *nrm, *cams, *zbuf, *images;
@@ -48,47 +44,18 @@ __global__ void __launch_bounds__(PROJ_THREADS) k_uv_project(ProjArgs a) {
         __syncthreads();
         if (!live) continue;
         for (int kk = 0; kk < nk; ++kk) {
-            const float *cam = s_cam + kk * 14;
-            // 1. the angle between the normal and the direction to the eye
-            const float dx = cam[9] - x[0], dy = cam[10] - x[1], dz = cam[11] - x[2];
-            const float len = sqrtf(dx * dx + dy * dy + dz * dz);
-            const float c = (n[0] * dx + n[1] * dy + n[2] * dz) / len;
-            if (!(c >= a.cos_min)) continue;
-            // 2. camera space, with the rasteriser's own arithmetic (raster.hip prepare_corner)
-            const float rx = x[0] - cam[9], ry = x[1] - cam[10], rz = x[2] - cam[11];
-            const float px = fmaf(cam[0], rx, fmaf(cam[1], ry, cam[2] * rz));
-            const float py = fmaf(cam[3], rx, fmaf(cam[4], ry, cam[5] * rz));
-            const float pz = fmaf(cam[6], rx, fmaf(cam[7], ry, cam[8] * rz));
-            if (!(pz < 0.f)) continue;
-            const float fx = cam[12], fy = cam[13];
-            const float X = px * fx / (-pz), Y = py * fy / (-pz);
-            // 3. pixel coordinates, pixel centres at integers; all four taps inside the image
-            const float u = ((X + 1.0f) * Wf - 1.0f) * 0.5f, v = ((1.0f - Y) * Hf - 1.0f) * 0.5f;
-            if (!(u >= 0.f && u < Wf - 1.0f && v >= 0.f && v < Hf - 1.0f)) continue;
-            const float uf = floorf(u), vf = floorf(v);
-            const int j0 = (int)uf, i0 = (int)vf;
-            const float tu = u - uf, tv = v - vf;
-            // 4. no tap on the background or on an eroded pixel
             const int k = k0 + kk;
-            const float *zb = a.zbuf + (int64_t)k * plane + (int64_t)i0 * a.W + j0;
-            const float z00 = zb[0], z01 = zb[1], z10 = zb[a.W], z11 = zb[a.W + 1];
-            if (!(z00 < 0.f && z01 < 0.f && z10 < 0.f && z11 < 0.f)) continue;
-            // 5. depth test against the nearest pixel centre
-            const float zt = tv >= 0.5f ? (tu >= 0.5f ? z11 : z10) : (tu >= 0.5f ? z01 : z00);
-            const float depth = -pz;
-            const float bias = a.slack * depth * 2.0f / fminf(fx * Wf, fy * Hf) * sqrtf(fmaxf(1.0f - c * c, 0.f)) / c +
-                               1e-4f * depth;
-            if (!(pz >= zt - bias)) continue;
+            ViewTap t;
+            // 1-5. does the point accept this view (view_shared.h)
+            if (!view_accept(x, n, s_cam + kk * 14, a.zbuf + (int64_t)k * plane, a.W, Wf, Hf, a.cos_min, a.slack, t)) continue;
             // 6. accumulate the weighted mean around the first accepted colour: the differences are exact zeros where
             // the taps or the views agree, so a colour all views share comes back as it is
-            const float w = powf(c, a.power);
-            const float *im = a.images + (int64_t)k * a.C * plane + (int64_t)i0 * a.W + j0;
+            const float w = powf(t.c, a.power);
+            const float *im = a.images + (int64_t)k * a.C * plane + t.off;
 #pragma unroll
             for (int ch = 0; ch < PROJ_MAX_C; ++ch) {
                 if (ch < a.C) {
-                    const float *t = im + ch * plane;
-                    const float top = t[0] + tu * (t[1] - t[0]), bot = t[a.W] + tu * (t[a.W + 1] - t[a.W]);
-                    const float col = top + tv * (bot - top);
+                    const float col = view_bilinear(im + ch * plane, a.W, t.tu, t.tv);
                     if (cnt == 0) first[ch] = col;
                     acc[ch] += w * (col - first[ch]);
                 }

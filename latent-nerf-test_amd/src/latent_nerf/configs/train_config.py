@@ -115,6 +115,7 @@ class OptimConfig:
 MESH_ATLASES = ("triangle", "charts")   # log.mesh_atlas (src/uv_atlas.py ATLAS_CHOICES)
 TEXTURE_FILLS = ("dilate", "pullpush")   # log.mesh_texture_fill (src/view_bake.py TEXTURE_FILLS)
 BAKE_UNSEEN = ("fallback", "inpaint")    # log.mesh_bake_unseen (src/view_bake.py BAKE_UNSEEN)
+BAKE_BLENDS = ("mean", "bands")          # log.mesh_bake_blend (src/view_bake.py BAKE_BLENDS)
 
 
 @dataclass
@@ -159,6 +160,14 @@ class LogConfig:
     # with mesh_bake_views: covered texels no view sees take the point bake's colour ("fallback") or are filled from the
     # seen texels ("inpaint")
     mesh_bake_unseen: str = "fallback"
+    # with mesh_bake_views: how the views that see a texel are combined.  "mean": their angle-weighted mean; "bands":
+    # two-band blending -- the weighted mean of the views' low-passed images plus the detail of the best view alone, so
+    # what a decoder invents per view is not averaged into a blur.  mesh_bake_band_sigma: the low-pass's sigma in
+    # decoded pixels (0 = one pixel of the render, the finest scale at which decoded views agree).  mesh_bake_exposure:
+    # one gain per view and channel, solved from the overlaps, takes brightness steps between views out
+    mesh_bake_blend: str = "mean"
+    mesh_bake_exposure: bool = False
+    mesh_bake_band_sigma: float = 0.0
     # evaluation also writes a normal-shaded render (*_normals.png / *_normals video) beside every *_rgb one
     eval_normals: bool = False
     max_keep_ckpts: int = 2
@@ -226,7 +235,13 @@ class TrainConfig:
         for n in ("mesh_min_component_faces", "mesh_min_component_diameter", "mesh_keep_largest", "mesh_smooth_iterations"):
             if not getattr(self.log, n) >= 0:
                 raise ValueError("log.%s must be >= 0, not %r" % (n, getattr(self.log, n)))
-        for n in ("mesh_bake_views", "mesh_bake_view_size"):
+        if self.log.mesh_bake_blend not in BAKE_BLENDS:
+            raise ValueError("log.mesh_bake_blend must be one of %s, not %r"
+                             % (" | ".join(BAKE_BLENDS), self.log.mesh_bake_blend))
+        if (self.log.mesh_bake_blend != "mean" or self.log.mesh_bake_exposure) and not self.log.mesh_bake_views > 0:
+            raise ValueError("log.mesh_bake_blend = %r / log.mesh_bake_exposure = %r need log.mesh_bake_views > 0"
+                             % (self.log.mesh_bake_blend, self.log.mesh_bake_exposure))
+        for n in ("mesh_bake_views", "mesh_bake_view_size", "mesh_bake_band_sigma"):
             if not getattr(self.log, n) >= 0:
                 raise ValueError("log.%s must be >= 0, not %r" % (n, getattr(self.log, n)))
         if self.log.mesh_bake_views > 0 and not self.log.mesh_texture_resolution > 0:

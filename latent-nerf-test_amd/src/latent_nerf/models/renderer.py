@@ -612,16 +612,19 @@ class NeRFRenderer(nn.Module):
 
     @torch.no_grad()
     def bake_views(self, verts, faces, vt, ft, images, cams, resolution, gutter=4, fallback=None, erode=0, cos_min=0.2,
-                   power=4.0, slack=2.0, fill="dilate", unseen="fallback"):
+                   power=4.0, slack=2.0, fill="dilate", unseen="fallback", blend="mean", exposure=False, band_sigma=0.0):
         """Project K images of the mesh (images [K,C,H,W] seen by the camera records cams [K,14]) into its UV atlas:
         texels from lnerf_uv_raster, texel normal = the winding normal of the covering face (marching cubes winds
         outwards), visibility from view_zbuffer at the images' size, colours from project_views, `fallback` [C,R,R]
         where no view sees a texel (unseen="inpaint": filled from the seen texels instead), `gutter` dilation rounds and
-        `fill` as bake_texture (view_bake.bake_views, shared with Latent-Paint).
-        -> dict(rgb [C,R,R], view_weight [R,R], view_count [R,R] int32, mask [R,R] uint8)."""
+        `fill` as bake_texture (view_bake.bake_views, shared with Latent-Paint).  blend = "bands" (two-band blending
+        at `band_sigma` pixels) and exposure = True (one gain per view and channel): view_bake.bake_views.
+        -> dict(rgb [C,R,R], view_weight [R,R], view_count [R,R] int32, mask [R,R] uint8; + view_gains [K,C] with
+        exposure, view_best [R,R] int32 with "bands")."""
         from ... import view_bake
         return view_bake.bake_views(verts, faces, vt, ft, images, cams, resolution, gutter=gutter, fallback=fallback,
-                                    erode=erode, cos_min=cos_min, power=power, slack=slack, fill=fill, unseen=unseen)
+                                    erode=erode, cos_min=cos_min, power=power, slack=slack, fill=fill, unseen=unseen,
+                                    blend=blend, exposure=exposure, band_sigma=band_sigma)
 
     @torch.no_grad()
     def render_bake_views(self, K, view_size=None):
@@ -658,7 +661,8 @@ class NeRFRenderer(nn.Module):
     def export_mesh(self, path, resolution=None, S=128, thresh=None, texture_resolution=0, gutter=4, target_faces=0,
                     field_normals=False, atlas="triangle", min_component_faces=0, min_component_diameter=0.0,
                     keep_largest=0, smooth_iterations=0, bake_views=0, view_size=None, view_decoder=None,
-                    view_erode=None, fill="dilate", unseen="fallback"):
+                    view_erode=None, fill="dilate", unseen="fallback", view_blend="mean", view_exposure=False,
+                    view_band_sigma=0.0):
         """Triangle mesh of the density field -> `path`/mesh.obj (the upstream renderer's export_mesh(path, resolution,
         S)): the density on a `resolution`^3 lattice over [-bound, bound]^3 (density_lattice), marching cubes on the GPU
         at iso `thresh` (default min(mean density, density_thresh), as upstream) with the box capped, vertex colours
@@ -696,15 +700,25 @@ class NeRFRenderer(nn.Module):
         latent_texture.pt -- is filled beyond the gutter over the whole atlas (bake_texture); "dilate" leaves the files
         byte for byte what they were.  unseen = "inpaint" (with bake_views): covered texels no view sees are filled from
         the seen ones instead of taking the point bake's colour.
+        view_blend = "bands" (with bake_views): two-band blending -- the low band of a texel is the weighted mean of the
+        views' low-passed images, everything finer comes from its best view alone, so the detail a decoder invents per
+        view is not averaged into a blur; view_band_sigma is the Gaussian's sigma in decoded pixels (0: max(1, decoded
+        side / render side), one render pixel, as view_erode's default); the result gains view_best [R,R] int32.
+        view_exposure = True: one gain per view and channel, solved from what the views show where they overlap
+        (view_bake.exposure_gains), takes the brightness steps between views out; the result gains view_gains [K,3].
+        Both are off by default and every file is then byte for byte what it was.
         Returns dict(verts [V,3], faces [F,3] int32, normals [V,3], colors [V,3], iso, path, faces_before (the
         marching-cubes face count), components and components_kept (None without a cleaning), faces_cleaned (the face
         count after the cleaning)) with device tensors, plus vt, ft, texture, mask, rgb when textured."""
         from ...uv_atlas import check_atlas_choice
         from .mesh_io import write_obj
-        from ...view_bake import BAKE_UNSEEN, TEXTURE_FILLS, check_choice
+        from ...view_bake import BAKE_BLENDS, BAKE_UNSEEN, TEXTURE_FILLS, check_choice
         check_atlas_choice(atlas, "export_mesh: atlas")
         check_choice(fill, TEXTURE_FILLS, "export_mesh: fill")
         check_choice(unseen, BAKE_UNSEEN, "export_mesh: unseen")
+        check_choice(view_blend, BAKE_BLENDS, "export_mesh: view_blend")
+        if not float(view_band_sigma) >= 0.0:
+            raise ValueError("export_mesh: view_band_sigma must be >= 0 (got %r)" % (view_band_sigma,))
         min_component_faces, min_component_diameter = int(min_component_faces), float(min_component_diameter)
         keep_largest, smooth_iterations = int(keep_largest), int(smooth_iterations)
         bake_views = int(bake_views)
@@ -713,6 +727,9 @@ class NeRFRenderer(nn.Module):
         if bake_views > 0 and int(texture_resolution) <= 0:
             raise ValueError("export_mesh: bake_views = %d needs texture_resolution > 0 (the views are baked into the "
                              "texture)" % bake_views)
+        if bake_views == 0 and (view_blend != "mean" or view_exposure):
+            raise ValueError("export_mesh: view_blend = %r / view_exposure = %r need bake_views > 0"
+                             % (view_blend, view_exposure))
         if min_component_faces < 0 or keep_largest < 0:
             raise ValueError("export_mesh: min_component_faces (%d) and keep_largest (%d) must be >= 0"
                              % (min_component_faces, keep_largest))
@@ -758,17 +775,18 @@ class NeRFRenderer(nn.Module):
             result.update(self._export_textured(str(path), verts, faces, normals, int(texture_resolution), gutter, S,
                                                 bool(field_normals), atlas,
                                                 views=(bake_views, view_size, view_decoder, view_erode), fill=fill,
-                                                unseen=unseen))
+                                                unseen=unseen,
+                                                blend=(view_blend, bool(view_exposure), float(view_band_sigma))))
         else:
             write_obj(out, verts.cpu().numpy(), faces.cpu().numpy(), normals.cpu().numpy(), colors.cpu().numpy())
         return result
 
     def _export_textured(self, path, verts, faces, normals, R, gutter, S, normal_map=False, atlas="triangle",
-                         views=(0, None, None, None), fill="dilate", unseen="fallback"):
+                         views=(0, None, None, None), fill="dilate", unseen="fallback", blend=("mean", False, 0.0)):
         """The textured half of export_mesh: atlas, bake, mesh.obj + mesh.mtl + albedo.png (+ latent_texture.pt;
         normal_map: + normal_object.png, the field's normals over the same atlas; views = (K, size, decoder, erode)
         with K > 0: albedo.png from K rendered views, the point bake's image as albedo_preview.png; `fill` and `unseen`
-        as export_mesh)."""
+        as export_mesh; blend = (view_blend, view_exposure, view_band_sigma))."""
         import warnings
 
         import numpy as np
@@ -799,8 +817,9 @@ class NeRFRenderer(nn.Module):
             from ...view_bake import to_uint8
             Image.fromarray(albedo).save(os.path.join(path, "albedo_preview.png"))
             seen = self._bake_rendered_views(verts, faces, vt, ft, R, gutter, baked["rgb"], *views, fill=fill,
-                                             unseen=unseen)
-            baked = dict(baked, view_rgb=seen["rgb"], view_weight=seen["view_weight"], view_count=seen["view_count"])
+                                             unseen=unseen, blend=blend)
+            baked = dict(baked, view_rgb=seen["rgb"], view_weight=seen["view_weight"], view_count=seen["view_count"],
+                         **{k: seen[k] for k in ("view_gains", "view_best") if k in seen})
             albedo = to_uint8(seen["rgb"])
         Image.fromarray(albedo).save(os.path.join(path, "albedo.png"))
         if (self.latent_mode or self.tuned) and baked["texture"].shape[0] == 4:
@@ -814,7 +833,7 @@ class NeRFRenderer(nn.Module):
         return dict(baked, vt=vt, ft=ft, **extra)
 
     def _bake_rendered_views(self, verts, faces, vt, ft, R, gutter, fallback, K, view_size, view_decoder, view_erode,
-                             fill="dilate", unseen="fallback"):
+                             fill="dilate", unseen="fallback", blend=("mean", False, 0.0)):
         """export_mesh's view bake: K renders, decoded as images, projected into the atlas over `fallback`."""
         renders, cams = self.render_bake_views(K, view_size)
         h, w = renders.shape[-2:]
@@ -832,7 +851,8 @@ class NeRFRenderer(nn.Module):
         if view_erode is None:
             view_erode = 0 if (H, W) == (h, w) else max(1, -(-H // h))
         return self.bake_views(verts, faces, vt, ft, images.float().clamp(0, 1), cams, R, gutter=gutter, fallback=fallback,
-                               erode=int(view_erode), fill=fill, unseen=unseen)
+                               erode=int(view_erode), fill=fill, unseen=unseen, blend=blend[0], exposure=blend[1],
+                               band_sigma=blend[2] if blend[2] > 0 else max(1.0, H / h))
 
     def shadow_extra_state(self):
         """Context manager: inside it the occupancy state (density grid, bitfield, mean) is a SHADOW copy, so

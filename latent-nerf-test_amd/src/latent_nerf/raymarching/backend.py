@@ -149,6 +149,10 @@ _SIGNATURES = {
     "lnerf_uv_raster": [_P, _I, _P, _P, _I, _P, _I, _I, _I, _L, _P, _Z, _P, _P, _P, _L, _P, _P],
     "lnerf_uv_dilate": [_P, _P, _I, _I, _I, _P, _P, _P],
     "lnerf_uv_project_views": [_P, _P, _L, _P, _I, _I, _I, _P, _P, _I, _F, _F, _F, _P, _P, _P, _P],
+    "lnerf_view_lowpass_scratch_bytes": [_I, _I, _I, _I],
+    "lnerf_view_lowpass": [_P, _P, _I, _I, _I, _I, _P, _I, _P, _Z, _P, _P],
+    "lnerf_view_overlap_stats": [_P, _P, _L, _P, _I, _I, _I, _P, _P, _I, _F, _F, _P, _P, _P],
+    "lnerf_uv_project_views_bands": [_P, _P, _L, _P, _I, _I, _I, _P, _P, _P, _P, _I, _F, _F, _F, _P, _P, _P, _P, _P],
     "lnerf_decimate_scratch_bytes": [_I, _I],
     "lnerf_decimate": [_P, _I, _P, _I, _I, _F, _I, _P, _Z, _P, _P, _P, _P, _P],
     "lnerf_atlas_buckets": [_P, _I, _P, _I, _P, _P, _P, _P],
@@ -193,6 +197,7 @@ _RESTYPES = {
     "lnerf_grid_encode_backward_workspace_bytes": _Z,
     "lnerf_marching_cubes_scratch_bytes": _Z,
     "lnerf_uv_raster_scratch_bytes": _Z,
+    "lnerf_view_lowpass_scratch_bytes": _Z,
     "lnerf_decimate_scratch_bytes": _Z,
     "lnerf_atlas_compact_scratch_bytes": _Z,
     "lnerf_atlas_boxes_scratch_bytes": _Z,

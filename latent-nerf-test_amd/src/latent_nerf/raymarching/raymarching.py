@@ -1271,3 +1271,115 @@ def project_views(pos, nrm, cams, zbuf, images, cos_min=0.2, power=4.0, slack=2.
             W, _chk(zbuf, "zbuf"), _chk(images, "images"), C, float(cos_min), float(power), float(slack),
             _p(out) if P else None, _p(weight) if P else None, _p(count) if P else None, _stream())
     return out, weight, count
+
+
+# ------------------------------------------------------------------------------ exposure matching, two-band blending
+LOWPASS_MAX_R = 64      # LNERF_LOWPASS_MAX_R
+STATS_MAX_K = 64        # LNERF_STATS_MAX_K
+
+
+def gaussian_taps(sigma):
+    """The 2r + 1 taps of view_lowpass: exp(-t^2 / (2 sigma^2)) for t = -r .. r in float64, normalised to sum 1,
+    r = ceil(3 sigma); sigma = 0 is the identity (r = 0, one tap of 1).  -> list of host floats (float64)."""
+    sigma = float(sigma)
+    if not (sigma >= 0.0 and math.isfinite(sigma)):
+        raise ValueError("gaussian_taps: sigma must be finite and >= 0 (got %r)" % (sigma,))
+    r = int(math.ceil(3.0 * sigma))
+    if r > LOWPASS_MAX_R:
+        raise ValueError("gaussian_taps: sigma = %g needs r = %d taps a side, more than %d" % (sigma, r, LOWPASS_MAX_R))
+    g = [math.exp(-(t * t) / (2.0 * sigma * sigma)) if sigma > 0 else 1.0 for t in range(-r, r + 1)]
+    total = math.fsum(g)
+    return [v / total for v in g]
+
+
+def _view_stack(op, cams, zbuf, images, dev, name="images"):
+    """The checks project_views makes of its image stack and z-buffer -> (cams, zbuf, images, K, C, H, W)."""
+    cams = _cams(cams, op, dev)
+    K = cams.shape[0]
+    if not isinstance(images, torch.Tensor) or images.dim() != 4 or images.shape[0] != K or not 1 <= images.shape[1] <= 4:
+        raise ValueError("%s: %s must be [K,C,H,W] with K = %d and 1 <= C <= 4" % (op, name, K))
+    C, H, W = (int(v) for v in images.shape[1:])
+    if not isinstance(zbuf, torch.Tensor) or tuple(zbuf.shape) != (K, H, W):
+        raise ValueError("%s: zbuf must be [K,H,W] = [%d,%d,%d]" % (op, K, H, W))
+    return cams, zbuf.to(dev).float().contiguous(), images.to(dev).float().contiguous(), K, C, H, W
+
+
+def _points(op, pos, nrm):
+    for t, name in ((pos, "pos"), (nrm, "nrm")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError("%s: %s must be [P,3]" % (op, name))
+    if pos.shape != nrm.shape:
+        raise ValueError("%s: pos %s and nrm %s differ" % (op, tuple(pos.shape), tuple(nrm.shape)))
+    return pos.float().contiguous(), nrm.to(pos.device).float().contiguous()
+
+
+def view_lowpass(images, zbuf, sigma):
+    """Masked, normalised Gaussian low-pass of K view images (lnerf_view_lowpass, include/lnerf_hip.h: the rule).
+    images [K,C,H,W], 1 <= C <= 4; zbuf [K,H,W] (view_zbuffer): a pixel is usable iff zbuf < 0; sigma in pixels, the
+    taps those of gaussian_taps.  Unusable pixels are left out of every sum (a NaN there reaches nothing); a pixel
+    with no usable pixel in reach gets 0.  -> low [K,C,H,W], written at every pixel."""
+    if not isinstance(images, torch.Tensor) or images.dim() != 4 or not 1 <= images.shape[1] <= 4 or images.shape[0] < 1:
+        raise ValueError("view_lowpass: images must be [K,C,H,W] with K >= 1 and 1 <= C <= 4")
+    K, C, H, W = (int(v) for v in images.shape)
+    if not isinstance(zbuf, torch.Tensor) or tuple(zbuf.shape) != (K, H, W):
+        raise ValueError("view_lowpass: zbuf must be [K,H,W] = [%d,%d,%d]" % (K, H, W))
+    taps = gaussian_taps(sigma)
+    r = len(taps) // 2
+    dev = images.device
+    images, zbuf = images.float().contiguous(), zbuf.to(dev).float().contiguous()
+    nbytes = int(_b.get_lib().lnerf_view_lowpass_scratch_bytes(K, C, H, W))
+    if nbytes == 0:
+        raise ValueError("view_lowpass: [%d,%d,%d,%d] is out of range (K C H W must stay below 2^31)" % (K, C, H, W))
+    scratch = _scratch(nbytes, dev)
+    low = torch.empty_like(images)
+    taps_host = (ctypes.c_float * len(taps))(*taps)
+    _b.call("lnerf_view_lowpass", _chk(images, "images"), _chk(zbuf, "zbuf"), K, C, H, W, taps_host, r, _p(scratch), nbytes,
+            _p(low), _stream())
+    return low
+
+
+def view_overlap_stats(pos, nrm, cams, zbuf, low, cos_min=0.2, slack=2.0):
+    """For every ordered pair of views, the number of points both accept and the sum of what the first shows there
+    (lnerf_view_overlap_stats, include/lnerf_hip.h: the rule): the input of view_bake.exposure_gains.  pos, nrm [P,3],
+    cams [K,14] with K <= 64, zbuf [K,H,W], low [K,C,H,W] (view_lowpass; finite, |value| <= 64); a point accepts a view
+    exactly where project_views does.  -> (N [K,K] int64, S [K,K,C] int64: sums of round(sample * 2^24)); integer sums,
+    so two calls give the same bits."""
+    pos, nrm = _points("view_overlap_stats", pos, nrm)
+    dev = pos.device
+    cams, zbuf, low, K, C, H, W = _view_stack("view_overlap_stats", cams, zbuf, low, dev, "low")
+    if K > STATS_MAX_K:
+        raise ValueError("view_overlap_stats: K = %d views, more than %d" % (K, STATS_MAX_K))
+    P = pos.shape[0]
+    N = torch.zeros(K, K, device=dev, dtype=torch.int64)
+    S = torch.zeros(K, K, C, device=dev, dtype=torch.int64)
+    _b.call("lnerf_view_overlap_stats", _chk(pos, "pos") if P else None, _chk(nrm, "nrm") if P else None, P, _p(cams), K, H,
+            W, _chk(zbuf, "zbuf"), _chk(low, "low"), C, float(cos_min), float(slack), _p(N), _p(S), _stream())
+    return N, S
+
+
+def project_views_bands(pos, nrm, cams, zbuf, images, low, gains=None, cos_min=0.2, power=4.0, slack=2.0):
+    """Two-band projection of K images onto surface points (lnerf_uv_project_views_bands, include/lnerf_hip.h: the rule).
+    Arguments as project_views, plus low [K,C,H,W] (view_lowpass of the images) and gains [K,C] or None (per view and
+    channel, applied to both bands; None multiplies nothing).  The low band of a point is the cosine^power-weighted mean
+    of the accepted views' low bands; everything above it comes from the one accepted view with the largest weight.
+    -> out [P,C], weight [P], count [P] int32 (both exactly project_views'), best [P] int32 (-1: no view)."""
+    pos, nrm = _points("project_views_bands", pos, nrm)
+    dev = pos.device
+    cams, zbuf, images, K, C, H, W = _view_stack("project_views_bands", cams, zbuf, images, dev)
+    if not isinstance(low, torch.Tensor) or tuple(low.shape) != (K, C, H, W):
+        raise ValueError("project_views_bands: low must be [K,C,H,W] = [%d,%d,%d,%d]" % (K, C, H, W))
+    low = low.to(dev).float().contiguous()
+    if gains is not None:
+        if not isinstance(gains, torch.Tensor) or tuple(gains.shape) != (K, C):
+            raise ValueError("project_views_bands: gains must be [K,C] = [%d,%d]" % (K, C))
+        gains = gains.to(dev).float().contiguous()
+    P = pos.shape[0]
+    out = torch.zeros(P, C, device=dev)
+    weight = torch.zeros(P, device=dev)
+    count = torch.zeros(P, device=dev, dtype=torch.int32)
+    best = torch.full((P,), -1, device=dev, dtype=torch.int32)
+    _b.call("lnerf_uv_project_views_bands", _chk(pos, "pos") if P else None, _chk(nrm, "nrm") if P else None, P, _p(cams),
+            K, H, W, _chk(zbuf, "zbuf"), _chk(images, "images"), _chk(low, "low"),
+            _chk(gains, "gains", allow_none=True), C, float(cos_min), float(power), float(slack),
+            _p(out) if P else None, _p(weight) if P else None, _p(count) if P else None, _p(best) if P else None, _stream())
+    return out, weight, count, best

@@ -669,7 +669,10 @@ class Trainer:
                                          keep_largest=int(getattr(self.cfg.log, "mesh_keep_largest", 0)),
                                          smooth_iterations=int(getattr(self.cfg.log, "mesh_smooth_iterations", 0)),
                                          fill=getattr(self.cfg.log, "mesh_texture_fill", "dilate"),
-                                         unseen=getattr(self.cfg.log, "mesh_bake_unseen", "fallback"))
+                                         unseen=getattr(self.cfg.log, "mesh_bake_unseen", "fallback"),
+                                         view_blend=getattr(self.cfg.log, "mesh_bake_blend", "mean"),
+                                         view_exposure=bool(getattr(self.cfg.log, "mesh_bake_exposure", False)),
+                                         view_band_sigma=float(getattr(self.cfg.log, "mesh_bake_band_sigma", 0.0)))
             self.log("exported %s (%d vertices, %d triangles; %d before decimation; iso %.4g)"
                      % (mesh["path"], mesh["verts"].shape[0], mesh["faces"].shape[0], mesh["faces_before"], mesh["iso"]))
             if mesh["components"] is not None:

@@ -16,6 +16,7 @@ INTERPOLATION_MODES = ("nearest", "bilinear", "bicubic", "mipmap")
 UV_ATLASES = ("triangle", "charts")
 TEXTURE_FILLS = ("dilate", "pullpush")   # log.mesh_texture_fill (src/view_bake.py TEXTURE_FILLS)
 BAKE_UNSEEN = ("fallback", "inpaint")    # log.mesh_bake_unseen (src/view_bake.py BAKE_UNSEEN)
+BAKE_BLENDS = ("mean", "bands")          # log.mesh_bake_blend (src/view_bake.py BAKE_BLENDS)
 
 RenderConfig = _cli.make_section("RenderConfig", (
     ("train_grid_size", int, 64, "side of the square training render, in latent pixels"),
@@ -73,6 +74,11 @@ LogConfig = _cli.make_section("LogConfig", (
                                          "built from it do not seam)"),
     ("mesh_bake_unseen", str, "fallback", "with mesh_bake_views: covered texels no view sees: " + " | ".join(BAKE_UNSEEN)
                                           + " (fallback: the decoded atlas; inpaint: filled from the seen texels)"),
+    ("mesh_bake_blend", str, "mean", "with mesh_bake_views: how the views that see a texel are combined: "
+                                     + " | ".join(BAKE_BLENDS) + " (mean: their angle-weighted mean; bands: the mean of "
+                                     "their low-passed images plus the detail of the best view alone)"),
+    ("mesh_bake_exposure", bool, False, "with mesh_bake_views: one gain per view and channel, solved from the overlaps"),
+    ("mesh_bake_band_sigma", float, 0.0, "mesh_bake_blend bands: sigma of the low-pass in render pixels (0 = 1 pixel)"),
     ("max_keep_ckpts", int, 2, "older checkpoints are deleted beyond this count"),
 ), namespace={"exp_dir": property(lambda self: Path(self.exp_root) / self.exp_name)}, doc="logging and saving")
 
@@ -115,6 +121,14 @@ class TrainConfig:
                              % (" | ".join(BAKE_UNSEEN), self.log.mesh_bake_unseen))
         if self.guide.uv_atlas not in UV_ATLASES:
             raise ValueError("guide.uv_atlas must be one of %s, not %r" % (" | ".join(UV_ATLASES), self.guide.uv_atlas))
+        if self.log.mesh_bake_blend not in BAKE_BLENDS:
+            raise ValueError("log.mesh_bake_blend must be one of %s, not %r"
+                             % (" | ".join(BAKE_BLENDS), self.log.mesh_bake_blend))
+        if not self.log.mesh_bake_band_sigma >= 0:
+            raise ValueError("log.mesh_bake_band_sigma must be >= 0 (got %s)" % self.log.mesh_bake_band_sigma)
+        if (self.log.mesh_bake_blend != "mean" or self.log.mesh_bake_exposure) and not self.log.mesh_bake_views > 0:
+            raise ValueError("log.mesh_bake_blend = %r / log.mesh_bake_exposure = %r need log.mesh_bake_views > 0"
+                             % (self.log.mesh_bake_blend, self.log.mesh_bake_exposure))
         if self.log.mesh_bake_views < 0:
             raise ValueError("log.mesh_bake_views must be >= 0 (got %s)" % self.log.mesh_bake_views)
         if self.log.mesh_bake_views > 0 and self.guide.texture_resolution < 1:

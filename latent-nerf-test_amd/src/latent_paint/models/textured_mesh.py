@@ -203,7 +203,8 @@ class TexturedMeshModel(nn.Module):
 
     # ------------------------------------------------------------------ export
     @torch.no_grad()
-    def export_mesh(self, path, guidance=None, bake_views=0, view_size=None, fill="dilate", unseen="fallback"):
+    def export_mesh(self, path, guidance=None, bake_views=0, view_size=None, fill="dilate", unseen="fallback",
+                    view_blend="mean", view_exposure=False, view_band_sigma=0.0):
         """Writes `albedo.png` (the decoded texture), `mesh.obj` (v / vt / f v/vt) and `mesh.mtl` into `path`.
         bake_views = K > 0: the decoder sees the whole atlas as one picture, so chart borders and unrelated neighbouring
         charts are decoded together; instead `albedo.png` is projected from K evaluation renders of the decoded mesh
@@ -215,13 +216,23 @@ class TexturedMeshModel(nn.Module):
         their bits), and so is the view bake's image beyond its gutter -- mip levels built from the files then do not
         seam at chart borders.  "dilate" leaves every file byte for byte what it was.  unseen = "inpaint" (K > 0):
         covered texels no view sees are filled from the seen ones instead of taking the decoded atlas' colour.
-        -> dict(rgb [3,R,R]; K > 0: + view_rgb, view_weight, view_count, mask)."""
+        view_blend = "bands", view_exposure = True, view_band_sigma (K > 0): two-band blending and per-view exposure
+        gains of view_bake.bake_views (sigma in pixels of the renders; 0: 1 pixel, the renders are not up-scaled); off
+        by default, and every file is then byte for byte what it was.
+        -> dict(rgb [3,R,R]; K > 0: + view_rgb, view_weight, view_count, mask; + view_best with "bands", view_gains
+        with view_exposure)."""
         from PIL import Image
         bake_views = int(bake_views)
         if bake_views < 0:
             raise ValueError("export_mesh: bake_views must be >= 0 (got %d)" % bake_views)
         view_bake.check_choice(fill, view_bake.TEXTURE_FILLS, "export_mesh: fill")
         view_bake.check_choice(unseen, view_bake.BAKE_UNSEEN, "export_mesh: unseen")
+        view_bake.check_choice(view_blend, view_bake.BAKE_BLENDS, "export_mesh: view_blend")
+        if not float(view_band_sigma) >= 0.0:
+            raise ValueError("export_mesh: view_band_sigma must be >= 0 (got %r)" % (view_band_sigma,))
+        if bake_views == 0 and (view_blend != "mean" or view_exposure):
+            raise ValueError("export_mesh: view_blend = %r / view_exposure = %r need bake_views > 0"
+                             % (view_blend, view_exposure))
         path = Path(path)
         path.mkdir(parents=True, exist_ok=True)
         if self.latent_mode:
@@ -238,7 +249,8 @@ class TexturedMeshModel(nn.Module):
         result = {"rgb": rgb[0]}
         if bake_views > 0:
             Image.fromarray(albedo).save(path / "albedo_preview.png")
-            result.update(self._bake_rendered_views(rgb, bake_views, view_size, fill, unseen))
+            result.update(self._bake_rendered_views(rgb, bake_views, view_size, fill, unseen,
+                                                    (view_blend, bool(view_exposure), float(view_band_sigma))))
             # (the projected image is rounded to 8 bits, as the NeRF exporter's; the preview above keeps the upstream
             # exporter's truncation, so that it and the K = 0 file stay byte for byte what they were)
             albedo = view_bake.to_uint8(result["view_rgb"])
@@ -246,7 +258,7 @@ class TexturedMeshModel(nn.Module):
         self._write_obj(path)
         return result
 
-    def _bake_rendered_views(self, rgb, K, view_size, fill="dilate", unseen="fallback"):
+    def _bake_rendered_views(self, rgb, K, view_size, fill="dilate", unseen="fallback", blend=("mean", False, 0.0)):
         """export_mesh's view bake over the decoded atlas `rgb` [1,3,R,R]: K renders of it on the mesh, projected back."""
         side = int(view_size or self.opt.render.eval_grid_size)
         poses = bake_view_poses(K)
@@ -256,9 +268,10 @@ class TexturedMeshModel(nn.Module):
         images = self.render_test(view["elev"], view["azim"], view["radius"], decode_func=lambda _t: rgb,
                                   dims=(side, side))["image"]
         baked = view_bake.bake_views(self.mesh.vertices, self.mesh.faces, self.vt, self.ft, images.clamp(0, 1), cams,
-                                     rgb.shape[-1], fallback=rgb[0].float().clamp(0, 1), fill=fill, unseen=unseen)
+                                     rgb.shape[-1], fallback=rgb[0].float().clamp(0, 1), fill=fill, unseen=unseen,
+                                     blend=blend[0], exposure=blend[1], band_sigma=blend[2])
         return {"view_rgb": baked["rgb"], "view_weight": baked["view_weight"], "view_count": baked["view_count"],
-                "mask": baked["mask"]}
+                "mask": baked["mask"], **{k: baked[k] for k in ("view_gains", "view_best") if k in baked}}
 
     def _write_obj(self, path):
         v = self.mesh.vertices.cpu().numpy()

@@ -184,7 +184,10 @@ class Trainer:
             self.mesh_model.export_mesh(target, guidance=self.diffusion,
                                         bake_views=int(getattr(self.cfg.log, "mesh_bake_views", 0)),
                                         fill=getattr(self.cfg.log, "mesh_texture_fill", "dilate"),
-                                        unseen=getattr(self.cfg.log, "mesh_bake_unseen", "fallback"))
+                                        unseen=getattr(self.cfg.log, "mesh_bake_unseen", "fallback"),
+                                        view_blend=getattr(self.cfg.log, "mesh_bake_blend", "mean"),
+                                        view_exposure=bool(getattr(self.cfg.log, "mesh_bake_exposure", False)),
+                                        view_band_sigma=float(getattr(self.cfg.log, "mesh_bake_band_sigma", 0.0)))
             self.log("saved mesh to %s" % target)
 
     @torch.no_grad()

@@ -1097,6 +1097,78 @@ int lnerf_mesh_smooth(const float *verts, int n_verts, const int32_t *faces, int
                       float mu, void *scratch, size_t scratch_bytes, float *verts_out, float *normals_out,
                       lnerf_stream_t stream);
 
+/* ---- Vertex gradients and edge antialiasing of the Latent-Paint renders (`optim.disp_lr`, `render.antialias`;
+ * csrc/rastergrad.hip).  Additive to ABI 7; every call above is unchanged.  The geometry half of the render's backward
+ * pass: each call differentiates one forward above and recomputes its terms from the same inputs.  f32, every operation
+ * rounded on its own.  Shared conventions: face_idx [B*H*W], bary [B*H*W,3], face_xy [B,F,3,2] and face_z [B,F,3] are
+ * what lnerf_raster_prepare_batch / lnerf_rasterize_batch wrote; the centre of pixel (i, j) is px = (2j+1)/W - 1,
+ * py = 1 - (2i+1)/H; a face_idx outside [0, F) is background and nothing is read through it; 1 <= B <= 65535,
+ * 1 <= H, W <= 32767, B * H * W < 2^31.  Every argument is checked before the first launch; no allocation, no
+ * synchronisation, no host read-back.  The calls that ADD INTO a gradient use float atomics (their sums depend on the
+ * order, within rounding); the others have one writer per element and give the same bits on every run.
+ *
+ * lnerf_raster_antialias_forward: image [B,H,W,C] -> out [B,H,W,C] (1 <= C <= 64; out must not be image); faces [F,3] are
+ *   the mesh's vertex ids.  The depth of a pixel is d = (b0*z0 + b1*z1) + b2*z2 on its face, -inf on background; larger is
+ *   nearer.  Pixel p looks at its neighbours inside the image in the order left, right, up, down, and evaluates the pair
+ *   (p, n) when their face_idx differ:
+ *     1. near = the pixel of larger depth, T its face; equal depths skip the pair.
+ *     2. horizontal pair: the line y = py.  For the edges (0,1), (1,2), (2,0) of T with projected ends (xa,ya), (xb,yb):
+ *          crosses iff (ya > py) != (yb > py);  x* = xa + (py - ya)*(xb - xa)/(yb - ya);
+ *          t = (x* - x_near)/(x_far - x_near)           (x_near, x_far: the two pixel centres)
+ *        the first edge in that order that crosses with 0 <= t <= 1 is taken; none: skip.  A vertical pair is the same
+ *        with x and y exchanged.
+ *     3. far is a face and both vertex ids of the taken edge occur in faces[far]: skip (an interior edge).
+ *     4. t < 0.5: near receives (0.5 - t)*(c_far - c_near); else far receives (t - 0.5)*(c_near - c_far); c = image.
+ *   out[p] = image[p] plus what lands on p, added in the neighbour order.  A pair is a function of its two pixels alone,
+ *   so each pixel evaluates its own pairs and both agree: no atomics.
+ * lnerf_raster_antialias_backward: grad_out [B,H,W,C] -> grad_image [B,H,W,C], OVERWRITTEN (gather form, one writer; its
+ *   own buffer), through the blend weights; and grad_face_xy [B,F,3,2], ADDED INTO, through t into the two corners of the
+ *   taken edge of T.  No gradient flows through the depths or through any decision.
+ *
+ * lnerf_raster_bary_backward: grad_bary [B*H*W,3] -> grad_face_xy, grad_face_z [B,F,3], both ADDED INTO.  The forward is
+ *   lnerf_rasterize's: w0 = e0/area, w1 = e1/area, w2 = 1 - w0 - w1, q_k = w_k/z_k, b_k = q_k/(q0 + q1 + q2), with w_k
+ *   recomputed from the pixel centre and the winning face (bary is not inverted).
+ * lnerf_interpolate_attributes_backward_bary: grad_bary[p,k] = sum_d attr[f,k,d] * dfeat[p,d], d ascending, 0 on
+ *   background; OVERWRITTEN.  attr [n_faces,3,D], 1 <= D <= 16: the half of lnerf_interpolate_attributes' backward that
+ *   lnerf_interpolate_attributes_backward does not give.
+ * lnerf_texture_map_backward_uv: mode 1 (bilinear) of lnerf_texture_map_forward only.  grad_uv[p] = sum_c dout[p,c] *
+ *   d texture / d(u,v) at the lookup's taps, OVERWRITTEN; an axis is 0 where its clamp is active (u or v outside [0,1], or
+ *   the texel position on or outside [0, R-1]) and both are 0 on background.  face_idx may be NULL (all foreground).
+ * lnerf_raster_prepare_batch_backward: grad_face_xy, grad_face_z -> grad_verts [n_verts,3], OVERWRITTEN: the sum over the
+ *   B views and over every face corner that references the vertex of the transpose of c = R (v - pos),
+ *   ix = cx*fx/(-cz), iy = cy*fy/(-cz), z = cz.  A corner whose three incoming gradients are 0 adds nothing.
+ *
+ * lnerf_mesh_umbrella: the face-weighted uniform Laplacian of x [n_verts,3] and its transpose, out [n_verts,3] (not x).
+ *   n_i = the number of face corners that hold vertex i.  transpose = 0:
+ *     (L x)_i = x_i - (1/(2 n_i)) * sum_{faces (i,j,k)} (x_j + x_k)
+ *   transpose = 1:
+ *     (L^T y)_i = y_i - sum_{faces (i,j,k)} (y_j/(2 n_j) + y_k/(2 n_k))
+ *   the sums over the corners i of every face; a vertex in no face gets x_i in both.  A face with an index outside
+ *   [0, n_verts) counts nowhere.  n_faces = 0 copies x.  The face terms are summed with float atomics into a zeroed
+ *   buffer of their own and subtracted from x in a last pass (their rounding is that of their own magnitude).  Scratch
+ *   (the degrees and that buffer): lnerf_mesh_umbrella_scratch_bytes() (0 = arguments out of range; 16-byte aligned). */
+int lnerf_raster_antialias_forward(const float *image, const int32_t *face_idx, const float *bary, const float *face_xy,
+                                   const float *face_z, const int32_t *faces, int B, int H, int W, int C, int n_faces,
+                                   float *out, lnerf_stream_t stream);
+int lnerf_raster_antialias_backward(const float *grad_out, const float *image, const int32_t *face_idx,
+                                    const float *bary, const float *face_xy, const float *face_z, const int32_t *faces,
+                                    int B, int H, int W, int C, int n_faces, float *grad_image, float *grad_face_xy,
+                                    lnerf_stream_t stream);
+int lnerf_raster_bary_backward(const float *grad_bary, const int32_t *face_idx, const float *face_xy,
+                               const float *face_z, int B, int H, int W, int n_faces, float *grad_face_xy,
+                               float *grad_face_z, lnerf_stream_t stream);
+int lnerf_interpolate_attributes_backward_bary(const int32_t *face_idx, const float *attr, const float *dfeat,
+                                               int n_pixels, int D, int n_faces, float *grad_bary,
+                                               lnerf_stream_t stream);
+int lnerf_texture_map_backward_uv(const float *uv, const int32_t *face_idx, const float *texture, const float *dout,
+                                  int n_pixels, int C, int R, float *grad_uv, lnerf_stream_t stream);
+int lnerf_raster_prepare_batch_backward(const float *grad_face_xy, const float *grad_face_z, const float *verts,
+                                        int n_verts, const int32_t *faces, int n_faces, const float *cams_dev, int B,
+                                        float *grad_verts, lnerf_stream_t stream);
+size_t lnerf_mesh_umbrella_scratch_bytes(int n_verts, int n_faces);
+int lnerf_mesh_umbrella(const float *x, int n_verts, const int32_t *faces, int n_faces, int transpose, void *scratch,
+                        size_t scratch_bytes, float *out, lnerf_stream_t stream);
+
 /* ---- shaded renders (shading = "lambertian" / "textureless"): the kernels around the field (csrc/shade.hip).  Additive
  * to ABI 7.  The normal is the upstream renderer's training normal, a central finite difference of sigma at six offset
  * points; its gradient is the field's ordinary backward at 7 m points.  All arithmetic is f32 + - * / sqrt in the order

@@ -172,6 +172,14 @@ _SIGNATURES = {
     "lnerf_mesh_filter": [_P, _I, _I, _P, _P, _Z, _P, _P, _P, _P],
     "lnerf_mesh_smooth_scratch_bytes": [_I, _I],
     "lnerf_mesh_smooth": [_P, _I, _P, _I, _I, _F, _F, _P, _Z, _P, _P, _P],
+    "lnerf_raster_antialias_forward": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
+    "lnerf_raster_antialias_backward": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P],
+    "lnerf_raster_bary_backward": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "lnerf_interpolate_attributes_backward_bary": [_P, _P, _P, _I, _I, _I, _P, _P],
+    "lnerf_texture_map_backward_uv": [_P, _P, _P, _P, _I, _I, _I, _P, _P],
+    "lnerf_raster_prepare_batch_backward": [_P, _P, _P, _I, _P, _I, _P, _I, _P, _P],
+    "lnerf_mesh_umbrella_scratch_bytes": [_I, _I],
+    "lnerf_mesh_umbrella": [_P, _I, _P, _I, _I, _P, _Z, _P, _P],
     "lnerf_fd_points": [_P, _F, _F, _L, _P, _P, _P, _P],
     "lnerf_shade_fd_forward": [_P, _P, _I, _P, _L, _I, _P, _I, _F, _P, _P, _P],
     "lnerf_shade_fd_backward": [_P, _P, _I, _P, _L, _I, _P, _I, _F, _P, _P, _P, _P, _P],
@@ -205,6 +213,7 @@ _RESTYPES = {
     "lnerf_mesh_components_scratch_bytes": _Z,
     "lnerf_mesh_filter_scratch_bytes": _Z,
     "lnerf_mesh_smooth_scratch_bytes": _Z,
+    "lnerf_mesh_umbrella_scratch_bytes": _Z,
 }
 
 _lib = None

@@ -26,6 +26,7 @@ RenderConfig = _cli.make_section("RenderConfig", (
     ("angle_front", float, 70, "azimuths within +-angle_front degrees count as the front view bucket"),
     ("backbone", str, "texture-mesh", "'texture-mesh' (latent texture) or 'texture-rgb-mesh' (RGB fine-tuning)"),
     ("batch_size", int, 1, "views rendered and guided per optimisation step (their gradients are averaged)"),
+    ("antialias", bool, False, "antialias the edges of every render: silhouettes become differentiable w.r.t. the vertices"),
 ), doc="mesh renderer")
 
 GuideConfig = _cli.make_section("GuideConfig", (
@@ -57,6 +58,10 @@ OptimConfig = _cli.make_section("OptimConfig", (
     ("lr", float, 1e-2, "Adam learning rate"),
     ("resume", bool, False, "continue from the experiment's latest checkpoint"),
     ("ckpt", Optional[str], None, "explicit checkpoint to load"),
+    ("disp_lr", float, 0.0, "Adam learning rate of the per-vertex offsets; 0 = the geometry stays fixed (the fork's "
+                            "switched-off value is 5e-5); needs render.antialias and the bilinear texture lookup"),
+    ("lap_weight", float, 100.0, "disp_lr > 0: weight of the mean squared Laplacian of the offsets"),
+    ("reg_weight", float, 10.0, "disp_lr > 0: weight of the mean squared offset"),
 ), doc="optimisation")
 
 LogConfig = _cli.make_section("LogConfig", (
@@ -136,6 +141,17 @@ class TrainConfig:
                              "exported texture" % self.log.mesh_bake_views)
         if self.render.batch_size < 1:
             raise ValueError("render.batch_size must be >= 1 (got %s)" % self.render.batch_size)
+        if not self.optim.disp_lr >= 0:
+            raise ValueError("optim.disp_lr must be >= 0 (got %s; 0 keeps the geometry fixed)" % self.optim.disp_lr)
+        for name in ("lap_weight", "reg_weight"):
+            if not getattr(self.optim, name) >= 0:
+                raise ValueError("optim.%s must be >= 0 (got %s)" % (name, getattr(self.optim, name)))
+        if self.optim.disp_lr > 0 and self.guide.texture_interpolation_mode != "bilinear":
+            raise ValueError("optim.disp_lr > 0 needs guide.texture_interpolation_mode bilinear (got %s): the lookup's "
+                             "gradient w.r.t. the UVs exists for that mode only" % self.guide.texture_interpolation_mode)
+        if self.optim.disp_lr > 0 and not self.render.antialias:
+            raise ValueError("optim.disp_lr > 0 needs render.antialias: without it a silhouette gives no gradient and "
+                             "only the texture slides over the surface")
         return self
 
 

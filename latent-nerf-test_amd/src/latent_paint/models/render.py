@@ -4,7 +4,9 @@ C-ABI raster kernels (csrc/raster.hip).  `render_views` / `render_views_texture`
 `render.batch_size`); the single-view methods are their B = 1 case, on the one tile-culled rasteriser.
 `interpolation_mode="mipmap"` is this project's own: the trilinear mip-mapped lookup of csrc/texmip.hip, for renders much
 smaller than their texture; with `mip_coverage` its pyramid is the coverage-weighted one of the same file, which keeps the
-texels no face covers out of every level."""
+texels no face covers out of every level.  Also this project's own: `verts` that require grad receive the image's gradient
+(csrc/rastergrad.hip: the transposes of projection, barycentrics, interpolation and the bilinear lookup), and
+`antialias_views` makes silhouettes differentiable; with plain vertices every call is what it was."""
 import math
 
 import torch
@@ -24,26 +26,40 @@ def _texture_shape(tex):
 
 
 class _InterpAttr(torch.autograd.Function):
+    """feat = sum_k bary_k attr_k.  The attributes' gradient always; the barycentrics' (lnerf_interpolate_attributes_
+    backward_bary) only when they are part of a graph, i.e. the vertices are being learned."""
+
     @staticmethod
     def forward(ctx, attr, face_idx, bary):
         P, D = face_idx.shape[0], attr.shape[-1]
         attr = attr.contiguous()
         feat = torch.empty(P, D, device=attr.device)
         _b.call("lnerf_interpolate_attributes", _p(face_idx), _p(bary), _chk(attr, "attr"), P, D, _p(feat), _stream())
-        ctx.save_for_backward(face_idx, bary)
+        ctx.save_for_backward(face_idx, bary, attr if ctx.needs_input_grad[2] else None)
         ctx.shape = attr.shape
         return feat
 
     @staticmethod
     def backward(ctx, dfeat):
-        face_idx, bary = ctx.saved_tensors
-        dattr = torch.zeros(ctx.shape, device=dfeat.device)
-        _b.call("lnerf_interpolate_attributes_backward", _p(face_idx), _p(bary), _chk(dfeat.contiguous(), "dfeat"),
-                face_idx.shape[0], ctx.shape[-1], _p(dattr), _stream())
-        return dattr, None, None
+        face_idx, bary, attr = ctx.saved_tensors
+        dfeat = dfeat.contiguous()
+        P, D = face_idx.shape[0], ctx.shape[-1]
+        dattr = dbary = None
+        if ctx.needs_input_grad[0]:
+            dattr = torch.zeros(ctx.shape, device=dfeat.device)
+            _b.call("lnerf_interpolate_attributes_backward", _p(face_idx), _p(bary), _chk(dfeat, "dfeat"), P, D,
+                    _p(dattr), _stream())
+        if ctx.needs_input_grad[2]:
+            dbary = torch.empty(P, 3, device=dfeat.device)
+            _b.call("lnerf_interpolate_attributes_backward_bary", _p(face_idx), _p(attr), _chk(dfeat, "dfeat"), P, D,
+                    attr.numel() // (3 * D), _p(dbary), _stream())
+        return dattr, None, dbary
 
 
 class _TextureMap(torch.autograd.Function):
+    """The point lookups.  The texture's gradient always; the UVs' (lnerf_texture_map_backward_uv, bilinear only) when
+    they are part of a graph."""
+
     @staticmethod
     def forward(ctx, tex, uv, face_idx, mode):
         C, R = _texture_shape(tex)
@@ -52,18 +68,143 @@ class _TextureMap(torch.autograd.Function):
         out = torch.empty(P, C, device=tex.device)
         _b.call("lnerf_texture_map_forward", _chk(uv, "uv"), _p(face_idx), _chk(tex, "texture"), P, C, R, mode, _p(out),
                 _stream())
-        ctx.save_for_backward(uv, face_idx)
+        ctx.save_for_backward(uv, face_idx, tex if ctx.needs_input_grad[1] else None)
         ctx.meta = (tex.shape, mode)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        uv, face_idx = ctx.saved_tensors
+        uv, face_idx, tex = ctx.saved_tensors
         shape, mode = ctx.meta
-        dtex = torch.zeros(shape, device=dout.device)
-        _b.call("lnerf_texture_map_backward", _p(uv), _p(face_idx), _chk(dout.contiguous(), "dout"), uv.shape[0],
-                shape[1], shape[2], mode, _p(dtex), _stream())
-        return dtex, None, None, None
+        dout = dout.contiguous()
+        dtex = duv = None
+        if ctx.needs_input_grad[0]:
+            dtex = torch.zeros(shape, device=dout.device)
+            _b.call("lnerf_texture_map_backward", _p(uv), _p(face_idx), _chk(dout, "dout"), uv.shape[0], shape[1],
+                    shape[2], mode, _p(dtex), _stream())
+        if ctx.needs_input_grad[1]:
+            if mode != _MODES["bilinear"]:
+                raise ValueError("texture_map: the UV gradient exists for the bilinear lookup only")
+            duv = torch.empty_like(uv)
+            _b.call("lnerf_texture_map_backward_uv", _p(uv), _p(face_idx), _p(tex), _chk(dout, "dout"), uv.shape[0],
+                    shape[1], shape[2], _p(duv), _stream())
+        return dtex, duv, None, None
+
+
+# ---- the geometry half of the backward pass (csrc/rastergrad.hip): vertices -> projected faces -> barycentrics
+class _PrepareBatch(torch.autograd.Function):
+    """lnerf_raster_prepare_batch with its transpose: verts [V,3] -> (face_z [B,F,3], face_xy [B,F,3,2], face_box)."""
+
+    @staticmethod
+    def forward(ctx, verts, faces32, cams, B, H, W):
+        F = faces32.shape[0]
+        face_z = torch.empty(B, F, 3, device=verts.device)
+        face_xy = torch.empty(B, F, 3, 2, device=verts.device)
+        face_box = torch.empty(B, F, 4, device=verts.device, dtype=torch.int16)
+        _b.call("lnerf_raster_prepare_batch", _chk(verts, "verts"), verts.shape[0], _chk(faces32, "faces", torch.int32),
+                F, _chk(cams, "cams"), B, H, W, _p(face_z), _p(face_xy), _p(face_box), _stream())
+        ctx.save_for_backward(verts, faces32, cams)
+        ctx.mark_non_differentiable(face_box)
+        return face_z, face_xy, face_box
+
+    @staticmethod
+    def backward(ctx, dz, dxy, _dbox):
+        verts, faces32, cams = ctx.saved_tensors
+        B, F = cams.shape[0], faces32.shape[0]
+        dz = torch.zeros(B, F, 3, device=verts.device) if dz is None else dz.contiguous()
+        dxy = torch.zeros(B, F, 3, 2, device=verts.device) if dxy is None else dxy.contiguous()
+        dverts = torch.empty_like(verts)
+        _b.call("lnerf_raster_prepare_batch_backward", _chk(dxy, "grad_face_xy"), _chk(dz, "grad_face_z"), _p(verts),
+                verts.shape[0], _p(faces32), F, _p(cams), B, _p(dverts), _stream())
+        return dverts, None, None, None, None, None
+
+
+class _RasterizeBatch(torch.autograd.Function):
+    """lnerf_rasterize_batch; the winners are discrete, the barycentrics carry lnerf_raster_bary_backward."""
+
+    @staticmethod
+    def forward(ctx, face_z, face_xy, face_box, H, W):
+        B, F = face_z.shape[0], face_z.shape[1]
+        face_idx = torch.empty(B * H * W, device=face_z.device, dtype=torch.int32)
+        bary = torch.empty(B * H * W, 3, device=face_z.device)
+        _b.call("lnerf_rasterize_batch", B, H, W, _p(face_z), _p(face_xy), _p(face_box), F, _p(face_idx), _p(bary),
+                _stream())
+        ctx.save_for_backward(face_z, face_xy, face_idx)
+        ctx.dims = (B, H, W, F)
+        ctx.mark_non_differentiable(face_idx)
+        return face_idx, bary
+
+    @staticmethod
+    def backward(ctx, _didx, dbary):
+        face_z, face_xy, face_idx = ctx.saved_tensors
+        B, H, W, F = ctx.dims
+        dz, dxy = torch.zeros_like(face_z), torch.zeros_like(face_xy)
+        if dbary is not None:
+            _b.call("lnerf_raster_bary_backward", _chk(dbary.contiguous(), "grad_bary"), _p(face_idx), _p(face_xy),
+                    _p(face_z), B, H, W, F, _p(dxy), _p(dz), _stream())
+        return dz, dxy, None, None, None
+
+
+class _Antialias(torch.autograd.Function):
+    """lnerf_raster_antialias_forward / _backward on image [B,H,W,C]."""
+
+    @staticmethod
+    def forward(ctx, image, face_xy, face_idx, bary, face_z, faces32):
+        B, H, W, C = image.shape
+        F = faces32.shape[0]
+        image = image.contiguous()
+        out = torch.empty_like(image)
+        _b.call("lnerf_raster_antialias_forward", _chk(image, "image"), _chk(face_idx, "face_idx", torch.int32),
+                _chk(bary, "bary"), _chk(face_xy, "face_xy"), _chk(face_z, "face_z"),
+                _chk(faces32, "faces", torch.int32), B, H, W, C, F, _p(out), _stream())
+        ctx.save_for_backward(image, face_xy, face_idx, bary, face_z, faces32)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        image, face_xy, face_idx, bary, face_z, faces32 = ctx.saved_tensors
+        B, H, W, C = image.shape
+        dimage = torch.empty_like(image)
+        dxy = torch.zeros_like(face_xy)
+        _b.call("lnerf_raster_antialias_backward", _chk(dout.contiguous(), "grad_out"), _p(image), _p(face_idx), _p(bary),
+                _p(face_xy), _p(face_z), _p(faces32), B, H, W, C, faces32.shape[0], _p(dimage), _p(dxy), _stream())
+        return dimage, dxy, None, None, None, None
+
+
+class _Umbrella(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, faces32):
+        ctx.save_for_backward(faces32)
+        return _umbrella(x, faces32, False)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _umbrella(dy, ctx.saved_tensors[0], True), None
+
+
+def _umbrella(x, faces32, transpose):
+    x = x.float().contiguous()
+    V, F = x.shape[0], faces32.shape[0]
+    nbytes = _b.get_lib().lnerf_mesh_umbrella_scratch_bytes(V, F)
+    scratch = torch.empty(max(nbytes, 16), device=x.device, dtype=torch.uint8)
+    out = torch.empty_like(x)
+    _b.call("lnerf_mesh_umbrella", _chk(x, "x"), V, _chk(faces32, "faces", torch.int32), F, int(bool(transpose)),
+            _p(scratch), nbytes, _p(out), _stream())
+    return out
+
+
+def mesh_umbrella(x, faces):
+    """The face-weighted uniform Laplacian of x [V,3] on the mesh `faces` [F,3] (lnerf_mesh_umbrella):
+    (L x)_i = x_i - (1 / (2 n_i)) sum over the faces (i,j,k) of (x_j + x_k), n_i the faces at i; a vertex in no face keeps
+    x_i.  Differentiable w.r.t. x: the backward is the same call with the transpose flag.  No dense matrix."""
+    if x.dim() != 2 or x.shape[1] != 3:
+        raise ValueError("mesh_umbrella: x must be [V,3] (got %s)" % (tuple(x.shape),))
+    return _Umbrella.apply(x, faces.to(x.device).to(torch.int32).contiguous())
+
+
+def _learns(verts):
+    """The vertices are part of a graph that is being recorded: the render then carries their gradient."""
+    return torch.is_grad_enabled() and verts.requires_grad
 
 
 def uv_footprint(face_idx, face_xy, face_z, face_uv, B, H, W):
@@ -145,7 +286,7 @@ class _TextureMip(torch.autograd.Function):
 
 class Renderer:
     def __init__(self, device, dim=(224, 224), interpolation_mode="nearest", max_mip_level=-1, lod_bias=0.0,
-                 mip_coverage=False, coverage_ring=1):
+                 mip_coverage=False, coverage_ring=1, antialias=False):
         assert interpolation_mode in ["nearest", "bilinear", "bicubic", "mipmap"], \
             "no interpolation mode %s" % interpolation_mode
         if not math.isfinite(lod_bias):
@@ -160,6 +301,7 @@ class Renderer:
         self.lod_bias = float(lod_bias)                # "mipmap" only: added to the level log2(footprint in texels)
         self.mip_coverage = bool(mip_coverage)         # "mipmap" only: the coverage-weighted pyramid (csrc/texmip.hip)
         self.coverage_ring = int(coverage_ring)        # ... rounds the covered texels are grown by (the bilinear taps' reach)
+        self.antialias = bool(antialias)               # the models antialias their renders' edges (antialias_views)
         self._coverage = {}                            # (side, levels, UV layout) -> (w0 [R,R] f32, wpyr [S])
         self.fov = math.pi / 3                         # kal.render.camera.generate_perspective_projection(np.pi / 3)
         self.dim = dim
@@ -204,6 +346,10 @@ class Renderer:
         verts = verts.to(self.device).float().contiguous()
         faces32 = faces.to(self.device).to(torch.int32).contiguous()
         F = faces32.shape[0]
+        if _learns(verts):   # the same two launches, as autograd nodes that carry the geometry backward
+            face_z, face_xy, face_box = _PrepareBatch.apply(verts, faces32, cams, B, H, W)
+            face_idx, bary = _RasterizeBatch.apply(face_z, face_xy, face_box, H, W)
+            return face_idx, bary, B, H, W, face_xy, face_z
         face_z = torch.empty(B, F, 3, device=self.device)
         face_xy = torch.empty(B, F, 3, 2, device=self.device)
         face_box = torch.empty(B, F, 4, device=self.device, dtype=torch.int16)
@@ -230,7 +376,8 @@ class Renderer:
 
     def render_views(self, mesh, face_attributes, elev, azim, radius, look_at_height=0.0):
         """B views in one call: elev, azim, radius are sequences of length B.  face_attributes [1,F,3,D] ->
-        (image [B,D,H,W], mask [B,1,H,W]); differentiable w.r.t. the attributes (their gradient sums over the views)."""
+        (image [B,D,H,W], mask [B,1,H,W]); differentiable w.r.t. the attributes (their gradient sums over the views) and,
+        when mesh.vertices require grad, w.r.t. the vertices inside every face (silhouettes: antialias_views)."""
         face_idx, bary, B, H, W = self._rasterize_views(mesh.vertices, mesh.faces, elev, azim, radius, look_at_height,
                                                         self.dim)
         feat = _InterpAttr.apply(face_attributes[0], face_idx, bary)
@@ -238,15 +385,25 @@ class Renderer:
         return feat.reshape(B, H, W, -1).permute(0, 3, 1, 2), mask.permute(0, 3, 1, 2)
 
     def render_views_texture(self, verts, faces, uv_face_attr, texture_map, elev, azim, radius, look_at_height=0.0,
-                             dims=None, white_background=False):
+                             dims=None, white_background=False, return_state=False):
         """B views of the textured mesh in one call -> (image [B,C,H,W], mask [B,1,H,W]).  The batch is B*H*W flat
-        pixels through the single-view kernels; the texture is shared, so its gradient sums over the views."""
+        pixels through the single-view kernels; the texture is shared, so its gradient sums over the views.
+        `verts` that require grad receive the image's gradient through the UVs (bilinear lookup only: any other mode
+        raises before a launch); the mask stays hard, so a silhouette moves only under antialias_views.
+        return_state: the rasterisation state of _rasterize_views_faces follows as a third result."""
         dims = self.dim if dims is None else dims
-        face_idx, bary, B, H, W, face_xy, face_z = self._rasterize_views_faces(verts, faces, elev, azim, radius,
-                                                                               look_at_height, dims)
+        learns = _learns(verts)
+        if learns and self.interpolation_mode != "bilinear":
+            raise ValueError("render_views_texture: vertex gradients need interpolation_mode bilinear (got %s)"
+                             % self.interpolation_mode)
+        state = self._rasterize_views_faces(verts, faces, elev, azim, radius, look_at_height, dims)
+        face_idx, bary, B, H, W, face_xy, face_z = state
         face_uv = uv_face_attr[0].detach().contiguous()
-        with torch.no_grad():                          # uv_features.detach() in the reference (:61)
+        if learns:
             uv = _InterpAttr.apply(face_uv, face_idx, bary).contiguous()
+        else:
+            with torch.no_grad():                      # uv_features.detach() in the reference (:61)
+                uv = _InterpAttr.apply(face_uv, face_idx, bary).contiguous()
         if self.interpolation_mode == "mipmap":
             R = texture_map.shape[-1]
             L = mip_levels(R, self.max_mip_level)      # per call: render_test passes the decoded, larger texture
@@ -259,7 +416,24 @@ class Renderer:
         image = image.reshape(B, H, W, -1) * mask
         if white_background:
             image = image + 1 * (1 - mask)
+        if return_state:
+            return image.permute(0, 3, 1, 2), mask.permute(0, 3, 1, 2), state
         return image.permute(0, 3, 1, 2), mask.permute(0, 3, 1, 2)
+
+    def antialias_views(self, image, raster_state, faces):
+        """Edge antialiasing of a rendered batch (lnerf_raster_antialias_forward): image [B,C,H,W] -> [B,C,H,W].  Across
+        every depth discontinuity between neighbouring pixels the nearer face's edge is located between the two pixel
+        centres and the pixel it cuts is blended with its neighbour by the covered fraction, which makes the image a
+        differentiable function of the projected edge: the gradient reaches the image and, through raster_state's
+        face_xy, the vertices.  raster_state: the tuple _rasterize_views_faces returned for these views; faces: the
+        mesh's [F,3] vertex ids (edges between faces that share both vertices are interior and left alone)."""
+        face_idx, bary, B, H, W, face_xy, face_z = raster_state
+        if image.dim() != 4 or image.shape[0] != B or tuple(image.shape[2:]) != (H, W):
+            raise ValueError("antialias_views: image must be [%d,C,%d,%d] (got %s)" % (B, H, W, tuple(image.shape)))
+        faces32 = faces.to(self.device).to(torch.int32).contiguous()
+        out = _Antialias.apply(image.float().permute(0, 2, 3, 1).contiguous(), face_xy, face_idx, bary.detach(),
+                               face_z.detach(), faces32)
+        return out.permute(0, 3, 1, 2)
 
     def render_single_view(self, mesh, face_attributes, elev=0, azim=0, radius=2, look_at_height=0.0):
         """face_attributes [1,F,3,D] -> (image [1,D,H,W], mask [1,1,H,W]); differentiable w.r.t. the attributes."""

@@ -21,7 +21,7 @@ from ... import view_bake
 from ...latent_nerf.raymarching.raymarching import bake_view_poses, pull_push_fill
 from ...uv_atlas import chart_atlas, check_atlas_choice, per_triangle_atlas
 from .mesh import Mesh
-from .render import Renderer, texture_coverage
+from .render import Renderer, mesh_umbrella, texture_coverage
 
 # latent -> RGB linear estimate (rows = latent channels), the table of textured_mesh.py:34-40
 LATENT_RGB_ROWS = ((0.298, 0.207, 0.208), (0.187, 0.286, 0.173), (-0.158, 0.189, 0.264), (-0.184, -0.271, -0.473))
@@ -63,9 +63,18 @@ class TexturedMeshModel(nn.Module):
                                  max_mip_level=getattr(opt.guide, "texture_max_mip_level", -1),
                                  lod_bias=getattr(opt.guide, "texture_lod_bias", 0.0),
                                  mip_coverage=getattr(opt.guide, "texture_mip_coverage", False),
-                                 coverage_ring=getattr(opt.guide, "texture_coverage_ring", 1))
+                                 coverage_ring=getattr(opt.guide, "texture_coverage_ring", 1),
+                                 antialias=getattr(getattr(opt, "render", None), "antialias", False))
         self.env_sphere, self.mesh = self.init_meshes()
         self.background_sphere_colors, self.texture_img, self.texture_img_rgb_finetune = self.init_paint()
+        # geometry learning (optim.disp_lr > 0): one offset per vertex, the fork's switched-off `displacement`
+        # (src/latent_paint_mesh/models/textured_mesh.py:77).  Registered only then: default checkpoints keep their keys.
+        optim = getattr(opt, "optim", None)
+        self.learn_geometry = float(getattr(optim, "disp_lr", 0.0)) > 0.0
+        self.lap_weight = float(getattr(optim, "lap_weight", 0.0))
+        self.reg_weight = float(getattr(optim, "reg_weight", 0.0))
+        if self.learn_geometry:
+            self.displacement = nn.Parameter(torch.zeros_like(self.mesh.vertices.to(self.device).float()))
         self.vt, self.ft = self.init_texture_map()
         # per-face-vertex UVs [1,F,3,2] (kal.ops.mesh.index_vertices_by_faces in the reference, :48-50)
         self.face_attributes = self.vt[self.ft.long()][None].detach()
@@ -148,6 +157,30 @@ class TexturedMeshModel(nn.Module):
         texture = self.texture_img if self.latent_mode else self.texture_img_rgb_finetune
         return [self.background_sphere_colors, texture]
 
+    def get_geometry_params(self):
+        """What the geometry group of the optimiser trains (at optim.disp_lr): the vertex offsets; [] when off."""
+        return [self.displacement] if self.learn_geometry else []
+
+    def surface_vertices(self):
+        """The vertices that are rendered and exported: the mesh's own, plus the learned offsets when geometry is on."""
+        if not self.learn_geometry:
+            return self.mesh.vertices
+        return self.mesh.vertices.to(self.device).float() + self.displacement
+
+    def geometry_loss(self):
+        """lap_weight * mean_i |(L d)_i|^2 + reg_weight * mean_i |d_i|^2 of the offsets d, L the face-weighted uniform
+        Laplacian (render.mesh_umbrella: no dense matrix, no inverse).  The fork's term
+        (src/latent_paint_mesh/models/textured_mesh.py:314-317) with its dense V x V `L` replaced, and a MEAN per vertex
+        where the fork sums, so that the weights do not depend on the size of the mesh."""
+        d = self.displacement
+        lap = mesh_umbrella(d, self.mesh.faces)
+        return self.lap_weight * lap.square().sum(-1).mean() + self.reg_weight * d.square().sum(-1).mean()
+
+    def _antialias(self, image, coverage, state):
+        """Edge-antialiased (image, mask) of one render: both go through the pass as one [B,C+1,H,W] batch."""
+        both = self.renderer.antialias_views(torch.cat([image, coverage], dim=1), state, self.mesh.faces)
+        return both[:, :-1], both[:, -1:]
+
     # ------------------------------------------------------------------ rendering
     def _view(self, theta, phi, radius):
         """Scalars (one view) or sequences of one length B -> the keyword arguments of Renderer.render_views*."""
@@ -169,36 +202,46 @@ class TexturedMeshModel(nn.Module):
     def render_train(self, theta, phi, radius):
         """-> {'image' [B,C,h,w], 'mask' [B,1,h,w], 'background', 'foreground'}; C = 4 latents (or 3 RGB when
         fine-tuning).  The rasterisation itself carries no gradient: 'image' is differentiable w.r.t. the texture
-        (under the mesh) and the background colours (elsewhere)."""
+        (under the mesh) and the background colours (elsewhere).
+        With render.antialias the composite and the coverage are edge-antialiased with the mesh's own raster state
+        ('image' and 'mask' are then the antialiased ones); with optim.disp_lr > 0 the mesh is rendered at
+        vertices + displacement, 'image' and 'mask' are differentiable w.r.t. the offsets (inside the faces through the
+        UVs, at silhouettes through the antialiasing) and 'geometry_loss' (geometry_loss(), a scalar) is added."""
         if self.latent_mode:
             texture, sky_colors = self.texture_img, self.background_sphere_colors
         else:
             texture = self.texture_img_rgb_finetune
             sky_colors = self.background_sphere_colors @ self.linear_rgb_estimator
         view = self._view(theta, phi, radius)
-        foreground, coverage = self.renderer.render_views_texture(
-            self.mesh.vertices, self.mesh.faces, self.face_attributes, texture, **view)
+        foreground, coverage, state = self.renderer.render_views_texture(
+            self.surface_vertices(), self.mesh.faces, self.face_attributes, texture, return_state=True, **view)
         background, _ = self.renderer.render_views(self.env_sphere, sky_colors, **view)
         coverage = coverage.detach()
         image = background * (1 - coverage) + foreground * coverage
+        if self.renderer.antialias:
+            image, coverage = self._antialias(image, coverage, state)
         out = {"image": image, "mask": coverage, "background": background, "foreground": foreground}
         if self.latent_mode and coverage.shape[-1] != LATENT_SIDE:
             # the diffusion model takes LATENT_SIDE x LATENT_SIDE latents whatever the render size
             out = {k: F.interpolate(v, (LATENT_SIDE, LATENT_SIDE), mode="bicubic") for k, v in out.items()}
+        if self.learn_geometry:
+            out["geometry_loss"] = self.geometry_loss()
         return out
 
     def render_test(self, theta, phi, radius, decode_func=None, dims=None):
         """Evaluation view: the latent texture is decoded to RGB first (`decode_func` = the guidance's
-        `decode_latents`), then rendered at `dims` on a white background."""
+        `decode_latents`), then rendered at `dims` on a white background; edge-antialiased with render.antialias."""
         if self.latent_mode:
             if decode_func is None:
                 raise ValueError("decode function was not supplied to decode the latent texture image")
             texture = decode_func(self.texture_img)
         else:
             texture = self.texture_img_rgb_finetune
-        image, coverage = self.renderer.render_views_texture(
-            self.mesh.vertices, self.mesh.faces, self.face_attributes, texture, dims=dims, white_background=True,
-            **self._view(theta, phi, radius))
+        image, coverage, state = self.renderer.render_views_texture(
+            self.surface_vertices(), self.mesh.faces, self.face_attributes, texture, dims=dims, white_background=True,
+            return_state=True, **self._view(theta, phi, radius))
+        if self.renderer.antialias:
+            image, coverage = self._antialias(image, coverage, state)
         return {"image": image, "texture_map": texture, "mask": coverage}
 
     # ------------------------------------------------------------------ export
@@ -243,7 +286,8 @@ class TexturedMeshModel(nn.Module):
         else:
             rgb = self.texture_img_rgb_finetune
         if fill == "pullpush":
-            covered = texture_coverage(self.mesh.vertices, self.mesh.faces, self.face_attributes[0], rgb.shape[-1], ring=0)
+            covered = texture_coverage(self.surface_vertices(), self.mesh.faces, self.face_attributes[0], rgb.shape[-1],
+                                       ring=0)
             rgb = pull_push_fill(rgb[0].float(), covered.float())[0][None]
         albedo = (rgb[0].permute(1, 2, 0).clamp(0, 1).cpu().numpy() * 255).astype(np.uint8)
         result = {"rgb": rgb[0]}
@@ -267,14 +311,14 @@ class TexturedMeshModel(nn.Module):
         # (the atlas is decoded already: render_test's decoder hands it back; the RGB backbone renders its own texture)
         images = self.render_test(view["elev"], view["azim"], view["radius"], decode_func=lambda _t: rgb,
                                   dims=(side, side))["image"]
-        baked = view_bake.bake_views(self.mesh.vertices, self.mesh.faces, self.vt, self.ft, images.clamp(0, 1), cams,
+        baked = view_bake.bake_views(self.surface_vertices(), self.mesh.faces, self.vt, self.ft, images.clamp(0, 1), cams,
                                      rgb.shape[-1], fallback=rgb[0].float().clamp(0, 1), fill=fill, unseen=unseen,
                                      blend=blend[0], exposure=blend[1], band_sigma=blend[2])
         return {"view_rgb": baked["rgb"], "view_weight": baked["view_weight"], "view_count": baked["view_count"],
                 "mask": baked["mask"], **{k: baked[k] for k in ("view_gains", "view_best") if k in baked}}
 
     def _write_obj(self, path):
-        v = self.mesh.vertices.cpu().numpy()
+        v = self.surface_vertices().detach().cpu().numpy()
         f = self.mesh.faces.cpu().numpy() + 1
         vt = self.vt.cpu().numpy()
         ft = self.ft.cpu().numpy() + 1

@@ -87,8 +87,10 @@ class Trainer:
         return [self.diffusion.get_text_embeds("%s, %s view" % (text, word)) for word in DIRECTION_WORDS]
 
     def init_optimizer(self):
-        return FusedAdam([{"params": self.mesh_model.get_params(), "lr": self.cfg.optim.lr}], betas=(0.9, 0.99),
-                         eps=1e-15)
+        groups = [{"params": self.mesh_model.get_params(), "lr": self.cfg.optim.lr}]
+        if self.mesh_model.get_geometry_params():   # optim.disp_lr > 0: the vertex offsets, at their own rate
+            groups.append({"params": self.mesh_model.get_geometry_params(), "lr": self.cfg.optim.disp_lr})
+        return FusedAdam(groups, betas=(0.9, 0.99), eps=1e-15)
 
     def init_dataloaders(self):
         r, lg = self.cfg.render, self.cfg.log
@@ -142,6 +144,8 @@ class Trainer:
         if k > 1:
             grad = grad / k
         pred.backward(gradient=grad)
+        if "geometry_loss" in out:   # optim.disp_lr > 0: the regulariser of the vertex offsets (a graph of its own)
+            out["geometry_loss"].backward()
         return pred, grad
 
     # ------------------------------------------------------------------ evaluation
@@ -231,6 +235,12 @@ class Trainer:
         weights = state["model"] if "model" in state else state      # bare state dicts are accepted too
         if not self.mesh_model.latent_mode:
             weights["texture_img_rgb_finetune"] = self._rgb_texture_from_latents(weights["texture_img"])
+        if self.mesh_model.learn_geometry and "displacement" not in weights:
+            self.log("checkpoint %s has no vertex offsets: geometry learning starts from zero offsets" % checkpoint)
+            weights["displacement"] = torch.zeros_like(self.mesh_model.displacement)
+        elif not self.mesh_model.learn_geometry and "displacement" in weights:
+            raise ValueError("checkpoint %s holds learned vertex offsets: load it with --optim.disp_lr > 0 (with 0 its "
+                             "texture would be rendered on the undisplaced mesh)" % checkpoint)
         if "model" not in state:
             self.mesh_model.load_state_dict(weights)
             return

@@ -6,26 +6,23 @@
 // per-face-vertex attributes, face_idx = -1 on background, texture lookup = grid_sample(align_corners=False,
 // padding 'border') on (u, 1 - v).
 #include "common.h"
+#include "raster_shared.h"
 #include "tex_shared.h"
 
 namespace lnerf {
 
-struct Cam {
-    float rot[9];   // rows: camera x, y, z axes in world space
-    float pos[3];
-    float fx, fy;   // 1 / tan(fov/2) (/ ratio)
-};
-
-// camera-space z and NDC xy of one face corner: the arithmetic both prepare kernels share
-__device__ __forceinline__ void prepare_corner(const float *__restrict__ verts, int v, const Cam &cam, float &cz,
-                                               float &ix, float &iy) {
-    const float x = verts[v * 3] - cam.pos[0], y = verts[v * 3 + 1] - cam.pos[1], z = verts[v * 3 + 2] - cam.pos[2];
-    const float cx = fmaf(cam.rot[0], x, fmaf(cam.rot[1], y, cam.rot[2] * z));
-    const float cy = fmaf(cam.rot[3], x, fmaf(cam.rot[4], y, cam.rot[5] * z));
-    cz = fmaf(cam.rot[6], x, fmaf(cam.rot[7], y, cam.rot[8] * z));
-    // image = (x * fx, y * fy) / (z * -1)
-    ix = cx * cam.fx / (-cz);
-    iy = cy * cam.fy / (-cz);
+// cam_project (raster_shared.h) of the three corners of face f, written to slot `at` of face_z / face_xy and returned
+__device__ __forceinline__ void prepare_face(const float *__restrict__ verts, const int32_t *__restrict__ faces, int f,
+                                             const Cam &cam, int64_t at, float *__restrict__ face_z,
+                                             float *__restrict__ face_xy, float x[3], float y[3], float z[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float *v = verts + faces[f * 3 + k] * 3;
+        const CamPoint c = cam_project(cam.rec, v[0], v[1], v[2]);
+        face_z[at * 3 + k] = z[k] = c.z;
+        face_xy[(at * 3 + k) * 2] = x[k] = c.x;
+        face_xy[(at * 3 + k) * 2 + 1] = y[k] = c.y;
+    }
 }
 
 __global__ void __launch_bounds__(256)
@@ -33,14 +30,8 @@ k_raster_prepare(const float *__restrict__ verts, const int32_t *__restrict__ fa
                  float *__restrict__ face_z, float *__restrict__ face_xy) {
     const int f = blockIdx.x * 256 + threadIdx.x;
     if (f >= F) return;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        float cz, ix, iy;
-        prepare_corner(verts, faces[f * 3 + k], cam, cz, ix, iy);
-        face_z[f * 3 + k] = cz;
-        face_xy[(f * 3 + k) * 2] = ix;
-        face_xy[(f * 3 + k) * 2 + 1] = iy;
-    }
+    float x[3], y[3], z[3];
+    prepare_face(verts, faces, f, cam, f, face_z, face_xy, x, y, z);
 }
 
 // The pixel box of a face (the rule is stated in include/lnerf_hip.h): inclusive (j_lo, j_hi, i_lo, i_hi), padded by one
@@ -50,8 +41,7 @@ struct alignas(8) Box { int16_t j_lo, j_hi, i_lo, i_hi; };
 __device__ __forceinline__ Box face_box(const float x[3], const float y[3], const float z[3], int H, int W) {
     const Box empty = {0, -1, 0, -1};
     if (!(z[0] < 0.f && z[1] < 0.f && z[2] < 0.f)) return empty;   // k_rasterize rejects it: behind the camera
-    const float area = (x[1] - x[0]) * (y[2] - y[0]) - (x[2] - x[0]) * (y[1] - y[0]);
-    if (area == 0.f) return empty;                                  // ... or degenerate
+    if (face_area(x[0], y[0], x[1], y[1], x[2], y[2]) == 0.f) return empty;   // ... or degenerate
     const float big = 3.4028234664e38f;
     bool finite = true;
 #pragma unroll
@@ -60,10 +50,10 @@ __device__ __forceinline__ Box face_box(const float x[3], const float y[3], cons
     const float xmin = fminf(fminf(x[0], x[1]), x[2]), xmax = fmaxf(fmaxf(x[0], x[1]), x[2]);
     const float ymin = fminf(fminf(y[0], y[1]), y[2]), ymax = fmaxf(fmaxf(y[0], y[1]), y[2]);
     const float Wf = (float)W, Hf = (float)H;
-    const float j_lo = fmaxf(floorf(((xmin + 1.0f) * Wf - 1.0f) * 0.5f) - 1.0f, 0.0f);
-    const float j_hi = fminf(ceilf(((xmax + 1.0f) * Wf - 1.0f) * 0.5f) + 1.0f, Wf - 1.0f);
-    const float i_lo = fmaxf(floorf(((1.0f - ymax) * Hf - 1.0f) * 0.5f) - 1.0f, 0.0f);
-    const float i_hi = fminf(ceilf(((1.0f - ymin) * Hf - 1.0f) * 0.5f) + 1.0f, Hf - 1.0f);
+    const float j_lo = fmaxf(floorf(ndc_to_col(xmin, Wf)) - 1.0f, 0.0f);
+    const float j_hi = fminf(ceilf(ndc_to_col(xmax, Wf)) + 1.0f, Wf - 1.0f);
+    const float i_lo = fmaxf(floorf(ndc_to_row(ymax, Hf)) - 1.0f, 0.0f);
+    const float i_hi = fminf(ceilf(ndc_to_row(ymin, Hf)) + 1.0f, Hf - 1.0f);
     if (j_lo > j_hi || i_lo > i_hi) return empty;                   // wholly off the image
     return Box{(int16_t)j_lo, (int16_t)j_hi, (int16_t)i_lo, (int16_t)i_hi};
 }
@@ -76,48 +66,29 @@ k_raster_prepare_batch(const float *__restrict__ verts, const int32_t *__restric
     const int f = blockIdx.x * 256 + threadIdx.x;
     if (f >= F) return;
     const int b = blockIdx.y;
-    Cam cam;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) cam.rot[i] = cams[b * 14 + i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) cam.pos[i] = cams[b * 14 + 9 + i];
-    cam.fx = cams[b * 14 + 12];
-    cam.fy = cams[b * 14 + 13];
     const int64_t bf = (int64_t)b * F + f;
     float x[3], y[3], z[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        prepare_corner(verts, faces[f * 3 + k], cam, z[k], x[k], y[k]);
-        face_z[bf * 3 + k] = z[k];
-        face_xy[(bf * 3 + k) * 2] = x[k];
-        face_xy[(bf * 3 + k) * 2 + 1] = y[k];
-    }
+    prepare_face(verts, faces, f, cam_read(cams + b * CAM_FLOATS), bf, face_z, face_xy, x, y, z);
     boxes[bf] = face_box(x, y, z, H, W);
 }
 
 constexpr int RTILE = 128;  // faces per LDS tile
 
-// What one pixel does with one face, shared by both rasterisers: inside test, perspective-correct weights and depth,
-// and the z-buffer update (strictly closer wins, so of equal depths the face tested first -- the lower index -- stays).
+// What one pixel does with one face, shared by both rasterisers: inside test, perspective-correct weights and depth (the
+// two stages of raster_shared.h), and the z-buffer update (strictly closer wins, so of equal depths the lower index stays).
 __device__ __forceinline__ void raster_face_test(float px, float py, float x0, float y0, float x1, float y1, float x2,
                                                  float y2, float z0, float z1, float z2, int f, float &best_z,
                                                  int &best_f, float &bw0, float &bw1, float &bw2) {
     if (!(z0 < 0.f && z1 < 0.f && z2 < 0.f)) return;  // behind the camera
-    const float area = (x1 - x0) * (y2 - y0) - (x2 - x0) * (y1 - y0);
+    const float area = face_area(x0, y0, x1, y1, x2, y2);
     if (area == 0.f) return;
-    const float e0 = (x1 - px) * (y2 - py) - (x2 - px) * (y1 - py);  // weight of vertex 0
-    const float e1 = (x2 - px) * (y0 - py) - (x0 - px) * (y2 - py);  // weight of vertex 1
-    const float inv = 1.0f / area;
-    const float w0 = e0 * inv, w1 = e1 * inv, w2 = 1.0f - w0 - w1;
-    if (w0 < 0.f || w1 < 0.f || w2 < 0.f) return;
-    // perspective-correct weights and depth
-    const float q0 = w0 / z0, q1 = w1 / z1, q2 = w2 / z2;
-    const float qs = q0 + q1 + q2;
-    const float z = 1.0f / qs;   // (sum w_k / z_k)^-1
-    if (z > best_z) {            // strictly closer; ties keep the lower face index
-        best_z = z;
+    const FaceW w = face_weights(area, px, py, x0, y0, x1, y1, x2, y2);
+    if (w.w0 < 0.f || w.w1 < 0.f || w.w2 < 0.f) return;
+    const FaceP p = face_perspective(w, z0, z1, z2);   // only inside the face
+    if (p.z > best_z) {          // strictly closer; ties keep the lower face index
+        best_z = p.z;
         best_f = f;
-        bw0 = q0 * z; bw1 = q1 * z; bw2 = q2 * z;
+        bw0 = p.b0; bw1 = p.b1; bw2 = p.b2;
     }
 }
 
@@ -130,8 +101,7 @@ k_rasterize(int H, int W, const float *__restrict__ face_z, const float *__restr
     const int p = blockIdx.x * 256 + threadIdx.x;
     const bool in = p < H * W;
     const int i = in ? p / W : 0, j = in ? p - i * W : 0;
-    const float px = (2.0f * (float)j + 1.0f) / (float)W - 1.0f;
-    const float py = 1.0f - (2.0f * (float)i + 1.0f) / (float)H;
+    const Ndc c = pixel_centre(i, j, H, W);
     float best_z = -3.0e38f;
     int best_f = -1;
     float bw0 = 0.f, bw1 = 0.f, bw2 = 0.f;
@@ -142,7 +112,7 @@ k_rasterize(int H, int W, const float *__restrict__ face_z, const float *__restr
         for (int k = threadIdx.x; k < nf * 3; k += 256) s_z[k] = face_z[(int64_t)f0 * 3 + k];
         __syncthreads();
         for (int f = 0; f < nf; ++f)
-            raster_face_test(px, py, s_xy[f * 6], s_xy[f * 6 + 1], s_xy[f * 6 + 2], s_xy[f * 6 + 3], s_xy[f * 6 + 4],
+            raster_face_test(c.x, c.y, s_xy[f * 6], s_xy[f * 6 + 1], s_xy[f * 6 + 2], s_xy[f * 6 + 3], s_xy[f * 6 + 4],
                              s_xy[f * 6 + 5], s_z[f * 3], s_z[f * 3 + 1], s_z[f * 3 + 2], f0 + f, best_z, best_f, bw0,
                              bw1, bw2);
     }
@@ -177,8 +147,7 @@ k_rasterize_tiles(int H, int W, const float *__restrict__ face_z, const float *_
     const int tj0 = blockIdx.x * TS, ti0 = blockIdx.y * TS;
     const int j = tj0 + pl % TS, i = ti0 + pl / TS;
     const bool in = i < H && j < W;
-    const float px = (2.0f * (float)j + 1.0f) / (float)W - 1.0f;
-    const float py = 1.0f - (2.0f * (float)i + 1.0f) / (float)H;
+    const Ndc c = pixel_centre(i, j, H, W);
     face_z += (int64_t)b * F * 3;
     face_xy += (int64_t)b * F * 6;
     boxes += (int64_t)b * F;
@@ -191,7 +160,7 @@ k_rasterize_tiles(int H, int W, const float *__restrict__ face_z, const float *_
         __syncthreads();
         for (int q = slice; q < qn; q += S) {
             const QFace r = s_q[q];   // every lane of the wave reads the same record: a broadcast
-            raster_face_test(px, py, r.x0, r.y0, r.x1, r.y1, r.x2, r.y2, r.z0, r.z1, r.z2, r.f, best_z, best_f, bw0,
+            raster_face_test(c.x, c.y, r.x0, r.y0, r.x1, r.y1, r.x2, r.y2, r.z0, r.z1, r.z2, r.f, best_z, best_f, bw0,
                              bw1, bw2);
         }
         __syncthreads();
@@ -368,13 +337,8 @@ int lnerf_raster_prepare(const float *verts, int n_verts, const int32_t *faces, 
                          float *face_z, float *face_xy, lnerf_stream_t stream) {
     LNERF_REQUIRE(n_verts > 0 && n_faces > 0, "raster_prepare: empty mesh");
     LNERF_REQUIRE(verts && faces && cam_host && face_z && face_xy, "raster_prepare: null pointer");
-    Cam cam;
-    for (int i = 0; i < 9; ++i) cam.rot[i] = cam_host[i];
-    for (int i = 0; i < 3; ++i) cam.pos[i] = cam_host[9 + i];
-    cam.fx = cam_host[12];
-    cam.fy = cam_host[13];
-    hipLaunchKernelGGL(k_raster_prepare, dim3((unsigned)div_up(n_faces, 256)), dim3(256), 0, as_stream(stream), verts,
-                       faces, n_faces, cam, face_z, face_xy);
+    LNERF_LAUNCH(k_raster_prepare, n_faces, 256, as_stream(stream), verts, faces, n_faces, cam_read(cam_host), face_z,
+                 face_xy);
     LNERF_CHECK_LAUNCH("raster_prepare");
     return LNERF_OK;
 }
@@ -383,8 +347,7 @@ int lnerf_rasterize(int H, int W, const float *face_z, const float *face_xy, int
                     float *bary, lnerf_stream_t stream) {
     LNERF_REQUIRE(H > 0 && W > 0 && n_faces > 0, "rasterize: bad sizes");
     LNERF_REQUIRE(face_z && face_xy && face_idx && bary, "rasterize: null pointer");
-    hipLaunchKernelGGL(k_rasterize, dim3((unsigned)div_up((int64_t)H * W, 256)), dim3(256), 0, as_stream(stream), H, W,
-                       face_z, face_xy, n_faces, face_idx, bary);
+    LNERF_LAUNCH(k_rasterize, (int64_t)H * W, 256, as_stream(stream), H, W, face_z, face_xy, n_faces, face_idx, bary);
     LNERF_CHECK_LAUNCH("rasterize");
     return LNERF_OK;
 }
@@ -393,8 +356,7 @@ int lnerf_raster_prepare_batch(const float *verts, int n_verts, const int32_t *f
                                const float *cams_dev, int B, int H, int W, float *face_z, float *face_xy,
                                int16_t *face_box, lnerf_stream_t stream) {
     LNERF_REQUIRE(n_verts > 0 && n_faces > 0, "raster_prepare_batch: empty mesh");
-    LNERF_REQUIRE(B >= 1 && B <= 65535, "raster_prepare_batch: B must be in [1, 65535]");
-    LNERF_REQUIRE(H >= 1 && W >= 1 && H <= 32767 && W <= 32767, "raster_prepare_batch: H and W must be in [1, 32767]");
+    if (int e = check_view_dims("raster_prepare_batch", B, H, W)) return e;
     LNERF_REQUIRE(verts && faces && cams_dev && face_z && face_xy && face_box, "raster_prepare_batch: null pointer");
     hipLaunchKernelGGL(k_raster_prepare_batch, dim3((unsigned)div_up(n_faces, 256), (unsigned)B), dim3(256), 0,
                        as_stream(stream), verts, faces, n_faces, cams_dev, H, W, face_z, face_xy,
@@ -405,8 +367,7 @@ int lnerf_raster_prepare_batch(const float *verts, int n_verts, const int32_t *f
 
 int lnerf_rasterize_batch(int B, int H, int W, const float *face_z, const float *face_xy, const int16_t *face_box,
                           int n_faces, int32_t *face_idx, float *bary, lnerf_stream_t stream) {
-    LNERF_REQUIRE(B >= 1 && B <= 65535, "rasterize_batch: B must be in [1, 65535]");
-    LNERF_REQUIRE(H >= 1 && W >= 1 && H <= 32767 && W <= 32767, "rasterize_batch: H and W must be in [1, 32767]");
+    if (int e = check_view_dims("rasterize_batch", B, H, W)) return e;
     LNERF_REQUIRE(n_faces > 0, "rasterize_batch: no faces");
     LNERF_REQUIRE(face_z && face_xy && face_box && face_idx && bary, "rasterize_batch: null pointer");
     LNERF_REQUIRE(((uintptr_t)face_box & 7) == 0, "rasterize_batch: face_box must be 8-byte aligned");
@@ -427,8 +388,7 @@ int lnerf_interpolate_attributes(const int32_t *face_idx, const float *bary, con
                                  float *feat, lnerf_stream_t stream) {
     LNERF_REQUIRE(n_pixels > 0 && D >= 1 && D <= 16, "interpolate_attributes: bad sizes");
     LNERF_REQUIRE(face_idx && bary && attr && feat, "interpolate_attributes: null pointer");
-    hipLaunchKernelGGL(k_interp_attr, dim3((unsigned)div_up((int64_t)n_pixels * D, 256)), dim3(256), 0,
-                       as_stream(stream), face_idx, bary, attr, n_pixels, D, feat);
+    LNERF_LAUNCH(k_interp_attr, (int64_t)n_pixels * D, 256, as_stream(stream), face_idx, bary, attr, n_pixels, D, feat);
     LNERF_CHECK_LAUNCH("interpolate_attributes");
     return LNERF_OK;
 }
@@ -437,8 +397,8 @@ int lnerf_interpolate_attributes_backward(const int32_t *face_idx, const float *
                                           int n_pixels, int D, float *dattr, lnerf_stream_t stream) {
     LNERF_REQUIRE(n_pixels > 0 && D >= 1 && D <= 16, "interpolate_attributes_backward: bad sizes");
     LNERF_REQUIRE(face_idx && bary && dfeat && dattr, "interpolate_attributes_backward: null pointer");
-    hipLaunchKernelGGL(k_interp_attr_bwd, dim3((unsigned)div_up((int64_t)n_pixels * D, 256)), dim3(256), 0,
-                       as_stream(stream), face_idx, bary, dfeat, n_pixels, D, dattr);
+    LNERF_LAUNCH(k_interp_attr_bwd, (int64_t)n_pixels * D, 256, as_stream(stream), face_idx, bary, dfeat, n_pixels, D,
+                 dattr);
     LNERF_CHECK_LAUNCH("interpolate_attributes_backward");
     return LNERF_OK;
 }
@@ -447,8 +407,8 @@ int lnerf_texture_map_forward(const float *uv, const int32_t *face_idx, const fl
                               int R, int mode, float *out, lnerf_stream_t stream) {
     LNERF_REQUIRE(n_pixels > 0 && C >= 1 && R >= 1 && mode >= 0 && mode <= 2, "texture_map_forward: bad arguments");
     LNERF_REQUIRE(uv && texture && out, "texture_map_forward: null pointer");
-    hipLaunchKernelGGL(k_texture_map<false>, dim3((unsigned)div_up((int64_t)n_pixels * C, 256)), dim3(256), 0,
-                       as_stream(stream), uv, face_idx, const_cast<float *>(texture), n_pixels, C, R, mode, out);
+    LNERF_LAUNCH(k_texture_map<false>, (int64_t)n_pixels * C, 256, as_stream(stream), uv, face_idx,
+                 const_cast<float *>(texture), n_pixels, C, R, mode, out);
     LNERF_CHECK_LAUNCH("texture_map_forward");
     return LNERF_OK;
 }
@@ -457,8 +417,8 @@ int lnerf_texture_map_backward(const float *uv, const int32_t *face_idx, const f
                                int mode, float *dtexture, lnerf_stream_t stream) {
     LNERF_REQUIRE(n_pixels > 0 && C >= 1 && R >= 1 && mode >= 0 && mode <= 2, "texture_map_backward: bad arguments");
     LNERF_REQUIRE(uv && dout && dtexture, "texture_map_backward: null pointer");
-    hipLaunchKernelGGL(k_texture_map<true>, dim3((unsigned)div_up((int64_t)n_pixels * C, 256)), dim3(256), 0,
-                       as_stream(stream), uv, face_idx, dtexture, n_pixels, C, R, mode, const_cast<float *>(dout));
+    LNERF_LAUNCH(k_texture_map<true>, (int64_t)n_pixels * C, 256, as_stream(stream), uv, face_idx, dtexture, n_pixels, C,
+                 R, mode, const_cast<float *>(dout));
     LNERF_CHECK_LAUNCH("texture_map_backward");
     return LNERF_OK;
 }

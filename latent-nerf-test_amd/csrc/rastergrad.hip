@@ -1,9 +1,10 @@
 // The geometry half of the Latent-Paint backward pass ("Vertex gradients and edge antialiasing"): gradients of
 // a rendered batch with respect to the projected faces and, through the projection, the vertices; the edge-antialiasing
 // pass that makes a silhouette differentiable under an image loss; and the face-weighted uniform Laplacian of the
-// displacement regulariser.  Everything here differentiates a forward of raster.hip / tex_shared.h and recomputes that
-// forward's terms from the same inputs; the contracts are in include/lnerf_hip.h.  f32, every operation rounded on its own.
+// displacement regulariser.  Everything here differentiates a forward of raster.hip / tex_shared.h and calls that forward's
+// functions (raster_shared.h, tex_shared.h) for its terms; contracts: include/lnerf_hip.h.  f32, each operation rounded alone.
 #include "common.h"
+#include "raster_shared.h"
 #include "tex_shared.h"
 
 namespace lnerf {
@@ -19,8 +20,8 @@ __device__ __forceinline__ AAPixel aa_pixel(const int32_t *__restrict__ face_idx
                                             const float *__restrict__ face_z, int b, int i, int j, int H, int W, int F) {
     const int64_t p = ((int64_t)b * H + i) * W + j;
     AAPixel r;
-    r.x = (2.0f * (float)j + 1.0f) / (float)W - 1.0f;
-    r.y = 1.0f - (2.0f * (float)i + 1.0f) / (float)H;
+    const Ndc c = pixel_centre(i, j, H, W);
+    r.x = c.x; r.y = c.y;
     const int f = face_idx[p];
     if (f < 0 || f >= F) {
         r.f = -1;
@@ -109,8 +110,7 @@ k_raster_antialias(const float *__restrict__ image, const float *__restrict__ go
                    float *__restrict__ gxy) {
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= (int64_t)B * H * W) return;
-    const int b = (int)(p / ((int64_t)H * W));
-    const int rem = (int)(p - (int64_t)b * H * W), i = rem / W, j = rem - i * W;
+    const auto [b, i, j] = pixel_of(p, H, W);
     const float *xy = face_xy + (int64_t)b * F * 6;
     const AAPixel me = aa_pixel(face_idx, bary, face_z, b, i, j, H, W, F);
     float w_in[4], w_out[4], dw[4];   // what this pixel receives per neighbour, and what the neighbour receives from it
@@ -161,7 +161,7 @@ k_raster_antialias(const float *__restrict__ image, const float *__restrict__ go
         const bool horizontal = n < 2;
         // the centres of near and far along the pair's axis, and the line across it
         const float mx = me.x, my = me.y;
-        const float ox = (2.0f * (float)nj + 1.0f) / (float)W - 1.0f, oy = 1.0f - (2.0f * (float)ni + 1.0f) / (float)H;
+        const auto [ox, oy] = pixel_centre(ni, nj, H, W);
         const float s_near = horizontal ? (r.a_near ? mx : ox) : (r.a_near ? my : oy);
         const float s_far = horizontal ? (r.a_near ? ox : mx) : (r.a_near ? oy : my);
         const float line = horizontal ? my : mx;   // (shared by both pixels of the pair)
@@ -180,8 +180,8 @@ k_raster_antialias(const float *__restrict__ image, const float *__restrict__ go
 }
 
 // ------------------------------------------------------------------------------------------------ barycentrics
-// One thread per pixel: the transpose of raster_face_test's weights on the winning face, w_k recomputed from the pixel
-// centre and the face (bary itself is not inverted).
+// One thread per pixel: the transpose of raster_face_test's weights on the winning face: both stages of raster_shared.h
+// on the pixel centre and the face (bary itself is not inverted), then their derivatives.
 __global__ void __launch_bounds__(256)
 k_raster_bary_bwd(const float *__restrict__ gbary, const int32_t *__restrict__ face_idx,
                   const float *__restrict__ face_xy, const float *__restrict__ face_z, int B, int H, int W, int F,
@@ -192,24 +192,17 @@ k_raster_bary_bwd(const float *__restrict__ gbary, const int32_t *__restrict__ f
     if (f < 0 || f >= F) return;
     const float g0 = gbary[p * 3], g1 = gbary[p * 3 + 1], g2 = gbary[p * 3 + 2];
     if (g0 == 0.f && g1 == 0.f && g2 == 0.f) return;
-    const int b = (int)(p / ((int64_t)H * W));
-    const int rem = (int)(p - (int64_t)b * H * W), i = rem / W, j = rem - i * W;
-    const float px = (2.0f * (float)j + 1.0f) / (float)W - 1.0f;
-    const float py = 1.0f - (2.0f * (float)i + 1.0f) / (float)H;
+    const auto [b, i, j] = pixel_of(p, H, W);
+    const auto [px, py] = pixel_centre(i, j, H, W);
     const int64_t bf = (int64_t)b * F + f;
     const float *c = face_xy + bf * 6, *z = face_z + bf * 3;
     const float x0 = c[0], y0 = c[1], x1 = c[2], y1 = c[3], x2 = c[4], y2 = c[5];
     const float z0 = z[0], z1 = z[1], z2 = z[2];
-    const float area = (x1 - x0) * (y2 - y0) - (x2 - x0) * (y1 - y0);
-    const float e0 = (x1 - px) * (y2 - py) - (x2 - px) * (y1 - py);
-    const float e1 = (x2 - px) * (y0 - py) - (x0 - px) * (y2 - py);
-    const float inv = 1.0f / area;
-    const float w0 = e0 * inv, w1 = e1 * inv, w2 = 1.0f - w0 - w1;
-    const float q0 = w0 / z0, q1 = w1 / z1, q2 = w2 / z2;
-    const float qs = q0 + q1 + q2, zi = 1.0f / qs;
-    const float b0 = q0 * zi, b1 = q1 * zi, b2 = q2 * zi;
+    const FaceW w = face_weights(face_area(x0, y0, x1, y1, x2, y2), px, py, x0, y0, x1, y1, x2, y2);
+    const FaceP pw = face_perspective(w, z0, z1, z2);
+    const float inv = w.inv, w0 = w.w0, w1 = w.w1, q0 = pw.q0, q1 = pw.q1, q2 = pw.q2, zi = pw.z;
     // b_k = q_k / qs
-    const float gb = (g0 * b0 + g1 * b1) + g2 * b2;
+    const float gb = (g0 * pw.b0 + g1 * pw.b1) + g2 * pw.b2;
     const float dq0 = (g0 - gb) * zi, dq1 = (g1 - gb) * zi, dq2 = (g2 - gb) * zi;
     // q_k = w_k / z_k
     const float dw0 = dq0 / z0, dw1 = dq1 / z1, dw2 = dq2 / z2;
@@ -263,8 +256,7 @@ k_texture_map_bwd_uv(const float *__restrict__ uv, const int32_t *__restrict__ f
         const bool live_y = v >= 0.f && v <= 1.f && y > 0.f && y < top;
         if (live_x || live_y) {
             const BilTaps b = bil_taps(u, v, R);
-            const float xc = clampf(x, 0.f, top), yc = clampf(y, 0.f, top);
-            const float fx = xc - floorf(xc), fy = yc - floorf(yc);
+            const float fx = b.ax, fy = b.ay;   // the fractions of the clamped position
             float sx = 0.f, sy = 0.f;
             for (int c = 0; c < C; ++c) {
                 const float *tc = tex + (int64_t)c * R * R;
@@ -282,33 +274,25 @@ k_texture_map_bwd_uv(const float *__restrict__ uv, const int32_t *__restrict__ f
 }
 
 // ------------------------------------------------------------------------------------------------ projection
-// One thread per (view, face): the transpose of prepare_corner for its three corners, atomics into grad_verts.  A corner
-// whose incoming gradient is all zero adds nothing (so a face the rasteriser rejects never divides by its z here).
+// One thread per (view, face): the transpose of cam_project (raster_shared.h) for its three corners, atomics into grad_verts.
+// A corner whose incoming gradient is all zero adds nothing (so a face the rasteriser rejects never divides by its z here).
 __global__ void __launch_bounds__(256)
 k_raster_prepare_batch_bwd(const float *__restrict__ gxy, const float *__restrict__ gz, const float *__restrict__ verts,
                            int V, const int32_t *__restrict__ faces, int F, const float *__restrict__ cams,
                            float *__restrict__ gverts) {
     const int f = blockIdx.x * 256 + threadIdx.x;
     if (f >= F) return;
-    const int b = blockIdx.y;
-    float rot[9], pos[3];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) rot[i] = cams[b * 14 + i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) pos[i] = cams[b * 14 + 9 + i];
-    const float fx = cams[b * 14 + 12], fy = cams[b * 14 + 13];
-    const int64_t bf = (int64_t)b * F + f;
+    const Cam cam = cam_read(cams + blockIdx.y * CAM_FLOATS);
+    const float *rot = cam.rec + CAM_ROT;
+    const float fx = cam.rec[CAM_FX], fy = cam.rec[CAM_FY];
+    const int64_t bf = (int64_t)blockIdx.y * F + f;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const float gix = gxy[(bf * 3 + k) * 2], giy = gxy[(bf * 3 + k) * 2 + 1], gcz = gz[bf * 3 + k];
         if (gix == 0.f && giy == 0.f && gcz == 0.f) continue;
         const int v = faces[f * 3 + k];
         if (v < 0 || v >= V) continue;
-        const float x = verts[v * 3] - pos[0], y = verts[v * 3 + 1] - pos[1], z = verts[v * 3 + 2] - pos[2];
-        const float cx = fmaf(rot[0], x, fmaf(rot[1], y, rot[2] * z));
-        const float cy = fmaf(rot[3], x, fmaf(rot[4], y, rot[5] * z));
-        const float cz = fmaf(rot[6], x, fmaf(rot[7], y, rot[8] * z));
-        const float ix = cx * fx / (-cz), iy = cy * fy / (-cz);
+        const auto [cz, ix, iy] = cam_project(cam.rec, verts[v * 3], verts[v * 3 + 1], verts[v * 3 + 2]);
         // ix = cx fx / (-cz), iy = cy fy / (-cz), z = cz
         const float dcx = gix * fx / (-cz), dcy = giy * fy / (-cz);
         const float dcz = gcz - (gix * ix + giy * iy) / cz;
@@ -366,15 +350,6 @@ static size_t umbrella_deg_bytes(int V) { return (((size_t)V * sizeof(int32_t)) 
 static size_t umbrella_scratch_bytes(int V, int F) {
     if (V < 1 || V > 0x7fffffff / 3 || F < 0 || F > LNERF_MESH_MAX_FACES) return 0;
     return umbrella_deg_bytes(V) + (((size_t)V * 3 * sizeof(float) + 15) & ~(size_t)15);
-}
-
-// the sizes every pixel kernel here shares
-static int check_raster_dims(const char *who, int B, int H, int W, int F) {
-    LNERF_REQUIRE(B >= 1 && B <= 65535, "%s: B must be in [1, 65535] (got %d)", who, B);
-    LNERF_REQUIRE(H >= 1 && W >= 1 && H <= 32767 && W <= 32767, "%s: H and W must be in [1, 32767] (got %d, %d)", who, H, W);
-    LNERF_REQUIRE((int64_t)B * H * W < ((int64_t)1 << 31), "%s: B * H * W must be below 2^31", who);
-    LNERF_REQUIRE(F >= 1 && F <= LNERF_MESH_MAX_FACES, "%s: n_faces must be in [1, %d] (got %d)", who, LNERF_MESH_MAX_FACES, F);
-    return LNERF_OK;
 }
 
 }  // namespace lnerf

@@ -32,15 +32,15 @@ static int64_t mip_texels(int R, int L) { return L > 0 ? mip_offset(R, L + 1) : 
 // the bilinear lookup on one level of side R: k_texture_map's mode 1 (raster.hip) and every level k_texture_mip reads
 struct BilTaps {
     int64_t i00, i01, i10, i11;
-    float w00, w01, w10, w11;
+    float w00, w01, w10, w11, ax, ay;   // the weights, and the fractions they are made of
 };
 __device__ __forceinline__ BilTaps bil_taps(float u, float v, int R) {
     float x, y;
     tex_coords(u, v, R, true, x, y);
     const float xf = floorf(x), yf = floorf(y);
     const int x0 = (int)xf, y0 = (int)yf, x1 = min(x0 + 1, R - 1), y1 = min(y0 + 1, R - 1);
-    const float ax = x - xf, ay = y - yf;
     BilTaps b;
+    const float ax = b.ax = x - xf, ay = b.ay = y - yf;
     b.w00 = (1.f - ax) * (1.f - ay); b.w01 = ax * (1.f - ay); b.w10 = (1.f - ax) * ay; b.w11 = ax * ay;
     b.i00 = (int64_t)y0 * R + x0; b.i01 = (int64_t)y0 * R + x1; b.i10 = (int64_t)y1 * R + x0; b.i11 = (int64_t)y1 * R + x1;
     return b;

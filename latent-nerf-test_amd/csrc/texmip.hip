@@ -22,12 +22,13 @@
 #include <math.h>
 
 #include "common.h"
+#include "raster_shared.h"
 #include "tex_shared.h"
 
 namespace lnerf {
 
-// One thread per pixel of the B views.  px, py, area, e0, e1 and the weights are k_rasterize's expressions (raster.hip
-// raster_face_test), so bw_k are the barycentrics that rasteriser wrote.  Every operation is rounded on its own.
+// One thread per pixel of the B views.  Calls the rasteriser's own pixel centre and both weight stages (raster_shared.h),
+// so bw_k are the barycentrics raster.hip wrote.  Every operation is rounded on its own.
 __global__ void __launch_bounds__(256)
 k_uv_footprint(const int32_t *__restrict__ face_idx, const float *__restrict__ face_xy,
                const float *__restrict__ face_z, const float *__restrict__ face_uv, int64_t P, int H, int W, int F,
@@ -39,24 +40,15 @@ k_uv_footprint(const int32_t *__restrict__ face_idx, const float *__restrict__ f
         rho[p] = 0.f;
         return;
     }
-    const int64_t hw = (int64_t)H * W;
-    const int64_t b = p / hw;
-    const int q = (int)(p - b * hw);
-    const int i = q / W, j = q - i * W;
-    const float px = (2.0f * (float)j + 1.0f) / (float)W - 1.0f;
-    const float py = 1.0f - (2.0f * (float)i + 1.0f) / (float)H;
-    const float *xy = face_xy + (b * F + f) * 6, *zz = face_z + (b * F + f) * 3, *uv = face_uv + (int64_t)f * 6;
+    const auto [b, i, j] = pixel_of(p, H, W);
+    const auto [px, py] = pixel_centre(i, j, H, W);
+    const int64_t bf = (int64_t)b * F + f;
+    const float *xy = face_xy + bf * 6, *zz = face_z + bf * 3, *uv = face_uv + (int64_t)f * 6;
     const float x0 = xy[0], y0 = xy[1], x1 = xy[2], y1 = xy[3], x2 = xy[4], y2 = xy[5];
     const float z0 = zz[0], z1 = zz[1], z2 = zz[2];
-    const float area = (x1 - x0) * (y2 - y0) - (x2 - x0) * (y1 - y0);
-    const float e0 = (x1 - px) * (y2 - py) - (x2 - px) * (y1 - py);
-    const float e1 = (x2 - px) * (y0 - py) - (x0 - px) * (y2 - py);
-    const float inv = 1.0f / area;
-    const float w0 = e0 * inv, w1 = e1 * inv, w2 = 1.0f - w0 - w1;
-    const float q0 = w0 / z0, q1 = w1 / z1, q2 = w2 / z2;
-    const float qs = q0 + q1 + q2;
-    const float z = 1.0f / qs;
-    const float bw0 = q0 * z, bw1 = q1 * z, bw2 = q2 * z;
+    const FaceW w = face_weights(face_area(x0, y0, x1, y1, x2, y2), px, py, x0, y0, x1, y1, x2, y2);
+    const FaceP pw = face_perspective(w, z0, z1, z2);
+    const float inv = w.inv, z = pw.z, bw0 = pw.b0, bw1 = pw.b1, bw2 = pw.b2;
     // the screen barycentrics are affine in (px, py): d w_k / d px, d w_k / d py
     const float w0x = (y1 - y2) * inv, w0y = (x2 - x1) * inv;
     const float w1x = (y2 - y0) * inv, w1y = (x0 - x2) * inv;
@@ -323,8 +315,7 @@ int lnerf_uv_footprint(const int32_t *face_idx, const float *face_xy, const floa
     LNERF_REQUIRE(n_faces > 0, "uv_footprint: no faces");
     LNERF_REQUIRE(face_idx && face_xy && face_z && face_uv && rho, "uv_footprint: null pointer");
     const int64_t P = (int64_t)B * H * W;
-    hipLaunchKernelGGL(k_uv_footprint, dim3((unsigned)div_up(P, 256)), dim3(256), 0, as_stream(stream), face_idx,
-                       face_xy, face_z, face_uv, P, H, W, n_faces, rho);
+    LNERF_LAUNCH(k_uv_footprint, P, 256, as_stream(stream), face_idx, face_xy, face_z, face_uv, P, H, W, n_faces, rho);
     LNERF_CHECK_LAUNCH("uv_footprint");
     return LNERF_OK;
 }

@@ -21,7 +21,7 @@ struct ProjArgs {
 };
 
 __global__ void __launch_bounds__(PROJ_THREADS) k_uv_project(ProjArgs a) {
-    __shared__ float s_cam[PROJ_CAM_TILE * 14];
+    __shared__ float s_cam[PROJ_CAM_TILE * CAM_FLOATS];
     const int64_t p = (int64_t)blockIdx.x * PROJ_THREADS + threadIdx.x;
     const bool live = p < a.P;
     float x[3] = {0.f, 0.f, 0.f}, n[3] = {0.f, 0.f, 0.f};
@@ -40,14 +40,14 @@ __global__ void __launch_bounds__(PROJ_THREADS) k_uv_project(ProjArgs a) {
     for (int k0 = 0; k0 < a.K; k0 += PROJ_CAM_TILE) {
         const int nk = min(PROJ_CAM_TILE, a.K - k0);
         __syncthreads();
-        for (int t = threadIdx.x; t < nk * 14; t += PROJ_THREADS) s_cam[t] = a.cams[(int64_t)k0 * 14 + t];
+        for (int t = threadIdx.x; t < nk * CAM_FLOATS; t += PROJ_THREADS) s_cam[t] = a.cams[(int64_t)k0 * CAM_FLOATS + t];
         __syncthreads();
         if (!live) continue;
         for (int kk = 0; kk < nk; ++kk) {
             const int k = k0 + kk;
             ViewTap t;
             // 1-5. does the point accept this view (view_shared.h)
-            if (!view_accept(x, n, s_cam + kk * 14, a.zbuf + (int64_t)k * plane, a.W, Wf, Hf, a.cos_min, a.slack, t)) continue;
+            if (!view_accept(x, n, s_cam + kk * CAM_FLOATS, a.zbuf + (int64_t)k * plane, a.W, Wf, Hf, a.cos_min, a.slack, t)) continue;
             // 6. accumulate the weighted mean around the first accepted colour: the differences are exact zeros where
             // the taps or the views agree, so a colour all views share comes back as it is
             const float w = powf(t.c, a.power);

@@ -3,11 +3,12 @@
 // (uvproject.hip) and the exposure / two-band kernels (viewblend.hip), so that all of them take the same decisions.
 #pragma once
 #include "common.h"
+#include "raster_shared.h"
 
 namespace lnerf {
 
 constexpr int PROJ_THREADS = 256;
-constexpr int PROJ_CAM_TILE = 64;   // camera records per LDS tile (64 * 14 floats = 3.5 KiB)
+constexpr int PROJ_CAM_TILE = 64;   // camera records per LDS tile (64 * CAM_FLOATS floats = 3.5 KiB)
 constexpr int PROJ_MAX_C = 4;
 
 // an accepted (point, view) pair: the cosine of step 1, the top-left tap's offset i0 * W + j0 in a [H,W] plane and the
@@ -21,20 +22,16 @@ struct ViewTap {
 __device__ __forceinline__ bool view_accept(const float *x, const float *n, const float *cam, const float *zplane, int W,
                                             float Wf, float Hf, float cos_min, float slack, ViewTap &t) {
     // 1. the angle between the normal and the direction to the eye
-    const float dx = cam[9] - x[0], dy = cam[10] - x[1], dz = cam[11] - x[2];
+    const float dx = cam[CAM_POS] - x[0], dy = cam[CAM_POS + 1] - x[1], dz = cam[CAM_POS + 2] - x[2];
     const float len = sqrtf(dx * dx + dy * dy + dz * dz);
     const float c = (n[0] * dx + n[1] * dy + n[2] * dz) / len;
     if (!(c >= cos_min)) return false;
-    // 2. camera space, with the rasteriser's own arithmetic (raster.hip prepare_corner)
-    const float rx = x[0] - cam[9], ry = x[1] - cam[10], rz = x[2] - cam[11];
-    const float px = fmaf(cam[0], rx, fmaf(cam[1], ry, cam[2] * rz));
-    const float py = fmaf(cam[3], rx, fmaf(cam[4], ry, cam[5] * rz));
-    const float pz = fmaf(cam[6], rx, fmaf(cam[7], ry, cam[8] * rz));
+    // 2. camera space: the rasteriser's own projection (raster_shared.h)
+    const auto [pz, X, Y] = cam_project(cam, x[0], x[1], x[2]);
     if (!(pz < 0.f)) return false;
-    const float fx = cam[12], fy = cam[13];
-    const float X = px * fx / (-pz), Y = py * fy / (-pz);
+    const float fx = cam[CAM_FX], fy = cam[CAM_FY];
     // 3. pixel coordinates, pixel centres at integers; all four taps inside the image
-    const float u = ((X + 1.0f) * Wf - 1.0f) * 0.5f, v = ((1.0f - Y) * Hf - 1.0f) * 0.5f;
+    const float u = ndc_to_col(X, Wf), v = ndc_to_row(Y, Hf);
     if (!(u >= 0.f && u < Wf - 1.0f && v >= 0.f && v < Hf - 1.0f)) return false;
     const float uf = floorf(u), vf = floorf(v);
     const int j0 = (int)uf, i0 = (int)vf;

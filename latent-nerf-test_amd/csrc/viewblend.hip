@@ -95,8 +95,8 @@ __device__ __forceinline__ long long wave_sum_i64(long long v) {
 
 __global__ void __launch_bounds__(PROJ_THREADS) k_overlap_stats(StatsArgs a) {
     static_assert(STATS_MAX_K <= 64, "the accepted views of a lane are one 64-bit mask");
-    __shared__ float s_cam[STATS_MAX_K * 14];
-    for (int t = threadIdx.x; t < a.K * 14; t += PROJ_THREADS) s_cam[t] = a.cams[t];
+    __shared__ float s_cam[STATS_MAX_K * CAM_FLOATS];
+    for (int t = threadIdx.x; t < a.K * CAM_FLOATS; t += PROJ_THREADS) s_cam[t] = a.cams[t];
     __syncthreads();
     const int64_t p = (int64_t)blockIdx.x * PROJ_THREADS + threadIdx.x;
     const bool live = p < a.P;
@@ -114,7 +114,7 @@ __global__ void __launch_bounds__(PROJ_THREADS) k_overlap_stats(StatsArgs a) {
     unsigned long long mine = 0, wave = 0;
     for (int k = 0; k < a.K; ++k) {
         ViewTap t;
-        const bool ok = live && view_accept(x, n, s_cam + k * 14, a.zbuf + k * plane, a.W, Wf, Hf, a.cos_min, a.slack, t);
+        const bool ok = live && view_accept(x, n, s_cam + k * CAM_FLOATS, a.zbuf + k * plane, a.W, Wf, Hf, a.cos_min, a.slack, t);
         if (ok) mine |= 1ull << k;
         if (__ballot(ok) != 0ull) wave |= 1ull << k;
     }
@@ -124,7 +124,7 @@ __global__ void __launch_bounds__(PROJ_THREADS) k_overlap_stats(StatsArgs a) {
         long long q[PROJ_MAX_C] = {0, 0, 0, 0};
         ViewTap t;
         // (the same arithmetic on the same inputs: accepted again, and the taps are inside the image)
-        if (has_i && view_accept(x, n, s_cam + i * 14, a.zbuf + i * plane, a.W, Wf, Hf, a.cos_min, a.slack, t)) {
+        if (has_i && view_accept(x, n, s_cam + i * CAM_FLOATS, a.zbuf + i * plane, a.W, Wf, Hf, a.cos_min, a.slack, t)) {
             const float *lw = a.low + (int64_t)i * a.C * plane + t.off;
 #pragma unroll
             for (int ch = 0; ch < PROJ_MAX_C; ++ch)
@@ -158,7 +158,7 @@ struct BandsArgs {
 };
 
 __global__ void __launch_bounds__(PROJ_THREADS) k_uv_project_bands(BandsArgs a) {
-    __shared__ float s_cam[PROJ_CAM_TILE * 14];
+    __shared__ float s_cam[PROJ_CAM_TILE * CAM_FLOATS];
     const int64_t p = (int64_t)blockIdx.x * PROJ_THREADS + threadIdx.x;
     const bool live = p < a.P;
     float x[3] = {0.f, 0.f, 0.f}, n[3] = {0.f, 0.f, 0.f};
@@ -178,13 +178,13 @@ __global__ void __launch_bounds__(PROJ_THREADS) k_uv_project_bands(BandsArgs a) 
     for (int k0 = 0; k0 < a.K; k0 += PROJ_CAM_TILE) {
         const int nk = min(PROJ_CAM_TILE, a.K - k0);
         __syncthreads();
-        for (int t = threadIdx.x; t < nk * 14; t += PROJ_THREADS) s_cam[t] = a.cams[(int64_t)k0 * 14 + t];
+        for (int t = threadIdx.x; t < nk * CAM_FLOATS; t += PROJ_THREADS) s_cam[t] = a.cams[(int64_t)k0 * CAM_FLOATS + t];
         __syncthreads();
         if (!live) continue;
         for (int kk = 0; kk < nk; ++kk) {
             const int k = k0 + kk;
             ViewTap t;
-            if (!view_accept(x, n, s_cam + kk * 14, a.zbuf + (int64_t)k * plane, a.W, Wf, Hf, a.cos_min, a.slack, t)) continue;
+            if (!view_accept(x, n, s_cam + kk * CAM_FLOATS, a.zbuf + (int64_t)k * plane, a.W, Wf, Hf, a.cos_min, a.slack, t)) continue;
             const float w = powf(t.c, a.power);
             const bool better = w > wbest;          // strict: the lowest k wins an exact tie
             const int64_t at = (int64_t)k * a.C * plane + t.off;

@@ -13,6 +13,7 @@ Conventions that differ from a CUDA port, by design for MI355X:
 """
 import ctypes
 import math
+import typing
 
 import torch
 
@@ -1211,6 +1212,43 @@ def _cams(cams, op, dev):
     return cams
 
 
+class RasterState(typing.NamedTuple):
+    """B views of one mesh, rasterised: per pixel the winning face (-1: background) and its barycentrics; the projected faces."""
+    face_idx: torch.Tensor   # [B*H*W] int32
+    bary: torch.Tensor       # [B*H*W,3]
+    B: int
+    H: int
+    W: int
+    face_xy: torch.Tensor    # [B,F,3,2]
+    face_z: torch.Tensor     # [B,F,3]
+
+
+def raster_project(verts, faces32, cams, H, W):
+    """lnerf_raster_prepare_batch: verts [V,3], faces32 [F,3] int32, cams [B,14] -> (face_z, face_xy, face_box [B,F,4])."""
+    B, F, dev = cams.shape[0], faces32.shape[0], verts.device
+    face_z, face_xy = torch.empty(B, F, 3, device=dev), torch.empty(B, F, 3, 2, device=dev)
+    face_box = torch.empty(B, F, 4, device=dev, dtype=torch.int16)
+    _b.call("lnerf_raster_prepare_batch", _chk(verts, "verts"), verts.shape[0], _chk(faces32, "faces", torch.int32), F,
+            _chk(cams, "cams"), B, H, W, _p(face_z), _p(face_xy), _p(face_box), _stream())
+    return face_z, face_xy, face_box
+
+
+def raster_cover(face_z, face_xy, face_box, H, W):
+    """lnerf_rasterize_batch on raster_project's result -> (face_idx [B*H*W], bary [B*H*W,3])."""
+    B, F = face_z.shape[0], face_z.shape[1]
+    face_idx = torch.empty(B * H * W, device=face_z.device, dtype=torch.int32)
+    bary = torch.empty(B * H * W, 3, device=face_z.device)
+    _b.call("lnerf_rasterize_batch", B, H, W, _p(face_z), _p(face_xy), _p(face_box), F, _p(face_idx), _p(bary), _stream())
+    return face_idx, bary
+
+
+def rasterize_views(verts, faces32, cams, H, W, project=raster_project, cover=raster_cover):
+    """The batched tile-culled rasteriser, both launches -> RasterState (`project`, `cover`: the steps as autograd nodes)."""
+    face_z, face_xy, face_box = project(verts, faces32, cams, H, W)
+    face_idx, bary = cover(face_z, face_xy, face_box, H, W)
+    return RasterState(face_idx, bary, cams.shape[0], H, W, face_xy, face_z)
+
+
 def view_zbuffer(verts, faces, cams, H, W, erode=0):
     """Camera z of the visible surface of a mesh at every pixel centre of K views -> zbuf [K,H,W] f32: the batched
     rasteriser (lnerf_raster_prepare_batch, lnerf_rasterize_batch) and, per view, its perspective-correct barycentrics
@@ -1220,18 +1258,12 @@ def view_zbuffer(verts, faces, cams, H, W, erode=0):
     H, W, erode = int(H), int(W), int(erode)
     if erode < 0:
         raise ValueError("view_zbuffer: erode must be >= 0")
-    verts, faces, V, F = _mesh_inputs(verts, faces, "view_zbuffer", 2 ** 31 - 1)
+    verts, faces, _, _ = _mesh_inputs(verts, faces, "view_zbuffer", 2 ** 31 - 1)
     dev = verts.device
     cams = _cams(cams, "view_zbuffer", dev)
     K = cams.shape[0]
-    face_z = torch.empty(K, F, 3, device=dev)
-    face_xy = torch.empty(K, F, 3, 2, device=dev)
-    face_box = torch.empty(K, F, 4, device=dev, dtype=torch.int16)
-    _b.call("lnerf_raster_prepare_batch", _p(verts), V, _p(faces), F, _p(cams), K, H, W, _p(face_z), _p(face_xy),
-            _p(face_box), _stream())
-    face_idx = torch.empty(K, H * W, device=dev, dtype=torch.int32)
-    bary = torch.empty(K, H * W, 3, device=dev)
-    _b.call("lnerf_rasterize_batch", K, H, W, _p(face_z), _p(face_xy), _p(face_box), F, _p(face_idx), _p(bary), _stream())
+    st = rasterize_views(verts, faces, cams, H, W)
+    face_idx, bary, face_z = st.face_idx.view(K, H * W), st.bary.view(K, H * W, 3), st.face_z
     zbuf = torch.empty(K, H * W, device=dev)
     for k in range(K):   # face indices are per view: one D = 1 interpolation over each view's own corner depths
         _b.call("lnerf_interpolate_attributes", _p(face_idx[k]), _p(bary[k]), _p(face_z[k]), H * W, 1, _p(zbuf[k]),
@@ -1248,21 +1280,9 @@ def project_views(pos, nrm, cams, zbuf, images, cos_min=0.2, power=4.0, slack=2.
     A view counts for a point where the point faces it (cosine >= cos_min), projects with all four bilinear taps on
     foreground pixels and passes the depth test (`slack` pixel footprints of bias); its colour is weighted by
     cosine^power.  -> out [P,C] (the weighted mean, 0 where no view counted), weight [P], count [P] int32."""
-    for t, name in ((pos, "pos"), (nrm, "nrm")):
-        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 3:
-            raise ValueError("project_views: %s must be [P,3]" % name)
-    if pos.shape != nrm.shape:
-        raise ValueError("project_views: pos %s and nrm %s differ" % (tuple(pos.shape), tuple(nrm.shape)))
+    pos, nrm = _points("project_views", pos, nrm)
     dev = pos.device
-    pos, nrm = pos.float().contiguous(), nrm.to(dev).float().contiguous()
-    cams = _cams(cams, "project_views", dev)
-    K = cams.shape[0]
-    if not isinstance(images, torch.Tensor) or images.dim() != 4 or images.shape[0] != K or not 1 <= images.shape[1] <= 4:
-        raise ValueError("project_views: images must be [K,C,H,W] with K = %d and 1 <= C <= 4" % K)
-    C, H, W = (int(v) for v in images.shape[1:])
-    if not isinstance(zbuf, torch.Tensor) or tuple(zbuf.shape) != (K, H, W):
-        raise ValueError("project_views: zbuf must be [K,H,W] = [%d,%d,%d]" % (K, H, W))
-    images, zbuf = images.to(dev).float().contiguous(), zbuf.to(dev).float().contiguous()
+    cams, zbuf, images, K, C, H, W = _view_stack("project_views", cams, zbuf, images, dev)
     P = pos.shape[0]
     out = torch.zeros(P, C, device=dev)
     weight = torch.zeros(P, device=dev)

@@ -12,8 +12,9 @@ import math
 import torch
 
 from ...latent_nerf.raymarching import backend as _b
-from ...latent_nerf.raymarching.raymarching import (_chk, _p, _stream, mip_build, mip_levels, mip_texels,  # noqa: F401
-                                                    mipcov_weights, pyramid_build, pyramid_fold, uv_dilate, uv_raster)
+from ...latent_nerf.raymarching.raymarching import (RasterState, _chk, _p, _stream, mip_build, mip_levels,  # noqa: F401
+                                                    mip_texels, mipcov_weights, pyramid_build, pyramid_fold,
+                                                    raster_cover, raster_project, rasterize_views, uv_dilate, uv_raster)
 
 _MODES = {"nearest": 0, "bilinear": 1, "bicubic": 2}   # lnerf_texture_map_*'s point lookups ("mipmap": _TextureMip)
 
@@ -96,13 +97,8 @@ class _PrepareBatch(torch.autograd.Function):
     """lnerf_raster_prepare_batch with its transpose: verts [V,3] -> (face_z [B,F,3], face_xy [B,F,3,2], face_box)."""
 
     @staticmethod
-    def forward(ctx, verts, faces32, cams, B, H, W):
-        F = faces32.shape[0]
-        face_z = torch.empty(B, F, 3, device=verts.device)
-        face_xy = torch.empty(B, F, 3, 2, device=verts.device)
-        face_box = torch.empty(B, F, 4, device=verts.device, dtype=torch.int16)
-        _b.call("lnerf_raster_prepare_batch", _chk(verts, "verts"), verts.shape[0], _chk(faces32, "faces", torch.int32),
-                F, _chk(cams, "cams"), B, H, W, _p(face_z), _p(face_xy), _p(face_box), _stream())
+    def forward(ctx, verts, faces32, cams, H, W):
+        face_z, face_xy, face_box = raster_project(verts, faces32, cams, H, W)
         ctx.save_for_backward(verts, faces32, cams)
         ctx.mark_non_differentiable(face_box)
         return face_z, face_xy, face_box
@@ -116,7 +112,7 @@ class _PrepareBatch(torch.autograd.Function):
         dverts = torch.empty_like(verts)
         _b.call("lnerf_raster_prepare_batch_backward", _chk(dxy, "grad_face_xy"), _chk(dz, "grad_face_z"), _p(verts),
                 verts.shape[0], _p(faces32), F, _p(cams), B, _p(dverts), _stream())
-        return dverts, None, None, None, None, None
+        return dverts, None, None, None, None
 
 
 class _RasterizeBatch(torch.autograd.Function):
@@ -124,13 +120,9 @@ class _RasterizeBatch(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, face_z, face_xy, face_box, H, W):
-        B, F = face_z.shape[0], face_z.shape[1]
-        face_idx = torch.empty(B * H * W, device=face_z.device, dtype=torch.int32)
-        bary = torch.empty(B * H * W, 3, device=face_z.device)
-        _b.call("lnerf_rasterize_batch", B, H, W, _p(face_z), _p(face_xy), _p(face_box), F, _p(face_idx), _p(bary),
-                _stream())
+        face_idx, bary = raster_cover(face_z, face_xy, face_box, H, W)
         ctx.save_for_backward(face_z, face_xy, face_idx)
-        ctx.dims = (B, H, W, F)
+        ctx.dims = (face_z.shape[0], H, W, face_z.shape[1])
         ctx.mark_non_differentiable(face_idx)
         return face_idx, bary
 
@@ -266,13 +258,12 @@ class _TextureMip(torch.autograd.Function):
     w0 [R,R] f32 and wpyr [S], the weights of the texture's side, the pyramid is the coverage-weighted one."""
 
     @staticmethod
-    def forward(ctx, tex, uv, face_idx, face_xy, face_z, face_uv, dims, L, lod_bias, w0=None, wpyr=None):
+    def forward(ctx, tex, uv, state, face_uv, L, lod_bias, w0=None, wpyr=None):
         C, R = _texture_shape(tex)
-        B, H, W = dims
         t = tex[0].contiguous()
-        rho = uv_footprint(face_idx, face_xy, face_z, face_uv, B, H, W)
-        out = mip_lookup(t, pyramid_build(t, L, w0, wpyr), uv, rho, face_idx, L, lod_bias, w0, wpyr)
-        ctx.save_for_backward(uv, rho, face_idx, w0, wpyr)
+        rho = uv_footprint(state.face_idx, state.face_xy, state.face_z, face_uv, state.B, state.H, state.W)
+        out = mip_lookup(t, pyramid_build(t, L, w0, wpyr), uv, rho, state.face_idx, L, lod_bias, w0, wpyr)
+        ctx.save_for_backward(uv, rho, state.face_idx, w0, wpyr)
         ctx.meta = (C, R, L, lod_bias)
         return out
 
@@ -281,7 +272,7 @@ class _TextureMip(torch.autograd.Function):
         uv, rho, face_idx, w0, wpyr = ctx.saved_tensors
         C, R, L, bias = ctx.meta
         dtex = mip_lookup_backward(dout.contiguous(), (C, R), uv, rho, face_idx, L, bias, w0, wpyr)
-        return (dtex[None],) + (None,) * 10
+        return (dtex[None],) + (None,) * 7
 
 
 class Renderer:
@@ -332,10 +323,11 @@ class Renderer:
 
     def _rasterize_views(self, verts, faces, elev, azim, radius, look_at_height, dims):
         """B views of one mesh through the tile-culled rasteriser -> (face_idx [B*H*W], bary [B*H*W,3], B, H, W)."""
-        return self._rasterize_views_faces(verts, faces, elev, azim, radius, look_at_height, dims)[:5]
+        st = self._rasterize_views_faces(verts, faces, elev, azim, radius, look_at_height, dims)
+        return st.face_idx, st.bary, st.B, st.H, st.W
 
     def _rasterize_views_faces(self, verts, faces, elev, azim, radius, look_at_height, dims):
-        """_rasterize_views' result followed by the projected faces it was made from: face_xy [B,F,3,2], face_z [B,F,3]."""
+        """The RasterState of B views: _rasterize_views' result followed by the projected faces it was made from."""
         elev, azim, radius = list(elev), list(azim), list(radius)
         B = len(elev)
         if B < 1 or len(azim) != B or len(radius) != B:
@@ -345,21 +337,8 @@ class Renderer:
         cams = self._cameras(elev, azim, radius, look_at_height)
         verts = verts.to(self.device).float().contiguous()
         faces32 = faces.to(self.device).to(torch.int32).contiguous()
-        F = faces32.shape[0]
-        if _learns(verts):   # the same two launches, as autograd nodes that carry the geometry backward
-            face_z, face_xy, face_box = _PrepareBatch.apply(verts, faces32, cams, B, H, W)
-            face_idx, bary = _RasterizeBatch.apply(face_z, face_xy, face_box, H, W)
-            return face_idx, bary, B, H, W, face_xy, face_z
-        face_z = torch.empty(B, F, 3, device=self.device)
-        face_xy = torch.empty(B, F, 3, 2, device=self.device)
-        face_box = torch.empty(B, F, 4, device=self.device, dtype=torch.int16)
-        _b.call("lnerf_raster_prepare_batch", _chk(verts, "verts"), verts.shape[0], _chk(faces32, "faces", torch.int32),
-                F, _chk(cams, "cams"), B, H, W, _p(face_z), _p(face_xy), _p(face_box), _stream())
-        face_idx = torch.empty(B * H * W, device=self.device, dtype=torch.int32)
-        bary = torch.empty(B * H * W, 3, device=self.device)
-        _b.call("lnerf_rasterize_batch", B, H, W, _p(face_z), _p(face_xy), _p(face_box), F, _p(face_idx), _p(bary),
-                _stream())
-        return face_idx, bary, B, H, W, face_xy, face_z
+        nodes = (_PrepareBatch.apply, _RasterizeBatch.apply) if _learns(verts) else ()   # the same launches, in the graph
+        return rasterize_views(verts, faces32, cams, H, W, *nodes)
 
     def coverage_weights(self, verts, faces, face_uv, R, L):
         """(w0 [R,R] f32 of 0 / 1, wpyr [S]) of one UV layout at one texture side, computed once: render_test passes the
@@ -371,8 +350,8 @@ class Renderer:
         return self._coverage[key]
 
     def _rasterize(self, verts, faces, elev, azim, radius, look_at_height, dims):
-        face_idx, bary, _, H, W = self._rasterize_views(verts, faces, [elev], [azim], [radius], look_at_height, dims)
-        return face_idx, bary, H, W
+        st = self._rasterize_views_faces(verts, faces, [elev], [azim], [radius], look_at_height, dims)
+        return st.face_idx, st.bary, st.H, st.W
 
     def render_views(self, mesh, face_attributes, elev, azim, radius, look_at_height=0.0):
         """B views in one call: elev, azim, radius are sequences of length B.  face_attributes [1,F,3,D] ->
@@ -397,19 +376,15 @@ class Renderer:
             raise ValueError("render_views_texture: vertex gradients need interpolation_mode bilinear (got %s)"
                              % self.interpolation_mode)
         state = self._rasterize_views_faces(verts, faces, elev, azim, radius, look_at_height, dims)
-        face_idx, bary, B, H, W, face_xy, face_z = state
+        face_idx, B, H, W = state.face_idx, state.B, state.H, state.W
         face_uv = uv_face_attr[0].detach().contiguous()
-        if learns:
-            uv = _InterpAttr.apply(face_uv, face_idx, bary).contiguous()
-        else:
-            with torch.no_grad():                      # uv_features.detach() in the reference (:61)
-                uv = _InterpAttr.apply(face_uv, face_idx, bary).contiguous()
+        with torch.set_grad_enabled(learns):           # off: uv_features.detach() in the reference (:61)
+            uv = _InterpAttr.apply(face_uv, face_idx, state.bary).contiguous()
         if self.interpolation_mode == "mipmap":
             R = texture_map.shape[-1]
             L = mip_levels(R, self.max_mip_level)      # per call: render_test passes the decoded, larger texture
             weights = self.coverage_weights(verts, faces, face_uv, R, L) if self.mip_coverage else ()
-            image = _TextureMip.apply(texture_map, uv, face_idx, face_xy, face_z, face_uv, (B, H, W), L, self.lod_bias,
-                                      *weights)
+            image = _TextureMip.apply(texture_map, uv, state, face_uv, L, self.lod_bias, *weights)
         else:
             image = _TextureMap.apply(texture_map, uv, face_idx, _MODES[self.interpolation_mode])
         mask = (face_idx > -1).float().reshape(B, H, W, 1)
@@ -425,14 +400,14 @@ class Renderer:
         every depth discontinuity between neighbouring pixels the nearer face's edge is located between the two pixel
         centres and the pixel it cuts is blended with its neighbour by the covered fraction, which makes the image a
         differentiable function of the projected edge: the gradient reaches the image and, through raster_state's
-        face_xy, the vertices.  raster_state: the tuple _rasterize_views_faces returned for these views; faces: the
+        face_xy, the vertices.  raster_state: the RasterState _rasterize_views_faces returned for these views; faces: the
         mesh's [F,3] vertex ids (edges between faces that share both vertices are interior and left alone)."""
-        face_idx, bary, B, H, W, face_xy, face_z = raster_state
-        if image.dim() != 4 or image.shape[0] != B or tuple(image.shape[2:]) != (H, W):
-            raise ValueError("antialias_views: image must be [%d,C,%d,%d] (got %s)" % (B, H, W, tuple(image.shape)))
+        st = RasterState(*raster_state)
+        if image.dim() != 4 or image.shape[0] != st.B or tuple(image.shape[2:]) != (st.H, st.W):
+            raise ValueError("antialias_views: image must be [%d,C,%d,%d] (got %s)" % (st.B, st.H, st.W, tuple(image.shape)))
         faces32 = faces.to(self.device).to(torch.int32).contiguous()
-        out = _Antialias.apply(image.float().permute(0, 2, 3, 1).contiguous(), face_xy, face_idx, bary.detach(),
-                               face_z.detach(), faces32)
+        out = _Antialias.apply(image.float().permute(0, 2, 3, 1).contiguous(), st.face_xy, st.face_idx, st.bary.detach(),
+                               st.face_z.detach(), faces32)
         return out.permute(0, 3, 1, 2)
 
     def render_single_view(self, mesh, face_attributes, elev=0, azim=0, radius=2, look_at_height=0.0):

@@ -29,7 +29,7 @@ def pixel_centres(H, W, dtype):
 
 
 def prepare(verts, faces, cams):
-    """verts [V,3], faces [F,3] long, cams [B,14] -> face_xy [B,F,3,2], face_z [B,F,3] (prepare_corner)."""
+    """verts [V,3], faces [F,3] long, cams [B,14] -> face_xy [B,F,3,2], face_z [B,F,3] (cam_project)."""
     rot, pos, fx, fy = cams[:, :9].reshape(-1, 3, 3), cams[:, 9:12], cams[:, 12], cams[:, 13]
     c = torch.einsum("bij,bvj->bvi", rot, verts[None] - pos[:, None])   # [B,V,3]
     cz = c[..., 2]

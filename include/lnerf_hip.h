@@ -74,10 +74,14 @@ const char *lnerf_build_info(void);
  *   "mlp_fwd_blocks":          persistent workgroups of the bf16 MLP forward (default 768).
  *   "mlp_fwd_wps":             wavefronts per SIMD the bf16 forward is compiled for, 3 (default) or 2.
  *   "mlp_bwd_blocks":          persistent workgroups of the MLP backward (default and maximum 512 = slab count).
- * and one switch between two forms of the same result (any value is taken as on / off):
+ * and two switches between two forms of the same result (any value is taken as on / off):
  *   "adam_skip":               1 (default) = the fused table update leaves 16-row groups with all-zero moments and zero
  *                              gradient alone where a moment map is bound (lnerf_moment_map_bind); 0 = the map is still
  *                              maintained, every group takes the step.  Bit-identical either way.
+ *   "adam_consts":             1 (default) = launches on a device step counter with a bound record
+ *                              (lnerf_adam_constants_bind) publish and read the step's bias corrections; 0 = every
+ *                              lane computes them from the counter, the record is neither read nor written.
+ *                              Bit-identical either way.
  */
 int lnerf_set_tuning(const char *key, int value);
 
@@ -770,6 +774,22 @@ size_t lnerf_moment_map_bytes(int num_levels, const int32_t *offsets_host);
 int lnerf_moment_map_build(const float *exp_avg, const float *exp_avg_sq, int num_levels, int level_dim,
                            const int32_t *offsets_host, void *map, size_t map_bytes, lnerf_stream_t stream);
 int lnerf_moment_map_bind(const float *exp_avg, void *map, size_t map_bytes);
+/* ---- Adam's bias corrections published once per step (additive to ABI 7).  With a device step counter every lane of
+ * every Adam kernel computed  bc1 = 1 - powf(beta1, t), bc2 = 1 - powf(beta2, t), 1 / bc1, 1 / bc2  from the same three
+ * numbers.  A record of LNERF_ADAM_CONSTANTS_BYTES bytes bound to the counter holds them as data:
+ *   float bc1, bc2, inv_bc1, inv_bc2;  int32 tag (the step t the four belong to);  12 bytes of padding.
+ *   lnerf_adam_constants_bind    binds `consts` (16-byte aligned, filled with 0xFF bytes by the owner: tag -1 = nothing
+ *     published) to the counter `step_dev` for these betas (process-wide registry under a mutex, keyed by step_dev).
+ *   lnerf_adam_constants_unbind  removes the binding (fine without one).  Unbind before either buffer is freed.
+ * Whoever ADVANCES a bound counter -- lnerf_adam_tick, LNERF_ADAM_TICK, LNERF_TAIL_TICK in either tail form -- computes
+ * the four values for the new step (the same device code every lane ran: the same bits) and stores them, then the tag.
+ * Whoever READS a bound counter -- lnerf_adam_step, lnerf_adam_step_multi(_shadow), lnerf_grid_encode_backward_adam(_tail),
+ * lnerf_step_tail -- reads the record with it and uses the values where tag == *step_dev; otherwise (a counter written
+ * from the host, a fresh record, a call with other betas than the binding's, no binding) it computes them as before.
+ * Nothing is ever read behind the counter's own words: an unbound int32[2] counter behaves as it always did. */
+#define LNERF_ADAM_CONSTANTS_BYTES 32
+int lnerf_adam_constants_bind(const int32_t *step_dev, float beta1, float beta2, void *consts);
+int lnerf_adam_constants_unbind(const int32_t *step_dev);
 int lnerf_cast_f32_to_bf16(const float *src, void *dst, int64_t n, lnerf_stream_t stream);
 
 /* ---- iso-surface extraction (marching cubes): NeRFRenderer.export_mesh's kernel (the upstream renderer runs

@@ -104,14 +104,14 @@ constexpr int TAIL_SHARDS = 8;                                     // arrival co
 // One slab block: `blk` = index of the block of 16 parameters, `lt` = thread inside the block (0..255), `part` = its
 // [TAIL_G][TAIL_P] floats of LDS.  `a`: the table's Adam arguments; `step_now` the device step counter when
 // a.step_dev is set (requested by the caller with ONE device-scope atomic load per wave -- the last block of the launch
-// to arrive rewrites it).  Every load that depends on nothing is requested first and together: the launch is a handful
-// of dependent round trips per block.  Contains block-wide barriers at named-barrier-free places: call it with all 256
+// to arrive rewrites it), `rec` the step's published bias corrections requested with it (adam_shared.h).  Every load
+// that depends on nothing is requested first and together: the launch is a handful of dependent round trips per block.  Contains block-wide barriers at named-barrier-free places: call it with all 256
 // threads of the block (the 1024-thread form synchronises the whole workgroup, see the caller).
 // BATCH: slab values a lane keeps in flight (32 = all of them: the stand-alone launch; 8 inside pass 2, whose 64
 // registers per lane must not spill -- the sum takes the slabs in the same order either way).
 template <int BATCH, typename SYNC>
 __device__ __forceinline__ void slab_block(int blk, int lt, const SlabAdam &sa, AdamArgs a, int32_t step_now,
-                                           float (*part)[TAIL_P], SYNC sync) {
+                                           const AdamConsts &rec, float (*part)[TAIL_P], SYNC sync) {
     static_assert(TAIL_SLABS_PER_LANE % BATCH == 0, "whole batches");
     const int pi = lt & (TAIL_P - 1), sg = lt / TAIL_P;
     const int p = blk * TAIL_P + pi;
@@ -141,7 +141,7 @@ __device__ __forceinline__ void slab_block(int blk, int lt, const SlabAdam &sa, 
     }
     if (a.step_dev) {
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // (the counter has been READ: see the arrival)
-        adam_bias_at(a, step_now);
+        adam_bias_from(a, step_now, rec);
     } else {
         adam_bias(a);
     }
@@ -173,7 +173,7 @@ __device__ __forceinline__ void slab_block(int blk, int lt, const SlabAdam &sa, 
 // returned), two levels: 8 shard counters (a line each: ~600 arrivals on ONE word queue for 7 us at the memory side), the
 // block that completes a shard arrives at the root, the block that completes the root is the last of the launch
 __device__ __forceinline__ void tail_arrive(int32_t *arrive, int total, int block, int32_t *tick, int32_t step_now,
-                                            unsigned int *gmax, int do_tick, int clear_gmax) {
+                                            const AdamArgs &a, unsigned int *gmax, int do_tick, int clear_gmax) {
     const int sh = block & (TAIL_SHARDS - 1);
     const int mine = (total - sh + TAIL_SHARDS - 1) / TAIL_SHARDS;   // blocks of this shard
     int32_t *cnt = arrive + (1 + sh) * CUR_STRIDE;
@@ -182,7 +182,10 @@ __device__ __forceinline__ void tail_arrive(int32_t *arrive, int total, int bloc
         const int shards = total < TAIL_SHARDS ? total : TAIL_SHARDS;
         if (__hip_atomic_fetch_add(arrive, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == shards - 1) {
             __hip_atomic_store(arrive, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (do_tick) __hip_atomic_store(&tick[0], step_now + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (do_tick) {
+                adam_consts_publish(a, step_now + 1);   // (the next step's bias corrections, for everyone who reads the counter)
+                __hip_atomic_store(&tick[0], step_now + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
             if (clear_gmax)
                 for (int l = 0; l < LNERF_MAX_LEVELS; ++l)
                     __hip_atomic_store(&gmax[l * CUR_STRIDE], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -223,6 +226,7 @@ template <int NW> __shared__ int s_red[NW];                 // the slice decisio
 template <int NW> __shared__ uint32_t s_bmp[NW][128];      // per wave: segment-start bitmap of a sub-batch (4096 records)
 template <int NW> __shared__ uint32_t s_soff[NW][64];      // per wave: (chunk slot - flat start) of its non-empty segments
 __shared__ uint32_t s_live[BK_ROWS >> 6];                  // the bucket's bytes of the moment map as they were before this step
+__shared__ AdamConsts s_consts;                            // the step's published bias corrections, parked across the record loop
 // The workspace as both passes and the step's tail see it (by value; built once per call on the host: scatter_ws)
 struct ScatterWs {
     unsigned int *gmax;                // level maxima, CUR_STRIDE words apart (raised by pass 1)
@@ -578,7 +582,7 @@ template <int RT> struct RowState {
 // One (level, bucket, slice) unit, the parts in order.  A return leaves through the kernel's end.
 template <int RT, typename REC, bool FUSE>
 __device__ __forceinline__ void reduce_bucket(const ReduceUnit &u, const GridMeta &meta, const BucketMeta &bm, const ScatterWs &ws,
-                                              const ReduceOut &out, int32_t step_now, bool have_step) {
+                                              const ReduceOut &out, int32_t step_now, const AdamConsts &rec, bool have_step) {
     constexpr int NW = RT / 64;
     const int l = u.l, nb = u.nb, tid = threadIdx.x, lane = tid & 63;
     // (uniform, and known to be: everything derived from it -- the wave's items, their chunk addresses -- stays in
@@ -639,6 +643,7 @@ __device__ __forceinline__ void reduce_bucket(const ReduceUnit &u, const GridMet
         if (lane < nmy) e_first = tab[(int64_t)(first + NW * lane) * nb];
         for (int i = tid; i < BK_ROWS * 2; i += RT) s_acc[i] = 0ll;
         if (FUSE && wave == 0) s_live[lane] = live_words;
+        if (FUSE && have_step && tid == 0) s_consts = rec;   // (parked: no vector register is held across the record loop)
         __syncthreads();
         step_now = __builtin_amdgcn_readfirstlane(step_now);   // (returned by now: into a scalar register for the loop)
         RED_STAMP(10);
@@ -650,12 +655,13 @@ __device__ __forceinline__ void reduce_bucket(const ReduceUnit &u, const GridMet
         RED_STAMP(12);
     } else {   // (FUSE: no records, but live groups whose moments decay)
         if (wave == 0) s_live[lane] = live_words;
+        if (have_step && tid == 0) s_consts = rec;
         __syncthreads();
         if (fin == FIN_ADAM_FAST) rs.prefetch(out.fu, tid);
     }
     if (!direct && !merge_slices<RT>(u, S, bm, ws, tid)) return;
     AdamArgs a = out.fu.a;   // (once, in front of the choice; have_step: the closing launch, see the kernel)
-    if (FUSE && have_step) adam_bias_at(a, __builtin_amdgcn_readfirstlane(step_now));
+    if (FUSE && have_step) adam_bias_from(a, __builtin_amdgcn_readfirstlane(step_now), s_consts);
     else if (FUSE) adam_bias(a);
     a.zero_grad = 0;
     switch (fin) {
@@ -683,13 +689,17 @@ k_scatter_reduce(GridMeta meta, BucketMeta bm, ScatterWs ws, ReduceOut out, int 
     // (requested here, consumed behind the workgroup's first barrier: no stall in front of the record stream)
     if (closing && out.fu.a.step_dev) step_now = __hip_atomic_load(out.fu.a.step_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const ReduceUnit u = reduce_unit<FUSE>((int)blockIdx.x, wg_lo, tj, meta.num_levels, bm);
+    // (with it the step's published bias corrections, where a record is bound to the counter: adam_shared.h.  By the
+    // waves that use them: every wave of a slab workgroup, the first wave of a bucket's, which parks them in LDS)
+    const bool rec_here = closing && out.fu.a.step_dev && (u.wg < 0 || __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) == 0);
+    const AdamConsts rec = adam_consts_request(rec_here ? out.fu.a.consts : nullptr);
     if (u.wg < 0) {
         // a SLAB workgroup of the closing launch: RT / 256 slab blocks, their 1 KiB of LDS each carved out of the tile
         const int sub = (int)threadIdx.x >> 8, lt = (int)threadIdx.x & 255;
         float (*part)[TAIL_P] = reinterpret_cast<float (*)[TAIL_P]>(s_acc) + sub * TAIL_G;
-        slab_block<8>((-1 - u.wg) * (RT / 256) + sub, lt, tj.sa, out.fu.a, step_now, part, [] { __syncthreads(); });
+        slab_block<8>((-1 - u.wg) * (RT / 256) + sub, lt, tj.sa, out.fu.a, step_now, rec, part, [] { __syncthreads(); });
     } else {
-        reduce_bucket<RT, REC, FUSE>(u, meta, bm, ws, out, step_now, closing && out.fu.a.step_dev != nullptr);
+        reduce_bucket<RT, REC, FUSE>(u, meta, bm, ws, out, step_now, rec, closing && out.fu.a.step_dev != nullptr);
     }
 #ifdef LNERF_STAMPS
     if (blockIdx.x < 4096) {   // (exit = the LAST wave's, with its stores acknowledged: the slot is free after that)
@@ -709,7 +719,7 @@ k_scatter_reduce(GridMeta meta, BucketMeta bm, ScatterWs ws, ReduceOut out, int 
         // (this wave is done.  The workgroup's other waves requested the counter as their first instruction and the
         // level maximum in front of the record loop; a workgroup's barriers wait for a wave's outstanding loads, and
         // a workgroup that leaves before its first barrier has not used either value)
-        tail_arrive(ws.arrive, (int)gridDim.x, (int)blockIdx.x, tj.tick, step_now, ws.gmax, tj.do_tick, tj.clear_gmax);
+        tail_arrive(ws.arrive, (int)gridDim.x, (int)blockIdx.x, tj.tick, step_now, out.fu.a, ws.gmax, tj.do_tick, tj.clear_gmax);
 }
 
 // the slab blocks + the closing arrival as a launch of their own (lnerf_step_tail)
@@ -718,12 +728,13 @@ k_step_tail(unsigned int *__restrict__ gmax, AdamArgs a, SlabAdam sa, int32_t *_
             int32_t *__restrict__ arrive, int do_tick, int clear_gmax) {
     int32_t step_now = 0;
     if (a.step_dev) step_now = __hip_atomic_load(a.step_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const AdamConsts rec = adam_consts_request(a.step_dev ? a.consts : nullptr);
     __shared__ float part[TAIL_G][TAIL_P];
-    if (sa.slabs) slab_block<TAIL_SLABS_PER_LANE>((int)blockIdx.x, (int)threadIdx.x, sa, a, step_now, part, [] { __syncthreads(); });
+    if (sa.slabs) slab_block<TAIL_SLABS_PER_LANE>((int)blockIdx.x, (int)threadIdx.x, sa, a, step_now, rec, part, [] { __syncthreads(); });
     else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     if (do_tick || clear_gmax) {
         __syncthreads();
-        if (threadIdx.x == 0) tail_arrive(arrive, (int)gridDim.x, (int)blockIdx.x, tick, step_now, gmax, do_tick, clear_gmax);
+        if (threadIdx.x == 0) tail_arrive(arrive, (int)gridDim.x, (int)blockIdx.x, tick, step_now, a, gmax, do_tick, clear_gmax);
     }
 }
 
@@ -753,10 +764,12 @@ static std::mutex g_maps_mutex;
 static std::unordered_map<const void *, BoundMap> g_maps;
 // with a bound map: leave groups with zero moments and zero gradient alone (0: the map is maintained, every group steps)
 int g_adam_skip = 1;
-// "adam_skip" switches between two forms of the SAME result; it is not one of the path-selecting keys below
+// "adam_skip" and "adam_consts" switch between two forms of the SAME result; they are not path-selecting keys
+// ("adam_consts": bound records of published bias corrections are used, lnerf_adam_constants_bind -- optim.hip)
 static bool set_form_switch(const char *key, int value) {
-    if (strcmp(key, "adam_skip") != 0) return false;
-    g_adam_skip = value ? 1 : 0;
+    if (strcmp(key, "adam_skip") == 0) g_adam_skip = value ? 1 : 0;
+    else if (strcmp(key, "adam_consts") == 0) g_adam_consts = value ? 1 : 0;
+    else return false;
     return true;
 }
 

@@ -25,6 +25,7 @@
 namespace lnerf {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 #define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
 
 // fragment slots in LDS (each slot: 64 lanes x 8 bf16 = 1 KiB)
@@ -104,15 +105,44 @@ static_assert((size_t)F_ALL * 1024 <= MLP_FRAG_BYTES, "fragment cache");
 __global__ void __launch_bounds__(256) k_mlp_build_fragments(MlpArgs a, __bf16 *out, int n_frag) {
     build_fragments(a, out, n_frag, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
 }
-__device__ __forceinline__ void fetch_fragments(const MlpArgs &a, __bf16 *frag, int n_frag, int tid, int nthreads) {
-    if (a.frag_global) {
-        const uint4 *src = reinterpret_cast<const uint4 *>(a.frag_global);
-        uint4 *dst = reinterpret_cast<uint4 *>(frag);
-        for (int e = tid; e < n_frag * 64; e += nthreads) dst[e] = src[e];
-    } else {
-        build_fragments(a, frag, n_frag, tid, nthreads);
+// The copy is cut in two, `request` (global -> registers) and `write` (registers -> LDS), so that a kernel can put the
+// requests of its first step's inputs BETWEEN them: vector loads return in issue order, the LDS writes wait for the
+// fragments only, and the inputs cross the fragments' round trip, the writes and the workgroup's barrier in flight.
+// Every lane loads N_FRAG * 64 / 256 rounded up times, the index clamped into the image (no branch around a load);
+// the write drops what lies past the end.
+template <int N_FRAG>
+struct FragmentCopy {
+    static constexpr int TOTAL = N_FRAG * 64, N = (TOTAL + 255) / 256;   // 16-byte words: of the image, per lane
+    u32x4 r[N];
+    __device__ __forceinline__ void request(const void *frag_global, int tid) {
+        const u32x4 *src = reinterpret_cast<const u32x4 *>(frag_global);
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const int e = tid + 256 * j;
+            r[j] = src[e < TOTAL ? e : TOTAL - 1];
+        }
     }
-}
+    __device__ __forceinline__ void write(__bf16 *frag, int tid) const {
+        u32x4 *dst = reinterpret_cast<u32x4 *>(frag);
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const int e = tid + 256 * j;
+            if (j < TOTAL / 256 || e < TOTAL) dst[e] = r[j];
+        }
+    }
+};
+// The biases of the hidden layers travel with the fragments: raw loads by every lane (index wrapped into the 64), the
+// first 64 threads write them to LDS.
+struct BiasCopy {
+    float b1, b2;
+    __device__ __forceinline__ void request(const MlpArgs &a, int tid) {
+        b1 = a.b1[tid & (MLP_HID - 1)];
+        b2 = a.b2[tid & (MLP_HID - 1)];
+    }
+    __device__ __forceinline__ void write(float *sB1, float *sB2, int tid) const {
+        if (tid < MLP_HID) { sB1[tid] = b1; sB2[tid] = b2; }
+    }
+};
 
 __device__ __forceinline__ bf16x8 ld_frag(const __bf16 *frag, int f, int lane) {
     return *reinterpret_cast<const bf16x8 *>(frag + (f * 64 + lane) * 8);
@@ -295,7 +325,6 @@ __device__ __forceinline__ void forward_hidden(const __bf16 *frag, const float *
 // that the wait of the NEXT step does not cover their acknowledgements too (a wave has one in-order counter for loads
 // and stores).  Without it the compiler waits where a value is first touched -- at the selects behind a load, at the
 // merge of two arms that load differently, at the first MFMA of the next step with vmcnt(0), i.e. for the stores.
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void pin_x(bf16x8 &a, bf16x8 &b) {
     u32x4 ua = __builtin_bit_cast(u32x4, a), ub = __builtin_bit_cast(u32x4, b);
     asm volatile("" : "+v"(ua), "+v"(ub));
@@ -311,13 +340,19 @@ __global__ void __launch_bounds__(256, WPS)
 k_mlp_forward_bf16(MlpArgs a, float *__restrict__ sigmas, float *__restrict__ rgbs) {
     __shared__ __attribute__((aligned(16))) __bf16 frag[F_FWD * 512];
     __shared__ float sB1[MLP_HID], sB2[MLP_HID], sB3[16];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, q = lane >> 4, c = lane & 15;
+    // The prologue is ONE exposed memory round trip, not two in series (nothing else is resident that could hide one: the
+    // persistent workgroups all start together).  The fragments and biases are requested first -- they need no M --, the
+    // first step's inputs behind them as soon as M is there, and only then are the fragments written to LDS.
+    FragmentCopy<F_FWD> fc;
+    BiasCopy bc;
+    const bool cached = __builtin_expect(a.frag_global != nullptr, 1);   // (a launch without the cache: the cold arm)
+    if (cached) fc.request(a.frag_global, tid);
+    bc.request(a, tid);
+    const float b3 = a.b3[c < a.out_dim ? c : a.out_dim - 1];   // (out_dim >= 2: the launcher checks)
+    __builtin_amdgcn_sched_barrier(0);
     int64_t M = a.m_host;
     if (a.m_dev) { const int64_t md = *a.m_dev; M = md < M ? md : M; }
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, q = lane >> 4, c = lane & 15;
-    fetch_fragments(a, frag, F_FWD, tid, 256);
-    if (tid < MLP_HID) { sB1[tid] = a.b1[tid]; sB2[tid] = a.b2[tid]; }
-    if (tid < 16) sB3[tid] = tid < a.out_dim ? a.b3[tid] : 0.f;
-    __syncthreads();
     const int nrgb = a.out_dim - 1;
     // The inputs of a step -- features and positions of this wave's two 16-sample tiles -- are requested one step ahead:
     // raw loads by EVERY lane (the four q lanes of a sample read the same position) of rows clamped into the valid
@@ -330,6 +365,12 @@ k_mlp_forward_bf16(MlpArgs a, float *__restrict__ sigmas, float *__restrict__ rg
         xB[t] = load_x<FB16>(a, mc, q);
         pos[t] = load_pos(a, mc);
     }
+    __builtin_amdgcn_sched_barrier(0);
+    if (cached) fc.write(frag, tid);
+    else build_fragments(a, frag, F_FWD, tid, 256);
+    bc.write(sB1, sB2, tid);
+    if (tid < 16) sB3[tid] = tid < a.out_dim ? b3 : 0.f;
+    __syncthreads();
     // (waited for HERE: a load still pending at the loop's entry makes the compiler wait at the top of every step)
     pin_x(xB[0], xB[1]);
     asm volatile("" : "+v"(pos[0].x), "+v"(pos[0].y), "+v"(pos[0].z), "+v"(pos[1].x), "+v"(pos[1].y), "+v"(pos[1].z));
@@ -652,18 +693,16 @@ k_mlp_backward_bf16(MlpArgs a, const float *__restrict__ sigmas, const float *__
     __shared__ __attribute__((aligned(16))) __bf16 imgA[STEP * RS];  // [sample][feature]: H2, then H1, then X
     __shared__ __attribute__((aligned(16))) __bf16 imgD[STEP * RS];  // [sample][feature]: dZ3, then dZ2, then dZ1
     __shared__ float sB1[MLP_HID], sB2[MLP_HID];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, q = lane >> 4, c = lane & 15;
+    // (the prologue of the forward: fragments and biases requested, then the first step's inputs, then the LDS writes)
+    FragmentCopy<F_ALL> fc;
+    BiasCopy bc;
+    const bool cached = __builtin_expect(a.frag_global != nullptr, 1);   // (a launch without the cache: the cold arm)
+    if (cached) fc.request(a.frag_global, tid);
+    bc.request(a, tid);
+    __builtin_amdgcn_sched_barrier(0);
     int64_t M = a.m_host;
     if (a.m_dev) { const int64_t md = *a.m_dev; M = md < M ? md : M; }
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, q = lane >> 4, c = lane & 15;
-    fetch_fragments(a, frag, F_ALL, tid, 256);
-    if (tid < MLP_HID) { sB1[tid] = a.b1[tid]; sB2[tid] = a.b2[tid]; }
-    __syncthreads();
-    bf16x8 ones;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ones[i] = (__bf16)1.0f;
-    WaveGrads g;
-    g.clear();
-
     // this wave's inputs of the first step; every later step's are requested one step ahead
     const int64_t wofs = 32 * w;
     Upstream<2, OUT5> up;
@@ -671,6 +710,16 @@ k_mlp_backward_bf16(MlpArgs a, const float *__restrict__ sigmas, const float *__
     bf16x8 xB[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) xB[t] = load_x<FB16>(a, clamp_row((int64_t)blockIdx.x * STEP + wofs + 16 * t + c, M), q);
+    __builtin_amdgcn_sched_barrier(0);
+    if (cached) fc.write(frag, tid);
+    else build_fragments(a, frag, F_ALL, tid, 256);
+    bc.write(sB1, sB2, tid);
+    __syncthreads();
+    bf16x8 ones;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) ones[i] = (__bf16)1.0f;
+    WaveGrads g;
+    g.clear();
     {   // (waited for HERE: a load still pending at the loop's entry makes the compiler wait at the top of every step)
         f32x4 none[2][2] = {};
         pin_step(xB, up, none);

@@ -3,6 +3,8 @@
 // and refreshes the bf16 shadow copy that the hash gather reads.  Pure HBM streaming: 16 B/lane.
 #include "common.h"
 #include "adam_shared.h"
+#include <mutex>
+#include <unordered_map>
 
 namespace lnerf {
 
@@ -93,13 +95,15 @@ struct AdamMulti {
 __global__ void __launch_bounds__(256) k_adam_multi(AdamMulti t, AdamArgs a, int32_t *tick) {
     if (tick) {
         const int32_t step_now = __hip_atomic_load(tick, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const AdamConsts rec = adam_consts_request(a.consts);   // (the step's bias corrections, if published: adam_shared.h)
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        adam_bias_at(a, step_now);
+        adam_bias_from(a, step_now, rec);
         __syncthreads();
         if (threadIdx.x == 0) {
             const int total = (int)(gridDim.x * gridDim.y);
             if (__hip_atomic_fetch_add(&tick[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == total - 1) {
                 __hip_atomic_store(&tick[1], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                adam_consts_publish(a, step_now + 1);
                 __hip_atomic_store(&tick[0], step_now + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
@@ -125,7 +129,12 @@ __global__ void __launch_bounds__(256) k_adam_multi(AdamMulti t, AdamArgs a, int
     }
 }
 
-__global__ void k_adam_tick(int32_t *step_dev) { *step_dev += 1; }
+// (a: betas and the bound record only -- the one thread that advances the counter publishes the new step's constants)
+__global__ void k_adam_tick(int32_t *step_dev, AdamArgs a) {
+    const int32_t next = *step_dev + 1;
+    adam_consts_publish(a, next);
+    *step_dev = next;
+}
 
 __global__ void __launch_bounds__(256) k_cast_bf16(const float *__restrict__ src, uint16_t *__restrict__ dst, int64_t n) {
     const int64_t n4 = n >> 2;
@@ -142,13 +151,55 @@ __global__ void __launch_bounds__(256) k_cast_bf16(const float *__restrict__ src
 
 }  // namespace lnerf
 
+// Records bound to a device step counter (lnerf_adam_constants_bind), by the counter's address, with the betas they are
+// computed for: a launch with other betas, or with the form switch off, neither reads nor fills the record -- the tag
+// then goes stale and every reader computes its own.
+namespace lnerf {
+struct BoundConsts { AdamConsts *rec; float beta1, beta2; };
+static std::mutex g_consts_mutex;
+static std::unordered_map<const void *, BoundConsts> g_consts;
+// "adam_consts" switches between two forms of the SAME result (lnerf_set_tuning): 1 = bound records are used
+int g_adam_consts = 1;
+AdamConsts *adam_consts_lookup(const int32_t *step_dev, float beta1, float beta2) {
+    if (!step_dev || !g_adam_consts) return nullptr;
+    std::lock_guard<std::mutex> lock(g_consts_mutex);
+    const auto it = g_consts.find(step_dev);
+    if (it == g_consts.end() || it->second.beta1 != beta1 || it->second.beta2 != beta2) return nullptr;
+    return it->second.rec;
+}
+}  // namespace lnerf
+
 using namespace lnerf;
 
 extern "C" {
 
+int lnerf_adam_constants_bind(const int32_t *step_dev, float beta1, float beta2, void *consts) {
+    LNERF_REQUIRE(step_dev && consts, "adam_constants_bind: null pointer");
+    LNERF_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "adam_constants_bind: betas must be in [0,1)");
+    LNERF_REQUIRE(((uintptr_t)consts & 15) == 0, "adam_constants_bind: the record must be 16-byte aligned");
+    std::lock_guard<std::mutex> lock(g_consts_mutex);
+    g_consts[step_dev] = {static_cast<AdamConsts *>(consts), beta1, beta2};
+    return LNERF_OK;
+}
+
+int lnerf_adam_constants_unbind(const int32_t *step_dev) {
+    LNERF_REQUIRE(step_dev, "adam_constants_unbind: null counter");
+    std::lock_guard<std::mutex> lock(g_consts_mutex);
+    g_consts.erase(step_dev);
+    return LNERF_OK;
+}
+
 int lnerf_adam_tick(int32_t *step_dev, lnerf_stream_t stream) {
     LNERF_REQUIRE(step_dev, "adam_tick: null counter");
-    hipLaunchKernelGGL(k_adam_tick, dim3(1), dim3(1), 0, as_stream(stream), step_dev);
+    AdamArgs a = {};
+    {   // the betas of the bound record, if any: the tick has none of its own
+        std::lock_guard<std::mutex> lock(g_consts_mutex);
+        const auto it = g_consts.find(step_dev);
+        if (it != g_consts.end() && g_adam_consts) {
+            a.beta1 = it->second.beta1; a.beta2 = it->second.beta2; a.consts = it->second.rec;
+        }
+    }
+    hipLaunchKernelGGL(k_adam_tick, dim3(1), dim3(1), 0, as_stream(stream), step_dev, a);
     LNERF_CHECK_LAUNCH("adam_tick");
     return LNERF_OK;
 }
@@ -172,6 +223,7 @@ int lnerf_adam_step(float *p, void *g, int grad_dtype, float *m, float *v, void 
     a.grad_scale = grad_scale;
     a.zero_grad = zero_grad;
     a.step_dev = step_dev;
+    a.consts = adam_consts_lookup(step_dev, beta1, beta2);
     int64_t blocks = div_up(div_up(n, 4), 256);
     if (blocks < 1) blocks = 1;
     if (blocks > 2048) blocks = 2048;
@@ -222,6 +274,7 @@ int lnerf_adam_step_multi_shadow(int count, float *const *p_host, float *const *
     a.grad_scale = grad_scale;
     a.zero_grad = zero_grad & 1;
     a.step_dev = step_dev;
+    a.consts = adam_consts_lookup(step_dev, beta1, beta2);
     const bool tick = (zero_grad & LNERF_ADAM_TICK) != 0;
     LNERF_REQUIRE(!tick || step_dev, "adam_step_multi: LNERF_ADAM_TICK needs the device step counter");
     int64_t bx = div_up(nmax, 256);

@@ -20,6 +20,7 @@ MLP_FRAGMENT_BYTES = 36 * 1024  # LNERF_MLP_FRAGMENT_BYTES: the bf16 weight-frag
 SCATTER_DEFER_FINISH = 0x200  # flag on the scatter's variant: accepted and ignored (pass 2 finishes the sliced buckets itself)
 MLP_DEFER_REDUCE = 0x200      # flag on lnerf_mlp_backward's precision tag: lnerf_step_tail sums the slabs
 TAIL_TICK, TAIL_CLEAR_SCATTER = 1, 2
+ADAM_CONSTANTS_BYTES = 32     # LNERF_ADAM_CONSTANTS_BYTES: the record of lnerf_adam_constants_bind
 GRID_BLOCKED = 0x400          # flag on the gather's / scatter's variant: blocked layout of the hashed levels
 GRID_TILED = 0x800            # ... the upstream's `tiled` layout (dense index wrapped instead of hashed)
 SCATTER_CLEARED = 0x100       # flag on the scatter's variant: the caller cleared the cursors (lnerf_grid_scatter_clear_bytes)
@@ -94,6 +95,8 @@ _SIGNATURES = {
     "lnerf_moment_map_bytes": [_I, _P],
     "lnerf_moment_map_build": [_P, _P, _I, _I, _P, _P, _Z, _P],
     "lnerf_moment_map_bind": [_P, _P, _Z],
+    "lnerf_adam_constants_bind": [_P, _F, _F, _P],
+    "lnerf_adam_constants_unbind": [_P],
     "lnerf_occ_sample_scratch_bytes": [_L],
     "lnerf_march_counter_len": [_L],
     "lnerf_occ_sample": [_P, _L, _I, _I, _F, _L, _U, _U, _P, _P, _P, _P],

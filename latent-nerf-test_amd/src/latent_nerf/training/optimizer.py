@@ -4,12 +4,20 @@ src/latent_paint/training/trainer.py:93-95: Adam(betas=(0.9, 0.99), eps=1e-15)).
 Two launches per step whatever the number of tensors: the hash table (16 B/lane streaming pass that also
 refreshes its bf16 shadow) and one multi-tensor launch for every small parameter."""
 import ctypes
+import weakref
 
 import torch
 
 from ..models import encoding as E
 from ..raymarching import backend as _b
 from ..raymarching.raymarching import _p, _stream
+
+
+def _unbind_adam_constants(step_dev_ptr):
+    try:
+        _b.get_lib().lnerf_adam_constants_unbind(ctypes.c_void_p(step_dev_ptr))
+    except Exception:   # (interpreter shutdown: the library may be gone)
+        pass
 
 
 class FusedAdam:
@@ -80,6 +88,13 @@ class FusedAdam:
         if capturable:
             dev = (self.big + self.small)[0][0].device
             self.step_dev = torch.tensor([1, 0], device=dev, dtype=torch.int32)  # [0]: value used by the NEXT step; [1]: arrival counter of the ticking launch
+            # the step's bias corrections as data (include/lnerf_hip.h, lnerf_adam_constants_bind): whichever launch
+            # advances the counter leaves them here for the next step's kernels.  All 0xFF = nothing published yet; a
+            # counter filled from the host (load_state_dict) simply does not match the tag, for one step.  Working
+            # state of the kernels, not optimiser state: not in state_dict().
+            self._adam_consts = torch.full((_b.ADAM_CONSTANTS_BYTES // 4,), -1, device=dev, dtype=torch.int32)
+            _b.call("lnerf_adam_constants_bind", _p(self.step_dev), float(betas[0]), float(betas[1]), _p(self._adam_consts))
+            weakref.finalize(self, _unbind_adam_constants, self.step_dev.data_ptr()).atexit = False
         if fuse_table_update:
             if encoder is None:
                 raise ValueError("fuse_table_update needs the encoder")

@@ -96,6 +96,13 @@ __device__ __forceinline__ uint32_t morton3d(uint32_t x, uint32_t y, uint32_t z)
     return expand_bits(x) | (expand_bits(y) << 1) | (expand_bits(z) << 2);
 }
 
+// the valid sample count of a launch: the host's bound, cut to the count on the device where the caller has one
+__device__ __forceinline__ int64_t valid_count(int64_t m_host, const int32_t *m_dev) {
+    int64_t M = m_host;
+    if (m_dev) { const int64_t md = *m_dev; M = md < M ? md : M; }
+    return M;
+}
+
 __device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
 
 // number of set bits of `mask` strictly below this lane (wave64)

@@ -243,8 +243,7 @@ __global__ void __launch_bounds__(256)
 k_grid_backward_atomic(const float *__restrict__ xyzs, float bound, const TG *__restrict__ dfeat, GridMeta meta,
                        int64_t m_host, const int32_t *__restrict__ m_dev, int64_t level_stride,
                        float *__restrict__ dtable, int variant) {
-    int64_t M = m_host;
-    if (m_dev) { const int64_t md = *m_dev; M = md < M ? md : M; }
+    const int64_t M = valid_count(m_host, m_dev);
     const TileMap tm = tile_map(variant, meta.num_levels);
     if (!tm.ok) return;
     const int l = tm.level;

@@ -11,6 +11,7 @@
 // -- no atomics, no partial buffer, the same bits on every call.  A wave reads 512 contiguous bytes of dfeat per level
 // and keeps the 8 vertex loads of the level in flight before it blends them, as the forward does.
 #include "grid_shared.h"
+#include "mlp_shared.h"
 
 namespace lnerf {
 
@@ -19,8 +20,7 @@ __global__ void __launch_bounds__(256)
 k_grid_backward_input(const float *__restrict__ xyzs, float bound, const TT *__restrict__ table, GridMeta meta,
                       int64_t m_host, const int32_t *__restrict__ m_dev, int64_t level_stride,
                       const float *__restrict__ dfeat, float *__restrict__ dxyz) {
-    int64_t M = m_host;
-    if (m_dev) { const int64_t md = *m_dev; M = md < M ? md : M; }
+    const int64_t M = valid_count(m_host, m_dev);
     const float two_b = 2.0f * bound;
     for (int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x; m < M; m += (int64_t)gridDim.x * 256) {
         const float x = xyzs[m * 3], y = xyzs[m * 3 + 1], z = xyzs[m * 3 + 2];
@@ -72,13 +72,11 @@ __global__ void __launch_bounds__(256)
 k_density_normals(const float *__restrict__ dxyz_enc, const float *__restrict__ xyzs, const float *__restrict__ sigmas,
                   float blob_scale, float blob_denom, int64_t m_host, const int32_t *__restrict__ m_dev,
                   float *__restrict__ grad_sigma, float *__restrict__ normals) {
-    int64_t M = m_host;
-    if (m_dev) { const int64_t md = *m_dev; M = md < M ? md : M; }
-    const float e15 = 3269017.3724721107f;  // exp(15): the trunc-exp clamp of the MLP backward
+    const int64_t M = valid_count(m_host, m_dev);
     for (int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x; m < M; m += (int64_t)gridDim.x * 256) {
         const float x = xyzs[m * 3], y = xyzs[m * 3 + 1], z = xyzs[m * 3 + 2];
         const float d2 = (x * x + y * y) + z * z;
-        const float e = fminf(sigmas[m], e15);
+        const float e = trunc_exp_grad(sigmas[m]);   // (the MLP backward's d sigma / d z)
         const float b = blob_scale * expf(-d2 / blob_denom);   // (= blob_of: the forward's value)
         const float eb = e * b;
         const float gx = fmaf(eb, -2.0f * x / blob_denom, dxyz_enc[m * 3]);

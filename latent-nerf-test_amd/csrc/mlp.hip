@@ -6,7 +6,22 @@
 // registers, feature on lanes) to the A layout (sample on lanes) through a per-wave LDS tile.
 //
 // MFMA 16x16x4 f32 lane maps (guide §3):  A[i = l&15][k = l>>4],  B[k = l>>4][j = l&15],
-// C/D[i = (l>>4)*4 + reg][j = l&15].
+// C/D[i = (l>>4)*4 + reg][j = l&15].  Every lane knows itself as (j, q) = (l & 15, l >> 4).
+//
+// Both kernels are a sequence of the parts below, in this order:
+//   load the weights (forward: registers, as B operands; backward: padded LDS images)
+//   per 64-sample tile, every wave on its 16 samples
+//     layer 1     bias_fill, dense over the features (feat_a; the backward parks x in the X tile), relu_store
+//     layer 2     bias_fill, dense over the layer-1 tile, relu_store
+//     forward:    layer 3 (dense into one 16-wide tile), exp and the blob on column 0, store
+//     backward:   upstream (dz3 in A layout, joins gb3)
+//                 dW3  dense, A = upstream, B = rows of A2
+//                 dA2  dense over W3;  mask_store by A2 (joins gb2)
+//                 dW2  outer
+//                 dA1  dense over W2;  mask_store by A1 (joins gb1)
+//                 dW1  outer
+//                 dX   dense over W1, stored level-major
+//   backward: fold_waves adds the four waves' accumulators into ONE slab per workgroup; k_mlp_reduce_slabs sums the slabs.
 #include "common.h"
 #include "mlp_shared.h"
 
@@ -23,12 +38,105 @@ __device__ __forceinline__ float load_feat(const MlpArgs &a, int level, int f, i
     return reinterpret_cast<const float *>(a.feat)[i];
 }
 
+// ------------------------------------------------------------------ the parts
+// a wave's C/D tiles start as the bias of their column (b[nt * stride]: registers with stride 1, LDS with 16), or as zero
+template <int NT>
+__device__ __forceinline__ void bias_fill(f32x4 (&t)[NT], const float *b, int stride) {
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) { const float v = b[nt * stride]; t[nt] = (f32x4){v, v, v, v}; }
+}
+template <int NT>
+__device__ __forceinline__ void zero_fill(f32x4 (&t)[NT]) {
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) t[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+}
+
+// acc[nt] += sum over k = 4 kk + q, kk ascending, of a(kk) * b(kk, nt): the one MFMA chain of this file
+template <int KK, int NT, class A, class B>
+__device__ __forceinline__ void dense(f32x4 (&acc)[NT], A a, B b) {
+#pragma unroll
+    for (int kk = 0; kk < KK; ++kk) {
+        const float x = a(kk);
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) acc[nt] = MFMA4(x, b(kk, nt), acc[nt]);
+    }
+}
+// its operands.  A from the level-major feature tensor: lane (s = j, k = 4kk + q) is level 2kk + (q >> 1), feature q & 1
+__device__ __forceinline__ float feat_a(const MlpArgs &a, int64_t M, int64_t m, int kk, int q) {
+    return m < M ? load_feat(a, 2 * kk + (q >> 1), q & 1, m) : 0.f;
+}
+// A[s][k] = T[s][k] of a wave's [sample][feature] LDS tile
+__device__ __forceinline__ auto a_tile(const float *T, int q, int j) {
+    return [=](int kk) { return T[j * LDH + 4 * kk + q]; };
+}
+// B[k][n] = T[n][k] (a weight matrix [out][in] applied forward) and B[k][n] = T[k][n] (applied backward, or the rows
+// of a [sample][feature] tile): T in LDS with leading dimension LD (a template argument: the backward sits at 252 of
+// 256 registers, and an index the compiler folds late is one it hoists out of the tile loop)
+template <int LD>
+__device__ __forceinline__ auto b_cols(const float *T, int q, int j) {
+    return [=](int kk, int nt) { return T[(nt * 16 + j) * LD + 4 * kk + q]; };
+}
+template <int LD>
+__device__ __forceinline__ auto b_rows(const float *T, int q, int j) {
+    return [=](int kk, int nt) { return T[(4 * kk + q) * LD + nt * 16 + j]; };
+}
+
+// ReLU of a wave's C/D tiles, kept in registers (the backward masks by them) and stored to the wave's LDS tile
+// T[sample][feature]: the C/D layout becomes the A layout of the next chain
+__device__ __forceinline__ void relu_store(float *T, f32x4 (&t)[4], int q, int j) {
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            t[nt][r] = fmaxf(t[nt][r], 0.f);
+            T[(q * 4 + r) * LDH + nt * 16 + j] = t[nt][r];
+        }
+}
+
+// dZ = dA where the activation was positive, stored as relu_store does; its column sums join gb (nt, then r; reduced
+// over lanes by fold_waves)
+__device__ __forceinline__ void mask_store(float *T, const f32x4 (&dA)[4], const f32x4 (&act)[4], float (&gb)[4], int q,
+                                           int j) {
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float d = act[nt][r] > 0.f ? dA[nt][r] : 0.f;
+            T[(q * 4 + r) * LDH + nt * 16 + j] = d;
+            gb[nt] += d;
+        }
+}
+
+// d loss / d z3 of (sample m, output k): sigma = trunc_exp(z3[0]) on column 0, the latents as they come; 0 outside
+__device__ __forceinline__ float upstream(const MlpArgs &a, int64_t M, const float *sigmas, const float *dsigmas,
+                                          const float *drgbs, int64_t m, int k) {
+    if (m >= M || k >= a.out_dim) return 0.f;
+    return k == 0 ? dsigmas[m] * trunc_exp_grad(sigmas[m]) : drgbs[m * (a.out_dim - 1) + (k - 1)];
+}
+
+// g[mt][nt] += sum_s dZ[s][mt*16 + i] * act[s][nt*16 + j] over the wave's 16 samples: both operands are rows of
+// [sample][feature] LDS tiles (dZ with leading dimension LDH, act with LD)
+template <int LD, int NT>
+__device__ __forceinline__ void outer(f32x4 (&g)[4][NT], const float *dZ, const float *act, int q, int j) {
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+        float av[4], bv[NT];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) av[t] = dZ[(4 * kk + q) * LDH + t * 16 + j];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) bv[t] = act[(4 * kk + q) * LD + t * 16 + j];
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) g[mt][nt] = MFMA4(av[mt], bv[nt], g[mt][nt]);
+    }
+}
+
 // ------------------------------------------------------------------ forward
 __global__ void __launch_bounds__(256)
 k_mlp_forward_f32(MlpArgs a, float *__restrict__ sigmas, float *__restrict__ rgbs) {
     __shared__ float sAct[4][16 * LDH];
-    int64_t M = a.m_host;
-    if (a.m_dev) { const int64_t md = *a.m_dev; M = md < M ? md : M; }
+    const int64_t M = valid_count(a.m_host, a.m_dev);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int j = lane & 15, q = lane >> 4;
     float *act = sAct[w];
@@ -52,53 +160,30 @@ k_mlp_forward_f32(MlpArgs a, float *__restrict__ sigmas, float *__restrict__ rgb
 
     for (int64_t tile = blockIdx.x; tile * 64 < M; tile += gridDim.x) {
         const int64_t m0 = tile * 64 + w * 16;
+        f32x4 acc[4], o[1];
         // ---- layer 1: A[s][k] straight from the level-major feature tensor
-        f32x4 acc[4];
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) acc[nt] = (f32x4){b1r[nt], b1r[nt], b1r[nt], b1r[nt]};
-        {
-            const int64_t m = m0 + j;
-            const bool in = m < M;
-#pragma unroll
-            for (int kk = 0; kk < 8; ++kk) {
-                const float x = in ? load_feat(a, 2 * kk + (q >> 1), q & 1, m) : 0.f;
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) acc[nt] = MFMA4(x, w1r[kk][nt], acc[nt]);
-            }
-        }
+        bias_fill(acc, b1r, 1);
+        dense<8>(acc, [&](int kk) { return feat_a(a, M, m0 + j, kk, q); }, [&](int kk, int nt) { return w1r[kk][nt]; });
         __syncthreads();  // previous tile's readers of `act` are done
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) act[(q * 4 + r) * LDH + nt * 16 + j] = fmaxf(acc[nt][r], 0.f);
+        relu_store(act, acc, q, j);
         __syncthreads();
         // ---- layer 2
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) acc[nt] = (f32x4){b2r[nt], b2r[nt], b2r[nt], b2r[nt]};
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk) {
-            const float x = act[j * LDH + 4 * kk + q];
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) acc[nt] = MFMA4(x, w2r[kk][nt], acc[nt]);
-        }
+        bias_fill(acc, b2r, 1);
+        dense<16>(acc, a_tile(act, q, j), [&](int kk, int nt) { return w2r[kk][nt]; });
         __syncthreads();
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) act[(q * 4 + r) * LDH + nt * 16 + j] = fmaxf(acc[nt][r], 0.f);
+        relu_store(act, acc, q, j);
         __syncthreads();
         // ---- layer 3 (one 16-wide output tile, columns >= out_dim are zero)
-        f32x4 o = (f32x4){b3r, b3r, b3r, b3r};
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk) o = MFMA4(act[j * LDH + 4 * kk + q], w3r[kk], o);
+        bias_fill(o, &b3r, 1);
+        dense<16>(o, a_tile(act, q, j), [&](int kk, int) { return w3r[kk]; });
         // ---- epilogue: lane holds h[s = q*4 + r][n = j]
         if (j < a.out_dim) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int64_t m = m0 + q * 4 + r;
                 if (m < M) {
-                    if (j == 0) sigmas[m] = expf(o[r] + blob_of(a, m));
-                    else rgbs[m * (a.out_dim - 1) + (j - 1)] = o[r];
+                    if (j == 0) sigmas[m] = expf(o[0][r] + blob_of(a, m));
+                    else rgbs[m * (a.out_dim - 1) + (j - 1)] = o[0][r];
                 }
             }
         }
@@ -110,204 +195,11 @@ constexpr int SL_W1 = MLP_SL_W1, SL_B1 = MLP_SL_B1, SL_W2 = MLP_SL_W2, SL_B2 = M
               SL_B3 = MLP_SL_B3, SLAB = MLP_SLAB;
 constexpr int BWD_MAX_BLOCKS = MLP_BWD_MAX_BLOCKS;
 
-__global__ void __launch_bounds__(256, 2)
-k_mlp_backward_f32(MlpArgs a, const float *__restrict__ sigmas, const float *__restrict__ dsigmas,
-                   const float *__restrict__ drgbs, float *__restrict__ dfeat, float *__restrict__ slabs) {
-    // one LDS block, carved by hand so that the per-wave activation tiles can be reused for the
-    // end-of-kernel reduction of the four waves' weight-gradient accumulators
-    constexpr int O_W1 = 0, O_W2 = O_W1 + HID * LDX, O_W3 = O_W2 + HID * LDH, O_B1 = O_W3 + OUTP * LDH,
-                  O_B2 = O_B1 + HID, O_X = O_B2 + HID, O_P = O_X + 4 * 16 * LDX, O_Q = O_P + 4 * 16 * LDH,
-                  O_END = O_Q + 4 * 16 * LDH;
-    static_assert(O_END - O_X >= SLAB, "activation tiles must hold one slab");
-    __shared__ float smem[O_END];
-    float *sW1 = smem + O_W1, *sW2 = smem + O_W2, *sW3 = smem + O_W3, *sB1 = smem + O_B1, *sB2 = smem + O_B2;
-    int64_t M = a.m_host;
-    if (a.m_dev) { const int64_t md = *a.m_dev; M = md < M ? md : M; }
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int j = lane & 15, q = lane >> 4;
-    const int nrgb = a.out_dim - 1;
-    for (int i = tid; i < HID * IN; i += 256) sW1[(i / IN) * LDX + (i % IN)] = a.w1[i];
-    for (int i = tid; i < HID * HID; i += 256) sW2[(i / HID) * LDH + (i % HID)] = a.w2[i];
-    for (int i = tid; i < OUTP * HID; i += 256)
-        sW3[(i / HID) * LDH + (i % HID)] = (i / HID) < a.out_dim ? a.w3[i] : 0.f;
-    if (tid < HID) { sB1[tid] = a.b1[tid]; sB2[tid] = a.b2[tid]; }
-    __syncthreads();
-    float *X = smem + O_X + w * 16 * LDX, *P = smem + O_P + w * 16 * LDH, *Q = smem + O_Q + w * 16 * LDH;
-    const float e15 = 3269017.3724721107f;  // exp(15)
-
-    f32x4 gW2[4][4], gW1[4][2], gW3[4];
-    float gb1[4] = {0.f, 0.f, 0.f, 0.f}, gb2[4] = {0.f, 0.f, 0.f, 0.f}, gb3[2] = {0.f, 0.f};
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) gW2[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        gW1[mt][0] = gW1[mt][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        gW3[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-
-    for (int64_t tile = blockIdx.x; tile * 64 < M; tile += gridDim.x) {
-        const int64_t m0 = tile * 64 + w * 16;
-        __syncthreads();  // previous tile's LDS readers are done
-        // ---- recompute layer 1; keep X in LDS ([s][k]) for dW1
-        f32x4 z[4], a1c[4], a2c[4];
-        {
-            const int64_t m = m0 + j;
-            const bool in = m < M;
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) { const float b = sB1[nt * 16 + j]; z[nt] = (f32x4){b, b, b, b}; }
-#pragma unroll
-            for (int kk = 0; kk < 8; ++kk) {
-                const float x = in ? load_feat(a, 2 * kk + (q >> 1), q & 1, m) : 0.f;
-                X[j * LDX + 4 * kk + q] = x;
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) z[nt] = MFMA4(x, sW1[(nt * 16 + j) * LDX + 4 * kk + q], z[nt]);
-            }
-        }
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                a1c[nt][r] = fmaxf(z[nt][r], 0.f);
-                P[(q * 4 + r) * LDH + nt * 16 + j] = a1c[nt][r];
-            }
-        __syncthreads();
-        // ---- recompute layer 2
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) { const float b = sB2[nt * 16 + j]; z[nt] = (f32x4){b, b, b, b}; }
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk) {
-            const float x = P[j * LDH + 4 * kk + q];
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) z[nt] = MFMA4(x, sW2[(nt * 16 + j) * LDH + 4 * kk + q], z[nt]);
-        }
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                a2c[nt][r] = fmaxf(z[nt][r], 0.f);
-                Q[(q * 4 + r) * LDH + nt * 16 + j] = a2c[nt][r];
-            }
-        __syncthreads();
-        // ---- dZ3 in A layout: lane (s = j, k = 4kk + q), kk = 0,1
-        float dz3[2];
-        {
-            const int64_t m = m0 + j;
-            const bool in = m < M;
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                const int k = 4 * kk + q;
-                float v = 0.f;
-                if (in && k < a.out_dim) {
-                    if (k == 0) v = dsigmas[m] * fminf(sigmas[m], e15);
-                    else v = drgbs[m * nrgb + (k - 1)];
-                }
-                dz3[kk] = v;
-                gb3[kk] += v;  // reduced over the 16 samples (lanes j) at the end
-            }
-        }
-        // ---- dW3[n3][h] += sum_s dZ3[s][n3] A2[s][h] : A[i = n3][k = s] from global, B = A2 rows
-        {
-            const int k = j;  // output row n3
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                const int64_t m = m0 + 4 * kk + q;
-                float v = 0.f;
-                if (m < M && k < a.out_dim) {
-                    if (k == 0) v = dsigmas[m] * fminf(sigmas[m], e15);
-                    else v = drgbs[m * nrgb + (k - 1)];
-                }
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) gW3[nt] = MFMA4(v, Q[(4 * kk + q) * LDH + nt * 16 + j], gW3[nt]);
-            }
-        }
-        // ---- dA2 = dZ3 W3 ; dZ2 = dA2 * (A2 > 0)
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) z[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) z[nt] = MFMA4(dz3[kk], sW3[(4 * kk + q) * LDH + nt * 16 + j], z[nt]);
-        __syncthreads();  // all reads of A2 from Q are done
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float d = a2c[nt][r] > 0.f ? z[nt][r] : 0.f;
-                Q[(q * 4 + r) * LDH + nt * 16 + j] = d;  // Q now holds dZ2 [s][o]
-                gb2[nt] += d;
-            }
-        __syncthreads();
-        // ---- dW2[o][i] += sum_s dZ2[s][o] A1[s][i]
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            float av[4], bv[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                av[t] = Q[(4 * kk + q) * LDH + t * 16 + j];
-                bv[t] = P[(4 * kk + q) * LDH + t * 16 + j];
-            }
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) gW2[mt][nt] = MFMA4(av[mt], bv[nt], gW2[mt][nt]);
-        }
-        // ---- dA1 = dZ2 W2 : A from Q (sample on lanes), B[k = o][n = i] = W2[o][i]
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) z[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk) {
-            const float x = Q[j * LDH + 4 * kk + q];
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) z[nt] = MFMA4(x, sW2[(4 * kk + q) * LDH + nt * 16 + j], z[nt]);
-        }
-        __syncthreads();  // all reads of A1 from P are done
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float d = a1c[nt][r] > 0.f ? z[nt][r] : 0.f;
-                P[(q * 4 + r) * LDH + nt * 16 + j] = d;  // P now holds dZ1 [s][o]
-                gb1[nt] += d;
-            }
-        __syncthreads();
-        // ---- dW1[o][i] += sum_s dZ1[s][o] X[s][i]
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            float av[4], bv[2];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) av[t] = P[(4 * kk + q) * LDH + t * 16 + j];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) bv[t] = X[(4 * kk + q) * LDX + t * 16 + j];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                gW1[mt][0] = MFMA4(av[mt], bv[0], gW1[mt][0]);
-                gW1[mt][1] = MFMA4(av[mt], bv[1], gW1[mt][1]);
-            }
-        }
-        // ---- dX = dZ1 W1 : B[k = o][n = i] = W1[o][i]
-        f32x4 dx[2];
-        dx[0] = dx[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk) {
-            const float x = P[j * LDH + 4 * kk + q];
-            dx[0] = MFMA4(x, sW1[(4 * kk + q) * LDX + j], dx[0]);
-            dx[1] = MFMA4(x, sW1[(4 * kk + q) * LDX + 16 + j], dx[1]);
-        }
-        // lane holds dX[s = q*4 + r][i = nt*16 + j] -> level-major dfeat
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            const int i = nt * 16 + j;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int64_t m = m0 + q * 4 + r;
-                if (m < M) dfeat[((int64_t)(i >> 1) * a.level_stride + m) * 2 + (i & 1)] = dx[nt][r];
-            }
-        }
-    }
-
-    // ---- the four waves add their accumulators into one LDS slab in wave order (deterministic),
-    //      then the workgroup writes ONE slab; k_mlp_reduce_slabs sums the slabs of all workgroups.
-    float *slab = smem + O_X;
+// the four waves add their accumulators into one LDS slab in wave order (deterministic); the workgroup then writes ONE
+// slab, and k_mlp_reduce_slabs sums the slabs of all workgroups
+__device__ __forceinline__ void fold_waves(float *slab, const f32x4 (&gW1)[4][2], const float (&gb1)[4],
+                                           const f32x4 (&gW2)[4][4], const float (&gb2)[4], const f32x4 (&gW3)[4],
+                                           const float (&gb3)[2], int tid, int w, int q, int j) {
     __syncthreads();
     for (int i = tid; i < SLAB; i += 256) slab[i] = 0.f;
     __syncthreads();
@@ -347,6 +239,94 @@ k_mlp_backward_f32(MlpArgs a, const float *__restrict__ sigmas, const float *__r
         }
         __syncthreads();
     }
+}
+
+__global__ void __launch_bounds__(256, 2)
+k_mlp_backward_f32(MlpArgs a, const float *__restrict__ sigmas, const float *__restrict__ dsigmas,
+                   const float *__restrict__ drgbs, float *__restrict__ dfeat, float *__restrict__ slabs) {
+    // one LDS block, carved by hand so that the per-wave activation tiles can be reused for the
+    // end-of-kernel reduction of the four waves' weight-gradient accumulators
+    constexpr int O_W1 = 0, O_W2 = O_W1 + HID * LDX, O_W3 = O_W2 + HID * LDH, O_B1 = O_W3 + OUTP * LDH,
+                  O_B2 = O_B1 + HID, O_X = O_B2 + HID, O_P = O_X + 4 * 16 * LDX, O_Q = O_P + 4 * 16 * LDH,
+                  O_END = O_Q + 4 * 16 * LDH;
+    static_assert(O_END - O_X >= SLAB, "activation tiles must hold one slab");
+    __shared__ float smem[O_END];
+    float *sW1 = smem + O_W1, *sW2 = smem + O_W2, *sW3 = smem + O_W3, *sB1 = smem + O_B1, *sB2 = smem + O_B2;
+    const int64_t M = valid_count(a.m_host, a.m_dev);
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int j = lane & 15, q = lane >> 4;
+    for (int i = tid; i < HID * IN; i += 256) sW1[(i / IN) * LDX + (i % IN)] = a.w1[i];
+    for (int i = tid; i < HID * HID; i += 256) sW2[(i / HID) * LDH + (i % HID)] = a.w2[i];
+    for (int i = tid; i < OUTP * HID; i += 256)
+        sW3[(i / HID) * LDH + (i % HID)] = (i / HID) < a.out_dim ? a.w3[i] : 0.f;
+    if (tid < HID) { sB1[tid] = a.b1[tid]; sB2[tid] = a.b2[tid]; }
+    __syncthreads();
+    float *X = smem + O_X + w * 16 * LDX, *P = smem + O_P + w * 16 * LDH, *Q = smem + O_Q + w * 16 * LDH;
+
+    f32x4 gW2[4][4], gW1[4][2], gW3[4];
+    float gb1[4] = {0.f, 0.f, 0.f, 0.f}, gb2[4] = {0.f, 0.f, 0.f, 0.f}, gb3[2] = {0.f, 0.f};
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) { zero_fill(gW2[mt]); zero_fill(gW1[mt]); gW3[mt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+
+    for (int64_t tile = blockIdx.x; tile * 64 < M; tile += gridDim.x) {
+        const int64_t m0 = tile * 64 + w * 16;
+        __syncthreads();  // previous tile's LDS readers are done
+        f32x4 z[4], a1c[4], a2c[4];
+        // ---- recompute layer 1; keep X in LDS ([s][k]) for dW1
+        bias_fill(a1c, sB1 + j, 16);
+        dense<8>(a1c, [&](int kk) { const float x = feat_a(a, M, m0 + j, kk, q); X[j * LDX + 4 * kk + q] = x; return x; },
+                 b_cols<LDX>(sW1, q, j));
+        relu_store(P, a1c, q, j);
+        __syncthreads();
+        // ---- recompute layer 2
+        bias_fill(a2c, sB2 + j, 16);
+        dense<16>(a2c, a_tile(P, q, j), b_cols<LDH>(sW2, q, j));
+        relu_store(Q, a2c, q, j);
+        __syncthreads();
+        // ---- dZ3 in A layout: lane (s = j, k = 4kk + q), kk = 0,1
+        float dz3[2];
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+            dz3[kk] = upstream(a, M, sigmas, dsigmas, drgbs, m0 + j, 4 * kk + q);
+            gb3[kk] += dz3[kk];  // reduced over the 16 samples (lanes j) at the end
+        }
+        // ---- dW3[n3][h] += sum_s dZ3[s][n3] A2[s][h] : A[i = n3][k = s] from global, B = A2 rows
+        dense<4>(gW3, [&](int kk) { return upstream(a, M, sigmas, dsigmas, drgbs, m0 + 4 * kk + q, j); },
+                 b_rows<LDH>(Q, q, j));
+        // ---- dA2 = dZ3 W3 ; dZ2 = dA2 * (A2 > 0)
+        zero_fill(z);
+        dense<2>(z, [&](int kk) { return dz3[kk]; }, b_rows<LDH>(sW3, q, j));
+        __syncthreads();  // all reads of A2 from Q are done
+        mask_store(Q, z, a2c, gb2, q, j);  // Q now holds dZ2 [s][o]
+        __syncthreads();
+        // ---- dW2[o][i] += sum_s dZ2[s][o] A1[s][i]
+        outer<LDH>(gW2, Q, P, q, j);
+        // ---- dA1 = dZ2 W2 : A from Q (sample on lanes), B[k = o][n = i] = W2[o][i]
+        zero_fill(z);
+        dense<16>(z, a_tile(Q, q, j), b_rows<LDH>(sW2, q, j));
+        __syncthreads();  // all reads of A1 from P are done
+        mask_store(P, z, a1c, gb1, q, j);  // P now holds dZ1 [s][o]
+        __syncthreads();
+        // ---- dW1[o][i] += sum_s dZ1[s][o] X[s][i]
+        outer<LDX>(gW1, P, X, q, j);
+        // ---- dX = dZ1 W1 : B[k = o][n = i] = W1[o][i]
+        f32x4 dx[2];
+        zero_fill(dx);
+        dense<16>(dx, a_tile(P, q, j), b_rows<LDX>(sW1, q, j));
+        // lane holds dX[s = q*4 + r][i = nt*16 + j] -> level-major dfeat
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) {
+            const int i = nt * 16 + j;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t m = m0 + q * 4 + r;
+                if (m < M) dfeat[((int64_t)(i >> 1) * a.level_stride + m) * 2 + (i & 1)] = dx[nt][r];
+            }
+        }
+    }
+
+    float *slab = smem + O_X;
+    fold_waves(slab, gW1, gb1, gW2, gb2, gW3, gb3, tid, w, q, j);
     float *gslab = slabs + (int64_t)blockIdx.x * SLAB;
     for (int i = tid; i < SLAB; i += 256) gslab[i] = slab[i];
 }
@@ -389,9 +369,18 @@ int g_mlp_fwd_wps = 3;   // wavefronts per SIMD the bf16 forward is compiled for
                          // register allocation is held at <= 168 so that they are co-resident) or 2
 int g_mlp_bwd_blocks = MLP_BWD_MAX_BLOCKS;  // persistent workgroups of the backward (<= MLP_BWD_MAX_BLOCKS slabs)
 
-static int mlp_common_checks(const char *who, const void *feat, int feat_dtype, int64_t level_stride, const float *xyzs,
-                             const float *w1, const float *b1, const float *w2, const float *b2, const float *w3,
-                             const float *b3, int out_dim, float blob_std, int64_t m_host, int precision) {
+// a flag bit riding on the precision tag: read it and take it off
+static bool take_flag(int &precision, int flag) {
+    const bool on = (precision & flag) != 0;
+    precision &= ~flag;
+    return on;
+}
+
+// the checks both entry points share, then the kernels' argument block (`precision` with its flag bits taken off)
+static int mlp_args(const char *who, const void *feat, int feat_dtype, int64_t level_stride, const float *xyzs,
+                    const float *w1, const float *b1, const float *w2, const float *b2, const float *w3, const float *b3,
+                    int out_dim, float blob_scale, float blob_std, int64_t m_host, const int32_t *m_dev, int precision,
+                    MlpArgs *a) {
     LNERF_REQUIRE(m_host >= 0 && level_stride >= m_host, "%s: need 0 <= m_host <= level_stride", who);
     // (the bf16 kernels address features and feature gradients with 32-bit byte offsets: 16 levels x level_stride x 8 B
     // must stay below 2^32; the exact-f32 kernels use 64-bit addressing and take any stride the scatter accepts)
@@ -403,6 +392,8 @@ static int mlp_common_checks(const char *who, const void *feat, int feat_dtype, 
     LNERF_REQUIRE(precision == LNERF_F32 || precision == LNERF_BF16, "%s: bad precision tag", who);
     LNERF_REQUIRE(blob_std > 0.f, "%s: blob_std must be > 0", who);
     if (m_host > 0) LNERF_REQUIRE(feat && xyzs && w1 && b1 && w2 && b2 && w3 && b3, "%s: null pointer", who);
+    *a = MlpArgs{feat, feat_dtype == LNERF_BF16, level_stride, xyzs, w1, b1, w2, b2, w3, b3, out_dim, blob_scale,
+                 2.0f * blob_std * blob_std, m_host, m_dev, nullptr};
     return LNERF_OK;
 }
 
@@ -424,17 +415,15 @@ int lnerf_mlp_forward(const void *feat, int feat_dtype, int64_t level_stride, co
                       float *rgbs, int precision, void *workspace, size_t workspace_bytes, lnerf_stream_t stream) {
     // (the caller keeps the fragments at the head of `workspace` current: the optimiser's fragment shadow, or an
     // earlier forward with the same weights)
-    const bool fragments_ready = (precision & LNERF_MLP_FRAGMENTS_READY) != 0;
-    precision &= ~LNERF_MLP_FRAGMENTS_READY;
-    int rc = mlp_common_checks("mlp_forward", feat, feat_dtype, level_stride, xyzs, w1, b1, w2, b2, w3, b3, out_dim,
-                               blob_std, m_host, precision);
+    const bool fragments_ready = take_flag(precision, LNERF_MLP_FRAGMENTS_READY);
+    MlpArgs a;
+    int rc = mlp_args("mlp_forward", feat, feat_dtype, level_stride, xyzs, w1, b1, w2, b2, w3, b3, out_dim, blob_scale,
+                      blob_std, m_host, m_dev, precision, &a);
     if (rc) return rc;
     if (m_host == 0) return LNERF_OK;
     LNERF_REQUIRE(sigmas && rgbs, "mlp_forward: null output");
     LNERF_REQUIRE(precision != LNERF_BF16 || out_dim != 5 || ((uintptr_t)rgbs & 15) == 0,
                   "mlp_forward: rgbs must be 16-byte aligned (one row per store)");
-    MlpArgs a{feat, feat_dtype == LNERF_BF16, level_stride, xyzs, w1, b1, w2, b2, w3, b3, out_dim, blob_scale,
-              2.0f * blob_std * blob_std, m_host, m_dev, nullptr};
     if (precision == LNERF_BF16) {
         // persistent workgroups walk ~M/128/blocks tiles each; with a workspace the weight fragments are built once per
         // launch (first MLP_FRAG_BYTES of it) instead of once per workgroup
@@ -481,13 +470,13 @@ int lnerf_mlp_backward(const void *feat, int feat_dtype, int64_t level_stride, c
                        const float *dsigmas, const float *drgbs, float *dfeat, float *dw1, float *db1, float *dw2,
                        float *db2, float *dw3, float *db3, int accumulate, void *workspace, size_t workspace_bytes,
                        int precision, void *clear_ptr, size_t clear_bytes, lnerf_stream_t stream) {
-    const bool fragments_ready = (precision & LNERF_MLP_FRAGMENTS_READY) != 0;
+    const bool fragments_ready = take_flag(precision, LNERF_MLP_FRAGMENTS_READY);
     // LNERF_MLP_DEFER_REDUCE: the per-workgroup gradient slabs stay in the workspace -- lnerf_step_tail sums them and
     // applies the Adam step (the d* outputs are not written and may be NULL)
-    const bool defer_reduce = (precision & LNERF_MLP_DEFER_REDUCE) != 0;
-    precision &= ~(LNERF_MLP_FRAGMENTS_READY | LNERF_MLP_DEFER_REDUCE);
-    int rc = mlp_common_checks("mlp_backward", feat, feat_dtype, level_stride, xyzs, w1, b1, w2, b2, w3, b3, out_dim,
-                               blob_std, m_host, precision);
+    const bool defer_reduce = take_flag(precision, LNERF_MLP_DEFER_REDUCE);
+    MlpArgs a;
+    int rc = mlp_args("mlp_backward", feat, feat_dtype, level_stride, xyzs, w1, b1, w2, b2, w3, b3, out_dim, blob_scale,
+                      blob_std, m_host, m_dev, precision, &a);
     if (rc) return rc;
     if (m_host == 0) return LNERF_OK;
     LNERF_REQUIRE(sigmas && dsigmas && drgbs && dfeat && (defer_reduce || (dw1 && db1 && dw2 && db2 && dw3 && db3)),
@@ -501,8 +490,6 @@ int lnerf_mlp_backward(const void *feat, int feat_dtype, int64_t level_stride, c
                   clear_bytes <= ((size_t)1 << 24), "mlp_backward: bad clear region");
     LNERF_REQUIRE(precision != LNERF_BF16 || out_dim != 5 || ((uintptr_t)drgbs & 15) == 0,
                   "mlp_backward: drgbs must be 16-byte aligned (one row per load)");
-    MlpArgs a{feat, feat_dtype == LNERF_BF16, level_stride, xyzs, w1, b1, w2, b2, w3, b3, out_dim, blob_scale,
-              2.0f * blob_std * blob_std, m_host, m_dev, nullptr};
     const int64_t blocks = lnerf_mlp_backward_slabs(m_host, precision);
     hipStream_t s = as_stream(stream);
     float *slabs = reinterpret_cast<float *>(static_cast<char *>(workspace) + MLP_FRAG_BYTES);

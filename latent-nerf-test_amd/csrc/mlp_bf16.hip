@@ -351,8 +351,7 @@ k_mlp_forward_bf16(MlpArgs a, float *__restrict__ sigmas, float *__restrict__ rg
     bc.request(a, tid);
     const float b3 = a.b3[c < a.out_dim ? c : a.out_dim - 1];   // (out_dim >= 2: the launcher checks)
     __builtin_amdgcn_sched_barrier(0);
-    int64_t M = a.m_host;
-    if (a.m_dev) { const int64_t md = *a.m_dev; M = md < M ? md : M; }
+    const int64_t M = valid_count(a.m_host, a.m_dev);
     const int nrgb = a.out_dim - 1;
     // The inputs of a step -- features and positions of this wave's two 16-sample tiles -- are requested one step ahead:
     // raw loads by EVERY lane (the four q lanes of a sample read the same position) of rows clamped into the valid
@@ -487,8 +486,7 @@ __device__ __forceinline__ void load_upstream(Upstream<T, false> &u, const MlpAr
 }
 // the B fragment of dZ3^T (slot (q, jj < 4) <-> output 4q + jj) of one column tile
 __device__ __forceinline__ void upstream_fragment(const float v[4], float sg, int q, bf16x8 &d3) {
-    const float e15 = 3269017.3724721107f;  // exp(15)
-    const float v0 = q == 0 ? v[0] * fminf(sg, e15) : v[0];
+    const float v0 = q == 0 ? v[0] * trunc_exp_grad(sg) : v[0];
     Pk8 d;
     d.u[0] = cvt_pk(v0, v[1]);
     d.u[1] = cvt_pk(v[2], v[3]);
@@ -701,8 +699,7 @@ k_mlp_backward_bf16(MlpArgs a, const float *__restrict__ sigmas, const float *__
     if (cached) fc.request(a.frag_global, tid);
     bc.request(a, tid);
     __builtin_amdgcn_sched_barrier(0);
-    int64_t M = a.m_host;
-    if (a.m_dev) { const int64_t md = *a.m_dev; M = md < M ? md : M; }
+    const int64_t M = valid_count(a.m_host, a.m_dev);
     // this wave's inputs of the first step; every later step's are requested one step ahead
     const int64_t wofs = 32 * w;
     Upstream<2, OUT5> up;

@@ -39,6 +39,10 @@ __device__ __forceinline__ float blob_at(const MlpArgs &a, const Pos3 &p) {
 }
 __device__ __forceinline__ float blob_of(const MlpArgs &a, int64_t m) { return blob_at(a, load_pos(a, m)); }
 
+// sigma = trunc_exp(z): exp forward, and backward d sigma / d z = exp(min(z, 15)) = min(sigma, exp(15))
+constexpr float TRUNC_EXP_MAX = 3269017.3724721107f;  // exp(15)
+__device__ __forceinline__ float trunc_exp_grad(float sigma) { return fminf(sigma, TRUNC_EXP_MAX); }
+
 // bf16 path launchers (mlp_bf16.hip)
 int launch_mlp_fragments_bf16(const MlpArgs &a, void *frag_out, bool backward_too, hipStream_t stream);
 int launch_mlp_fragment_maps(int out_dim, int32_t *m1, int32_t *m2, int32_t *m3, hipStream_t stream);

@@ -24,8 +24,7 @@ __global__ void __launch_bounds__(FD_BLOCK)
 k_fd_points(const float *__restrict__ xyzs, float bound, float eps, int64_t m_host, const int32_t *__restrict__ m_dev,
             float *__restrict__ pts7, int32_t *__restrict__ m7_dev) {
     __shared__ float stage[FD_BLOCK * FD_FLOATS];
-    int64_t M = m_host;
-    if (m_dev) { const int64_t md = *m_dev; M = md < M ? md : M; }
+    int64_t M = valid_count(m_host, m_dev);
     if (M < 0) M = 0;
     if (m7_dev && blockIdx.x == 0 && threadIdx.x == 0) m7_dev[0] = (int32_t)(FD_ROWS * M);
     for (int64_t base = (int64_t)blockIdx.x * FD_BLOCK; base < M; base += (int64_t)gridDim.x * FD_BLOCK) {   // block-uniform

@@ -72,6 +72,7 @@ class Buffers:
         self.drgbs = XM.padded(case["drgbs"], stride, stale).to(dev)
         self.W = [case[k].to(dev) for k in XM.W_NAMES]
         self.feat_tag = _B().F32 if feat_dtype == torch.float32 else _B().BF16
+        self.blob_scale = XM.BLOB_SCALE     # (tests/test_gpu_mlp_f32_bits.py runs with its own)
 
     def m_dev(self, value):
         return None if value is None else torch.tensor([value], dtype=torch.int32, device=self.dev)
@@ -79,7 +80,7 @@ class Buffers:
     def forward_args(self, m_host, m_dev, sigmas, rgbs, tag, ws, out_dim=None, stride=None, blob_std=XM.BLOB_STD,
                      rgbs_offset=0, ws_bytes=None):
         return (_p(self.feat), self.feat_tag, int(self.stride if stride is None else stride), _p(self.xyz),
-                *[_p(t) for t in self.W], int(self.out_dim if out_dim is None else out_dim), XM.BLOB_SCALE, blob_std,
+                *[_p(t) for t in self.W], int(self.out_dim if out_dim is None else out_dim), self.blob_scale, blob_std,
                 int(m_host), _p(m_dev), _p(sigmas), _p(rgbs, rgbs_offset), tag, _p(ws),
                 (0 if ws is None else ws.numel()) if ws_bytes is None else ws_bytes, _stream())
 
@@ -95,7 +96,7 @@ class Buffers:
     def backward_args(self, m_host, m_dev, dfeat, grads, accumulate, ws, tag, clear=None, clear_bytes=0, out_dim=None,
                       stride=None, blob_std=XM.BLOB_STD, drgbs_offset=0, ws_bytes=None):
         return (_p(self.feat), self.feat_tag, int(self.stride if stride is None else stride), _p(self.xyz),
-                *[_p(t) for t in self.W], int(self.out_dim if out_dim is None else out_dim), XM.BLOB_SCALE, blob_std,
+                *[_p(t) for t in self.W], int(self.out_dim if out_dim is None else out_dim), self.blob_scale, blob_std,
                 int(m_host), _p(m_dev), _p(self.sigmas), _p(self.dsigmas), _p(self.drgbs, drgbs_offset), _p(dfeat),
                 *[_p(g) for g in grads], int(accumulate), _p(ws), ws.numel() if ws_bytes is None else ws_bytes, tag,
                 _p(clear), clear_bytes, _stream())

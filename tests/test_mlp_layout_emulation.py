@@ -2,7 +2,8 @@
 
 The kernel body is replayed lane by lane with tests/emu/mfma_emulator.py for one 16-sample
 wave tile and compared with a plain numpy MLP forward/backward.  This does not execute any
-product code; it pins the layout reasoning the HIP kernel is written from."""
+product code; it pins the layout reasoning the HIP kernel is written from.  The comments name the
+parts of csrc/mlp.hip (its header lists them in this order) that each block replays."""
 import numpy as np
 
 from tests.emu.mfma_emulator import mfma_16x16x4_f32 as mfma
@@ -38,7 +39,7 @@ def test_forward_and_backward_tile_layout():
 
     lanes = np.arange(64)
     j, q = lanes & 15, lanes >> 4
-    # ---------------- forward, as k_mlp_forward_f32
+    # ---------------- forward, as k_mlp_forward_f32: layer 1 (bias_fill, dense over feat_a, relu_store)
     act = np.zeros(16 * LDH)
     acc = [np.repeat(b1[nt * 16 + j][:, None], 4, 1) for nt in range(4)]
     for kk in range(8):
@@ -50,6 +51,7 @@ def test_forward_and_backward_tile_layout():
         for r in range(4):
             act[(q * 4 + r) * LDH + nt * 16 + j] = a1c[nt][:, r]
     P = act.copy()
+    # layer 2: the chain's A operand is the tile just stored (a_tile), B the columns of W2
     acc = [np.repeat(b2[nt * 16 + j][:, None], 4, 1) for nt in range(4)]
     for kk in range(16):
         xa = act[j * LDH + 4 * kk + q]
@@ -60,6 +62,7 @@ def test_forward_and_backward_tile_layout():
         for r in range(4):
             act[(q * 4 + r) * LDH + nt * 16 + j] = a2c[nt][:, r]
     Q = act.copy()
+    # layer 3: one 16-wide tile, rows >= out_dim of W3 / b3 are zero
     W3p = np.zeros((OUTP, HID)); W3p[:out_dim] = W3
     b3p = np.zeros(OUTP); b3p[:out_dim] = b3
     o = np.repeat(b3p[j][:, None], 4, 1)
@@ -71,7 +74,7 @@ def test_forward_and_backward_tile_layout():
             h[q[l] * 4 + r, j[l]] = o[l, r]
     np.testing.assert_allclose(h[:, :out_dim], h_ref, rtol=1e-9, atol=1e-9)
 
-    # ---------------- backward, as k_mlp_backward_f32
+    # ---------------- backward, as k_mlp_backward_f32 (layers 1 and 2 recomputed as above; x parked in the X tile)
     X = np.zeros(16 * LDX)
     for kk in range(8):
         X[j * LDX + 4 * kk + q] = x[j, 4 * kk + q]
@@ -82,7 +85,7 @@ def test_forward_and_backward_tile_layout():
     for o_ in range(out_dim):
         sW3[o_ * LDH:o_ * LDH + HID] = W3[o_]
     z0 = lambda: np.zeros((64, 4))
-    # dz3 in A layout + db3
+    # upstream(m, k) in A layout (s = j, k = 4kk + q); it joins gb3
     dz3a = []
     gb3 = []
     for kk in range(2):
@@ -90,7 +93,7 @@ def test_forward_and_backward_tile_layout():
         v = np.where(k < out_dim, dz3[j, np.minimum(k, out_dim - 1)], 0.0)
         dz3a.append(v)
         gb3.append(v.copy())
-    # dW3
+    # dW3: dense with A = upstream(s = 4kk + q, k = j), B = rows of A2 (b_rows of Q)
     gW3 = [z0() for _ in range(4)]
     for kk in range(4):
         s = 4 * kk + q
@@ -104,7 +107,7 @@ def test_forward_and_backward_tile_layout():
                 dW3[q[l] * 4 + r, nt * 16 + j[l]] = gW3[nt][l, r]
     np.testing.assert_allclose(dW3[:out_dim], g["dW3"], rtol=1e-9, atol=1e-9)
     assert np.abs(dW3[out_dim:]).max() == 0
-    # dA2 / dZ2
+    # dA2: dense over W3 (b_rows); mask_store by A2 -> dZ2 in Q, column sums join gb2
     z = [z0() for _ in range(4)]
     for kk in range(2):
         for nt in range(4):
@@ -115,7 +118,7 @@ def test_forward_and_backward_tile_layout():
             d = np.where(a2c[nt][:, r] > 0, z[nt][:, r], 0.0)
             Q[(q * 4 + r) * LDH + nt * 16 + j] = d
             gb2[nt] += d
-    # dW2
+    # dW2: outer(dZ2 in Q, A1 in P)
     gW2 = [[z0() for _ in range(4)] for _ in range(4)]
     for kk in range(4):
         av = [Q[(4 * kk + q) * LDH + t * 16 + j] for t in range(4)]
@@ -130,7 +133,7 @@ def test_forward_and_backward_tile_layout():
                 for r in range(4):
                     dW2[mt * 16 + q[l] * 4 + r, nt * 16 + j[l]] = gW2[mt][nt][l, r]
     np.testing.assert_allclose(dW2, g["dW2"], rtol=1e-9, atol=1e-9)
-    # dA1 / dZ1
+    # dA1: dense over W2 (b_rows); mask_store by A1 -> dZ1 in P, column sums join gb1
     z = [z0() for _ in range(4)]
     for kk in range(16):
         xa = Q[j * LDH + 4 * kk + q]
@@ -142,7 +145,7 @@ def test_forward_and_backward_tile_layout():
             d = np.where(a1c[nt][:, r] > 0, z[nt][:, r], 0.0)
             P[(q * 4 + r) * LDH + nt * 16 + j] = d
             gb1[nt] += d
-    # dW1
+    # dW1: outer(dZ1 in P, X)
     gW1 = [[z0(), z0()] for _ in range(4)]
     for kk in range(4):
         av = [P[(4 * kk + q) * LDH + t * 16 + j] for t in range(4)]
@@ -157,7 +160,7 @@ def test_forward_and_backward_tile_layout():
                 for r in range(4):
                     dW1[mt * 16 + q[l] * 4 + r, nt * 16 + j[l]] = gW1[mt][nt][l, r]
     np.testing.assert_allclose(dW1, g["dW1"], rtol=1e-9, atol=1e-9)
-    # dX
+    # dX: dense over W1 (b_rows), two 16-wide tiles
     dx = [z0(), z0()]
     for kk in range(16):
         xa = P[j * LDH + 4 * kk + q]
@@ -169,7 +172,7 @@ def test_forward_and_backward_tile_layout():
             for r in range(4):
                 dX[q[l] * 4 + r, nt * 16 + j[l]] = dx[nt][l, r]
     np.testing.assert_allclose(dX, g["dx"], rtol=1e-9, atol=1e-9)
-    # biases: xor-shuffle reductions
+    # biases: the xor-shuffle reductions of fold_waves
     for nt in range(4):
         v1 = gb1[nt].reshape(4, 16).sum(0)
         v2 = gb2[nt].reshape(4, 16).sum(0)

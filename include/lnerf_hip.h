@@ -1357,6 +1357,76 @@ int lnerf_image_smooth_forward(const float *img, int B, int H, int W, int C, flo
 int lnerf_image_smooth_backward(const float *img, int B, int H, int W, int C, const float *d_loss, float *d_img,
                                 lnerf_stream_t stream);
 
+/* ---- Shaded Latent-Paint renders (`render.shading`; csrc/meshshade.hip): smooth vertex normals, and per pixel the
+ * interpolated normal, spherical-harmonic lighting and depth, each with its transpose.  Additive to ABI 7; every call
+ * above is unchanged.  The conventions of the vertex-gradient block hold: f32 throughout, every operation rounded on its
+ * own in the written order; every argument is checked before the first launch; no allocation, no synchronisation, no host
+ * read-back; pixel indices are 64-bit; a face_idx outside [0, F) is background and nothing is read through it;
+ * 1 <= B <= 65535, 1 <= H, W <= 32767, B * H * W < 2^31, 1 <= n_faces <= LNERF_MESH_MAX_FACES, 1 <= n_verts <= (2^31-1)/3.
+ * A dot product is a.b = (ax*bx + ay*by) + az*bz.  float64 restatement: tests/meshshade_reference.py.
+ *
+ * Vertex normals (world space, once per step for all B views).
+ *   Corner table: the caller supplies it, because topology is fixed in Latent-Paint.  corner_start [V+1] and corner_list
+ *   [3F] are int32; a corner id is c = 3f + k, ascending within a vertex; vertex i owns the entries corner_start[i] ..
+ *   corner_start[i+1] - 1 (both clamped into [0, 3F]).  The kernel skips an entry with c outside [0, 3F) or with
+ *   faces[c] != i.  A wrong table gives wrong normals but never an out-of-range access.
+ *   Face normal: c_f = (v1 - v0) x (v2 - v0), l = sqrt(c.c), n_f = c_f / l.  A face with l == 0, a non-finite l, or a
+ *   vertex id outside [0, V) contributes nothing.
+ *   Vertex normal: s_i = sum of n_f over the vertex's corners in table order, m = sqrt(s.s), vn_i = s_i / m if m >= 1e-6,
+ *   else vn_i = 0.  This is the normalised form; the fork keeps it commented out beside its mean of face normals (the
+ *   unnormalised mean shortens the normal where the surface bends and so darkens creases).
+ * lnerf_vertex_normals_forward: vnormals [V,3].  Gather form: one writer per vertex, identical bits on every run.
+ * lnerf_vertex_normals_backward: grad_vnormals [V,3] -> grad_verts [V,3], OVERWRITTEN.  The gradient passes through both
+ *   normalisations and the cross product; a zeroed vn_i or a skipped face passes nothing.  Also gather form over the
+ *   corner table, with no float atomics: pass 1 writes gs_i = (g_i - vn_i (vn_i.g_i)) / m per vertex into scratch
+ *   (0 where vn_i = 0); pass 2, per vertex j and per corner (f, k) of j in table order, takes dL/dn_f =
+ *   (gs_v0 + gs_v1) + gs_v2, gc = (dL/dn_f - n_f (n_f.dL/dn_f)) / l, ge1 = e2 x gc, ge2 = gc x e1 (e1 = v1 - v0,
+ *   e2 = v2 - v0) and adds -ge1 - ge2 (k = 0), ge1 (k = 1) or ge2 (k = 2).  One writer per vertex, identical bits on every
+ *   run; it is the forward's transpose for a table that lists every corner of every face once.  Scratch (16-byte aligned):
+ *   lnerf_vertex_normals_scratch_bytes(n_verts, n_faces), where 0 means arguments out of range.
+ *
+ * Pixel shading (one thread per pixel, 256-thread groups, no LDS).  face_idx [B*H*W], bary [B*H*W,3], face_z [B,F,3]
+ * are what lnerf_raster_prepare_batch / lnerf_rasterize_batch wrote; faces [F,3]; vnormals [V,3]; lights [B,9], a device
+ * array with one row per view.
+ * lnerf_raster_shade_forward: outputs normal [B*H*W,3], lighting [B*H*W], depth [B*H*W].  Any output pointer may be NULL
+ *   and is then skipped (all three NULL: refused).  On a foreground pixel with face f:
+ *     a = (b0*vn0 + b1*vn1) + b2*vn2, where vn_k = vnormals[faces[f][k]].  A vertex id out of range makes the pixel
+ *       background.
+ *     m = sqrt(a.a).  n = a/m if m >= 1e-6, else n = 0.
+ *     depth = -((b0*z0 + b1*z1) + b2*z2).  This is the antialias pass's d with the sign flipped, positive in front of the
+ *       camera.
+ *     lighting = min(max(sum_{k=0..8} lights[b,k]*Y_k(n), 1e-8), 1), summed for ascending k.
+ *   The basis, with n = (x, y, z):
+ *     Y0 = 0.28209479177387814          Y1 = -0.4886025119029199*y          Y2 = 0.4886025119029199*z
+ *     Y3 = -0.4886025119029199*x        Y4 = 1.0925484305920792*x*y         Y5 = -1.0925484305920792*y*z
+ *     Y6 = 0.94617469575755997*z*z - 0.31539156525251999                    Y7 = -1.0925484305920792*x*z
+ *     Y8 = 0.5462742152960396*(x*x - y*y)
+ *   (products from the left: c*x*y = (c*x)*y).  This is the nine-term real SH basis, in the order and signs of the library
+ *   the fork calls.  With the fork's default lights (1,0,1, 1,0,0, 0,0,0) it reduces to 0.2821 + 0.4886 (n_z - n_x).
+ *   Background pixels hold 0 in all three outputs.
+ * lnerf_raster_shade_backward: grad_normal, grad_lighting, grad_depth (each may be NULL: no gradient through that output;
+ *   all three NULL: refused), plus the forward's inputs.  Outputs: grad_bary [B*H*W,3], OVERWRITTEN, 0 on background;
+ *   grad_vnormals [V,3] and grad_face_z [B,F,3], ADDED INTO with float atomics, as in lnerf_raster_bary_backward (their
+ *   sums depend on the order, within rounding).  No gradient flows through lighting where the clamp is active (the sum
+ *   below 1e-8 or above 1), through n where m < 1e-6, or through face_idx; lights gets no gradient.  All terms are
+ *   recomputed from the inputs, so the forward saves nothing.  Per foreground pixel: gn = grad_normal + grad_lighting *
+ *   sum_k lights[b,k] dY_k/dn;  ga = (gn - n (n.gn)) / m;  grad_bary_k = ga.vn_k - grad_depth*z_k;
+ *   grad_vnormals[faces[f][k]] += ga*b_k;  grad_face_z[b,f,k] += -(grad_depth*b_k). */
+int lnerf_vertex_normals_forward(const float *verts, int n_verts, const int32_t *faces, int n_faces,
+                                 const int32_t *corner_start, const int32_t *corner_list, float *vnormals,
+                                 lnerf_stream_t stream);
+size_t lnerf_vertex_normals_scratch_bytes(int n_verts, int n_faces);
+int lnerf_vertex_normals_backward(const float *grad_vnormals, const float *verts, int n_verts, const int32_t *faces,
+                                  int n_faces, const int32_t *corner_start, const int32_t *corner_list, void *scratch,
+                                  size_t scratch_bytes, float *grad_verts, lnerf_stream_t stream);
+int lnerf_raster_shade_forward(const int32_t *face_idx, const float *bary, const float *face_z, const int32_t *faces,
+                               const float *vnormals, const float *lights, int B, int H, int W, int n_faces, int n_verts,
+                               float *normal, float *lighting, float *depth, lnerf_stream_t stream);
+int lnerf_raster_shade_backward(const float *grad_normal, const float *grad_lighting, const float *grad_depth,
+                                const int32_t *face_idx, const float *bary, const float *face_z, const int32_t *faces,
+                                const float *vnormals, const float *lights, int B, int H, int W, int n_faces, int n_verts,
+                                float *grad_bary, float *grad_vnormals, float *grad_face_z, lnerf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

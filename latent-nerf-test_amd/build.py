@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "liblnerf_hip.so")
-SOURCES = ["api.cc", "rays.hip", "occupancy.hip", "grid_gather.hip", "grid_input.hip", "grid_bin.hip", "grid.hip", "grid_tv.hip", "mlp.hip", "mlp_bf16.hip", "composite.hip", "optim.hip", "bg.hip", "mesh.hip", "raster.hip", "guidance.hip", "isosurface.hip", "uvbake.hip", "uvproject.hip", "viewblend.hip", "decimate.hip", "shade.hip", "atlas.hip", "meshclean.hip", "distortion.hip", "normal_image.hip", "texmip.hip", "rastergrad.hip"]
+SOURCES = ["api.cc", "rays.hip", "occupancy.hip", "grid_gather.hip", "grid_input.hip", "grid_bin.hip", "grid.hip", "grid_tv.hip", "mlp.hip", "mlp_bf16.hip", "composite.hip", "optim.hip", "bg.hip", "mesh.hip", "raster.hip", "guidance.hip", "isosurface.hip", "uvbake.hip", "uvproject.hip", "viewblend.hip", "decimate.hip", "shade.hip", "atlas.hip", "meshclean.hip", "distortion.hip", "normal_image.hip", "texmip.hip", "rastergrad.hip", "meshshade.hip"]
 DEPS = ["common.h", "span_walk.h", "mlp_shared.h", "adam_shared.h", "grid_shared.h", "mc_tables.h", "scan.h", "uv_shared.h", "mesh_shared.h", "tex_shared.h", "view_shared.h", "raster_shared.h", os.path.join("..", "..", "include", "lnerf_hip.h")]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 

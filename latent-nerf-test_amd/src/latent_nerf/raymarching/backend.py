@@ -194,6 +194,11 @@ _SIGNATURES = {
     "lnerf_normal_image_backward": [_P, _P, _P, _L, _F, _F, _F, _P, _P, _P, _P],
     "lnerf_image_smooth_forward": [_P, _I, _I, _I, _I, _P, _P],
     "lnerf_image_smooth_backward": [_P, _I, _I, _I, _I, _P, _P, _P],
+    "lnerf_vertex_normals_forward": [_P, _I, _P, _I, _P, _P, _P, _P],
+    "lnerf_vertex_normals_scratch_bytes": [_I, _I],
+    "lnerf_vertex_normals_backward": [_P, _P, _I, _P, _I, _P, _P, _P, _Z, _P, _P],
+    "lnerf_raster_shade_forward": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "lnerf_raster_shade_backward": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "lnerf_step_tail": [_I, _I, _P, _P, _P, _L, _I, _P, _Z, _P, _P, _P, _P, _P, _F, _P, _Z, _I, _I, _P, _P, _P, _F, _P,
                         _F, _F, _F, _I, _P, _F, _I, _P],
 }
@@ -217,6 +222,7 @@ _RESTYPES = {
     "lnerf_mesh_filter_scratch_bytes": _Z,
     "lnerf_mesh_smooth_scratch_bytes": _Z,
     "lnerf_mesh_umbrella_scratch_bytes": _Z,
+    "lnerf_vertex_normals_scratch_bytes": _Z,
 }
 
 _lib = None

@@ -17,6 +17,8 @@ UV_ATLASES = ("triangle", "charts")
 TEXTURE_FILLS = ("dilate", "pullpush")   # log.mesh_texture_fill (src/view_bake.py TEXTURE_FILLS)
 BAKE_UNSEEN = ("fallback", "inpaint")    # log.mesh_bake_unseen (src/view_bake.py BAKE_UNSEEN)
 BAKE_BLENDS = ("mean", "bands")          # log.mesh_bake_blend (src/view_bake.py BAKE_BLENDS)
+SHADINGS = ("albedo", "lambertian", "textureless")   # render.shading
+DEFAULT_LIGHTS = (1.0, 0.0, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0)   # render.lights (models/render.py DEFAULT_LIGHTS)
 
 RenderConfig = _cli.make_section("RenderConfig", (
     ("train_grid_size", int, 64, "side of the square training render, in latent pixels"),
@@ -27,6 +29,10 @@ RenderConfig = _cli.make_section("RenderConfig", (
     ("backbone", str, "texture-mesh", "'texture-mesh' (latent texture) or 'texture-rgb-mesh' (RGB fine-tuning)"),
     ("batch_size", int, 1, "views rendered and guided per optimisation step (their gradients are averaged)"),
     ("antialias", bool, False, "antialias the edges of every render: silhouettes become differentiable w.r.t. the vertices"),
+    ("shading", str, "albedo", " | ".join(SHADINGS) + " (lambertian: the training render times its SH lighting from smooth "
+                               "vertex normals; textureless: the lighting alone, RGB backbone only)"),
+    ("shading_ratio", float, 1.0, "shading other than albedo: the probability that a training step is shaded"),
+    ("lights", Tuple[float, ...], DEFAULT_LIGHTS, "shading: nine spherical-harmonic coefficients (l = 0, 1, 2) of the light"),
 ), doc="mesh renderer")
 
 GuideConfig = _cli.make_section("GuideConfig", (
@@ -84,6 +90,7 @@ LogConfig = _cli.make_section("LogConfig", (
                                      "their low-passed images plus the detail of the best view alone)"),
     ("mesh_bake_exposure", bool, False, "with mesh_bake_views: one gain per view and channel, solved from the overlaps"),
     ("mesh_bake_band_sigma", float, 0.0, "mesh_bake_blend bands: sigma of the low-pass in render pixels (0 = 1 pixel)"),
+    ("eval_maps", bool, False, "evaluation also writes *_normals.png, *_depth.png and *_shaded.png beside every *_rgb.png"),
     ("max_keep_ckpts", int, 2, "older checkpoints are deleted beyond this count"),
 ), namespace={"exp_dir": property(lambda self: Path(self.exp_root) / self.exp_name)}, doc="logging and saving")
 
@@ -152,6 +159,17 @@ class TrainConfig:
         if self.optim.disp_lr > 0 and not self.render.antialias:
             raise ValueError("optim.disp_lr > 0 needs render.antialias: without it a silhouette gives no gradient and "
                              "only the texture slides over the surface")
+        if self.render.shading not in SHADINGS:
+            raise ValueError("render.shading must be one of %s, not %r" % (" | ".join(SHADINGS), self.render.shading))
+        if not 0.0 <= self.render.shading_ratio <= 1.0:
+            raise ValueError("render.shading_ratio must be in [0, 1] (got %s)" % self.render.shading_ratio)
+        if self.render.shading == "textureless" and self.render.backbone != "texture-rgb-mesh":
+            raise ValueError("render.shading textureless needs render.backbone texture-rgb-mesh: a grey latent is not "
+                             "defined (the lighting would be written into all four latent channels)")
+        lights = self.render.lights
+        if (not isinstance(lights, (tuple, list)) or len(lights) != 9
+                or not all(isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v) for v in lights)):
+            raise ValueError("render.lights must be nine finite floats (got %r)" % (lights,))
         return self
 
 

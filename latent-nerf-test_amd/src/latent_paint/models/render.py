@@ -6,7 +6,9 @@ C-ABI raster kernels (csrc/raster.hip).  `render_views` / `render_views_texture`
 smaller than their texture; with `mip_coverage` its pyramid is the coverage-weighted one of the same file, which keeps the
 texels no face covers out of every level.  Also this project's own: `verts` that require grad receive the image's gradient
 (csrc/rastergrad.hip: the transposes of projection, barycentrics, interpolation and the bilinear lookup), and
-`antialias_views` makes silhouettes differentiable; with plain vertices every call is what it was."""
+`antialias_views` makes silhouettes differentiable; with plain vertices every call is what it was.  `shade_views`
+(csrc/meshshade.hip) adds what the fork's live trainer renders beside the image: smooth vertex normals interpolated per
+pixel, nine-term spherical-harmonic lighting and depth, differentiable w.r.t. the vertices like the image."""
 import math
 
 import torch
@@ -163,6 +165,102 @@ class _Antialias(torch.autograd.Function):
         return dimage, dxy, None, None, None, None
 
 
+# ---- shading (csrc/meshshade.hip): vertices -> smooth vertex normals -> per pixel normal, SH lighting and depth
+DEFAULT_LIGHTS = (1.0, 0.0, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0)   # the fork's nine SH coefficients: 0.2821 + 0.4886 (n_z - n_x)
+
+
+def check_lights(lights, what):
+    """Nine finite floats -> a tuple of them; anything else raises ValueError naming `what`."""
+    try:
+        vals = tuple(float(v) for v in lights)
+    except (TypeError, ValueError):
+        vals = ()
+    if len(vals) != 9 or not all(math.isfinite(v) for v in vals):
+        raise ValueError("%s must be nine finite floats, the SH coefficients of l = 0, 1, 2 (got %r)" % (what, lights))
+    return vals
+
+
+def corner_table(faces, n_verts):
+    """The corners of every vertex -> (corner_start [V+1], corner_list [3F]) int32 on faces' device, the table
+    lnerf_vertex_normals_* gather over: corner id c = 3 f + k, vertex i owns corner_list[corner_start[i]:corner_start[i+1]],
+    ascending (a stable sort of faces.flatten()).  Corners whose vertex id lies outside [0, n_verts) are in no list; the
+    tail of corner_list they leave is -1."""
+    flat = faces.reshape(-1).long()
+    valid = (flat >= 0) & (flat < n_verts)
+    order = torch.sort(flat, stable=True).indices
+    order = order[valid[order]]
+    start = torch.zeros(n_verts + 1, dtype=torch.int64, device=faces.device)
+    start[1:] = torch.cumsum(torch.bincount(flat[valid], minlength=n_verts), 0)
+    corners = torch.full((flat.numel(),), -1, dtype=torch.int32, device=faces.device)
+    corners[:order.numel()] = order.to(torch.int32)
+    return start.to(torch.int32).contiguous(), corners
+
+
+def vertex_normals(verts, faces32, corner_start, corner_list):
+    """lnerf_vertex_normals_forward -> [V,3]: unit sums of the unit normals of every vertex's faces (0 where they cancel)."""
+    vn = torch.empty_like(verts)
+    _b.call("lnerf_vertex_normals_forward", _chk(verts, "verts"), verts.shape[0], _chk(faces32, "faces", torch.int32),
+            faces32.shape[0], _chk(corner_start, "corner_start", torch.int32), _chk(corner_list, "corner_list", torch.int32),
+            _p(vn), _stream())
+    return vn
+
+
+def shade_pixels(vnormals, bary, face_z, face_idx, faces32, lights, B, H, W):
+    """lnerf_raster_shade_forward -> (normal [B*H*W,3], lighting [B*H*W], depth [B*H*W]), 0 on background."""
+    P, dev = B * H * W, vnormals.device
+    normal, lighting, depth = torch.empty(P, 3, device=dev), torch.empty(P, device=dev), torch.empty(P, device=dev)
+    _b.call("lnerf_raster_shade_forward", _chk(face_idx, "face_idx", torch.int32), _chk(bary, "bary"),
+            _chk(face_z, "face_z"), _chk(faces32, "faces", torch.int32), _chk(vnormals, "vnormals"), _chk(lights, "lights"),
+            B, H, W, faces32.shape[0], vnormals.shape[0], _p(normal), _p(lighting), _p(depth), _stream())
+    return normal, lighting, depth
+
+
+class _VertexNormals(torch.autograd.Function):
+    """lnerf_vertex_normals_forward / _backward over verts [V,3]."""
+
+    @staticmethod
+    def forward(ctx, verts, faces32, corner_start, corner_list):
+        ctx.save_for_backward(verts, faces32, corner_start, corner_list)
+        return vertex_normals(verts, faces32, corner_start, corner_list)
+
+    @staticmethod
+    def backward(ctx, dvn):
+        verts, faces32, corner_start, corner_list = ctx.saved_tensors
+        V, F = verts.shape[0], faces32.shape[0]
+        nbytes = _b.get_lib().lnerf_vertex_normals_scratch_bytes(V, F)
+        scratch = torch.empty(max(nbytes, 16), device=verts.device, dtype=torch.uint8)
+        dverts = torch.empty_like(verts)
+        _b.call("lnerf_vertex_normals_backward", _chk(dvn.contiguous(), "grad_vnormals"), _p(verts), V, _p(faces32), F,
+                _p(corner_start), _p(corner_list), _p(scratch), nbytes, _p(dverts), _stream())
+        return dverts, None, None, None
+
+
+class _ShadePixels(torch.autograd.Function):
+    """lnerf_raster_shade_forward / _backward over (vnormals, bary, face_z): grad_bary goes on to _RasterizeBatch,
+    grad_face_z to _PrepareBatch, grad_vnormals to _VertexNormals.  An output no loss uses hands the kernel a NULL."""
+
+    @staticmethod
+    def forward(ctx, vnormals, bary, face_z, face_idx, faces32, lights, B, H, W):
+        ctx.save_for_backward(vnormals, bary, face_z, face_idx, faces32, lights)
+        ctx.dims = (B, H, W)
+        ctx.set_materialize_grads(False)
+        return shade_pixels(vnormals, bary, face_z, face_idx, faces32, lights, B, H, W)
+
+    @staticmethod
+    def backward(ctx, dnormal, dlighting, ddepth):
+        vnormals, bary, face_z, face_idx, faces32, lights = ctx.saved_tensors
+        if dnormal is None and dlighting is None and ddepth is None:
+            return (None,) * 9
+        B, H, W = ctx.dims
+        grads = [None if g is None else g.contiguous() for g in (dnormal, dlighting, ddepth)]
+        dbary = torch.empty_like(bary)
+        dvn, dz = torch.zeros_like(vnormals), torch.zeros_like(face_z)
+        _b.call("lnerf_raster_shade_backward", *[_chk(g, "grad", allow_none=True) for g in grads], _p(face_idx), _p(bary),
+                _p(face_z), _p(faces32), _p(vnormals), _p(lights), B, H, W, faces32.shape[0], vnormals.shape[0],
+                _p(dbary), _p(dvn), _p(dz), _stream())
+        return (dvn, dbary, dz) + (None,) * 6
+
+
 class _Umbrella(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, faces32):
@@ -277,9 +375,11 @@ class _TextureMip(torch.autograd.Function):
 
 class Renderer:
     def __init__(self, device, dim=(224, 224), interpolation_mode="nearest", max_mip_level=-1, lod_bias=0.0,
-                 mip_coverage=False, coverage_ring=1, antialias=False):
+                 mip_coverage=False, coverage_ring=1, antialias=False, lights=DEFAULT_LIGHTS):
         assert interpolation_mode in ["nearest", "bilinear", "bicubic", "mipmap"], \
             "no interpolation mode %s" % interpolation_mode
+        self.lights = check_lights(lights, "Renderer: lights")   # shade_views: nine SH coefficients, every view's default
+        self._corners = {}                             # (faces, V) -> corner_table: the topology is fixed
         if not math.isfinite(lod_bias):
             raise ValueError("Renderer: lod_bias must be finite (got %r)" % (lod_bias,))
         if mip_coverage and interpolation_mode != "mipmap":
@@ -409,6 +509,49 @@ class Renderer:
         out = _Antialias.apply(image.float().permute(0, 2, 3, 1).contiguous(), st.face_xy, st.face_idx, st.bary.detach(),
                                st.face_z.detach(), faces32)
         return out.permute(0, 3, 1, 2)
+
+    def corner_table(self, faces, n_verts):
+        """corner_table of one mesh, computed once (keyed like coverage_weights: Latent-Paint never changes its faces)."""
+        key = (faces.data_ptr(), tuple(faces.shape), int(n_verts))
+        if key not in self._corners:
+            self._corners[key] = corner_table(faces.to(self.device), int(n_verts))
+        return self._corners[key]
+
+    def _lights(self, lights, B):
+        """None (self.lights), nine floats or [B,9] -> [B,9] f32 on the device, one row per view."""
+        if torch.is_tensor(lights) and lights.dim() == 2:
+            if tuple(lights.shape) != (B, 9) or not bool(torch.isfinite(lights).all()):
+                raise ValueError("shade_views: lights must be nine floats or a finite [%d,9] (got %s)"
+                                 % (B, tuple(lights.shape)))
+            return lights.detach().to(self.device).float().contiguous()
+        row = self.lights if lights is None else check_lights(lights, "shade_views: lights")
+        return torch.tensor([row] * B, dtype=torch.float32).to(self.device)
+
+    def shade_views(self, verts, faces, raster_state, lights=None):
+        """The shading of a rendered batch (csrc/meshshade.hip) -> (normal [B,3,H,W], lighting [B,1,H,W], depth [B,1,H,W]).
+        normal: the smooth vertex normals of the mesh (unit sums of unit face normals, world space) interpolated with the
+        pixel's barycentrics and normalised; lighting: nine-term SH under `lights` (nine floats or [B,9]; None:
+        self.lights), clamped to [1e-8, 1]; depth: the camera-space distance along the view axis, positive.  Background
+        pixels hold 0 in all three.  raster_state: the RasterState _rasterize_views_faces returned for these verts.
+        With `verts` that require grad all three are differentiable w.r.t. them: through the normals, and through the
+        barycentrics and depths of raster_state when that was rendered from the same `verts`.  Otherwise no graph is
+        recorded and the two forward kernels are all that is launched."""
+        st = RasterState(*raster_state)
+        verts = verts.to(self.device).float().contiguous()
+        faces32 = faces.to(self.device).to(torch.int32).contiguous()
+        corner_start, corner_list = self.corner_table(faces, verts.shape[0])
+        lights = self._lights(lights, st.B)
+        if _learns(verts):
+            vn = _VertexNormals.apply(verts, faces32, corner_start, corner_list)
+            normal, lighting, depth = _ShadePixels.apply(vn, st.bary, st.face_z, st.face_idx, faces32, lights,
+                                                         st.B, st.H, st.W)
+        else:
+            with torch.no_grad():
+                vn = vertex_normals(verts, faces32, corner_start, corner_list)
+                normal, lighting, depth = shade_pixels(vn, st.bary.detach(), st.face_z.detach(), st.face_idx, faces32,
+                                                       lights, st.B, st.H, st.W)
+        as_image = lambda t, c: t.reshape(st.B, st.H, st.W, c).permute(0, 3, 1, 2)
+        return as_image(normal, 3), as_image(lighting, 1), as_image(depth, 1)
 
     def render_single_view(self, mesh, face_attributes, elev=0, azim=0, radius=2, look_at_height=0.0):
         """face_attributes [1,F,3,D] -> (image [1,D,H,W], mask [1,1,H,W]); differentiable w.r.t. the attributes."""

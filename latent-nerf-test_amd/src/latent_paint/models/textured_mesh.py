@@ -21,7 +21,7 @@ from ... import view_bake
 from ...latent_nerf.raymarching.raymarching import bake_view_poses, pull_push_fill
 from ...uv_atlas import chart_atlas, check_atlas_choice, per_triangle_atlas
 from .mesh import Mesh
-from .render import Renderer, mesh_umbrella, texture_coverage
+from .render import DEFAULT_LIGHTS, Renderer, mesh_umbrella, texture_coverage
 
 # latent -> RGB linear estimate (rows = latent channels), the table of textured_mesh.py:34-40
 LATENT_RGB_ROWS = ((0.298, 0.207, 0.208), (0.187, 0.286, 0.173), (-0.158, 0.189, 0.264), (-0.184, -0.271, -0.473))
@@ -64,7 +64,17 @@ class TexturedMeshModel(nn.Module):
                                  lod_bias=getattr(opt.guide, "texture_lod_bias", 0.0),
                                  mip_coverage=getattr(opt.guide, "texture_mip_coverage", False),
                                  coverage_ring=getattr(opt.guide, "texture_coverage_ring", 1),
-                                 antialias=getattr(getattr(opt, "render", None), "antialias", False))
+                                 antialias=getattr(getattr(opt, "render", None), "antialias", False),
+                                 lights=getattr(getattr(opt, "render", None), "lights", DEFAULT_LIGHTS))
+        # shaded training renders (render.shading): the fork's `image * lighting` (src/latent_paint_mesh/training/
+        # trainer.py).  The draw of render.shading_ratio has a RandomState of its own, so the trainer's draws stay put.
+        self.shading = getattr(getattr(opt, "render", None), "shading", "albedo")
+        self.shading_ratio = float(getattr(getattr(opt, "render", None), "shading_ratio", 1.0))
+        if self.shading not in ("albedo", "lambertian", "textureless"):
+            raise ValueError("render.shading must be albedo, lambertian or textureless (got %r)" % (self.shading,))
+        if self.shading == "textureless" and latent_mode:
+            raise ValueError("render.shading textureless needs the RGB backbone: a grey latent is not defined")
+        self._shading_rng = np.random.RandomState(int(getattr(getattr(opt, "optim", None), "seed", 0)))
         self.env_sphere, self.mesh = self.init_meshes()
         self.background_sphere_colors, self.texture_img, self.texture_img_rgb_finetune = self.init_paint()
         # geometry learning (optim.disp_lr > 0): one offset per vertex, the fork's switched-off `displacement`
@@ -193,10 +203,10 @@ class TexturedMeshModel(nn.Module):
         as_floats = lambda a: [float(v) for v in a]
         return {"elev": as_floats(theta), "azim": as_floats(phi), "radius": as_floats(radius), "look_at_height": self.dy}
 
-    def render(self, theta, phi, radius, decode_func=None, test=False, dims=None):
+    def render(self, theta, phi, radius, decode_func=None, test=False, dims=None, maps=False):
         """theta, phi, radius: scalars (one view, [1,...] results) or sequences of length B ([B,...] results)."""
         if test:
-            return self.render_test(theta, phi, radius, decode_func, dims=dims)
+            return self.render_test(theta, phi, radius, decode_func, dims=dims, maps=maps)
         return self.render_train(theta, phi, radius)
 
     def render_train(self, theta, phi, radius):
@@ -206,7 +216,13 @@ class TexturedMeshModel(nn.Module):
         With render.antialias the composite and the coverage are edge-antialiased with the mesh's own raster state
         ('image' and 'mask' are then the antialiased ones); with optim.disp_lr > 0 the mesh is rendered at
         vertices + displacement, 'image' and 'mask' are differentiable w.r.t. the offsets (inside the faces through the
-        UVs, at silhouettes through the antialiasing) and 'geometry_loss' (geometry_loss(), a scalar) is added."""
+        UVs, at silhouettes through the antialiasing) and 'geometry_loss' (geometry_loss(), a scalar) is added.
+        With render.shading lambertian / textureless a step is shaded with probability render.shading_ratio: the
+        foreground is `foreground * lighting` on every channel, latent or RGB, as the fork trains (textureless: the
+        lighting alone on three channels, RGB backbone only); composite, antialiasing and resize follow as before, and
+        'normal' [B,3,h,w], 'lighting', 'depth' [B,1,h,w] (Renderer.shade_views, at the render's size) and 'shading' (the
+        mode) are added.  The lighting depends on the surface's orientation, so the offsets then receive the image's
+        gradient inside a face even under a constant texture."""
         if self.latent_mode:
             texture, sky_colors = self.texture_img, self.background_sphere_colors
         else:
@@ -217,6 +233,10 @@ class TexturedMeshModel(nn.Module):
             self.surface_vertices(), self.mesh.faces, self.face_attributes, texture, return_state=True, **view)
         background, _ = self.renderer.render_views(self.env_sphere, sky_colors, **view)
         coverage = coverage.detach()
+        maps = self._shading_maps(state) if self._shaded_step() else None
+        if maps is not None:   # lighting is 0 on background, as the foreground is
+            foreground = (foreground * maps["lighting"] if self.shading == "lambertian"
+                          else maps["lighting"].expand(-1, 3, -1, -1))
         image = background * (1 - coverage) + foreground * coverage
         if self.renderer.antialias:
             image, coverage = self._antialias(image, coverage, state)
@@ -224,13 +244,26 @@ class TexturedMeshModel(nn.Module):
         if self.latent_mode and coverage.shape[-1] != LATENT_SIDE:
             # the diffusion model takes LATENT_SIDE x LATENT_SIDE latents whatever the render size
             out = {k: F.interpolate(v, (LATENT_SIDE, LATENT_SIDE), mode="bicubic") for k, v in out.items()}
+        if maps is not None:   # (at the render's own size: a resampled normal is no unit vector)
+            out.update(maps, shading=self.shading)
         if self.learn_geometry:
             out["geometry_loss"] = self.geometry_loss()
         return out
 
-    def render_test(self, theta, phi, radius, decode_func=None, dims=None):
+    def _shaded_step(self):
+        """Whether this training step is shaded: never with render.shading albedo (and nothing is drawn then), else with
+        probability render.shading_ratio."""
+        return self.shading != "albedo" and float(self._shading_rng.uniform(0, 1)) < self.shading_ratio
+
+    def _shading_maps(self, state):
+        """{'normal' [B,3,H,W], 'lighting' [B,1,H,W], 'depth' [B,1,H,W]} of a rendered batch (Renderer.shade_views)."""
+        normal, lighting, depth = self.renderer.shade_views(self.surface_vertices(), self.mesh.faces, state)
+        return {"normal": normal, "lighting": lighting, "depth": depth}
+
+    def render_test(self, theta, phi, radius, decode_func=None, dims=None, maps=False):
         """Evaluation view: the latent texture is decoded to RGB first (`decode_func` = the guidance's
-        `decode_latents`), then rendered at `dims` on a white background; edge-antialiased with render.antialias."""
+        `decode_latents`), then rendered at `dims` on a white background; edge-antialiased with render.antialias.
+        maps: 'normal', 'lighting' and 'depth' of the same views (Renderer.shade_views, at `dims`) are added."""
         if self.latent_mode:
             if decode_func is None:
                 raise ValueError("decode function was not supplied to decode the latent texture image")
@@ -242,7 +275,10 @@ class TexturedMeshModel(nn.Module):
             return_state=True, **self._view(theta, phi, radius))
         if self.renderer.antialias:
             image, coverage = self._antialias(image, coverage, state)
-        return {"image": image, "texture_map": texture, "mask": coverage}
+        out = {"image": image, "texture_map": texture, "mask": coverage}
+        if maps:
+            out.update(self._shading_maps(state))
+        return out
 
     # ------------------------------------------------------------------ export
     @torch.no_grad()

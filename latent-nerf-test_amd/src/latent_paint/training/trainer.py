@@ -10,6 +10,7 @@ does, `pred_rgb.backward(gradient=grad)` (src/latent_paint_mesh/training/trainer
 
 Rendering, its backward and the Adam step run on the HIP library; this file is plumbing."""
 import json
+import math
 from pathlib import Path
 
 import numpy as np
@@ -155,12 +156,27 @@ class Trainer:
         return decode_with(self.diffusion, latents)
 
     @torch.no_grad()
-    def eval_render(self, data):
+    def eval_render(self, data, maps=False):
+        """-> (image [B,H,W,3], texture [1,R,R,3]) in [0, 1]; maps: + {'normals', 'depth', 'shaded'} [B,H,W,3] as written
+        by log.eval_maps: n * 0.5 + 0.5; the depth of each image mapped to [0, 1], near bright and background 0; the image
+        times its SH lighting (render.lights) on the mesh."""
         side = self.cfg.render.eval_grid_size
         out = self.mesh_model.render(theta=data["theta"], phi=data["phi"], radius=data["radius"],
-                                     decode_func=self._decode, test=True, dims=(side, side))
+                                     decode_func=self._decode, test=True, dims=(side, side), maps=maps)
         as_image = lambda t: t.permute(0, 2, 3, 1).contiguous().clamp(0, 1)
-        return as_image(out["image"]), as_image(out["texture_map"])
+        image, texture = as_image(out["image"]), as_image(out["texture_map"])
+        if not maps:
+            return image, texture
+        depth, lit = out["depth"], out["lighting"]
+        on_mesh = depth > 0
+        far = torch.where(on_mesh, depth, depth.new_full((), -math.inf)).amax(dim=(1, 2, 3), keepdim=True)
+        near = torch.where(on_mesh, depth, depth.new_full((), math.inf)).amin(dim=(1, 2, 3), keepdim=True)
+        span = torch.where(far > near, far - near, torch.ones_like(far))
+        shown = torch.where(on_mesh, torch.where(far > near, (far - depth) / span, torch.ones_like(depth)),
+                            torch.zeros_like(depth))
+        return image, texture, {"normals": as_image(out["normal"] * 0.5 + 0.5),
+                                "depth": as_image(shown.expand(-1, 3, -1, -1)),
+                                "shaded": image * as_image(torch.where(on_mesh, lit, torch.ones_like(lit)))}
 
     @torch.no_grad()
     def evaluate(self, dataloader, save_path: Path, save_as_video=False):
@@ -168,13 +184,16 @@ class Trainer:
         self.mesh_model.eval()
         save_path.mkdir(exist_ok=True, parents=True)
         frames, texture = [], None
+        with_maps = bool(getattr(self.cfg.log, "eval_maps", False)) and not save_as_video
         for i, data in enumerate(dataloader):
-            preds, textures = self.eval_render(data)
+            preds, textures, *extra = self.eval_render(data, maps=with_maps)
             frame, texture = tensor2numpy(preds[0]), textures
             if save_as_video:
                 frames.append(frame)
             else:
                 Image.fromarray(frame).save(save_path / ("step_%05d_%04d_rgb.png" % (self.train_step, i)))
+            for name, img in (extra[0].items() if extra else ()):   # log.eval_maps: beside the *_rgb.png
+                Image.fromarray(tensor2numpy(img[0])).save(save_path / ("step_%05d_%04d_%s.png" % (self.train_step, i, name)))
         if texture is not None:   # the texture map is the same for every view
             Image.fromarray(tensor2numpy(texture[0])).save(save_path / ("step_%05d_texture.png" % self.train_step))
         if save_as_video and frames:
